@@ -380,6 +380,25 @@ def rccl_witness(torch, dist, local_rank, world):
             "backend": dist.get_backend()}
 
 
+DUMP_BYTES = 64_000_000         # --dump-outputs: the files' size in all (64 MB, .npy headers included)
+DUMP_SEED = 0x5EED0D0
+
+
+def dump_outputs(dirname, streams):
+    """--dump-outputs: what the timed loop handed its caller in its last step, so that two builds can be compared output
+    for output.  `streams`: host uint16 codestreams in a fixed order.  Writes codestream_lengths.npy (float64, each
+    codestream's length in shorts) and codestreams.npy (float32, their words concatenated -- or, past DUMP_BYTES, the
+    words at a fixed sample of positions: DUMP_SEED's draw over the concatenation's length, in ascending order)."""
+    os.makedirs(dirname, exist_ok=True)
+    lengths = np.array([s.size for s in streams], np.float64)
+    words = np.concatenate(streams)
+    room = (DUMP_BYTES - 2 * 4096 - lengths.nbytes) // 4
+    if words.size > room:
+        words = words[np.sort(np.random.default_rng(DUMP_SEED).choice(words.size, room, replace=False))]
+    np.save(os.path.join(dirname, "codestream_lengths.npy"), lengths)
+    np.save(os.path.join(dirname, "codestreams.npy"), words.astype(np.float32))
+
+
 def cpu_baseline_leg(orc, frame_np, AW, AH, W, H, wl, lossy, qs, sample_rows, gpu_stream_u16, budget_s=8.0):
     """The oracle (C port, OpenMP over codeblocks / DWT rows + columns) on the box's host cores.  Same stage boundaries
     as the GPU step (level shift + DWT, BPC, pack) on preallocated, warmed buffers; file I/O and padding excluded.
@@ -609,6 +628,8 @@ def intra_main(args, rank, local_rank, world, witness):
     if not banded:
         stage = codec.profile_read(min(steps, 256)).mean(axis=0)
         codec.profile_begin(0)
+    if args.dump_outputs and rank == 0:             # the last step's frame: rank 0's splice, or the one-GPU codestream
+        dump_outputs(args.dump_outputs, [(last[0] if banded else out[:codec.last_total()]).cpu().numpy().view(np.uint16)])
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -791,9 +812,16 @@ def main():
     ap.add_argument("--dry", action="store_true",
                     help="the N-rank protocol only (launcher, rendezvous, per-step exchange, timing) on CPU tensors: no GPU, "
                          "no codec, no throughput -- what the CPU tests of the launcher run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's codestreams) to DIR/*.npy, "
+                         "at most 64 MB (dump_outputs): same arguments, same inputs, so two builds compare output for output")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 80 if args.workload.startswith("4k") else (400 if args.workload == "16k_intra" else 22)
+    if args.steps < 1 and not args.dry:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if args.dump_outputs and (args.dry or args.phase in ("iso", "lone")):
+        raise SystemExit("bench.py: --dump-outputs writes the timed loop's outputs: not with --dry or --phase iso / lone")
     if args.backend == "gloo" and not args.dry:
         raise SystemExit("bench.py: --backend gloo only with --dry (the codec has no CPU path)")
 
@@ -992,6 +1020,16 @@ def main():
     stage_ms = np.concatenate([c.profile_read(prof_cap) for c in codecs], axis=0) / batch   # per frame
     for c in codecs:
         c.profile_begin(0)
+    if args.dump_outputs and rank == 0:
+        # the last step's outputs that stay in place: every frame of each stream's last call, read before the checks
+        # below launch on these contexts (they overwrite a context's last totals)
+        got = []
+        for k in sorted(last_call):
+            f0, dst = last_call[k]
+            with torch.cuda.stream(streams[k]):
+                totals = [codecs[k].last_total()] if batch == 1 else codecs[k].last_totals(batch)
+                got += [dst[b, :tl].cpu().numpy().view(np.uint16) for b, tl in enumerate(totals)]
+        dump_outputs(args.dump_outputs, got)
     if phase == "pipelined":
         # ---- a traced run of the pipelined shape alone: the timed loop and nothing else (no output checks, no isolated
         # phases, no round trip -- each of those would add launches of another shape to the trace)

@@ -382,6 +382,41 @@ def test_bench_gpu_count_comes_from_sysfs_not_from_hip():
     assert b.dwt_required_bytes(P, 5, False, False) == b.dwt_bytes(P, 5, 1)
 
 
+def test_bench_dump_outputs_is_exact_within_budget_and_reproducible(tmp_path):
+    """bench.py --dump-outputs: lengths and words as float (exact), the whole concatenation when it fits, and past the
+    64 MB budget the same seeded sample of positions on every run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    small = [np.arange(65536, dtype=np.uint16), np.array([7, 65535], np.uint16)]
+    b.dump_outputs(str(tmp_path / "s"), small)
+    assert np.load(tmp_path / "s" / "codestream_lengths.npy").tolist() == [65536.0, 2.0]
+    words = np.load(tmp_path / "s" / "codestreams.npy")
+    assert words.dtype == np.float32 and np.array_equal(words, np.concatenate(small).astype(np.float64))
+    rng = np.random.default_rng(3)
+    big = [rng.integers(0, 65536, 10_000_000 + i, dtype=np.uint16) for i in range(2)]
+    for d in ("a", "c"):
+        b.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["codestream_lengths.npy", "codestreams.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64_000_000
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "c" / f))
+    sample = np.load(tmp_path / "a" / "codestreams.npy")
+    allw = np.concatenate(big)
+    idx = np.sort(np.random.default_rng(b.DUMP_SEED).choice(allw.size, sample.size, replace=False))
+    assert sample.size > 15_000_000 and np.array_equal(sample, allw[idx].astype(np.float32))
+
+
+def test_bench_refuses_a_dump_without_a_timed_loop():
+    for argv in (("--dry",), ("--phase", "lone")):
+        r = _run_bench("--gpus", "1", "--steps", "1", "--dump-outputs", "out", *argv)
+        assert r.returncode != 0 and "--dump-outputs" in r.stderr and not r.stdout.strip()
+    r = _run_bench("--gpus", "1", "--steps", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_bench_refuses_more_gpus_than_the_node_has():
     """No quiet world = 1 run: asking for more GPUs than the node has is an error (here: none visible, or one)."""
     if torch.cuda.device_count() >= 64:
