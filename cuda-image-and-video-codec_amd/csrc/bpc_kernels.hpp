@@ -23,6 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <type_traits>
 
 namespace picsong {
@@ -380,6 +381,47 @@ __device__ __forceinline__ PlaneLut plane_lut(const LutView &v, const LutGeo &g,
     pl.sign = lut_get<SINGLE>(v, gi + 0) | (lut_get<SINGLE>(v, gi + 1) << 8) | (lut_get<SINGLE>(v, gi + 2) << 16) | (lut_get<SINGLE>(v, gi + 3) << 24);
     pl.sig8x4 = pl.sig8 * 0x01010101u;
     return pl;
+}
+// Host side: may a context coding `wl` levels take this table array?  Returns nullptr, or why not (written into msg).
+// What the coders read is only equal to the oracle's po_lut_at (the index clamped into the whole array) where
+// - k = 0 and -cp 3: the array is one table -- the SINGLE clamp bounds an index by the LDS copy of table 0, not by the
+//   array, so an array of several tables would diverge past table 0's end;
+// - -k > 0 whole-table copies: the furthest index plane_lut forms -- the highest group find_subband can give, bit-plane
+//   15, the last entry of a section, for each of the three sections -- lies inside one table plus the kLutSlack entries
+//   bulk_setup copies behind it (lut_get<false> reads the LDS unbounded).  The groups are level * nSub + sb with sb
+//   0..2 for the detail levels 0 .. wl - 1 and sb = 0 for LL (level wl): the highest is max(wl * nSub, (wl - 1) * nSub
+//   + 2) -- the LL group for nSub >= 2, level wl - 1's HH group for nSub = 1.  With the shipped 9/4/1 contexts and nSub
+//   = 3: n_sign >= (wl * 3 * nBp + 16) * 4 - kLutSlack; sections sized for the context's wl pass for n_bitplanes >= 12.
+// Every -k > 0 table is held to the whole-table bound, as the host may take those instantiations for any frame.
+inline const char *lut_refusal(const LutGeo &g, int wl, bool bulk, bool cp3, int n_tables, char *msg, size_t cap)
+{
+    if (g.nBp < 1 || g.nSub < 1 || g.nRef < 1 || g.nSig < 1 || g.nSign < 1) {
+        snprintf(msg, cap, "LUT geometry n_bitplanes %d, n_subbands %d, n_ref / n_sig / n_sign %d / %d / %d: every one must "
+                 "be positive", g.nBp, g.nSub, g.nRef, g.nSig, g.nSign);
+        return msg;
+    }
+    if (!bulk || cp3) {
+        if (n_tables > 1) {
+            snprintf(msg, cap, "LUT of %d bit-plane tables on a %s context: it codes with one table (the -k > 0 layout "
+                     "belongs to a context with k > 0)", n_tables, cp3 ? "-cp 3" : "k = 0");
+            return msg;
+        }
+        return nullptr;
+    }
+    const long grp_ll = (long)wl * g.nSub, grp_hh = (long)(wl - 1) * g.nSub + 2;
+    const long top = (grp_ll > grp_hh ? grp_ll : grp_hh) * g.nBp + kMaxPlanes;   // planes up to bit-plane 15 of the top group, + 1
+    const long one = (long)g.nRef + g.nSig + g.nSign;
+    long reach = top * g.cRef;                                   // one past the furthest index of each section
+    if ((long)g.nRef + top * g.cSig > reach) reach = (long)g.nRef + top * g.cSig;
+    if ((long)g.nRef + g.nSig + top * g.cSign > reach) reach = (long)g.nRef + g.nSig + top * g.cSign;
+    if (reach - one > kLutSlack) {
+        snprintf(msg, cap, "LUT geometry n_bitplanes %d, n_subbands %d, n_ref / n_sig / n_sign %d / %d / %d at wl %d: the "
+                 "-k > 0 coders read %ld entries past one table of %ld, the copy they keep holds %d (sections sized for "
+                 "wl %d with n_bitplanes >= 12 fit)", g.nBp, g.nSub, g.nRef, g.nSig, g.nSign, wl, reach - one, one,
+                 kLutSlack, wl);
+        return msg;
+    }
+    return nullptr;
 }
 // k = 0: every codeblock of the workgroup uses table 0; every thread copies its share of it
 __device__ __forceinline__ void lut_to_lds(const int32_t *lut, int total, uint8_t *lds)
@@ -1936,7 +1978,9 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcDecWgWaves, !BULK ? PICSONG_BP
 void bpc_decode_kernel(BpcArgs a)
 {
     static_assert(NP == kDecSmallPlanes, "one instantiation for every plane count (the planes are parked in the scratch)");
-    static_assert(!C16 || S16, "the 16-bit coefficient form belongs to the frame paths");
+    // the int16 form stores a raw codeblock's (word & 0xFFFFFF) >> 1: only the packed stream's uint16 words (S16) keep
+    // that within 0x7FFF; a staging word may carry more bits
+    static_assert(!C16 || S16, "the 16-bit coefficient form belongs to the frame paths (it reads the packed stream's shorts)");
     static_assert(BULK || !COMPACT, "compact table copies belong to the -k > 0 instantiations");
     constexpr int kTab = COMPACT ? kBulkCompactBytes : kLutLdsMax;       // bytes of one LDS table copy
     __shared__ uint8_t lds_lut[(BULK ? 2 : 1) * kTab];

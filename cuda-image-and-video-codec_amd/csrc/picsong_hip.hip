@@ -469,6 +469,18 @@ void picsong_ctx_destroy(picsong_ctx *c)
     delete c;
 }
 
+// the geometry checks both setters share (lut_refusal, bpc_kernels.hpp): run before the context's table is replaced
+static int lut_admit(const picsong_ctx *c, const picsong_lut_info &li, int n_tables)
+{
+    LutGeo g;
+    g.nBp = li.n_bitplanes; g.nSub = li.n_subbands; g.cRef = li.ctx_ref; g.cSign = li.ctx_sign; g.cSig = li.ctx_sig;
+    g.prec = li.precision; g.nRef = li.n_ref; g.nSig = li.n_sig; g.nSign = li.n_sign;
+    char msg[320];
+    if (lut_refusal(g, c->p.wl, c->p.k > 0.0f, c->p.cp == 3, n_tables, msg, sizeof msg))
+        return fail(PICSONG_ERR_ARG, "%s", msg);
+    return PICSONG_OK;
+}
+
 int picsong_ctx_set_lut_component(picsong_ctx *c, int comp, const picsong_lut_info *info, const int32_t *host_table)
 {
     if (!c || !info || !host_table) return fail(PICSONG_ERR_ARG, "set_lut: null argument");
@@ -491,6 +503,7 @@ int picsong_ctx_set_lut_component(picsong_ctx *c, int comp, const picsong_lut_in
     for (size_t i = 0; i < total; i++)
         if (host_table[i] < 0 || host_table[i] > 255)
             return fail(PICSONG_ERR_ARG, "LUT entry %zu = %d outside 0..255", i, host_table[i]);
+    if (int rc = lut_admit(c, *info, n_tables)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (c->d_lut[comp] && !c->lut_borrowed[comp]) (void)hipFree(c->d_lut[comp]);
     c->d_lut[comp] = nullptr;
@@ -531,6 +544,7 @@ int picsong_ctx_set_lut_device(picsong_ctx *c, int comp, const picsong_lut_info 
         return fail(PICSONG_ERR_ARG, "LUT table of %zu entries exceeds the %d the coder kernels hold in LDS", one,
                     (cp3 ? kLutLdsMax3 : kLutLdsMax) - kLutSlack);
     if (li.n_tables <= 0) li.n_tables = 1;
+    if (int rc = lut_admit(c, li, li.n_tables)) return rc;
     if (c->d_lut[comp] && !c->lut_borrowed[comp]) (void)hipFree(c->d_lut[comp]);
     c->d_lut[comp] = const_cast<int32_t *>(d_table);
     c->lut_borrowed[comp] = true;

@@ -115,7 +115,12 @@ int  picsong_ctx_padded_dims(const picsong_ctx *ctx, int *aw, int *ah, int *n_co
  * plane count instead, which serves a lone frame and costs frames in flight nothing.  Default: off. */
 int  picsong_ctx_set_pipelined(picsong_ctx *ctx, int on);
 /* RGB: component c (0,1,2) uses its own table, files {ref,sig,sign}{R,G,B}.txt_0
- * (Engine::initLUT Engines/Engine.cu:124-136: _LUTInformation[i]); picsong_ctx_set_lut == component 0 */
+ * (Engine::initLUT Engines/Engine.cu:124-136: _LUTInformation[i]); picsong_ctx_set_lut == component 0.
+ * Both setters refuse (PICSONG_ERR_ARG, the context keeps the table it held) a table whose geometry the coders cannot
+ * read as the whole array clamps it: several tables (n_tables > 1) on a k = 0 or -cp 3 context, which codes with one;
+ * and on a -k > 0 context, sections that leave the furthest index the coders form -- bit-plane 15 of the highest
+ * subband group, max(wl * n_subbands, (wl - 1) * n_subbands + 2) -- more than 16 entries past one table (with three
+ * subbands and sections sized for the context's wl: n_bitplanes < 12). */
 int  picsong_ctx_set_lut_component(picsong_ctx *ctx, int component, const picsong_lut_info *info,
                                    const int32_t *host_table);
 

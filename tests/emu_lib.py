@@ -58,6 +58,16 @@ def _geo(lut):
                      g["precision"], g["n_ref"], g["n_sig"], g["n_sign"]], np.int32)
 
 
+def lut_refusal(lut, wl, k=0.0):
+    """What the context setters say about `lut` on a context of `wl` levels and factor k (the shared lut_refusal of the
+    product): None when a context takes it, else the setter's message."""
+    msg = C.create_string_buffer(512)
+    cp = getattr(lut, "cp", 2)
+    if lib().emu_lut_refusal(_p(_geo(lut)), wl, C.c_float(k), cp, int(getattr(lut, "n_tables", 1)), msg, len(msg)):
+        return msg.value.decode()
+    return None
+
+
 def aligned_zeros(n, dtype, align=64):
     """numpy buffer whose data pointer is `align`-byte aligned (the vector kernels need 16)."""
     raw = np.zeros(n * np.dtype(dtype).itemsize + align, np.uint8)
@@ -294,6 +304,7 @@ def bpc_decode_stream_k(stream, AW, AH, wl, lut, k, c16=False):
     bad = lib().emu_bpc_decode_stream_k(_p(stream), int(stream.size), AW, AH, wl, _p(tab), _p(geo), _p(coef), _p(flag),
                                         C.c_float(k), int(getattr(lut, "n_tables", 1)), int(c16))
     assert int(bad) == 0
+    bpc_decode_stream_k.last_flag = int(flag[0])
     return coef
 
 

@@ -385,6 +385,14 @@ static BpcArgs mk(int aw, int ah, int wl, const int32_t *lut, const int *geo, in
     return a;
 }
 
+// what picsong_ctx_set_lut_component / _device decide about a table before a context takes it (lut_refusal): 0 = the
+// context takes it, 1 = refused, the reason in msg
+extern "C" int emu_lut_refusal(const int *geo, int wl, float k, int cp, int n_tables, char *msg, int cap)
+{
+    const LutGeo g{geo[0], geo[1], geo[2], geo[3], geo[4], geo[5], geo[6], geo[7], geo[8]};
+    return lut_refusal(g, wl, k > 0.0f, cp == 3, n_tables, msg, (size_t)cap) ? 1 : 0;
+}
+
 // k > 0 (n_tables bit-plane tables in lut) runs the BULK instantiations, like picsong_hip.hip
 // codeblocks [cb_begin, cb_begin + cb_count) of the frame (cb_count < 0: all), like bpc_encode_impl
 void emu_bpc_encode_range(const void *coeffs, int is_float, int aw, int ah, int wl, const int32_t *lut, const int *geo,

@@ -167,6 +167,67 @@ class Lut:
             pass
 
 
+class CallerLut:
+    """A caller's own table: a numpy array and an explicit geometry, as picsong_ctx_set_lut_component / _device take
+    them.  The oracle's PoLut points at `table` itself, so oracle and emulator read the same entries."""
+
+    def __init__(self, table, geometry, n_tables=1, cp=2):
+        self.table = np.ascontiguousarray(table, np.int32)
+        self.cp = cp
+        self.n_tables = n_tables
+        self.c = PoLut()
+        for k, v in geometry.items():
+            setattr(self.c, k, int(v))
+        self.c.n_tables, self.c.cp = n_tables, cp
+        self.total = self.c.n_ref + (2 if cp == 3 else 1) * (self.c.n_sig + self.c.n_sign)
+        if self.table.size < self.total * n_tables:
+            raise ValueError(f"table of {self.table.size} entries, the geometry asks for {self.total * n_tables}")
+        self.c.table = self.table.ctypes.data_as(C.POINTER(C.c_int32))
+
+    geometry = Lut.geometry
+
+
+def _sections(lut):
+    """Per table of the array: [(contexts, entries)] of its sections in order (ref, sig, sign[, cp_sig, cp_sign])."""
+    g = lut.geometry()
+    sec = [(g["ctx_ref"], g["n_ref"]), (g["ctx_sig"], g["n_sig"]), (g["ctx_sign"], g["n_sign"])]
+    return sec + sec[1:] if lut.cp == 3 else sec
+
+
+def lut_cut_bitplanes(lut, n):
+    """`lut` (any layout) keeping bit-planes bp < n of every group of every section: n_bitplanes = n."""
+    g = lut.geometry()
+    nbp = g["n_bitplanes"]
+    parts, sizes = [], []
+    for j in range(lut.n_tables):
+        off = j * lut.total
+        for ctx, size in _sections(lut):
+            groups = size // (nbp * ctx)
+            assert groups * nbp * ctx == size
+            parts.append(lut.table[off:off + size].reshape(groups, nbp, ctx)[:, :n].ravel())
+            off += size
+            if j == 0:
+                sizes.append(groups * n * ctx)
+    geo = dict(g, n_bitplanes=n, n_ref=sizes[0], n_sig=sizes[1], n_sign=sizes[2])
+    return CallerLut(np.concatenate(parts), geo, lut.n_tables, lut.cp)
+
+
+def lut_shorten_sections(lut, d_ref, d_sig, d_sign):
+    """`lut` with n_ref / n_sig / n_sign declared d_* entries smaller: every section loses its last d_* entries."""
+    g = lut.geometry()
+    d = [d_ref, d_sig, d_sign]
+    if lut.cp == 3:
+        d += d[1:]
+    parts = []
+    for j in range(lut.n_tables):
+        off = j * lut.total
+        for (ctx, size), cut in zip(_sections(lut), d):
+            parts.append(lut.table[off:off + size - cut])
+            off += size
+    geo = dict(g, n_ref=g["n_ref"] - d_ref, n_sig=g["n_sig"] - d_sig, n_sign=g["n_sign"] - d_sign)
+    return CallerLut(np.concatenate(parts), geo, lut.n_tables, lut.cp)
+
+
 def lut_for(lossy, wl, fill=0):
     return Lut(os.path.join(LUT_DIR, "n1_lossy" if lossy else "n1_lossless"), wl, 1, fill)
 
@@ -182,6 +243,68 @@ def lut_for_cp3(lossy, wl, fill=0):
 def lut_for_k(lossy, wl, fill=0):
     """All bit-plane tables (files _0 .. _14) of the R component: the -k > 0 layout."""
     return Lut(os.path.join(LUT_DIR, "n1_lossy" if lossy else "n1_lossless"), wl, 1, fill, n_tables=0)
+
+
+def lut_keep_groups(lut, groups, n_subbands):
+    """`lut` declared with `n_subbands` subbands a level and sections of their first `groups` groups."""
+    g = lut.geometry()
+    nbp = g["n_bitplanes"]
+    parts = []
+    for j in range(lut.n_tables):
+        off = j * lut.total
+        for ctx, size in _sections(lut):
+            parts.append(lut.table[off:off + groups * nbp * ctx])
+            off += size
+    geo = dict(g, n_subbands=n_subbands, n_ref=groups * nbp * g["ctx_ref"], n_sig=groups * nbp * g["ctx_sig"],
+               n_sign=groups * nbp * g["ctx_sign"])
+    return CallerLut(np.concatenate(parts), geo, lut.n_tables, lut.cp)
+
+
+# ---- caller tables whose geometry is not the context's (the setters' admission matrix) ----
+def caller_table(layout, name, wl):
+    """layout: "k0" (file _0), "cp3" (the five sections of -cp 3) or "k" (every bit-plane file, the -k > 0 layout)."""
+    load = {"k0": lut_for, "cp3": lut_for_cp3, "k": lut_for_k}[layout]
+    if name == "wl-1":                        # sections short by one level's groups
+        return load(False, wl - 1)
+    if name == "wl+1":                        # longer than the context needs
+        return load(False, wl + 1)
+    if name.startswith("bp"):                 # bit-planes bp < N of every group
+        return lut_cut_bitplanes(load(False, wl), int(name[2:]))
+    if name.startswith("short"):              # n_ref / n_sig / n_sign declared N planes of a group smaller
+        p = int(name[5:])
+        return lut_shorten_sections(load(False, wl), p * 1, p * 9, p * 4)
+    if name == "nsub1":                       # one subband a level, sections sized for it: groups 0 .. wl
+        return lut_keep_groups(load(False, wl), wl + 1, 1)
+    if name == "nsub1+":                      # ... and one group more: level wl - 1's HH group (sb 2) is wl + 1
+        return lut_keep_groups(load(False, wl), wl + 2, 1)
+    if name == "ntab4":                       # fewer bit-plane tables than the codeblocks' MSBs ask for
+        return Lut(os.path.join(LUT_DIR, "n1_lossless"), wl, 1, 0, n_tables=4)
+    if name == "ntab15":                      # the -k > 0 array on a k = 0 context
+        return lut_for_k(False, wl)
+    raise ValueError(name)
+
+
+def deep_coeffs(W, H, seed, raw_cb=None):
+    """Sparse codeblocks whose spikes reach MSB 15 (every subband has such codeblocks, the LL group included), two with
+    a shallower MSB, and `raw_cb` filled with noise that takes the raw fallback."""
+    rng = np.random.default_rng(seed)
+    coef = np.zeros((H, W), np.int32)
+    ncx, ncy = W // 64, H // 64
+    for cy in range(ncy):
+        for cx in range(ncx):
+            cb = cy * ncx + cx
+            peak = {3: 6000, 6: 300}.get(cb, 65535)
+            blk = rng.integers(-1, 2, (64, 64)) * (rng.integers(0, 4, (64, 64)) == 0) * (cb > 0)   # (LL: spikes only)
+            ys, xs = rng.integers(0, 64, 24), rng.integers(0, 64, 24)
+            blk[ys, xs] = rng.integers(-peak, peak + 1, 24)
+            blk[1, 1] = peak if peak >= 32768 else blk[1, 1]
+            if cb == raw_cb:
+                blk = rng.integers(-30000, 30001, (64, 64))
+            coef[cy * 64:cy * 64 + 64, cx * 64:cx * 64 + 64] = blk
+    # the deepest levels' subbands are a few samples wide at a high wl: give them large magnitudes of both signs, so
+    # that the significance and sign symbols of their top planes are coded
+    coef[:8, :8] = rng.integers(4096, 65536, (8, 8)) * rng.choice([-1, 1], (8, 8))
+    return coef
 
 
 def consecutive_bitplanes(msb, k, level, sb, wl):

@@ -949,3 +949,90 @@ def test_damaged_streams_decode_without_leaving_their_buffers(oracle, pa, torch)
     # and the context is still good for a clean stream
     assert np.array_equal(c.decode_frame(torch.from_numpy(good).cuda()).cpu().numpy()[:H, :W], img)
     c.close()
+
+
+# ---- caller tables whose geometry is not the context's: taken and coded as the oracle codes, or refused ---------------
+def _lut_info(pa, lut):
+    info = pa.LutInfo()
+    for k, v in lut.geometry().items():
+        setattr(info, k, v)
+    info.n_tables, info.cp = lut.n_tables, lut.cp
+    return info
+
+
+def _set_caller_table(pa, torch, c, lut, setter):
+    """picsong_ctx_set_lut_component (a host copy) or picsong_ctx_set_lut_device (the caller's device table, which must
+    outlive its use: returned); returns (rc, device table or None)."""
+    import ctypes as C
+    info = _lut_info(pa, lut)
+    if setter == "component":
+        tab = np.ascontiguousarray(lut.table[:lut.total * lut.n_tables], np.int32)
+        return c.L.picsong_ctx_set_lut_component(c.h, 0, C.byref(info), tab.ctypes.data_as(C.c_void_p)), None
+    d = _dev(torch, lut.table[:lut.total * lut.n_tables])
+    return c.L.picsong_ctx_set_lut_device(c.h, 0, C.byref(info), C.c_void_p(d.data_ptr())), d
+
+
+def _stage_parity(oracle, torch, c, coef, wl, lut, k):
+    H, W = coef.shape
+    st_o, sz_o = oracle.bpc_encode(coef, wl, lut, k=k)
+    st, sz = c.bpc_encode(_dev(torch, coef))
+    st, sz = st.cpu().numpy(), sz.cpu().numpy()
+    assert np.array_equal(sz, sz_o)
+    for cb in range(sz_o.size):
+        n = sz_o[cb]
+        assert np.array_equal(st[cb * 4096:cb * 4096 + n], st_o[cb * 4096:cb * 4096 + n]), cb
+    ref = oracle.bpc_decode(st_o, sz_o, W, H, wl, lut, k=k)
+    back = c.bpc_decode(_dev(torch, st_o), _dev(torch, sz_o)).cpu().numpy().reshape(H, W)
+    assert np.array_equal(back, ref)
+    assert c.range_flag() == 0
+
+
+_GPU_CT_CASES = ([("k0", t, True) for t in ("wl-1", "wl+1", "bp8", "short4", "nsub1")] + [("k0", "ntab15", False)]
+                 + [("cp3", t, True) for t in ("wl-1", "bp8", "nsub1")]
+                 + [(m, t, ok) for m in ("k", "k-hint", "k-fulltab", "wholegeo")
+                    for t, ok in (("wl-1", False), ("wl+1", True), ("bp12", True), ("bp11", False), ("bp8", False),
+                                  ("short3", True), ("short4", False), ("ntab4", True), ("nsub1", False),
+                                  ("nsub1+", True))])
+
+
+@pytest.mark.parametrize("setter", ["component", "device"])
+@pytest.mark.parametrize("mode,table,accepted", _GPU_CT_CASES)
+def test_caller_table_lut_geometry_taken_or_refused(oracle, pa, torch, monkeypatch, mode, table, accepted, setter):
+    """Both setters with a caller's table of another geometry (tests/test_kernels_emulated.py has the same matrix on the
+    emulator).  Taken: the stage coders and the frame paths give the oracle's staging, sizes, codestream and decode.
+    Refused: PICSONG_ERR_ARG naming the geometry, and the context keeps coding with the table it held.  -k > 0 runs the
+    lone-frame encoder (whole tables), the pipelined one (compact copies where the geometry allows), the whole-table
+    coders by PICSONG_BULK_FULLTAB=1, and a geometry whose codeblocks take whole tables by themselves."""
+    W, H, wl = (128, 128, 5) if mode == "wholegeo" else (256, 256, 2)
+    if table.startswith("nsub1") and mode != "wholegeo":
+        W, H, wl = 256, 256, 1          # level 0's HH group (2, past LL's 1) has coded codeblocks at MSB 15
+    layout = {"k0": "k0", "cp3": "cp3"}.get(mode, "k")
+    k = 0.7 if layout == "k" else 0.0
+    if mode == "k-fulltab":
+        monkeypatch.setenv("PICSONG_BULK_FULLTAB", "1")
+    load = {"k0": oracle.lut_for, "cp3": oracle.lut_for_cp3, "k": oracle.lut_for_k}[layout]
+    good = load(False, wl)
+    lut = oracle.caller_table(layout, table, wl)
+    coef = oracle.deep_coeffs(W, H, 17, raw_cb=(W // 64) * (H // 64) - 1)
+    img = oracle.gen_frame(W, H, 3)
+    c = pa.Codec(W, H, wl=wl, k=k, cp=3 if layout == "cp3" else 2, pipelined=(mode == "k-hint"))
+    rc, d_good = _set_caller_table(pa, torch, c, good, setter)
+    assert rc == 0
+    rc, d_lut = _set_caller_table(pa, torch, c, lut, setter)
+    if accepted:
+        assert rc == 0, c.L.picsong_last_error().decode()
+        _stage_parity(oracle, torch, c, coef, wl, lut, k)
+        s = c.encode_frame(_dev(torch, oracle.pad_frame(img)), 0)
+        ref = oracle.encode_frame(img, wl, False, 1.0, lut, 0, 0, k=k)
+        assert np.array_equal(s.cpu().numpy().view(np.uint16), ref)
+        want = oracle.decode_frame(ref, W, H, wl, False, 1.0, lut, k=k)
+        assert np.array_equal(c.decode_frame(s.clone()).cpu().numpy()[:H, :W], want)
+    else:
+        assert rc == -1                                               # PICSONG_ERR_ARG
+        msg = c.L.picsong_last_error().decode()
+        g = lut.geometry()
+        assert (f"n_bitplanes {g['n_bitplanes']}" in msg and f"wl {wl}" in msg) or "bit-plane tables" in msg, msg
+        _stage_parity(oracle, torch, c, coef, wl, good, k)           # the context still codes with its previous table
+    torch.cuda.synchronize()
+    c.close()
+    del d_good, d_lut

@@ -778,3 +778,123 @@ def test_decode_frame_path_with_16_bit_coefficients_and_fused_levels(oracle, E, 
         monkeypatch.setenv("PICSONG_DWT_EXACT_REPLAY", "0")
         pix, flags = E.dwt_inverse_u8_c16(c16, wl, lossy, qs, extra=extra)
         assert flags == 5 and np.array_equal(pix, ref_pix)
+
+
+# ---- caller tables whose geometry is not the context's ---------------------------------------------------------------
+# The context setters take any table with any declared geometry (the façade hands over the caller's own device table on
+# every Code / Decode).  The contract for an index outside the table is the oracle's po_lut_at: clamped into the whole
+# array.  A table is either taken, and then every coder path equals the oracle bit for bit, or refused by the setter
+# (lut_refusal, the same function here and in picsong_ctx_set_lut_component / _device).
+_CT_K = 0.7
+# (mode, W, H, wl): k0 = two passes, k = 0; cp3 = three passes; compact = -k > 0, the geometry takes the compact table
+# copies; fulltab = the same with PICSONG_BULK_FULLTAB=1; wholegeo = -k > 0 whose geometry takes whole tables by itself
+_CT_MODES = {"k0": (256, 256, 2), "cp3": (256, 256, 2), "compact": (256, 256, 2), "fulltab": (256, 256, 2),
+             "wholegeo": (128, 128, 5)}
+# table -> taken by a context of that mode?  -k > 0: refused where the coders would read further than one table plus the
+# kLutSlack entries behind it (bit-plane 15 of the highest group: n_bitplanes < 12, sign sections short by more than
+# three planes, or one subband a level with sections that end at the LL group wl -- level wl - 1's HH group is wl + 1);
+# k = 0 / -cp 3: refused only for an array of several tables.
+_CT_CASES = ([("k0", t, True) for t in ("wl-1", "wl+1", "bp12", "bp8", "short2", "short4", "nsub1")]
+             + [("k0", "ntab15", False)]
+             + [("cp3", t, True) for t in ("wl-1", "bp12", "bp8", "short4", "nsub1")]
+             + [(m, t, ok) for m in ("compact", "fulltab", "wholegeo")
+                for t, ok in (("wl-1", False), ("wl+1", True), ("bp12", True), ("bp11", False), ("bp8", False),
+                              ("short2", True), ("short3", True), ("short4", False), ("ntab4", True),
+                              ("nsub1", False), ("nsub1+", True))])
+
+
+@pytest.mark.parametrize("mode,table,accepted", _CT_CASES)
+def test_caller_table_lut_geometry_against_the_oracle(oracle, E, monkeypatch, mode, table, accepted):
+    """A table the setters take codes and decodes exactly as the oracle does on every path of the mode: staging, sizes,
+    the packed stream, and the decode in the staging and stream forms, 32-bit and int16 (the int16 form at every
+    coefficient that fits it: MSB 15 magnitudes do not, and the frame paths never take it for them).  A refused table
+    is checked here for the setters' verdict and message only: the emulator has no context object, so that a refused
+    table leaves the context's previous one in place is checked by the GPU test of the same matrix."""
+    W, H, wl = _CT_MODES[mode]
+    if table.startswith("nsub1") and mode != "wholegeo":
+        W, H, wl = 256, 256, 1          # level 0's HH group (2, past LL's 1) has coded codeblocks at MSB 15
+    layout = {"k0": "k0", "cp3": "cp3"}.get(mode, "k")
+    k = _CT_K if layout == "k" else 0.0
+    if mode == "fulltab":
+        monkeypatch.setenv("PICSONG_BULK_FULLTAB", "1")
+    else:
+        monkeypatch.delenv("PICSONG_BULK_FULLTAB", raising=False)
+    lut = oracle.caller_table(layout, table, wl)
+    refusal = E.lut_refusal(lut, wl, k)
+    if refusal is None:
+        coef = oracle.deep_coeffs(W, H, 17, raw_cb=(W // 64) * (H // 64) - 1)
+        st_o, sz_o = oracle.bpc_encode(coef, wl, lut, k=k)
+        msbs = st_o[::4096][sz_o < 4096]
+        assert sz_o[-1] == 4096 and (sz_o < 4096).sum() >= sz_o.size // 2 and msbs.max() == 15
+        # the LL codeblock is coded from bit-plane 15 (a table without the LL group's entries makes it raw)
+        assert (sz_o[0] < 4096 and st_o[0] == 15) or table == "wl-1"
+        st_e, sz_e, flag = (E.bpc3_encode(coef, wl, lut) if layout == "cp3" else E.bpc_encode(coef, wl, lut, k=k))
+        assert flag == 0
+        assert np.array_equal(sz_e, sz_o)
+        for cb in range(sz_o.size):
+            n = sz_o[cb]
+            assert np.array_equal(st_e[cb * 4096:cb * 4096 + n], st_o[cb * 4096:cb * 4096 + n]), cb
+        stream = oracle.bitstream_pack(st_o, sz_o, None)
+        assert np.array_equal(E.pack(st_e, sz_e), stream)
+        ref = oracle.bpc_decode(st_o, sz_o, W, H, wl, lut, k=k)
+        assert np.array_equal(ref[sz_o.reshape(H // 64, W // 64).repeat(64, 0).repeat(64, 1) < 4096],
+                              coef[sz_o.reshape(H // 64, W // 64).repeat(64, 0).repeat(64, 1) < 4096])
+        fits = np.abs(ref) < 32768                 # where the int16 form is defined (the frame paths take it only then)
+        assert fits.mean() > 0.99
+        if layout == "cp3":
+            assert np.array_equal(E.bpc3_decode(st_o, sz_o, W, H, wl, lut), ref)
+        elif layout == "k0":
+            assert np.array_equal(E.bpc_decode(st_o, sz_o, W, H, wl, lut), ref)
+            assert np.array_equal(E.bpc_decode_stream(stream, W, H, wl, lut), ref) and E.bpc_decode_stream.last_bad == 0
+            assert np.array_equal(E.bpc_decode_stream16(stream, W, H, wl, lut)[fits], ref[fits])
+        else:
+            assert np.array_equal(E.bpc_decode(st_o, sz_o, W, H, wl, lut, k=k), ref)
+            assert np.array_equal(E.bpc_decode_stream_k(stream, W, H, wl, lut, k), ref)
+            assert np.array_equal(E.bpc_decode_stream_k(stream, W, H, wl, lut, k, c16=True)[fits], ref[fits])
+    if accepted:
+        assert refusal is None
+    else:
+        assert refusal is not None
+        g = lut.geometry()
+        assert (f"n_bitplanes {g['n_bitplanes']}" in refusal and f"wl {wl}" in refusal) or "bit-plane tables" in refusal
+
+
+@pytest.mark.parametrize("wl", [1, 2, 3, 4, 5, 6])
+def test_shipped_tables_are_taken_at_every_wl(oracle, E, wl):
+    """The setters' geometry check refuses none of the shipped tables in the layout of their mode."""
+    for lossy in (False, True):
+        assert E.lut_refusal(oracle.lut_for(lossy, wl), wl) is None
+        assert E.lut_refusal(oracle.lut_for_k(lossy, wl), wl, 0.5) is None
+        assert E.lut_refusal(oracle.lut_for_cp3(lossy, wl), wl) is None
+        assert E.lut_refusal(oracle.lut_for(lossy, wl), wl, 0.5) is None        # one bit-plane table is enough for k > 0
+
+
+@pytest.mark.parametrize("k", [0.0, 0.6])
+def test_raw_codeblocks_with_high_shorts_decode_alike_in_both_forms(oracle, E, k):
+    """Raw codeblocks travel as (magnitude << 1 | sign) shorts; with magnitudes of 2^14 .. 2^15 - 1 every short is
+    >= 0x8000 -- word 0, the one in the MSB's slot, included.  The int16 decode form (it reads uint16 stream words only)
+    must give what the 32-bit form and the oracle give, with the range flag clear."""
+    rng = np.random.default_rng(41)
+    W, H, wl = 192, 64, 1
+    coef = rng.integers(-200, 201, (H, W)).astype(np.int32)           # codeblock 1: coded
+    for cx in (0, 2):
+        coef[:, cx * 64:cx * 64 + 64] = rng.integers(16384, 32768, (64, 64)) * rng.choice([-1, 1], (64, 64))
+    coef[0, 0], coef[0, 128] = 32767, -16384
+    lut = oracle.lut_for_k(False, wl) if k > 0 else oracle.lut_for(False, wl)
+    st_o, sz_o = oracle.bpc_encode(coef, wl, lut, k=k)
+    assert sz_o[0] == 4096 and sz_o[2] == 4096 and sz_o[1] < 4096
+    stream = oracle.bitstream_pack(st_o, sz_o, None)
+    assert stream[9] >= 0x8000 and stream[9 + 4] >= 0x8000            # word 0 of both raw codeblocks, in the MSB slot
+    assert (stream[9 + 6:][:4095] >= 0x8000).all()                     # codeblock 0's other shorts
+    st_u, sz_u = oracle.bitstream_unpack(stream, sz_o.size)
+    ref = oracle.bpc_decode(st_u, sz_u, W, H, wl, lut, k=k)
+    assert np.array_equal(ref, coef)
+    if k > 0:
+        assert np.array_equal(E.bpc_decode_stream_k(stream, W, H, wl, lut, k), ref)
+        assert E.bpc_decode_stream_k.last_flag == 0
+        assert np.array_equal(E.bpc_decode_stream_k(stream, W, H, wl, lut, k, c16=True).astype(np.int32), ref)
+        assert E.bpc_decode_stream_k.last_flag == 0
+    else:
+        assert np.array_equal(E.bpc_decode_stream(stream, W, H, wl, lut), ref) and E.bpc_decode_stream.last_flag == 0
+        assert np.array_equal(E.bpc_decode_stream16(stream, W, H, wl, lut).astype(np.int32), ref)
+        assert E.bpc_decode_stream16.last_flag == 0 and E.bpc_decode_stream16.last_bad == 0
