@@ -94,6 +94,10 @@ struct BpcArgs {
     const int32_t *cw16_total;
     unsigned long long cw16_stride;
     uint32_t cw16_max;
+    // decoders, reduced-resolution calls (picsong_decode_frame_reduced): the launch decodes the rectangle of the first
+    // ncx_r codeblock columns of the raster's rows, ncb_r codeblocks in row order -- index i of a frame's launch is
+    // codeblock (i / ncx_r) * ncx + i % ncx_r; waves_per_frame counts the rectangle's waves.  0: every codeblock.
+    int ncx_r, ncb_r;
 };
 
 // ---- cross-lane helpers ---------------------------------------------------------------------
@@ -2006,9 +2010,18 @@ void bpc_decode_kernel(BpcArgs a)
             if (a.lut_c[0]) a.lut = f == 0 ? a.lut_c[0] : (f == 1 ? a.lut_c[1] : a.lut_c[2]);
         }
     }
-    const int cb = a.cb_base + 2 * wave + (int)half;
-    const bool valid = cb < a.nCB;
-    const int cbx = valid ? cb % a.ncx : 0, cby = valid ? cb / a.ncx : 0;
+    // (each half maps on its own: with an odd ncx_r a wave's two codeblocks may lie in two rows)
+    int cb = a.cb_base + 2 * wave + (int)half, cbx, cby;
+    bool valid;
+    if (a.ncx_r > 0) {                                      // (a reduced launch starts at codeblock 0)
+        cby = cb / a.ncx_r; cbx = cb - cby * a.ncx_r;
+        valid = cb < a.ncb_r;
+        cb = cby * a.ncx + cbx;
+    } else {
+        valid = cb < a.nCB;
+        cbx = cb % a.ncx; cby = cb / a.ncx;
+    }
+    if (!valid) cbx = cby = 0;
     // (C16: the lane's first coefficient in 16-bit words, expressed in the 32-bit words of coeffs_out's type)
     const size_t cbase = (size_t)(cby * 64) * (size_t)a.AW + (size_t)(cbx * 64) + 2u * t;
     int32_t *const obase = C16 ? reinterpret_cast<int32_t *>(reinterpret_cast<int16_t *>(a.coeffs_out) + cbase) : a.coeffs_out + cbase;

@@ -227,10 +227,11 @@ inline bool plan_dwt_fwd2(const std::vector<FwdLaunch> &plan, Fwd2Launch &f, boo
 }
 
 // the 16-bit form exists in the vector-only kernel instantiations: every level of the frame on the vector path
-inline bool dwt_c16_geometry_ok(int aw, int ah, int wl)
+// (lo > 0: a reduced-resolution decode, which runs the synthesis levels lo .. wl - 1 only)
+inline bool dwt_c16_geometry_ok(int aw, int ah, int wl, int lo = 0)
 {   // every level on the vector path: level widths multiples of 4 (and rows 16-byte aligned: aw % 4 == 0)
     if (const char *e = getenv("PICSONG_DWT_NOVEC")) if (atoi(e) != 0) return false;
-    for (int l = 0; l < wl; l++) {
+    for (int l = lo; l < wl; l++) {
         const int W = aw >> l;
         if (W < 4 || (W & 3) || ((W >> 1) & 1)) return false;
     }
@@ -284,15 +285,49 @@ inline std::vector<InvLaunch> plan_dwt_inverse(const int32_t *d_in, void *d_out,
 }
 inline bool plan_inv_is_c16(const std::vector<InvLaunch> &plan) { return !plan.empty() && plan[0].a.c16 != 0; }
 
+// ---- reduced-resolution decode (picsong_decode_frame_reduced and its mirrors; no reference counterpart).  The image
+// at 1/2^r of the frame's size is LL_r, the synthesis stopped after level r.  Its inputs -- the subbands of levels
+// r + 1 .. wl and LL_wl -- fill the corner [0, AW >> r) x [0, AH >> r) of the Mallat array, so only the codeblocks that
+// meet that corner are decoded: the first ncx_r columns of the first ncy_r codeblock rows.
+struct ReducedRect { int ncx_r, ncy_r; };
+inline bool reduce_ok(int wl, int r) { return r >= 0 && r <= wl - 1; }
+inline ReducedRect reduced_rect(int aw, int ah, int r)
+{
+    return { ((aw >> r) + 63) / 64, ((ah >> r) + 63) / 64 };
+}
+// decoder waves of one frame: two codeblocks a wave, the rectangle's codeblocks in row order (BpcArgs::ncx_r)
+inline int reduced_waves(const ReducedRect &q) { return (q.ncx_r * q.ncy_r + 1) / 2; }
+// picsong_reduced_dims: d = { visible width, height (ceil(W / 2^r) x ceil(H / 2^r)), padded width, height, codeblocks }
+inline void reduced_dims(int w, int h, int aw, int ah, int r, int d[5])
+{
+    const ReducedRect q = reduced_rect(aw, ah, r);
+    d[0] = (w + (1 << r) - 1) >> r; d[1] = (h + (1 << r) - 1) >> r;
+    d[2] = aw >> r; d[3] = ah >> r;
+    d[4] = q.ncx_r * q.ncy_r;
+}
+// the synthesis levels wl - 1 .. r of plan_dwt_inverse: level r's output, (AW >> r) x (AH >> r) with row stride AW >> r,
+// is the reduced image.  The 16-bit form stays where the levels that run all take the vector kernels.
+inline std::vector<InvLaunch> plan_dwt_inverse_reduced(const int32_t *d_in, void *d_out, int aw, int ah, int wl, float qs,
+                                                       bool fast, bool c16, int r)
+{
+    std::vector<InvLaunch> v = plan_dwt_inverse(d_in, d_out, aw, ah, wl, qs, fast, c16);
+    v.resize(v.size() - (size_t)r);
+    bool all_vec = true;
+    for (const InvLaunch &f : v) all_vec = all_vec && f.vec;
+    for (InvLaunch &f : v) f.a.c16 = c16 && all_vec ? 1 : 0;
+    return v;
+}
+
 // May a decode context take the 16-bit coefficient form between its decoder and its synthesis?  The bound of coef16_ok
 // (an honest stream of such a context has no magnitude of 2^15 or more), the vector kernels on every level, at least
 // two levels (the coarsest level that also writes pixels has no C16 instantiation), and for 9/7 the verified
 // reciprocal divisions (the lean kernels are the ones with a C16 form).  PICSONG_DEC_C16=0 keeps the 32-bit arrays.
-inline bool dec_c16_ok(bool lossy, int wl, float qs, int in_max, int aw, int ah, bool fast_div)
+// lo > 0: a reduced-resolution decode's synthesis, levels lo .. wl - 1 (the two-level minimum counts those).
+inline bool dec_c16_ok(bool lossy, int wl, float qs, int in_max, int aw, int ah, bool fast_div, int lo = 0)
 {
     if (const char *e = getenv("PICSONG_DEC_C16")) if (atoi(e) == 0) return false;
     if (const char *e = getenv("PICSONG_DWT_INV97")) if (atoi(e) == 0) return false;
-    return wl >= 2 && (!lossy || fast_div) && coef16_ok(lossy, wl, qs, in_max) && dwt_c16_geometry_ok(aw, ah, wl);
+    return wl - lo >= 2 && (!lossy || fast_div) && coef16_ok(lossy, wl, qs, in_max) && dwt_c16_geometry_ok(aw, ah, wl, lo);
 }
 
 // Synthesis levels 1 and 0 of an inverse plan as ONE launch of dwt_inv2_kernel (dwt_kernels.hpp): the decode frame

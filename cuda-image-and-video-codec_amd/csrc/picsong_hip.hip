@@ -675,13 +675,15 @@ int picsong_dwt_forward_tail(picsong_ctx *c, void *d_out, void *stream)
 // pointers allow it (plan_inv_is_c16), BEFORE the decoder is launched: inverse_plan, then the decoder, then run_inverse.
 // (the grey frame paths take the 16-bit form only with the fused pixel store; planes_out: an RGB frame's components,
 // whose finest level writes T samples for the inverse colour transform, take it too)
+// reduce > 0: the levels wl - 1 .. reduce only (plan_dwt_inverse_reduced), level `reduce` the one that writes the pixels
 static std::vector<InvLaunch> inverse_plan(picsong_ctx *c, const int32_t *d_in, void *d_out, uint8_t *d_pixels, bool *fused,
-                                           unsigned frames, size_t pix_stride, bool want_c16, bool planes_out = false)
+                                           unsigned frames, size_t pix_stride, bool want_c16, bool planes_out = false,
+                                           int reduce = 0)
 {
     if (fused) *fused = false;
     const bool px = d_pixels && (((uintptr_t)d_pixels) & 3u) == 0 && (pix_stride & 3u) == 0;
-    std::vector<InvLaunch> plan = plan_dwt_inverse(d_in, d_out, c->aw, c->ah, c->p.wl, c->p.qs, c->fast_div,
-                                                   want_c16 && (px || planes_out));
+    std::vector<InvLaunch> plan = plan_dwt_inverse_reduced(d_in, d_out, c->aw, c->ah, c->p.wl, c->p.qs, c->fast_div,
+                                                           want_c16 && (px || planes_out), reduce);
     if (px && !plan.empty() && plan.back().vec) {
         plan.back().a.dst_u8 = d_pixels;
         plan.back().a.off = 1 << (c->p.bit_depth - 1);
@@ -851,6 +853,16 @@ int picsong_bpc_encode(picsong_ctx *c, const void *d_coeffs, int32_t *d_staging,
     return bpc_encode_widened(c, d_coeffs, d_staging, d_sizes, (hipStream_t)stream, 0);
 }
 
+// The decoder's codeblocks in a call at 1/2^reduce resolution (reduced_rect; reduce = 0: every codeblock, the fields
+// stay 0): sets BpcArgs::ncx_r / ncb_r and returns the waves of one frame.
+static int decode_rect(const picsong_ctx *c, BpcArgs &a, int reduce)
+{
+    if (reduce == 0) return (c->ncb + 1) / 2;
+    const ReducedRect q = reduced_rect(c->aw, c->ah, reduce);
+    a.ncx_r = q.ncx_r; a.ncb_r = q.ncx_r * q.ncy_r;
+    return reduced_waves(q);
+}
+
 // PICSONG_DEC_STAGING=1: the frame paths unpack into the 32-bit staging first, as picsong_bitstream_unpack +
 // picsong_bpc_decode do (A/B of the decoder that reads the stream itself)
 static bool dec_from_stream(const picsong_ctx *c)
@@ -862,9 +874,10 @@ static bool dec_from_stream(const picsong_ctx *c)
 // d_stream16 != nullptr (k = 0, -cp 2): the codewords come from the packed stream, d_offsets the scan of its lengths
 // (scan_stream_kernel); d_staging is then not read
 // c16 (with d_stream16): the coefficients leave as an int16 Mallat array at d_coeffs (bpc_decode_kernel's C16 form)
+// reduce > 0: only the codeblocks of the 1/2^reduce image's corner (decode_rect)
 static int bpc_decode_impl(picsong_ctx *c, const int32_t *d_staging, const int32_t *d_sizes, int32_t *d_coeffs,
                            hipStream_t s, int comp = 0, const uint16_t *d_stream16 = nullptr,
-                           const int32_t *d_offsets = nullptr, bool c16 = false)
+                           const int32_t *d_offsets = nullptr, bool c16 = false, int reduce = 0)
 {
     BpcArgs a;
     int rc = bpc_args(c, a, comp);
@@ -874,7 +887,7 @@ static int bpc_decode_impl(picsong_ctx *c, const int32_t *d_staging, const int32
     a.sizes = const_cast<int32_t *>(d_sizes);
     if (int rc2 = ensure_plane_scratch(c)) return rc2;      // the decoder parks its finished planes there too
     a.plane_scratch = c->d_plane_scratch;
-    const unsigned waves = (unsigned)((c->ncb + 1) / 2);
+    const unsigned waves = (unsigned)decode_rect(c, a, reduce);
     if (c->p.cp == 3) {
         bpc3_kernel<true><<<(waves + kBpc3WgWaves - 1) / kBpc3WgWaves, 64 * kBpc3WgWaves, 0, s>>>(a);
         HIP_TRY(hipGetLastError());
@@ -919,17 +932,17 @@ static int bpc_decode_impl(picsong_ctx *c, const int32_t *d_staging, const int32
 static int unpack_impl(picsong_ctx *c, const uint16_t *d_stream, int32_t *d_staging, int32_t *d_sizes,
                        bool memset_staging, hipStream_t s);
 static int decode_stream_impl(picsong_ctx *c, const uint16_t *d_stream, int32_t *d_coeffs, hipStream_t s, int comp,
-                              bool c16 = false)
+                              bool c16 = false, int reduce = 0)
 {
     int rc;
     if (!dec_from_stream(c)) {
         if (c16) return fail(PICSONG_ERR_ARG, "the 16-bit coefficient form decodes from the stream itself");
         if ((rc = unpack_impl(c, d_stream, c->d_staging, c->d_sizes, false, s))) return rc;
-        return bpc_decode_impl(c, c->d_staging, c->d_sizes, d_coeffs, s, comp);
+        return bpc_decode_impl(c, c->d_staging, c->d_sizes, d_coeffs, s, comp, nullptr, nullptr, false, reduce);
     }
     scan_stream_kernel<<<1, scan_threads(c->ncb), 0, s>>>(d_stream, c->ncb, c->d_sizes, c->d_offsets, c->d_total, c->d_flag, 0);
     HIP_TRY(hipGetLastError());
-    return bpc_decode_impl(c, nullptr, c->d_sizes, d_coeffs, s, comp, d_stream, c->d_offsets, c16);
+    return bpc_decode_impl(c, nullptr, c->d_sizes, d_coeffs, s, comp, d_stream, c->d_offsets, c16, reduce);
 }
 
 int picsong_bpc_decode(picsong_ctx *c, const int32_t *d_staging, const int32_t *d_sizes, int32_t *d_coeffs,
@@ -1118,28 +1131,68 @@ int picsong_encode_frame(picsong_ctx *c, const uint8_t *d_frame, int iter, uint1
     return rc;
 }
 
-int picsong_decode_frame(picsong_ctx *c, const uint16_t *d_stream, uint8_t *d_frame_out, void *stream)
+// The decode calls at 1/2^reduce resolution: may the decoder hand the synthesis 16-bit coefficients?  c->c16_dec
+// (reduce = 0), or dec_c16_ok over the levels such a call runs.
+static bool dec_c16_reduced(const picsong_ctx *c, int reduce)
 {
-    if (!c || !d_frame_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame: null argument");
+    if (reduce == 0) return c->c16_dec;
+    return c->p.cp != 3 && c->p.bit_depth == 8 &&
+           dec_c16_ok(c->p.lossy != 0, c->p.wl, c->p.qs, c->p.is_rgb ? 255 : 128, c->aw, c->ah, c->fast_div, reduce);
+}
+// the refusals the reduced calls share (nothing is launched)
+static int reduced_args_ok(const picsong_ctx *c, int reduce, const char *who)
+{
+    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 3 contexts have no reduced-resolution decode", who);
+    if (!reduce_ok(c->p.wl, reduce))
+        return fail(PICSONG_ERR_ARG, "%s: reduce %d outside 0..%d (wl - 1)", who, reduce, c->p.wl - 1);
+    return PICSONG_OK;
+}
+
+// picsong_decode_frame (reduce = 0) and picsong_decode_frame_reduced: the pixels of level `reduce`, row stride AW >> reduce
+static int decode_frame_impl(picsong_ctx *c, const uint16_t *d_stream, uint8_t *d_frame_out, hipStream_t s, int reduce)
+{
     int rc = ensure_workspace(c, true);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
     // (16-bit coefficients between the decoder and the synthesis where the context's magnitudes are bounded and this
     // call's pointers take the vector kernels: c->c16_dec, plan_inv_is_c16)
     bool fused = false;
     const std::vector<InvLaunch> plan = inverse_plan(c, c->d_coef_i, c->d_coef, d_frame_out, &fused, 1, 0,
-                                                     c->c16_dec && dec_from_stream(c));
-    if ((rc = decode_stream_impl(c, d_stream, c->d_coef_i, s, 0, plan_inv_is_c16(plan)))) return rc;
+                                                     dec_c16_reduced(c, reduce) && dec_from_stream(c), false, reduce);
+    if ((rc = decode_stream_impl(c, d_stream, c->d_coef_i, s, 0, plan_inv_is_c16(plan), reduce))) return rc;
     if ((rc = run_inverse(c, plan, s))) return rc;
     if (fused) return PICSONG_OK;            // the finest level wrote the pixels itself
-    const void *img = (const char *)c->d_coef + c->extra * 4;
-    const size_t n4 = c->P / 4;
+    const void *img = plan.back().a.dst;     // (level `reduce`'s samples, packed: c->extra elements in when reduce = 0)
+    const size_t n4 = (size_t)(c->aw >> reduce) * (size_t)(c->ah >> reduce) / 4;
     const int off = 1 << (c->p.bit_depth - 1);
     const int grid = (int)((n4 + 255) / 256 > 8192 ? 8192 : (n4 + 255) / 256);
     if (c->p.lossy) clamp_to_u8_f32_kernel<<<grid, 256, 0, s>>>((const float *)img, d_frame_out, n4, (float)off);
     else clamp_to_u8_i32_kernel<<<grid, 256, 0, s>>>((const int32_t *)img, d_frame_out, n4, off);
     HIP_TRY(hipGetLastError());
     return PICSONG_OK;
+}
+
+int picsong_decode_frame(picsong_ctx *c, const uint16_t *d_stream, uint8_t *d_frame_out, void *stream)
+{
+    if (!c || !d_frame_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame: null argument");
+    return decode_frame_impl(c, d_stream, d_frame_out, (hipStream_t)stream, 0);
+}
+
+int picsong_reduced_dims(const picsong_ctx *c, int reduce, int *rw, int *rh, int *paw, int *pah, int *n_codeblocks)
+{
+    if (!c || !rw || !rh || !paw || !pah || !n_codeblocks) return fail(PICSONG_ERR_ARG, "reduced_dims: null argument");
+    if (!reduce_ok(c->p.wl, reduce))
+        return fail(PICSONG_ERR_ARG, "reduced_dims: reduce %d outside 0..%d (wl - 1)", reduce, c->p.wl - 1);
+    int d[5];
+    reduced_dims(c->p.width, c->p.height, c->aw, c->ah, reduce, d);
+    *rw = d[0]; *rh = d[1]; *paw = d[2]; *pah = d[3]; *n_codeblocks = d[4];
+    return PICSONG_OK;
+}
+
+int picsong_decode_frame_reduced(picsong_ctx *c, const uint16_t *d_stream, int reduce, uint8_t *d_out, void *stream)
+{
+    if (!c || !d_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame_reduced: null argument");
+    if (int rc = reduced_args_ok(c, reduce, "decode_frame_reduced")) return rc;
+    return decode_frame_impl(c, d_stream, d_out, (hipStream_t)stream, reduce);
 }
 
 int picsong_encode_stripe_coded(picsong_ctx *c, const void *d_coeffs, int cb_begin, int cb_count, uint16_t *d_stream,
@@ -1239,9 +1292,10 @@ static void launch_bulk_encode_frames(picsong_ctx *c, BpcArgs &a, unsigned frame
     if (cmp && c->pipelined) bpc_encode_kernel<true, true><<<wgs, 64, 0, s>>>(a);
     else bpc_encode_kernel<true><<<wgs, 64, 0, s>>>(a);
 }
-static void launch_bulk_decode_frames(picsong_ctx *c, BpcArgs &a, unsigned frames, bool cmp, bool direct, bool c16, hipStream_t s)
+// (wpf: the waves of one frame, decode_rect)
+static void launch_bulk_decode_frames(BpcArgs &a, unsigned frames, int wpf, bool cmp, bool direct, bool c16, hipStream_t s)
 {
-    a.waves_per_frame = (c->ncb + 1) / 2;
+    a.waves_per_frame = wpf;
     const unsigned wgs = frames * (unsigned)a.waves_per_frame;
     if (direct && c16) {
         if (cmp) bpc_decode_kernel<true, kDecSmallPlanes, true, true, true><<<wgs, 64, 0, s>>>(a);
@@ -1339,16 +1393,21 @@ int picsong_last_totals(picsong_ctx *c, void *stream, int n, int *h_totals)
 
 // n frames decoded through ONE launch per stage: the mirror of picsong_encode_frames (unpack with blockIdx.y =
 // frame, one decoder grid over n x nCB codeblocks, grid.z = frame for the inverse transform's levels)
-int picsong_decode_frames(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_frames_out,
-                          size_t frame_stride, void *stream)
+// picsong_decode_frames (reduce = 0) and picsong_decode_frames_reduced: frame f's pixels of level `reduce` at
+// d_frames_out + f * frame_stride, row stride AW >> reduce
+static int decode_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_frames_out,
+                              size_t frame_stride, void *stream, int reduce, const char *who)
 {
-    if (!c || !d_streams || !d_frames_out) return fail(PICSONG_ERR_ARG, "decode_frames: null argument");
-    if (n < 1 || n > 64) return fail(PICSONG_ERR_ARG, "decode_frames: n = %d outside 1..64", n);
+    if (!c || !d_streams || !d_frames_out) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (n < 1 || n > 64) return fail(PICSONG_ERR_ARG, "%s: n = %d outside 1..64", who, n);
     if (c->p.cp == 3 || c->p.is_rgb)
-        return fail(PICSONG_ERR_ARG, "decode_frames: grey -cp 2 contexts only (-cp 3: frame by frame; RGB: picsong_decode_rgb_frame)");
-    if (n > 1 && (stream_stride < picsong_max_stream_shorts(c->aw, c->ah) || frame_stride < c->P))
-        return fail(PICSONG_ERR_ARG, "decode_frames: strides %zu shorts / %zu bytes too small", stream_stride, frame_stride);
-    if (n == 1) return picsong_decode_frame(c, d_streams, d_frames_out, stream);
+        return fail(PICSONG_ERR_ARG, "%s: grey -cp 2 contexts only (-cp 3: frame by frame; RGB: picsong_decode_rgb_frame)", who);
+    if (!reduce_ok(c->p.wl, reduce))
+        return fail(PICSONG_ERR_ARG, "%s: reduce %d outside 0..%d (wl - 1)", who, reduce, c->p.wl - 1);
+    const size_t px = (size_t)(c->aw >> reduce) * (size_t)(c->ah >> reduce);      // bytes of one frame's pixels
+    if (n > 1 && (stream_stride < picsong_max_stream_shorts(c->aw, c->ah) || frame_stride < px))
+        return fail(PICSONG_ERR_ARG, "%s: strides %zu shorts / %zu bytes too small", who, stream_stride, frame_stride);
+    if (n == 1) return decode_frame_impl(c, d_streams, d_frames_out, (hipStream_t)stream, reduce);
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_batch(c, n);
     if (rc) return rc;
@@ -1373,13 +1432,13 @@ int picsong_decode_frames(picsong_ctx *c, int n, const uint16_t *d_streams, size
     // ---- decoder: one grid over the n frames' codeblock pairs, both plane-count classes
     BpcArgs a;
     if ((rc = bpc_args(c, a, 0))) return rc;
-    const int wpf = (c->ncb + 1) / 2;
+    const int wpf = decode_rect(c, a, reduce);
     a.cb_base = 0; a.nCB = c->ncb;
     a.coeffs_out = c->b_coef_i; a.staging = c->b_staging; a.sizes = c->b_sizes; a.plane_scratch = c->b_plane_scratch;
     // (the synthesis is planned first: it says whether this call's coefficients can travel as int16)
     bool fused = false;
     const std::vector<InvLaunch> plan = inverse_plan(c, c->b_coef_i, c->b_coef, d_frames_out, &fused, (unsigned)n, frame_stride,
-                                                     c->c16_dec && direct);
+                                                     dec_c16_reduced(c, reduce) && direct, false, reduce);
     const bool c16 = plan_inv_is_c16(plan);
     a.frames = n; a.waves_per_frame = wpf; a.coef_z = (unsigned long long)c->P * (c16 ? 2ull : 4ull);
     const unsigned wgs = (unsigned)(((size_t)n * (size_t)wpf + kBpcDecWgWaves - 1) / kBpcDecWgWaves);
@@ -1387,7 +1446,7 @@ int picsong_decode_frames(picsong_ctx *c, int n, const uint16_t *d_streams, size
         a.cw16 = d_streams; a.cw16_offsets = c->b_offsets; a.cw16_total = c->b_total; a.cw16_stride = stream_stride;
         a.cw16_max = (uint32_t)picsong_max_stream_shorts(c->aw, c->ah);
     }
-    if (a.k > 0.0f) launch_bulk_decode_frames(c, a, (unsigned)n, bulk_compact(c, 0), direct, c16, s);
+    if (a.k > 0.0f) launch_bulk_decode_frames(a, (unsigned)n, wpf, bulk_compact(c, 0), direct, c16, s);
     else if (direct) {
         if (c16) bpc_decode_kernel<false, kDecSmallPlanes, true, true><<<wgs, 64 * kBpcDecWgWaves, 0, s>>>(a);
         else bpc_decode_kernel<false, kDecSmallPlanes, true><<<wgs, 64 * kBpcDecWgWaves, 0, s>>>(a);
@@ -1398,16 +1457,30 @@ int picsong_decode_frames(picsong_ctx *c, int n, const uint16_t *d_streams, size
     // ---- inverse transform, pixels out of the finest level where its vector kernel applies
     if ((rc = run_inverse(c, plan, s, (unsigned)n))) return rc;
     if (fused) return PICSONG_OK;
-    const size_t n4 = c->P / 4;
+    const size_t n4 = px / 4;
     const int off = 1 << (c->p.bit_depth - 1);
     const int grid = (int)((n4 + 255) / 256 > 8192 ? 8192 : (n4 + 255) / 256);
     for (int f = 0; f < n; f++) {
-        const void *img = (const char *)c->b_coef + ((size_t)f * (c->P + c->extra) + c->extra) * 4;
+        // (level `reduce`'s samples of frame f: c->extra elements into its work buffer when reduce = 0)
+        const void *img = (const char *)plan.back().a.dst + (size_t)f * (c->P + c->extra) * 4;
         if (c->p.lossy) clamp_to_u8_f32_kernel<<<grid, 256, 0, s>>>((const float *)img, d_frames_out + (size_t)f * frame_stride, n4, (float)off);
         else clamp_to_u8_i32_kernel<<<grid, 256, 0, s>>>((const int32_t *)img, d_frames_out + (size_t)f * frame_stride, n4, off);
     }
     HIP_TRY(hipGetLastError());
     return PICSONG_OK;
+}
+
+int picsong_decode_frames(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_frames_out,
+                          size_t frame_stride, void *stream)
+{
+    return decode_frames_impl(c, n, d_streams, stream_stride, d_frames_out, frame_stride, stream, 0, "decode_frames");
+}
+
+int picsong_decode_frames_reduced(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                  uint8_t *d_frames_out, size_t frame_stride, void *stream)
+{
+    return decode_frames_impl(c, n, d_streams, stream_stride, d_frames_out, frame_stride, stream, reduce,
+                              "decode_frames_reduced");
 }
 
 int picsong_copy_last_totals(picsong_ctx *c, void *stream, int n, int32_t *d_totals)
@@ -1441,18 +1514,23 @@ int picsong_rgb_forward(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, 
     return PICSONG_OK;
 }
 
-int picsong_rgb_inverse(picsong_ctx *c, const void *d_c0, const void *d_c1, const void *d_c2, uint8_t *d_r,
-                        uint8_t *d_g, uint8_t *d_b, void *stream)
+// the inverse colour transform of n4 * 4 samples (picsong_rgb_inverse: the padded frame's P)
+static int rgb_inverse_n(picsong_ctx *c, const void *d_c0, const void *d_c1, const void *d_c2, uint8_t *d_r, uint8_t *d_g,
+                         uint8_t *d_b, size_t n4, hipStream_t s)
 {
-    if (!c || !d_r || !d_g || !d_b || !d_c0 || !d_c1 || !d_c2) return fail(PICSONG_ERR_ARG, "rgb_inverse: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n4 = c->P / 4;
     const int off = 1 << (c->p.bit_depth - 1);
     const int grid = (int)((n4 + 255) / 256 > 8192 ? 8192 : (n4 + 255) / 256);
     if (c->p.lossy) rgb_inverse_kernel<float><<<grid, 256, 0, s>>>((const float *)d_c0, (const float *)d_c1, (const float *)d_c2, d_r, d_g, d_b, n4, off);
     else rgb_inverse_kernel<int32_t><<<grid, 256, 0, s>>>((const int32_t *)d_c0, (const int32_t *)d_c1, (const int32_t *)d_c2, d_r, d_g, d_b, n4, off);
     HIP_TRY(hipGetLastError());
     return PICSONG_OK;
+}
+
+int picsong_rgb_inverse(picsong_ctx *c, const void *d_c0, const void *d_c1, const void *d_c2, uint8_t *d_r,
+                        uint8_t *d_g, uint8_t *d_b, void *stream)
+{
+    if (!c || !d_r || !d_g || !d_b || !d_c0 || !d_c1 || !d_c2) return fail(PICSONG_ERR_ARG, "rgb_inverse: null argument");
+    return rgb_inverse_n(c, d_c0, d_c1, d_c2, d_r, d_g, d_b, c->P / 4, (hipStream_t)stream);
 }
 
 int picsong_encode_plane(picsong_ctx *c, const void *d_plane, int comp, int with_header, uint16_t *d_stream, void *stream)
@@ -1581,17 +1659,24 @@ int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *
     return PICSONG_OK;
 }
 
-int picsong_decode_rgb_frame(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_r, uint8_t *d_g,
-                             uint8_t *d_b, void *stream)
+// picsong_decode_rgb_frame (reduce = 0) and picsong_decode_rgb_frame_reduced: the three components' level `reduce`,
+// then the inverse colour transform over its (AW >> reduce) x (AH >> reduce) samples
+static int decode_rgb_impl(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_r, uint8_t *d_g,
+                           uint8_t *d_b, void *stream, int reduce, const char *who)
 {
-    if (!c || !d_streams || !d_r || !d_g || !d_b) return fail(PICSONG_ERR_ARG, "decode_rgb_frame: null argument");
-    if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "decode_rgb_frame: the context is not an RGB one");
-    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "decode_rgb_frame: -cp 3 decodes its planes one by one (picsong_decode_plane)");
-    if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah)) return fail(PICSONG_ERR_ARG, "decode_rgb_frame: stream stride smaller than a worst-case codestream");
+    if (!c || !d_streams || !d_r || !d_g || !d_b) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: the context is not an RGB one", who);
+    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 3 decodes its planes one by one (picsong_decode_plane)", who);
+    if (!reduce_ok(c->p.wl, reduce))
+        return fail(PICSONG_ERR_ARG, "%s: reduce %d outside 0..%d (wl - 1)", who, reduce, c->p.wl - 1);
+    if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah)) return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
     HIP_TRY(hipSetDevice(c->device));
     BpcArgs a;
     int rc = bpc_args_rgb(c, a);
     if (rc) return rc;
+    // (k = 0: a component's waves are whole workgroups, as bpc_args_rgb lays them; -k > 0: exactly its waves)
+    const int wpf = decode_rect(c, a, reduce);
+    if (reduce > 0) a.waves_per_frame = (wpf + kBpcDecWgWaves - 1) / kBpcDecWgWaves * kBpcDecWgWaves;
     if ((rc = ensure_batch(c, 3))) return rc;
     if ((rc = ensure_coef_i(c, 3))) return rc;
     c->last_batch = -1;
@@ -1610,7 +1695,8 @@ int picsong_decode_rgb_frame(picsong_ctx *c, const uint16_t *d_streams, size_t s
     }
     // (16-bit coefficients between the decoder and the synthesis where the context's magnitudes are bounded: the
     // plan says whether this call's arrays take the vector kernels)
-    const std::vector<InvLaunch> plan = inverse_plan(c, c->b_coef_i, c->b_coef, nullptr, nullptr, 3u, 0, c->c16_dec && direct, true);
+    const std::vector<InvLaunch> plan = inverse_plan(c, c->b_coef_i, c->b_coef, nullptr, nullptr, 3u, 0,
+                                                     dec_c16_reduced(c, reduce) && direct, true, reduce);
     const bool c16 = plan_inv_is_c16(plan);
     a.coeffs_out = c->b_coef_i; a.staging = c->b_staging; a.sizes = c->b_sizes; a.plane_scratch = c->b_plane_scratch;
     a.coef_z = (unsigned long long)c->P * (c16 ? 2ull : 4ull);
@@ -1620,7 +1706,7 @@ int picsong_decode_rgb_frame(picsong_ctx *c, const uint16_t *d_streams, size_t s
         a.cw16_max = (uint32_t)picsong_max_stream_shorts(c->aw, c->ah);
     }
     if (a.k > 0.0f) {
-        launch_bulk_decode_frames(c, a, 3u, bulk_compact(c, 0) && bulk_compact(c, 1) && bulk_compact(c, 2), direct, c16, s);
+        launch_bulk_decode_frames(a, 3u, wpf, bulk_compact(c, 0) && bulk_compact(c, 1) && bulk_compact(c, 2), direct, c16, s);
     } else if (direct) {
         if (c16) bpc_decode_kernel<false, kDecSmallPlanes, true, true><<<wgs3, 64 * kBpcDecWgWaves, 0, s>>>(a);
         else bpc_decode_kernel<false, kDecSmallPlanes, true><<<wgs3, 64 * kBpcDecWgWaves, 0, s>>>(a);
@@ -1671,9 +1757,22 @@ int picsong_decode_rgb_frame(picsong_ctx *c, const uint16_t *d_streams, size_t s
         return PICSONG_OK;
     }
     if ((rc = run_inverse(c, plan, s, 3u))) return rc;
-    const char *img = (const char *)c->b_coef + c->extra * 4;
+    const char *img = (const char *)plan.back().a.dst;      // (level `reduce`: c->extra elements in when reduce = 0)
     const size_t z = (c->P + c->extra) * 4;
-    return picsong_rgb_inverse(c, img, img + z, img + 2 * z, d_r, d_g, d_b, stream);
+    return rgb_inverse_n(c, img, img + z, img + 2 * z, d_r, d_g, d_b,
+                         (size_t)(c->aw >> reduce) * (size_t)(c->ah >> reduce) / 4, s);
+}
+
+int picsong_decode_rgb_frame(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_r, uint8_t *d_g,
+                             uint8_t *d_b, void *stream)
+{
+    return decode_rgb_impl(c, d_streams, stream_stride, d_r, d_g, d_b, stream, 0, "decode_rgb_frame");
+}
+
+int picsong_decode_rgb_frame_reduced(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, int reduce, uint8_t *d_r,
+                                     uint8_t *d_g, uint8_t *d_b, void *stream)
+{
+    return decode_rgb_impl(c, d_streams, stream_stride, d_r, d_g, d_b, stream, reduce, "decode_rgb_frame_reduced");
 }
 
 int picsong_pad_frame_host(const uint8_t *in, int w, int h, uint8_t *out, int aw, int ah)

@@ -46,6 +46,7 @@ struct Options {
     std::string devices;                        // --devices a,b,..: explicit device list (a device may repeat)
     float qs = 1.0f, k = 0.0f;
     std::string metrics;
+    int reduce = 0;                             // -reduce r: decode the image at 1/2^r of its size
 };
 
 [[noreturn]] void die(const std::string &msg)
@@ -98,7 +99,8 @@ void help()
         "                     (--devices a,b,c names them explicitly); every device copies its codestreams to the\n"
         "                     writer's pinned ring over its own host link, the output file is the 1-GPU file\n"
         " -framesPerLaunch B  frames coded / decoded per launch (default: 4 up to 4K frames, 1 above)\n"
-        " --lut-fill V        value of LUT entries the loader never writes (default 0)\n";
+        " --lut-fill V        value of LUT entries the loader never writes (default 0)\n"
+        " -reduce r           decoding: the image at 1/2^r of its size, r in 0..wl-1 (resolution reduction)\n";
 }
 
 template <typename T> void echo(const char *flag, const T &v)
@@ -117,6 +119,8 @@ Options parse(const Args &a)
     geti("-numberOfStreams", o.streams); geti("-video", o.video);
     geti("-device", o.device); geti("--lut-fill", o.lut_fill); gets("--metrics", o.metrics);
     geti("-gpus", o.gpus); geti("-framesPerLaunch", o.frames_per_launch); gets("--devices", o.devices);
+    geti("-reduce", o.reduce);
+    if (a.has("-reduce") && o.cd != 1) die("Incorrect parameters. -reduce applies to decoding (-cd 1) only.");
     if (o.cd == 0) {
         geti("-xSize", o.x); geti("-ySize", o.y); geti("-cbWidth", o.cb_width); geti("-cbHeight", o.cb_height);
         geti("-wl", o.wl); geti("-cp", o.cp); geti("-endianess", o.endianess); geti("-bps", o.bps);
@@ -210,7 +214,11 @@ void write_metrics(const Options &o, const char *mode, long frames, double secon
     m << "{\"mode\": \"" << mode << "\", \"frames\": " << frames << ", \"seconds\": " << seconds
       << ", \"mpixels_per_s\": " << (seconds > 0 ? (double)frames * o.x * o.y / seconds / 1e6 : 0.0)
       << ", \"dwt_ms\": " << dwt << ", \"bpc_ms\": " << bpc << ", \"pack_ms\": " << pack
-      << ", \"stream_shorts\": " << shorts << "}\n";
+      << ", \"stream_shorts\": " << shorts;
+    // decoding: the size of the images written (1/2^reduce of the frame's, -reduce)
+    if (std::string(mode).compare(0, 6, "decode") == 0)
+        m << ", \"width\": " << o.x << ", \"height\": " << o.y << ", \"reduce\": " << o.reduce;
+    m << "}\n";
 }
 
 // ---- RGB coding (CodingEngine::runImage / runVideo, RGB branches: CodingEngine.cu:598-633,676-712,
@@ -577,8 +585,12 @@ void write_pgm(const std::string &path, const uint8_t *pix, int w, int h, int bi
 // 736-769,868-940): three component streams per frame -> Decode + DWTDecode each -> inverse colour
 // transform (offset + clamp fused) -> planar R, G, B planes of W*H bytes appended to <o>
 // (IOManager::writeDecodedFrameUChar / writeDecodedFrameComponentUChar, IO/IOManager.ipp:236-262).
+// What a decode writes (-reduce r, picsong_reduced_dims): w x h visible pixels a frame of rows pw bytes apart, out of a
+// padded image of pw x ph; r = 0: the frame itself (W x H of AW x AH).
+struct OutDims { int r, w, h, pw, ph; };
+
 int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, std::ifstream &in,
-                   const std::vector<long> &shorts, long nframes, int aw, int ah)
+                   const std::vector<long> &shorts, long nframes, int aw, int ah, const OutDims &od)
 {
     const size_t P = (size_t)aw * ah, max_shorts = picsong_max_stream_shorts(aw, ah);
     const size_t extra = picsong_dwt_extra(aw, ah, p.wl);
@@ -592,7 +604,7 @@ int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, 
     HIPCK(hipMalloc(&d_in, max_shorts * 2 * (batched ? 3 : 1)));
     HIPCK(hipHostMalloc(&h_pix, P));
     for (int c = 0; c < 3; c++) { HIPCK(hipMalloc(&d_pix[c], P)); HIPCK(hipMalloc(&d_plane[c], (P + extra) * 4)); }
-    std::vector<uint8_t> crop((size_t)p.width * p.height);
+    std::vector<uint8_t> crop((size_t)od.w * od.h);
     { std::ofstream trunc(o.output, std::ios::binary | std::ios::trunc); }
     auto t0 = std::chrono::steady_clock::now();
     size_t pos = 0;
@@ -609,16 +621,18 @@ int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, 
             if (!batched) CK(picsong_decode_plane(ctx, d_in, c, d_plane[c], s));
             HIPCK(hipStreamSynchronize(s));          // h_in (and, plane by plane, d_in) are reused for the next component
         }
-        if (batched)
+        if (od.r > 0)
+            CK(picsong_decode_rgb_frame_reduced(ctx, d_in, max_shorts, od.r, d_pix[0], d_pix[1], d_pix[2], s));
+        else if (batched)
             CK(picsong_decode_rgb_frame(ctx, d_in, max_shorts, d_pix[0], d_pix[1], d_pix[2], s));
         else
             CK(picsong_rgb_inverse(ctx, d_plane[0] + extra * 4, d_plane[1] + extra * 4, d_plane[2] + extra * 4, d_pix[0],
                                    d_pix[1], d_pix[2], s));
         std::ofstream out(o.output, std::ios::binary | std::ios::app);
         for (int c = 0; c < 3; c++) {
-            HIPCK(hipMemcpyAsync(h_pix, d_pix[c], P, hipMemcpyDeviceToHost, s));
+            HIPCK(hipMemcpyAsync(h_pix, d_pix[c], (size_t)od.pw * od.ph, hipMemcpyDeviceToHost, s));
             HIPCK(hipStreamSynchronize(s));
-            for (int y = 0; y < p.height; y++) memcpy(&crop[(size_t)y * p.width], h_pix + (size_t)y * aw, (size_t)p.width);
+            for (int y = 0; y < od.h; y++) memcpy(&crop[(size_t)y * od.w], h_pix + (size_t)y * od.pw, (size_t)od.w);
             out.write(reinterpret_cast<const char *>(crop.data()), (std::streamsize)crop.size());
         }
     }
@@ -637,15 +651,17 @@ int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, 
 // thread launches H2D + decode + D2H on the slot's stream, two writer threads wait for their slot's
 // stream, crop and pwrite the frame at f * W * H (IOManager::writeDecodedFrame IO/IOManager.ipp:214-231
 // appends raw W*H bytes per frame).
-int run_decode_video(const Options &o, const picsong_params &p, const std::vector<long> &frame_shorts, long nframes)
+int run_decode_video(const Options &o, const picsong_params &p, const std::vector<long> &frame_shorts, long nframes,
+                     const OutDims &od)
 {
     const int aw = picsong_pad_dim(p.width), ah = picsong_pad_dim(p.height);
-    const size_t P = (size_t)aw * ah, max_shorts = picsong_max_stream_shorts(aw, ah);
-    const size_t frame_bytes = (size_t)p.width * p.height;
+    const size_t max_shorts = picsong_max_stream_shorts(aw, ah);
+    // (P: the bytes of one decoded, padded frame -- of the reduced image with -reduce)
+    const size_t P = (size_t)od.pw * od.ph, frame_bytes = (size_t)od.w * od.h;
     const int nslots = (o.streams < 3 ? 3 : o.streams) + 3;
     // groups of B consecutive frames per launch (picsong_decode_frames), as the encoder's video engine codes them:
     // a 4K frame alone is one decoder wave per SIMD
-    int B = o.frames_per_launch > 0 ? o.frames_per_launch : (P <= (size_t)3840 * 2176 ? 4 : 1);
+    int B = o.frames_per_launch > 0 ? o.frames_per_launch : ((size_t)aw * ah <= (size_t)3840 * 2176 ? 4 : 1);
     if (p.cp == 3) B = 1;
     if (B > 16) B = 16;
     if ((long)B > nframes) B = (int)nframes;
@@ -667,7 +683,7 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
         HIPCK(hipMalloc(&k.d_in, max_shorts * 2 * B));
         HIPCK(hipHostMalloc(&k.h_pix, P * B));
         HIPCK(hipMalloc(&k.d_pix, P * B));
-        if (aw != p.width) k.crop.resize(frame_bytes);
+        if (od.pw != od.w) k.crop.resize(frame_bytes);
         k.expect = i;
     }
     std::vector<size_t> in_off((size_t)nframes + 1, 0);
@@ -724,8 +740,8 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
             if (hipStreamSynchronize(k.stream) != hipSuccess) err = "HIP error while decoding a frame";
             for (long f = g * B; err.empty() && f < nframes && f < (g + 1) * B; f++) {
                 const uint8_t *pix = k.h_pix + (size_t)(f - g * B) * P, *src = pix;
-                if (aw != p.width) {
-                    for (int y = 0; y < p.height; y++) memcpy(&k.crop[(size_t)y * p.width], pix + (size_t)y * aw, (size_t)p.width);
+                if (od.pw != od.w) {
+                    for (int y = 0; y < od.h; y++) memcpy(&k.crop[(size_t)y * od.w], pix + (size_t)y * od.pw, (size_t)od.w);
                     src = k.crop.data();
                 }
                 size_t left = frame_bytes, done = 0;
@@ -764,7 +780,9 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
                                (size_t)frame_shorts[(size_t)(g * B + b)] * 2, hipMemcpyHostToDevice, k.stream) != hipSuccess)
                 err = "HIP error in the codestream upload";
         if (!err.empty()) { }
-        else if (picsong_decode_frames(k.ctx, n, k.d_in, max_shorts, k.d_pix, P, k.stream) != PICSONG_OK) err = picsong_last_error();
+        else if ((od.r > 0 ? picsong_decode_frames_reduced(k.ctx, n, k.d_in, max_shorts, od.r, k.d_pix, P, k.stream)
+                           : picsong_decode_frames(k.ctx, n, k.d_in, max_shorts, k.d_pix, P, k.stream)) != PICSONG_OK)
+            err = picsong_last_error();
         else if (hipMemcpyAsync(k.h_pix, k.d_pix, P * (size_t)n, hipMemcpyDeviceToHost, k.stream) != hipSuccess)
             err = "HIP error in the frame download";
         std::lock_guard<std::mutex> lk(mu);
@@ -779,7 +797,7 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::cout << "The time spent with the app without considering allocation periods and I/O is: " << sec << std::endl;
     Options mo = o;
-    mo.x = p.width; mo.y = p.height;
+    mo.x = od.w; mo.y = od.h;
     write_metrics(mo, "decode", nframes, sec, 0, 0, 0, (long)in_off[(size_t)nframes]);
     for (auto &k : sl) {
         picsong_ctx_destroy(k.ctx);
@@ -801,6 +819,9 @@ int run_decode(const Options &o)
     CK(picsong_header_unpack(hdr, &p));
     if (!((p.components == 1 && !p.is_rgb) || (p.components == 3 && p.is_rgb)))
         die("This stream uses a component layout not built here.");
+    if (o.reduce < 0 || o.reduce > p.wl - 1)
+        die("Incorrect parameters. -reduce must lie in 0.." + std::to_string(p.wl - 1) + " (the stream has " +
+            std::to_string(p.wl) + " wavelet levels).");
     const long nframes = o.video ? p.frames : 1;
     std::vector<long> frame_shorts;
     if (o.video || p.is_rgb) {
@@ -821,13 +842,15 @@ int run_decode(const Options &o)
     load_lut(ctx, lo, p.wl, p.components, p.k, p.cp);
     int aw, ah, ncb;
     CK(picsong_ctx_padded_dims(ctx, &aw, &ah, &ncb));
-    if (p.is_rgb) return run_decode_rgb(o, p, ctx, in, frame_shorts, nframes, aw, ah);
+    OutDims od = { o.reduce, 0, 0, 0, 0 };
+    CK(picsong_reduced_dims(ctx, o.reduce, &od.w, &od.h, &od.pw, &od.ph, &ncb));
+    if (p.is_rgb) return run_decode_rgb(o, p, ctx, in, frame_shorts, nframes, aw, ah, od);
     if (o.video) {
         picsong_ctx_destroy(ctx);
         in.close();
-        return run_decode_video(lo, p, frame_shorts, nframes);
+        return run_decode_video(lo, p, frame_shorts, nframes, od);
     }
-    const size_t P = (size_t)aw * ah, max_shorts = picsong_max_stream_shorts(aw, ah);
+    const size_t P = (size_t)od.pw * od.ph, max_shorts = picsong_max_stream_shorts(aw, ah);
     hipStream_t s;
     HIPCK(hipStreamCreate(&s));
     uint16_t *h_in, *d_in;
@@ -836,7 +859,7 @@ int run_decode(const Options &o)
     HIPCK(hipMalloc(&d_in, max_shorts * 2));
     HIPCK(hipHostMalloc(&h_pix, P));
     HIPCK(hipMalloc(&d_pix, P));
-    std::vector<uint8_t> crop((size_t)p.width * p.height);
+    std::vector<uint8_t> crop((size_t)od.w * od.h);
     if (o.video) { std::ofstream trunc(o.output, std::ios::binary | std::ios::app); }
     auto t0 = std::chrono::steady_clock::now();
     size_t pos = 0;
@@ -849,22 +872,23 @@ int run_decode(const Options &o)
         if ((size_t)in.gcount() != n * 2) die("Input file is shorter than its _SIZE sidecar says.");
         pos += n;
         HIPCK(hipMemcpyAsync(d_in, h_in, n * 2, hipMemcpyHostToDevice, s));
-        CK(picsong_decode_frame(ctx, d_in, d_pix, s));
+        if (od.r > 0) CK(picsong_decode_frame_reduced(ctx, d_in, od.r, d_pix, s));
+        else CK(picsong_decode_frame(ctx, d_in, d_pix, s));
         HIPCK(hipMemcpyAsync(h_pix, d_pix, P, hipMemcpyDeviceToHost, s));
         HIPCK(hipStreamSynchronize(s));
-        for (int y = 0; y < p.height; y++) memcpy(&crop[(size_t)y * p.width], h_pix + (size_t)y * aw, (size_t)p.width);
+        for (int y = 0; y < od.h; y++) memcpy(&crop[(size_t)y * od.w], h_pix + (size_t)y * od.pw, (size_t)od.w);
         if (o.video) {
             // IOManager::writeDecodedFrame IO/IOManager.ipp:214-231: raw W*H bytes appended
             std::ofstream out(o.output, std::ios::binary | std::ios::app);
             out.write(reinterpret_cast<const char *>(crop.data()), (std::streamsize)crop.size());
         } else {
-            write_pgm(o.output, crop.data(), p.width, p.height, p.bit_depth);
+            write_pgm(o.output, crop.data(), od.w, od.h, p.bit_depth);
         }
     }
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::cout << "The time spent with the app without considering allocation periods and I/O is: " << sec << std::endl;
     Options mo = o;
-    mo.x = p.width; mo.y = p.height;
+    mo.x = od.w; mo.y = od.h;
     write_metrics(mo, "decode", nframes, sec, 0, 0, 0, (long)pos);
     picsong_ctx_destroy(ctx);
     (void)hipStreamDestroy(s);

@@ -44,6 +44,8 @@ EXPORTS = [
     "picsong_encode_frames", "picsong_last_totals", "picsong_selftest_lds_order",
     "picsong_dwt_forward_band", "picsong_dwt_forward_tail", "picsong_encode_stripe_coded", "picsong_lut_load_cp",
     "picsong_copy_last_totals", "picsong_decode_frames", "picsong_encode_rgb_frame", "picsong_decode_rgb_frame",
+    "picsong_reduced_dims", "picsong_decode_frame_reduced", "picsong_decode_frames_reduced",
+    "picsong_decode_rgb_frame_reduced",
 ]
 
 _lib = None
@@ -115,6 +117,11 @@ def load():
     if hasattr(L, "picsong_encode_rgb_frame"):
         L.picsong_encode_rgb_frame.argtypes = [vp, vp, vp, vp, i, vp, C.c_size_t, vp]
         L.picsong_decode_rgb_frame.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp]
+    if hasattr(L, "picsong_reduced_dims"):
+        L.picsong_reduced_dims.argtypes = [vp, i] + [C.POINTER(i)] * 5
+        L.picsong_decode_frame_reduced.argtypes = [vp, vp, i, vp, vp]
+        L.picsong_decode_frames_reduced.argtypes = [vp, i, vp, C.c_size_t, i, vp, C.c_size_t, vp]
+        L.picsong_decode_rgb_frame_reduced.argtypes = [vp, vp, C.c_size_t, i, vp, vp, vp, vp]
     if hasattr(L, "picsong_lut_load_cp"):
         L.picsong_lut_load_cp.argtypes = [C.c_char_p, i, i, i, i, C.POINTER(LutInfo), vp, C.c_size_t]
     if hasattr(L, "picsong_dwt_forward_band"):
@@ -426,3 +433,34 @@ class Codec:
         out = self.torch.empty(self.P, dtype=self.torch.uint8, device=self.dev)
         _check(self.L.picsong_decode_frame(self.h, self._p(stream), self._p(out), self._stream()))
         return out.view(self.ah, self.aw)
+
+    # ---- reduced-resolution decode (1/2^r of the frame's size; r = 0 is the full decode) ----
+    def reduced_dims(self, r):
+        """(visible width, height, padded width, height, codeblocks decoded) of the image at 1/2^r."""
+        d = [C.c_int() for _ in range(5)]
+        _check(self.L.picsong_reduced_dims(self.h, r, *[C.byref(x) for x in d]))
+        return tuple(x.value for x in d)
+
+    def decode_frame_reduced(self, stream, r):
+        """The padded reduced image, uint8 (AH >> r, AW >> r)."""
+        out = self.torch.empty((self.ah >> r, self.aw >> r), dtype=self.torch.uint8, device=self.dev)
+        _check(self.L.picsong_decode_frame_reduced(self.h, self._p(stream), r, self._p(out), self._stream()))
+        return out
+
+    def decode_frames_reduced(self, streams, r, out=None):
+        """streams: int16 [n, >= max_stream_shorts()]; returns uint8 [n, AH >> r, AW >> r] (or fills `out`, whose
+        frames may lie further apart)."""
+        n = streams.shape[0]
+        assert streams.stride(-1) == 1
+        if out is None:
+            out = self.torch.empty((n, self.ah >> r, self.aw >> r), dtype=self.torch.uint8, device=self.dev)
+        _check(self.L.picsong_decode_frames_reduced(self.h, n, self._p(streams), streams.stride(0), r, self._p(out),
+                                                    out.stride(0), self._stream()))
+        return out
+
+    def decode_rgb_frame_reduced(self, streams, r):
+        """streams: int16 [3, >= max_stream_shorts()]; returns the three reduced u8 planes (AH >> r, AW >> r)."""
+        outs = [self.torch.empty((self.ah >> r, self.aw >> r), dtype=self.torch.uint8, device=self.dev) for _ in range(3)]
+        _check(self.L.picsong_decode_rgb_frame_reduced(self.h, self._p(streams), streams.stride(0), r, self._p(outs[0]),
+                                                       self._p(outs[1]), self._p(outs[2]), self._stream()))
+        return outs

@@ -257,6 +257,32 @@ int picsong_encode_rgb_frame(picsong_ctx *ctx, const uint8_t *d_r, const uint8_t
 int picsong_decode_rgb_frame(picsong_ctx *ctx, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_r, uint8_t *d_g,
                              uint8_t *d_b, void *stream);
 
+/* ---- reduced-resolution decode (JPEG 2000's resolution reduction, OpenJPEG -r / Kakadu -reduce; the reference has no
+ *      counterpart): the image at 1/2^reduce of the frame's size, for thumbnails, previews and editing proxies.  It is
+ *      LL_reduce, the intermediate the full synthesis makes on its way to level 0, level-shifted and clamped as the
+ *      full decode's pixels are (5/3: clamp(v + 128); 9/7: rint(v + 128 + 0.01), clamped) -- the low-pass filters have
+ *      DC gain 1.  Only the codeblocks that meet the corner [0, AW >> reduce) x [0, AH >> reduce) of the Mallat array
+ *      (the subbands of levels reduce + 1 .. wl and LL_wl) are read and decoded, and only the synthesis levels
+ *      wl - 1 .. reduce run.  reduce = 0 is the full decode, byte-identical to the calls above; reduce = wl (the coded
+ *      LL band itself) is refused.
+ *      picsong_reduced_dims: rw x rh = ceil(W / 2^reduce) x ceil(H / 2^reduce), the visible part; paw x pah =
+ *      (AW >> reduce) x (AH >> reduce), what the calls write; n_codeblocks = ceil(paw / 64) * ceil(pah / 64), the
+ *      codeblocks a call decodes (per frame, per component).
+ *      The calls write exactly paw * pah bytes a frame (a plane), row stride paw, and no byte beyond them.  Refused
+ *      (PICSONG_ERR_ARG, nothing launched): reduce outside 0..wl - 1, -cp 3 contexts, null pointers, and the stride
+ *      checks of the full-size calls (frame_stride >= paw * pah).  Alignment as picsong_decode_frame: a 4-byte
+ *      aligned output takes the fused pixel store, any other pointer a separate clamp over paw * pah samples; same
+ *      bytes.  picsong_range_flag covers the codeblocks a call decodes (and every length of the stream).
+ *      picsong_decode_frames_reduced: the batched mirror of picsong_decode_frames (n = 1..64, one launch per stage;
+ *      byte-identical to n calls of picsong_decode_frame_reduced).  picsong_decode_rgb_frame_reduced: the mirror of
+ *      picsong_decode_rgb_frame, the inverse RCT / ICT applied to the three components' LL_reduce. ---- */
+int picsong_reduced_dims(const picsong_ctx *ctx, int reduce, int *rw, int *rh, int *paw, int *pah, int *n_codeblocks);
+int picsong_decode_frame_reduced(picsong_ctx *ctx, const uint16_t *d_stream, int reduce, uint8_t *d_out, void *stream);
+int picsong_decode_frames_reduced(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                  uint8_t *d_frames_out, size_t frame_stride, void *stream);
+int picsong_decode_rgb_frame_reduced(picsong_ctx *ctx, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                     uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, void *stream);
+
 /* ---- intra-frame sharding (BASELINE config 5): codeblocks are independent
  *      (correctCBBorders zeroes outside neighbours, BPC/BPCEngine.cu:465-484), so a rank can code
  *      the stripe [cb_begin, cb_begin + cb_count) of the frame's raster-ordered codeblocks.  The

@@ -74,3 +74,37 @@ for a in sys.argv[1:]:
             dt = (time.perf_counter() - t0) / (ncalls * nb)
         okb = all(bool(torch.equal(o[j], frame.view(c.ah, c.aw))) for o in outs for j in range(nb)) if not lossy else None
         print(f"decode {nb} frames per call over {len(cs)} streams: {dt * 1e3:.3f} ms/frame = {W * H / dt / 1e6:.0f} Mpixel/s, roundtrip_ok={okb}")
+
+for a in sys.argv[1:]:
+    if a.startswith("--reduce="):
+        # the image at 1/2^r of the frame's size (picsong_decode_frame_reduced / _frames_reduced): a lone frame, then
+        # 4-frame batches alternating over the streams; the rate counts the full frame's pixels
+        r = int(a.split("=")[1])
+        for _ in range(3):
+            d = c.decode_frame_reduced(s, r)
+        torch.cuda.synchronize()
+        n = 20
+        t0 = time.perf_counter()
+        for _ in range(n):
+            d = c.decode_frame_reduced(s, r)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / n
+        print(f"decode reduce={r} lone {W}x{H} -> {c.aw >> r}x{c.ah >> r}: {dt * 1e3:.3f} ms/frame = {W * H / dt / 1e6:.0f} Mpixel/s")
+        nb = 4
+        sb = torch.stack([torch.nn.functional.pad(s, (0, c.max_stream_shorts() - s.numel())) for _ in range(nb)])
+        cs = [pa.Codec(W, H, wl=wl, lossy=lossy, qs=qs, lut_folder=lut) for _ in range(max(nstreams, 1))]
+        sts = [torch.cuda.Stream() for _ in cs]
+        outs = [torch.empty((nb, c.ah >> r, c.aw >> r), dtype=torch.uint8, device="cuda") for _ in cs]
+        for rep in range(2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ncalls = 15
+            for i in range(ncalls):
+                k = i % len(cs)
+                with torch.cuda.stream(sts[k]):
+                    cs[k].decode_frames_reduced(sb, r, outs[k])
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0) / (ncalls * nb)
+        okr = all(bool(torch.equal(o[j], d)) for o in outs for j in range(nb))
+        print(f"decode reduce={r} {nb} frames per call over {len(cs)} streams: {dt * 1e3:.3f} ms/frame = "
+              f"{W * H / dt / 1e6:.0f} Mpixel/s, batch_equals_lone={okr}")
