@@ -52,6 +52,8 @@ struct LutGeo {
     int nRef, nSig, nSign;         // section sizes; table = [ref | sig | sign]
 };
 
+constexpr int kBpcWinRects = 22;        // window calls: 3 (wl - r) + 1 rectangles at most (wl <= 7)
+
 struct BpcArgs {
     const void *coeffs_in;         // encoder: Mallat T[AW*AH]
     int32_t *coeffs_out;           // decoder: Mallat int32[AW*AH]
@@ -98,6 +100,14 @@ struct BpcArgs {
     // ncx_r codeblock columns of the raster's rows, ncb_r codeblocks in row order -- index i of a frame's launch is
     // codeblock (i / ncx_r) * ncx + i % ncx_r; waves_per_frame counts the rectangle's waves.  0: every codeblock.
     int ncx_r, ncb_r;
+    // decoders, window calls (picsong_decode_frame_window): the launch decodes the codeblocks of win_n rectangles of the
+    // raster (launch_plan.hpp, window_plan), in row order, one after the other: rectangle i starts at codeblock column
+    // win_x[i], row win_y[i], is win_w[i] codeblocks wide, and index win_before[i] of a frame's launch is its first
+    // codeblock; win_before[win_n] = all of them.  A wave half's index picks its rectangle; a codeblock that an earlier
+    // rectangle holds is skipped (codeblocks that straddle subbands at coarse levels are listed twice).  ncx_r / ncb_r
+    // are the one-rectangle case of the same mapping.  waves_per_frame counts the table's waves.  0: not used.
+    int win_n;
+    int win_x[kBpcWinRects], win_y[kBpcWinRects], win_w[kBpcWinRects], win_before[kBpcWinRects + 1];
 };
 
 // ---- cross-lane helpers ---------------------------------------------------------------------
@@ -2010,12 +2020,34 @@ void bpc_decode_kernel(BpcArgs a)
             if (a.lut_c[0]) a.lut = f == 0 ? a.lut_c[0] : (f == 1 ? a.lut_c[1] : a.lut_c[2]);
         }
     }
-    // (each half maps on its own: with an odd ncx_r a wave's two codeblocks may lie in two rows)
+    // (each half maps on its own: with an odd rectangle width a wave's two codeblocks may lie in two rows or rectangles)
     int cb = a.cb_base + 2 * wave + (int)half, cbx, cby;
     bool valid;
-    if (a.ncx_r > 0) {                                      // (a reduced launch starts at codeblock 0)
-        cby = cb / a.ncx_r; cbx = cb - cby * a.ncx_r;
-        valid = cb < a.ncb_r;
+    if (a.ncx_r > 0 || a.win_n > 0) {                       // (a reduced or window launch starts at codeblock 0)
+        // the half's rectangle: the last one that starts at or before its index (ncx_r: the corner, the only one).
+        // Constant indices only -- unrolled selects over the table keep the argument struct out of scratch memory.
+        int rx = 0, ry = 0, rw = a.ncx_r, rb = 0, total = a.ncb_r;
+        if (a.win_n > 0) {
+            total = a.win_before[0];
+#pragma unroll
+            for (int i = 0; i < kBpcWinRects; i++) {
+                const bool in = i < a.win_n && cb >= a.win_before[i];
+                rx = in ? a.win_x[i] : rx; ry = in ? a.win_y[i] : ry; rw = in ? a.win_w[i] : rw; rb = in ? a.win_before[i] : rb;
+                total = i + 1 == a.win_n ? a.win_before[i + 1] : total;
+            }
+        }
+        const int j = cb - rb;
+        cby = j / rw; cbx = j - cby * rw;
+        cbx += rx; cby += ry;
+        valid = cb < total;
+        if (a.win_n > 0) {
+#pragma unroll
+            for (int i = 0; i < kBpcWinRects; i++) {        // listed by an earlier rectangle: that one decodes it
+                const int dx = cbx - a.win_x[i], k = (cby - a.win_y[i]) * a.win_w[i] + dx;
+                const bool earlier = i < a.win_n && a.win_before[i] < rb;
+                if (earlier && dx >= 0 && dx < a.win_w[i] && k >= 0 && k < a.win_before[i + 1] - a.win_before[i]) valid = false;
+            }
+        }
         cb = cby * a.ncx + cbx;
     } else {
         valid = cb < a.nCB;

@@ -318,6 +318,85 @@ inline std::vector<InvLaunch> plan_dwt_inverse_reduced(const int32_t *d_in, void
     return v;
 }
 
+// ---- window decode (picsong_decode_frame_window and its mirrors; no reference counterpart).  The window R_r =
+// [x, x + w) x [y, y + h) of the 1/2^r image (LL_r) depends on a cone of the Mallat array.  Per synthesis level
+// l = r .. wl - 1 (level l outputs LL_l, W_l x H_l = (AW >> l) x (AH >> l)), the rectangle R_l of LL_l needs the
+// rectangle S_l of level l's subband coordinates (W_l / 2 x H_l / 2), per axis, with [a, b) = R_l and K the subband size:
+//   5/3: [max(0, floor(a / 2) - 1), min(K, ceil(b / 2) + 1))    9/7: [max(0, floor(a / 2) - 2), min(K, ceil(b / 2) + 2))
+// -- the 2 and 4 lifting steps of the synthesis; the symmetric extension at the true edges stays inside the clamped
+// interval.  R_{l+1} = S_l.  Level l reads S_l in HL (+W_l / 2 in x), LH (+H_l / 2 in y) and HH (both), and level
+// wl - 1 reads S_{wl-1} itself as LL_wl.  The call decodes the 64 x 64 codeblocks of the Mallat raster that meet one of
+// those at most 3 (wl - r) + 1 rectangles, each codeblock once.  The whole padded reduced image's window is the reduced
+// call's corner (reduced_rect).
+struct IRect { int x0, y0, x1, y1; };                   // [x0, x1) x [y0, y1)
+constexpr int kWindowMaxRects = 22;                     // 3 (wl - r) + 1, wl <= 7
+struct WindowPlan {
+    int r, wl, lossy;
+    IRect R[8];                                         // R[l], l = r .. wl: LL_l's rectangle (R[r] the window, R[wl] = S[wl - 1])
+    IRect S[8];                                         // S[l], l = r .. wl - 1: level l's subband rectangle
+    int n_rects;
+    IRect cb[kWindowMaxRects];                          // the Mallat rectangles in codeblock units, level wl - 1 first
+    int n_cb;                                           // distinct codeblocks among them
+    int n_cb_listed;                                    // the rectangles' codeblocks, a codeblock counted once per rectangle
+};
+inline bool window_ok(int paw, int pah, int x, int y, int w, int h)
+{
+    return w >= 1 && h >= 1 && x >= 0 && y >= 0 && (long long)x + w <= paw && (long long)y + h <= pah;
+}
+inline WindowPlan window_plan(int aw, int ah, int wl, bool lossy, int r, int x, int y, int w, int h)
+{
+    WindowPlan p;
+    p.r = r; p.wl = wl; p.lossy = lossy ? 1 : 0;
+    const int e = lossy ? 2 : 1;
+    auto cone = [e](int a, int b, int K, int &lo, int &hi) {
+        lo = a / 2 - e; if (lo < 0) lo = 0;
+        hi = (b + 1) / 2 + e; if (hi > K) hi = K;
+    };
+    p.R[r] = { x, y, x + w, y + h };
+    for (int l = r; l < wl; l++) {
+        const int hW = (aw >> l) / 2, hH = (ah >> l) / 2;
+        IRect s;
+        cone(p.R[l].x0, p.R[l].x1, hW, s.x0, s.x1);
+        cone(p.R[l].y0, p.R[l].y1, hH, s.y0, s.y1);
+        p.S[l] = s; p.R[l + 1] = s;
+    }
+    p.n_rects = 0;
+    auto add = [&p](int x0, int y0, int x1, int y1) { p.cb[p.n_rects++] = { x0 / 64, y0 / 64, (x1 + 63) / 64, (y1 + 63) / 64 }; };
+    for (int l = wl - 1; l >= r; l--) {
+        const IRect &s = p.S[l];
+        const int hW = (aw >> l) / 2, hH = (ah >> l) / 2;
+        if (l == wl - 1) add(s.x0, s.y0, s.x1, s.y1);
+        add(s.x0 + hW, s.y0, s.x1 + hW, s.y1);
+        add(s.x0, s.y0 + hH, s.x1, s.y1 + hH);
+        add(s.x0 + hW, s.y0 + hH, s.x1 + hW, s.y1 + hH);
+    }
+    const int ncx = aw / 64;
+    std::vector<uint8_t> seen((size_t)ncx * (size_t)(ah / 64), 0);
+    p.n_cb = p.n_cb_listed = 0;
+    for (int i = 0; i < p.n_rects; i++) {
+        const IRect &q = p.cb[i];
+        p.n_cb_listed += (q.x1 - q.x0) * (q.y1 - q.y0);
+        for (int cy = q.y0; cy < q.y1; cy++)
+            for (int cx = q.x0; cx < q.x1; cx++) {
+                uint8_t &v = seen[(size_t)cy * ncx + cx];
+                p.n_cb += v ? 0 : 1;
+                v = 1;
+            }
+    }
+    return p;
+}
+// decoder waves of one frame of a window call: two listed codeblocks a wave (a codeblock an earlier rectangle holds
+// is listed again and skipped, BpcArgs::win_n)
+inline int window_waves(const WindowPlan &p) { return (p.n_cb_listed + 1) / 2; }
+// the most waves a window call of the context can need -- the whole image at r = 0 lists every rectangle at its
+// largest -- whole workgroups of `wg` waves: what the decoder's plane scratch holds for each frame
+inline int window_waves_cap(int aw, int ah, int wl, bool lossy, int ncb, int wg)
+{
+    int wv = window_waves(window_plan(aw, ah, wl, lossy, 0, 0, 0, aw, ah));
+    if (wv < (ncb + 1) / 2) wv = (ncb + 1) / 2;
+    return (wv + wg - 1) / wg * wg;
+}
+
 // May a decode context take the 16-bit coefficient form between its decoder and its synthesis?  The bound of coef16_ok
 // (an honest stream of such a context has no magnitude of 2^15 or more), the vector kernels on every level, at least
 // two levels (the coarsest level that also writes pixels has no C16 instantiation), and for 9/7 the verified

@@ -16,6 +16,7 @@
 #include "bpc_kernels.hpp"
 #include "dwt_kernels.hpp"
 #include "launch_plan.hpp"
+#include "window_kernels.hpp"
 #include "pack_kernels.hpp"
 
 using namespace picsong;
@@ -48,6 +49,7 @@ struct picsong_ctx {
     picsong_params p;
     int device;
     int aw, ah, ncb;
+    int dec_waves;        // waves of a frame's coder launch the plane scratch holds (dec_scratch_waves)
     size_t P, extra;
     bool fast_div;        // 9/7 synthesis: reciprocal form of the divisions verified for this qs
     bool c16;             // frame paths: coded coefficients travel as int16 between transform and coder (coef16_ok)
@@ -416,6 +418,7 @@ int picsong_ctx_create(const picsong_params *p, int device, picsong_ctx **out)
     c->ncb = (aw / PICSONG_CB) * (ah / PICSONG_CB);
     c->P = (size_t)aw * (size_t)ah;
     c->extra = picsong_dwt_extra(aw, ah, p->wl);
+    c->dec_waves = window_waves_cap(aw, ah, p->wl, p->lossy != 0, c->ncb, kBpcEncWgWaves);
     c->fast_div = p->lossy != 0 && dequant_fast_ok(p->qs, p->wl);
     // 8-bit samples: 128 after the level shift; 255 covers the chroma differences of the RGB path's RCT
     c->c16 = p->bit_depth == 8 && dwt_c16_geometry_ok(c->aw, c->ah, p->wl) &&
@@ -782,6 +785,9 @@ static bool bulk_compact(picsong_ctx *c, int comp)
     return c->bulk_compact[comp] == 1;
 }
 
+// the waves of a frame's coder launch the bit-plane scratch holds, whole workgroups: every codeblock pair, or the most a
+// window call lists (window_waves_cap: a codeblock that straddles subbands may be listed twice)
+static int dec_scratch_waves(const picsong_ctx *c) { return c->dec_waves; }
 // the coders' bit-plane scratch: kEncScratchDwordsPerWave per wave of a frame's launch (whole workgroups), allocated
 // at the first use
 static int ensure_plane_scratch(picsong_ctx *c)
@@ -790,7 +796,7 @@ static int ensure_plane_scratch(picsong_ctx *c)
     static_assert(kBpcEncWgWaves % kBpc3WgWaves == 0, "-cp 3 launches fit the same allocation");
     if (c->d_plane_scratch) return PICSONG_OK;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMalloc(&c->d_plane_scratch, (size_t)(((c->ncb + 1) / 2 + kBpcEncWgWaves - 1) / kBpcEncWgWaves * kBpcEncWgWaves) * kEncScratchDwordsPerWave * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&c->d_plane_scratch, (size_t)dec_scratch_waves(c) * kEncScratchDwordsPerWave * sizeof(uint32_t)));
     return PICSONG_OK;
 }
 
@@ -855,8 +861,10 @@ int picsong_bpc_encode(picsong_ctx *c, const void *d_coeffs, int32_t *d_staging,
 
 // The decoder's codeblocks in a call at 1/2^reduce resolution (reduced_rect; reduce = 0: every codeblock, the fields
 // stay 0): sets BpcArgs::ncx_r / ncb_r and returns the waves of one frame.
-static int decode_rect(const picsong_ctx *c, BpcArgs &a, int reduce)
+// win != nullptr (window calls): the plan's rectangle table instead (BpcArgs::win_n, window_bpc_table)
+static int decode_rect(const picsong_ctx *c, BpcArgs &a, int reduce, const WindowPlan *win = nullptr)
 {
+    if (win) return window_bpc_table(a, *win);
     if (reduce == 0) return (c->ncb + 1) / 2;
     const ReducedRect q = reduced_rect(c->aw, c->ah, reduce);
     a.ncx_r = q.ncx_r; a.ncb_r = q.ncx_r * q.ncy_r;
@@ -874,10 +882,11 @@ static bool dec_from_stream(const picsong_ctx *c)
 // d_stream16 != nullptr (k = 0, -cp 2): the codewords come from the packed stream, d_offsets the scan of its lengths
 // (scan_stream_kernel); d_staging is then not read
 // c16 (with d_stream16): the coefficients leave as an int16 Mallat array at d_coeffs (bpc_decode_kernel's C16 form)
-// reduce > 0: only the codeblocks of the 1/2^reduce image's corner (decode_rect)
+// reduce > 0: only the codeblocks of the 1/2^reduce image's corner (decode_rect); win: only a window's (decode_rect)
 static int bpc_decode_impl(picsong_ctx *c, const int32_t *d_staging, const int32_t *d_sizes, int32_t *d_coeffs,
                            hipStream_t s, int comp = 0, const uint16_t *d_stream16 = nullptr,
-                           const int32_t *d_offsets = nullptr, bool c16 = false, int reduce = 0)
+                           const int32_t *d_offsets = nullptr, bool c16 = false, int reduce = 0,
+                           const WindowPlan *win = nullptr)
 {
     BpcArgs a;
     int rc = bpc_args(c, a, comp);
@@ -887,7 +896,7 @@ static int bpc_decode_impl(picsong_ctx *c, const int32_t *d_staging, const int32
     a.sizes = const_cast<int32_t *>(d_sizes);
     if (int rc2 = ensure_plane_scratch(c)) return rc2;      // the decoder parks its finished planes there too
     a.plane_scratch = c->d_plane_scratch;
-    const unsigned waves = (unsigned)decode_rect(c, a, reduce);
+    const unsigned waves = (unsigned)decode_rect(c, a, reduce, win);
     if (c->p.cp == 3) {
         bpc3_kernel<true><<<(waves + kBpc3WgWaves - 1) / kBpc3WgWaves, 64 * kBpc3WgWaves, 0, s>>>(a);
         HIP_TRY(hipGetLastError());
@@ -932,17 +941,17 @@ static int bpc_decode_impl(picsong_ctx *c, const int32_t *d_staging, const int32
 static int unpack_impl(picsong_ctx *c, const uint16_t *d_stream, int32_t *d_staging, int32_t *d_sizes,
                        bool memset_staging, hipStream_t s);
 static int decode_stream_impl(picsong_ctx *c, const uint16_t *d_stream, int32_t *d_coeffs, hipStream_t s, int comp,
-                              bool c16 = false, int reduce = 0)
+                              bool c16 = false, int reduce = 0, const WindowPlan *win = nullptr)
 {
     int rc;
     if (!dec_from_stream(c)) {
         if (c16) return fail(PICSONG_ERR_ARG, "the 16-bit coefficient form decodes from the stream itself");
         if ((rc = unpack_impl(c, d_stream, c->d_staging, c->d_sizes, false, s))) return rc;
-        return bpc_decode_impl(c, c->d_staging, c->d_sizes, d_coeffs, s, comp, nullptr, nullptr, false, reduce);
+        return bpc_decode_impl(c, c->d_staging, c->d_sizes, d_coeffs, s, comp, nullptr, nullptr, false, reduce, win);
     }
     scan_stream_kernel<<<1, scan_threads(c->ncb), 0, s>>>(d_stream, c->ncb, c->d_sizes, c->d_offsets, c->d_total, c->d_flag, 0);
     HIP_TRY(hipGetLastError());
-    return bpc_decode_impl(c, nullptr, c->d_sizes, d_coeffs, s, comp, d_stream, c->d_offsets, c16, reduce);
+    return bpc_decode_impl(c, nullptr, c->d_sizes, d_coeffs, s, comp, d_stream, c->d_offsets, c16, reduce, win);
 }
 
 int picsong_bpc_decode(picsong_ctx *c, const int32_t *d_staging, const int32_t *d_sizes, int32_t *d_coeffs,
@@ -1148,11 +1157,41 @@ static int reduced_args_ok(const picsong_ctx *c, int reduce, const char *who)
     return PICSONG_OK;
 }
 
+// The windowed synthesis (window_kernels.hpp) of `frames` frames, grid.z = frame: frame z's coefficients at coef_i +
+// z * coef_z bytes, its scratch (T[P + extra]) at work + z * work_z bytes.  u8 != nullptr: level r writes frame z's
+// window at u8 + z * u8_z, row stride pitch; else level r's samples stay at frame z's `work` (compact, row stride w).
+static int run_window(picsong_ctx *c, const WindowPlan &w, const int32_t *coef_i, void *work, unsigned frames,
+                      unsigned long long coef_z, unsigned long long work_z, uint8_t *u8, size_t pitch,
+                      unsigned long long u8_z, hipStream_t s)
+{
+    std::vector<WinLaunch> plan = plan_window_synthesis(w, coef_i, work, c->P, c->aw, c->ah, c->p.qs, u8, pitch,
+                                                        1 << (c->p.bit_depth - 1));
+    for (WinLaunch &f : plan) {
+        f.a.mallat_z = coef_z; f.a.ll_z = work_z; f.a.dst_z = work_z; f.a.u8_z = u8_z;
+        f.grid.z = frames;
+        if (c->p.lossy) {
+            if (f.u8) dwt_window_kernel<float, true><<<f.grid, 256, 0, s>>>(f.a);
+            else dwt_window_kernel<float, false><<<f.grid, 256, 0, s>>>(f.a);
+        } else {
+            if (f.u8) dwt_window_kernel<int, true><<<f.grid, 256, 0, s>>>(f.a);
+            else dwt_window_kernel<int, false><<<f.grid, 256, 0, s>>>(f.a);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return PICSONG_OK;
+}
+
 // picsong_decode_frame (reduce = 0) and picsong_decode_frame_reduced: the pixels of level `reduce`, row stride AW >> reduce
-static int decode_frame_impl(picsong_ctx *c, const uint16_t *d_stream, uint8_t *d_frame_out, hipStream_t s, int reduce)
+// win != nullptr (picsong_decode_frame_window): the window of level `reduce`, row stride pitch
+static int decode_frame_impl(picsong_ctx *c, const uint16_t *d_stream, uint8_t *d_frame_out, hipStream_t s, int reduce,
+                             const WindowPlan *win = nullptr, size_t pitch = 0)
 {
     int rc = ensure_workspace(c, true);
     if (rc) return rc;
+    if (win) {      // the decoder over the window's codeblocks (32-bit coefficients), then the cone's synthesis
+        if ((rc = decode_stream_impl(c, d_stream, c->d_coef_i, s, 0, false, reduce, win))) return rc;
+        return run_window(c, *win, c->d_coef_i, c->d_coef, 1u, 0, 0, d_frame_out, pitch, 0, s);
+    }
     // (16-bit coefficients between the decoder and the synthesis where the context's magnitudes are bounded and this
     // call's pointers take the vector kernels: c->c16_dec, plan_inv_is_c16)
     bool fused = false;
@@ -1193,6 +1232,40 @@ int picsong_decode_frame_reduced(picsong_ctx *c, const uint16_t *d_stream, int r
     if (!c || !d_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame_reduced: null argument");
     if (int rc = reduced_args_ok(c, reduce, "decode_frame_reduced")) return rc;
     return decode_frame_impl(c, d_stream, d_out, (hipStream_t)stream, reduce);
+}
+
+// the refusals the window calls share (nothing is launched); sets *plan
+static int window_args_ok(const picsong_ctx *c, int reduce, int x, int y, int w, int h, const char *who, WindowPlan *plan)
+{
+    if (int rc = reduced_args_ok(c, reduce, who)) return rc;
+    if (w < 1 || h < 1) return fail(PICSONG_ERR_ARG, "%s: window %d x %d is empty", who, w, h);
+    const int paw = c->aw >> reduce, pah = c->ah >> reduce;
+    if (!window_ok(paw, pah, x, y, w, h))
+        return fail(PICSONG_ERR_ARG, "%s: window [%d, %lld) x [%d, %lld) not inside the %d x %d padded image at reduce %d", who,
+                    x, (long long)x + w, y, (long long)y + h, paw, pah, reduce);
+    *plan = window_plan(c->aw, c->ah, c->p.wl, c->p.lossy != 0, reduce, x, y, w, h);
+    if (window_waves(*plan) > dec_scratch_waves(c))             // (cannot happen: window_waves_cap bounds every window)
+        return fail(PICSONG_ERR_ARG, "%s: the window lists more codeblocks than the decoder's scratch holds", who);
+    return PICSONG_OK;
+}
+
+int picsong_window_codeblocks(const picsong_ctx *c, int reduce, int x, int y, int w, int h, int *n_codeblocks)
+{
+    if (!c || !n_codeblocks) return fail(PICSONG_ERR_ARG, "window_codeblocks: null argument");
+    WindowPlan plan;
+    if (int rc = window_args_ok(c, reduce, x, y, w, h, "window_codeblocks", &plan)) return rc;
+    *n_codeblocks = plan.n_cb;
+    return PICSONG_OK;
+}
+
+int picsong_decode_frame_window(picsong_ctx *c, const uint16_t *d_stream, int reduce, int x, int y, int w, int h,
+                                uint8_t *d_out, size_t out_pitch, void *stream)
+{
+    if (!c || !d_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame_window: null argument");
+    WindowPlan plan;
+    if (int rc = window_args_ok(c, reduce, x, y, w, h, "decode_frame_window", &plan)) return rc;
+    if (out_pitch < (size_t)w) return fail(PICSONG_ERR_ARG, "decode_frame_window: out_pitch %zu < w %d", out_pitch, w);
+    return decode_frame_impl(c, d_stream, d_out, (hipStream_t)stream, reduce, &plan, out_pitch);
 }
 
 int picsong_encode_stripe_coded(picsong_ctx *c, const void *d_coeffs, int cb_begin, int cb_count, uint16_t *d_stream,
@@ -1258,7 +1331,7 @@ static int ensure_batch(picsong_ctx *c, int n)
     HIP_TRY(hipDeviceSynchronize());                 // a smaller batch may still be running on the old buffers
     free_batch(c);
     // (scratch for whole workgroups per frame: the RGB form pads every component's waves to workgroups)
-    const size_t waves = (size_t)n * (size_t)(((c->ncb + 1) / 2 + kBpcEncWgWaves - 1) / kBpcEncWgWaves * kBpcEncWgWaves);
+    const size_t waves = (size_t)n * (size_t)dec_scratch_waves(c);
     HIP_TRY(hipMalloc(&c->b_coef, (size_t)n * (c->P + c->extra) * 4));
     HIP_TRY(hipMalloc(&c->b_staging, (size_t)n * c->P * sizeof(int32_t)));
     HIP_TRY(hipMalloc(&c->b_sizes, (size_t)n * (size_t)c->ncb * sizeof(int32_t)));
@@ -1395,8 +1468,11 @@ int picsong_last_totals(picsong_ctx *c, void *stream, int n, int *h_totals)
 // frame, one decoder grid over n x nCB codeblocks, grid.z = frame for the inverse transform's levels)
 // picsong_decode_frames (reduce = 0) and picsong_decode_frames_reduced: frame f's pixels of level `reduce` at
 // d_frames_out + f * frame_stride, row stride AW >> reduce
+// win != nullptr (picsong_decode_frames_window): frame f's window of level `reduce` at d_frames_out + f * frame_stride,
+// row stride pitch
 static int decode_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_frames_out,
-                              size_t frame_stride, void *stream, int reduce, const char *who)
+                              size_t frame_stride, void *stream, int reduce, const char *who,
+                              const WindowPlan *win = nullptr, size_t pitch = 0)
 {
     if (!c || !d_streams || !d_frames_out) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     if (n < 1 || n > 64) return fail(PICSONG_ERR_ARG, "%s: n = %d outside 1..64", who, n);
@@ -1405,9 +1481,11 @@ static int decode_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, 
     if (!reduce_ok(c->p.wl, reduce))
         return fail(PICSONG_ERR_ARG, "%s: reduce %d outside 0..%d (wl - 1)", who, reduce, c->p.wl - 1);
     const size_t px = (size_t)(c->aw >> reduce) * (size_t)(c->ah >> reduce);      // bytes of one frame's pixels
-    if (n > 1 && (stream_stride < picsong_max_stream_shorts(c->aw, c->ah) || frame_stride < px))
+    // (a window's bytes: its last row ends (h - 1) * pitch + w bytes in)
+    const size_t span = win ? (size_t)(win->R[reduce].y1 - win->R[reduce].y0 - 1) * pitch + (size_t)(win->R[reduce].x1 - win->R[reduce].x0) : px;
+    if (n > 1 && (stream_stride < picsong_max_stream_shorts(c->aw, c->ah) || frame_stride < span))
         return fail(PICSONG_ERR_ARG, "%s: strides %zu shorts / %zu bytes too small", who, stream_stride, frame_stride);
-    if (n == 1) return decode_frame_impl(c, d_streams, d_frames_out, (hipStream_t)stream, reduce);
+    if (n == 1) return decode_frame_impl(c, d_streams, d_frames_out, (hipStream_t)stream, reduce, win, pitch);
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_batch(c, n);
     if (rc) return rc;
@@ -1432,13 +1510,15 @@ static int decode_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, 
     // ---- decoder: one grid over the n frames' codeblock pairs, both plane-count classes
     BpcArgs a;
     if ((rc = bpc_args(c, a, 0))) return rc;
-    const int wpf = decode_rect(c, a, reduce);
+    const int wpf = decode_rect(c, a, reduce, win);
     a.cb_base = 0; a.nCB = c->ncb;
     a.coeffs_out = c->b_coef_i; a.staging = c->b_staging; a.sizes = c->b_sizes; a.plane_scratch = c->b_plane_scratch;
-    // (the synthesis is planned first: it says whether this call's coefficients can travel as int16)
+    // (the synthesis is planned first: it says whether this call's coefficients can travel as int16; a window's
+    // synthesis reads 32-bit ones)
     bool fused = false;
-    const std::vector<InvLaunch> plan = inverse_plan(c, c->b_coef_i, c->b_coef, d_frames_out, &fused, (unsigned)n, frame_stride,
-                                                     dec_c16_reduced(c, reduce) && direct, false, reduce);
+    const std::vector<InvLaunch> plan = win ? std::vector<InvLaunch>()
+                                            : inverse_plan(c, c->b_coef_i, c->b_coef, d_frames_out, &fused, (unsigned)n,
+                                                           frame_stride, dec_c16_reduced(c, reduce) && direct, false, reduce);
     const bool c16 = plan_inv_is_c16(plan);
     a.frames = n; a.waves_per_frame = wpf; a.coef_z = (unsigned long long)c->P * (c16 ? 2ull : 4ull);
     const unsigned wgs = (unsigned)(((size_t)n * (size_t)wpf + kBpcDecWgWaves - 1) / kBpcDecWgWaves);
@@ -1454,6 +1534,9 @@ static int decode_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, 
         bpc_decode_kernel<false, kDecSmallPlanes><<<wgs, 64 * kBpcDecWgWaves, 0, s>>>(a);
     }
     HIP_TRY(hipGetLastError());
+    if (win)
+        return run_window(c, *win, c->b_coef_i, c->b_coef, (unsigned)n, (unsigned long long)c->P * 4ull,
+                          (unsigned long long)(c->P + c->extra) * 4ull, d_frames_out, pitch, frame_stride, s);
     // ---- inverse transform, pixels out of the finest level where its vector kernel applies
     if ((rc = run_inverse(c, plan, s, (unsigned)n))) return rc;
     if (fused) return PICSONG_OK;
@@ -1481,6 +1564,17 @@ int picsong_decode_frames_reduced(picsong_ctx *c, int n, const uint16_t *d_strea
 {
     return decode_frames_impl(c, n, d_streams, stream_stride, d_frames_out, frame_stride, stream, reduce,
                               "decode_frames_reduced");
+}
+
+int picsong_decode_frames_window(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x,
+                                 int y, int w, int h, uint8_t *d_out, size_t out_pitch, size_t frame_stride, void *stream)
+{
+    const char *who = "decode_frames_window";
+    if (!c || !d_streams || !d_out) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    WindowPlan plan;
+    if (int rc = window_args_ok(c, reduce, x, y, w, h, who, &plan)) return rc;
+    if (out_pitch < (size_t)w) return fail(PICSONG_ERR_ARG, "%s: out_pitch %zu < w %d", who, out_pitch, w);
+    return decode_frames_impl(c, n, d_streams, stream_stride, d_out, frame_stride, stream, reduce, who, &plan, out_pitch);
 }
 
 int picsong_copy_last_totals(picsong_ctx *c, void *stream, int n, int32_t *d_totals)
@@ -1661,8 +1755,10 @@ int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *
 
 // picsong_decode_rgb_frame (reduce = 0) and picsong_decode_rgb_frame_reduced: the three components' level `reduce`,
 // then the inverse colour transform over its (AW >> reduce) x (AH >> reduce) samples
+// win != nullptr (picsong_decode_rgb_frame_window): the window of level `reduce`, the planes' row stride pitch
 static int decode_rgb_impl(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_r, uint8_t *d_g,
-                           uint8_t *d_b, void *stream, int reduce, const char *who)
+                           uint8_t *d_b, void *stream, int reduce, const char *who, const WindowPlan *win = nullptr,
+                           size_t pitch = 0)
 {
     if (!c || !d_streams || !d_r || !d_g || !d_b) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: the context is not an RGB one", who);
@@ -1675,8 +1771,8 @@ static int decode_rgb_impl(picsong_ctx *c, const uint16_t *d_streams, size_t str
     int rc = bpc_args_rgb(c, a);
     if (rc) return rc;
     // (k = 0: a component's waves are whole workgroups, as bpc_args_rgb lays them; -k > 0: exactly its waves)
-    const int wpf = decode_rect(c, a, reduce);
-    if (reduce > 0) a.waves_per_frame = (wpf + kBpcDecWgWaves - 1) / kBpcDecWgWaves * kBpcDecWgWaves;
+    const int wpf = decode_rect(c, a, reduce, win);
+    if (reduce > 0 || win) a.waves_per_frame = (wpf + kBpcDecWgWaves - 1) / kBpcDecWgWaves * kBpcDecWgWaves;
     if ((rc = ensure_batch(c, 3))) return rc;
     if ((rc = ensure_coef_i(c, 3))) return rc;
     c->last_batch = -1;
@@ -1694,9 +1790,10 @@ static int decode_rgb_impl(picsong_ctx *c, const uint16_t *d_streams, size_t str
         HIP_TRY(hipGetLastError());
     }
     // (16-bit coefficients between the decoder and the synthesis where the context's magnitudes are bounded: the
-    // plan says whether this call's arrays take the vector kernels)
-    const std::vector<InvLaunch> plan = inverse_plan(c, c->b_coef_i, c->b_coef, nullptr, nullptr, 3u, 0,
-                                                     dec_c16_reduced(c, reduce) && direct, true, reduce);
+    // plan says whether this call's arrays take the vector kernels; a window's synthesis reads 32-bit ones)
+    const std::vector<InvLaunch> plan = win ? std::vector<InvLaunch>()
+                                            : inverse_plan(c, c->b_coef_i, c->b_coef, nullptr, nullptr, 3u, 0,
+                                                           dec_c16_reduced(c, reduce) && direct, true, reduce);
     const bool c16 = plan_inv_is_c16(plan);
     a.coeffs_out = c->b_coef_i; a.staging = c->b_staging; a.sizes = c->b_sizes; a.plane_scratch = c->b_plane_scratch;
     a.coef_z = (unsigned long long)c->P * (c16 ? 2ull : 4ull);
@@ -1714,6 +1811,17 @@ static int decode_rgb_impl(picsong_ctx *c, const uint16_t *d_streams, size_t str
         bpc_decode_kernel<false, kDecSmallPlanes><<<wgs3, 64 * kBpcDecWgWaves, 0, s>>>(a);
     }
     HIP_TRY(hipGetLastError());
+    if (win) {      // the three components' cones (grid.z = component), then the inverse RCT / ICT over the window
+        const unsigned long long z = (unsigned long long)(c->P + c->extra) * 4ull;
+        if ((rc = run_window(c, *win, c->b_coef_i, c->b_coef, 3u, (unsigned long long)c->P * 4ull, z, nullptr, 0, 0, s))) return rc;
+        const IRect &o = win->R[reduce];
+        const int w = o.x1 - o.x0, h = o.y1 - o.y0, off = 1 << (c->p.bit_depth - 1);
+        const dim3 grid((unsigned)((w + 255) / 256), (unsigned)h);
+        if (c->p.lossy) window_rgb_kernel<float><<<grid, 256, 0, s>>>((const float *)c->b_coef, z, w, h, d_r, d_g, d_b, pitch, off);
+        else window_rgb_kernel<int><<<grid, 256, 0, s>>>((const int *)c->b_coef, z, w, h, d_r, d_g, d_b, pitch, off);
+        HIP_TRY(hipGetLastError());
+        return PICSONG_OK;
+    }
     // 5/3 with 16-bit coefficients: the finest level of the three components and the inverse colour transform as ONE
     // launch (dwt_inv_rgb_kernel: the 32-bit planes are never written); PICSONG_RGB_NOFUSE=1 keeps the two
     const bool px_aligned = ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 3u) == 0;
@@ -1773,6 +1881,17 @@ int picsong_decode_rgb_frame_reduced(picsong_ctx *c, const uint16_t *d_streams, 
                                      uint8_t *d_g, uint8_t *d_b, void *stream)
 {
     return decode_rgb_impl(c, d_streams, stream_stride, d_r, d_g, d_b, stream, reduce, "decode_rgb_frame_reduced");
+}
+
+int picsong_decode_rgb_frame_window(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
+                                    int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, size_t out_pitch, void *stream)
+{
+    const char *who = "decode_rgb_frame_window";
+    if (!c || !d_streams || !d_r || !d_g || !d_b) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    WindowPlan plan;
+    if (int rc = window_args_ok(c, reduce, x, y, w, h, who, &plan)) return rc;
+    if (out_pitch < (size_t)w) return fail(PICSONG_ERR_ARG, "%s: out_pitch %zu < w %d", who, out_pitch, w);
+    return decode_rgb_impl(c, d_streams, stream_stride, d_r, d_g, d_b, stream, reduce, who, &plan, out_pitch);
 }
 
 int picsong_pad_frame_host(const uint8_t *in, int w, int h, uint8_t *out, int aw, int ah)

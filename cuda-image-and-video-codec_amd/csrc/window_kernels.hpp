@@ -1,0 +1,269 @@
+// window_kernels.hpp -- the synthesis of a window's dependency cone (picsong_decode_frame_window and its mirrors; no
+// reference counterpart), one level a launch, for gfx950 and the CPU wave emulator.
+//
+// Level l computes LL_l over the rectangle R_l of window_plan (launch_plan.hpp) only.  It reads LL_{l+1} over R_{l+1}
+// (the previous launch's compact rectangle, or the Mallat array at l = wl - 1) and HL / LH / HH over S_l from the
+// Mallat array.  A workgroup owns a kWinTile x kWinTile tile of R_l and builds in LDS the interleaved samples of the
+// tile plus a halo of 2 (5/3) or 4 (9/7) samples a side -- the radius of the 2 / 4 lifting steps.  Halo samples outside
+// LL_l come from their mirror position (reflect's whole-sample symmetric extension, folded twice: a level may be 4
+// samples wide and the 9/7 halo is 4), so every lifting step runs the interior formula on every tile sample and the
+// samples in LL_l are those of whole-image lifting: the oracle's edges (x[-1] = x[1], x[n] = x[n-2]) included.
+// The lifting runs in the oracle's order (po_53_inv_1d / po_97_inv_1d): horizontal over all the tile's rows, then
+// vertical, a barrier between steps.  9/7 divides as the oracle does -- ((m * s) / q) / qs on the read, x / N1 and
+// x / N2 with true divisions (div_n1<true>, div_n2<true>), explicit fmaf in po_97_inv_1d's operation order.
+// Intermediate levels store R_l as T (row stride its width); level r stores pixels into the caller's window through
+// to_pixel (grey), or T that window_rgb_kernel turns into the three pixel planes (RGB).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "bpc_kernels.hpp"
+#include "dwt_kernels.hpp"
+#include "launch_plan.hpp"
+
+namespace picsong {
+
+constexpr int kWinTile = 64;            // output samples per tile side; 256 threads a workgroup
+
+struct WinSynArgs {
+    const int32_t *mallat;              // the decoder's int32 Mallat array, row stride AW
+    int AW;
+    const void *ll;                     // LL_{l+1} over R_{l+1}: T, row stride ll_stride, its origin at (ll_x0, ll_y0)
+    int ll_x0, ll_y0, ll_stride;
+    int first;                          // l = wl - 1: LL_wl is read (and de-quantised) from the Mallat array instead
+    int W, H;                           // LL_l's size
+    int x0, y0, x1, y1;                 // R_l
+    void *dst;                          // T over R_l, row stride x1 - x0 (no U8OUT)
+    uint8_t *dst_u8;                    // U8OUT: the window's pixels, row (y - y0) at dst_u8 + (y - y0) * pitch
+    unsigned long long pitch;
+    int off;                            // level shift
+    float qs, q[4];                     // 9/7: the quantisation steps of level l (LL, HL, LH, HH) and the context's qs
+    // grid.z = frames of a batched call (or the components of an RGB frame): frame z reads mallat + z * mallat_z and
+    // ll + z * ll_z, writes dst + z * dst_z and dst_u8 + z * u8_z (bytes)
+    unsigned long long mallat_z, ll_z, dst_z, u8_z;
+};
+
+// reflect() folded twice (see above); i in [-4, n + 3], n >= 4
+__device__ __forceinline__ int win_mirror(int i, int n)
+{
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        if (i < 0) i = -i;
+        if (i >= n) i = 2 * (n - 1) - i;
+    }
+    return i;
+}
+
+// one lifting step of po_53_inv_1d / po_97_inv_1d on sample x with neighbours p (before) and n (after).
+// 5/3: STEP 0 the even update, 1 the odd prediction.  9/7: STEP 0..3 = A4 (even), A3 (odd), A2 (even), A1 (odd).
+template <int STEP> __device__ __forceinline__ int win_lift(int x, int p, int n)
+{
+    if constexpr (STEP == 0) return x - ((p + n + 2) >> 2);
+    else return x + ((p + n) >> 1);
+}
+template <int STEP> __device__ __forceinline__ float win_lift(float x, float p, float n)
+{
+    constexpr float A = STEP == 0 ? PS_A4 : (STEP == 1 ? PS_A3 : (STEP == 2 ? PS_A2 : PS_A1));
+    return fmaf(-(p + n), A, x);
+}
+
+// STEP over the tile's samples of its parity (even steps: even coordinates), horizontally (along rows) or vertically.
+// Tile sample (i, j) is LL_l's (gx0 + i, gy0 + j); nx x ny samples in use, row stride TS.  The tile's outer samples
+// have no neighbour on one side and are left as they are: each step shrinks the exact region by one, the halo by as many.
+template <typename T, int STEP, bool HORIZ, int TS>
+__device__ __forceinline__ void win_step(T *tile, int nx, int ny, int gx0, int gy0)
+{
+    constexpr int par = STEP & 1;
+    if constexpr (HORIZ) {
+        const int i0 = 1 + (((gx0 + 1) & 1) ^ par);          // first i >= 1 with (gx0 + i) & 1 == par
+        const int half = (nx - 1 - i0 + 1) / 2;               // i = i0, i0 + 2, ... < nx - 1
+        for (int j = (int)threadIdx.x >> 5; j < ny; j += 8)
+            for (int k = (int)threadIdx.x & 31; k < half; k += 32) {
+                T *p = tile + j * TS + i0 + 2 * k;
+                p[0] = win_lift<STEP>(p[0], p[-1], p[1]);
+            }
+    } else {
+        const int j0 = 1 + (((gy0 + 1) & 1) ^ par);
+        const int half = (ny - 1 - j0 + 1) / 2;
+        for (int k = (int)threadIdx.x >> 6; k < half; k += 4)
+            for (int i = (int)threadIdx.x & 63; i < nx; i += 64) {
+                T *p = tile + (j0 + 2 * k) * TS + i;
+                p[0] = win_lift<STEP>(p[0], p[-TS], p[TS]);
+            }
+    }
+    __syncthreads();
+}
+
+// T = int (5/3) or float (9/7); U8OUT: level r of a grey call, pixels into the window
+template <typename T, bool U8OUT>
+__global__ __launch_bounds__(256) void dwt_window_kernel(WinSynArgs a)
+{
+    constexpr bool LOSSY = std::is_same<T, float>::value;
+    constexpr int HL = LOSSY ? 4 : 2;                        // halo: the lifting steps of a direction
+    constexpr int TS = kWinTile + 2 * HL;
+    __shared__ T tile[TS * TS];
+    {
+        const unsigned long long z = blockIdx.z;
+        a.mallat = (const int32_t *)((const char *)a.mallat + z * a.mallat_z);
+        a.ll = (const char *)a.ll + z * a.ll_z;
+        a.dst = (char *)a.dst + z * a.dst_z;
+        if (U8OUT) a.dst_u8 += z * a.u8_z;
+    }
+    const int tx0 = a.x0 + (int)blockIdx.x * kWinTile, ty0 = a.y0 + (int)blockIdx.y * kWinTile;
+    const int tw = imin(kWinTile, a.x1 - tx0), th = imin(kWinTile, a.y1 - ty0);
+    const int gx0 = tx0 - HL, gy0 = ty0 - HL;               // LL_l coordinates of tile sample (0, 0)
+    const int nx = tw + 2 * HL, ny = th + 2 * HL;
+    const int hW = a.W >> 1, hH = a.H >> 1;
+
+    // ---- load: the interleaved samples, mirrored where outside LL_l; 9/7 takes the horizontal pass's divisions here
+    // (x / N1 on odd columns, x / N2 on even ones: po_97_inv_1d's first operations on a sample, pointwise)
+    for (int j = (int)threadIdx.x >> 6; j < ny; j += 4) {
+        const int gy = win_mirror(gy0 + j, a.H);
+        const int n = gy >> 1, by = gy & 1;
+        for (int i = (int)threadIdx.x & 63; i < nx; i += 64) {
+            const int gx = win_mirror(gx0 + i, a.W);
+            const int m = gx >> 1, bx = gx & 1;
+            T v;
+            if (!bx && !by && !a.first) {
+                v = reinterpret_cast<const T *>(a.ll)[(size_t)(n - a.ll_y0) * (size_t)a.ll_stride + (size_t)(m - a.ll_x0)];
+            } else {
+                const int32_t c = a.mallat[(size_t)(n + by * hH) * (size_t)a.AW + (size_t)(m + bx * hW)];
+                if constexpr (LOSSY) {
+                    const float q = by ? (bx ? a.q[3] : a.q[2]) : (bx ? a.q[1] : a.q[0]);
+                    v = dequant<false>(c, q, 0.0f, a.qs, 0.0f);
+                } else {
+                    v = c;
+                }
+            }
+            if constexpr (LOSSY) v = bx ? div_n1<true>(v) : div_n2<true>(v);
+            tile[j * TS + i] = v;
+        }
+    }
+    __syncthreads();
+
+    // ---- horizontal, every row of the tile
+    if constexpr (LOSSY) {
+        win_step<T, 0, true, TS>(tile, nx, ny, gx0, gy0);
+        win_step<T, 1, true, TS>(tile, nx, ny, gx0, gy0);
+        win_step<T, 2, true, TS>(tile, nx, ny, gx0, gy0);
+        win_step<T, 3, true, TS>(tile, nx, ny, gx0, gy0);
+        // the vertical pass's divisions, pointwise: x / N1 on odd rows, x / N2 on even ones
+        for (int j = (int)threadIdx.x >> 6; j < ny; j += 4) {
+            const bool odd = ((gy0 + j) & 1) != 0;
+            for (int i = (int)threadIdx.x & 63; i < nx; i += 64) {
+                T &v = tile[j * TS + i];
+                v = odd ? div_n1<true>(v) : div_n2<true>(v);
+            }
+        }
+        __syncthreads();
+        win_step<T, 0, false, TS>(tile, nx, ny, gx0, gy0);
+        win_step<T, 1, false, TS>(tile, nx, ny, gx0, gy0);
+        win_step<T, 2, false, TS>(tile, nx, ny, gx0, gy0);
+        win_step<T, 3, false, TS>(tile, nx, ny, gx0, gy0);
+    } else {
+        win_step<T, 0, true, TS>(tile, nx, ny, gx0, gy0);
+        win_step<T, 1, true, TS>(tile, nx, ny, gx0, gy0);
+        win_step<T, 0, false, TS>(tile, nx, ny, gx0, gy0);
+        win_step<T, 1, false, TS>(tile, nx, ny, gx0, gy0);
+    }
+
+    // ---- store the tile's own samples
+    const int ox = tx0 - a.x0, oy = ty0 - a.y0, ow = a.x1 - a.x0;
+    for (int j = (int)threadIdx.x >> 6; j < th; j += 4)
+        for (int i = (int)threadIdx.x & 63; i < tw; i += 64) {
+            const T v = tile[(j + HL) * TS + i + HL];
+            if constexpr (U8OUT) a.dst_u8[(size_t)(oy + j) * a.pitch + (size_t)(ox + i)] = (uint8_t)to_pixel(v, a.off);
+            else reinterpret_cast<T *>(a.dst)[(size_t)(oy + j) * (size_t)ow + (size_t)(ox + i)] = v;
+        }
+}
+
+// RGB window calls: the inverse RCT / ICT of the three components' level-r samples (compact, w x h, row stride w, the
+// components z_stride bytes apart), level shift and clamp -- rgb_inverse_kernel's arithmetic -- into the three pixel
+// planes, row i at r / g / b + i * pitch
+template <typename T>
+__global__ __launch_bounds__(256) void window_rgb_kernel(const T *c0, unsigned long long z_stride, int w, int h, uint8_t *r,
+                                                         uint8_t *g, uint8_t *b, unsigned long long pitch, int off)
+{
+    const T *c1 = (const T *)((const char *)c0 + z_stride), *c2 = (const T *)((const char *)c0 + 2 * z_stride);
+    const float M[3][3] = { { 1.0f, 0.0f, 1.402f }, { 1.0f, -0.344136f, -0.714136f }, { 1.0f, 1.772f, 0.0f } };
+    const int y = (int)blockIdx.y;
+    for (int x = (int)(blockIdx.x * blockDim.x + threadIdx.x); x < w; x += (int)(gridDim.x * blockDim.x)) {
+        const size_t i = (size_t)y * (size_t)w + (size_t)x;
+        int R, G, B;
+        if constexpr (std::is_integral<T>::value) {
+            const int yy = (int)c0[i], cb = (int)c1[i], cr = (int)c2[i];
+            G = yy - ((cb + cr) >> 2);
+            R = cr + G;
+            B = cb + G;
+        } else {
+            const float yy = c0[i], cb = c1[i], cr = c2[i];
+            R = (int)rintf(fmaf(M[0][2], cr, fmaf(M[0][1], cb, M[0][0] * yy)) + 0.01f);
+            G = (int)rintf(fmaf(M[1][2], cr, fmaf(M[1][1], cb, M[1][0] * yy)) + 0.01f);
+            B = (int)rintf(fmaf(M[2][2], cr, fmaf(M[2][1], cb, M[2][0] * yy)) + 0.01f);
+        }
+        const size_t o = (size_t)y * (size_t)pitch + (size_t)x;
+        r[o] = (uint8_t)clamp_u8(R + off);
+        g[o] = (uint8_t)clamp_u8(G + off);
+        b[o] = (uint8_t)clamp_u8(B + off);
+    }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------
+// The decoder's rectangle table of a window plan (BpcArgs::win_n ...); returns the waves of one frame
+inline int window_bpc_table(BpcArgs &a, const WindowPlan &p)
+{
+    static_assert(kWindowMaxRects == kBpcWinRects, "the plan's rectangles fill the decoder's table");
+    a.ncx_r = a.ncb_r = 0;
+    a.win_n = p.n_rects;
+    int before = 0;
+    for (int i = 0; i < kBpcWinRects; i++) {
+        const bool used = i < p.n_rects;
+        a.win_x[i] = used ? p.cb[i].x0 : 0;
+        a.win_y[i] = used ? p.cb[i].y0 : 0;
+        a.win_w[i] = used ? p.cb[i].x1 - p.cb[i].x0 : 1;
+        a.win_before[i] = before;
+        if (used) before += (p.cb[i].x1 - p.cb[i].x0) * (p.cb[i].y1 - p.cb[i].y0);
+    }
+    a.win_before[kBpcWinRects] = before;
+    return window_waves(p);
+}
+
+// The synthesis launches of a window plan, level wl - 1 first.  Level l > r writes its compact rectangle into `work`
+// (one frame's T[P + extra] scratch): levels r + 1, r + 3, ... at element P (each at most P / 4 samples: the `extra`
+// region, wl >= 2 whenever such a level exists), levels r + 2, r + 4, ... at element 0; level r (rgb) at element 0.
+// Level r of a grey call writes the pixels: u8 != nullptr.
+struct WinLaunch { WinSynArgs a; dim3 grid; bool u8; };
+inline std::vector<WinLaunch> plan_window_synthesis(const WindowPlan &p, const int32_t *mallat, void *work, size_t P, int aw,
+                                                    int ah, float qs, uint8_t *u8, size_t pitch, int off)
+{
+    std::vector<WinLaunch> v;
+    for (int l = p.wl - 1; l >= p.r; l--) {
+        WinLaunch f;
+        WinSynArgs &a = f.a;
+        a.mallat = mallat; a.AW = aw;
+        a.first = l == p.wl - 1 ? 1 : 0;
+        const IRect &in = p.R[l + 1], &out = p.R[l];
+        if (a.first) { a.ll = mallat; a.ll_x0 = a.ll_y0 = 0; a.ll_stride = aw; }
+        else {
+            a.ll = (const char *)work + (((l + 1 - p.r) & 1) ? P : 0) * 4;
+            a.ll_x0 = in.x0; a.ll_y0 = in.y0; a.ll_stride = in.x1 - in.x0;
+        }
+        a.W = aw >> l; a.H = ah >> l;
+        a.x0 = out.x0; a.y0 = out.y0; a.x1 = out.x1; a.y1 = out.y1;
+        a.dst = (char *)work + (((l - p.r) & 1) ? P : 0) * 4;
+        a.dst_u8 = l == p.r ? u8 : nullptr;
+        a.pitch = pitch;
+        a.off = off;
+        a.qs = qs;
+        for (int k = 0; k < 4; k++) a.q[k] = kQSteps[l][k];
+        a.mallat_z = a.ll_z = a.dst_z = a.u8_z = 0;
+        f.grid = dim3((unsigned)((out.x1 - out.x0 + kWinTile - 1) / kWinTile), (unsigned)((out.y1 - out.y0 + kWinTile - 1) / kWinTile), 1);
+        f.u8 = a.dst_u8 != nullptr;
+        v.push_back(f);
+    }
+    return v;
+}
+
+}  // namespace picsong

@@ -47,6 +47,8 @@ struct Options {
     float qs = 1.0f, k = 0.0f;
     std::string metrics;
     int reduce = 0;                             // -reduce r: decode the image at 1/2^r of its size
+    int win = 0, wx = 0, wy = 0, ww = 0, wh = 0; // -window x,y,w,h: decode that rectangle of the image at 1/2^r
+    int win_cb = 0;                             // (the codeblocks a window decodes, for --metrics)
 };
 
 [[noreturn]] void die(const std::string &msg)
@@ -100,7 +102,9 @@ void help()
         "                     writer's pinned ring over its own host link, the output file is the 1-GPU file\n"
         " -framesPerLaunch B  frames coded / decoded per launch (default: 4 up to 4K frames, 1 above)\n"
         " --lut-fill V        value of LUT entries the loader never writes (default 0)\n"
-        " -reduce r           decoding: the image at 1/2^r of its size, r in 0..wl-1 (resolution reduction)\n";
+        " -reduce r           decoding: the image at 1/2^r of its size, r in 0..wl-1 (resolution reduction)\n"
+        " -window x,y,w,h     decoding: only the w x h rectangle at (x, y) of the image (at 1/2^r with -reduce r), from the\n"
+        "                     codeblocks it depends on (spatial random access)\n";
 }
 
 template <typename T> void echo(const char *flag, const T &v)
@@ -121,6 +125,16 @@ Options parse(const Args &a)
     geti("-gpus", o.gpus); geti("-framesPerLaunch", o.frames_per_launch); gets("--devices", o.devices);
     geti("-reduce", o.reduce);
     if (a.has("-reduce") && o.cd != 1) die("Incorrect parameters. -reduce applies to decoding (-cd 1) only.");
+    if (a.has("-window")) {
+        if (o.cd != 1) die("Incorrect parameters. -window applies to decoding (-cd 1) only.");
+        const std::string v = a.get("-window");
+        char tail = 0;
+        if (sscanf(v.c_str(), "%d,%d,%d,%d%c", &o.wx, &o.wy, &o.ww, &o.wh, &tail) != 4 || o.wx < 0 || o.wy < 0 || o.ww < 1 ||
+            o.wh < 1)
+            die("Incorrect parameters. -window takes x,y,w,h: x, y >= 0, w, h >= 1.");
+        o.win = 1;
+        echo("-window", v);
+    }
     if (o.cd == 0) {
         geti("-xSize", o.x); geti("-ySize", o.y); geti("-cbWidth", o.cb_width); geti("-cbHeight", o.cb_height);
         geti("-wl", o.wl); geti("-cp", o.cp); geti("-endianess", o.endianess); geti("-bps", o.bps);
@@ -218,6 +232,8 @@ void write_metrics(const Options &o, const char *mode, long frames, double secon
     // decoding: the size of the images written (1/2^reduce of the frame's, -reduce)
     if (std::string(mode).compare(0, 6, "decode") == 0)
         m << ", \"width\": " << o.x << ", \"height\": " << o.y << ", \"reduce\": " << o.reduce;
+    if (o.win)
+        m << ", \"window\": [" << o.wx << ", " << o.wy << ", " << o.ww << ", " << o.wh << "], \"codeblocks\": " << o.win_cb;
     m << "}\n";
 }
 
@@ -586,8 +602,9 @@ void write_pgm(const std::string &path, const uint8_t *pix, int w, int h, int bi
 // transform (offset + clamp fused) -> planar R, G, B planes of W*H bytes appended to <o>
 // (IOManager::writeDecodedFrameUChar / writeDecodedFrameComponentUChar, IO/IOManager.ipp:236-262).
 // What a decode writes (-reduce r, picsong_reduced_dims): w x h visible pixels a frame of rows pw bytes apart, out of a
-// padded image of pw x ph; r = 0: the frame itself (W x H of AW x AH).
-struct OutDims { int r, w, h, pw, ph; };
+// padded image of pw x ph; r = 0: the frame itself (W x H of AW x AH).  win (-window x,y,w,h): the w x h window at
+// (x, y) of the image at 1/2^r, rows pw = w bytes apart (ph = h).
+struct OutDims { int r, w, h, pw, ph, win = 0, x = 0, y = 0; };
 
 int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, std::ifstream &in,
                    const std::vector<long> &shorts, long nframes, int aw, int ah, const OutDims &od)
@@ -621,7 +638,10 @@ int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, 
             if (!batched) CK(picsong_decode_plane(ctx, d_in, c, d_plane[c], s));
             HIPCK(hipStreamSynchronize(s));          // h_in (and, plane by plane, d_in) are reused for the next component
         }
-        if (od.r > 0)
+        if (od.win)
+            CK(picsong_decode_rgb_frame_window(ctx, d_in, max_shorts, od.r, od.x, od.y, od.w, od.h, d_pix[0], d_pix[1],
+                                               d_pix[2], (size_t)od.pw, s));
+        else if (od.r > 0)
             CK(picsong_decode_rgb_frame_reduced(ctx, d_in, max_shorts, od.r, d_pix[0], d_pix[1], d_pix[2], s));
         else if (batched)
             CK(picsong_decode_rgb_frame(ctx, d_in, max_shorts, d_pix[0], d_pix[1], d_pix[2], s));
@@ -780,8 +800,10 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
                                (size_t)frame_shorts[(size_t)(g * B + b)] * 2, hipMemcpyHostToDevice, k.stream) != hipSuccess)
                 err = "HIP error in the codestream upload";
         if (!err.empty()) { }
-        else if ((od.r > 0 ? picsong_decode_frames_reduced(k.ctx, n, k.d_in, max_shorts, od.r, k.d_pix, P, k.stream)
-                           : picsong_decode_frames(k.ctx, n, k.d_in, max_shorts, k.d_pix, P, k.stream)) != PICSONG_OK)
+        else if ((od.win ? picsong_decode_frames_window(k.ctx, n, k.d_in, max_shorts, od.r, od.x, od.y, od.w, od.h, k.d_pix,
+                                                        (size_t)od.pw, P, k.stream)
+                  : od.r > 0 ? picsong_decode_frames_reduced(k.ctx, n, k.d_in, max_shorts, od.r, k.d_pix, P, k.stream)
+                             : picsong_decode_frames(k.ctx, n, k.d_in, max_shorts, k.d_pix, P, k.stream)) != PICSONG_OK)
             err = picsong_last_error();
         else if (hipMemcpyAsync(k.h_pix, k.d_pix, P * (size_t)n, hipMemcpyDeviceToHost, k.stream) != hipSuccess)
             err = "HIP error in the frame download";
@@ -844,6 +866,16 @@ int run_decode(const Options &o)
     CK(picsong_ctx_padded_dims(ctx, &aw, &ah, &ncb));
     OutDims od = { o.reduce, 0, 0, 0, 0 };
     CK(picsong_reduced_dims(ctx, o.reduce, &od.w, &od.h, &od.pw, &od.ph, &ncb));
+    if (o.win) {                             // the window inside the visible image at 1/2^r, written w x h
+        if (p.cp == 3) die("Incorrect parameters. -window does not apply to -cp 3 streams.");
+        if ((long)o.wx + o.ww > od.w || (long)o.wy + o.wh > od.h)
+            die("Incorrect parameters. -window " + std::to_string(o.wx) + "," + std::to_string(o.wy) + "," +
+                std::to_string(o.ww) + "," + std::to_string(o.wh) + " is not inside the " + std::to_string(od.w) + "x" +
+                std::to_string(od.h) + " image.");
+        CK(picsong_window_codeblocks(ctx, o.reduce, o.wx, o.wy, o.ww, o.wh, &lo.win_cb));
+        od.win = 1; od.x = o.wx; od.y = o.wy;
+        od.w = od.pw = o.ww; od.h = od.ph = o.wh;
+    }
     if (p.is_rgb) return run_decode_rgb(o, p, ctx, in, frame_shorts, nframes, aw, ah, od);
     if (o.video) {
         picsong_ctx_destroy(ctx);
@@ -872,7 +904,8 @@ int run_decode(const Options &o)
         if ((size_t)in.gcount() != n * 2) die("Input file is shorter than its _SIZE sidecar says.");
         pos += n;
         HIPCK(hipMemcpyAsync(d_in, h_in, n * 2, hipMemcpyHostToDevice, s));
-        if (od.r > 0) CK(picsong_decode_frame_reduced(ctx, d_in, od.r, d_pix, s));
+        if (od.win) CK(picsong_decode_frame_window(ctx, d_in, od.r, od.x, od.y, od.w, od.h, d_pix, (size_t)od.pw, s));
+        else if (od.r > 0) CK(picsong_decode_frame_reduced(ctx, d_in, od.r, d_pix, s));
         else CK(picsong_decode_frame(ctx, d_in, d_pix, s));
         HIPCK(hipMemcpyAsync(h_pix, d_pix, P, hipMemcpyDeviceToHost, s));
         HIPCK(hipStreamSynchronize(s));
@@ -887,7 +920,7 @@ int run_decode(const Options &o)
     }
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::cout << "The time spent with the app without considering allocation periods and I/O is: " << sec << std::endl;
-    Options mo = o;
+    Options mo = lo;
     mo.x = od.w; mo.y = od.h;
     write_metrics(mo, "decode", nframes, sec, 0, 0, 0, (long)pos);
     picsong_ctx_destroy(ctx);

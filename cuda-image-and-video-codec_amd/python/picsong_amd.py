@@ -46,6 +46,8 @@ EXPORTS = [
     "picsong_copy_last_totals", "picsong_decode_frames", "picsong_encode_rgb_frame", "picsong_decode_rgb_frame",
     "picsong_reduced_dims", "picsong_decode_frame_reduced", "picsong_decode_frames_reduced",
     "picsong_decode_rgb_frame_reduced",
+    "picsong_window_codeblocks", "picsong_decode_frame_window", "picsong_decode_frames_window",
+    "picsong_decode_rgb_frame_window",
 ]
 
 _lib = None
@@ -122,6 +124,11 @@ def load():
         L.picsong_decode_frame_reduced.argtypes = [vp, vp, i, vp, vp]
         L.picsong_decode_frames_reduced.argtypes = [vp, i, vp, C.c_size_t, i, vp, C.c_size_t, vp]
         L.picsong_decode_rgb_frame_reduced.argtypes = [vp, vp, C.c_size_t, i, vp, vp, vp, vp]
+    if hasattr(L, "picsong_window_codeblocks"):
+        L.picsong_window_codeblocks.argtypes = [vp, i, i, i, i, i, C.POINTER(i)]
+        L.picsong_decode_frame_window.argtypes = [vp, vp, i, i, i, i, i, vp, C.c_size_t, vp]
+        L.picsong_decode_frames_window.argtypes = [vp, i, vp, C.c_size_t, i, i, i, i, i, vp, C.c_size_t, C.c_size_t, vp]
+        L.picsong_decode_rgb_frame_window.argtypes = [vp, vp, C.c_size_t, i, i, i, i, i, vp, vp, vp, C.c_size_t, vp]
     if hasattr(L, "picsong_lut_load_cp"):
         L.picsong_lut_load_cp.argtypes = [C.c_char_p, i, i, i, i, C.POINTER(LutInfo), vp, C.c_size_t]
     if hasattr(L, "picsong_dwt_forward_band"):
@@ -463,4 +470,46 @@ class Codec:
         outs = [self.torch.empty((self.ah >> r, self.aw >> r), dtype=self.torch.uint8, device=self.dev) for _ in range(3)]
         _check(self.L.picsong_decode_rgb_frame_reduced(self.h, self._p(streams), streams.stride(0), r, self._p(outs[0]),
                                                        self._p(outs[1]), self._p(outs[2]), self._stream()))
+        return outs
+
+    # ---- window decode: the rectangle [x, x + w) x [y, y + h) of the padded image at 1/2^r ----
+    def window_codeblocks(self, x, y, w, h, r=0):
+        """The codeblocks one window call decodes (per frame, per component)."""
+        n = C.c_int()
+        _check(self.L.picsong_window_codeblocks(self.h, r, x, y, w, h, C.byref(n)))
+        return n.value
+
+    def _window_out(self, out, h, w):
+        if out is None:
+            return self.torch.empty((h, w), dtype=self.torch.uint8, device=self.dev)
+        assert out.dtype == self.torch.uint8 and out.dim() == 2 and tuple(out.shape) == (h, w) and out.stride(1) == 1
+        return out
+
+    def decode_frame_window(self, stream, x, y, w, h, r=0, out=None):
+        """The window, uint8 (h, w); or written into `out`, a 2-D uint8 view whose row stride is the pitch."""
+        out = self._window_out(out, h, w)
+        _check(self.L.picsong_decode_frame_window(self.h, self._p(stream), r, x, y, w, h, self._p(out), out.stride(0),
+                                                  self._stream()))
+        return out
+
+    def decode_frames_window(self, streams, x, y, w, h, r=0, out=None):
+        """streams: int16 [n, >= max_stream_shorts()]; returns uint8 [n, h, w] (or fills `out`, a 3-D uint8 view:
+        frame stride out.stride(0), pitch out.stride(1))."""
+        n = streams.shape[0]
+        assert streams.stride(-1) == 1
+        if out is None:
+            out = self.torch.empty((n, h, w), dtype=self.torch.uint8, device=self.dev)
+        assert out.dtype == self.torch.uint8 and tuple(out.shape) == (n, h, w) and out.stride(2) == 1
+        _check(self.L.picsong_decode_frames_window(self.h, n, self._p(streams), streams.stride(0), r, x, y, w, h,
+                                                   self._p(out), out.stride(1), out.stride(0), self._stream()))
+        return out
+
+    def decode_rgb_frame_window(self, streams, x, y, w, h, r=0, outs=None):
+        """streams: int16 [3, >= max_stream_shorts()]; returns the three u8 windows (h, w) (or fills `outs`, three 2-D
+        uint8 views with the same row stride)."""
+        outs = [self._window_out(None if outs is None else o, h, w) for o in (outs or [None] * 3)]
+        assert outs[0].stride(0) == outs[1].stride(0) == outs[2].stride(0)
+        _check(self.L.picsong_decode_rgb_frame_window(self.h, self._p(streams), streams.stride(0), r, x, y, w, h,
+                                                      self._p(outs[0]), self._p(outs[1]), self._p(outs[2]),
+                                                      outs[0].stride(0), self._stream()))
         return outs

@@ -283,6 +283,32 @@ int picsong_decode_frames_reduced(picsong_ctx *ctx, int n, const uint16_t *d_str
 int picsong_decode_rgb_frame_reduced(picsong_ctx *ctx, const uint16_t *d_streams, size_t stream_stride, int reduce,
                                      uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, void *stream);
 
+/* ---- window decode (JPEG 2000 style spatial random access, OpenJPEG -d / Kakadu -region; the reference has no
+ *      counterpart): the rectangle [x, x + w) x [y, y + h) of the padded image at 1/2^reduce resolution (the paw x pah
+ *      of picsong_reduced_dims), byte for byte that rectangle of picsong_decode_frame_reduced's output, decoded from
+ *      only the codeblocks it depends on.  Per synthesis level l = reduce .. wl - 1 the rectangle R_l of LL_l needs the
+ *      subband rectangle S_l = [max(0, floor(a / 2) - e), min(K, ceil(b / 2) + e)) per axis ([a, b) = R_l, K the
+ *      subband size, e = 1 for 5/3, 2 for 9/7), R_{l+1} = S_l; the call decodes the codeblocks that meet S_l in HL, LH
+ *      and HH of every such level and S_{wl-1} as LL_wl, and computes only that cone of the synthesis.
+ *      Row i of the window goes to d_out + i * out_pitch, w bytes; nothing else is written (not the gap between rows,
+ *      not past the last row); any alignment.  picsong_decode_frames_window: frame f at d_out + f * frame_stride,
+ *      byte-identical to n calls of picsong_decode_frame_window (n = 1..64, one launch per stage).
+ *      picsong_decode_rgb_frame_window: the inverse RCT / ICT of the three components' windows, the three planes with
+ *      the same pitch.  picsong_window_codeblocks: the codeblocks one call decodes (per frame, per component).
+ *      Refused (PICSONG_ERR_ARG, nothing launched): reduce outside 0..wl - 1, w < 1 or h < 1, a window not inside
+ *      paw x pah, out_pitch < w, frame_stride < (h - 1) * out_pitch + w (n > 1), the stream-stride and n checks of the
+ *      reduced calls, null pointers, -cp 3 contexts.  picsong_range_flag covers the codeblocks a call decodes (and
+ *      every length of the stream). ---- */
+int picsong_window_codeblocks(const picsong_ctx *ctx, int reduce, int x, int y, int w, int h, int *n_codeblocks);
+int picsong_decode_frame_window(picsong_ctx *ctx, const uint16_t *d_stream, int reduce, int x, int y, int w, int h,
+                                uint8_t *d_out, size_t out_pitch, void *stream);
+int picsong_decode_frames_window(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                 int x, int y, int w, int h, uint8_t *d_out, size_t out_pitch, size_t frame_stride,
+                                 void *stream);
+int picsong_decode_rgb_frame_window(picsong_ctx *ctx, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                    int x, int y, int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b,
+                                    size_t out_pitch, void *stream);
+
 /* ---- intra-frame sharding (BASELINE config 5): codeblocks are independent
  *      (correctCBBorders zeroes outside neighbours, BPC/BPCEngine.cu:465-484), so a rank can code
  *      the stripe [cb_begin, cb_begin + cb_count) of the frame's raster-ordered codeblocks.  The
