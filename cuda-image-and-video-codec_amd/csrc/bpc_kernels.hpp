@@ -54,6 +54,8 @@ struct LutGeo {
 
 constexpr int kBpcWinRects = 22;        // window calls: 3 (wl - r) + 1 rectangles at most (wl <= 7)
 
+struct PlaneRec;                        // (below: the k = 0 encoder's plane records)
+
 struct BpcArgs {
     const void *coeffs_in;         // encoder: Mallat T[AW*AH]
     int32_t *coeffs_out;           // decoder: Mallat int32[AW*AH]
@@ -84,6 +86,10 @@ struct BpcArgs {
     // codes with table lut_c[f] (same geometry); waves_per_frame is then a whole number of workgroups, a workgroup's
     // LDS copy of the table being its frame's.  lut_c[0] = nullptr: every frame uses `lut`
     const int32_t *lut_c[3];
+    // k = 0 encoder: the table's plane records (plane_record: picsong_ctx_set_lut* builds them), plane_img_recs(wl) of
+    // them; img_c[f] beside lut_c[f].  nullptr: the launch's workgroups build the records themselves from `lut`
+    const PlaneRec *plane_img;
+    const PlaneRec *img_c[3];
     // decoder, frame paths (k = 0, -cp 2): the codewords are read from the packed stream itself -- no unpack launch, no
     // staging.  cw16 = the frame's stream (9 header shorts, nCB x (MSB, length), the codewords: BitStreamBuilder.cu:106-137),
     // cw16_offsets[cb] = the scan of the lengths and *cw16_total the stream's length as they give it (scan_stream_kernel):
@@ -394,6 +400,58 @@ __device__ __forceinline__ PlaneLut plane_lut(const LutView &v, const LutGeo &g,
     pl.sig8 = lut_get<SINGLE>(v, si + 8);
     pl.sign = lut_get<SINGLE>(v, gi + 0) | (lut_get<SINGLE>(v, gi + 1) << 8) | (lut_get<SINGLE>(v, gi + 2) << 16) | (lut_get<SINGLE>(v, gi + 3) << 24);
     pl.sig8x4 = pl.sig8 * 0x01010101u;
+    return pl;
+}
+// ---- plane records: plane_lut<true> done once per table, not once per wave and plane -------------------------------
+// What plane_lut<true> returns depends on the table and on (subband group, bit-plane) alone, and a context's table stays
+// what it is from picsong_ctx_set_lut* on: the k = 0 encoder reads its planes' probabilities from an IMAGE of records
+// built when the context takes the table -- one 16-byte LDS read a plane where plane_lut forms three indices, reads 14
+// clamped bytes and packs them (83 vector instructions and 14 LDS reads, five times a typical wave), and a 16-byte
+// copy a thread at the start of a workgroup where lut_to_lds converts the 3360 int32 entries of the table to bytes.
+// Record [slot][bp], slot = level * 3 + sb as find_subband gives them (the group level * nSub + sb of the table: the
+// same number when nSub = 3), bp = 0 .. kMaxPlanes - 1: { sig0, sig1, sign, ref | sig8 << 8 }, every byte what
+// plane_lut<true> delivers -- the index clamped into the one table included (plane_record).
+struct alignas(16) PlaneRec { uint32_t sig0, sig1, sign, refsig8; };
+constexpr int kPlaneImgMaxWl = 7;                                       // picsong_ctx_create: wl 1..7
+constexpr int kPlaneImgMaxRecs = (3 * kPlaneImgMaxWl + 1) * kMaxPlanes;
+__host__ __device__ inline int plane_img_recs(int wl) { return (3 * wl + 1) * kMaxPlanes; }
+// one record from the int32 table as the setters hold it (host: picsong_ctx_set_lut_component; device:
+// plane_img_kernel for a caller's device table, and the encoder itself for a launch that comes without an image)
+__host__ __device__ inline PlaneRec plane_record(const int32_t *lut, const LutGeo &g, int slot, int bp)
+{
+    const int total = g.nRef + g.nSig + g.nSign;
+    const int grp = (slot / 3) * g.nSub + slot % 3;
+    const int ri = (grp * g.nBp + bp) * g.cRef;
+    const int si = (grp * g.nBp + bp) * g.cSig + g.nRef;
+    const int gi = (grp * g.nBp + bp) * g.cSign + g.nRef + g.nSig;
+    auto at = [&](int idx) -> uint32_t { return (uint32_t)lut[idx < 0 ? 0 : (idx >= total ? total - 1 : idx)] & 0xFFu; };
+    PlaneRec r;
+    r.sig0 = at(si + 0) | (at(si + 1) << 8) | (at(si + 2) << 16) | (at(si + 3) << 24);
+    r.sig1 = at(si + 4) | (at(si + 5) << 8) | (at(si + 6) << 16) | (at(si + 7) << 24);
+    r.sign = at(gi + 0) | (at(gi + 1) << 8) | (at(gi + 2) << 16) | (at(gi + 3) << 24);
+    r.refsig8 = at(ri) | (at(si + 8) << 8);
+    return r;
+}
+// the image of a caller's device table (picsong_ctx_set_lut_device), one block on the caller's stream
+__global__ __launch_bounds__(256) void plane_img_kernel(const int32_t *lut, LutGeo g, int wl, PlaneRec *img)
+{
+    for (int i = (int)threadIdx.x; i < plane_img_recs(wl); i += (int)blockDim.x) img[i] = plane_record(lut, g, i / kMaxPlanes, i % kMaxPlanes);
+}
+// start of a k = 0 encoder workgroup: its frame's image into LDS, 16 bytes a thread (wl = 5: one move each)
+__device__ __forceinline__ void plane_img_to_lds(const PlaneRec *img, const int32_t *lut, const LutGeo &g, int wl, PlaneRec *lds)
+{
+    const int n = plane_img_recs(wl);
+    if (img) { for (int i = (int)threadIdx.x; i < n; i += (int)blockDim.x) lds[i] = img[i]; }
+    else { for (int i = (int)threadIdx.x; i < n; i += (int)blockDim.x) lds[i] = plane_record(lut, g, i / kMaxPlanes, i % kMaxPlanes); }
+    __syncthreads();
+}
+__device__ __forceinline__ PlaneLut plane_lut_img(const PlaneRec *lds, int slot, int bp)
+{
+    const PlaneRec r = lds[slot * kMaxPlanes + bp];
+    PlaneLut pl;
+    pl.sig0 = r.sig0; pl.sig1 = r.sig1; pl.sign = r.sign;
+    pl.ref = r.refsig8 & 0xFFu; pl.sig8 = r.refsig8 >> 8;
+    pl.sig8x4 = __builtin_amdgcn_perm(r.refsig8, r.refsig8, 0x01010101u);      // byte 1 in all four
     return pl;
 }
 // Host side: may a context coding `wl` levels take this table array?  Returns nullptr, or why not (written into msg).
@@ -1339,7 +1397,8 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
 {
     static_assert(BULK || !COMPACT, "compact table copies belong to the -k > 0 instantiations");
     constexpr int kTab = COMPACT ? kBulkCompactBytes : kLutLdsMax;       // bytes of one LDS table copy
-    __shared__ uint8_t lds_lut[(BULK ? 2 : 1) * kTab];
+    // -k > 0: a byte copy of its table per codeblock; k = 0: the table's plane records (plane_img_to_lds)
+    __shared__ alignas(16) uint8_t lds_lut[BULK ? 2 * kTab : kPlaneImgMaxRecs * (int)sizeof(PlaneRec)];
     __shared__ uint32_t lds_cnt[2 * (BULK ? 1 : kBpcEncWgWaves)];      // codeword counters of the workgroup's codeblocks
     __shared__ uint8_t sign_tab[BULK ? 256 : 4];             // -k > 0: the bulk scan's sign contexts (sign_table2_fill)
     const uint32_t lane = threadIdx.x & 63u, half = lane >> 5, t = lane & 31u;
@@ -1357,7 +1416,10 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
             a.staging16 += (size_t)f * (size_t)a.AW * (size_t)a.AH;
             a.sizes += (size_t)f * (size_t)(a.nCB - a.cb_base);
             // (scalar selects: indexing the argument struct with f would move all of it to scratch memory)
-            if (a.lut_c[0]) a.lut = f == 0 ? a.lut_c[0] : (f == 1 ? a.lut_c[1] : a.lut_c[2]);
+            if (a.lut_c[0]) {
+                a.lut = f == 0 ? a.lut_c[0] : (f == 1 ? a.lut_c[1] : a.lut_c[2]);
+                a.plane_img = f == 0 ? a.img_c[0] : (f == 1 ? a.img_c[1] : a.img_c[2]);
+            }
         }
     }
     const int cb = a.cb_base + 2 * wave + (int)half;
@@ -1415,9 +1477,10 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
     LutGeo gl = a.g;                                         // (COMPACT: the copy's own section sizes and the lane's group in it)
     int grpc = grp;
     if constexpr (BULK) { cbp = bulk_setup<COMPACT>(a, coded, msb, cbx, cby, grp, t, lds_lut + half * kTab, bl, loff, gl, grpc); bl.sgt = sign_tab; }
-    else lut_to_lds(a.lut, a.g.nRef + a.g.nSig + a.g.nSign, lds_lut);
+    else plane_img_to_lds(a.plane_img, a.lut, a.g, a.wl, reinterpret_cast<PlaneRec *>(lds_lut));
     const LutView lv = { lds_lut + (BULK ? half * kTab : 0u), a.lut, a.g.nRef + a.g.nSig + a.g.nSign,
                          (a.g.nRef + a.g.nSig + a.g.nSign) * (BULK ? a.n_tables : 1), loff };
+    const PlaneRec *const recs = reinterpret_cast<const PlaneRec *>(lds_lut) + (level * 3 + sb) * kMaxPlanes;   // k = 0: the lane's group
 
     int np = coded ? (msb + 1 - cbp > 0 ? msb + 1 - cbp : 0) : 0;
     { int o = __shfl_xor(np, 32); np = np > o ? np : o; }
@@ -1467,7 +1530,7 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
         const bool act = live && bp >= cbp;
 
         PlaneLut pl = { 0u, 0u, 0u, 0u, 0u, 0u };
-        if (act) pl = plane_lut<!BULK>(lv, gl, grpc, bp);
+        if (act) { if constexpr (BULK) pl = plane_lut<false>(lv, gl, grpc, bp); else pl = plane_lut_img(recs, 0, bp); }
 
         const U64 BL = BLn, BR = BRn;
         const U64 AL2 = u_or(AL, BL), AR2 = u_or(AR, BR);            // state after this plane's SPP

@@ -5,8 +5,8 @@
 // buildCodeStreamLUTBS (reference BitStreamBuilder/BitStreamBuilder.cu:33-171,198-229,290-323).
 // The stream layout is the reference's; the method is not: the reference launches
 // one thread per staged value and binary-searches the prefix array through a 256-entry index;
-// here one workgroup owns one codeblock, so both sides of the copy are contiguous bursts and no
-// search exists.  The scan is a single-workgroup wave scan (nCB <= 65,536).
+// here one workgroup (one wave, over the encoders' 16-bit staging) owns one codeblock, so both sides of the copy are
+// contiguous bursts and no search exists.  The scan is a single-workgroup wave scan (nCB <= 65,536).
 // (Round 2 measured the scan folded away -- a workgroup per group of 1..16 codeblocks summing the lengths before
 // its group itself, sixteen loads in flight, the group's payload copied as one run: bit-identical, one launch
 // instead of two (three on the decoder's side), and SLOWER: 31 us against 8 + 14.5 for an 8K frame, 146 against
@@ -90,19 +90,27 @@ __global__ __launch_bounds__(1024) void scan_sizes_kernel(const int32_t *sizes, 
     if (tid == (int)blockDim.x - 1) *total = 9 + 2 * n + (base + inc) + 1;
 }
 
-// one workgroup per codeblock (buildBitStreamLUTBS BitStreamBuilder.cu:106-137 layout); blockIdx.y = frame
-// of a batched launch (staging advances by frame_words, sizes / offsets by n, total by 1, out by
+// one codeblock per workgroup (W = int32_t) or per WAVE (W = uint16_t); buildBitStreamLUTBS BitStreamBuilder.cu:106-137
+// layout; blockIdx.y = frame of a batched launch (staging advances by frame_words, sizes / offsets by n, total by 1, out by
 // out_stride shorts; only the frame hdr.has - 1 == blockIdx.y carries the populated header -- has = 0: none;
 // has < 0: -has is a bit mask of the frames that carry it (the components of an RGB frame))
 // W = the staging's word: uint16_t, the encoders' own (BpcArgs::staging16: the frame paths), or int32_t, the reference's
 // array as a caller of picsong_bitstream_pack holds it
+constexpr int kPack16Waves = 4;                            // 16-bit staging: codeblocks (waves) a workgroup
+// workgroups of a launch over n codeblocks (grid.x; a larger grid's extra waves of the 16-bit form do nothing)
+template <typename W>
+__host__ __device__ inline unsigned pack_blocks(int n) { return sizeof(W) == 2 ? (unsigned)((n + kPack16Waves - 1) / kPack16Waves) : (unsigned)n; }
 template <typename W>
 __global__ __launch_bounds__(256) void pack_kernel(const W *staging, const int32_t *sizes,
                                                    const int32_t *offsets, const int32_t *total, int n,
                                                    HeaderArg hdr, uint16_t *out, size_t frame_words = 0,
                                                    size_t out_stride = 0)
 {
-    const int cb = blockIdx.x, tid = threadIdx.x;
+    // 16-bit staging: ONE WAVE per codeblock, four to a workgroup.  (A workgroup per codeblock was eight waves for 613
+    // bytes each at 8K: 71 vector and 82 scalar instructions a wave, nearly all of it the same setup eight times over.)
+    const int tid = sizeof(W) == 2 ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
+    const int cb = sizeof(W) == 2 ? (int)blockIdx.x * kPack16Waves + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)blockIdx.x;
+    if (cb >= n) return;
     {
         const size_t f = blockIdx.y;
         staging += f * frame_words; sizes += f * (size_t)n; offsets += f * (size_t)n; total += f; out += f * out_stride;
@@ -112,29 +120,34 @@ __global__ __launch_bounds__(256) void pack_kernel(const W *staging, const int32
     const int len = sizes[cb];
     uint16_t *dst = out + 9 + 2 * (size_t)n + (size_t)offsets[cb];
     if constexpr (sizeof(W) == 2) {
-        // 16-bit staging: the copy moves PAIRS of words -- a dword load from staging word 1 + 2 p, a dword store to
-        // stream short 2 p (either may sit at an odd short: the target takes unaligned dword accesses) -- so a codeblock's
-        // 4095 words are at most eight pairs a thread, all eight loads ahead of the stores; an odd count's last word is
-        // stored as a short.
-        const int nw = len - 1, np = (nw + 1) >> 1;
-        uint32_t v[8];
-        if (np > 0) {
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                // (no branch around a load: a thread without a pair re-reads the last one; the one pair that would
-                // reach past the codeblock's 4096 words -- word 4095 of a raw block -- reads words 4094, 4095 instead)
-                const int pr = tid + 256 * q, pc = pr < np ? pr : np - 1;
-                const int w0 = 1 + 2 * pc, wl = w0 < 4094 ? w0 : 4094;
-                __builtin_memcpy(&v[q], st + wl, 4);
-                if (wl != w0) v[q] >>= 16;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int pr = tid + 256 * q;
-            if (pr < np) {
-                if (2 * pr + 1 < nw) __builtin_memcpy(dst + 2 * pr, &v[q], 4);
-                else dst[2 * pr] = (uint16_t)v[q];
+        // The copy moves 16-byte CHUNKS -- chunk i is staging words 1 + 8 i .. 8 + 8 i and stream shorts 8 i .. 8 i + 7;
+        // both sides sit at any short, the target takes unaligned accesses of every width -- four a lane and round, all
+        // four loads ahead of the stores: one round for up to 2048 codewords, two for the longest codeblock (4095).  A
+        // count that is no multiple of eight ends with a chunk that ENDS with the last word and overlaps the one before
+        // (the same shorts stored twice); fewer than eight words go one a lane.  No branch around a load: a lane without
+        // a chunk reads the last one.
+        const uint32_t nw = len < 1 ? 0u : (len > 4096 ? 4095u : (uint32_t)(len - 1));   // (the encoders' lengths are 1 .. 4096)
+        const char *const src = reinterpret_cast<const char *>(st + 1);
+        char *const dstb = reinterpret_cast<char *>(dst);
+        if (nw < 8u) {
+            const uint16_t tv = st[1u + ((uint32_t)tid < nw ? (uint32_t)tid : 0u)];
+            if ((uint32_t)tid < nw) dst[tid] = tv;
+        } else {
+            const uint32_t nch = (nw + 7u) >> 3, last = 2u * nw - 16u;      // chunks; byte offset of the last one
+            // (four named chunks, not an array: one the optimiser does not take apart in time ends up in LDS)
+            auto chunk_at = [&](uint32_t ci) { return 16u * ci < last ? 16u * ci : last; };
+            auto load_chunk = [&](uint32_t ci) { uint4 r; __builtin_memcpy(&r, src + chunk_at(ci), 16); return r; };
+            auto store_chunk = [&](uint32_t ci, const uint4 &r) { if (ci < nch) __builtin_memcpy(dstb + chunk_at(ci), &r, 16); };
+#pragma clang loop unroll(disable)
+            for (uint32_t c0 = 0; c0 < nch; c0 += 256u) {
+                const uint32_t ci = c0 + (uint32_t)tid;
+                uint4 v0 = load_chunk(ci);
+                const uint4 v1 = load_chunk(ci + 64u), v2 = load_chunk(ci + 128u), v3 = load_chunk(ci + 192u);
+                // (the first chunk's load would otherwise sink into the branch around its store, behind the wait for it)
+#if defined(__AMDGCN__)
+                asm volatile("" : "+v"(v0.x));
+#endif
+                store_chunk(ci, v0); store_chunk(ci + 64u, v1); store_chunk(ci + 128u, v2); store_chunk(ci + 192u, v3);
             }
         }
     } else {

@@ -61,6 +61,7 @@ struct picsong_ctx {
     int32_t *d_lut[3];
     bool has_lut[3];
     bool lut_borrowed[3]; // d_lut[k] is the caller's device table (picsong_ctx_set_lut_device): not freed here
+    PlaneRec *d_img[3];   // k = 0, -cp 2: the table's plane records for the encoder (plane_record), kPlaneImgMaxRecs
     // small scratch
     int32_t *d_offsets;   // nCB
     uint32_t *d_plane_scratch;   // encoder: planes below the 8 held in registers, 8 KB per wave (lazy)
@@ -447,6 +448,8 @@ void picsong_ctx_destroy(picsong_ctx *c)
     (void)hipSetDevice(c->device);
     for (int k = 0; k < 3; k++)
         if (c->d_lut[k] && !c->lut_borrowed[k]) (void)hipFree(c->d_lut[k]);
+    for (int k = 0; k < 3; k++)
+        if (c->d_img[k]) (void)hipFree(c->d_img[k]);
     if (c->d_offsets) (void)hipFree(c->d_offsets);
     if (c->d_plane_scratch) (void)hipFree(c->d_plane_scratch);
     if (c->d_total) (void)hipFree(c->d_total);
@@ -484,6 +487,42 @@ static int lut_admit(const picsong_ctx *c, const picsong_lut_info &li, int n_tab
     return PICSONG_OK;
 }
 
+// The k = 0 encoder's image of component comp's table (bpc_kernels.hpp, plane records).  A host table's records are
+// built here, once, when the context takes it; a caller's device table may change under the context as it always
+// could, so its records are rebuilt from it by one small block ahead of every encoder launch, on that launch's stream
+// (plane_img_refresh).  Contexts that code with -k > 0 or -cp 3 keep no image.
+static bool ctx_uses_plane_img(const picsong_ctx *c) { return !(c->p.k > 0.0f) && c->p.cp != 3; }
+static LutGeo lut_geo(const picsong_lut_info &li)
+{
+    LutGeo g;
+    g.nBp = li.n_bitplanes; g.nSub = li.n_subbands; g.cRef = li.ctx_ref; g.cSign = li.ctx_sign; g.cSig = li.ctx_sig;
+    g.prec = li.precision; g.nRef = li.n_ref; g.nSig = li.n_sig; g.nSign = li.n_sign;
+    return g;
+}
+static int plane_img_alloc(picsong_ctx *c, int comp)
+{
+    if (!c->d_img[comp]) HIP_TRY(hipMalloc(&c->d_img[comp], kPlaneImgMaxRecs * sizeof(PlaneRec)));
+    return PICSONG_OK;
+}
+static int plane_img_from_host(picsong_ctx *c, int comp, const picsong_lut_info &li, const int32_t *host_table)
+{
+    if (!ctx_uses_plane_img(c)) return PICSONG_OK;
+    if (int rc = plane_img_alloc(c, comp)) return rc;
+    const LutGeo g = lut_geo(li);
+    std::vector<PlaneRec> img((size_t)plane_img_recs(c->p.wl));
+    for (size_t i = 0; i < img.size(); i++) img[i] = plane_record(host_table, g, (int)i / kMaxPlanes, (int)i % kMaxPlanes);
+    HIP_TRY(hipMemcpy(c->d_img[comp], img.data(), img.size() * sizeof(PlaneRec), hipMemcpyHostToDevice));
+    return PICSONG_OK;
+}
+// ahead of a k = 0 encoder launch on stream s
+static int plane_img_refresh(picsong_ctx *c, int comp, hipStream_t s)
+{
+    if (!ctx_uses_plane_img(c) || !c->lut_borrowed[comp]) return PICSONG_OK;
+    plane_img_kernel<<<1, 256, 0, s>>>(c->d_lut[comp], lut_geo(c->li[comp]), c->p.wl, c->d_img[comp]);
+    HIP_TRY(hipGetLastError());
+    return PICSONG_OK;
+}
+
 int picsong_ctx_set_lut_component(picsong_ctx *c, int comp, const picsong_lut_info *info, const int32_t *host_table)
 {
     if (!c || !info || !host_table) return fail(PICSONG_ERR_ARG, "set_lut: null argument");
@@ -508,6 +547,7 @@ int picsong_ctx_set_lut_component(picsong_ctx *c, int comp, const picsong_lut_in
             return fail(PICSONG_ERR_ARG, "LUT entry %zu = %d outside 0..255", i, host_table[i]);
     if (int rc = lut_admit(c, *info, n_tables)) return rc;
     HIP_TRY(hipSetDevice(c->device));
+    if (int rc = plane_img_from_host(c, comp, *info, host_table)) return rc;
     if (c->d_lut[comp] && !c->lut_borrowed[comp]) (void)hipFree(c->d_lut[comp]);
     c->d_lut[comp] = nullptr;
     c->lut_borrowed[comp] = false;
@@ -548,6 +588,10 @@ int picsong_ctx_set_lut_device(picsong_ctx *c, int comp, const picsong_lut_info 
                     (cp3 ? kLutLdsMax3 : kLutLdsMax) - kLutSlack);
     if (li.n_tables <= 0) li.n_tables = 1;
     if (int rc = lut_admit(c, li, li.n_tables)) return rc;
+    if (ctx_uses_plane_img(c)) {
+        HIP_TRY(hipSetDevice(c->device));
+        if (int rc = plane_img_alloc(c, comp)) return rc;
+    }
     if (c->d_lut[comp] && !c->lut_borrowed[comp]) (void)hipFree(c->d_lut[comp]);
     c->d_lut[comp] = const_cast<int32_t *>(d_table);
     c->lut_borrowed[comp] = true;
@@ -764,6 +808,7 @@ static int bpc_args(picsong_ctx *c, BpcArgs &a, int comp = 0)
     const picsong_lut_info &li = c->li[comp];
     a.AW = c->aw; a.AH = c->ah; a.wl = c->p.wl; a.nCB = c->ncb; a.ncx = c->aw / PICSONG_CB;
     a.lut = c->d_lut[comp];
+    a.plane_img = ctx_uses_plane_img(c) ? c->d_img[comp] : nullptr;
     a.g.nBp = li.n_bitplanes; a.g.nSub = li.n_subbands; a.g.cRef = li.ctx_ref;
     a.g.cSign = li.ctx_sign; a.g.cSig = li.ctx_sig; a.g.prec = li.precision;
     a.g.nRef = li.n_ref; a.g.nSig = li.n_sig; a.g.nSign = li.n_sign;
@@ -831,7 +876,10 @@ static int bpc_encode_impl(picsong_ctx *c, const void *d_coeffs, uint16_t *d_sta
         if (bulk_compact(c, comp) && c->pipelined) bpc_encode_kernel<true, true><<<(unsigned)((cb_count + 1) / 2), 64, 0, s>>>(a);
         else bpc_encode_kernel<true><<<(unsigned)((cb_count + 1) / 2), 64, 0, s>>>(a);
     }
-    else bpc_encode_kernel<false><<<(unsigned)(((cb_count + 1) / 2 + kBpcEncWgWaves - 1) / kBpcEncWgWaves), 64 * kBpcEncWgWaves, 0, s>>>(a);
+    else {
+        if (int rc2 = plane_img_refresh(c, comp, s)) return rc2;
+        bpc_encode_kernel<false><<<(unsigned)(((cb_count + 1) / 2 + kBpcEncWgWaves - 1) / kBpcEncWgWaves), 64 * kBpcEncWgWaves, 0, s>>>(a);
+    }
     HIP_TRY(hipGetLastError());
     return PICSONG_OK;
 }
@@ -1031,7 +1079,7 @@ static int pack_range(picsong_ctx *c, const W *d_staging, const int32_t *d_sizes
     c->last_batch = 0;                                      // the most recent total is d_total (picsong_copy_last_totals)
     scan_sizes_kernel<<<1, scan_threads(n), 0, s>>>(d_sizes, n, c->d_offsets, c->d_total);
     HIP_TRY(hipGetLastError());
-    pack_kernel<W><<<(unsigned)n, 256, 0, s>>>(d_staging, d_sizes, c->d_offsets, c->d_total, n, h, d_stream);
+    pack_kernel<W><<<pack_blocks<W>(n), 256, 0, s>>>(d_staging, d_sizes, c->d_offsets, c->d_total, n, h, d_stream);
     HIP_TRY(hipGetLastError());
     return PICSONG_OK;
 }
@@ -1429,7 +1477,10 @@ int picsong_encode_frames(picsong_ctx *c, int n, const uint8_t *d_frames, size_t
     a.frames = n; a.waves_per_frame = wpf; a.coef_z = coef_z;
     const size_t waves = (size_t)n * (size_t)wpf;
     if (a.k > 0.0f) launch_bulk_encode_frames(c, a, (unsigned)n, bulk_compact(c, 0), s);
-    else bpc_encode_kernel<false><<<(unsigned)((waves + kBpcEncWgWaves - 1) / kBpcEncWgWaves), 64 * kBpcEncWgWaves, 0, s>>>(a);
+    else {
+        if ((rc = plane_img_refresh(c, 0, s))) return rc;
+        bpc_encode_kernel<false><<<(unsigned)((waves + kBpcEncWgWaves - 1) / kBpcEncWgWaves), 64 * kBpcEncWgWaves, 0, s>>>(a);
+    }
     HIP_TRY(hipGetLastError());
 
     if (ev) HIP_TRY(hipEventRecord(ev[2], s));
@@ -1444,7 +1495,7 @@ int picsong_encode_frames(picsong_ctx *c, int n, const uint8_t *d_frames, size_t
     }
     scan_sizes_kernel<<<(unsigned)n, scan_threads(c->ncb), 0, s>>>(c->b_sizes, c->ncb, c->b_offsets, c->b_total);
     HIP_TRY(hipGetLastError());
-    pack_kernel<uint16_t><<<dim3((unsigned)c->ncb, (unsigned)n), 256, 0, s>>>(a.staging16, c->b_sizes, c->b_offsets, c->b_total,
+    pack_kernel<uint16_t><<<dim3(pack_blocks<uint16_t>(c->ncb), (unsigned)n), 256, 0, s>>>(a.staging16, c->b_sizes, c->b_offsets, c->b_total,
                                                                               c->ncb, h, d_streams, c->P, stream_stride);
     HIP_TRY(hipGetLastError());
     if (ev) HIP_TRY(hipEventRecord(ev[3], s));
@@ -1665,7 +1716,7 @@ static int bpc_args_rgb(picsong_ctx *c, BpcArgs &a)
             x.n_ref != y.n_ref || x.n_sig != y.n_sig || x.n_sign != y.n_sign || x.n_tables != y.n_tables)
             return fail(PICSONG_ERR_ARG, "the components' tables differ in geometry: code the planes one by one (picsong_encode_plane)");
     }
-    for (int k = 0; k < 3; k++) a.lut_c[k] = c->d_lut[k];
+    for (int k = 0; k < 3; k++) { a.lut_c[k] = c->d_lut[k]; a.img_c[k] = ctx_uses_plane_img(c) ? c->d_img[k] : nullptr; }
     const int wpf = (c->ncb + 1) / 2;
     a.cb_base = 0; a.nCB = c->ncb;
     a.frames = 3; a.waves_per_frame = (wpf + kBpcEncWgWaves - 1) / kBpcEncWgWaves * kBpcEncWgWaves;
@@ -1732,6 +1783,7 @@ int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *
     if (a.k > 0.0f) {
         launch_bulk_encode_frames(c, a, 3u, bulk_compact(c, 0) && bulk_compact(c, 1) && bulk_compact(c, 2), s);
     } else {
+        for (int k = 0; k < 3; k++) if ((rc = plane_img_refresh(c, k, s))) return rc;
         bpc_encode_kernel<false><<<(unsigned)(3 * a.waves_per_frame / kBpcEncWgWaves), 64 * kBpcEncWgWaves, 0, s>>>(a);
     }
     HIP_TRY(hipGetLastError());
@@ -1746,7 +1798,7 @@ int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *
     }
     scan_sizes_kernel<<<3, scan_threads(c->ncb), 0, s>>>(c->b_sizes, c->ncb, c->b_offsets, c->b_total);
     HIP_TRY(hipGetLastError());
-    pack_kernel<uint16_t><<<dim3((unsigned)c->ncb, 3u), 256, 0, s>>>(a.staging16, c->b_sizes, c->b_offsets, c->b_total, c->ncb, h,
+    pack_kernel<uint16_t><<<dim3(pack_blocks<uint16_t>(c->ncb), 3u), 256, 0, s>>>(a.staging16, c->b_sizes, c->b_offsets, c->b_total, c->ncb, h,
                                                           d_streams, c->P, stream_stride);
     HIP_TRY(hipGetLastError());
     c->last_batch = 3;

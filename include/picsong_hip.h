@@ -128,7 +128,10 @@ int  picsong_ctx_set_lut_component(picsong_ctx *ctx, int component, const picson
  * (`int* LUTInformation` + six integers, BPC/BPCEngine.hpp:16-17; Engine::initLUT made that copy,
  * Engines/Engine.cu:111-136).  This adopts such a caller-owned device table for component slot c without
  * copying it: it must stay valid while the context uses it.  info->n_ref / n_sig / n_sign == 0 are derived
- * from the geometry and the context's wl (IO/IOManager.ipp:431-433). */
+ * from the geometry and the context's wl (IO/IOManager.ipp:431-433).
+ * The k = 0 encoder codes from an image of per-(subband group, bit-plane) records of the table.  For a host table the
+ * setter builds it once; for a table adopted here one small block rebuilds it from the table ahead of every encoder
+ * launch, on that launch's stream, so the entries may change between calls as they always could. */
 int  picsong_ctx_set_lut_device(picsong_ctx *ctx, int component, const picsong_lut_info *info,
                                 const int32_t *d_table);
 
