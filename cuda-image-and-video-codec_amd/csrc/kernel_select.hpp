@@ -1,0 +1,206 @@
+// kernel_select.hpp -- which template instantiation of a kernel a planned launch takes, with its grid and its scratch
+// (pure host code, no device code: functions from a plan's fields or a coder's mode flags to a kernel function pointer).
+// The one copy of that policy: the C-ABI implementation (picsong_hip.hip) writes select_x(...)<<<grid, block, 0, s>>>(args),
+// the CPU wave-emulator drivers (tests/hipemu/) emu::launch(grid, block, [&] { k(args); }) on the same pointer.
+// What the environment says arrives as a parameter (lean97, the coders' `compact`): each caller reads its switches at
+// the moment it always did.
+#pragma once
+#include <string.h>
+
+#include "bpc_kernels.hpp"
+#include "dwt_kernels.hpp"
+#include "launch_plan.hpp"
+#include "pack_kernels.hpp"
+#include "window_kernels.hpp"
+
+namespace picsong {
+
+using FwdKernel = void (*)(DwtFwdArgs);
+using Fwd2Kernel = void (*)(DwtFwd2Args);
+using InvKernel = void (*)(DwtInvArgs);
+using Inv2Kernel = void (*)(DwtInv2Args);
+using InvRgbKernel = void (*)(DwtInvArgs, uint8_t *, uint8_t *, uint8_t *);
+using WinKernel = void (*)(WinSynArgs);
+using BpcKernel = void (*)(BpcArgs);
+
+// ---- forward transform: one level (256 threads, grid f.gx x f.gy x frames)
+template <int BAND, bool VEC>
+inline FwdKernel fwd_kernel_of(bool lossy, bool u8)
+{
+    if (lossy) return u8 ? dwt_fwd_kernel<float, true, true, BAND, VEC> : dwt_fwd_kernel<float, true, false, BAND, VEC>;
+    return u8 ? dwt_fwd_kernel<int, false, true, BAND, VEC> : dwt_fwd_kernel<int, false, false, BAND, VEC>;
+}
+inline FwdKernel select_fwd(bool lossy, const FwdLaunch &f)
+{
+    switch (f.band) {
+    case 32: return f.vec ? fwd_kernel_of<32, true>(lossy, f.u8) : fwd_kernel_of<32, false>(lossy, f.u8);
+    case 16: return f.vec ? fwd_kernel_of<16, true>(lossy, f.u8) : fwd_kernel_of<16, false>(lossy, f.u8);
+    case 8: return f.vec ? fwd_kernel_of<8, true>(lossy, f.u8) : fwd_kernel_of<8, false>(lossy, f.u8);
+    default: return f.vec ? fwd_kernel_of<4, true>(lossy, f.u8) : fwd_kernel_of<4, false>(lossy, f.u8);
+    }
+}
+
+// ---- the fused forward head, levels 0 and 1 (256 threads, grid f2.gx x f2.gy x frames)
+// c16: coded subbands as int16 (DwtFwdArgs::c16); rgb: the colour transform in the load stage, grid.z = component
+// (RCT on the integer head, ICT on the 9/7 one; plan_dwt_fwd2 with kF2PairsRgb, always 16-bit)
+inline Fwd2Kernel select_fwd2(bool lossy, bool c16, bool rgb = false)
+{
+    if (rgb) return lossy ? dwt_fwd2_kernel<float, true, true, kF2PairsRgb, true, true> : dwt_fwd2_kernel<int, false, true, kF2PairsRgb, true, true>;
+    if (c16) return lossy ? dwt_fwd2_kernel<float, true, true, kF2PairsLossy, true> : dwt_fwd2_kernel<int, false, true, kF2Pairs, true>;
+    return lossy ? dwt_fwd2_kernel<float, true, true, kF2PairsLossy> : dwt_fwd2_kernel<int, false, true, kF2Pairs>;
+}
+
+// ---- synthesis: one level (256 threads, grid f.gx x f.gy x frames)
+template <int BAND, bool C16>
+inline InvKernel inv97_kernel_of(const DwtInvArgs &a)
+{
+    if (a.dst_u8) return a.one_div ? dwt_inv97_kernel<BAND, true, false, true, C16> : dwt_inv97_kernel<BAND, true, false, false, C16>;
+    if (a.first) return a.one_div ? dwt_inv97_kernel<BAND, false, true, true, C16> : dwt_inv97_kernel<BAND, false, true, false, C16>;
+    return a.one_div ? dwt_inv97_kernel<BAND, false, false, true, C16> : dwt_inv97_kernel<BAND, false, false, false, C16>;
+}
+template <int BAND, bool VEC, bool U8OUT>
+inline InvKernel inv_kernel_of(bool lossy, bool fast)
+{
+    if (lossy && fast) return dwt_inv_kernel<float, true, BAND, VEC, U8OUT, true>;
+    if (lossy) return dwt_inv_kernel<float, true, BAND, VEC, U8OUT>;
+    return dwt_inv_kernel<int, false, BAND, VEC, U8OUT>;
+}
+template <int BAND>
+inline InvKernel inv_level_of(bool lossy, bool lean97, const InvLaunch &f)
+{
+    if (f.a.c16) {
+        // the decode frame paths' 16-bit coefficients (dec_c16_ok: vector kernels, 9/7 through the lean kernel, the
+        // coarsest level never the one that writes pixels)
+        if (lossy) return inv97_kernel_of<BAND, true>(f.a);
+        return f.a.dst_u8 ? dwt_inv_kernel<int, false, BAND, true, true, false, true> : dwt_inv_kernel<int, false, BAND, true, false, false, true>;
+    }
+    // f.fast: the 9/7 divisions in their reciprocal form (verified for the context's qs at creation); the vector
+    // launches of such a context are the lean kernel's (lean97 = false, PICSONG_DWT_INV97=0: dwt_inv_kernel's FAST
+    // instantiations)
+    // (a coarsest level that also writes pixels, wl = 1, stays with dwt_inv_kernel)
+    if (lossy && f.fast && lean97 && f.vec && !(f.a.first && f.a.dst_u8)) return inv97_kernel_of<BAND, false>(f.a);
+    if (f.vec && f.a.dst_u8) return inv_kernel_of<BAND, true, true>(lossy, f.fast);   // finest level of the frame path: pixels out, clamp fused
+    return f.vec ? inv_kernel_of<BAND, true, false>(lossy, f.fast) : inv_kernel_of<BAND, false, false>(lossy, f.fast);
+}
+inline InvKernel select_inv(bool lossy, bool lean97, const InvLaunch &f)
+{
+    switch (f.band) {
+    case 32: return inv_level_of<32>(lossy, lean97, f);
+    case 16: return inv_level_of<16>(lossy, lean97, f);
+    case 8: return inv_level_of<8>(lossy, lean97, f);
+    default: return inv_level_of<4>(lossy, lean97, f);
+    }
+}
+
+// ---- the fused synthesis pair, levels 1 and 0 (plan_dwt_inv2; 256 threads, grid f2.gx x f2.gy x frames)
+inline Inv2Kernel select_inv2(bool lossy, bool one_div)
+{
+    if (!lossy) return dwt_inv2_kernel<false, false>;
+    return one_div ? dwt_inv2_kernel<true, true> : dwt_inv2_kernel<true, false>;
+}
+
+// ---- the fused RGB synthesis tails: the finest level of the three components + the inverse colour transform as one
+// launch.  5/3: dwt_inv_rgb_kernel on the level's own grid; 9/7: dwt_inv97_rgb_kernel, the components as the three
+// waves of a workgroup, one strip a workgroup.
+struct InvRgbLaunch { InvRgbKernel kernel; unsigned gx, gy, threads; };
+inline InvRgbLaunch select_inv_rgb(bool lossy, const InvLaunch &f)
+{
+    if (!lossy) {
+        switch (f.band) {
+        case 32: return { dwt_inv_rgb_kernel<32>, f.gx, f.gy, 256 };
+        case 16: return { dwt_inv_rgb_kernel<16>, f.gx, f.gy, 256 };
+        case 8: return { dwt_inv_rgb_kernel<8>, f.gx, f.gy, 256 };
+        default: return { dwt_inv_rgb_kernel<4>, f.gx, f.gy, 256 };
+        }
+    }
+    const unsigned gx = (unsigned)((f.a.W + kStripUseful - 1) / kStripUseful);
+    switch (f.band) {
+    case 32: return { f.a.one_div ? dwt_inv97_rgb_kernel<32, true> : dwt_inv97_rgb_kernel<32, false>, gx, f.gy, 192 };
+    case 16: return { f.a.one_div ? dwt_inv97_rgb_kernel<16, true> : dwt_inv97_rgb_kernel<16, false>, gx, f.gy, 192 };
+    case 8: return { f.a.one_div ? dwt_inv97_rgb_kernel<8, true> : dwt_inv97_rgb_kernel<8, false>, gx, f.gy, 192 };
+    default: return { f.a.one_div ? dwt_inv97_rgb_kernel<4, true> : dwt_inv97_rgb_kernel<4, false>, gx, f.gy, 192 };
+    }
+}
+
+// ---- the window synthesis (256 threads, the WinLaunch's grid)
+inline WinKernel select_window(bool lossy, bool u8)
+{
+    if (lossy) return u8 ? dwt_window_kernel<float, true> : dwt_window_kernel<float, false>;
+    return u8 ? dwt_window_kernel<int, true> : dwt_window_kernel<int, false>;
+}
+
+// ---- the coders: kernel, threads a workgroup, workgroups for `waves` waves (a wave codes a codeblock pair), and the
+// dwords of BpcArgs::plane_scratch the launch needs (whole workgroups)
+struct BpcLaunch { BpcKernel kernel; unsigned threads, wgs; size_t scratch_dwords; };
+inline BpcLaunch bpc_launch(BpcKernel kernel, int wg_waves, unsigned waves)
+{
+    const unsigned wgs = (waves + (unsigned)wg_waves - 1) / (unsigned)wg_waves;
+    return { kernel, 64u * (unsigned)wg_waves, wgs, (size_t)wgs * (size_t)wg_waves * kEncScratchDwordsPerWave };
+}
+// cp3: three coding passes, one kernel for both directions (bpc3_kernel).  bulk (-k > 0): the BULK instantiation (bulk
+// scan below the consecutive bit-planes, tables in LDS), one-wave workgroups.
+// Two instantiations of the -k > 0 encoder: with compact table copies it is asked for six waves a SIMD (80
+// registers, some of its prologue spilled) -- what frames in flight want: 133 -> 142 Gpixel/s at k = 0.5; with
+// whole tables its LDS bounds it to four waves anyway, it takes 102 registers and spills nothing -- what a lone
+// frame wants, whose 4080 waves are four to a SIMD whatever the kernel allows: 0.376 against 0.411 ms.  The
+// context's hint (picsong_ctx_set_pipelined) chooses: compact_pipelined = the tables fit the compact copies
+// (bulk_compact) and the hint is set.
+inline BpcLaunch select_encoder(bool cp3, bool bulk, bool compact_pipelined, unsigned waves)
+{
+    if (cp3) return bpc_launch(bpc3_kernel<false>, kBpc3WgWaves, waves);
+    if (bulk) return bpc_launch(compact_pipelined ? bpc_encode_kernel<true, true> : bpc_encode_kernel<true>, 1, waves);
+    return bpc_launch(bpc_encode_kernel<false>, kBpcEncWgWaves, waves);
+}
+// compact (-k > 0): the COMPACT table copies (bulk_compact); from_stream: the codewords come from the packed stream
+// (BpcArgs::cw16*), not the staging; c16 (with from_stream only): the coefficients leave as an int16 Mallat array.
+// kernel = nullptr: refused -- the 16-bit coefficient form decodes from the stream itself.
+// (-k > 0 is one launch: the two-pass planes are parked in the scratch whatever their number)
+inline BpcLaunch select_decoder(bool cp3, bool bulk, bool compact, bool from_stream, bool c16, unsigned waves)
+{
+    if (c16 && !from_stream) return { nullptr, 0, 0, 0 };
+    if (cp3) return bpc_launch(bpc3_kernel<true>, kBpc3WgWaves, waves);
+    if (bulk) {
+        BpcKernel k = compact ? bpc_decode_kernel<true, kDecSmallPlanes, false, false, true> : bpc_decode_kernel<true, kDecSmallPlanes>;
+        if (c16) k = compact ? bpc_decode_kernel<true, kDecSmallPlanes, true, true, true> : bpc_decode_kernel<true, kDecSmallPlanes, true, true>;
+        else if (from_stream) k = compact ? bpc_decode_kernel<true, kDecSmallPlanes, true, false, true> : bpc_decode_kernel<true, kDecSmallPlanes, true>;
+        return bpc_launch(k, 1, waves);
+    }
+    if (c16) return bpc_launch(bpc_decode_kernel<false, kDecSmallPlanes, true, true>, kBpcDecWgWaves, waves);
+    if (from_stream) return bpc_launch(bpc_decode_kernel<false, kDecSmallPlanes, true>, kBpcDecWgWaves, waves);
+    return bpc_launch(bpc_decode_kernel<false, kDecSmallPlanes>, kBpcDecWgWaves, waves);
+}
+
+// ---- helpers of both sides
+// geo: the nine fields in LutGeo's order (the emulator's entry points take them so)
+inline LutGeo lut_geo(int nBp, int nSub, int cRef, int cSign, int cSig, int prec, int nRef, int nSig, int nSign)
+{
+    return LutGeo{ nBp, nSub, cRef, cSign, cSig, prec, nRef, nSig, nSign };
+}
+inline LutGeo lut_geo(const int *geo) { return lut_geo(geo[0], geo[1], geo[2], geo[3], geo[4], geo[5], geo[6], geo[7], geo[8]); }
+
+// the base BpcArgs of a frame: geometry, table, flag; everything else 0
+inline BpcArgs bpc_frame_args(int aw, int ah, int wl, const int32_t *lut, const LutGeo &g, int *range_flag)
+{
+    BpcArgs a;
+    memset(&a, 0, sizeof a);
+    a.AW = aw; a.AH = ah; a.wl = wl; a.ncx = aw / 64; a.nCB = (aw / 64) * (ah / 64);
+    a.lut = lut; a.g = g; a.range_flag = range_flag;
+    return a;
+}
+
+// -k > 0: does the table geometry let every codeblock of the frame use the COMPACT LDS copies (bulk_max_span_bytes: the
+// geometry's widest codeblock)?  (PICSONG_BULK_FULLTAB=1 keeps the whole-table instantiations: the callers' switch)
+inline bool bulk_compact(int aw, int ah, int wl, const LutGeo &g)
+{
+    return bulk_max_span_bytes(aw, ah, wl, g.nBp, g.nSub, g.cRef, g.cSig, g.cSign) <= kBulkCompactBytes;
+}
+
+// workgroups (256 threads) of the element-wise kernels -- level shift, clamp, RGB transforms -- over n items, grid-stride
+// beyond `cap`
+inline unsigned elementwise_blocks(size_t n, unsigned cap = 8192)
+{
+    const size_t b = (n + 255) / 256;
+    return (unsigned)(b > cap ? cap : b);
+}
+
+}  // namespace picsong

@@ -1,5 +1,6 @@
 // picsong_hip.hip -- C-ABI implementation (include/picsong_hip.h): host launch logic for the
-// gfx950 kernels in dwt_kernels.hpp / bpc_kernels.hpp / pack_kernels.hpp.
+// gfx950 kernels in dwt_kernels.hpp / bpc_kernels.hpp / pack_kernels.hpp / window_kernels.hpp.  Which instantiation a
+// launch takes, its grid and its scratch: kernel_select.hpp, shared with the emulator drivers of tests/hipemu/.
 // No CPU fallback exists: without a GPU every device entry point returns PICSONG_ERR_NODEVICE.
 #include "../../include/picsong_hip.h"
 
@@ -13,11 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "bpc_kernels.hpp"
-#include "dwt_kernels.hpp"
-#include "launch_plan.hpp"
-#include "window_kernels.hpp"
-#include "pack_kernels.hpp"
+#include "kernel_select.hpp"
 
 using namespace picsong;
 
@@ -45,6 +42,18 @@ int fail(int code, const char *fmt, ...)
 
 }  // namespace
 
+// A workspace of the frame pipeline.  The context keeps two: a single frame's, and a batch's with every array n times
+// as long, frame after frame.
+struct Workspace {
+    void *coef;               // T[P + extra]: the transform's work buffer
+    int32_t *staging;         // int32[P] (the encoders' 16-bit staging lives in it too)
+    int32_t *sizes;           // int32[nCB]
+    int32_t *offsets;         // int32[nCB]
+    int32_t *total;           // 1
+    uint32_t *plane_scratch;  // the coders' bit-planes below the 8 held in registers, 8 KB per wave
+    int32_t *coef_i;          // int32[P]: decoded coefficients
+};
+
 struct picsong_ctx {
     picsong_params p;
     int device;
@@ -62,23 +71,12 @@ struct picsong_ctx {
     bool has_lut[3];
     bool lut_borrowed[3]; // d_lut[k] is the caller's device table (picsong_ctx_set_lut_device): not freed here
     PlaneRec *d_img[3];   // k = 0, -cp 2: the table's plane records for the encoder (plane_record), kPlaneImgMaxRecs
-    // small scratch
-    int32_t *d_offsets;   // nCB
-    uint32_t *d_plane_scratch;   // encoder: planes below the 8 held in registers, 8 KB per wave (lazy)
-    int32_t *d_total;     // 1
     int *d_flag;          // 1
     int32_t *h_pinned;    // [0] total, [1] flag
-    // frame pipeline workspace (lazy)
-    void *d_coef;         // T[P + extra]
-    int32_t *d_staging;   // int32[P]
-    int32_t *d_sizes;     // int32[nCB]
-    int32_t *d_coef_i;    // int32[P] (decode)
+    Workspace one;        // a frame's (lazy: ensure_workspace, ensure_plane_scratch; offsets and total at creation)
     // batched frame path (picsong_encode_frames): workspaces for batch_cap frames, laid frame after frame
-    int batch_cap;
-    void *b_coef; int32_t *b_staging, *b_sizes, *b_offsets, *b_total;
-    int32_t *b_coef_i;    // decoded coefficients of a batch (picsong_decode_frames; lazy)
-    int b_coef_i_cap;
-    uint32_t *b_plane_scratch;
+    Workspace batch;      // (coef_i: the decoded coefficients of a batch, picsong_decode_frames; b_coef_i_cap planes, lazy)
+    int batch_cap, b_coef_i_cap;
     int32_t *h_totals;    // pinned, batch_cap
     int last_batch;       // frames of the most recent picsong_encode_frames
     // stage profiling (HIP events on the launch stream)
@@ -86,89 +84,11 @@ struct picsong_ctx {
     int prof_cap, prof_n;
 };
 
-template <int BAND>
-static void launch_inv(const picsong_ctx *c, const InvLaunch &f, hipStream_t s, unsigned frames = 1)
+// PICSONG_DWT_INV97=0 keeps the 9/7 synthesis levels off the lean kernel (select_inv): read once per process
+static bool lean97_levels()
 {
-    dim3 grid(f.gx, f.gy, frames);
-    // f.fast: the 9/7 divisions in their reciprocal form (verified for this context's qs at creation); the vector
-    // launches of such a context are the lean kernel's (PICSONG_DWT_INV97=0: dwt_inv_kernel's FAST instantiations)
     static const bool lean97 = !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0);
-    // (a coarsest level that also writes pixels, wl = 1, stays with dwt_inv_kernel)
-    const bool l97 = c->p.lossy && f.fast && lean97 && f.vec && !(f.a.first && f.a.dst_u8);
-    if (f.a.c16) {
-        // the decode frame paths' 16-bit coefficients (dec_c16_ok: vector kernels, 9/7 through the lean kernel, the
-        // coarsest level never the one that writes pixels)
-        if (c->p.lossy) {
-            if (f.a.dst_u8) {
-                if (f.a.one_div) dwt_inv97_kernel<BAND, true, false, true, true><<<grid, 256, 0, s>>>(f.a);
-                else dwt_inv97_kernel<BAND, true, false, false, true><<<grid, 256, 0, s>>>(f.a);
-            } else if (f.a.first) {
-                if (f.a.one_div) dwt_inv97_kernel<BAND, false, true, true, true><<<grid, 256, 0, s>>>(f.a);
-                else dwt_inv97_kernel<BAND, false, true, false, true><<<grid, 256, 0, s>>>(f.a);
-            } else {
-                if (f.a.one_div) dwt_inv97_kernel<BAND, false, false, true, true><<<grid, 256, 0, s>>>(f.a);
-                else dwt_inv97_kernel<BAND, false, false, false, true><<<grid, 256, 0, s>>>(f.a);
-            }
-        } else if (f.a.dst_u8) dwt_inv_kernel<int, false, BAND, true, true, false, true><<<grid, 256, 0, s>>>(f.a);
-        else dwt_inv_kernel<int, false, BAND, true, false, false, true><<<grid, 256, 0, s>>>(f.a);
-        return;
-    }
-    if (l97) {
-        if (f.a.dst_u8) {
-            if (f.a.one_div) dwt_inv97_kernel<BAND, true, false, true><<<grid, 256, 0, s>>>(f.a);
-            else dwt_inv97_kernel<BAND, true, false, false><<<grid, 256, 0, s>>>(f.a);
-        } else if (f.a.first) {
-            if (f.a.one_div) dwt_inv97_kernel<BAND, false, true, true><<<grid, 256, 0, s>>>(f.a);
-            else dwt_inv97_kernel<BAND, false, true, false><<<grid, 256, 0, s>>>(f.a);
-        } else {
-            if (f.a.one_div) dwt_inv97_kernel<BAND, false, false, true><<<grid, 256, 0, s>>>(f.a);
-            else dwt_inv97_kernel<BAND, false, false, false><<<grid, 256, 0, s>>>(f.a);
-        }
-    } else if (f.vec && f.a.dst_u8) {   // finest level of the frame path: pixels out, clamp fused
-        if (c->p.lossy && f.fast) dwt_inv_kernel<float, true, BAND, true, true, true><<<grid, 256, 0, s>>>(f.a);
-        else if (c->p.lossy) dwt_inv_kernel<float, true, BAND, true, true><<<grid, 256, 0, s>>>(f.a);
-        else dwt_inv_kernel<int, false, BAND, true, true><<<grid, 256, 0, s>>>(f.a);
-    } else if (f.vec) {
-        if (c->p.lossy && f.fast) dwt_inv_kernel<float, true, BAND, true, false, true><<<grid, 256, 0, s>>>(f.a);
-        else if (c->p.lossy) dwt_inv_kernel<float, true, BAND, true><<<grid, 256, 0, s>>>(f.a);
-        else dwt_inv_kernel<int, false, BAND, true><<<grid, 256, 0, s>>>(f.a);
-    } else {
-        if (c->p.lossy && f.fast) dwt_inv_kernel<float, true, BAND, false, false, true><<<grid, 256, 0, s>>>(f.a);
-        else if (c->p.lossy) dwt_inv_kernel<float, true, BAND, false><<<grid, 256, 0, s>>>(f.a);
-        else dwt_inv_kernel<int, false, BAND, false><<<grid, 256, 0, s>>>(f.a);
-    }
-}
-
-template <int BAND, bool VEC>
-static void launch_fwd_v(bool lossy, const FwdLaunch &f, dim3 grid, hipStream_t s)
-{
-    if (lossy) {
-        if (f.u8) dwt_fwd_kernel<float, true, true, BAND, VEC><<<grid, 256, 0, s>>>(f.a);
-        else dwt_fwd_kernel<float, true, false, BAND, VEC><<<grid, 256, 0, s>>>(f.a);
-    } else {
-        if (f.u8) dwt_fwd_kernel<int, false, true, BAND, VEC><<<grid, 256, 0, s>>>(f.a);
-        else dwt_fwd_kernel<int, false, false, BAND, VEC><<<grid, 256, 0, s>>>(f.a);
-    }
-}
-
-template <int BAND>
-static void launch_fwd(const picsong_ctx *c, const FwdLaunch &f, hipStream_t s, unsigned frames = 1)
-{
-    dim3 grid(f.gx, f.gy, frames);
-    if (f.vec) launch_fwd_v<BAND, true>(c->p.lossy != 0, f, grid, s);
-    else launch_fwd_v<BAND, false>(c->p.lossy != 0, f, grid, s);
-}
-
-static void launch_fwd2(bool lossy, const Fwd2Launch &f, hipStream_t s, unsigned frames = 1)
-{
-    dim3 grid(f.gx, f.gy, frames);
-    if (f.a.l0.c16) {                     // frame paths: coded subbands as int16 (DwtFwdArgs::c16)
-        if (lossy) dwt_fwd2_kernel<float, true, true, kF2PairsLossy, true><<<grid, 256, 0, s>>>(f.a);
-        else dwt_fwd2_kernel<int, false, true, kF2Pairs, true><<<grid, 256, 0, s>>>(f.a);
-        return;
-    }
-    if (lossy) dwt_fwd2_kernel<float, true, true, kF2PairsLossy><<<grid, 256, 0, s>>>(f.a);
-    else dwt_fwd2_kernel<int, false, true, kF2Pairs><<<grid, 256, 0, s>>>(f.a);
+    return lean97;
 }
 
 // Levels [from, end) of a forward plan, one launch each.  `frames` = grid.z of a batched call.
@@ -177,15 +97,23 @@ static int launch_fwd_levels(const picsong_ctx *c, const std::vector<FwdLaunch> 
 {
     for (size_t l = from; l < plan.size(); l++) {
         const FwdLaunch &f = plan[l];
-        switch (f.band) {
-        case 32: launch_fwd<32>(c, f, s, frames); break;
-        case 16: launch_fwd<16>(c, f, s, frames); break;
-        case 8: launch_fwd<8>(c, f, s, frames); break;
-        default: launch_fwd<4>(c, f, s, frames); break;
-        }
+        select_fwd(c->p.lossy != 0, f)<<<dim3(f.gx, f.gy, frames), 256, 0, s>>>(f.a);
         HIP_TRY(hipGetLastError());
     }
     return PICSONG_OK;
+}
+
+// A forward plan, levels 0 and 1 in one launch where plan_dwt_fwd2 allows it (LL1 stays in registers)
+static int launch_fwd_plan(const picsong_ctx *c, const std::vector<FwdLaunch> &plan, hipStream_t s, unsigned frames = 1)
+{
+    const bool lossy = c->p.lossy != 0;
+    Fwd2Launch f2;
+    const bool fused01 = plan_dwt_fwd2(plan, f2, true, lossy);
+    if (fused01) {
+        select_fwd2(lossy, f2.a.l0.c16 != 0)<<<dim3(f2.gx, f2.gy, frames), 256, 0, s>>>(f2.a);
+        HIP_TRY(hipGetLastError());
+    }
+    return launch_fwd_levels(c, plan, fused01 ? 2 : 0, s, frames);
 }
 
 
@@ -428,18 +356,32 @@ int picsong_ctx_create(const picsong_params *p, int device, picsong_ctx **out)
     // (an RGB context: picsong_decode_rgb_frame's three components; the plane-by-plane calls keep the 32-bit arrays)
     c->c16_dec = p->cp != 3 && p->bit_depth == 8 &&
                  dec_c16_ok(p->lossy != 0, p->wl, p->qs, p->is_rgb ? 255 : 128, c->aw, c->ah, c->fast_div);
-    hipError_t e = hipMalloc(&c->d_offsets, sizeof(int32_t) * (size_t)c->ncb);
-    if (e == hipSuccess) e = hipMalloc(&c->d_total, sizeof(int32_t));
+    hipError_t e = hipMalloc(&c->one.offsets, sizeof(int32_t) * (size_t)c->ncb);
+    if (e == hipSuccess) e = hipMalloc(&c->one.total, sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc(&c->d_flag, sizeof(int));
     if (e == hipSuccess) e = hipHostMalloc(&c->h_pinned, 2 * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemset(c->d_flag, 0, sizeof(int));
-    if (e == hipSuccess) e = hipMemset(c->d_total, 0, sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemset(c->one.total, 0, sizeof(int32_t));
     if (e != hipSuccess) {
         picsong_ctx_destroy(c);
         return fail(PICSONG_ERR_HIP, "ctx_create: %s", hipGetErrorString(e));
     }
     *out = c;
     return PICSONG_OK;
+}
+
+static void free_workspace(Workspace &w)
+{
+    void *const p[] = { w.coef, w.staging, w.sizes, w.offsets, w.total, w.plane_scratch, w.coef_i };
+    for (void *q : p) if (q) (void)hipFree(q);
+    w = Workspace();
+}
+
+static void free_batch(picsong_ctx *c)
+{
+    free_workspace(c->batch);
+    if (c->h_totals) (void)hipHostFree(c->h_totals);
+    c->h_totals = nullptr; c->batch_cap = 0; c->b_coef_i_cap = 0;
 }
 
 void picsong_ctx_destroy(picsong_ctx *c)
@@ -450,24 +392,10 @@ void picsong_ctx_destroy(picsong_ctx *c)
         if (c->d_lut[k] && !c->lut_borrowed[k]) (void)hipFree(c->d_lut[k]);
     for (int k = 0; k < 3; k++)
         if (c->d_img[k]) (void)hipFree(c->d_img[k]);
-    if (c->d_offsets) (void)hipFree(c->d_offsets);
-    if (c->d_plane_scratch) (void)hipFree(c->d_plane_scratch);
-    if (c->d_total) (void)hipFree(c->d_total);
     if (c->d_flag) (void)hipFree(c->d_flag);
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-    if (c->d_coef) (void)hipFree(c->d_coef);
-    if (c->d_staging) (void)hipFree(c->d_staging);
-    if (c->d_sizes) (void)hipFree(c->d_sizes);
-    if (c->d_coef_i) (void)hipFree(c->d_coef_i);
-    if (c->b_coef) (void)hipFree(c->b_coef);
-    if (c->b_staging) (void)hipFree(c->b_staging);
-    if (c->b_sizes) (void)hipFree(c->b_sizes);
-    if (c->b_offsets) (void)hipFree(c->b_offsets);
-    if (c->b_total) (void)hipFree(c->b_total);
-    if (c->b_plane_scratch) (void)hipFree(c->b_plane_scratch);
-    if (c->b_coef_i) (void)hipFree(c->b_coef_i);
-    c->b_coef_i = nullptr; c->b_coef_i_cap = 0;
-    if (c->h_totals) (void)hipHostFree(c->h_totals);
+    free_workspace(c->one);
+    free_batch(c);
     if (c->prof_ev) {
         for (hipEvent_t e : *c->prof_ev) (void)hipEventDestroy(e);
         delete c->prof_ev;
@@ -475,14 +403,38 @@ void picsong_ctx_destroy(picsong_ctx *c)
     delete c;
 }
 
-// the geometry checks both setters share (lut_refusal, bpc_kernels.hpp): run before the context's table is replaced
+static LutGeo lut_geo(const picsong_lut_info &li)
+{
+    return lut_geo(li.n_bitplanes, li.n_subbands, li.ctx_ref, li.ctx_sign, li.ctx_sig, li.precision, li.n_ref, li.n_sig, li.n_sign);
+}
+
+// The refusals both setters share, in the order they are made.  About the caller's arguments:
+static int lut_args_ok(const picsong_ctx *c, int comp, const picsong_lut_info *info, const int32_t *table, const char *who)
+{
+    if (!c || !info || !table) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (comp < 0 || comp > 2) return fail(PICSONG_ERR_ARG, "%s: component %d outside 0..2", who, comp);
+    // the context formation of BPCEngine.cu:222-308 is fixed to 9 / 4 / 1 contexts
+    if (info->ctx_sig != 9 || info->ctx_sign != 4 || info->ctx_ref != 1)
+        return fail(PICSONG_ERR_ARG, "LUT contexts must be 9/4/1 (sig/sign/ref), got %d/%d/%d", info->ctx_sig,
+                    info->ctx_sign, info->ctx_ref);
+    if (info->precision < 1 || info->precision > 8) return fail(PICSONG_ERR_ARG, "LUT precision %d", info->precision);
+    return PICSONG_OK;
+}
+// ... about one table's entries (*one) against the coders' LDS copy:
+static int lut_fits_lds(const picsong_ctx *c, const picsong_lut_info &li, size_t *one)
+{
+    const bool cp3 = c->p.cp == 3;
+    *one = (size_t)li.n_ref + (cp3 ? 2 : 1) * ((size_t)li.n_sig + li.n_sign);
+    if (*one + (size_t)kLutSlack > (size_t)(cp3 ? kLutLdsMax3 : kLutLdsMax))
+        return fail(PICSONG_ERR_ARG, "LUT table of %zu entries exceeds the %d the coder kernels hold in LDS", *one,
+                    (cp3 ? kLutLdsMax3 : kLutLdsMax) - kLutSlack);
+    return PICSONG_OK;
+}
+// ... and the geometry checks (lut_refusal, bpc_kernels.hpp): run before the context's table is replaced
 static int lut_admit(const picsong_ctx *c, const picsong_lut_info &li, int n_tables)
 {
-    LutGeo g;
-    g.nBp = li.n_bitplanes; g.nSub = li.n_subbands; g.cRef = li.ctx_ref; g.cSign = li.ctx_sign; g.cSig = li.ctx_sig;
-    g.prec = li.precision; g.nRef = li.n_ref; g.nSig = li.n_sig; g.nSign = li.n_sign;
     char msg[320];
-    if (lut_refusal(g, c->p.wl, c->p.k > 0.0f, c->p.cp == 3, n_tables, msg, sizeof msg))
+    if (lut_refusal(lut_geo(li), c->p.wl, c->p.k > 0.0f, c->p.cp == 3, n_tables, msg, sizeof msg))
         return fail(PICSONG_ERR_ARG, "%s", msg);
     return PICSONG_OK;
 }
@@ -492,13 +444,6 @@ static int lut_admit(const picsong_ctx *c, const picsong_lut_info &li, int n_tab
 // could, so its records are rebuilt from it by one small block ahead of every encoder launch, on that launch's stream
 // (plane_img_refresh).  Contexts that code with -k > 0 or -cp 3 keep no image.
 static bool ctx_uses_plane_img(const picsong_ctx *c) { return !(c->p.k > 0.0f) && c->p.cp != 3; }
-static LutGeo lut_geo(const picsong_lut_info &li)
-{
-    LutGeo g;
-    g.nBp = li.n_bitplanes; g.nSub = li.n_subbands; g.cRef = li.ctx_ref; g.cSign = li.ctx_sign; g.cSig = li.ctx_sig;
-    g.prec = li.precision; g.nRef = li.n_ref; g.nSig = li.n_sig; g.nSign = li.n_sign;
-    return g;
-}
 static int plane_img_alloc(picsong_ctx *c, int comp)
 {
     if (!c->d_img[comp]) HIP_TRY(hipMalloc(&c->d_img[comp], kPlaneImgMaxRecs * sizeof(PlaneRec)));
@@ -525,22 +470,14 @@ static int plane_img_refresh(picsong_ctx *c, int comp, hipStream_t s)
 
 int picsong_ctx_set_lut_component(picsong_ctx *c, int comp, const picsong_lut_info *info, const int32_t *host_table)
 {
-    if (!c || !info || !host_table) return fail(PICSONG_ERR_ARG, "set_lut: null argument");
-    if (comp < 0 || comp > 2) return fail(PICSONG_ERR_ARG, "set_lut: component %d outside 0..2", comp);
-    // the context formation of BPCEngine.cu:222-308 is fixed to 9 / 4 / 1 contexts
-    if (info->ctx_sig != 9 || info->ctx_sign != 4 || info->ctx_ref != 1)
-        return fail(PICSONG_ERR_ARG, "LUT contexts must be 9/4/1 (sig/sign/ref), got %d/%d/%d", info->ctx_sig,
-                    info->ctx_sign, info->ctx_ref);
-    if (info->precision < 1 || info->precision > 8) return fail(PICSONG_ERR_ARG, "LUT precision %d", info->precision);
+    if (int rc = lut_args_ok(c, comp, info, host_table, "set_lut")) return rc;
     const bool cp3 = c->p.cp == 3;
     if (cp3 != (info->cp == 3))
         return fail(PICSONG_ERR_ARG, "the context codes %d passes, the table is laid out for %d (picsong_lut_load_cp)",
                     c->p.cp, info->cp == 3 ? 3 : 2);
-    const size_t one = (size_t)info->n_ref + (cp3 ? 2 : 1) * ((size_t)info->n_sig + info->n_sign);
     const int n_tables = info->n_tables > 0 ? info->n_tables : 1;
-    if (one + (size_t)kLutSlack > (size_t)(cp3 ? kLutLdsMax3 : kLutLdsMax))
-        return fail(PICSONG_ERR_ARG, "LUT table of %zu entries exceeds the %d the coder kernels hold in LDS", one,
-                    (cp3 ? kLutLdsMax3 : kLutLdsMax) - kLutSlack);
+    size_t one;
+    if (int rc = lut_fits_lds(c, *info, &one)) return rc;
     const size_t total = one * (size_t)n_tables;
     for (size_t i = 0; i < total; i++)
         if (host_table[i] < 0 || host_table[i] > 255)
@@ -562,12 +499,7 @@ int picsong_ctx_set_lut_component(picsong_ctx *c, int comp, const picsong_lut_in
 
 int picsong_ctx_set_lut_device(picsong_ctx *c, int comp, const picsong_lut_info *info, const int32_t *d_table)
 {
-    if (!c || !info || !d_table) return fail(PICSONG_ERR_ARG, "set_lut_device: null argument");
-    if (comp < 0 || comp > 2) return fail(PICSONG_ERR_ARG, "set_lut_device: component %d outside 0..2", comp);
-    if (info->ctx_sig != 9 || info->ctx_sign != 4 || info->ctx_ref != 1)
-        return fail(PICSONG_ERR_ARG, "LUT contexts must be 9/4/1 (sig/sign/ref), got %d/%d/%d", info->ctx_sig,
-                    info->ctx_sign, info->ctx_ref);
-    if (info->precision < 1 || info->precision > 8) return fail(PICSONG_ERR_ARG, "LUT precision %d", info->precision);
+    if (int rc = lut_args_ok(c, comp, info, d_table, "set_lut_device")) return rc;
     picsong_lut_info li = *info;
     // section sizes follow from the geometry (IO/IOManager.ipp:431-433) when the caller left them 0
     const int wl = c->p.wl;
@@ -582,10 +514,8 @@ int picsong_ctx_set_lut_device(picsong_ctx *c, int comp, const picsong_lut_info 
         return fail(PICSONG_ERR_ARG, "the context codes %d passes, the device table is laid out for %d", c->p.cp,
                     info->cp == 3 ? 3 : 2);
     li.cp = c->p.cp;
-    const size_t one = (size_t)li.n_ref + (cp3 ? 2 : 1) * ((size_t)li.n_sig + li.n_sign);
-    if (one + (size_t)kLutSlack > (size_t)(cp3 ? kLutLdsMax3 : kLutLdsMax))
-        return fail(PICSONG_ERR_ARG, "LUT table of %zu entries exceeds the %d the coder kernels hold in LDS", one,
-                    (cp3 ? kLutLdsMax3 : kLutLdsMax) - kLutSlack);
+    size_t one;
+    if (int rc = lut_fits_lds(c, li, &one)) return rc;
     if (li.n_tables <= 0) li.n_tables = 1;
     if (int rc = lut_admit(c, li, li.n_tables)) return rc;
     if (ctx_uses_plane_img(c)) {
@@ -631,7 +561,7 @@ int picsong_level_shift_fwd(picsong_ctx *c, const uint8_t *d_in, void *d_out, vo
     hipStream_t s = (hipStream_t)stream;
     const size_t n4 = c->P / 4;
     const int off = 1 << (c->p.bit_depth - 1);
-    const int grid = (int)((n4 + 255) / 256 > 4096 ? 4096 : (n4 + 255) / 256);
+    const unsigned grid = elementwise_blocks(n4, 4096);
     if (c->p.lossy) level_shift_fwd_kernel<float><<<grid, 256, 0, s>>>(d_in, (float *)d_out, n4, off);
     else level_shift_fwd_kernel<int32_t><<<grid, 256, 0, s>>>(d_in, (int32_t *)d_out, n4, off);
     HIP_TRY(hipGetLastError());
@@ -643,7 +573,7 @@ int picsong_level_shift_inv(picsong_ctx *c, void *d_data, void *stream)
     if (!c || !d_data) return fail(PICSONG_ERR_ARG, "level_shift_inv: null argument");
     hipStream_t s = (hipStream_t)stream;
     const int off = 1 << (c->p.bit_depth - 1);
-    const int grid = (int)((c->P + 255) / 256 > 8192 ? 8192 : (c->P + 255) / 256);
+    const unsigned grid = elementwise_blocks(c->P);
     if (c->p.lossy) level_shift_inv_f32_kernel<<<grid, 256, 0, s>>>((float *)d_data, c->P, (float)off);
     else level_shift_inv_i32_kernel<<<grid, 256, 0, s>>>((int32_t *)d_data, c->P, off);
     HIP_TRY(hipGetLastError());
@@ -663,13 +593,7 @@ static int dwt_forward_impl(picsong_ctx *c, const void *d_in, bool u8in, void *d
     const std::vector<FwdLaunch> plan = plan_dwt_forward(d_in, u8in, d_out, c->aw, c->ah, c->p.wl, c->p.qs, want_c16);
     if (got_c16) *got_c16 = plan_is_c16(plan);
     else if (want_c16 && !plan_is_c16(plan)) return fail(PICSONG_ERR_ARG, "the 16-bit coefficient form needs the vector kernels on every level");
-    Fwd2Launch f2;
-    const bool fused01 = plan_dwt_fwd2(plan, f2, true, c->p.lossy != 0);
-    if (fused01) {                       // levels 0 and 1 in one launch, LL1 stays in registers
-        launch_fwd2(c->p.lossy != 0, f2, s);
-        HIP_TRY(hipGetLastError());
-    }
-    return launch_fwd_levels(c, plan, fused01 ? 2 : 0, s);
+    return launch_fwd_plan(c, plan, s);
 }
 
 int picsong_dwt_forward(picsong_ctx *c, const void *d_in, void *d_out, void *stream)
@@ -684,16 +608,6 @@ int picsong_dwt_forward_u8(picsong_ctx *c, const uint8_t *d_in, void *d_out, voi
     return dwt_forward_impl(c, d_in, true, d_out, (hipStream_t)stream);
 }
 
-static void launch_fwd_any(picsong_ctx *c, const FwdLaunch &f, hipStream_t s)
-{
-    switch (f.band) {
-    case 32: launch_fwd<32>(c, f, s); break;
-    case 16: launch_fwd<16>(c, f, s); break;
-    case 8: launch_fwd<8>(c, f, s); break;
-    default: launch_fwd<4>(c, f, s); break;
-    }
-}
-
 int picsong_dwt_forward_band(picsong_ctx *c, const uint8_t *d_frame, int row0, int rows, void *d_out, void *stream)
 {
     if (!c || !d_frame || !d_out) return fail(PICSONG_ERR_ARG, "dwt_forward_band: null argument");
@@ -701,9 +615,8 @@ int picsong_dwt_forward_band(picsong_ctx *c, const uint8_t *d_frame, int row0, i
         return fail(PICSONG_ERR_ARG, "dwt_forward_band: rows [%d, %d) must be even and inside [0, %d)", row0, row0 + rows, c->ah);
     std::vector<FwdLaunch> plan = plan_dwt_forward(d_frame, true, d_out, c->aw, c->ah, c->p.wl, c->p.qs);
     plan_restrict_band(plan[0], row0, rows);
-    launch_fwd_any(c, plan[0], (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    plan.resize(1);
+    return launch_fwd_levels(c, plan, 0, (hipStream_t)stream);
 }
 
 int picsong_dwt_forward_tail(picsong_ctx *c, void *d_out, void *stream)
@@ -757,44 +670,21 @@ static int run_inverse(picsong_ctx *c, const std::vector<InvLaunch> &plan, hipSt
     const size_t n = fused10 ? plan.size() - 2 : plan.size();
     for (size_t l = 0; l < n; l++) {
         const InvLaunch &f = plan[l];
-        switch (f.band) {
-        case 32: launch_inv<32>(c, f, s, frames); break;
-        case 16: launch_inv<16>(c, f, s, frames); break;
-        case 8: launch_inv<8>(c, f, s, frames); break;
-        default: launch_inv<4>(c, f, s, frames); break;
-        }
+        select_inv(c->p.lossy != 0, lean97_levels(), f)<<<dim3(f.gx, f.gy, frames), 256, 0, s>>>(f.a);
         HIP_TRY(hipGetLastError());
     }
     if (fused10) {
-        const dim3 grid(f2.gx, f2.gy, frames);
-        if (!c->p.lossy) dwt_inv2_kernel<false, false><<<grid, 256, 0, s>>>(f2.a);
-        else if (f2.a.l0.one_div) dwt_inv2_kernel<true, true><<<grid, 256, 0, s>>>(f2.a);
-        else dwt_inv2_kernel<true, false><<<grid, 256, 0, s>>>(f2.a);
+        select_inv2(c->p.lossy != 0, f2.a.l0.one_div != 0)<<<dim3(f2.gx, f2.gy, frames), 256, 0, s>>>(f2.a);
         HIP_TRY(hipGetLastError());
     }
     return PICSONG_OK;
-}
-
-static int dwt_inverse_impl(picsong_ctx *c, const int32_t *d_in, void *d_out, uint8_t *d_pixels, bool *fused,
-                            hipStream_t s, unsigned frames = 1, size_t pix_stride = 0)
-{
-    return run_inverse(c, inverse_plan(c, d_in, d_out, d_pixels, fused, frames, pix_stride, false), s, frames);
 }
 
 int picsong_dwt_inverse(picsong_ctx *c, const int32_t *d_in, void *d_out, void *stream)
 {
     if (!c || !d_in || !d_out) return fail(PICSONG_ERR_ARG, "dwt_inverse: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    for (const InvLaunch &f : plan_dwt_inverse(d_in, d_out, c->aw, c->ah, c->p.wl, c->p.qs, c->fast_div)) {
-        switch (f.band) {
-        case 32: launch_inv<32>(c, f, s); break;
-        case 16: launch_inv<16>(c, f, s); break;
-        case 8: launch_inv<8>(c, f, s); break;
-        default: launch_inv<4>(c, f, s); break;
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    return PICSONG_OK;
+    // (32-bit coefficients, no pixels: a launch per level, plan_dwt_inv2 never applies)
+    return run_inverse(c, plan_dwt_inverse(d_in, d_out, c->aw, c->ah, c->p.wl, c->p.qs, c->fast_div), (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -804,30 +694,23 @@ static int bpc_args(picsong_ctx *c, BpcArgs &a, int comp = 0)
 {
     if (comp < 0 || comp > 2) return fail(PICSONG_ERR_ARG, "component %d outside 0..2", comp);
     if (!c->has_lut[comp]) return fail(PICSONG_ERR_ARG, "no LUT loaded for component %d: call picsong_ctx_set_lut first", comp);
-    memset(&a, 0, sizeof a);
     const picsong_lut_info &li = c->li[comp];
-    a.AW = c->aw; a.AH = c->ah; a.wl = c->p.wl; a.nCB = c->ncb; a.ncx = c->aw / PICSONG_CB;
-    a.lut = c->d_lut[comp];
+    a = bpc_frame_args(c->aw, c->ah, c->p.wl, c->d_lut[comp], lut_geo(li), c->d_flag);
     a.plane_img = ctx_uses_plane_img(c) ? c->d_img[comp] : nullptr;
-    a.g.nBp = li.n_bitplanes; a.g.nSub = li.n_subbands; a.g.cRef = li.ctx_ref;
-    a.g.cSign = li.ctx_sign; a.g.cSig = li.ctx_sig; a.g.prec = li.precision;
-    a.g.nRef = li.n_ref; a.g.nSig = li.n_sig; a.g.nSign = li.n_sign;
-    a.range_flag = c->d_flag;
     a.k = c->p.k; a.n_tables = li.n_tables > 0 ? li.n_tables : 1;
     return PICSONG_OK;
 }
 
-// -k > 0: may the launch take the kernels' COMPACT table copies (bulk_max_span_bytes: the geometry's widest codeblock)?
-// PICSONG_BULK_FULLTAB=1 keeps the whole-table instantiations (the tests cross-check both)
-static bool bulk_compact(picsong_ctx *c, int comp)
+// -k > 0: may a launch over the tables of components comp .. comp + ncomp - 1 take the kernels' COMPACT table copies
+// (bulk_compact, kernel_select.hpp)?  PICSONG_BULK_FULLTAB=1 keeps the whole-table instantiations (the tests cross-check both)
+static bool bulk_compact(picsong_ctx *c, int comp, int ncomp = 1)
 {
     if (const char *e = getenv("PICSONG_BULK_FULLTAB")) if (atoi(e) != 0) return false;
-    if (c->bulk_compact[comp] < 0) {
-        const picsong_lut_info &li = c->li[comp];
-        c->bulk_compact[comp] = bulk_max_span_bytes(c->aw, c->ah, c->p.wl, li.n_bitplanes, li.n_subbands, li.ctx_ref, li.ctx_sig,
-                                                    li.ctx_sign) <= kBulkCompactBytes ? 1 : 0;
+    for (int k = comp; k < comp + ncomp; k++) {
+        if (c->bulk_compact[k] < 0) c->bulk_compact[k] = picsong::bulk_compact(c->aw, c->ah, c->p.wl, lut_geo(c->li[k])) ? 1 : 0;
+        if (c->bulk_compact[k] != 1) return false;
     }
-    return c->bulk_compact[comp] == 1;
+    return true;
 }
 
 // the waves of a frame's coder launch the bit-plane scratch holds, whole workgroups: every codeblock pair, or the most a
@@ -839,9 +722,23 @@ static int ensure_plane_scratch(picsong_ctx *c)
 {
     static_assert(kBpcEncWgWaves == kBpcDecWgWaves, "one scratch serves the launches of both directions");
     static_assert(kBpcEncWgWaves % kBpc3WgWaves == 0, "-cp 3 launches fit the same allocation");
-    if (c->d_plane_scratch) return PICSONG_OK;
+    if (c->one.plane_scratch) return PICSONG_OK;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMalloc(&c->d_plane_scratch, (size_t)dec_scratch_waves(c) * kEncScratchDwordsPerWave * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&c->one.plane_scratch, (size_t)dec_scratch_waves(c) * kEncScratchDwordsPerWave * sizeof(uint32_t)));
+    return PICSONG_OK;
+}
+
+// The encoder launch of every path: `waves` waves (a codeblock pair each) over the tables of components comp ..
+// comp + ncomp - 1, the caller's `a` complete but for the kernel's choice.  Ahead of a k = 0 launch the plane records of
+// a caller's device tables are rebuilt (plane_img_refresh).
+static int launch_encoder(picsong_ctx *c, const BpcArgs &a, unsigned waves, int comp, int ncomp, hipStream_t s)
+{
+    const bool bulk = a.k > 0.0f;
+    if (!bulk)
+        for (int k = comp; k < comp + ncomp; k++) if (int rc = plane_img_refresh(c, k, s)) return rc;
+    const BpcLaunch l = select_encoder(c->p.cp == 3, bulk, bulk && bulk_compact(c, comp, ncomp) && c->pipelined, waves);
+    l.kernel<<<l.wgs, l.threads, 0, s>>>(a);
+    HIP_TRY(hipGetLastError());
     return PICSONG_OK;
 }
 
@@ -860,28 +757,8 @@ static int bpc_encode_impl(picsong_ctx *c, const void *d_coeffs, uint16_t *d_sta
     a.coeffs_in = d_coeffs; a.is_float = c->p.lossy ? 1 : 0;
     a.staging16 = d_stage16; a.sizes = d_sizes;
     if (int rc2 = ensure_plane_scratch(c)) return rc2;
-    a.plane_scratch = c->d_plane_scratch;
-    if (c->p.cp == 3) {        // three coding passes: one kernel for both directions (bpc3_kernel)
-        bpc3_kernel<false><<<(unsigned)(((cb_count + 1) / 2 + kBpc3WgWaves - 1) / kBpc3WgWaves), 64 * kBpc3WgWaves, 0, s>>>(a);
-        HIP_TRY(hipGetLastError());
-        return PICSONG_OK;
-    }
-    // -k > 0: the BULK instantiation (bulk scan below the consecutive bit-planes, table s in LDS)
-    if (a.k > 0.0f) {
-        // Two instantiations of the -k > 0 encoder: with compact table copies it is asked for six waves a SIMD (80
-        // registers, some of its prologue spilled) -- what frames in flight want: 133 -> 142 Gpixel/s at k = 0.5; with
-        // whole tables its LDS bounds it to four waves anyway, it takes 102 registers and spills nothing -- what a lone
-        // frame wants, whose 4080 waves are four to a SIMD whatever the kernel allows: 0.376 against 0.411 ms.  The
-        // context's hint (picsong_ctx_set_pipelined) chooses.
-        if (bulk_compact(c, comp) && c->pipelined) bpc_encode_kernel<true, true><<<(unsigned)((cb_count + 1) / 2), 64, 0, s>>>(a);
-        else bpc_encode_kernel<true><<<(unsigned)((cb_count + 1) / 2), 64, 0, s>>>(a);
-    }
-    else {
-        if (int rc2 = plane_img_refresh(c, comp, s)) return rc2;
-        bpc_encode_kernel<false><<<(unsigned)(((cb_count + 1) / 2 + kBpcEncWgWaves - 1) / kBpcEncWgWaves), 64 * kBpcEncWgWaves, 0, s>>>(a);
-    }
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    a.plane_scratch = c->one.plane_scratch;
+    return launch_encoder(c, a, (unsigned)((cb_count + 1) / 2), comp, 1, s);
 }
 
 // The stage-level call keeps the reference's contract -- an int32 array of 4096 words a codeblock, 0xFFFFFFFF wherever
@@ -890,9 +767,9 @@ static int bpc_encode_impl(picsong_ctx *c, const void *d_coeffs, uint16_t *d_sta
 static int bpc_encode_widened(picsong_ctx *c, const void *d_coeffs, int32_t *d_staging, int32_t *d_sizes, hipStream_t s, int comp)
 {
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->d_staging) HIP_TRY(hipMalloc(&c->d_staging, c->P * sizeof(int32_t)));
-    if (d_staging == c->d_staging) return fail(PICSONG_ERR_ARG, "bpc_encode: the context's own staging passed as the output");
-    uint16_t *const st16 = reinterpret_cast<uint16_t *>(c->d_staging);
+    if (!c->one.staging) HIP_TRY(hipMalloc(&c->one.staging, c->P * sizeof(int32_t)));
+    if (d_staging == c->one.staging) return fail(PICSONG_ERR_ARG, "bpc_encode: the context's own staging passed as the output");
+    uint16_t *const st16 = reinterpret_cast<uint16_t *>(c->one.staging);
     HIP_TRY(hipMemsetAsync(d_staging, 0xFF, c->P * sizeof(int32_t), s));
     int rc = bpc_encode_impl(c, d_coeffs, st16, d_sizes, s, 0, -1, comp);
     if (rc) return rc;
@@ -927,79 +804,69 @@ static bool dec_from_stream(const picsong_ctx *c)
     return !staged && c->p.cp != 3;
 }
 
-// d_stream16 != nullptr (k = 0, -cp 2): the codewords come from the packed stream, d_offsets the scan of its lengths
-// (scan_stream_kernel); d_staging is then not read
-// c16 (with d_stream16): the coefficients leave as an int16 Mallat array at d_coeffs (bpc_decode_kernel's C16 form)
-// reduce > 0: only the codeblocks of the 1/2^reduce image's corner (decode_rect); win: only a window's (decode_rect)
-static int bpc_decode_impl(picsong_ctx *c, const int32_t *d_staging, const int32_t *d_sizes, int32_t *d_coeffs,
-                           hipStream_t s, int comp = 0, const uint16_t *d_stream16 = nullptr,
-                           const int32_t *d_offsets = nullptr, bool c16 = false, int reduce = 0,
-                           const WindowPlan *win = nullptr)
+// Stream intake: the codeblock lengths of n streams `stride` shorts apart into w.sizes, their scan into w.offsets and
+// w.total -- `direct`, one launch, for a decoder that reads the streams itself; else the codewords unpacked into
+// w.staging as well (-k > 0 through the staging, -cp 3, PICSONG_DEC_STAGING)
+static int stream_intake(picsong_ctx *c, const uint16_t *d_streams, unsigned n, size_t stride, bool direct, const Workspace &w,
+                         hipStream_t s)
 {
-    BpcArgs a;
-    int rc = bpc_args(c, a, comp);
-    if (rc) return rc;
-    a.coeffs_out = d_coeffs;
-    a.staging = const_cast<int32_t *>(d_staging);
-    a.sizes = const_cast<int32_t *>(d_sizes);
-    if (int rc2 = ensure_plane_scratch(c)) return rc2;      // the decoder parks its finished planes there too
-    a.plane_scratch = c->d_plane_scratch;
-    const unsigned waves = (unsigned)decode_rect(c, a, reduce, win);
-    if (c->p.cp == 3) {
-        bpc3_kernel<true><<<(waves + kBpc3WgWaves - 1) / kBpc3WgWaves, 64 * kBpc3WgWaves, 0, s>>>(a);
+    if (direct) {
+        scan_stream_kernel<<<n, scan_threads(c->ncb), 0, s>>>(d_streams, c->ncb, w.sizes, w.offsets, w.total, c->d_flag, stride);
         HIP_TRY(hipGetLastError());
         return PICSONG_OK;
     }
-    if (a.k > 0.0f) {
-        // (one launch: the two-pass planes are parked in the scratch whatever their number)
-        const bool cmp = bulk_compact(c, comp);
-        if (d_stream16) {
-            a.cw16 = d_stream16; a.cw16_offsets = d_offsets; a.cw16_total = c->d_total;
-            a.cw16_max = (uint32_t)picsong_max_stream_shorts(c->aw, c->ah);
-            if (c16) {
-                if (cmp) bpc_decode_kernel<true, kDecSmallPlanes, true, true, true><<<waves, 64, 0, s>>>(a);
-                else bpc_decode_kernel<true, kDecSmallPlanes, true, true><<<waves, 64, 0, s>>>(a);
-            } else {
-                if (cmp) bpc_decode_kernel<true, kDecSmallPlanes, true, false, true><<<waves, 64, 0, s>>>(a);
-                else bpc_decode_kernel<true, kDecSmallPlanes, true><<<waves, 64, 0, s>>>(a);
-            }
-        } else {
-            if (c16) return fail(PICSONG_ERR_ARG, "the 16-bit coefficient form decodes from the stream itself");
-            if (cmp) bpc_decode_kernel<true, kDecSmallPlanes, false, false, true><<<waves, 64, 0, s>>>(a);
-            else bpc_decode_kernel<true, kDecSmallPlanes><<<waves, 64, 0, s>>>(a);
-        }
-    } else {
-        const unsigned wgs = (waves + kBpcDecWgWaves - 1) / kBpcDecWgWaves;
-        if (d_stream16) {
-            a.cw16 = d_stream16; a.cw16_offsets = d_offsets; a.cw16_total = c->d_total;
-            a.cw16_max = (uint32_t)picsong_max_stream_shorts(c->aw, c->ah);
-            if (c16) bpc_decode_kernel<false, kDecSmallPlanes, true, true><<<wgs, 64 * kBpcDecWgWaves, 0, s>>>(a);
-            else bpc_decode_kernel<false, kDecSmallPlanes, true><<<wgs, 64 * kBpcDecWgWaves, 0, s>>>(a);
-        } else {
-            if (c16) return fail(PICSONG_ERR_ARG, "the 16-bit coefficient form decodes from the stream itself");
-            bpc_decode_kernel<false, kDecSmallPlanes><<<wgs, 64 * kBpcDecWgWaves, 0, s>>>(a);
-        }
-    }
+    read_sizes_kernel<<<dim3((unsigned)((c->ncb + 255) / 256), n), 256, 0, s>>>(d_streams, c->ncb, w.sizes, c->d_flag, stride);
+    HIP_TRY(hipGetLastError());
+    scan_sizes_kernel<<<n, scan_threads(c->ncb), 0, s>>>(w.sizes, c->ncb, w.offsets, w.total);
+    HIP_TRY(hipGetLastError());
+    unpack_kernel<<<dim3((unsigned)c->ncb, n), 256, 0, s>>>(d_streams, w.sizes, w.offsets, c->ncb, w.staging, stride, c->P);
     HIP_TRY(hipGetLastError());
     return PICSONG_OK;
 }
 
-// a frame path's decoder: lengths and offsets out of the stream (one launch), then the coder reading the stream itself;
-// or the unpack into the staging (-k > 0, -cp 3, PICSONG_DEC_STAGING)
-static int unpack_impl(picsong_ctx *c, const uint16_t *d_stream, int32_t *d_staging, int32_t *d_sizes,
-                       bool memset_staging, hipStream_t s);
+// The decoder launch of every path: `waves` waves over w's sizes, staging and plane scratch, coefficients into w.coef_i.
+// d_streams != nullptr (k = 0 or -k > 0, -cp 2): the codewords come from the packed streams, `stride` shorts apart, at
+// w.offsets (stream_intake's scan); w.staging is then not read
+// c16 (with d_streams): the coefficients leave as int16 Mallat arrays (bpc_decode_kernel's C16 form)
+// compact: the tables of the launch take the COMPACT copies (-k > 0, bulk_compact)
+static int launch_decoder(picsong_ctx *c, BpcArgs &a, unsigned waves, bool compact, const Workspace &w,
+                          const uint16_t *d_streams, size_t stride, bool c16, hipStream_t s)
+{
+    const BpcLaunch l = select_decoder(c->p.cp == 3, a.k > 0.0f, compact, d_streams != nullptr, c16, waves);
+    if (!l.kernel) return fail(PICSONG_ERR_ARG, "the 16-bit coefficient form decodes from the stream itself");
+    a.coeffs_out = w.coef_i; a.staging = w.staging; a.sizes = w.sizes; a.plane_scratch = w.plane_scratch;
+    if (d_streams) {
+        a.cw16 = d_streams; a.cw16_offsets = w.offsets; a.cw16_total = w.total; a.cw16_stride = stride;
+        a.cw16_max = (uint32_t)picsong_max_stream_shorts(c->aw, c->ah);
+    }
+    l.kernel<<<l.wgs, l.threads, 0, s>>>(a);
+    HIP_TRY(hipGetLastError());
+    return PICSONG_OK;
+}
+
+// One frame's decoder over the context's own scratch: d_staging / d_sizes / d_coeffs may be the caller's arrays
+// reduce > 0: only the codeblocks of the 1/2^reduce image's corner (decode_rect); win: only a window's (decode_rect)
+static int bpc_decode_impl(picsong_ctx *c, const int32_t *d_staging, const int32_t *d_sizes, int32_t *d_coeffs,
+                           hipStream_t s, int comp = 0, const uint16_t *d_stream16 = nullptr, bool c16 = false,
+                           int reduce = 0, const WindowPlan *win = nullptr)
+{
+    BpcArgs a;
+    int rc = bpc_args(c, a, comp);
+    if (rc) return rc;
+    if (int rc2 = ensure_plane_scratch(c)) return rc2;      // the decoder parks its finished planes there too
+    Workspace w = c->one;
+    w.staging = const_cast<int32_t *>(d_staging); w.sizes = const_cast<int32_t *>(d_sizes); w.coef_i = d_coeffs;
+    const unsigned waves = (unsigned)decode_rect(c, a, reduce, win);
+    return launch_decoder(c, a, waves, a.k > 0.0f && bulk_compact(c, comp), w, d_stream16, 0, c16, s);
+}
+
+// a frame path's decoder: the stream's intake, then the coder -- reading the stream itself, or the staging
 static int decode_stream_impl(picsong_ctx *c, const uint16_t *d_stream, int32_t *d_coeffs, hipStream_t s, int comp,
                               bool c16 = false, int reduce = 0, const WindowPlan *win = nullptr)
 {
-    int rc;
-    if (!dec_from_stream(c)) {
-        if (c16) return fail(PICSONG_ERR_ARG, "the 16-bit coefficient form decodes from the stream itself");
-        if ((rc = unpack_impl(c, d_stream, c->d_staging, c->d_sizes, false, s))) return rc;
-        return bpc_decode_impl(c, c->d_staging, c->d_sizes, d_coeffs, s, comp, nullptr, nullptr, false, reduce, win);
-    }
-    scan_stream_kernel<<<1, scan_threads(c->ncb), 0, s>>>(d_stream, c->ncb, c->d_sizes, c->d_offsets, c->d_total, c->d_flag, 0);
-    HIP_TRY(hipGetLastError());
-    return bpc_decode_impl(c, nullptr, c->d_sizes, d_coeffs, s, comp, d_stream, c->d_offsets, c16, reduce, win);
+    const bool direct = dec_from_stream(c);
+    if (int rc = stream_intake(c, d_stream, 1u, 0, direct, c->one, s)) return rc;
+    return bpc_decode_impl(c, c->one.staging, c->one.sizes, d_coeffs, s, comp, direct ? d_stream : nullptr, c16, reduce, win);
 }
 
 int picsong_bpc_decode(picsong_ctx *c, const int32_t *d_staging, const int32_t *d_sizes, int32_t *d_coeffs,
@@ -1061,27 +928,40 @@ int picsong_last_total(picsong_ctx *c, void *stream, int *h_total)
 {
     if (!c || !h_total) return fail(PICSONG_ERR_ARG, "last_total: null argument");
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(&c->h_pinned[0], c->d_total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&c->h_pinned[0], c->one.total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     *h_total = c->h_pinned[0];
     return PICSONG_OK;
 }
 
+// The pack of n frames' codeblocks, frame after frame in w (sizes, offsets, totals) and in the staging: the header
+// argument, the scan of the lengths, the copy into streams `stream_stride` shorts apart.
 // W: uint16_t = the encoders' own staging (the frame paths), int32_t = a caller's array (picsong_bitstream_pack)
+// h_header != nullptr: the populated header, on the frames `has` names (HeaderArg::has, pack_kernels.hpp)
 extern "C++" {
+template <typename W>
+static int pack_frames(picsong_ctx *c, const W *d_staging, const Workspace &w, int ncb, unsigned n, const uint16_t *h_header,
+                       int has, uint16_t *d_streams, size_t stream_stride, hipStream_t s)
+{
+    HeaderArg h;
+    memset(&h, 0, sizeof h);
+    if (h_header) { memcpy(h.h, h_header, sizeof h.h); h.has = has; }
+    scan_sizes_kernel<<<n, scan_threads(ncb), 0, s>>>(w.sizes, ncb, w.offsets, w.total);
+    HIP_TRY(hipGetLastError());
+    pack_kernel<W><<<dim3(pack_blocks<W>(ncb), n), 256, 0, s>>>(d_staging, w.sizes, w.offsets, w.total, ncb, h, d_streams, c->P,
+                                                              stream_stride);
+    HIP_TRY(hipGetLastError());
+    return PICSONG_OK;
+}
+// codeblocks [cb_begin, cb_begin + n) of one frame out of the context's own offsets and total
 template <typename W>
 static int pack_range(picsong_ctx *c, const W *d_staging, const int32_t *d_sizes, int n,
                       const uint16_t *h_header, uint16_t *d_stream, hipStream_t s)
 {
-    HeaderArg h;
-    memset(&h, 0, sizeof h);
-    if (h_header) { memcpy(h.h, h_header, sizeof h.h); h.has = 1; }
-    c->last_batch = 0;                                      // the most recent total is d_total (picsong_copy_last_totals)
-    scan_sizes_kernel<<<1, scan_threads(n), 0, s>>>(d_sizes, n, c->d_offsets, c->d_total);
-    HIP_TRY(hipGetLastError());
-    pack_kernel<W><<<pack_blocks<W>(n), 256, 0, s>>>(d_staging, d_sizes, c->d_offsets, c->d_total, n, h, d_stream);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    c->last_batch = 0;                                      // the most recent total is one.total (picsong_copy_last_totals)
+    Workspace w = c->one;
+    w.sizes = const_cast<int32_t *>(d_sizes);
+    return pack_frames(c, d_staging, w, n, 1u, h_header, 1, d_stream, 0, s);
 }
 }  // extern "C++"
 
@@ -1095,26 +975,16 @@ int picsong_bitstream_pack(picsong_ctx *c, const int32_t *d_staging, const int32
     return PICSONG_OK;
 }
 
-static int unpack_impl(picsong_ctx *c, const uint16_t *d_stream, int32_t *d_staging, int32_t *d_sizes,
-                       bool memset_staging, hipStream_t s)
-{
-    // BSEngine::deviceMemoryAllocator BitStreamBuilder.cu:281-284.  Slots beyond a codeblock's length
-    // are never read by the decoder, so the frame path skips this 4*AW*AH-byte fill.
-    if (memset_staging) HIP_TRY(hipMemsetAsync(d_staging, 0xFF, c->P * sizeof(int32_t), s));
-    read_sizes_kernel<<<(unsigned)((c->ncb + 255) / 256), 256, 0, s>>>(d_stream, c->ncb, d_sizes, c->d_flag);
-    HIP_TRY(hipGetLastError());
-    scan_sizes_kernel<<<1, scan_threads(c->ncb), 0, s>>>(d_sizes, c->ncb, c->d_offsets, c->d_total);
-    HIP_TRY(hipGetLastError());
-    unpack_kernel<<<(unsigned)c->ncb, 256, 0, s>>>(d_stream, d_sizes, c->d_offsets, c->ncb, d_staging);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
-}
-
 int picsong_bitstream_unpack(picsong_ctx *c, const uint16_t *d_stream, int32_t *d_staging, int32_t *d_sizes,
                              void *stream)
 {
     if (!c || !d_staging || !d_sizes || !d_stream) return fail(PICSONG_ERR_ARG, "bitstream_unpack: null argument");
-    return unpack_impl(c, d_stream, d_staging, d_sizes, true, (hipStream_t)stream);
+    // BSEngine::deviceMemoryAllocator BitStreamBuilder.cu:281-284.  Slots beyond a codeblock's length
+    // are never read by the decoder, so the frame paths skip this 4*AW*AH-byte fill.
+    HIP_TRY(hipMemsetAsync(d_staging, 0xFF, c->P * sizeof(int32_t), (hipStream_t)stream));
+    Workspace w = c->one;
+    w.staging = d_staging; w.sizes = d_sizes;
+    return stream_intake(c, d_stream, 1u, 0, false, w, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1123,10 +993,11 @@ int picsong_bitstream_unpack(picsong_ctx *c, const uint16_t *d_stream, int32_t *
 static int ensure_workspace(picsong_ctx *c, bool decode)
 {
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->d_coef) HIP_TRY(hipMalloc(&c->d_coef, (c->P + c->extra) * 4));
-    if (!c->d_staging) HIP_TRY(hipMalloc(&c->d_staging, c->P * sizeof(int32_t)));
-    if (!c->d_sizes) HIP_TRY(hipMalloc(&c->d_sizes, (size_t)c->ncb * sizeof(int32_t)));
-    if (decode && !c->d_coef_i) HIP_TRY(hipMalloc(&c->d_coef_i, c->P * sizeof(int32_t)));
+    Workspace &w = c->one;
+    if (!w.coef) HIP_TRY(hipMalloc(&w.coef, (c->P + c->extra) * 4));
+    if (!w.staging) HIP_TRY(hipMalloc(&w.staging, c->P * sizeof(int32_t)));
+    if (!w.sizes) HIP_TRY(hipMalloc(&w.sizes, (size_t)c->ncb * sizeof(int32_t)));
+    if (decode && !w.coef_i) HIP_TRY(hipMalloc(&w.coef_i, c->P * sizeof(int32_t)));
     return PICSONG_OK;
 }
 
@@ -1175,16 +1046,15 @@ int picsong_encode_frame(picsong_ctx *c, const uint8_t *d_frame, int iter, uint1
     // (an unaligned frame pointer, or PICSONG_DWT_NOVEC set after the context was created, takes the per-column kernels
     // and with them the 32-bit arrays: `c16` is what this call's plan delivers, as in picsong_encode_frames)
     bool c16 = false;
-    if ((rc = dwt_forward_impl(c, d_frame, true, c->d_coef, s, c->c16, &c16))) return rc;
+    if ((rc = dwt_forward_impl(c, d_frame, true, c->one.coef, s, c->c16, &c16))) return rc;
     if (ev) HIP_TRY(hipEventRecord(ev[1], s));
-    uint16_t *const st16 = reinterpret_cast<uint16_t *>(c->d_staging);      // (the context's staging holds the 16-bit form)
-    if ((rc = bpc_encode_impl(c, c->d_coef, st16, c->d_sizes, s, 0, -1, 0, c16))) return rc;
+    uint16_t *const st16 = reinterpret_cast<uint16_t *>(c->one.staging);      // (the context's staging holds the 16-bit form)
+    if ((rc = bpc_encode_impl(c, c->one.coef, st16, c->one.sizes, s, 0, -1, 0, c16))) return rc;
     if (ev) HIP_TRY(hipEventRecord(ev[2], s));
     uint16_t hdr[PICSONG_HDR_SHORTS];
     if (iter == 0) picsong_header_pack(&c->p, hdr);
-    rc = pack_range(c, st16, c->d_sizes, c->ncb, iter == 0 ? hdr : nullptr, d_stream, s);
+    rc = pack_range(c, st16, c->one.sizes, c->ncb, iter == 0 ? hdr : nullptr, d_stream, s);
     if (ev) HIP_TRY(hipEventRecord(ev[3], s));
-    c->last_batch = 0;                                      // the most recent call's total is d_total
     return rc;
 }
 
@@ -1217,15 +1087,20 @@ static int run_window(picsong_ctx *c, const WindowPlan &w, const int32_t *coef_i
     for (WinLaunch &f : plan) {
         f.a.mallat_z = coef_z; f.a.ll_z = work_z; f.a.dst_z = work_z; f.a.u8_z = u8_z;
         f.grid.z = frames;
-        if (c->p.lossy) {
-            if (f.u8) dwt_window_kernel<float, true><<<f.grid, 256, 0, s>>>(f.a);
-            else dwt_window_kernel<float, false><<<f.grid, 256, 0, s>>>(f.a);
-        } else {
-            if (f.u8) dwt_window_kernel<int, true><<<f.grid, 256, 0, s>>>(f.a);
-            else dwt_window_kernel<int, false><<<f.grid, 256, 0, s>>>(f.a);
-        }
+        select_window(c->p.lossy != 0, f.u8)<<<f.grid, 256, 0, s>>>(f.a);
         HIP_TRY(hipGetLastError());
     }
+    return PICSONG_OK;
+}
+
+// n4 * 4 samples of a synthesis that did not write its pixels itself: level shift + clamp
+static int clamp_pixels(picsong_ctx *c, const void *img, uint8_t *d_out, size_t n4, hipStream_t s)
+{
+    const int off = 1 << (c->p.bit_depth - 1);
+    const unsigned grid = elementwise_blocks(n4);
+    if (c->p.lossy) clamp_to_u8_f32_kernel<<<grid, 256, 0, s>>>((const float *)img, d_out, n4, (float)off);
+    else clamp_to_u8_i32_kernel<<<grid, 256, 0, s>>>((const int32_t *)img, d_out, n4, off);
+    HIP_TRY(hipGetLastError());
     return PICSONG_OK;
 }
 
@@ -1237,25 +1112,19 @@ static int decode_frame_impl(picsong_ctx *c, const uint16_t *d_stream, uint8_t *
     int rc = ensure_workspace(c, true);
     if (rc) return rc;
     if (win) {      // the decoder over the window's codeblocks (32-bit coefficients), then the cone's synthesis
-        if ((rc = decode_stream_impl(c, d_stream, c->d_coef_i, s, 0, false, reduce, win))) return rc;
-        return run_window(c, *win, c->d_coef_i, c->d_coef, 1u, 0, 0, d_frame_out, pitch, 0, s);
+        if ((rc = decode_stream_impl(c, d_stream, c->one.coef_i, s, 0, false, reduce, win))) return rc;
+        return run_window(c, *win, c->one.coef_i, c->one.coef, 1u, 0, 0, d_frame_out, pitch, 0, s);
     }
     // (16-bit coefficients between the decoder and the synthesis where the context's magnitudes are bounded and this
     // call's pointers take the vector kernels: c->c16_dec, plan_inv_is_c16)
     bool fused = false;
-    const std::vector<InvLaunch> plan = inverse_plan(c, c->d_coef_i, c->d_coef, d_frame_out, &fused, 1, 0,
+    const std::vector<InvLaunch> plan = inverse_plan(c, c->one.coef_i, c->one.coef, d_frame_out, &fused, 1, 0,
                                                      dec_c16_reduced(c, reduce) && dec_from_stream(c), false, reduce);
-    if ((rc = decode_stream_impl(c, d_stream, c->d_coef_i, s, 0, plan_inv_is_c16(plan), reduce))) return rc;
+    if ((rc = decode_stream_impl(c, d_stream, c->one.coef_i, s, 0, plan_inv_is_c16(plan), reduce))) return rc;
     if ((rc = run_inverse(c, plan, s))) return rc;
     if (fused) return PICSONG_OK;            // the finest level wrote the pixels itself
-    const void *img = plan.back().a.dst;     // (level `reduce`'s samples, packed: c->extra elements in when reduce = 0)
-    const size_t n4 = (size_t)(c->aw >> reduce) * (size_t)(c->ah >> reduce) / 4;
-    const int off = 1 << (c->p.bit_depth - 1);
-    const int grid = (int)((n4 + 255) / 256 > 8192 ? 8192 : (n4 + 255) / 256);
-    if (c->p.lossy) clamp_to_u8_f32_kernel<<<grid, 256, 0, s>>>((const float *)img, d_frame_out, n4, (float)off);
-    else clamp_to_u8_i32_kernel<<<grid, 256, 0, s>>>((const int32_t *)img, d_frame_out, n4, off);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    // (level `reduce`'s samples, packed: c->extra elements in when reduce = 0)
+    return clamp_pixels(c, plan.back().a.dst, d_frame_out, (size_t)(c->aw >> reduce) * (size_t)(c->ah >> reduce) / 4, s);
 }
 
 int picsong_decode_frame(picsong_ctx *c, const uint16_t *d_stream, uint8_t *d_frame_out, void *stream)
@@ -1326,9 +1195,9 @@ int picsong_encode_stripe_coded(picsong_ctx *c, const void *d_coeffs, int cb_beg
     int rc = ensure_workspace(c, false);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    uint16_t *const st16 = reinterpret_cast<uint16_t *>(c->d_staging);
-    if ((rc = bpc_encode_impl(c, d_coeffs, st16, c->d_sizes, s, cb_begin, cb_count))) return rc;
-    return pack_range(c, st16 + (size_t)cb_begin * PICSONG_CB_WORDS, c->d_sizes + cb_begin, cb_count, nullptr,
+    uint16_t *const st16 = reinterpret_cast<uint16_t *>(c->one.staging);
+    if ((rc = bpc_encode_impl(c, d_coeffs, st16, c->one.sizes, s, cb_begin, cb_count))) return rc;
+    return pack_range(c, st16 + (size_t)cb_begin * PICSONG_CB_WORDS, c->one.sizes + cb_begin, cb_count, nullptr,
                       d_stream, s);
 }
 
@@ -1342,10 +1211,10 @@ int picsong_encode_frame_stripe(picsong_ctx *c, const uint8_t *d_frame, int cb_b
     int rc = ensure_workspace(c, false);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = dwt_forward_impl(c, d_frame, true, c->d_coef, s))) return rc;
-    uint16_t *const st16 = reinterpret_cast<uint16_t *>(c->d_staging);
-    if ((rc = bpc_encode_impl(c, c->d_coef, st16, c->d_sizes, s, cb_begin, cb_count))) return rc;
-    return pack_range(c, st16 + (size_t)cb_begin * PICSONG_CB_WORDS, c->d_sizes + cb_begin, cb_count, nullptr,
+    if ((rc = dwt_forward_impl(c, d_frame, true, c->one.coef, s))) return rc;
+    uint16_t *const st16 = reinterpret_cast<uint16_t *>(c->one.staging);
+    if ((rc = bpc_encode_impl(c, c->one.coef, st16, c->one.sizes, s, cb_begin, cb_count))) return rc;
+    return pack_range(c, st16 + (size_t)cb_begin * PICSONG_CB_WORDS, c->one.sizes + cb_begin, cb_count, nullptr,
                       d_stream, s);
 }
 
@@ -1357,21 +1226,6 @@ int picsong_encode_frame_stripe(picsong_ctx *c, const uint8_t *d_frame, int cb_b
 // (Engines/CodingEngine.cu:990-1061), this is the same frames-in-flight idea without depending on the
 // runtime's queues.
 // ---------------------------------------------------------------------------------------------
-static void free_batch(picsong_ctx *c)
-{
-    if (c->b_coef) (void)hipFree(c->b_coef);
-    if (c->b_staging) (void)hipFree(c->b_staging);
-    if (c->b_sizes) (void)hipFree(c->b_sizes);
-    if (c->b_offsets) (void)hipFree(c->b_offsets);
-    if (c->b_total) (void)hipFree(c->b_total);
-    if (c->b_plane_scratch) (void)hipFree(c->b_plane_scratch);
-    if (c->b_coef_i) (void)hipFree(c->b_coef_i);
-    c->b_coef_i = nullptr; c->b_coef_i_cap = 0;
-    if (c->h_totals) (void)hipHostFree(c->h_totals);
-    c->b_coef = nullptr; c->b_staging = c->b_sizes = c->b_offsets = c->b_total = nullptr;
-    c->b_plane_scratch = nullptr; c->h_totals = nullptr; c->batch_cap = 0;
-}
-
 static int ensure_batch(picsong_ctx *c, int n)
 {
     if (n <= c->batch_cap) return PICSONG_OK;
@@ -1380,12 +1234,13 @@ static int ensure_batch(picsong_ctx *c, int n)
     free_batch(c);
     // (scratch for whole workgroups per frame: the RGB form pads every component's waves to workgroups)
     const size_t waves = (size_t)n * (size_t)dec_scratch_waves(c);
-    HIP_TRY(hipMalloc(&c->b_coef, (size_t)n * (c->P + c->extra) * 4));
-    HIP_TRY(hipMalloc(&c->b_staging, (size_t)n * c->P * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&c->b_sizes, (size_t)n * (size_t)c->ncb * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&c->b_offsets, (size_t)n * (size_t)c->ncb * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&c->b_total, (size_t)n * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&c->b_plane_scratch, waves * kEncScratchDwordsPerWave * sizeof(uint32_t)));
+    Workspace &w = c->batch;
+    HIP_TRY(hipMalloc(&w.coef, (size_t)n * (c->P + c->extra) * 4));
+    HIP_TRY(hipMalloc(&w.staging, (size_t)n * c->P * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(&w.sizes, (size_t)n * (size_t)c->ncb * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(&w.offsets, (size_t)n * (size_t)c->ncb * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(&w.total, (size_t)n * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(&w.plane_scratch, waves * kEncScratchDwordsPerWave * sizeof(uint32_t)));
     HIP_TRY(hipHostMalloc(&c->h_totals, (size_t)n * sizeof(int32_t)));
     c->batch_cap = n;
     return PICSONG_OK;
@@ -1396,37 +1251,19 @@ static int ensure_coef_i(picsong_ctx *c, int n)
 {
     if (c->b_coef_i_cap >= n) return PICSONG_OK;
     HIP_TRY(hipDeviceSynchronize());
-    if (c->b_coef_i) (void)hipFree(c->b_coef_i);
-    c->b_coef_i = nullptr; c->b_coef_i_cap = 0;
-    HIP_TRY(hipMalloc(&c->b_coef_i, (size_t)n * c->P * sizeof(int32_t)));
+    if (c->batch.coef_i) (void)hipFree(c->batch.coef_i);
+    c->batch.coef_i = nullptr; c->b_coef_i_cap = 0;
+    HIP_TRY(hipMalloc(&c->batch.coef_i, (size_t)n * c->P * sizeof(int32_t)));
     c->b_coef_i_cap = n;
     return PICSONG_OK;
 }
 
-// -k > 0 over the frames (or the three components) of a batched call: the BULK coder instantiations, one-wave
-// workgroups -- a frame is exactly its codeblock pairs, no padding waves --, chosen as bpc_encode_impl / bpc_decode_impl
-// choose them for one frame (`cmp`: every table the launch uses takes the compact LDS copies)
-static void launch_bulk_encode_frames(picsong_ctx *c, BpcArgs &a, unsigned frames, bool cmp, hipStream_t s)
+// a batched forward plan: level 0 reads frame z at + z * src_z0 bytes, every level works in frame z's buffer of coef_z bytes
+static void plan_frame_strides(std::vector<FwdLaunch> &plan, unsigned long long src_z0, unsigned long long coef_z)
 {
-    a.waves_per_frame = (c->ncb + 1) / 2;
-    const unsigned wgs = frames * (unsigned)a.waves_per_frame;
-    if (cmp && c->pipelined) bpc_encode_kernel<true, true><<<wgs, 64, 0, s>>>(a);
-    else bpc_encode_kernel<true><<<wgs, 64, 0, s>>>(a);
-}
-// (wpf: the waves of one frame, decode_rect)
-static void launch_bulk_decode_frames(BpcArgs &a, unsigned frames, int wpf, bool cmp, bool direct, bool c16, hipStream_t s)
-{
-    a.waves_per_frame = wpf;
-    const unsigned wgs = frames * (unsigned)a.waves_per_frame;
-    if (direct && c16) {
-        if (cmp) bpc_decode_kernel<true, kDecSmallPlanes, true, true, true><<<wgs, 64, 0, s>>>(a);
-        else bpc_decode_kernel<true, kDecSmallPlanes, true, true><<<wgs, 64, 0, s>>>(a);
-    } else if (direct) {
-        if (cmp) bpc_decode_kernel<true, kDecSmallPlanes, true, false, true><<<wgs, 64, 0, s>>>(a);
-        else bpc_decode_kernel<true, kDecSmallPlanes, true><<<wgs, 64, 0, s>>>(a);
-    } else {
-        if (cmp) bpc_decode_kernel<true, kDecSmallPlanes, false, false, true><<<wgs, 64, 0, s>>>(a);
-        else bpc_decode_kernel<true, kDecSmallPlanes><<<wgs, 64, 0, s>>>(a);
+    for (size_t l = 0; l < plan.size(); l++) {
+        plan[l].a.src_z = l == 0 ? src_z0 : coef_z;
+        plan[l].a.dst_z = coef_z;
     }
 }
 
@@ -1453,51 +1290,29 @@ int picsong_encode_frames(picsong_ctx *c, int n, const uint8_t *d_frames, size_t
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
 
     // ---- DWT: the single-frame plan of frame 0 with grid.z = n
-    std::vector<FwdLaunch> plan = plan_dwt_forward(d_frames, true, c->b_coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16);
+    std::vector<FwdLaunch> plan = plan_dwt_forward(d_frames, true, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16);
     a.c16 = plan_is_c16(plan) ? 1 : 0;
-    for (size_t l = 0; l < plan.size(); l++) {
-        plan[l].a.src_z = l == 0 ? (unsigned long long)frame_stride : (unsigned long long)coef_z;
-        plan[l].a.dst_z = (unsigned long long)coef_z;
-    }
-    Fwd2Launch f2;
-    const bool fused01 = plan_dwt_fwd2(plan, f2, true, c->p.lossy != 0);
-    if (fused01) {
-        launch_fwd2(c->p.lossy != 0, f2, s, (unsigned)n);
-        HIP_TRY(hipGetLastError());
-    }
-    if (int rc = launch_fwd_levels(c, plan, fused01 ? 2 : 0, s, (unsigned)n)) return rc;
+    plan_frame_strides(plan, frame_stride, coef_z);
+    if ((rc = launch_fwd_plan(c, plan, s, (unsigned)n))) return rc;
 
     if (ev) HIP_TRY(hipEventRecord(ev[1], s));
     // ---- coder: one grid over the n frames' codeblock pairs
     const int wpf = (c->ncb + 1) / 2;
     a.cb_base = 0; a.nCB = c->ncb;
-    a.coeffs_in = c->b_coef; a.is_float = c->p.lossy ? 1 : 0;
-    a.staging16 = reinterpret_cast<uint16_t *>(c->b_staging);   // (16-bit staging: frame f's at + f * P shorts)
-    a.sizes = c->b_sizes; a.plane_scratch = c->b_plane_scratch;
+    a.coeffs_in = c->batch.coef; a.is_float = c->p.lossy ? 1 : 0;
+    a.staging16 = reinterpret_cast<uint16_t *>(c->batch.staging);   // (16-bit staging: frame f's at + f * P shorts)
+    a.sizes = c->batch.sizes; a.plane_scratch = c->batch.plane_scratch;
     a.frames = n; a.waves_per_frame = wpf; a.coef_z = coef_z;
-    const size_t waves = (size_t)n * (size_t)wpf;
-    if (a.k > 0.0f) launch_bulk_encode_frames(c, a, (unsigned)n, bulk_compact(c, 0), s);
-    else {
-        if ((rc = plane_img_refresh(c, 0, s))) return rc;
-        bpc_encode_kernel<false><<<(unsigned)((waves + kBpcEncWgWaves - 1) / kBpcEncWgWaves), 64 * kBpcEncWgWaves, 0, s>>>(a);
-    }
-    HIP_TRY(hipGetLastError());
+    // (-k > 0, one-wave workgroups: a frame is exactly its codeblock pairs, no padding waves)
+    if ((rc = launch_encoder(c, a, (unsigned)n * (unsigned)wpf, 0, 1, s))) return rc;
 
     if (ev) HIP_TRY(hipEventRecord(ev[2], s));
-    // ---- pack
-    HeaderArg h;
-    memset(&h, 0, sizeof h);
-    if (first_iter <= 0 && first_iter + n > 0) {          // the batch holds the video's frame 0
-        uint16_t hdr[PICSONG_HDR_SHORTS];
-        picsong_header_pack(&c->p, hdr);
-        memcpy(h.h, hdr, sizeof h.h);
-        h.has = -first_iter + 1;
-    }
-    scan_sizes_kernel<<<(unsigned)n, scan_threads(c->ncb), 0, s>>>(c->b_sizes, c->ncb, c->b_offsets, c->b_total);
-    HIP_TRY(hipGetLastError());
-    pack_kernel<uint16_t><<<dim3(pack_blocks<uint16_t>(c->ncb), (unsigned)n), 256, 0, s>>>(a.staging16, c->b_sizes, c->b_offsets, c->b_total,
-                                                                              c->ncb, h, d_streams, c->P, stream_stride);
-    HIP_TRY(hipGetLastError());
+    // ---- pack: the populated header where the batch holds the video's frame 0
+    uint16_t hdr[PICSONG_HDR_SHORTS];
+    const bool has0 = first_iter <= 0 && first_iter + n > 0;
+    if (has0) picsong_header_pack(&c->p, hdr);
+    if ((rc = pack_frames(c, a.staging16, c->batch, c->ncb, (unsigned)n, has0 ? hdr : nullptr, -first_iter + 1, d_streams,
+                          stream_stride, s))) return rc;
     if (ev) HIP_TRY(hipEventRecord(ev[3], s));
     c->last_batch = n;
     return PICSONG_OK;
@@ -1509,7 +1324,7 @@ int picsong_last_totals(picsong_ctx *c, void *stream, int n, int *h_totals)
     if (n < 1 || n > c->last_batch) return fail(PICSONG_ERR_ARG, "last_totals: %d frames, the last batch had %d", n, c->last_batch);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(c->h_totals, c->b_total, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(c->h_totals, c->batch.total, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (int i = 0; i < n; i++) h_totals[i] = c->h_totals[i];
     return PICSONG_OK;
@@ -1543,64 +1358,35 @@ static int decode_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, 
     c->last_batch = -1;                                     // the batch buffers hold a decode now: no encode totals to hand out
     if ((rc = ensure_coef_i(c, n))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    // ---- unpack: lengths, offsets, codewords of the n streams
-    const bool direct = dec_from_stream(c);                 // the coder reads the streams themselves: no unpack, no staging
-    if (direct) {
-        scan_stream_kernel<<<(unsigned)n, scan_threads(c->ncb), 0, s>>>(d_streams, c->ncb, c->b_sizes, c->b_offsets, c->b_total, c->d_flag, stream_stride);
-        HIP_TRY(hipGetLastError());
-    } else {
-        read_sizes_kernel<<<dim3((unsigned)((c->ncb + 255) / 256), (unsigned)n), 256, 0, s>>>(d_streams, c->ncb, c->b_sizes, c->d_flag,
-                                                                                          stream_stride);
-        HIP_TRY(hipGetLastError());
-        scan_sizes_kernel<<<(unsigned)n, scan_threads(c->ncb), 0, s>>>(c->b_sizes, c->ncb, c->b_offsets, c->b_total);
-        HIP_TRY(hipGetLastError());
-        unpack_kernel<<<dim3((unsigned)c->ncb, (unsigned)n), 256, 0, s>>>(d_streams, c->b_sizes, c->b_offsets, c->ncb, c->b_staging,
-                                                                         stream_stride, c->P);
-        HIP_TRY(hipGetLastError());
-    }
+    // ---- intake: lengths, offsets (and, when the coder does not read the streams itself, codewords) of the n streams
+    const bool direct = dec_from_stream(c);
+    if ((rc = stream_intake(c, d_streams, (unsigned)n, stream_stride, direct, c->batch, s))) return rc;
     // ---- decoder: one grid over the n frames' codeblock pairs, both plane-count classes
     BpcArgs a;
     if ((rc = bpc_args(c, a, 0))) return rc;
     const int wpf = decode_rect(c, a, reduce, win);
     a.cb_base = 0; a.nCB = c->ncb;
-    a.coeffs_out = c->b_coef_i; a.staging = c->b_staging; a.sizes = c->b_sizes; a.plane_scratch = c->b_plane_scratch;
     // (the synthesis is planned first: it says whether this call's coefficients can travel as int16; a window's
     // synthesis reads 32-bit ones)
     bool fused = false;
     const std::vector<InvLaunch> plan = win ? std::vector<InvLaunch>()
-                                            : inverse_plan(c, c->b_coef_i, c->b_coef, d_frames_out, &fused, (unsigned)n,
+                                            : inverse_plan(c, c->batch.coef_i, c->batch.coef, d_frames_out, &fused, (unsigned)n,
                                                            frame_stride, dec_c16_reduced(c, reduce) && direct, false, reduce);
     const bool c16 = plan_inv_is_c16(plan);
     a.frames = n; a.waves_per_frame = wpf; a.coef_z = (unsigned long long)c->P * (c16 ? 2ull : 4ull);
-    const unsigned wgs = (unsigned)(((size_t)n * (size_t)wpf + kBpcDecWgWaves - 1) / kBpcDecWgWaves);
-    if (direct) {
-        a.cw16 = d_streams; a.cw16_offsets = c->b_offsets; a.cw16_total = c->b_total; a.cw16_stride = stream_stride;
-        a.cw16_max = (uint32_t)picsong_max_stream_shorts(c->aw, c->ah);
-    }
-    if (a.k > 0.0f) launch_bulk_decode_frames(a, (unsigned)n, wpf, bulk_compact(c, 0), direct, c16, s);
-    else if (direct) {
-        if (c16) bpc_decode_kernel<false, kDecSmallPlanes, true, true><<<wgs, 64 * kBpcDecWgWaves, 0, s>>>(a);
-        else bpc_decode_kernel<false, kDecSmallPlanes, true><<<wgs, 64 * kBpcDecWgWaves, 0, s>>>(a);
-    } else {
-        bpc_decode_kernel<false, kDecSmallPlanes><<<wgs, 64 * kBpcDecWgWaves, 0, s>>>(a);
-    }
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch_decoder(c, a, (unsigned)n * (unsigned)wpf, a.k > 0.0f && bulk_compact(c, 0), c->batch,
+                             direct ? d_streams : nullptr, stream_stride, c16, s))) return rc;
     if (win)
-        return run_window(c, *win, c->b_coef_i, c->b_coef, (unsigned)n, (unsigned long long)c->P * 4ull,
+        return run_window(c, *win, c->batch.coef_i, c->batch.coef, (unsigned)n, (unsigned long long)c->P * 4ull,
                           (unsigned long long)(c->P + c->extra) * 4ull, d_frames_out, pitch, frame_stride, s);
     // ---- inverse transform, pixels out of the finest level where its vector kernel applies
     if ((rc = run_inverse(c, plan, s, (unsigned)n))) return rc;
     if (fused) return PICSONG_OK;
-    const size_t n4 = px / 4;
-    const int off = 1 << (c->p.bit_depth - 1);
-    const int grid = (int)((n4 + 255) / 256 > 8192 ? 8192 : (n4 + 255) / 256);
     for (int f = 0; f < n; f++) {
         // (level `reduce`'s samples of frame f: c->extra elements into its work buffer when reduce = 0)
         const void *img = (const char *)plan.back().a.dst + (size_t)f * (c->P + c->extra) * 4;
-        if (c->p.lossy) clamp_to_u8_f32_kernel<<<grid, 256, 0, s>>>((const float *)img, d_frames_out + (size_t)f * frame_stride, n4, (float)off);
-        else clamp_to_u8_i32_kernel<<<grid, 256, 0, s>>>((const int32_t *)img, d_frames_out + (size_t)f * frame_stride, n4, off);
+        if ((rc = clamp_pixels(c, img, d_frames_out + (size_t)f * frame_stride, px / 4, s))) return rc;
     }
-    HIP_TRY(hipGetLastError());
     return PICSONG_OK;
 }
 
@@ -1637,7 +1423,7 @@ int picsong_copy_last_totals(picsong_ctx *c, void *stream, int n, int32_t *d_tot
     if (!single && (n < 1 || n > c->last_batch))
         return fail(PICSONG_ERR_ARG, "copy_last_totals: %d frames, the last batch had %d", n, c->last_batch);
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(d_totals, single ? c->d_total : c->b_total, (size_t)n * sizeof(int32_t),
+    HIP_TRY(hipMemcpyAsync(d_totals, single ? c->one.total : c->batch.total, (size_t)n * sizeof(int32_t),
                            hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PICSONG_OK;
 }
@@ -1652,7 +1438,7 @@ int picsong_rgb_forward(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, 
     hipStream_t s = (hipStream_t)stream;
     const size_t n4 = c->P / 4;
     const int off = 1 << (c->p.bit_depth - 1);
-    const int grid = (int)((n4 + 255) / 256 > 8192 ? 8192 : (n4 + 255) / 256);
+    const unsigned grid = elementwise_blocks(n4);
     if (c->p.lossy) rgb_forward_kernel<float><<<grid, 256, 0, s>>>(d_r, d_g, d_b, (float *)d_c0, (float *)d_c1, (float *)d_c2, n4, off);
     else rgb_forward_kernel<int32_t><<<grid, 256, 0, s>>>(d_r, d_g, d_b, (int32_t *)d_c0, (int32_t *)d_c1, (int32_t *)d_c2, n4, off);
     HIP_TRY(hipGetLastError());
@@ -1664,7 +1450,7 @@ static int rgb_inverse_n(picsong_ctx *c, const void *d_c0, const void *d_c1, con
                          uint8_t *d_b, size_t n4, hipStream_t s)
 {
     const int off = 1 << (c->p.bit_depth - 1);
-    const int grid = (int)((n4 + 255) / 256 > 8192 ? 8192 : (n4 + 255) / 256);
+    const unsigned grid = elementwise_blocks(n4);
     if (c->p.lossy) rgb_inverse_kernel<float><<<grid, 256, 0, s>>>((const float *)d_c0, (const float *)d_c1, (const float *)d_c2, d_r, d_g, d_b, n4, off);
     else rgb_inverse_kernel<int32_t><<<grid, 256, 0, s>>>((const int32_t *)d_c0, (const int32_t *)d_c1, (const int32_t *)d_c2, d_r, d_g, d_b, n4, off);
     HIP_TRY(hipGetLastError());
@@ -1684,12 +1470,12 @@ int picsong_encode_plane(picsong_ctx *c, const void *d_plane, int comp, int with
     int rc = ensure_workspace(c, false);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = dwt_forward_impl(c, d_plane, false, c->d_coef, s))) return rc;
-    uint16_t *const st16 = reinterpret_cast<uint16_t *>(c->d_staging);
-    if ((rc = bpc_encode_impl(c, c->d_coef, st16, c->d_sizes, s, 0, -1, comp))) return rc;
+    if ((rc = dwt_forward_impl(c, d_plane, false, c->one.coef, s))) return rc;
+    uint16_t *const st16 = reinterpret_cast<uint16_t *>(c->one.staging);
+    if ((rc = bpc_encode_impl(c, c->one.coef, st16, c->one.sizes, s, 0, -1, comp))) return rc;
     uint16_t hdr[PICSONG_HDR_SHORTS];
     if (with_header) picsong_header_pack(&c->p, hdr);
-    return pack_range(c, st16, c->d_sizes, c->ncb, with_header ? hdr : nullptr, d_stream, s);
+    return pack_range(c, st16, c->one.sizes, c->ncb, with_header ? hdr : nullptr, d_stream, s);
 }
 
 int picsong_decode_plane(picsong_ctx *c, const uint16_t *d_stream, int comp, void *d_plane_out, void *stream)
@@ -1698,13 +1484,19 @@ int picsong_decode_plane(picsong_ctx *c, const uint16_t *d_stream, int comp, voi
     int rc = ensure_workspace(c, true);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = decode_stream_impl(c, d_stream, c->d_coef_i, s, comp))) return rc;
-    return picsong_dwt_inverse(c, c->d_coef_i, d_plane_out, stream);
+    if ((rc = decode_stream_impl(c, d_stream, c->one.coef_i, s, comp))) return rc;
+    return picsong_dwt_inverse(c, c->one.coef_i, d_plane_out, stream);
 }
 
 
 // The three component tables of an RGB context for ONE coder grid: same geometry, every frame f of the batched
-// launch coding with table f; waves_per_frame = whole workgroups.
+// launch coding with table f; k = 0: a component's waves_per_frame are whole workgroups; -k > 0 (one-wave workgroups):
+// exactly its waves.
+static int rgb_component_waves(const BpcArgs &a, int wpf)
+{
+    static_assert(kBpcEncWgWaves == kBpcDecWgWaves, "one layout serves the launches of both directions");
+    return a.k > 0.0f ? wpf : (wpf + kBpcEncWgWaves - 1) / kBpcEncWgWaves * kBpcEncWgWaves;
+}
 static int bpc_args_rgb(picsong_ctx *c, BpcArgs &a)
 {
     int rc = bpc_args(c, a, 0);
@@ -1717,9 +1509,8 @@ static int bpc_args_rgb(picsong_ctx *c, BpcArgs &a)
             return fail(PICSONG_ERR_ARG, "the components' tables differ in geometry: code the planes one by one (picsong_encode_plane)");
     }
     for (int k = 0; k < 3; k++) { a.lut_c[k] = c->d_lut[k]; a.img_c[k] = ctx_uses_plane_img(c) ? c->d_img[k] : nullptr; }
-    const int wpf = (c->ncb + 1) / 2;
     a.cb_base = 0; a.nCB = c->ncb;
-    a.frames = 3; a.waves_per_frame = (wpf + kBpcEncWgWaves - 1) / kBpcEncWgWaves * kBpcEncWgWaves;
+    a.frames = 3; a.waves_per_frame = rgb_component_waves(a, (c->ncb + 1) / 2);
     return PICSONG_OK;
 }
 
@@ -1738,7 +1529,7 @@ int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *
     if ((rc = ensure_coef_i(c, 3))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t coef_z = (c->P + c->extra) * 4;
-    char *planes = (char *)c->b_coef_i;
+    char *planes = (char *)c->batch.coef_i;
     // ---- lossless: the colour transform in the fused head's load stage (dwt_fwd2_kernel<..., RGB>): the head reads the
     // three u8 planes and delivers component blockIdx.z -- no component plane is ever written (the separate transform
     // kernel reads 100 MB and writes 400 MB of them per 8K frame, and level 0 reads them back)
@@ -1747,18 +1538,13 @@ int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *
     // separate colour transform below)
     const bool planes_aligned = ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 15u) == 0;
     if (c->c16 && planes_aligned && !getenv("PICSONG_RGB_NOFUSE")) {
-        std::vector<FwdLaunch> plan = plan_dwt_forward(d_r, true, c->b_coef, c->aw, c->ah, c->p.wl, c->p.qs, true);
+        std::vector<FwdLaunch> plan = plan_dwt_forward(d_r, true, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, true);
+        plan_frame_strides(plan, 0, coef_z);                 // level 0: every component reads the three planes
+        plan[0].a.src_g = d_g; plan[0].a.src_b = d_b;
         Fwd2Launch f2;
         if (plan_is_c16(plan) && plan_dwt_fwd2(plan, f2, true, c->p.lossy != 0, kF2PairsRgb)) {
-            for (size_t l = 0; l < plan.size(); l++) {
-                plan[l].a.src_z = l == 0 ? 0ull : (unsigned long long)coef_z;      // level 0: every component reads the three planes
-                plan[l].a.dst_z = (unsigned long long)coef_z;
-            }
-            plan[0].a.src_g = d_g; plan[0].a.src_b = d_b;
-            f2.a.l0 = plan[0].a; f2.a.l1 = plan[1].a;
             // (RCT on the integer head, ICT on the 9/7 one: the component planes are never written)
-            if (c->p.lossy) dwt_fwd2_kernel<float, true, true, kF2PairsRgb, true, true><<<dim3(f2.gx, f2.gy, 3u), 256, 0, s>>>(f2.a);
-            else dwt_fwd2_kernel<int, false, true, kF2PairsRgb, true, true><<<dim3(f2.gx, f2.gy, 3u), 256, 0, s>>>(f2.a);
+            select_fwd2(c->p.lossy != 0, true, true)<<<dim3(f2.gx, f2.gy, 3u), 256, 0, s>>>(f2.a);
             HIP_TRY(hipGetLastError());
             if ((rc = launch_fwd_levels(c, plan, 2, s, 3u))) return rc;
             a.c16 = 1;
@@ -1768,39 +1554,21 @@ int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *
     if (!fused_rgb) {
     // ---- colour transform (level shift fused) into three planes, then the transform of all three per launch
     if ((rc = picsong_rgb_forward(c, d_r, d_g, d_b, planes, planes + c->P * 4, planes + 2 * c->P * 4, stream))) return rc;
-    std::vector<FwdLaunch> plan = plan_dwt_forward(planes, false, c->b_coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16);
+    std::vector<FwdLaunch> plan = plan_dwt_forward(planes, false, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16);
     a.c16 = plan_is_c16(plan) ? 1 : 0;
-    for (size_t l = 0; l < plan.size(); l++) {
-        plan[l].a.src_z = l == 0 ? (unsigned long long)c->P * 4ull : (unsigned long long)coef_z;
-        plan[l].a.dst_z = (unsigned long long)coef_z;
-    }
+    plan_frame_strides(plan, (unsigned long long)c->P * 4ull, coef_z);
     if ((rc = launch_fwd_levels(c, plan, 0, s, 3u))) return rc;
     }
     // ---- coder: one grid over the three components' codeblock pairs, component f with table f
-    a.coeffs_in = c->b_coef; a.is_float = c->p.lossy ? 1 : 0;
-    a.staging16 = reinterpret_cast<uint16_t *>(c->b_staging);
-    a.sizes = c->b_sizes; a.plane_scratch = c->b_plane_scratch; a.coef_z = coef_z;
-    if (a.k > 0.0f) {
-        launch_bulk_encode_frames(c, a, 3u, bulk_compact(c, 0) && bulk_compact(c, 1) && bulk_compact(c, 2), s);
-    } else {
-        for (int k = 0; k < 3; k++) if ((rc = plane_img_refresh(c, k, s))) return rc;
-        bpc_encode_kernel<false><<<(unsigned)(3 * a.waves_per_frame / kBpcEncWgWaves), 64 * kBpcEncWgWaves, 0, s>>>(a);
-    }
-    HIP_TRY(hipGetLastError());
+    a.coeffs_in = c->batch.coef; a.is_float = c->p.lossy ? 1 : 0;
+    a.staging16 = reinterpret_cast<uint16_t *>(c->batch.staging);
+    a.sizes = c->batch.sizes; a.plane_scratch = c->batch.plane_scratch; a.coef_z = coef_z;
+    if ((rc = launch_encoder(c, a, 3u * (unsigned)a.waves_per_frame, 0, 3, s))) return rc;
     // ---- pack: the populated header on the components of header_mask
-    HeaderArg h;
-    memset(&h, 0, sizeof h);
-    if (header_mask & 7) {
-        uint16_t hdr[PICSONG_HDR_SHORTS];
-        picsong_header_pack(&c->p, hdr);
-        memcpy(h.h, hdr, sizeof h.h);
-        h.has = -(header_mask & 7);
-    }
-    scan_sizes_kernel<<<3, scan_threads(c->ncb), 0, s>>>(c->b_sizes, c->ncb, c->b_offsets, c->b_total);
-    HIP_TRY(hipGetLastError());
-    pack_kernel<uint16_t><<<dim3(pack_blocks<uint16_t>(c->ncb), 3u), 256, 0, s>>>(a.staging16, c->b_sizes, c->b_offsets, c->b_total, c->ncb, h,
-                                                          d_streams, c->P, stream_stride);
-    HIP_TRY(hipGetLastError());
+    uint16_t hdr[PICSONG_HDR_SHORTS];
+    if (header_mask & 7) picsong_header_pack(&c->p, hdr);
+    if ((rc = pack_frames(c, a.staging16, c->batch, c->ncb, 3u, (header_mask & 7) ? hdr : nullptr, -(header_mask & 7), d_streams,
+                          stream_stride, s))) return rc;
     c->last_batch = 3;
     return PICSONG_OK;
 }
@@ -1822,97 +1590,48 @@ static int decode_rgb_impl(picsong_ctx *c, const uint16_t *d_streams, size_t str
     BpcArgs a;
     int rc = bpc_args_rgb(c, a);
     if (rc) return rc;
-    // (k = 0: a component's waves are whole workgroups, as bpc_args_rgb lays them; -k > 0: exactly its waves)
-    const int wpf = decode_rect(c, a, reduce, win);
-    if (reduce > 0 || win) a.waves_per_frame = (wpf + kBpcDecWgWaves - 1) / kBpcDecWgWaves * kBpcDecWgWaves;
+    a.waves_per_frame = rgb_component_waves(a, decode_rect(c, a, reduce, win));
     if ((rc = ensure_batch(c, 3))) return rc;
     if ((rc = ensure_coef_i(c, 3))) return rc;
     c->last_batch = -1;
     hipStream_t s = (hipStream_t)stream;
     const bool direct = dec_from_stream(c);
-    if (direct) {
-        scan_stream_kernel<<<3, scan_threads(c->ncb), 0, s>>>(d_streams, c->ncb, c->b_sizes, c->b_offsets, c->b_total, c->d_flag, stream_stride);
-        HIP_TRY(hipGetLastError());
-    } else {
-        read_sizes_kernel<<<dim3((unsigned)((c->ncb + 255) / 256), 3u), 256, 0, s>>>(d_streams, c->ncb, c->b_sizes, c->d_flag, stream_stride);
-        HIP_TRY(hipGetLastError());
-        scan_sizes_kernel<<<3, scan_threads(c->ncb), 0, s>>>(c->b_sizes, c->ncb, c->b_offsets, c->b_total);
-        HIP_TRY(hipGetLastError());
-        unpack_kernel<<<dim3((unsigned)c->ncb, 3u), 256, 0, s>>>(d_streams, c->b_sizes, c->b_offsets, c->ncb, c->b_staging, stream_stride, c->P);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = stream_intake(c, d_streams, 3u, stream_stride, direct, c->batch, s))) return rc;
     // (16-bit coefficients between the decoder and the synthesis where the context's magnitudes are bounded: the
     // plan says whether this call's arrays take the vector kernels; a window's synthesis reads 32-bit ones)
     const std::vector<InvLaunch> plan = win ? std::vector<InvLaunch>()
-                                            : inverse_plan(c, c->b_coef_i, c->b_coef, nullptr, nullptr, 3u, 0,
+                                            : inverse_plan(c, c->batch.coef_i, c->batch.coef, nullptr, nullptr, 3u, 0,
                                                            dec_c16_reduced(c, reduce) && direct, true, reduce);
     const bool c16 = plan_inv_is_c16(plan);
-    a.coeffs_out = c->b_coef_i; a.staging = c->b_staging; a.sizes = c->b_sizes; a.plane_scratch = c->b_plane_scratch;
     a.coef_z = (unsigned long long)c->P * (c16 ? 2ull : 4ull);
-    const unsigned wgs3 = (unsigned)(3 * a.waves_per_frame / kBpcDecWgWaves);
-    if (direct) {
-        a.cw16 = d_streams; a.cw16_offsets = c->b_offsets; a.cw16_total = c->b_total; a.cw16_stride = stream_stride;
-        a.cw16_max = (uint32_t)picsong_max_stream_shorts(c->aw, c->ah);
-    }
-    if (a.k > 0.0f) {
-        launch_bulk_decode_frames(a, 3u, wpf, bulk_compact(c, 0) && bulk_compact(c, 1) && bulk_compact(c, 2), direct, c16, s);
-    } else if (direct) {
-        if (c16) bpc_decode_kernel<false, kDecSmallPlanes, true, true><<<wgs3, 64 * kBpcDecWgWaves, 0, s>>>(a);
-        else bpc_decode_kernel<false, kDecSmallPlanes, true><<<wgs3, 64 * kBpcDecWgWaves, 0, s>>>(a);
-    } else {
-        bpc_decode_kernel<false, kDecSmallPlanes><<<wgs3, 64 * kBpcDecWgWaves, 0, s>>>(a);
-    }
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch_decoder(c, a, 3u * (unsigned)a.waves_per_frame, a.k > 0.0f && bulk_compact(c, 0, 3), c->batch,
+                             direct ? d_streams : nullptr, stream_stride, c16, s))) return rc;
     if (win) {      // the three components' cones (grid.z = component), then the inverse RCT / ICT over the window
         const unsigned long long z = (unsigned long long)(c->P + c->extra) * 4ull;
-        if ((rc = run_window(c, *win, c->b_coef_i, c->b_coef, 3u, (unsigned long long)c->P * 4ull, z, nullptr, 0, 0, s))) return rc;
+        if ((rc = run_window(c, *win, c->batch.coef_i, c->batch.coef, 3u, (unsigned long long)c->P * 4ull, z, nullptr, 0, 0, s))) return rc;
         const IRect &o = win->R[reduce];
         const int w = o.x1 - o.x0, h = o.y1 - o.y0, off = 1 << (c->p.bit_depth - 1);
         const dim3 grid((unsigned)((w + 255) / 256), (unsigned)h);
-        if (c->p.lossy) window_rgb_kernel<float><<<grid, 256, 0, s>>>((const float *)c->b_coef, z, w, h, d_r, d_g, d_b, pitch, off);
-        else window_rgb_kernel<int><<<grid, 256, 0, s>>>((const int *)c->b_coef, z, w, h, d_r, d_g, d_b, pitch, off);
+        if (c->p.lossy) window_rgb_kernel<float><<<grid, 256, 0, s>>>((const float *)c->batch.coef, z, w, h, d_r, d_g, d_b, pitch, off);
+        else window_rgb_kernel<int><<<grid, 256, 0, s>>>((const int *)c->batch.coef, z, w, h, d_r, d_g, d_b, pitch, off);
         HIP_TRY(hipGetLastError());
         return PICSONG_OK;
     }
-    // 5/3 with 16-bit coefficients: the finest level of the three components and the inverse colour transform as ONE
-    // launch (dwt_inv_rgb_kernel: the 32-bit planes are never written); PICSONG_RGB_NOFUSE=1 keeps the two
+    // 16-bit coefficients: the finest level of the three components and the inverse colour transform as ONE launch
+    // (select_inv_rgb; PICSONG_RGB_NOFUSE=1 keeps the two).  5/3: the 32-bit planes are never written (dwt_inv_rgb_kernel).
+    // 9/7, the lean kernel's domain: the three components as the three waves of a workgroup, a row pair exchanged
+    // through LDS, the inverse ICT at the stores (dwt_inv97_rgb_kernel).
     const bool px_aligned = ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 3u) == 0;
-    if (!c->p.lossy && c16 && plan.size() >= 2 && plan.back().vec && px_aligned && !getenv("PICSONG_RGB_NOFUSE")) {
+    bool tail = c16 && plan.size() >= 2 && plan.back().vec && px_aligned && !getenv("PICSONG_RGB_NOFUSE");
+    if (tail && c->p.lossy)
+        tail = plan.back().fast && !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0);
+    if (tail) {
         std::vector<InvLaunch> head(plan.begin(), plan.end() - 1);
         if ((rc = run_inverse(c, head, s, 3u))) return rc;
-        const InvLaunch &f = plan.back();
-        DwtInvArgs fa = f.a;
+        DwtInvArgs fa = plan.back().a;
         fa.off = 1 << (c->p.bit_depth - 1);
-        const dim3 grid(f.gx, f.gy, 1);
-        switch (f.band) {
-        case 32: dwt_inv_rgb_kernel<32><<<grid, 256, 0, s>>>(fa, d_r, d_g, d_b); break;
-        case 16: dwt_inv_rgb_kernel<16><<<grid, 256, 0, s>>>(fa, d_r, d_g, d_b); break;
-        case 8: dwt_inv_rgb_kernel<8><<<grid, 256, 0, s>>>(fa, d_r, d_g, d_b); break;
-        default: dwt_inv_rgb_kernel<4><<<grid, 256, 0, s>>>(fa, d_r, d_g, d_b); break;
-        }
-        HIP_TRY(hipGetLastError());
-        return PICSONG_OK;
-    }
-    // 9/7 with 16-bit coefficients (the lean kernel's domain): the finest level of the three components as the three
-    // waves of a workgroup, a row pair exchanged through LDS, the inverse ICT at the stores (dwt_inv97_rgb_kernel)
-    if (c->p.lossy && c16 && plan.size() >= 2 && plan.back().vec && plan.back().fast && px_aligned && !getenv("PICSONG_RGB_NOFUSE") &&
-        !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0)) {
-        std::vector<InvLaunch> head(plan.begin(), plan.end() - 1);
-        if ((rc = run_inverse(c, head, s, 3u))) return rc;
-        const InvLaunch &f = plan.back();
-        DwtInvArgs fa = f.a;
-        fa.off = 1 << (c->p.bit_depth - 1);
-        const dim3 grid((unsigned)((fa.W + kStripUseful - 1) / kStripUseful), f.gy, 1);
-#define PS_INV97_RGB(B)                                                                              \
-        do { if (fa.one_div) dwt_inv97_rgb_kernel<B, true><<<grid, 192, 0, s>>>(fa, d_r, d_g, d_b);   \
-             else dwt_inv97_rgb_kernel<B, false><<<grid, 192, 0, s>>>(fa, d_r, d_g, d_b); } while (0)
-        switch (f.band) {
-        case 32: PS_INV97_RGB(32); break;
-        case 16: PS_INV97_RGB(16); break;
-        case 8: PS_INV97_RGB(8); break;
-        default: PS_INV97_RGB(4); break;
-        }
-#undef PS_INV97_RGB
+        const InvRgbLaunch l = select_inv_rgb(c->p.lossy != 0, plan.back());
+        l.kernel<<<dim3(l.gx, l.gy, 1), l.threads, 0, s>>>(fa, d_r, d_g, d_b);
         HIP_TRY(hipGetLastError());
         return PICSONG_OK;
     }

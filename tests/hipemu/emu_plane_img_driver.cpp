@@ -1,25 +1,20 @@
 // TEST INFRASTRUCTURE ONLY -- the k = 0 encoder's plane records (bpc_kernels.hpp: plane_record, plane_img_kernel,
-// plane_lut_img) and the one-wave-a-codeblock pack on the CPU wave emulator, launched as picsong_hip.hip launches them.
+// plane_lut_img) and the one-wave-a-codeblock pack on the CPU wave emulator, launched as picsong_hip.hip launches them
+// (kernel_select.hpp: the encoder's kernel, grid and scratch).
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
-#include "../../cuda-image-and-video-codec_amd/csrc/bpc_kernels.hpp"
-#include "../../cuda-image-and-video-codec_amd/csrc/pack_kernels.hpp"
+#include "../../cuda-image-and-video-codec_amd/csrc/kernel_select.hpp"
 
 using namespace picsong;
-
-static LutGeo geo_of(const int *geo)
-{
-    return LutGeo{geo[0], geo[1], geo[2], geo[3], geo[4], geo[5], geo[6], geo[7], geo[8]};
-}
 
 extern "C" int emu_plane_img_recs(int wl) { return plane_img_recs(wl); }
 
 // the records as picsong_ctx_set_lut_component builds them (host) or as plane_img_kernel does (a caller's device table)
 extern "C" void emu_plane_img_build(const int32_t *lut, const int *geo, int wl, int by_kernel, uint32_t *out)
 {
-    const LutGeo g = geo_of(geo);
+    const LutGeo g = lut_geo(geo);
     PlaneRec *img = reinterpret_cast<PlaneRec *>(out);
     if (by_kernel) emu::launch(dim3(1), dim3(256), [&] { plane_img_kernel(lut, g, wl, img); });
     else for (int i = 0; i < plane_img_recs(wl); i++) img[i] = plane_record(lut, g, i / kMaxPlanes, i % kMaxPlanes);
@@ -28,7 +23,7 @@ extern "C" void emu_plane_img_build(const int32_t *lut, const int *geo, int wl, 
 // plane_lut<true> over the byte copy of the table the coders keep in LDS: {sig0, sig1, sig8, sign, ref, sig8x4}
 extern "C" void emu_plane_lut_ref(const int32_t *lut, const int *geo, int grp, int bp, uint32_t *out)
 {
-    const LutGeo g = geo_of(geo);
+    const LutGeo g = lut_geo(geo);
     const int total = g.nRef + g.nSig + g.nSign;
     std::vector<uint8_t> bytes((size_t)total);
     for (int i = 0; i < total; i++) bytes[i] = (uint8_t)((uint32_t)lut[i] & 0xFFu);
@@ -50,32 +45,30 @@ extern "C" void emu_plane_lut_img(const uint32_t *img, int slot, int bp, uint32_
 extern "C" void emu_bpc_encode_img(const int32_t *coeffs, int aw, int ah, int wl, const int32_t *const *luts, const int *geo,
                                    int frames, int32_t *staging, int32_t *sizes, int *flag)
 {
-    const LutGeo g = geo_of(geo);
+    const LutGeo g = lut_geo(geo);
     const int ncb = (aw / 64) * (ah / 64), wpf = (ncb + 1) / 2;
     std::vector<std::vector<PlaneRec>> imgs((size_t)frames);
     for (int f = 0; f < frames; f++) {
         imgs[f].resize((size_t)plane_img_recs(wl));
         for (int i = 0; i < plane_img_recs(wl); i++) imgs[f][i] = plane_record(luts[f], g, i / kMaxPlanes, i % kMaxPlanes);
     }
-    BpcArgs a;
-    memset(&a, 0, sizeof a);
-    a.AW = aw; a.AH = ah; a.wl = wl; a.ncx = aw / 64; a.nCB = ncb; a.cb_base = 0;
-    a.g = g; a.range_flag = flag; a.sizes = sizes;
-    a.coeffs_in = coeffs; a.is_float = 0; a.c16 = 0;
+    BpcArgs a = bpc_frame_args(aw, ah, wl, luts[0], g, flag);
+    a.sizes = sizes; a.coeffs_in = coeffs;
     a.k = 0.0f; a.n_tables = 1;
-    a.lut = luts[0]; a.plane_img = imgs[0].data();
+    a.plane_img = imgs[0].data();
     std::vector<uint16_t> st16((size_t)frames * (size_t)aw * (size_t)ah, 0xDEADu);     // poisoned
     a.staging16 = st16.data();
-    unsigned wgs = (unsigned)((wpf + kBpcEncWgWaves - 1) / kBpcEncWgWaves);
+    unsigned waves = (unsigned)wpf;
     if (frames > 1) {
         a.frames = frames; a.waves_per_frame = (wpf + kBpcEncWgWaves - 1) / kBpcEncWgWaves * kBpcEncWgWaves;
         a.coef_z = (unsigned long long)aw * (unsigned long long)ah * 4ull;
         for (int f = 0; f < frames && f < 3; f++) { a.lut_c[f] = luts[f]; a.img_c[f] = imgs[f].data(); }
-        wgs = (unsigned)(frames * a.waves_per_frame / kBpcEncWgWaves);
+        waves = (unsigned)(frames * a.waves_per_frame);
     }
-    std::vector<uint32_t> plane_scratch((size_t)wgs * kBpcEncWgWaves * kEncScratchDwordsPerWave, 0xDEADBEEFu);
+    const BpcLaunch enc = select_encoder(false, false, false, waves);
+    std::vector<uint32_t> plane_scratch(enc.scratch_dwords, 0xDEADBEEFu);
     a.plane_scratch = plane_scratch.data();
-    emu::launch(dim3(wgs), dim3(64 * kBpcEncWgWaves), [&] { bpc_encode_kernel<false>(a); });
+    emu::launch(dim3(enc.wgs), dim3(enc.threads), [&] { enc.kernel(a); });
     memset(staging, 0xFF, (size_t)frames * (size_t)aw * (size_t)ah * 4);
     for (int f = 0; f < frames; f++)
         emu::launch(dim3((unsigned)ncb), dim3(256), [&] {

@@ -1,61 +1,13 @@
 // TEST INFRASTRUCTURE ONLY -- the reduced-resolution decode (picsong_decode_frame_reduced) on the CPU wave emulator:
 // the decoder over the codeblock rectangle of the 1/2^r image's corner and the synthesis stopped at level r, through
-// the same plan functions (launch_plan.hpp) and kernel sources as cuda-image-and-video-codec_amd/csrc/picsong_hip.hip.
+// the same plan functions (launch_plan.hpp), the same choice of kernel, grid and scratch (kernel_select.hpp) and the same
+// kernel sources as cuda-image-and-video-codec_amd/csrc/picsong_hip.hip.
 // Built by tests/test_reduced_decode_emulated.py with the flags of tests/hipemu/Makefile.
 #include <hip/hip_runtime.h>
 
-#include "../../cuda-image-and-video-codec_amd/csrc/bpc_kernels.hpp"
-#include "../../cuda-image-and-video-codec_amd/csrc/dwt_kernels.hpp"
-#include "../../cuda-image-and-video-codec_amd/csrc/launch_plan.hpp"
-#include "../../cuda-image-and-video-codec_amd/csrc/pack_kernels.hpp"
+#include "../../cuda-image-and-video-codec_amd/csrc/kernel_select.hpp"
 
 using namespace picsong;
-
-template <int BAND> static void red_inv(const InvLaunch &f, int lossy)
-{   // mirrors launch_inv (picsong_hip.hip) for the instantiations a frame path selects
-    DwtInvArgs a = f.a;
-    const dim3 grid(f.gx, f.gy);
-    if (a.c16) {
-        if (lossy) {
-            if (a.dst_u8) {
-                if (a.one_div) emu::launch(grid, dim3(256), [&] { dwt_inv97_kernel<BAND, true, false, true, true>(a); });
-                else emu::launch(grid, dim3(256), [&] { dwt_inv97_kernel<BAND, true, false, false, true>(a); });
-            } else if (a.first) {
-                if (a.one_div) emu::launch(grid, dim3(256), [&] { dwt_inv97_kernel<BAND, false, true, true, true>(a); });
-                else emu::launch(grid, dim3(256), [&] { dwt_inv97_kernel<BAND, false, true, false, true>(a); });
-            } else {
-                if (a.one_div) emu::launch(grid, dim3(256), [&] { dwt_inv97_kernel<BAND, false, false, true, true>(a); });
-                else emu::launch(grid, dim3(256), [&] { dwt_inv97_kernel<BAND, false, false, false, true>(a); });
-            }
-        } else if (a.dst_u8) emu::launch(grid, dim3(256), [&] { dwt_inv_kernel<int, false, BAND, true, true, false, true>(a); });
-        else emu::launch(grid, dim3(256), [&] { dwt_inv_kernel<int, false, BAND, true, false, false, true>(a); });
-        return;
-    }
-    if (lossy && f.fast && f.vec && !(a.first && a.dst_u8)) {
-        if (a.dst_u8) {
-            if (a.one_div) emu::launch(grid, dim3(256), [&] { dwt_inv97_kernel<BAND, true, false, true>(a); });
-            else emu::launch(grid, dim3(256), [&] { dwt_inv97_kernel<BAND, true, false, false>(a); });
-        } else if (a.first) {
-            if (a.one_div) emu::launch(grid, dim3(256), [&] { dwt_inv97_kernel<BAND, false, true, true>(a); });
-            else emu::launch(grid, dim3(256), [&] { dwt_inv97_kernel<BAND, false, true, false>(a); });
-        } else {
-            if (a.one_div) emu::launch(grid, dim3(256), [&] { dwt_inv97_kernel<BAND, false, false, true>(a); });
-            else emu::launch(grid, dim3(256), [&] { dwt_inv97_kernel<BAND, false, false, false>(a); });
-        }
-    } else if (f.vec && a.dst_u8) {
-        if (lossy && f.fast) emu::launch(grid, dim3(256), [&] { dwt_inv_kernel<float, true, BAND, true, true, true>(a); });
-        else if (lossy) emu::launch(grid, dim3(256), [&] { dwt_inv_kernel<float, true, BAND, true, true>(a); });
-        else emu::launch(grid, dim3(256), [&] { dwt_inv_kernel<int, false, BAND, true, true>(a); });
-    } else if (f.vec) {
-        if (lossy && f.fast) emu::launch(grid, dim3(256), [&] { dwt_inv_kernel<float, true, BAND, true, false, true>(a); });
-        else if (lossy) emu::launch(grid, dim3(256), [&] { dwt_inv_kernel<float, true, BAND, true>(a); });
-        else emu::launch(grid, dim3(256), [&] { dwt_inv_kernel<int, false, BAND, true>(a); });
-    } else {
-        if (lossy && f.fast) emu::launch(grid, dim3(256), [&] { dwt_inv_kernel<float, true, BAND, false, false, true>(a); });
-        else if (lossy) emu::launch(grid, dim3(256), [&] { dwt_inv_kernel<float, true, BAND, false>(a); });
-        else emu::launch(grid, dim3(256), [&] { dwt_inv_kernel<int, false, BAND, false>(a); });
-    }
-}
 
 extern "C" {
 
@@ -93,13 +45,8 @@ int emu_decode_reduced(const uint16_t *stream, unsigned stream_shorts, int aw, i
     std::vector<int32_t> sizes(ncb), offsets(ncb), stage;
     int32_t total = 0;
     int bad = 0;
-    BpcArgs a;
-    memset(&a, 0, sizeof a);
-    a.AW = aw; a.AH = ah; a.wl = wl; a.ncx = aw / 64; a.nCB = ncb;
-    a.lut = lut;
-    a.g.nBp = geo[0]; a.g.nSub = geo[1]; a.g.cRef = geo[2]; a.g.cSign = geo[3]; a.g.cSig = geo[4];
-    a.g.prec = geo[5]; a.g.nRef = geo[6]; a.g.nSig = geo[7]; a.g.nSign = geo[8];
-    a.range_flag = flag; a.sizes = sizes.data(); a.coeffs_out = coef;
+    BpcArgs a = bpc_frame_args(aw, ah, wl, lut, lut_geo(geo), flag);
+    a.sizes = sizes.data(); a.coeffs_out = coef;
     a.k = k; a.n_tables = n_tables;
     if (r > 0) {
         const ReducedRect q = reduced_rect(aw, ah, r);
@@ -117,55 +64,29 @@ int emu_decode_reduced(const uint16_t *stream, unsigned stream_shorts, int aw, i
         a.cw16 = stream; a.cw16_offsets = offsets.data(); a.cw16_total = &total; a.cw16_max = stream_shorts;
     }
     if (bad) res |= 8;
-    const bool cmp = k > 0.0f && bulk_max_span_bytes(aw, ah, wl, geo[0], geo[1], geo[2], geo[4], geo[3]) <= kBulkCompactBytes;
-    if (k > 0.0f) {
-        std::vector<uint32_t> ps((size_t)waves * kEncScratchDwordsPerWave, 0xDEADBEEFu);
-        a.plane_scratch = ps.data();
-        const dim3 grid(waves);
-        if (staging) {
-            if (cmp) emu::launch(grid, dim3(64), [&] { bpc_decode_kernel<true, kDecSmallPlanes, false, false, true>(a); });
-            else emu::launch(grid, dim3(64), [&] { bpc_decode_kernel<true, kDecSmallPlanes>(a); });
-        } else if (c16p) {
-            if (cmp) emu::launch(grid, dim3(64), [&] { bpc_decode_kernel<true, kDecSmallPlanes, true, true, true>(a); });
-            else emu::launch(grid, dim3(64), [&] { bpc_decode_kernel<true, kDecSmallPlanes, true, true>(a); });
-        } else {
-            if (cmp) emu::launch(grid, dim3(64), [&] { bpc_decode_kernel<true, kDecSmallPlanes, true, false, true>(a); });
-            else emu::launch(grid, dim3(64), [&] { bpc_decode_kernel<true, kDecSmallPlanes, true>(a); });
-        }
-    } else {
-        const dim3 wgs((waves + kBpcDecWgWaves - 1) / kBpcDecWgWaves);
-        std::vector<uint32_t> ps((size_t)wgs.x * kBpcDecWgWaves * kEncScratchDwordsPerWave, 0xDEADBEEFu);
-        a.plane_scratch = ps.data();
-        if (staging) emu::launch(wgs, dim3(64 * kBpcDecWgWaves), [&] { bpc_decode_kernel<false, kDecSmallPlanes>(a); });
-        else if (c16p) emu::launch(wgs, dim3(64 * kBpcDecWgWaves), [&] { bpc_decode_kernel<false, kDecSmallPlanes, true, true>(a); });
-        else emu::launch(wgs, dim3(64 * kBpcDecWgWaves), [&] { bpc_decode_kernel<false, kDecSmallPlanes, true>(a); });
-    }
+    const BpcLaunch dec = select_decoder(false, k > 0.0f, k > 0.0f && bulk_compact(aw, ah, wl, a.g), !staging, c16p, waves);
+    std::vector<uint32_t> ps(dec.scratch_dwords, 0xDEADBEEFu);
+    a.plane_scratch = ps.data();
+    emu::launch(dim3(dec.wgs), dim3(dec.threads), [&] { dec.kernel(a); });
 
     // ---- synthesis (run_inverse), then the clamp where level r did not write the pixels itself
     Inv2Launch f2;
     const bool fused = plan_dwt_inv2(plan, f2, lossy != 0);
     const size_t n = fused ? plan.size() - 2 : plan.size();
-    for (size_t l = 0; l < n; l++) {
-        switch (plan[l].band) {
-        case 32: red_inv<32>(plan[l], lossy); break;
-        case 16: red_inv<16>(plan[l], lossy); break;
-        case 8: red_inv<8>(plan[l], lossy); break;
-        default: red_inv<4>(plan[l], lossy); break;
-        }
+    for (size_t l = 0; l < n; l++) {        // (the frame paths' levels: the lean 9/7 kernel where it applies)
+        const InvKernel kl = select_inv(lossy != 0, true, plan[l]);
+        emu::launch(dim3(plan[l].gx, plan[l].gy), dim3(256), [&] { kl(plan[l].a); });
     }
     if (fused) {
-        DwtInv2Args a2 = f2.a;
-        const dim3 grid(f2.gx, f2.gy);
-        if (!lossy) emu::launch(grid, dim3(256), [&] { dwt_inv2_kernel<false, false>(a2); });
-        else if (a2.l0.one_div) emu::launch(grid, dim3(256), [&] { dwt_inv2_kernel<true, true>(a2); });
-        else emu::launch(grid, dim3(256), [&] { dwt_inv2_kernel<true, false>(a2); });
+        const Inv2Kernel k2 = select_inv2(lossy != 0, f2.a.l0.one_div != 0);
+        emu::launch(dim3(f2.gx, f2.gy), dim3(256), [&] { k2(f2.a); });
         res |= 4;
     }
     if (!(res & 1)) {
         const size_t n4 = (size_t)(aw >> r) * (size_t)(ah >> r) / 4;
         const void *img = plan.back().a.dst;
-        if (lossy) emu::launch(dim3(4), dim3(256), [&] { clamp_to_u8_f32_kernel((const float *)img, pixels, n4, 128.0f); });
-        else emu::launch(dim3(4), dim3(256), [&] { clamp_to_u8_i32_kernel((const int32_t *)img, pixels, n4, 128); });
+        if (lossy) emu::launch(dim3(elementwise_blocks(n4)), dim3(256), [&] { clamp_to_u8_f32_kernel((const float *)img, pixels, n4, 128.0f); });
+        else emu::launch(dim3(elementwise_blocks(n4)), dim3(256), [&] { clamp_to_u8_i32_kernel((const int32_t *)img, pixels, n4, 128); });
     }
     return res;
 }

@@ -1,14 +1,11 @@
 // TEST INFRASTRUCTURE ONLY -- the window decode (picsong_decode_frame_window) on the CPU wave emulator: the decoder over
 // the rectangle table of window_plan and the cone's synthesis (dwt_window_kernel), through the same plan functions
-// (launch_plan.hpp, window_kernels.hpp) and kernel sources as cuda-image-and-video-codec_amd/csrc/picsong_hip.hip.
+// (launch_plan.hpp, window_kernels.hpp), the same choice of kernel, grid and scratch (kernel_select.hpp) and the same
+// kernel sources as cuda-image-and-video-codec_amd/csrc/picsong_hip.hip.
 // Built by tests/test_window_decode_emulated.py with the flags of tests/hipemu/Makefile.
 #include <hip/hip_runtime.h>
 
-#include "../../cuda-image-and-video-codec_amd/csrc/bpc_kernels.hpp"
-#include "../../cuda-image-and-video-codec_amd/csrc/dwt_kernels.hpp"
-#include "../../cuda-image-and-video-codec_amd/csrc/launch_plan.hpp"
-#include "../../cuda-image-and-video-codec_amd/csrc/pack_kernels.hpp"
-#include "../../cuda-image-and-video-codec_amd/csrc/window_kernels.hpp"
+#include "../../cuda-image-and-video-codec_amd/csrc/kernel_select.hpp"
 
 using namespace picsong;
 
@@ -45,13 +42,8 @@ int emu_decode_window(const uint16_t *stream, unsigned stream_shorts, int aw, in
     std::vector<int32_t> sizes(ncb), offsets(ncb), stage;
     int32_t total = 0;
     int bad = 0, res = 0;
-    BpcArgs a;
-    memset(&a, 0, sizeof a);
-    a.AW = aw; a.AH = ah; a.wl = wl; a.ncx = aw / 64; a.nCB = ncb;
-    a.lut = lut;
-    a.g.nBp = geo[0]; a.g.nSub = geo[1]; a.g.cRef = geo[2]; a.g.cSign = geo[3]; a.g.cSig = geo[4];
-    a.g.prec = geo[5]; a.g.nRef = geo[6]; a.g.nSig = geo[7]; a.g.nSign = geo[8];
-    a.range_flag = flag; a.sizes = sizes.data(); a.coeffs_out = coef;
+    BpcArgs a = bpc_frame_args(aw, ah, wl, lut, lut_geo(geo), flag);
+    a.sizes = sizes.data(); a.coeffs_out = coef;
     a.k = k; a.n_tables = n_tables;
     const unsigned waves = (unsigned)window_bpc_table(a, plan);
     if (staging) {
@@ -65,37 +57,17 @@ int emu_decode_window(const uint16_t *stream, unsigned stream_shorts, int aw, in
         a.cw16 = stream; a.cw16_offsets = offsets.data(); a.cw16_total = &total; a.cw16_max = stream_shorts;
     }
     if (bad) res |= 8;
-    const bool cmp = k > 0.0f && bulk_max_span_bytes(aw, ah, wl, geo[0], geo[1], geo[2], geo[4], geo[3]) <= kBulkCompactBytes;
-    if (k > 0.0f) {
-        std::vector<uint32_t> ps((size_t)waves * kEncScratchDwordsPerWave, 0xDEADBEEFu);
-        a.plane_scratch = ps.data();
-        const dim3 grid(waves);
-        if (staging) {
-            if (cmp) emu::launch(grid, dim3(64), [&] { bpc_decode_kernel<true, kDecSmallPlanes, false, false, true>(a); });
-            else emu::launch(grid, dim3(64), [&] { bpc_decode_kernel<true, kDecSmallPlanes>(a); });
-        } else {
-            if (cmp) emu::launch(grid, dim3(64), [&] { bpc_decode_kernel<true, kDecSmallPlanes, true, false, true>(a); });
-            else emu::launch(grid, dim3(64), [&] { bpc_decode_kernel<true, kDecSmallPlanes, true>(a); });
-        }
-    } else {
-        const dim3 wgs((waves + kBpcDecWgWaves - 1) / kBpcDecWgWaves);
-        std::vector<uint32_t> ps((size_t)wgs.x * kBpcDecWgWaves * kEncScratchDwordsPerWave, 0xDEADBEEFu);
-        a.plane_scratch = ps.data();
-        if (staging) emu::launch(wgs, dim3(64 * kBpcDecWgWaves), [&] { bpc_decode_kernel<false, kDecSmallPlanes>(a); });
-        else emu::launch(wgs, dim3(64 * kBpcDecWgWaves), [&] { bpc_decode_kernel<false, kDecSmallPlanes, true>(a); });
-    }
+    // (32-bit coefficients: a window's synthesis reads no 16-bit ones)
+    const BpcLaunch dec = select_decoder(false, k > 0.0f, k > 0.0f && bulk_compact(aw, ah, wl, a.g), !staging, false, waves);
+    std::vector<uint32_t> ps(dec.scratch_dwords, 0xDEADBEEFu);
+    a.plane_scratch = ps.data();
+    emu::launch(dim3(dec.wgs), dim3(dec.threads), [&] { dec.kernel(a); });
 
     // ---- the cone's synthesis (run_window)
     std::vector<WinLaunch> syn = plan_window_synthesis(plan, coef, work.data(), P, aw, ah, qs, pixels, pitch, 128);
-    for (WinLaunch &f : syn) {
-        WinSynArgs sa = f.a;
-        if (lossy) {
-            if (f.u8) emu::launch(f.grid, dim3(256), [&] { dwt_window_kernel<float, true>(sa); });
-            else emu::launch(f.grid, dim3(256), [&] { dwt_window_kernel<float, false>(sa); });
-        } else {
-            if (f.u8) emu::launch(f.grid, dim3(256), [&] { dwt_window_kernel<int, true>(sa); });
-            else emu::launch(f.grid, dim3(256), [&] { dwt_window_kernel<int, false>(sa); });
-        }
+    for (const WinLaunch &f : syn) {
+        const WinKernel kw = select_window(lossy != 0, f.u8);
+        emu::launch(f.grid, dim3(256), [&] { kw(f.a); });
     }
     return res;
 }
