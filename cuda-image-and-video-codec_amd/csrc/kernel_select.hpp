@@ -11,6 +11,7 @@
 #include "dwt_kernels.hpp"
 #include "launch_plan.hpp"
 #include "pack_kernels.hpp"
+#include "train_kernels.hpp"
 #include "window_kernels.hpp"
 
 namespace picsong {
@@ -22,6 +23,7 @@ using Inv2Kernel = void (*)(DwtInv2Args);
 using InvRgbKernel = void (*)(DwtInvArgs, uint8_t *, uint8_t *, uint8_t *);
 using WinKernel = void (*)(WinSynArgs);
 using BpcKernel = void (*)(BpcArgs);
+using StatsKernel = void (*)(BpcArgs, unsigned long long *, int);
 
 // ---- forward transform: one level (256 threads, grid f.gx x f.gy x frames)
 template <int BAND, bool VEC>
@@ -186,6 +188,37 @@ inline BpcArgs bpc_frame_args(int aw, int ah, int wl, const int32_t *lut, const 
     a.AW = aw; a.AH = ah; a.wl = wl; a.ncx = aw / 64; a.nCB = (aw / 64) * (ah / 64);
     a.lut = lut; a.g = g; a.range_flag = range_flag;
     return a;
+}
+
+// ---- the training statistics (bpc_stats_kernel): a persistent grid over `pairs` codeblock pairs (all frames of the
+// call), a wave a pair at a time; the dwords of BpcArgs::plane_scratch its waves need
+struct StatsLaunch { StatsKernel kernel; unsigned threads, wgs; size_t scratch_dwords; };
+inline unsigned stats_wgs(size_t pairs)
+{
+    const size_t w = (pairs + kTrainWgWaves - 1) / kTrainWgWaves;
+    return (unsigned)(w < 1 ? 1 : (w > kTrainMaxWgs ? kTrainMaxWgs : w));
+}
+inline StatsLaunch select_stats(size_t pairs)
+{
+    const unsigned wgs = stats_wgs(pairs);
+    return { bpc_stats_kernel, 64u * (unsigned)kTrainWgWaves, wgs, (size_t)wgs * kTrainWgWaves * kEncScratchDwordsPerWave };
+}
+// the encoder-side arguments of a statistics launch over `frames` coefficient arrays coef_z bytes apart
+inline BpcArgs stats_args(int aw, int ah, int wl, const LutGeo &g, int *range_flag, const void *coeffs, bool is_float, bool c16,
+                          int frames, unsigned long long coef_z, uint32_t *plane_scratch)
+{
+    BpcArgs a = bpc_frame_args(aw, ah, wl, nullptr, g, range_flag);
+    a.coeffs_in = coeffs; a.is_float = is_float ? 1 : 0; a.c16 = c16 ? 1 : 0;
+    a.frames = frames; a.waves_per_frame = (a.nCB + 1) / 2; a.coef_z = coef_z;
+    a.plane_scratch = plane_scratch;
+    return a;
+}
+// section sizes a geometry implies for `wl` (IO/IOManager.ipp:431-433) where the caller left them 0
+inline void lut_geo_sections(LutGeo &g, int wl)
+{
+    if (g.nRef <= 0) g.nRef = g.nSub * g.nBp * g.cRef * wl + g.nBp * g.cRef;
+    if (g.nSig <= 0) g.nSig = g.nSub * g.nBp * g.cSig * wl + g.nBp * g.cSig;
+    if (g.nSign <= 0) g.nSign = g.nSub * g.nBp * g.cSign * wl + g.nBp * g.cSign;
 }
 
 // -k > 0: does the table geometry let every codeblock of the frame use the COMPACT LDS copies (bulk_max_span_bytes: the

@@ -6,6 +6,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <sys/stat.h>
+
+#include <cerrno>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -82,6 +85,14 @@ struct picsong_ctx {
     // stage profiling (HIP events on the launch stream)
     std::vector<hipEvent_t> *prof_ev;   // 4 per frame
     int prof_cap, prof_n;
+    // training (picsong_train_begin): the geometry counted for, uint64[train_total][2] per component slot, and the plane
+    // scratch of the statistics kernel's persistent grid (grown to the largest launch seen)
+    bool train_on;
+    picsong_lut_info train_li;
+    int train_total;
+    unsigned long long *d_train[3];
+    uint32_t *train_scratch;
+    size_t train_scratch_dwords;
 };
 
 // PICSONG_DWT_INV97=0 keeps the 9/7 synthesis levels off the lean kernel (select_inv): read once per process
@@ -396,6 +407,8 @@ void picsong_ctx_destroy(picsong_ctx *c)
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     free_workspace(c->one);
     free_batch(c);
+    for (int k = 0; k < 3; k++) if (c->d_train[k]) (void)hipFree(c->d_train[k]);
+    if (c->train_scratch) (void)hipFree(c->train_scratch);
     if (c->prof_ev) {
         for (hipEvent_t e : *c->prof_ev) (void)hipEventDestroy(e);
         delete c->prof_ev;
@@ -1514,20 +1527,14 @@ static int bpc_args_rgb(picsong_ctx *c, BpcArgs &a)
     return PICSONG_OK;
 }
 
-int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
-                             uint16_t *d_streams, size_t stream_stride, void *stream)
+// An RGB frame's colour transform (level shift fused) and the forward transform of its three components, component k's
+// coefficients into c->batch.coef + k * (P + extra) * 4 bytes (ensure_batch(3) and ensure_coef_i(3) done); *c16: the
+// coefficient form this call's plan delivers.  The head of picsong_encode_rgb_frame and picsong_train_rgb_frame.
+static int rgb_forward_transform(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, hipStream_t s,
+                                 bool *c16)
 {
-    if (!c || !d_r || !d_g || !d_b || !d_streams) return fail(PICSONG_ERR_ARG, "encode_rgb_frame: null argument");
-    if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "encode_rgb_frame: the context is not an RGB one");
-    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "encode_rgb_frame: -cp 3 codes its planes one by one (picsong_encode_plane)");
-    if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah)) return fail(PICSONG_ERR_ARG, "encode_rgb_frame: stream stride smaller than a worst-case codestream");
-    HIP_TRY(hipSetDevice(c->device));
-    BpcArgs a;
-    int rc = bpc_args_rgb(c, a);
-    if (rc) return rc;
-    if ((rc = ensure_batch(c, 3))) return rc;
-    if ((rc = ensure_coef_i(c, 3))) return rc;
-    hipStream_t s = (hipStream_t)stream;
+    *c16 = false;
+    int rc;
     const size_t coef_z = (c->P + c->extra) * 4;
     char *planes = (char *)c->batch.coef_i;
     // ---- lossless: the colour transform in the fused head's load stage (dwt_fwd2_kernel<..., RGB>): the head reads the
@@ -1547,18 +1554,39 @@ int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *
             select_fwd2(c->p.lossy != 0, true, true)<<<dim3(f2.gx, f2.gy, 3u), 256, 0, s>>>(f2.a);
             HIP_TRY(hipGetLastError());
             if ((rc = launch_fwd_levels(c, plan, 2, s, 3u))) return rc;
-            a.c16 = 1;
+            *c16 = true;
             fused_rgb = true;
         }
     }
     if (!fused_rgb) {
     // ---- colour transform (level shift fused) into three planes, then the transform of all three per launch
-    if ((rc = picsong_rgb_forward(c, d_r, d_g, d_b, planes, planes + c->P * 4, planes + 2 * c->P * 4, stream))) return rc;
+    if ((rc = picsong_rgb_forward(c, d_r, d_g, d_b, planes, planes + c->P * 4, planes + 2 * c->P * 4, (void *)s))) return rc;
     std::vector<FwdLaunch> plan = plan_dwt_forward(planes, false, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16);
-    a.c16 = plan_is_c16(plan) ? 1 : 0;
+    *c16 = plan_is_c16(plan);
     plan_frame_strides(plan, (unsigned long long)c->P * 4ull, coef_z);
     if ((rc = launch_fwd_levels(c, plan, 0, s, 3u))) return rc;
     }
+    return PICSONG_OK;
+}
+
+int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
+                             uint16_t *d_streams, size_t stream_stride, void *stream)
+{
+    if (!c || !d_r || !d_g || !d_b || !d_streams) return fail(PICSONG_ERR_ARG, "encode_rgb_frame: null argument");
+    if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "encode_rgb_frame: the context is not an RGB one");
+    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "encode_rgb_frame: -cp 3 codes its planes one by one (picsong_encode_plane)");
+    if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah)) return fail(PICSONG_ERR_ARG, "encode_rgb_frame: stream stride smaller than a worst-case codestream");
+    HIP_TRY(hipSetDevice(c->device));
+    BpcArgs a;
+    int rc = bpc_args_rgb(c, a);
+    if (rc) return rc;
+    if ((rc = ensure_batch(c, 3))) return rc;
+    if ((rc = ensure_coef_i(c, 3))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t coef_z = (c->P + c->extra) * 4;
+    bool c16 = false;
+    if ((rc = rgb_forward_transform(c, d_r, d_g, d_b, s, &c16))) return rc;
+    a.c16 = c16 ? 1 : 0;
     // ---- coder: one grid over the three components' codeblock pairs, component f with table f
     a.coeffs_in = c->batch.coef; a.is_float = c->p.lossy ? 1 : 0;
     a.staging16 = reinterpret_cast<uint16_t *>(c->batch.staging);
@@ -1663,6 +1691,248 @@ int picsong_decode_rgb_frame_window(picsong_ctx *c, const uint16_t *d_streams, s
     if (int rc = window_args_ok(c, reduce, x, y, w, h, who, &plan)) return rc;
     if (out_pitch < (size_t)w) return fail(PICSONG_ERR_ARG, "%s: out_pitch %zu < w %d", who, out_pitch, w);
     return decode_rgb_impl(c, d_streams, stream_stride, d_r, d_g, d_b, stream, reduce, who, &plan, out_pitch);
+}
+
+// ---------------------------------------------------------------------------------------------
+// training: the statistics of the two-pass coder's decisions (train_kernels.hpp) and the tables made from them
+// ---------------------------------------------------------------------------------------------
+static int train_ready(const picsong_ctx *c, const char *who)
+{
+    if (!c) return fail(PICSONG_ERR_ARG, "%s: null context", who);
+    if (!c->train_on) return fail(PICSONG_ERR_ARG, "%s: call picsong_train_begin first", who);
+    return PICSONG_OK;
+}
+
+static void train_free(picsong_ctx *c)
+{
+    for (int k = 0; k < 3; k++) {
+        if (c->d_train[k]) (void)hipFree(c->d_train[k]);
+        c->d_train[k] = nullptr;
+    }
+    c->train_on = false;
+    c->train_total = 0;
+}
+
+int picsong_train_begin(picsong_ctx *c, const picsong_lut_info *geo)
+{
+    if (!c || !geo) return fail(PICSONG_ERR_ARG, "train_begin: null argument");
+    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "train_begin: -cp 3 contexts code other decisions (cp_sig / cp_sign): not trained");
+    if (c->p.k > 0.0f) return fail(PICSONG_ERR_ARG, "train_begin: -k > 0 contexts code from the bit-plane files _1.._14: not trained");
+    if (geo->n_bitplanes < 1 || geo->n_subbands < 1 || geo->ctx_ref < 1 || geo->ctx_sig < 1 || geo->ctx_sign < 1)
+        return fail(PICSONG_ERR_ARG, "train_begin: geometry %d bit-planes, %d subbands, %d/%d/%d contexts (ref/sig/sign): each must be >= 1",
+                    geo->n_bitplanes, geo->n_subbands, geo->ctx_ref, geo->ctx_sig, geo->ctx_sign);
+    if (geo->n_ref < 0 || geo->n_sig < 0 || geo->n_sign < 0) return fail(PICSONG_ERR_ARG, "train_begin: negative section size");
+    picsong_lut_info li = *geo;
+    // section sizes of 0 follow from the geometry and the context's wl (64-bit: a geometry of large numbers must not
+    // wrap on its way to the refusal)
+    const long long planes = ((long long)li.n_subbands * c->p.wl + 1) * li.n_bitplanes;
+    const long long n_ref = li.n_ref > 0 ? li.n_ref : planes * li.ctx_ref, n_sig = li.n_sig > 0 ? li.n_sig : planes * li.ctx_sig,
+                    n_sign = li.n_sign > 0 ? li.n_sign : planes * li.ctx_sign;
+    const long long total = n_ref + n_sig + n_sign;
+    if (planes > kTrainMaxEntries || total > kTrainMaxEntries)
+        return fail(PICSONG_ERR_ARG, "train_begin: a table of %lld entries exceeds the %d a workgroup's copy holds", total, kTrainMaxEntries);
+    LutGeo g = lut_geo(li);
+    g.nRef = (int)n_ref; g.nSig = (int)n_sig; g.nSign = (int)n_sign;
+    li.n_ref = g.nRef; li.n_sig = g.nSig; li.n_sign = g.nSign;
+    li.n_files = 3; li.n_bp_files = 1; li.n_tables = 1; li.cp = 2;
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->train_on) { HIP_TRY(hipDeviceSynchronize()); train_free(c); }
+    const size_t bytes = (size_t)total * 2 * sizeof(unsigned long long);
+    for (int k = 0; k < 3; k++) {
+        hipError_t e = hipMalloc(&c->d_train[k], bytes);
+        if (e == hipSuccess) e = hipMemset(c->d_train[k], 0, bytes);
+        if (e != hipSuccess) { train_free(c); return fail(PICSONG_ERR_HIP, "train_begin: %s", hipGetErrorString(e)); }
+    }
+    c->train_li = li;
+    c->train_total = (int)total;
+    c->train_on = true;
+    return PICSONG_OK;
+}
+
+int picsong_train_info(const picsong_ctx *c, picsong_lut_info *info)
+{
+    if (int rc = train_ready(c, "train_info")) return rc;
+    if (!info) return fail(PICSONG_ERR_ARG, "train_info: null argument");
+    *info = c->train_li;
+    return PICSONG_OK;
+}
+
+int picsong_train_reset(picsong_ctx *c)
+{
+    if (int rc = train_ready(c, "train_reset")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());                        // (no stream argument: calls in flight on any stream count first)
+    for (int k = 0; k < 3; k++) HIP_TRY(hipMemset(c->d_train[k], 0, (size_t)c->train_total * 2 * sizeof(unsigned long long)));
+    return PICSONG_OK;
+}
+
+int picsong_train_end(picsong_ctx *c)
+{
+    if (int rc = train_ready(c, "train_end")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    train_free(c);
+    if (c->train_scratch) (void)hipFree(c->train_scratch);
+    c->train_scratch = nullptr; c->train_scratch_dwords = 0;
+    return PICSONG_OK;
+}
+
+// The statistics launch of every path: `frames` coefficient arrays coef_z bytes apart into slot comp's counters
+static int launch_stats(picsong_ctx *c, int comp, const void *d_coeffs, bool c16, int frames, unsigned long long coef_z, hipStream_t s)
+{
+    const size_t pairs = (size_t)frames * (size_t)((c->ncb + 1) / 2);
+    const StatsLaunch l = select_stats(pairs);
+    if (!train_pairs_ok(pairs, l.wgs)) return fail(PICSONG_ERR_ARG, "train: %zu codeblock pairs in one launch", pairs);
+    if (c->train_scratch_dwords < l.scratch_dwords) {
+        HIP_TRY(hipDeviceSynchronize());                    // a smaller launch may still be running on the old scratch
+        if (c->train_scratch) (void)hipFree(c->train_scratch);
+        c->train_scratch = nullptr; c->train_scratch_dwords = 0;
+        HIP_TRY(hipMalloc(&c->train_scratch, l.scratch_dwords * sizeof(uint32_t)));
+        c->train_scratch_dwords = l.scratch_dwords;
+    }
+    const BpcArgs a = stats_args(c->aw, c->ah, c->p.wl, lut_geo(c->train_li), c->d_flag, d_coeffs, c->p.lossy != 0 && !c16, c16,
+                                 frames, coef_z, c->train_scratch);
+    l.kernel<<<l.wgs, l.threads, 0, s>>>(a, c->d_train[comp], (int)pairs);
+    HIP_TRY(hipGetLastError());
+    return PICSONG_OK;
+}
+
+int picsong_train_coeffs(picsong_ctx *c, int comp, const void *d_coeffs, void *stream)
+{
+    if (int rc = train_ready(c, "train_coeffs")) return rc;
+    if (!d_coeffs) return fail(PICSONG_ERR_ARG, "train_coeffs: null argument");
+    if (comp < 0 || comp > 2) return fail(PICSONG_ERR_ARG, "train_coeffs: component %d outside 0..2", comp);
+    HIP_TRY(hipSetDevice(c->device));
+    return launch_stats(c, comp, d_coeffs, false, 1, 0, (hipStream_t)stream);
+}
+
+int picsong_train_frames(picsong_ctx *c, int n, const uint8_t *d_frames, size_t frame_stride, void *stream)
+{
+    if (int rc = train_ready(c, "train_frames")) return rc;
+    if (!d_frames) return fail(PICSONG_ERR_ARG, "train_frames: null argument");
+    if (n < 1 || n > 64) return fail(PICSONG_ERR_ARG, "train_frames: %d frames outside 1..64", n);
+    if (n > 1 && frame_stride < c->P) return fail(PICSONG_ERR_ARG, "train_frames: stride smaller than a padded frame");
+    if (c->p.is_rgb) return fail(PICSONG_ERR_ARG, "train_frames: grey contexts only (an RGB frame's components: picsong_train_rgb_frame)");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_batch(c, n);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t coef_z = (c->P + c->extra) * 4;
+    bool c16 = false;
+    if (((((uintptr_t)d_frames) | frame_stride) & 15u) == 0) {
+        // ---- the transform of picsong_encode_frames: frame 0's plan with grid.z = n
+        std::vector<FwdLaunch> plan = plan_dwt_forward(d_frames, true, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16);
+        c16 = plan_is_c16(plan);
+        plan_frame_strides(plan, frame_stride, coef_z);
+        if ((rc = launch_fwd_plan(c, plan, s, (unsigned)n))) return rc;
+    } else {
+        // ---- frames whose alignment differs from one another: a plan each, the 32-bit arrays for all of them
+        for (int f = 0; f < n; f++) {
+            const std::vector<FwdLaunch> plan = plan_dwt_forward(d_frames + (size_t)f * frame_stride, true, (char *)c->batch.coef + (size_t)f * coef_z,
+                                                                 c->aw, c->ah, c->p.wl, c->p.qs, false);
+            if ((rc = launch_fwd_plan(c, plan, s))) return rc;
+        }
+    }
+    return launch_stats(c, 0, c->batch.coef, c16, n, coef_z, s);
+}
+
+int picsong_train_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, void *stream)
+{
+    if (int rc = train_ready(c, "train_rgb_frame")) return rc;
+    if (!d_r || !d_g || !d_b) return fail(PICSONG_ERR_ARG, "train_rgb_frame: null argument");
+    if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "train_rgb_frame: the context is not an RGB one");
+    if ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 3u) return fail(PICSONG_ERR_ARG, "train_rgb_frame: the planes need 4-byte alignment");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_batch(c, 3))) return rc;
+    if ((rc = ensure_coef_i(c, 3))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t coef_z = (c->P + c->extra) * 4;
+    bool c16 = false;
+    if ((rc = rgb_forward_transform(c, d_r, d_g, d_b, s, &c16))) return rc;
+    // (a launch a component: a workgroup's on-chip copy of the counters belongs to one slot)
+    for (int k = 0; k < 3; k++)
+        if ((rc = launch_stats(c, k, (const char *)c->batch.coef + (size_t)k * coef_z, c16, 1, 0, s))) return rc;
+    return PICSONG_OK;
+}
+
+int picsong_train_counts(picsong_ctx *c, int comp, void *stream, uint64_t *h_counts, size_t capacity_entries)
+{
+    if (int rc = train_ready(c, "train_counts")) return rc;
+    if (comp < 0 || comp > 2) return fail(PICSONG_ERR_ARG, "train_counts: component %d outside 0..2", comp);
+    if (!h_counts) return c->train_total;
+    if (capacity_entries < (size_t)c->train_total)
+        return fail(PICSONG_ERR_ARG, "train_counts: capacity %zu < %d entries", capacity_entries, c->train_total);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(hipMemcpy(h_counts, c->d_train[comp], (size_t)c->train_total * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PICSONG_OK;
+}
+
+// ---- host only: counts -> table -> folder
+static int lut_info_complete(const picsong_lut_info *info, const char *who)
+{
+    if (info->n_bitplanes < 1 || info->n_subbands < 1 || info->ctx_ref < 1 || info->ctx_sig < 1 || info->ctx_sign < 1)
+        return fail(PICSONG_ERR_ARG, "%s: geometry fields must be >= 1", who);
+    if (info->ctx_ref > 16 || info->ctx_sig > 16 || info->ctx_sign > 16) return fail(PICSONG_ERR_ARG, "%s: context counts above 16 are not supported", who);
+    if (info->precision < 1 || info->precision > 8) return fail(PICSONG_ERR_ARG, "%s: precision %d outside 1..8", who, info->precision);
+    if (info->n_ref < 1 || info->n_sig < 1 || info->n_sign < 1)
+        return fail(PICSONG_ERR_ARG, "%s: section sizes missing (picsong_train_info / picsong_lut_load fill them in)", who);
+    return PICSONG_OK;
+}
+
+int picsong_lut_from_counts(const picsong_lut_info *info, const uint64_t *counts, const int32_t *prior, int32_t *table)
+{
+    if (!info || !counts || !table) return fail(PICSONG_ERR_ARG, "lut_from_counts: null argument");
+    if (int rc = lut_info_complete(info, "lut_from_counts")) return rc;
+    const size_t total = (size_t)info->n_ref + info->n_sig + info->n_sign;
+    const int prec = info->precision;
+    const uint64_t top = ((uint64_t)1 << prec) - 1;
+    for (size_t i = 0; i < total; i++) {
+        const uint64_t z = counts[2 * i], o = counts[2 * i + 1], t = z + o;
+        if (t == 0) { table[i] = prior ? prior[i] : (int32_t)(1 << (prec - 1)); continue; }
+        if (t < z || z > (~(uint64_t)0 >> (prec + 1))) return fail(PICSONG_ERR_ARG, "lut_from_counts: entry %zu's counts overflow 64 bits", i);
+        uint64_t p = ((z << prec) + t / 2) / t;
+        p = p < 1 ? 1 : (p > top ? top : p);
+        table[i] = (int32_t)p;
+    }
+    return PICSONG_OK;
+}
+
+int picsong_lut_save(const char *folder_c, int component, const picsong_lut_info *info, int wl, const int32_t *table)
+{
+    if (!folder_c || !info || !table || !*folder_c) return fail(PICSONG_ERR_ARG, "lut_save: null argument");
+    if (component < 0 || component > 3) return fail(PICSONG_ERR_ARG, "lut_save: component %d outside 0..3", component);
+    if (wl < 1 || wl > 10) return fail(PICSONG_ERR_ARG, "lut_save: wl %d out of range", wl);
+    if (int rc = lut_info_complete(info, "lut_save")) return rc;
+    const int nB = info->n_bitplanes, nS = info->n_subbands, groups = nS * wl + 1;
+    if (info->n_ref != groups * nB * info->ctx_ref || info->n_sig != groups * nB * info->ctx_sig || info->n_sign != groups * nB * info->ctx_sign)
+        return fail(PICSONG_ERR_ARG, "lut_save: the section sizes %d/%d/%d are not those of wl %d (%d groups of %d planes)", info->n_ref,
+                    info->n_sig, info->n_sign, wl, groups, nB);
+    std::string folder(folder_c);
+    if (folder.back() != '/') folder += '/';
+    if (mkdir(folder.c_str(), 0777) != 0 && errno != EEXIST) return fail(PICSONG_ERR_IO, "lut_save: cannot create %s: %s", folder.c_str(), strerror(errno));
+    FILE *f = fopen((folder + "header.txt").c_str(), "wb");
+    if (!f) return fail(PICSONG_ERR_IO, "lut_save: cannot write %sheader.txt: %s", folder.c_str(), strerror(errno));
+    fprintf(f, "LUT_N_BITPLANES;%d\nLUT_N_SUBBANDS;%d\nN_CONTEXT_REFINEMENT;%d\nN_CONTEXT_SIGN;%d\nN_CONTEXT_SIGNIFICANCE;%d\n"
+               "MULT_PRECISION;%d\nLUT_N_FILES;3\nAMOUNT_OF_BITPLANE_FILES;1\n", nB, nS, info->ctx_ref, info->ctx_sign, info->ctx_sig, info->precision);
+    if (fclose(f) != 0) return fail(PICSONG_ERR_IO, "lut_save: writing %sheader.txt failed", folder.c_str());
+    static const char *suffix[4] = { ".txt_0", "R.txt_0", "G.txt_0", "B.txt_0" };
+    const struct { const char *stem; int C, base; } sec[3] = { { "ref", info->ctx_ref, 0 }, { "sig", info->ctx_sig, info->n_ref },
+                                                               { "sign", info->ctx_sign, info->n_ref + info->n_sig } };
+    for (int k = 0; k < 3; k++) {
+        const std::string path = folder + sec[k].stem + suffix[component];
+        if (!(f = fopen(path.c_str(), "wb"))) return fail(PICSONG_ERR_IO, "lut_save: cannot write %s: %s", path.c_str(), strerror(errno));
+        const int32_t *T = table + sec[k].base;
+        for (int grp = 0; grp < groups; grp++)
+            for (int bp = 0; bp < nB; bp++) {
+                fprintf(f, "%d %d %d : ", grp / nS, grp % nS, bp);
+                for (int x = 0; x < sec[k].C; x++) fprintf(f, "%d ", T[((size_t)grp * nB + bp) * sec[k].C + x]);
+                fputc('\n', f);
+            }
+        if (fclose(f) != 0) return fail(PICSONG_ERR_IO, "lut_save: writing %s failed", path.c_str());
+    }
+    return PICSONG_OK;
 }
 
 int picsong_pad_frame_host(const uint8_t *in, int w, int h, uint8_t *out, int aw, int ah)

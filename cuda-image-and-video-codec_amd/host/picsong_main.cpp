@@ -49,6 +49,7 @@ struct Options {
     int reduce = 0;                             // -reduce r: decode the image at 1/2^r of its size
     int win = 0, wx = 0, wy = 0, ww = 0, wh = 0; // -window x,y,w,h: decode that rectangle of the image at 1/2^r
     int win_cb = 0;                             // (the codeblocks a window decodes, for --metrics)
+    std::string train;                          // -train <outFolder>: count the input's coding decisions, write a LUT folder
 };
 
 [[noreturn]] void die(const std::string &msg)
@@ -104,7 +105,10 @@ void help()
         " --lut-fill V        value of LUT entries the loader never writes (default 0)\n"
         " -reduce r           decoding: the image at 1/2^r of its size, r in 0..wl-1 (resolution reduction)\n"
         " -window x,y,w,h     decoding: only the w x h rectangle at (x, y) of the image (at 1/2^r with -reduce r), from the\n"
-        "                     codeblocks it depends on (spatial random access)\n";
+        "                     codeblocks it depends on (spatial random access)\n"
+        " -train <outFolder>  coding (-cd 0, -cp 2, -k 0): code nothing; count the input's coding decisions and write the\n"
+        "                     probability tables fitted to them as a LUT folder for this -wl (no -o needed).  -LUTFolder,\n"
+        "                     if given, is the prior: its geometry, and its values for entries the input never reaches\n";
 }
 
 template <typename T> void echo(const char *flag, const T &v)
@@ -134,6 +138,11 @@ Options parse(const Args &a)
             die("Incorrect parameters. -window takes x,y,w,h: x, y >= 0, w, h >= 1.");
         o.win = 1;
         echo("-window", v);
+    }
+    if (a.has("-train")) {
+        if (o.cd != 0) die("Incorrect parameters. -train applies to coding (-cd 0) only.");
+        gets("-train", o.train);
+        if (o.train.empty()) die("Incorrect parameters. -train takes the folder to write.");
     }
     if (o.cd == 0) {
         geti("-xSize", o.x); geti("-ySize", o.y); geti("-cbWidth", o.cb_width); geti("-cbHeight", o.cb_height);
@@ -308,6 +317,91 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
     return 0;
 }
 
+// ---- training (-train <outFolder>): the input read exactly as an encode reads it, its frames through the training
+// calls in groups of B per launch (grey) or a frame at a time (RGB: one launch per stage, component c into slot c),
+// then the counts of every component made into a table (picsong_lut_from_counts) and written as the folder's files:
+// R for a grey input -- what a grey encode loads -- and R, G, B for an RGB one.
+int run_train(const Options &o, size_t file_base, long nframes)
+{
+    HIPCK(hipSetDevice(o.device));
+    const int aw = picsong_pad_dim(o.x), ah = picsong_pad_dim(o.y), comps = o.is_rgb ? 3 : 1;
+    const size_t P = (size_t)aw * ah;
+    picsong_params params = make_params(o);
+    picsong_ctx *ctx = nullptr;
+    CK(picsong_ctx_create(&params, o.device, &ctx));
+    // the geometry counted for: the prior folder's, or the shipped folders' 15 / 3 / 1 / 4 / 9 / 7
+    picsong_lut_info geo;
+    memset(&geo, 0, sizeof geo);
+    geo.n_bitplanes = 15; geo.n_subbands = 3; geo.ctx_ref = 1; geo.ctx_sign = 4; geo.ctx_sig = 9; geo.precision = 7;
+    std::vector<std::vector<int32_t>> prior((size_t)comps);
+    if (!o.lut_folder.empty()) {
+        for (int c = 0; c < comps; c++) {
+            picsong_lut_info pi;
+            CK(picsong_lut_load(o.lut_folder.c_str(), c + 1, o.wl, o.lut_fill, &pi, nullptr, 0));
+            prior[(size_t)c].resize((size_t)pi.n_ref + pi.n_sig + pi.n_sign);
+            CK(picsong_lut_load(o.lut_folder.c_str(), c + 1, o.wl, o.lut_fill, &pi, prior[(size_t)c].data(), prior[(size_t)c].size()));
+            if (c == 0) geo = pi;
+        }
+    }
+    CK(picsong_train_begin(ctx, &geo));
+    picsong_lut_info info;
+    CK(picsong_train_info(ctx, &info));
+    int B = o.frames_per_launch > 0 ? o.frames_per_launch : (P <= (size_t)3840 * 2176 ? 4 : 1);
+    if (o.is_rgb) B = 3;                                    // (the three planes of a frame)
+    if (B > 16) B = 16;
+    hipStream_t s;
+    HIPCK(hipStreamCreate(&s));
+    uint8_t *h_in, *d_in;
+    HIPCK(hipHostMalloc(&h_in, P * B));
+    HIPCK(hipMalloc(&d_in, P * B));
+    std::vector<uint8_t> raw((size_t)o.x * o.y);
+    std::ifstream in(o.input, std::ios::binary);
+    if (!in) die("Cannot open input file " + o.input);
+    auto t0 = std::chrono::steady_clock::now();
+    const long planes = nframes * comps;
+    for (long f = 0; f < planes; f += B) {
+        const int n = (int)std::min<long>(B, planes - f);
+        for (int j = 0; j < n; j++) {
+            if (!read_frame(in, file_base, (size_t)(f + j), o.x, o.y, raw.data())) die("Input file is shorter than the requested frames.");
+            CK(picsong_pad_frame_host(raw.data(), o.x, o.y, h_in + (size_t)j * P, aw, ah));
+        }
+        HIPCK(hipMemcpyAsync(d_in, h_in, P * n, hipMemcpyHostToDevice, s));
+        if (o.is_rgb) CK(picsong_train_rgb_frame(ctx, d_in, d_in + P, d_in + 2 * P, s));
+        else CK(picsong_train_frames(ctx, n, d_in, P, s));
+        HIPCK(hipStreamSynchronize(s));                      // h_in and d_in are reused for the next group
+    }
+    const int entries = picsong_train_counts(ctx, 0, s, nullptr, 0);
+    if (entries <= 0) die(std::string("picsong_train_counts failed: ") + picsong_last_error());
+    std::vector<uint64_t> counts((size_t)entries * 2);
+    std::vector<int32_t> table((size_t)entries);
+    unsigned long long symbols = 0;
+    long seen = 0;
+    for (int c = 0; c < comps; c++) {
+        CK(picsong_train_counts(ctx, c, s, counts.data(), (size_t)entries));
+        for (int e = 0; e < entries; e++) {
+            const uint64_t t = counts[2 * (size_t)e] + counts[2 * (size_t)e + 1];
+            symbols += t;
+            seen += t != 0;
+        }
+        const bool has_prior = prior[(size_t)c].size() >= (size_t)entries;
+        CK(picsong_lut_from_counts(&info, counts.data(), has_prior ? prior[(size_t)c].data() : nullptr, table.data()));
+        CK(picsong_lut_save(o.train.c_str(), c + 1, &info, o.wl, table.data()));
+    }
+    int flag = 0;
+    CK(picsong_range_flag(ctx, s, &flag));
+    double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::cout << "Trained " << o.train << " for -wl " << o.wl << ": " << symbols << " symbols counted, " << seen << " of "
+              << (long)entries * comps << " entries seen" << std::endl;
+    if (flag) std::cout << "Warning: codeblocks with more than 16 bit-planes were left out." << std::endl;
+    std::cout << "The time spent with the app without considering allocation periods is: " << sec << std::endl;
+    write_metrics(o, "train", nframes, sec, 0, 0, 0, 0);
+    CK(picsong_train_end(ctx));
+    picsong_ctx_destroy(ctx);
+    (void)hipStreamDestroy(s);
+    (void)hipHostFree(h_in); (void)hipFree(d_in);
+    return 0;
+}
+
 constexpr long kProfFrames = 256;     // frames per pipeline slot whose stages are timed with HIP events
 
 // ---- coding engine: CodingEngine::runImage / runVideo call sequence ---------------------------
@@ -320,7 +414,7 @@ int run_encode(Options o)
         if (o.x != pgm.w || o.y != pgm.h) die("Incorrect parameters. -xSize/-ySize differ from the PGM header.");
     }
     // Launcher.cu:132
-    if (o.qs < 0 || o.qs > 1 || o.wl < 1 || o.x <= 0 || o.y <= 0 || o.wl > 10 || o.input.empty() || o.output.empty() ||
+    if (o.qs < 0 || o.qs > 1 || o.wl < 1 || o.x <= 0 || o.y <= 0 || o.wl > 10 || o.input.empty() || (o.output.empty() && o.train.empty()) ||
         o.cb_width % 64 != 0 || o.cb_height > 20 || o.cb_height < 18 || o.cp < 2 || o.cp > 3 || o.k < 0 || o.k > 65.535f)
         die("Incorrect parameters. Please choose valid values.");
     if (!((o.is_rgb && o.components == 3) || (!o.is_rgb && o.components == 1)))
@@ -329,6 +423,11 @@ int run_encode(Options o)
     if (o.signed_or_unsigned != 0 || o.bps != 8) die("Only unsigned 8-bit samples are built in this MI355X hot-path build.");
     const long nframes = o.video ? o.frames : 1;
     if (nframes <= 0) die("Incorrect parameters. Please choose valid values. (-frames)");
+    if (!o.train.empty()) {
+        if (o.k > 0) die("Incorrect parameters. -train counts the two-pass coder's decisions (-k must be 0).");
+        if (o.cp == 3) die("Incorrect parameters. -train does not apply to -cp 3.");
+        return run_train(o, pgm.is_pgm ? pgm.offset : 0, nframes);
+    }
     if (o.is_rgb) return run_encode_rgb(o, pgm.is_pgm ? pgm.offset : 0, nframes);
     // ---- devices: -gpus N takes devices D .. D+N-1, --devices names them (a device may repeat: several
     // worker sets on one GPU, which is also how the sharded path is exercised on a one-GPU box)

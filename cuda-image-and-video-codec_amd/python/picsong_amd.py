@@ -48,6 +48,9 @@ EXPORTS = [
     "picsong_decode_rgb_frame_reduced",
     "picsong_window_codeblocks", "picsong_decode_frame_window", "picsong_decode_frames_window",
     "picsong_decode_rgb_frame_window",
+    "picsong_train_begin", "picsong_train_info", "picsong_train_reset", "picsong_train_end", "picsong_train_coeffs",
+    "picsong_train_frames", "picsong_train_rgb_frame", "picsong_train_counts", "picsong_lut_from_counts",
+    "picsong_lut_save",
 ]
 
 _lib = None
@@ -135,6 +138,17 @@ def load():
         L.picsong_dwt_forward_band.argtypes = [vp, vp, i, i, vp, vp]
         L.picsong_dwt_forward_tail.argtypes = [vp, vp, vp]
         L.picsong_encode_stripe_coded.argtypes = [vp, vp, i, i, vp, vp]
+    if hasattr(L, "picsong_train_begin"):
+        L.picsong_train_begin.argtypes = [vp, C.POINTER(LutInfo)]
+        L.picsong_train_info.argtypes = [vp, C.POINTER(LutInfo)]
+        L.picsong_train_reset.argtypes = [vp]
+        L.picsong_train_end.argtypes = [vp]
+        L.picsong_train_coeffs.argtypes = [vp, i, vp, vp]
+        L.picsong_train_frames.argtypes = [vp, i, vp, C.c_size_t, vp]
+        L.picsong_train_rgb_frame.argtypes = [vp, vp, vp, vp, vp]
+        L.picsong_train_counts.argtypes = [vp, i, vp, vp, C.c_size_t]
+        L.picsong_lut_from_counts.argtypes = [C.POINTER(LutInfo), vp, vp, vp]
+        L.picsong_lut_save.argtypes = [C.c_char_p, i, C.POINTER(LutInfo), i, vp]
     _lib = L
     return L
 
@@ -173,6 +187,32 @@ def lut_load(folder, wl, component=1, fill=0, n_tables=1, cp=2):
     _check(L.picsong_lut_load_k(folder.encode(), component, wl, fill, n_tables, C.byref(info),
                                 table.ctypes.data_as(C.c_void_p), table.size))
     return info, table
+
+
+TRAIN_GEOMETRY = dict(n_bitplanes=15, n_subbands=3, ctx_ref=1, ctx_sign=4, ctx_sig=9, precision=7)   # the shipped folders'
+
+
+def lut_from_counts(info, counts, prior=None):
+    """The table of uint64 counts[entries][2] (picsong_lut_from_counts); `info` complete (Codec.train_info, lut_load)."""
+    counts = np.ascontiguousarray(counts, np.uint64)
+    n = info.n_ref + info.n_sig + info.n_sign
+    assert counts.shape == (n, 2)
+    table = np.empty(n, np.int32)
+    pp = None
+    if prior is not None:
+        prior = np.ascontiguousarray(prior, np.int32)
+        assert prior.size >= n
+        pp = prior.ctypes.data_as(C.c_void_p)
+    _check(load().picsong_lut_from_counts(C.byref(info), counts.ctypes.data_as(C.c_void_p), pp,
+                                          table.ctypes.data_as(C.c_void_p)))
+    return table
+
+
+def lut_save(folder, component, info, wl, table):
+    """Write `table` as a LUT folder's files of `component` (0 un-suffixed, 1/2/3 = R/G/B) for `wl` levels."""
+    table = np.ascontiguousarray(table, np.int32)
+    assert table.size >= info.n_ref + info.n_sig + info.n_sign
+    _check(load().picsong_lut_save(os.fsencode(folder), component, C.byref(info), wl, table.ctypes.data_as(C.c_void_p)))
 
 
 def make_params(width, height, wl=5, lossy=False, qs=1.0, frames=0, rgb=False, k=0.0, cp=2):
@@ -249,6 +289,46 @@ class Codec:
         table = np.ascontiguousarray(table, np.int32)
         _check(self.L.picsong_ctx_set_lut_component(self.h, component, C.byref(info),
                                                     table.ctypes.data_as(C.c_void_p)))
+
+    # ---- training: the statistics a probability table is made from (k = 0, -cp 2 contexts; no table needed) ----
+    def train_begin(self, **geometry):
+        """Allocate and zero the counters; geometry fields default to the shipped folders' (TRAIN_GEOMETRY)."""
+        info = LutInfo(**dict(TRAIN_GEOMETRY, **geometry))
+        _check(self.L.picsong_train_begin(self.h, C.byref(info)))
+        return self.train_info()
+
+    def train_info(self):
+        info = LutInfo()
+        _check(self.L.picsong_train_info(self.h, C.byref(info)))
+        return info
+
+    def train_reset(self):
+        _check(self.L.picsong_train_reset(self.h))
+
+    def train_end(self):
+        _check(self.L.picsong_train_end(self.h))
+
+    def train_coeffs(self, coef, component=0):
+        """coef: the Mallat array as bpc_encode takes it (int32 / float32 device tensor of AW*AH elements)."""
+        _check(self.L.picsong_train_coeffs(self.h, component, self._p(coef), self._stream()))
+
+    def train_frames(self, frames_u8_padded):
+        """frames_u8_padded: uint8 [n, AH*AW] (or [n, AH, AW]) device tensor, rows contiguous; into slot 0."""
+        n = frames_u8_padded.shape[0]
+        assert frames_u8_padded.stride(-1) == 1
+        _check(self.L.picsong_train_frames(self.h, n, self._p(frames_u8_padded), frames_u8_padded.stride(0), self._stream()))
+
+    def train_rgb_frame(self, r, g, b):
+        _check(self.L.picsong_train_rgb_frame(self.h, self._p(r), self._p(g), self._p(b), self._stream()))
+
+    def train_counts(self, component=0):
+        """uint64 [entries, 2] (zeros, ones) of a component slot; synchronises."""
+        n = self.L.picsong_train_counts(self.h, component, self._stream(), None, 0)
+        if n < 0:
+            _check(n)
+        out = np.zeros((n, 2), np.uint64)
+        _check(self.L.picsong_train_counts(self.h, component, self._stream(), out.ctypes.data_as(C.c_void_p), n))
+        return out
 
     # ---- RGB path ----
     def rgb_forward(self, r, g, b):

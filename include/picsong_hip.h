@@ -312,6 +312,60 @@ int picsong_decode_rgb_frame_window(picsong_ctx *ctx, const uint16_t *d_streams,
                                     int x, int y, int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b,
                                     size_t out_pitch, void *stream);
 
+/* ---- training: probability tables from a corpus (the reference ships four trained folders and no way to make one).
+ *      The coder adapts nothing at run time: every binary decision is coded with the stationary probability of a table
+ *      entry.  These calls count, for the two-pass coder at k = 0 (-cp 2, file _0 of ref / sig / sign), every decision
+ *      the coder would code in the given data: counts[entry][symbol], entry = the table index the coder reads (the raw
+ *      index clamped to the table, so bit-plane 15 of a group counts where the coder looks: in the next group when
+ *      n_bitplanes = 15).  At k = 0 the decisions depend on the coefficients alone, never on a table: a context needs
+ *      none set.  All-zero codeblocks contribute nothing; a codeblock with MSB > 15 contributes nothing and raises
+ *      picsong_range_flag.  The counts are exact integers, identical from run to run.
+ *      picsong_train_begin: allocates and zeroes uint64[n_ref + n_sig + n_sign][2] for the three component slots.
+ *        `geometry`: n_bitplanes, n_subbands and the three context counts; n_ref / n_sig / n_sign of 0 are derived for
+ *        the context's wl (IO/IOManager.ipp:431-433).  A second begin starts over.  picsong_train_info returns the
+ *        geometry with its section sizes filled in (n_files 3, n_bp_files 1, n_tables 1, cp 2): what
+ *        picsong_lut_from_counts, picsong_lut_save and picsong_ctx_set_lut take.
+ *      picsong_train_coeffs: the stage-level seam; d_coeffs as picsong_bpc_encode takes it (Mallat T[AW*AH]).
+ *      picsong_train_frames: n = 1..64 padded u8 frames, frame f at d_frames + f * frame_stride bytes, through the
+ *        forward transform of the encode calls (level shift; 9/7 with the context's qs) and ONE statistics launch over
+ *        the n x nCB codeblocks; into slot 0.  16-byte aligned frames take the vector kernels and the 16-bit coefficient
+ *        form as picsong_encode_frames does; any other pointer or stride is accepted too (per-column kernels, 32-bit
+ *        arrays, a transform launch a frame): same counts, slower.
+ *      picsong_train_rgb_frame: RCT / ICT + transform as picsong_encode_rgb_frame; component c into slot c.
+ *      picsong_train_counts: synchronises `stream` and copies slot `component` to h_counts ([entry][2]: zeros, ones;
+ *        capacity_entries >= the entry count); with h_counts == NULL it returns the entry count instead.
+ *      All but picsong_train_counts are asynchronous on `stream` and accumulate across calls; picsong_train_reset
+ *      zeroes the three slots, picsong_train_end frees them.
+ *      Refused (PICSONG_ERR_ARG, nothing launched): training calls before picsong_train_begin; -cp 3 and -k > 0
+ *      contexts (they code other decisions: the bit-plane files _1.._14 and the cp_sig / cp_sign sections are not
+ *      trained); a geometry with n_bitplanes < 1, n_subbands < 1 or a context count < 1, or with more entries than a
+ *      workgroup's on-chip copy holds (4864; wl = 7 at 15 / 3 / 1 / 4 / 9 has 4620); the n / stride / null checks of the
+ *      encode calls; picsong_train_rgb_frame on a grey context and picsong_train_frames on an RGB one. ---- */
+int picsong_train_begin(picsong_ctx *ctx, const picsong_lut_info *geometry);
+int picsong_train_info(const picsong_ctx *ctx, picsong_lut_info *info);
+int picsong_train_reset(picsong_ctx *ctx);
+int picsong_train_end(picsong_ctx *ctx);
+int picsong_train_coeffs(picsong_ctx *ctx, int component, const void *d_coeffs, void *stream);
+int picsong_train_frames(picsong_ctx *ctx, int n, const uint8_t *d_frames, size_t frame_stride, void *stream);
+int picsong_train_rgb_frame(picsong_ctx *ctx, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, void *stream);
+int picsong_train_counts(picsong_ctx *ctx, int component, void *stream, uint64_t *h_counts, size_t capacity_entries);
+/* Host only.  picsong_lut_from_counts: the table of the counts.  For every entry with t = zeros + ones > 0:
+ *   p = clamp((zeros * 2^precision + t / 2) / t, 1, 2^precision - 1) in 64-bit integer arithmetic -- the probability of
+ *   a 0 in the coder's fixed point, rounded to nearest, kept off the two values that end a codeword at once; an entry
+ *   with t = 0 keeps prior_table's value, or 2^(precision - 1) without a prior (the 64 of the shipped files and of the
+ *   loader's group fill).  info: complete (picsong_train_info / picsong_lut_load); counts: [entry][2]; table and
+ *   prior_table: n_ref + n_sig + n_sign ints.
+ * picsong_lut_save: writes header.txt (LUT_N_FILES;3, AMOUNT_OF_BITPLANE_FILES;1) and {ref,sig,sign}{,R,G,B}.txt_0
+ *   (component 0 = un-suffixed, 1/2/3 = R/G/B as picsong_lut_load) in the reference's text format, every group
+ *   (level 0..wl-1 x subband 0..n_subbands-1, then (wl, 0): LL) with all its n_bitplanes planes, so that
+ *   picsong_lut_load(folder, component, wl, fill, ..) returns exactly `table` for any fill.  Creates `folder` (one
+ *   level) if absent; PICSONG_ERR_IO if it cannot be created or written; writes only those files inside it.  The
+ *   section sizes of `info` must be the ones wl implies.
+ *   A TRAINED FOLDER BELONGS TO THE wl IT WAS WRITTEN FOR: the loader reads group (wl, 0) as LL, so at another wl the
+ *   LL statistics land on a detail subband's group (the shipped folders are laid out for wl = 5 in the same way). */
+int picsong_lut_from_counts(const picsong_lut_info *info, const uint64_t *counts, const int32_t *prior_table, int32_t *table);
+int picsong_lut_save(const char *folder, int component, const picsong_lut_info *info, int wl, const int32_t *table);
+
 /* ---- intra-frame sharding (BASELINE config 5): codeblocks are independent
  *      (correctCBBorders zeroes outside neighbours, BPC/BPCEngine.cu:465-484), so a rank can code
  *      the stripe [cb_begin, cb_begin + cb_count) of the frame's raster-ordered codeblocks.  The
