@@ -175,7 +175,8 @@ __device__ __forceinline__ uint32_t sign_ctx(int h, int v)
     return (K >> (3 * (hs * 3 + vs + 4))) & 7u;
 }
 
-// findSubband BPCEngine.cu:143-170
+// findSubband BPCEngine.cu:143-170: the smallest a in 1..wl with x >= AW >> a or y >= AH >> a gives level a - 1 and the
+// subband (x only: 0, y only: 1, both: 2); none: the LL band, level wl, subband 0.
 __device__ __forceinline__ void find_subband(int x, int y, int AW, int AH, int wl, int &level, int &sb)
 {
     level = wl; sb = 0;
@@ -183,6 +184,32 @@ __device__ __forceinline__ void find_subband(int x, int y, int AW, int AH, int w
         bool cx = x >= (AW >> a), cy = y >= (AH >> a);
         if (cx || cy) { level = a - 1; sb = cx ? (cy ? 2 : 0) : 1; break; }
     }
+}
+// PICSONG_ENC_SUBBAND_SELECT (default 1): the same values without an exit that depends on the lane's x -- the levels
+// are walked from wl DOWN to 1 and a qualifying level overwrites the result by selects, so the smallest one is written
+// last.  (Lanes of one codeblock lie in different subbands wherever a subband's width is no multiple of 64; the compiler
+// unrolls the search's divergent loop by 8 and keeps its scalar state in VGPR lanes: in the k = 0 encoder 68 v_readlane
+// and 38 v_writelane once per wave, and 26 SGPRs more over the whole kernel, which then spills SGPRs into VGPR lanes in
+// its plane loop too.)  The trip count and the thresholds AW >> a, AH >> a are wave-uniform.  The k = 0 encoder and the
+// statistics kernel call this form; the decoders, -k > 0 and -cp 3 keep the search (the decoders' scratch frames grow
+// with the select form).  =0 builds the search here too.
+#ifndef PICSONG_ENC_SUBBAND_SELECT
+#define PICSONG_ENC_SUBBAND_SELECT 1
+#endif
+__device__ __forceinline__ void find_subband_sel(int x, int y, int AW, int AH, int wl, int &level, int &sb)
+{
+#if PICSONG_ENC_SUBBAND_SELECT
+    level = wl; sb = 0;
+#pragma unroll 1
+    for (int a = wl; a >= 1; a--) {
+        const bool cx = x >= (AW >> a), cy = y >= (AH >> a);
+        const int s = cx ? (cy ? 2 : 0) : 1;
+        level = (cx | cy) ? a - 1 : level;
+        sb = (cx | cy) ? s : sb;
+    }
+#else
+    find_subband(x, y, AW, AH, wl, level, sb);
+#endif
 }
 
 __device__ __forceinline__ uint32_t lut_at(const int32_t *lut, int idx, int total)
@@ -855,18 +882,35 @@ __device__ __forceinline__ uint32_t spread4_raw(uint32_t mask, uint32_t g4)
 }
 __device__ __forceinline__ uint32_t spread4(uint32_t mask, uint32_t g4) { return spread4_raw<0>(mask, g4) & 0x01010101u; }
 // significance probabilities (computeContext BPCEngine.cu:222-230 + the LUT read) of rows g4 .. g4+3
-__device__ __forceinline__ uint32_t sig_probs4(const ColHalf &cp, const PlaneLut &pl, uint32_t g4)
+// -- in two steps: contexts 0..7, and the fix-up of the rows with context 8
+__device__ __forceinline__ uint32_t sig_probs4_07(const ColHalf &cp, const PlaneLut &pl, uint32_t g4)
 {
     // the three context bits land on bits 0, 1, 2 of the rows' bytes by the multiplier's own shift; two
     // bit-field inserts keep exactly those (strays of one product never reach the bits taken from another)
     uint32_t sel = bfi32(0x01010101u, spread4_raw<0>(cp.n0, g4), spread4_raw<1>(cp.n1, g4));
     sel = bfi32(0x03030303u, sel, spread4_raw<2>(cp.n2, g4)) & 0x07070707u;      // bytes 0..7: the context
-    const uint32_t p07 = __builtin_amdgcn_perm(pl.sig1, pl.sig0, sel);
+    return __builtin_amdgcn_perm(pl.sig1, pl.sig0, sel);
+}
+__device__ __forceinline__ uint32_t sig_probs4_fix8(const ColHalf &cp, const PlaneLut &pl, uint32_t g4, uint32_t p07)
+{
     // context 8 (n3 set => n0 = n1 = n2 = 0): those bytes take p8 -- a second permute whose selector is the
     // identity (bytes 0..3 = p07's) plus 4 where n3 is set (bytes 4..7 = p8 four times)
     const uint32_t sel8 = (spread4(cp.n3, g4) << 2) | 0x03020100u;
     return __builtin_amdgcn_perm(pl.sig8x4, p07, sel8);
 }
+__device__ __forceinline__ uint32_t sig_probs4(const ColHalf &cp, const PlaneLut &pl, uint32_t g4)
+{
+    return sig_probs4_fix8(cp, pl, g4, sig_probs4_07(cp, pl, g4));
+}
+// PICSONG_ENC_CTX8_GATE (default 1): the k = 0 encoder runs the fix-up only in the 4-row groups in which some lane of
+// the wave has all eight neighbours visibly significant -- a scalar test of the group's nibble of m8, the OR over the
+// wave of both columns' n3, formed once per 32-row half-pass that has rows to visit.  On an 8K photographic frame 57 % of the live groups
+// have no such lane, and the fix-up is 12 vector instructions a group (8 of them half-rate) of a group head's 50.
+// A lane with n3 set that codes nothing at that row opens the gate for nothing; a coded lane with context 8 always
+// opens it.  =0 runs the fix-up in every group.
+#ifndef PICSONG_ENC_CTX8_GATE
+#define PICSONG_ENC_CTX8_GATE 1
+#endif
 // sign probabilities (computeSignContext :252-308: LUT index c >> 1 = c2 c1) of rows g4 .. g4+3
 __device__ __forceinline__ uint32_t sign_probs4(const ColHalf &cp, const PlaneLut &pl, uint32_t g4)
 {
@@ -1470,7 +1514,8 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
     }
 
     int level, sb;
-    find_subband(cbx * 64 + 2 * (int)t, cby * 64, a.AW, a.AH, a.wl, level, sb);
+    if constexpr (BULK) find_subband(cbx * 64 + 2 * (int)t, cby * 64, a.AW, a.AH, a.wl, level, sb);
+    else find_subband_sel(cbx * 64 + 2 * (int)t, cby * 64, a.AW, a.AH, a.wl, level, sb);
     const int grp = level * a.g.nSub + sb;
     int cbp = 0, loff = 0;                                   // planes >= cbp take the two passes
     BulkLane bl;
@@ -1554,12 +1599,21 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
                 const uint32_t al = act ? w_of(AL, hw) : 0xFFFFFFFFu, ar = act ? w_of(AR, hw) : 0xFFFFFFFFu;
                 const uint32_t nl = w_of(BL, hw) & ~al, nr = w_of(BR, hw) & ~ar;      // become significant in this plane
                 uint32_t rows = wave_or32(~(al & ar));
+                // rows at which some lane has context 8 in either column (PICSONG_ENC_CTX8_GATE); a half-pass with no
+                // rows to visit does without the reduction
+                constexpr bool GATE8 = PICSONG_ENC_CTX8_GATE && !BULK;
+                uint32_t m8 = 0xFFFFFFFFu;
+                if (GATE8 && rows) m8 = wave_or32(cpL.n3 | cpR.n3);
                 while (rows) {
-                    // a group of four rows: their probabilities are gathered together (sig_probs4)
+                    // a group of four rows: their probabilities are gathered together (sig_probs4_07 / _fix8)
                     const uint32_t g4 = (uint32_t)__builtin_ctz(rows) & ~3u;
                     uint32_t sub = (rows >> g4) & 0xFu;
                     rows &= ~(0xFu << g4);
-                    const uint32_t P4L = sig_probs4(cpL, pl, g4), P4R = sig_probs4(cpR, pl, g4);
+                    uint32_t P4L, P4R;
+                    if constexpr (GATE8) {
+                        P4L = sig_probs4_07(cpL, pl, g4); P4R = sig_probs4_07(cpR, pl, g4);
+                        if ((m8 >> g4) & 0xFu) { P4L = sig_probs4_fix8(cpL, pl, g4, P4L); P4R = sig_probs4_fix8(cpR, pl, g4, P4R); }
+                    } else { P4L = sig_probs4(cpL, pl, g4); P4R = sig_probs4(cpR, pl, g4); }
                     const uint32_t Q4L = sign_probs4(cpL, pl, g4), Q4R = sign_probs4(cpR, pl, g4);
                     // the group's rows, unrolled: the byte of P4 / Q4 a row takes is then a constant of the
                     // instruction (SDWA), and a row costs two scalar instructions of loop control, not six

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(64 * kTrainWgWaves) void bpc_stats_kernel(BpcArgs a
         }
 
         int level, sb;
-        find_subband(cbx * 64 + 2 * (int)t, cby * 64, a.AW, a.AH, a.wl, level, sb);
+        find_subband_sel(cbx * 64 + 2 * (int)t, cby * 64, a.AW, a.AH, a.wl, level, sb);
         const int G = (level * a.g.nSub + sb) * a.g.nBp;
         // does a half's group differ between its lanes?  (codeblocks that straddle subbands at the coarse levels)
         const int Gp = (int)dpp_prev((uint32_t)G);
