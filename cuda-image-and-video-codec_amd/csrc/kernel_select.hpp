@@ -11,6 +11,8 @@
 #include "dwt_kernels.hpp"
 #include "launch_plan.hpp"
 #include "pack_kernels.hpp"
+#include "rate_kernels.hpp"
+#include "rate_search.hpp"
 #include "train_kernels.hpp"
 #include "window_kernels.hpp"
 
@@ -24,6 +26,7 @@ using InvRgbKernel = void (*)(DwtInvArgs, uint8_t *, uint8_t *, uint8_t *);
 using WinKernel = void (*)(WinSynArgs);
 using BpcKernel = void (*)(BpcArgs);
 using StatsKernel = void (*)(BpcArgs, unsigned long long *, int);
+using QuantKernel = void (*)(QuantArgs);
 
 // ---- forward transform: one level (256 threads, grid f.gx x f.gy x frames)
 template <int BAND, bool VEC>
@@ -51,6 +54,9 @@ inline Fwd2Kernel select_fwd2(bool lossy, bool c16, bool rgb = false)
     if (c16) return lossy ? dwt_fwd2_kernel<float, true, true, kF2PairsLossy, true> : dwt_fwd2_kernel<int, false, true, kF2Pairs, true>;
     return lossy ? dwt_fwd2_kernel<float, true, true, kF2PairsLossy> : dwt_fwd2_kernel<int, false, true, kF2Pairs>;
 }
+
+// the rate calls' RGB head (plan_dwt_forward_unit): the ICT in the load stage, the coefficients in the 32-bit float form
+inline Fwd2Kernel select_fwd2_rgb_f32() { return dwt_fwd2_kernel<float, true, true, kF2PairsRgb, false, true>; }
 
 // ---- synthesis: one level (256 threads, grid f.gx x f.gy x frames)
 template <int BAND, bool C16>
@@ -226,6 +232,32 @@ inline void lut_geo_sections(LutGeo &g, int wl)
 inline bool bulk_compact(int aw, int ah, int wl, const LutGeo &g)
 {
     return bulk_max_span_bytes(aw, ah, wl, g.nBp, g.nSub, g.cRef, g.cSig, g.cSign) <= kBulkCompactBytes;
+}
+
+// ---- the rate calls' quantisation pass (quantise_kernel, rate_kernels.hpp): K = 1..3 candidate gains over the
+// unquantised float arrays of n frames, a workgroup (256 threads) a row at a time
+struct QuantLaunch { QuantKernel kernel; unsigned wgs; };
+inline QuantLaunch select_quantise(int K, int n, int ah)
+{
+    const size_t rows = (size_t)n * (size_t)ah;
+    const unsigned wgs = (unsigned)(rows > 8192 ? 8192 : rows);
+    return { K >= 3 ? quantise_kernel<3> : (K == 2 ? quantise_kernel<2> : quantise_kernel<1>), wgs };
+}
+// its arguments: the gains q(j) of `js`, candidate c as int16 where c16[c]; frames src_z / dst_z bytes apart
+inline QuantArgs quantise_args(const void *src, unsigned long long src_z, void *dst, unsigned long long dst_z, int aw, int ah,
+                               int wl, int n, int K, const int *js, const bool *c16)
+{
+    QuantArgs a;
+    memset(&a, 0, sizeof a);
+    a.src = src; a.src_z = src_z; a.dst = dst; a.dst_z = dst_z;
+    a.AW = aw; a.AH = ah; a.wl = wl; a.n = n;
+    for (int c = 0; c < kQuantMaxK; c++) {
+        a.qs[c] = rate_q(js[c < K ? c : K - 1]);
+        a.c16[c] = c16[c < K ? c : K - 1] ? 1 : 0;
+    }
+    for (int l = 0; l < 10; l++)
+        for (int k = 0; k < 4; k++) a.q[l][k] = kQSteps[l][k];
+    return a;
 }
 
 // workgroups (256 threads) of the element-wise kernels -- level shift, clamp, RGB transforms -- over n items, grid-stride

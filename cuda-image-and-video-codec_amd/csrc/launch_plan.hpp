@@ -161,6 +161,18 @@ inline std::vector<FwdLaunch> plan_dwt_forward(const void *d_in, bool u8in, void
 }
 inline bool plan_is_c16(const std::vector<FwdLaunch> &plan) { return !plan.empty() && plan[0].a.c16 != 0; }
 
+// The UNQUANTISED 9/7 transform of the rate calls (picsong_encode_frame_rate): the same plan with every step and qs at
+// 1.0f -- x * 1.0f * 1.0f is x, the transform is exact -- in the 32-bit float form, so one frame lands in one float
+// Mallat array at d_out (the last level's LL in its corner as usual).  quantise_kernel (rate_kernels.hpp) makes the
+// coefficients of any qs from it.
+inline std::vector<FwdLaunch> plan_dwt_forward_unit(const void *d_in, bool u8in, void *d_out, int aw, int ah, int wl)
+{
+    std::vector<FwdLaunch> v = plan_dwt_forward(d_in, u8in, d_out, aw, ah, wl, 1.0f, false);
+    for (FwdLaunch &f : v)
+        for (int k = 0; k < 4; k++) f.a.q[k] = 1.0f;
+    return v;
+}
+
 // Level 0 restricted to the input rows [row0, row0 + rows) (both even): the launch then produces the row
 // pairs [row0 / 2, (row0 + rows) / 2) of HL / LH / HH (Mallat) and of LL (scratch, or Mallat when wl = 1).
 inline void plan_restrict_band(FwdLaunch &f, int row0, int rows)

@@ -93,6 +93,10 @@ struct picsong_ctx {
     unsigned long long *d_train[3];
     uint32_t *train_scratch;
     size_t train_scratch_dwords;
+    // rate calls (picsong_encode_frame_rate): the unquantised transform's work buffers, rate_cap frames of rate_z bytes
+    void *rate_coef;
+    int rate_cap;
+    size_t rate_z;
 };
 
 // PICSONG_DWT_INV97=0 keeps the 9/7 synthesis levels off the lean kernel (select_inv): read once per process
@@ -315,6 +319,19 @@ int picsong_lut_load_cp(const char *folder_c, int component, int wl, int fill, i
 // ---------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------
+// What a context derives from its qs (and its geometry): picsong_ctx_create and picsong_ctx_set_qs
+static void ctx_derive_qs(picsong_ctx *c)
+{
+    const picsong_params *p = &c->p;
+    c->fast_div = p->lossy != 0 && dequant_fast_ok(p->qs, p->wl);
+    // 8-bit samples: 128 after the level shift; 255 covers the chroma differences of the RGB path's RCT
+    c->c16 = p->bit_depth == 8 && dwt_c16_geometry_ok(c->aw, c->ah, p->wl) &&
+             coef16_ok(p->lossy != 0, p->wl, p->qs, p->is_rgb ? 255 : 128);
+    // (an RGB context: picsong_decode_rgb_frame's three components; the plane-by-plane calls keep the 32-bit arrays)
+    c->c16_dec = p->cp != 3 && p->bit_depth == 8 &&
+                 dec_c16_ok(p->lossy != 0, p->wl, p->qs, p->is_rgb ? 255 : 128, c->aw, c->ah, c->fast_div);
+}
+
 int picsong_ctx_create(const picsong_params *p, int device, picsong_ctx **out)
 {
     if (!p || !out) return fail(PICSONG_ERR_ARG, "ctx_create: null argument");
@@ -359,14 +376,8 @@ int picsong_ctx_create(const picsong_params *p, int device, picsong_ctx **out)
     c->P = (size_t)aw * (size_t)ah;
     c->extra = picsong_dwt_extra(aw, ah, p->wl);
     c->dec_waves = window_waves_cap(aw, ah, p->wl, p->lossy != 0, c->ncb, kBpcEncWgWaves);
-    c->fast_div = p->lossy != 0 && dequant_fast_ok(p->qs, p->wl);
-    // 8-bit samples: 128 after the level shift; 255 covers the chroma differences of the RGB path's RCT
-    c->c16 = p->bit_depth == 8 && dwt_c16_geometry_ok(c->aw, c->ah, p->wl) &&
-             coef16_ok(p->lossy != 0, p->wl, p->qs, p->is_rgb ? 255 : 128);
+    ctx_derive_qs(c);
     c->bulk_compact[0] = c->bulk_compact[1] = c->bulk_compact[2] = -1;
-    // (an RGB context: picsong_decode_rgb_frame's three components; the plane-by-plane calls keep the 32-bit arrays)
-    c->c16_dec = p->cp != 3 && p->bit_depth == 8 &&
-                 dec_c16_ok(p->lossy != 0, p->wl, p->qs, p->is_rgb ? 255 : 128, c->aw, c->ah, c->fast_div);
     hipError_t e = hipMalloc(&c->one.offsets, sizeof(int32_t) * (size_t)c->ncb);
     if (e == hipSuccess) e = hipMalloc(&c->one.total, sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc(&c->d_flag, sizeof(int));
@@ -409,6 +420,7 @@ void picsong_ctx_destroy(picsong_ctx *c)
     free_batch(c);
     for (int k = 0; k < 3; k++) if (c->d_train[k]) (void)hipFree(c->d_train[k]);
     if (c->train_scratch) (void)hipFree(c->train_scratch);
+    if (c->rate_coef) (void)hipFree(c->rate_coef);
     if (c->prof_ev) {
         for (hipEvent_t e : *c->prof_ev) (void)hipEventDestroy(e);
         delete c->prof_ev;
@@ -553,6 +565,27 @@ int picsong_ctx_set_pipelined(picsong_ctx *c, int on)
 {
     if (!c) return fail(PICSONG_ERR_ARG, "set_pipelined: null context");
     c->pipelined = on != 0;
+    return PICSONG_OK;
+}
+
+int picsong_ctx_set_qs(picsong_ctx *c, float qs)
+{
+    if (!c) return fail(PICSONG_ERR_ARG, "set_qs: null context");
+    if (!(qs > 0.0f)) return fail(PICSONG_ERR_ARG, "set_qs: qs %g must be positive", qs);
+    // (picsong_ctx_create keeps the coding launcher's (0, 1]; here every gain the header's 14 bits store is taken, up to
+    // q(16383): the rate search's grid, and what a decoder may meet in a stream)
+    if (!(qs <= rate_q(kRateJMax))) return fail(PICSONG_ERR_ARG, "set_qs: qs %g is beyond the header's range (0, %g]", qs, rate_q(kRateJMax));
+    c->p.qs = qs;
+    ctx_derive_qs(c);
+    return PICSONG_OK;
+}
+
+int picsong_rate_qs(int j, float *qs)
+{
+    if (!qs) return fail(PICSONG_ERR_ARG, "rate_qs: null argument");
+    if (!rate_header_exact(j))
+        return fail(PICSONG_ERR_ARG, "rate_qs: j = %d is outside 1..%d or not stored exactly by the header", j, kRateJMax);
+    *qs = rate_q(j);
     return PICSONG_OK;
 }
 
@@ -1599,6 +1632,214 @@ int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *
                           stream_stride, s))) return rc;
     c->last_batch = 3;
     return PICSONG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// rate calls: encode to a target size (rate_search.hpp: the grid and the procedure; rate_kernels.hpp: the quantise pass)
+//   1. the UNQUANTISED transform of the n frames (plan_dwt_forward_unit), once, into float Mallat arrays;
+//   2. per round of the search: quantise_kernel writes the coefficients of the round's K candidates as K * n "frames" of
+//      the batch buffers, ONE batched coder launch codes them, the size scan totals them, ONE read-back through pinned
+//      memory brings the K * n totals to the stepper -- no pack;
+//   3. the winner is packed (from the last round's staging when it was coded there, else after one more quantise + coder
+//      launch of it alone) with a header whose qs field is the result.
+// PICSONG_RATE_K=1 keeps one candidate a round (the measurements of tools/rate_bench.py compare both).
+// ---------------------------------------------------------------------------------------------
+struct RateJob {
+    int n;                                  // frames (RGB: 1 frame, three components)
+    const uint8_t *frames; size_t frame_stride;
+    const uint8_t *r, *g, *b;               // RGB planes (frames == nullptr)
+    int first_iter, header_mask;
+    uint16_t *d_streams; size_t stream_stride;
+    bool single;                            // picsong_encode_frame_rate: the length also where picsong_encode_frame leaves it
+};
+
+static int rate_candidates(const picsong_ctx *c)
+{
+    // an RGB frame's coder launch maps frame f to table f for its three components only: one candidate a round
+    if (c->p.is_rgb) return 1;
+    if (const char *e = getenv("PICSONG_RATE_K")) if (atoi(e) == 1) return 1;
+    return kRateMaxK;
+}
+
+static int ensure_rate(picsong_ctx *c, int frames)
+{
+    if (frames <= c->rate_cap) return PICSONG_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    if (c->rate_coef) (void)hipFree(c->rate_coef);
+    c->rate_coef = nullptr; c->rate_cap = 0;
+    c->rate_z = ((c->P + c->extra + 3) & ~(size_t)3) * 4;   // (16-byte aligned arrays: quantise_kernel's loads)
+    HIP_TRY(hipMalloc(&c->rate_coef, (size_t)frames * c->rate_z));
+    c->rate_cap = frames;
+    return PICSONG_OK;
+}
+
+// step 1: the unquantised coefficients of the job's frames (RGB: of the three components), array f at rate_coef + f * rate_z
+static int rate_transform(picsong_ctx *c, const RateJob &job, hipStream_t s)
+{
+    int rc;
+    if (!c->p.is_rgb) {
+        std::vector<FwdLaunch> plan = plan_dwt_forward_unit(job.frames, true, c->rate_coef, c->aw, c->ah, c->p.wl);
+        plan_frame_strides(plan, job.frame_stride, c->rate_z);
+        return launch_fwd_plan(c, plan, s, (unsigned)job.n);
+    }
+    // the ICT in the fused head's load stage where the planes allow it (as rgb_forward_transform), 32-bit float form
+    const bool planes_aligned = ((((uintptr_t)job.r) | ((uintptr_t)job.g) | ((uintptr_t)job.b)) & 15u) == 0;
+    if (planes_aligned && !getenv("PICSONG_RGB_NOFUSE")) {
+        std::vector<FwdLaunch> plan = plan_dwt_forward_unit(job.r, true, c->rate_coef, c->aw, c->ah, c->p.wl);
+        plan_frame_strides(plan, 0, c->rate_z);
+        plan[0].a.src_g = job.g; plan[0].a.src_b = job.b;
+        Fwd2Launch f2;
+        if (plan_dwt_fwd2(plan, f2, true, true, kF2PairsRgb)) {
+            select_fwd2_rgb_f32()<<<dim3(f2.gx, f2.gy, 3u), 256, 0, s>>>(f2.a);
+            HIP_TRY(hipGetLastError());
+            return launch_fwd_levels(c, plan, 2, s, 3u);
+        }
+    }
+    char *planes = (char *)c->batch.coef_i;
+    if ((rc = picsong_rgb_forward(c, job.r, job.g, job.b, planes, planes + c->P * 4, planes + 2 * c->P * 4, (void *)s))) return rc;
+    std::vector<FwdLaunch> plan = plan_dwt_forward_unit(planes, false, c->rate_coef, c->aw, c->ah, c->p.wl);
+    plan_frame_strides(plan, (unsigned long long)c->P * 4ull, c->rate_z);
+    return launch_fwd_levels(c, plan, 0, s, 3u);
+}
+
+// step 2's launches for the candidates js[0 .. m): quantise, coder, size scan; the m * nf totals are then in batch.total
+// (nf: coded arrays a candidate -- the n frames, or an RGB frame's three components)
+static int rate_probe(picsong_ctx *c, BpcArgs a, int nf, int m, const int *js, hipStream_t s)
+{
+    int rc;
+    const int in_max = c->p.is_rgb ? 255 : 128;
+    bool c16 = c->p.bit_depth == 8 && dwt_c16_geometry_ok(c->aw, c->ah, c->p.wl);
+    for (int i = 0; i < m; i++) c16 = c16 && coef16_ok(true, c->p.wl, rate_q(js[i]), in_max);
+    const bool forms[kQuantMaxK] = { c16, c16, c16 };       // (one coder launch reads one form)
+    const unsigned long long dst_z = (unsigned long long)c->P * 4ull;
+    const QuantArgs qa = quantise_args(c->rate_coef, c->rate_z, c->batch.coef, dst_z, c->aw, c->ah, c->p.wl, nf, m, js, forms);
+    const QuantLaunch ql = select_quantise(m, nf, c->ah);
+    ql.kernel<<<ql.wgs, 256, 0, s>>>(qa);
+    HIP_TRY(hipGetLastError());
+    a.c16 = c16 ? 1 : 0; a.is_float = 1;
+    a.coeffs_in = c->batch.coef; a.coef_z = dst_z;
+    a.staging16 = reinterpret_cast<uint16_t *>(c->batch.staging);
+    a.sizes = c->batch.sizes; a.plane_scratch = c->batch.plane_scratch;
+    if (c->p.is_rgb) {                                      // (m == 1: component f codes with table f)
+        if ((rc = launch_encoder(c, a, 3u * (unsigned)a.waves_per_frame, 0, 3, s))) return rc;
+    } else {
+        a.cb_base = 0; a.nCB = c->ncb;
+        a.frames = m * nf; a.waves_per_frame = (c->ncb + 1) / 2;
+        if ((rc = launch_encoder(c, a, (unsigned)(m * nf) * (unsigned)a.waves_per_frame, 0, 1, s))) return rc;
+    }
+    scan_sizes_kernel<<<(unsigned)(m * nf), scan_threads(c->ncb), 0, s>>>(c->batch.sizes, c->ncb, c->batch.offsets, c->batch.total);
+    HIP_TRY(hipGetLastError());
+    return PICSONG_OK;
+}
+
+static int rate_impl(picsong_ctx *c, const RateJob &job, size_t target_shorts, int j_min, int j_max, hipStream_t s, int *h_j,
+                     int *h_totals, const char *who)
+{
+    // (the callers have made the null, context-kind, stride and alignment checks)
+    if (!c->p.lossy) return fail(PICSONG_ERR_ARG, "%s: a lossless context has no quantiser to search", who);
+    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 3 contexts have no rate control", who);
+    if (target_shorts == 0) return fail(PICSONG_ERR_ARG, "%s: target_shorts must be positive", who);
+    if (!rate_range_ok(j_min, j_max))
+        return fail(PICSONG_ERR_ARG, "%s: range [%d, %d] is neither 0, 0 (the whole grid) nor inside 1..%d", who, j_min, j_max, kRateJMax);
+    const std::vector<int> grid = rate_grid(j_min, j_max);
+    if (grid.empty()) return fail(PICSONG_ERR_ARG, "%s: no header-exact quantiser in [%d, %d]", who, j_min, j_max);
+    HIP_TRY(hipSetDevice(c->device));
+    const bool rgb = c->p.is_rgb != 0;
+    const int nf = rgb ? 3 : job.n, K = rate_candidates(c);
+    BpcArgs a;
+    int rc = rgb ? bpc_args_rgb(c, a) : bpc_args(c, a, 0);
+    if (rc) return rc;
+    if ((rc = ensure_batch(c, K * nf))) return rc;
+    if (rgb && (rc = ensure_coef_i(c, 3))) return rc;
+    if ((rc = ensure_rate(c, nf))) return rc;
+    c->last_batch = -1;                                     // (until the result is packed: no totals to hand out)
+    if ((rc = rate_transform(c, job, s))) return rc;
+
+    const long long target = target_shorts > (size_t)1 << 62 ? (long long)1 << 62 : (long long)target_shorts;
+    RateStepper st((int)grid.size(), target, K);
+    int idx[kRateMaxK], js[kRateMaxK], m = 0, last_js[kRateMaxK] = { 0, 0, 0 }, last_m = 0;
+    while ((m = st.next(idx)) > 0) {
+        for (int i = 0; i < m; i++) js[i] = grid[(size_t)idx[i]];
+        if ((rc = rate_probe(c, a, nf, m, js, s))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->h_totals, c->batch.total, (size_t)(m * nf) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        long long sizes[kRateMaxK] = { 0, 0, 0 };
+        for (int i = 0; i < m; i++)
+            for (int f = 0; f < nf; f++) sizes[i] += c->h_totals[i * nf + f];
+        st.take(sizes);
+        for (int i = 0; i < m; i++) last_js[i] = js[i];
+        last_m = m;
+    }
+    *h_j = 0;
+    if (st.result() < 0)
+        return fail(PICSONG_ERR_RATE, "%s: no quantiser of the search range meets %zu shorts", who, target_shorts);
+    const int j = grid[(size_t)st.result()];
+    // ---- the winner's staging: candidate `slot` of the last round, or coded once more on its own
+    int slot = -1;
+    for (int i = 0; i < last_m; i++) if (last_js[i] == j) slot = i;
+    if (slot < 0) {
+        if ((rc = rate_probe(c, a, nf, 1, &j, s))) return rc;
+        slot = 0;
+    }
+    Workspace w = c->batch;
+    w.sizes += (size_t)slot * (size_t)nf * (size_t)c->ncb; w.offsets += (size_t)slot * (size_t)nf * (size_t)c->ncb;
+    w.total += (size_t)slot * (size_t)nf;
+    const uint16_t *st16 = reinterpret_cast<const uint16_t *>(c->batch.staging) + (size_t)slot * (size_t)nf * c->P;
+    picsong_params hp = c->p;
+    hp.qs = rate_q(j);
+    uint16_t hdr[PICSONG_HDR_SHORTS];
+    picsong_header_pack(&hp, hdr);
+    const bool has_hdr = rgb ? (job.header_mask & 7) != 0 : (job.first_iter <= 0 && job.first_iter + job.n > 0);
+    const int has = rgb ? -(job.header_mask & 7) : -job.first_iter + 1;
+    if ((rc = pack_frames(c, st16, w, c->ncb, (unsigned)nf, has_hdr ? hdr : nullptr, has, job.d_streams, job.stream_stride, s))) return rc;
+    // (the lengths where the plain calls leave theirs: picsong_last_total(s) / picsong_copy_last_totals cover a rate call)
+    if (slot > 0) HIP_TRY(hipMemcpyAsync(c->batch.total, w.total, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (job.single) HIP_TRY(hipMemcpyAsync(c->one.total, w.total, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->h_totals, w.total, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int f = 0; f < nf; f++) h_totals[f] = c->h_totals[f];
+    c->last_batch = job.single ? 0 : nf;
+    *h_j = j;
+    return PICSONG_OK;
+}
+
+int picsong_encode_frames_rate(picsong_ctx *c, int n, const uint8_t *d_frames, size_t frame_stride, int first_iter,
+                               size_t target_shorts, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
+                               void *stream, int *h_j, int *h_totals)
+{
+    const char *who = "encode_frames_rate";
+    if (!c || !d_frames || !d_streams || !h_j || !h_totals) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (n < 1 || n > 16) return fail(PICSONG_ERR_ARG, "%s: %d frames outside 1..16", who, n);
+    if (c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: grey contexts only (an RGB frame: picsong_encode_rgb_frame_rate)", who);
+    if (n > 1 && (frame_stride < c->P || stream_stride < picsong_max_stream_shorts(c->aw, c->ah)))
+        return fail(PICSONG_ERR_ARG, "%s: strides smaller than a padded frame / a worst-case codestream", who);
+    if (((uintptr_t)d_frames | frame_stride) & 15u) return fail(PICSONG_ERR_ARG, "%s: frames must be 16-byte aligned", who);
+    const RateJob job = { n, d_frames, frame_stride, nullptr, nullptr, nullptr, first_iter, 0, d_streams, stream_stride, false };
+    return rate_impl(c, job, target_shorts, j_min, j_max, (hipStream_t)stream, h_j, h_totals, who);
+}
+
+int picsong_encode_frame_rate(picsong_ctx *c, const uint8_t *d_frame, int iter, size_t target_shorts, int j_min, int j_max,
+                              uint16_t *d_stream, void *stream, int *h_j, int *h_total)
+{
+    const char *who = "encode_frame_rate";
+    if (!c || !d_frame || !d_stream || !h_j || !h_total) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: grey contexts only (an RGB frame: picsong_encode_rgb_frame_rate)", who);
+    // (any alignment, as picsong_encode_frame: an unaligned frame takes the per-column transform kernels)
+    const RateJob job = { 1, d_frame, 0, nullptr, nullptr, nullptr, iter == 0 ? 0 : 1, 0, d_stream, 0, true };
+    return rate_impl(c, job, target_shorts, j_min, j_max, (hipStream_t)stream, h_j, h_total, who);
+}
+
+int picsong_encode_rgb_frame_rate(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
+                                  size_t target_shorts, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
+                                  void *stream, int *h_j, int *h_totals)
+{
+    const char *who = "encode_rgb_frame_rate";
+    if (!c || !d_r || !d_g || !d_b || !d_streams || !h_j || !h_totals) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: the context is not an RGB one", who);
+    if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah)) return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
+    if ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 3u) return fail(PICSONG_ERR_ARG, "%s: the planes need 4-byte alignment", who);
+    const RateJob job = { 1, nullptr, 0, d_r, d_g, d_b, 0, header_mask, d_streams, stream_stride, false };
+    return rate_impl(c, job, target_shorts, j_min, j_max, (hipStream_t)stream, h_j, h_totals, who);
 }
 
 // picsong_decode_rgb_frame (reduce = 0) and picsong_decode_rgb_frame_reduced: the three components' level `reduce`,

@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdio>
@@ -50,6 +51,8 @@ struct Options {
     int win = 0, wx = 0, wy = 0, ww = 0, wh = 0; // -window x,y,w,h: decode that rectangle of the image at 1/2^r
     int win_cb = 0;                             // (the codeblocks a window decodes, for --metrics)
     std::string train;                          // -train <outFolder>: count the input's coding decisions, write a LUT folder
+    float rate = 0.0f;                          // -rate <bpp>: choose qs so that the output meets that many bits per pixel
+    bool has_rate = false, has_qs = false;
 };
 
 [[noreturn]] void die(const std::string &msg)
@@ -108,7 +111,11 @@ void help()
         "                     codeblocks it depends on (spatial random access)\n"
         " -train <outFolder>  coding (-cd 0, -cp 2, -k 0): code nothing; count the input's coding decisions and write the\n"
         "                     probability tables fitted to them as a LUT folder for this -wl (no -o needed).  -LUTFolder,\n"
-        "                     if given, is the prior: its geometry, and its values for entries the input never reaches\n";
+        "                     if given, is the prior: its geometry, and its values for entries the input never reaches\n"
+        " -rate <bpp>         coding, -type 1: choose -qs so that a frame takes at most bpp bits per pixel (floor(bpp W H / 16)\n"
+        "                     shorts; an RGB frame's three components share it).  A video gets ONE qs (its stream has one header):\n"
+        "                     the search runs on the first min(frames, 16) frames and their summed target, the whole video is\n"
+        "                     coded at the result.  Not with -qs, -type 0 or -cp 3\n";
 }
 
 template <typename T> void echo(const char *flag, const T &v)
@@ -144,6 +151,13 @@ Options parse(const Args &a)
         gets("-train", o.train);
         if (o.train.empty()) die("Incorrect parameters. -train takes the folder to write.");
     }
+    if (a.has("-rate")) {
+        if (o.cd != 0) die("Incorrect parameters. -rate applies to coding (-cd 0) only.");
+        getf("-rate", o.rate);
+        o.has_rate = true;
+        if (!(o.rate > 0.0f)) die("Incorrect parameters. -rate takes a positive number of bits per pixel.");
+    }
+    o.has_qs = a.has("-qs");
     if (o.cd == 0) {
         geti("-xSize", o.x); geti("-ySize", o.y); geti("-cbWidth", o.cb_width); geti("-cbHeight", o.cb_height);
         geti("-wl", o.wl); geti("-cp", o.cp); geti("-endianess", o.endianess); geti("-bps", o.bps);
@@ -246,6 +260,28 @@ void write_metrics(const Options &o, const char *mode, long frames, double secon
     m << "}\n";
 }
 
+// ---- -rate <bpp>: the target of one frame in shorts, floor(bpp * W * H / 16) (W x H unpadded; the three components of an
+// RGB frame share it), and the two console lines
+size_t rate_target_shorts(const Options &o)
+{
+    return (size_t)std::floor((double)o.rate * (double)o.x * (double)o.y / 16.0);
+}
+void rate_report_choice(int j, float qs, size_t target, long nframes_searched)
+{
+    std::cout << "Rate control: qs " << qs << " (j = " << j << ") chosen for " << target << " shorts over " << nframes_searched
+              << " frame(s)" << std::endl;
+}
+void rate_report_achieved(const Options &o, long total_shorts, long nframes)
+{
+    std::cout << "Rate control: achieved " << (double)total_shorts * 16.0 / ((double)o.x * o.y * (double)nframes)
+              << " bits per pixel over the whole output (target " << o.rate << ")" << std::endl;
+}
+[[noreturn]] void rate_die(int rc, const char *call)
+{
+    if (rc == PICSONG_ERR_RATE) die(std::string("-rate: no quantiser meets the target size (") + picsong_last_error() + ")");
+    die(std::string(call) + " failed: " + picsong_last_error());
+}
+
 // ---- RGB coding (CodingEngine::runImage / runVideo, RGB branches: CodingEngine.cu:598-633,676-712,
 // 760-818,873-930): the input holds planar R, G, B planes per frame; RCT / ICT with the level shift
 // fused, then every component is coded as a frame of its own with its own LUT and appended to <o>,
@@ -287,7 +323,17 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
             HIPCK(hipStreamSynchronize(s));          // h_in is reused for the next plane
         }
         int totals[3] = { 0, 0, 0 };
-        if (batched) {
+        if (o.has_rate && f == 0) {
+            // the search on the first frame (an image: the frame); the rest of a video is coded at the result
+            int j = 0;
+            float q = 0.0f;
+            const int rc = picsong_encode_rgb_frame_rate(ctx, d_in[0], d_in[1], d_in[2], o.video ? 7 : 1, rate_target_shorts(o), 0, 0,
+                                                         d_out, max_shorts, s, &j, totals);
+            if (rc != PICSONG_OK) rate_die(rc, "picsong_encode_rgb_frame_rate");
+            CK(picsong_rate_qs(j, &q));
+            CK(picsong_ctx_set_qs(ctx, q));
+            rate_report_choice(j, q, rate_target_shorts(o), 1);
+        } else if (batched) {
             CK(picsong_encode_rgb_frame(ctx, d_in[0], d_in[1], d_in[2], o.video ? (f == 0 ? 7 : 0) : 1, d_out, max_shorts, s));
             CK(picsong_last_totals(ctx, s, 3, totals));
         } else {
@@ -309,6 +355,7 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
     }
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::cout << "The time spent with the app without considering allocation periods is: " << sec << std::endl;
+    if (o.has_rate) rate_report_achieved(o, total_shorts, nframes);
     write_metrics(o, "encode_rgb", nframes, sec, 0, 0, 0, total_shorts);
     picsong_ctx_destroy(ctx);
     (void)hipStreamDestroy(s);
@@ -423,6 +470,12 @@ int run_encode(Options o)
     if (o.signed_or_unsigned != 0 || o.bps != 8) die("Only unsigned 8-bit samples are built in this MI355X hot-path build.");
     const long nframes = o.video ? o.frames : 1;
     if (nframes <= 0) die("Incorrect parameters. Please choose valid values. (-frames)");
+    if (o.has_rate) {
+        if (o.has_qs) die("Incorrect parameters. -rate chooses the quantiser: it cannot be combined with -qs.");
+        if (o.type != 1) die("Incorrect parameters. -rate applies to lossy coding (-type 1) only.");
+        if (o.cp == 3) die("Incorrect parameters. -rate does not apply to -cp 3.");
+        if (!o.train.empty()) die("Incorrect parameters. -rate does not apply to -train.");
+    }
     if (!o.train.empty()) {
         if (o.k > 0) die("Incorrect parameters. -train counts the two-pass coder's decisions (-k must be 0).");
         if (o.cp == 3) die("Incorrect parameters. -train does not apply to -cp 3.");
@@ -485,6 +538,39 @@ int run_encode(Options o)
     }
     const int fd = open(o.input.c_str(), O_RDONLY);
     if (fd < 0) die("Cannot open input file " + o.input);
+    if (o.has_rate && o.video) {
+        // -rate on a video: the first slot's context (rank 0 of -gpus N) searches on the first min(frames, 16) frames and
+        // their summed target, then every context takes the chosen qs: the stream has one header, hence one qs
+        const int n = (int)std::min<long>(nframes, 16);
+        Worker &k = w[0];
+        HIPCK(hipSetDevice(k.device));
+        uint8_t *h_f = nullptr, *d_f = nullptr;
+        uint16_t *d_s = nullptr;
+        HIPCK(hipHostMalloc(&h_f, P * (size_t)n));
+        HIPCK(hipMalloc(&d_f, P * (size_t)n));
+        HIPCK(hipMalloc(&d_s, max_shorts * 2 * (size_t)n));
+        std::vector<uint8_t> raw(frame_bytes);
+        for (int f = 0; f < n; f++) {
+            size_t got = 0;
+            while (got < frame_bytes) {
+                ssize_t m = pread(fd, raw.data() + got, frame_bytes - got, (off_t)(file_base + (size_t)f * frame_bytes + got));
+                if (m <= 0) break;
+                got += (size_t)m;
+            }
+            if (got != frame_bytes) die("Input file is shorter than the requested frames.");
+            CK(picsong_pad_frame_host(raw.data(), o.x, o.y, h_f + (size_t)f * P, aw, ah));
+        }
+        HIPCK(hipMemcpyAsync(d_f, h_f, P * (size_t)n, hipMemcpyHostToDevice, k.stream));
+        int j = 0, totals[16];
+        float q = 0.0f;
+        const size_t target = rate_target_shorts(o) * (size_t)n;
+        const int rc = picsong_encode_frames_rate(k.ctx, n, d_f, P, 0, target, 0, 0, d_s, max_shorts, k.stream, &j, totals);
+        if (rc != PICSONG_OK) rate_die(rc, "picsong_encode_frames_rate");
+        CK(picsong_rate_qs(j, &q));
+        for (auto &x : w) CK(picsong_ctx_set_qs(x.ctx, q));
+        rate_report_choice(j, q, target, n);
+        (void)hipHostFree(h_f); (void)hipFree(d_f); (void)hipFree(d_s);
+    }
     // image: one truncating write (IOManager.ipp:615-620); video: append + _SIZE (:176-190)
     const int ofd = open(o.output.c_str(), O_WRONLY | O_CREAT | (o.video ? 0 : O_TRUNC), 0644);
     if (ofd < 0) die("Cannot open output file " + o.output);
@@ -638,6 +724,15 @@ int run_encode(Options o)
         std::string err;
         if (hipSetDevice(k.device) != hipSuccess ||
             hipMemcpyAsync(k.d_in, k.h_in, P * (size_t)n, hipMemcpyHostToDevice, k.stream) != hipSuccess) err = "HIP error in the frame upload";
+        else if (o.has_rate && !o.video) {
+            // an image: one rate call (synchronous); its length is the context's last total, as after picsong_encode_frame
+            int j = 0, total = 0;
+            float q = 0.0f;
+            const int rc = picsong_encode_frame_rate(k.ctx, k.d_in, 0, rate_target_shorts(o), 0, 0, k.d_out, k.stream, &j, &total);
+            if (rc == PICSONG_ERR_RATE) err = std::string("-rate: no quantiser meets the target size (") + picsong_last_error() + ")";
+            else if (rc != PICSONG_OK || picsong_rate_qs(j, &q) != PICSONG_OK) err = picsong_last_error();
+            else rate_report_choice(j, q, rate_target_shorts(o), 1);
+        }
         else if (B == 1) { if (picsong_encode_frame(k.ctx, k.d_in, g == 0 ? 0 : 1, k.d_out, k.stream) != PICSONG_OK) err = picsong_last_error(); }
         else if (picsong_encode_frames(k.ctx, n, k.d_in, P, (int)(g * B), k.d_out, max_shorts, k.stream) != PICSONG_OK) err = picsong_last_error();
         t_launch += secs(tm1, now());
@@ -675,6 +770,7 @@ int run_encode(Options o)
     }
     std::cout << "The time spent with the app without considering allocation periods is: " << sec << std::endl;
     std::cout << "BPC acum time is: " << (counted ? bpc / counted * (double)ngroups : 0.0) / 1e3 << std::endl;
+    if (o.has_rate) rate_report_achieved(o, total_shorts, nframes);
     write_metrics(o, "encode", nframes, sec, counted ? dwt / counted / B : 0, counted ? bpc / counted / B : 0,
                   counted ? pack / counted / B : 0, total_shorts);
     for (auto &k : w) {
@@ -685,6 +781,16 @@ int run_encode(Options o)
         free(k.h_raw);
     }
     return 0;
+}
+
+// A decode context from a stream's header.  picsong_ctx_create keeps the coding launcher's -qs range (0, 1]; a stream coded
+// by -rate may carry any gain the header stores (up to 1.6383): such a context is created at 1 and re-tuned.
+void create_decode_ctx(picsong_params p, int device, picsong_ctx **ctx)
+{
+    const float qs = p.qs;
+    if (p.lossy && qs > 1.0f) p.qs = 1.0f;
+    CK(picsong_ctx_create(&p, device, ctx));
+    if (p.lossy && qs > 1.0f) CK(picsong_ctx_set_qs(*ctx, qs));
 }
 
 // ---- decoding engine: DecodingEngine::runImage / runVideo call sequence -----------------------
@@ -795,7 +901,7 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
     std::vector<Slot> sl((size_t)nslots);
     for (int i = 0; i < nslots; i++) {
         Slot &k = sl[(size_t)i];
-        CK(picsong_ctx_create(&p, o.device, &k.ctx));
+        create_decode_ctx(p, o.device, &k.ctx);
         load_lut(k.ctx, o, p.wl, 1, p.k, p.cp);
         HIPCK(hipStreamCreate(&k.stream));
         HIPCK(hipHostMalloc(&k.h_in, max_shorts * 2 * B));
@@ -958,7 +1064,7 @@ int run_decode(const Options &o)
     }
     HIPCK(hipSetDevice(o.device));
     picsong_ctx *ctx = nullptr;
-    CK(picsong_ctx_create(&p, o.device, &ctx));
+    create_decode_ctx(p, o.device, &ctx);
     Options lo = o;
     load_lut(ctx, lo, p.wl, p.components, p.k, p.cp);
     int aw, ah, ncb;

@@ -13,6 +13,7 @@ PKG = os.path.dirname(HERE)
 SO_PATH = os.environ.get("PICSONG_SO", os.path.join(PKG, "csrc", "libpicsong_hip.so"))
 
 PICSONG_OK = 0
+PICSONG_ERR_RATE = -7
 
 
 class Params(C.Structure):
@@ -51,6 +52,8 @@ EXPORTS = [
     "picsong_train_begin", "picsong_train_info", "picsong_train_reset", "picsong_train_end", "picsong_train_coeffs",
     "picsong_train_frames", "picsong_train_rgb_frame", "picsong_train_counts", "picsong_lut_from_counts",
     "picsong_lut_save",
+    "picsong_rate_qs", "picsong_ctx_set_qs", "picsong_encode_frame_rate", "picsong_encode_frames_rate",
+    "picsong_encode_rgb_frame_rate",
 ]
 
 _lib = None
@@ -149,6 +152,14 @@ def load():
         L.picsong_train_counts.argtypes = [vp, i, vp, vp, C.c_size_t]
         L.picsong_lut_from_counts.argtypes = [C.POINTER(LutInfo), vp, vp, vp]
         L.picsong_lut_save.argtypes = [C.c_char_p, i, C.POINTER(LutInfo), i, vp]
+    if hasattr(L, "picsong_rate_qs"):
+        L.picsong_rate_qs.argtypes = [i, C.POINTER(C.c_float)]
+        L.picsong_ctx_set_qs.argtypes = [vp, C.c_float]
+        L.picsong_encode_frame_rate.argtypes = [vp, vp, i, C.c_size_t, i, i, vp, vp, C.POINTER(i), C.POINTER(i)]
+        L.picsong_encode_frames_rate.argtypes = [vp, i, vp, C.c_size_t, i, C.c_size_t, i, i, vp, C.c_size_t, vp,
+                                                 C.POINTER(i), C.POINTER(i)]
+        L.picsong_encode_rgb_frame_rate.argtypes = [vp, vp, vp, vp, i, C.c_size_t, i, i, vp, C.c_size_t, vp,
+                                                    C.POINTER(i), C.POINTER(i)]
     _lib = L
     return L
 
@@ -160,6 +171,24 @@ class PicsongError(RuntimeError):
 def _check(rc):
     if rc != PICSONG_OK:
         raise PicsongError(f"picsong error {rc}: {load().picsong_last_error().decode()}")
+
+
+class RateError(PicsongError):
+    """No quantiser of the search range meets the target size (PICSONG_ERR_RATE)."""
+
+
+def _check_rate(rc):
+    if rc == PICSONG_ERR_RATE:
+        raise RateError(load().picsong_last_error().decode())
+    _check(rc)
+
+
+def rate_qs(j):
+    """q(j) = float32(j / 10000.0), the gain a decoder reads for a stored j; raises for a j outside 1..16383 or one the
+    header does not store exactly (picsong_rate_qs)."""
+    q = C.c_float()
+    _check(load().picsong_rate_qs(j, C.byref(q)))
+    return q.value
 
 
 def pad_dim(v):
@@ -289,6 +318,42 @@ class Codec:
         table = np.ascontiguousarray(table, np.int32)
         _check(self.L.picsong_ctx_set_lut_component(self.h, component, C.byref(info),
                                                     table.ctypes.data_as(C.c_void_p)))
+
+    # ---- rate control: the 9/7 encode calls with qs chosen to meet a size (synchronous) ----
+    def set_qs(self, qs):
+        """The context's qs from now on (picsong_ctx_set_qs): tables and buffers stay."""
+        _check(self.L.picsong_ctx_set_qs(self.h, qs))
+        self.params.qs = qs
+
+    def encode_frame_rate(self, frame_u8_padded, target_shorts, j_min=0, j_max=0, iter_=0, out=None):
+        """Returns (j, codestream): the stream of picsong_encode_frame at qs = rate_qs(j), j the quantiser search's
+        result for target_shorts; raises RateError when nothing of the range fits."""
+        if out is None:
+            out = self.torch.empty(self.max_stream_shorts(), dtype=self.torch.int16, device=self.dev)
+        j, t = C.c_int(), C.c_int()
+        _check_rate(self.L.picsong_encode_frame_rate(self.h, self._p(frame_u8_padded), iter_, target_shorts, j_min, j_max,
+                                                     self._p(out), self._stream(), C.byref(j), C.byref(t)))
+        return j.value, out[:t.value]
+
+    def encode_frames_rate(self, frames_u8_padded, target_shorts, j_min=0, j_max=0, first_iter=0):
+        """frames_u8_padded: uint8 [n, AH*AW], n <= 16; target_shorts for the sum of the n streams.  Returns (j, streams)."""
+        n = frames_u8_padded.shape[0]
+        assert frames_u8_padded.stride(-1) == 1
+        out = self.torch.empty((n, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        j, t = C.c_int(), (C.c_int * n)()
+        _check_rate(self.L.picsong_encode_frames_rate(self.h, n, self._p(frames_u8_padded), frames_u8_padded.stride(0),
+                                                      first_iter, target_shorts, j_min, j_max, self._p(out), out.stride(0),
+                                                      self._stream(), C.byref(j), t))
+        return j.value, [out[f, :t[f]] for f in range(n)]
+
+    def encode_rgb_frame_rate(self, r, g, b, target_shorts, j_min=0, j_max=0, header_mask=1):
+        """target_shorts for the sum of the three components' streams.  Returns (j, the three codestreams)."""
+        out = self.torch.empty((3, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        j, t = C.c_int(), (C.c_int * 3)()
+        _check_rate(self.L.picsong_encode_rgb_frame_rate(self.h, self._p(r), self._p(g), self._p(b), header_mask,
+                                                         target_shorts, j_min, j_max, self._p(out), out.stride(0),
+                                                         self._stream(), C.byref(j), t))
+        return j.value, [out[k, :t[k]] for k in range(3)]
 
     # ---- training: the statistics a probability table is made from (k = 0, -cp 2 contexts; no table needed) ----
     def train_begin(self, **geometry):

@@ -33,6 +33,7 @@ extern "C" {
 #define PICSONG_ERR_NOMEM (-4)
 #define PICSONG_ERR_RANGE (-5)      /* a codeblock exceeded the supported magnitude range */
 #define PICSONG_ERR_NODEVICE (-6)   /* no usable GPU: the product has no CPU fallback */
+#define PICSONG_ERR_RATE (-7)       /* no quantiser of the search range meets the target size */
 
 #define PICSONG_CB 64               /* codeblock edge, BPC/BPCEngine.cuh:29-36 */
 #define PICSONG_CB_WORDS 4096       /* staging ints per codeblock */
@@ -365,6 +366,57 @@ int picsong_train_counts(picsong_ctx *ctx, int component, void *stream, uint64_t
  *   LL statistics land on a detail subband's group (the shipped folders are laid out for wl = 5 in the same way). */
 int picsong_lut_from_counts(const picsong_lut_info *info, const uint64_t *counts, const int32_t *prior_table, int32_t *table);
 int picsong_lut_save(const char *folder, int component, const picsong_lut_info *info, int wl, const int32_t *table);
+
+/* ---- encode to a target size (JPEG 2000 style rate control, OpenJPEG -r / Kakadu -rate; the reference has no
+ *      counterpart): the 9/7 calls above with the quantiser gain qs CHOSEN so that the codestream meets a size.
+ *      The grid.  The header stores qs as (int)(qs * 10000) in 14 bits and a decoder reads q(j) = (float)(j / 10000.0):
+ *      only the values q(j), j = 1..16383, ever reach a decoder, and for 1143 of them the float product stores j - 1
+ *      (7, 14, 28, ... 16383).  The search runs over the header-exact grid G, the 15240 values of j the header carries
+ *      unchanged (1 2 3 4 5 6 8 9 ... 16382).  picsong_rate_qs (host only): q(j); PICSONG_ERR_ARG for j outside 1..16383
+ *      or not in G.
+ *      The result.  Size against j is not monotone (a finer quantiser can code a few shorts shorter), so the result is
+ *      defined by a procedure, not as a maximum: with G' = the entries of G inside [j_min, j_max] (j_min = j_max = 0: all
+ *      of G; else 1 <= j_min <= j_max <= 16383; a range without a grid entry is PICSONG_ERR_ARG),
+ *          lo = -1, hi = len(G');  while hi - lo > 1: mid = (lo + hi) / 2;  size(G'[mid]) <= target ? lo = mid : hi = mid
+ *      and the result is G'[lo]; size(j) = the codestream length in shorts, header and terminator included, as
+ *      picsong_last_total reports it, summed over the call's frames / components.  14 probes over the whole grid.
+ *      On success *h_j is the result, the streams are BYTE-IDENTICAL to what picsong_encode_frame / picsong_encode_frames /
+ *      picsong_encode_rgb_frame write on a context created with qs = q(*h_j) (the header carries that qs), and
+ *      h_total(s) receive their lengths (1, n and 3 of them).  When nothing fits (size(G'[0]) > target) the call returns
+ *      PICSONG_ERR_RATE with *h_j = 0; the streams are then unspecified, and no short beyond picsong_max_stream_shorts
+ *      per stream is ever written.
+ *      How.  The transform runs once with unit steps into float arrays; each round of the search quantises them for up
+ *      to three candidates (the midpoint and the two midpoints that follow from either outcome: two steps of the
+ *      procedure) and codes them in one batched coder launch; only the result is packed.  The calls are SYNCHRONOUS on
+ *      `stream`: one read-back of the candidates' lengths per round, through pinned memory, and one at the end.  The
+ *      lengths come back through h_total(s), and stay where the plain calls leave theirs (picsong_last_total after the
+ *      single-frame call, picsong_last_totals / picsong_copy_last_totals after all three).
+ *      The context's own qs is NOT changed.  picsong_ctx_set_qs sets it -- re-deriving everything picsong_ctx_create
+ *      derives from qs, tables and buffers kept -- so that a caller codes the rest of a video at the chosen qs without a
+ *      new context; it refuses qs <= 0 and qs > q(16383) = 1.6383, what the header cannot store.  (picsong_ctx_create
+ *      keeps the reference launcher's range (0, 1]; the grid is the header's whole range, so a result above j = 10000 --
+ *      an easy image and a generous target -- is reached through picsong_ctx_set_qs, by a decoder too: create the context
+ *      at qs = 1 and set the header's value.)
+ *      picsong_range_flag accumulates over every probe of a call: a probe FINER than the result can raise it even when
+ *      the result's own stream would not.
+ *      The context grows its workspace at the first call: one float array per frame and the batch buffers of 3 n frames.
+ *      picsong_encode_frames_rate: n = 1..16 (the candidates share the 64-frame batched grid), target_shorts for the SUM of
+ *      the n streams, strides and alignment as picsong_encode_frames; any -k.  picsong_encode_rgb_frame_rate:
+ *      target_shorts for the sum of the three components' streams; one candidate a round (the coder maps a launch's frames
+ *      to the component tables for three frames only); same result.
+ *      Refused (PICSONG_ERR_ARG, nothing launched): lossless contexts, -cp 3 contexts, the grey calls on an RGB context and
+ *      the RGB call on a grey one, target_shorts = 0, a bad range, and the null / stride / alignment checks of the plain
+ *      calls (h_j and h_total(s) must not be null). ---- */
+int picsong_rate_qs(int j, float *qs);
+int picsong_ctx_set_qs(picsong_ctx *ctx, float qs);
+int picsong_encode_frame_rate(picsong_ctx *ctx, const uint8_t *d_frame, int iter, size_t target_shorts, int j_min, int j_max,
+                              uint16_t *d_stream, void *stream, int *h_j, int *h_total);
+int picsong_encode_frames_rate(picsong_ctx *ctx, int n, const uint8_t *d_frames, size_t frame_stride, int first_iter,
+                               size_t target_shorts, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
+                               void *stream, int *h_j, int *h_totals);
+int picsong_encode_rgb_frame_rate(picsong_ctx *ctx, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
+                                  size_t target_shorts, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
+                                  void *stream, int *h_j, int *h_totals);
 
 /* ---- intra-frame sharding (BASELINE config 5): codeblocks are independent
  *      (correctCBBorders zeroes outside neighbours, BPC/BPCEngine.cu:465-484), so a rank can code

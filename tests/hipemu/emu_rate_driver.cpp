@@ -1,0 +1,108 @@
+// TEST INFRASTRUCTURE ONLY -- the rate calls' pieces on the CPU wave emulator: the search (rate_search.hpp, the very
+// stepper picsong_hip.hip walks), the unquantised forward transform (plan_dwt_forward_unit, launched the way
+// launch_fwd_plan / rate_transform do) and quantise_kernel with the launch and the arguments kernel_select.hpp gives it.
+// Built by tests/test_rate_emulated.py with the flags of tests/hipemu/Makefile.
+#include <hip/hip_runtime.h>
+
+#include "../../cuda-image-and-video-codec_amd/csrc/kernel_select.hpp"
+
+using namespace picsong;
+
+static void emu_fwd_levels(const std::vector<FwdLaunch> &plan, size_t from, unsigned frames)
+{
+    for (size_t l = from; l < plan.size(); l++) {
+        const FwdLaunch &f = plan[l];
+        const FwdKernel k = select_fwd(true, f);
+        emu::launch(dim3(f.gx, f.gy, frames), dim3(256), [&] { k(f.a); });
+    }
+}
+
+extern "C" {
+
+float emu_rate_q(int j) { return rate_q(j); }
+int emu_rate_header_exact(int j) { return rate_header_exact(j) ? 1 : 0; }
+
+// G' into out (capacity cap); returns its length, -1 for a bad range
+int emu_rate_grid(int j_min, int j_max, int *out, int cap)
+{
+    if (!rate_range_ok(j_min, j_max)) return -1;
+    const std::vector<int> g = rate_grid(j_min, j_max);
+    for (size_t i = 0; i < g.size() && (int)i < cap; i++) out[i] = g[i];
+    return (int)g.size();
+}
+
+// The search as rate_impl runs it, over a synthetic size function given as a table size_by_j[0 .. 16383].  Returns the
+// result j, 0 when nothing fits, -1 for a range without a grid entry.  stats: { rounds, probes used, probes made };
+// probed (capacity 64): the j of every probe made, round by round.
+int emu_rate_search(const long long *size_by_j, long long target, int j_min, int j_max, int K, int *stats, int *probed)
+{
+    if (!rate_range_ok(j_min, j_max)) return -1;
+    const std::vector<int> grid = rate_grid(j_min, j_max);
+    if (grid.empty()) return -1;
+    RateStepper st((int)grid.size(), target, K);
+    int idx[kRateMaxK], m, made = 0;
+    while ((m = st.next(idx)) > 0) {
+        long long sizes[kRateMaxK] = { 0, 0, 0 };
+        for (int i = 0; i < m; i++) {
+            sizes[i] = size_by_j[grid[(size_t)idx[i]]];
+            if (probed && made < 64) probed[made] = grid[(size_t)idx[i]];
+            made++;
+        }
+        st.take(sizes);
+    }
+    if (stats) { stats[0] = st.rounds(); stats[1] = st.probes(); stats[2] = made; }
+    return st.result() < 0 ? 0 : grid[(size_t)st.result()];
+}
+
+// the unquantised transform of `frames` frames (u8 with the level shift fused, or float), frame z at in + z * in_z bytes,
+// into the float work buffers out + z * out_z bytes; returns 1 when levels 0 and 1 went through the fused head
+int emu_rate_unit_forward(const void *in, int u8in, unsigned long long in_z, void *out, unsigned long long out_z, int aw,
+                          int ah, int wl, int frames)
+{
+    std::vector<FwdLaunch> plan = plan_dwt_forward_unit(in, u8in != 0, out, aw, ah, wl);
+    for (size_t l = 0; l < plan.size(); l++) { plan[l].a.src_z = l == 0 ? in_z : out_z; plan[l].a.dst_z = out_z; }
+    Fwd2Launch f2;
+    const bool fused01 = plan_dwt_fwd2(plan, f2, true, true);
+    if (fused01) {
+        const Fwd2Kernel k = select_fwd2(true, false);
+        emu::launch(dim3(f2.gx, f2.gy, (unsigned)frames), dim3(256), [&] { k(f2.a); });
+    }
+    emu_fwd_levels(plan, fused01 ? 2 : 0, (unsigned)frames);
+    return fused01 ? 1 : 0;
+}
+
+// an RGB frame's three components, the ICT in the fused head's load stage (rate_transform's first form); 0: the form
+// does not apply to the geometry
+int emu_rate_unit_forward_rgb(const uint8_t *r, const uint8_t *g, const uint8_t *b, void *out, unsigned long long out_z,
+                              int aw, int ah, int wl)
+{
+    std::vector<FwdLaunch> plan = plan_dwt_forward_unit(r, true, out, aw, ah, wl);
+    for (size_t l = 0; l < plan.size(); l++) { plan[l].a.src_z = l == 0 ? 0ull : out_z; plan[l].a.dst_z = out_z; }
+    plan[0].a.src_g = g; plan[0].a.src_b = b;
+    Fwd2Launch f2;
+    if (!plan_dwt_fwd2(plan, f2, true, true, kF2PairsRgb)) return 0;
+    const Fwd2Kernel k = select_fwd2_rgb_f32();
+    emu::launch(dim3(f2.gx, f2.gy, 3u), dim3(256), [&] { k(f2.a); });
+    emu_fwd_levels(plan, 2, 3u);
+    return 1;
+}
+
+// quantise_kernel over n float arrays for the K candidates js (candidate c as int16 where c16[c]); max_wgs > 0 caps the
+// grid (a workgroup then takes several rows)
+void emu_rate_quantise(const void *src, unsigned long long src_z, void *dst, unsigned long long dst_z, int aw, int ah, int wl,
+                       int n, int K, const int *js, const int *c16, int max_wgs)
+{
+    bool forms[kQuantMaxK] = { false, false, false };
+    for (int c = 0; c < K; c++) forms[c] = c16[c] != 0;
+    const QuantArgs a = quantise_args(src, src_z, dst, dst_z, aw, ah, wl, n, K, js, forms);
+    QuantLaunch l = select_quantise(K, n, ah);
+    if (max_wgs > 0 && l.wgs > (unsigned)max_wgs) l.wgs = (unsigned)max_wgs;
+    emu::launch(dim3(l.wgs), dim3(256), [&] { l.kernel(a); });
+}
+
+int emu_rate_coef16_ok(int wl, int j, int in_max, int aw, int ah)
+{
+    return coef16_ok(true, wl, rate_q(j), in_max) && dwt_c16_geometry_ok(aw, ah, wl) ? 1 : 0;
+}
+
+}  // extern "C"
