@@ -989,6 +989,61 @@ __device__ __forceinline__ void enc_spp_coeff(EncCoder &c, uint32_t rowbit, uint
         enc_site2<J>(c, onem, onem & __builtin_amdgcn_ballot_w64((s2 & rowbit) != 0u), Q4, prec, upper_mask);
 }
 
+// ---- the first plane of the k = 0 encoder (PICSONG_ENC_FIRST_PLANE, default 1) -----------------------------------------
+// Step 0 of a wave codes plane `msb` of each half's own codeblock: nothing is significant yet (A = 0, N = B), and the
+// generic plane body pays for much that cannot happen there.  Every coded lane codes at every significance site, so the
+// lanes of a site are ONE wave-constant mask (`onm` = ballot(coded)): no test of A per site, no mask of rows to visit.
+// The row below is all zeros, and for a left coefficient so is its own row: its context is the count of the three
+// neighbours above (n2 = n3 = 0: one table word, two spreads), its sign context has no horizontal part (c2 = 0, c1 =
+// `up significant`, c0 = `up significant and negative`: one spread); a right coefficient sees five neighbours at most (n3 =
+// 0).  Context 8 cannot occur: no reduction of n3 over the wave, no gate, no fix-up.  The refinement pass is empty.
+// make_col is handed literal zeros and folds; of the twelve neighbour-column moves of a plane six remain.
+// The groups of four rows are a LOOP over a scalar counter: unrolled, the eight group bodies of both halves would
+// double the kernel's code.  =0 builds the kernel with step 0 in the generic body.
+#ifndef PICSONG_ENC_FIRST_PLANE
+#define PICSONG_ENC_FIRST_PLANE 1
+#endif
+// enc_spp_coeff with A = 0 and N = B (0 in a lane outside onm)
+template <int J>
+__device__ __forceinline__ void enc_spp_coeff_first(EncCoder &c, uint32_t rowbit, uint64_t onm, uint32_t B,
+                                                    uint32_t s2, uint32_t P4, uint32_t Q4, uint32_t prec, uint32_t upper_mask)
+{
+    const uint64_t onem = __builtin_amdgcn_ballot_w64((B & rowbit) != 0u);
+    enc_site2<J>(c, onm, onem, P4, prec, upper_mask);
+    if (onem != 0ull)
+        enc_site2<J>(c, onem, onem & __builtin_amdgcn_ballot_w64((s2 & rowbit) != 0u), Q4, prec, upper_mask);
+}
+// The significance pass of rows 32 HW .. 32 HW + 31 at step 0.  BL / BR: the plane's bits of the lane's columns (0 in an
+// idle half), BPL / BNL: lane-1's right and lane+1's left column, sgNL: lane+1's left sign column; onm != 0.
+template <int HW>
+__device__ __forceinline__ void enc_spp_first_half(EncCoder &c, uint64_t onm, const U64 &BL, const U64 &BR, const U64 &BPL,
+                                                   const U64 &BNL, const U64 &sgL, const U64 &sgR, const U64 &sgNL,
+                                                   const PlaneLut &pl, uint32_t prec, uint32_t upper_mask)
+{
+    const ColHalf cpL = make_col(up_of(BPL, HW), up_of(BL, HW), up_of(BR, HW), 0u, 0u, 0u, 0u, 0u,
+                                 up_of(BL, HW), up_of(sgL, HW), 0u, 0u, 0u, 0u, 0u, 0u, w_of(sgL, HW));
+    const ColHalf cpR = make_col(up_of(BL, HW), up_of(BR, HW), up_of(BNL, HW), w_of(BL, HW), w_of(BNL, HW), 0u, 0u, 0u,
+                                 up_of(BR, HW), up_of(sgR, HW), 0u, 0u,
+                                 w_of(BL, HW), w_of(sgL, HW), w_of(BNL, HW), w_of(sgNL, HW), w_of(sgR, HW));
+    const uint32_t bl = w_of(BL, HW), br = w_of(BR, HW);
+#pragma unroll 1
+    for (uint32_t g4 = 0u; g4 < 32u; g4 += 4u) {
+        // left column: contexts 0..3 (the first table word) and sign contexts 0 / 1
+        const uint32_t selL = bfi32(0x01010101u, spread4_raw<0>(cpL.n0, g4), spread4_raw<1>(cpL.n1, g4)) & 0x03030303u;
+        const uint32_t P4L = __builtin_amdgcn_perm(0u, pl.sig0, selL), P4R = sig_probs4_07(cpR, pl, g4);
+        const uint32_t Q4L = __builtin_amdgcn_perm(0u, pl.sign, spread4(cpL.c1, g4)), Q4R = sign_probs4(cpR, pl, g4);
+        const uint32_t gbit = 1u << g4;
+#define PS_SPP_ROW(J)                                                                                    \
+        {                                                                                                 \
+            const uint32_t rowbit = vgpr_of(gbit << J);                                                   \
+            enc_spp_coeff_first<J>(c, rowbit, onm, bl, cpL.s2, P4L, Q4L, prec, upper_mask);               \
+            enc_spp_coeff_first<J>(c, rowbit, onm, br, cpR.s2, P4R, Q4R, prec, upper_mask);               \
+        }
+        PS_SPP_ROW(0) PS_SPP_ROW(1) PS_SPP_ROW(2) PS_SPP_ROW(3)
+#undef PS_SPP_ROW
+    }
+}
+
 __device__ __forceinline__ uint32_t dec_site(Coder &c, uint32_t inact, uint32_t p, uint32_t prec,
                                              uint32_t upper_mask, const int32_t *stage);
 template <bool KEEP>
@@ -1305,6 +1360,15 @@ __device__ __forceinline__ void opaque32(uint32_t &x)
     (void)x;
 #endif
 }
+// the lane's number in its wave, from no register (threadIdx.x & 63 asks for one to be kept, or spilled and reloaded)
+__device__ __forceinline__ uint32_t lane_number()
+{
+#if defined(__AMDGCN__)
+    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+#else
+    return threadIdx.x & 63u;
+#endif
+}
 // nothing is scheduled across this point
 __device__ __forceinline__ void sched_fence()
 {
@@ -1441,6 +1505,7 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
 {
     static_assert(BULK || !COMPACT, "compact table copies belong to the -k > 0 instantiations");
     constexpr int kTab = COMPACT ? kBulkCompactBytes : kLutLdsMax;       // bytes of one LDS table copy
+    constexpr bool PEEL = !BULK && PICSONG_ENC_FIRST_PLANE != 0;        // step 0 in a body of its own (enc_spp_first_half)
     // -k > 0: a byte copy of its table per codeblock; k = 0: the table's plane records (plane_img_to_lds)
     __shared__ alignas(16) uint8_t lds_lut[BULK ? 2 * kTab : kPlaneImgMaxRecs * (int)sizeof(PlaneRec)];
     __shared__ uint32_t lds_cnt[2 * (BULK ? 1 : kBpcEncWgWaves)];      // codeword counters of the workgroup's codeblocks
@@ -1550,13 +1615,35 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
     c.slot0 = half * kStageCb + kStageBytes; c.lim = c.slot0 + kStageBytes * 4094u; c.pone = 1u << prec;
     c.stw = reinterpret_cast<char *>(stw);
     U64 AL = { 0u, 0u }, AR = { 0u, 0u };                 // significant before the current plane
+    // With two plane bodies the kernel has no register left for what a lane can form again with an instruction: slot 0's
+    // offset comes from `lim`, which every reservation keeps in a register (one subtraction at the top of a plane, where it
+    // was a reload from the wave's private scratch), and the epilogue numbers its lane afresh instead of keeping t, half
+    // and the codeblock's index through the planes.
+    if constexpr (PEEL) opaque32(c.lim);
     U64 BLn, BRn;
     load_plane(0, BLn, BRn);
 
     bool live = coded;                                     // false once the codeblock is bound for the raw fallback
     PS_BPC_TRACE(1, __builtin_amdgcn_s_memrealtime());
     PS_BPC_TRACE(3, (unsigned long long)np);
-    for (int p = 0; p < np; p++) {
+    int p0 = 0;                                            // the first step the loop below codes
+    if constexpr (PEEL) {
+        // step 0 in a body of its own (enc_spp_first_half): plane msb of each half's own codeblock, nothing significant
+        // before it; the next plane is on its way from the scratch meanwhile.  np > 0: some lane of the wave is coded.
+        if (np > 0) {
+            const U64 BL = BLn, BR = BRn;
+            if (np > 1) load_plane(1, BLn, BRn);
+            PlaneLut pl = { 0u, 0u, 0u, 0u, 0u, 0u };
+            if (coded) pl = plane_lut_img(recs, 0, msb);
+            const uint64_t onm = __builtin_amdgcn_ballot_w64(coded);
+            const U64 BPL = u_prev(BR, t), BNL = u_next(BL, t), sgNL = u_next(sgL, t);
+            enc_spp_first_half<0>(c, onm, BL, BR, BPL, BNL, sgL, sgR, sgNL, pl, prec, upper_mask);
+            enc_spp_first_half<1>(c, onm, BL, BR, BPL, BNL, sgL, sgR, sgNL, pl, prec, upper_mask);
+            AL = BL; AR = BR;
+            p0 = 1;
+        }
+    }
+    for (int p = p0; p < np; p++) {
         const int bp = msb - p;
         if (!BULK && p > 0) {
             // A codeblock that has used up its 4095 codeword slots ends as raw words whatever else is coded
@@ -1565,7 +1652,7 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
             // plane or two of a dozen; their waves were the tail of the whole launch.)
 #if PS_ENC_LDS
             wave_lds_done();
-            const uint32_t used = (*c.ldscnt - c.slot0) / kStageBytes;
+            const uint32_t used = (*c.ldscnt - (PEEL ? c.lim - kStageBytes * 4094u : c.slot0)) / kStageBytes;
 #else
             const uint32_t used = half ? c.cnt_hi : c.cnt_lo;
 #endif
@@ -1579,6 +1666,12 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
 
         const U64 BL = BLn, BR = BRn;
         const U64 AL2 = u_or(AL, BL), AR2 = u_or(AR, BR);            // state after this plane's SPP
+        if constexpr (PEEL) {
+            // The sign columns' shifted forms (up_of / dn_of below) are formed in every plane, one funnel shift each: hoisted
+            // out of the loop they are six registers the kernel does not have -- six spills ahead of the loop and six
+            // scratch loads in every plane.
+            opaque32(sgL.lo); opaque32(sgL.hi); opaque32(sgR.lo); opaque32(sgR.hi);
+        }
         {
             const U64 sgPL = u_prev(sgR, t), sgNL = u_next(sgL, t);  // neighbour sign columns
             const U64 APL = u_prev(AR, t), APL2 = u_prev(AR2, t);    // lane-1's right column
@@ -1707,13 +1800,21 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
         *reinterpret_cast<uint16_t *>(c.stw + sl) = (uint16_t)c.L;
     }
     wave_lds_done();                                       // every lane's last atomic has landed
-    const uint32_t cw_count = (*c.ldscnt - c.slot0) / kStageBytes;
+    const uint32_t cw_count = (*c.ldscnt - (PEEL ? c.lim - kStageBytes * 4094u : c.slot0)) / kStageBytes;
     const uint32_t size = (cw_count > 4095u ? 4095u : cw_count) + 1u;
 #else
     if (coded) *reinterpret_cast<uint16_t *>(c.stw + c.off) = (uint16_t)c.L;
     const uint32_t size = (half ? c.cnt_hi : c.cnt_lo) + 1u;
 #endif
-    if (valid && t == 0u) a.sizes[cb] = (int32_t)size;
+    // (PEEL: the lane's number within its half, its codeblock and that one's staging, formed again)
+    uint32_t te = t;
+    int cbe = cb;
+    uint16_t *ste = st;
+    if constexpr (PEEL) {
+        const uint32_t le = lane_number();
+        te = le & 31u; cbe = a.cb_base + 2 * wave + (int)(le >> 5); ste = stw + (size_t)(le >> 5) * 4096u;
+    }
+    if (valid && te == 0u) a.sizes[cbe] = (int32_t)size;
     // word 0 (the MSB) and expansionFix :1905-1912 (which overwrites the whole block) must land after every
     // codeword store of the block, the lanes' first-reservation stores to word 0 included
     wave_stores_issued();
@@ -1722,10 +1823,10 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
             uint32_t m0, m1, n0, n1;
             load_row(a, cbyte + (uint32_t)i * rstride, m0, m1, n0, n1);
             const uint32_t w0 = ((m0 << 1) + n0) & 0xFFFFu, w1 = ((m1 << 1) + n1) & 0xFFFFu;
-            *reinterpret_cast<uint32_t *>(st + t * 128u + 2u * (uint32_t)i) = w0 | (w1 << 16);
+            *reinterpret_cast<uint32_t *>(ste + te * 128u + 2u * (uint32_t)i) = w0 | (w1 << 16);
         }
-    } else if (valid && t == 0u) {
-        st[0] = (uint16_t)msb;
+    } else if (valid && te == 0u) {
+        ste[0] = (uint16_t)msb;
     }
 }
 
