@@ -1423,12 +1423,51 @@ __device__ __forceinline__ void bit_transpose_8x8x4(uint32_t (&x)[8])
 // after every load: the compiler does not unswitch the passes' loop, every load was waited for before the next one went
 // out, and the prologue of a lone frame was 64 round trips to the memory side one after the other.  As a template
 // parameter instead the six inlined variants cost the whole kernel its register allocation: 620 bytes of scratch.)
+//
+// The int16 array's rows on packed halves (PICSONG_ENC_PROLOGUE_PK16, default 1; 0 = unpacked to 32 bits like the other
+// modes): a row's dword is the lane's two coefficients, and nothing the pass wants of them needs 32 bits -- the
+// magnitudes are 0 - w and max as packed 16-bit operations (-32768 wraps to itself: 0x8000, magnitude 32768 read
+// unsigned, what the 32-bit form gives), their plane bytes are bytes 0 / 1 (left column) and 2 / 3 (right column) of the
+// packed word for the same four permutes, the OR of the magnitudes is folded over its halves once after the rows, and
+// the signs are bits 15 and 31 of the raw word, shifted down together and pushed into ONE accumulator per word of four
+// rows (left column's rows in byte 0, right column's in byte 2).  Five vector instructions a row instead of nine.
+#ifndef PICSONG_ENC_PROLOGUE_PK16
+#define PICSONG_ENC_PROLOGUE_PK16 1
+#endif
+// |lo half|, |hi half| of w, each in its half (two's complement wrap: 0x8000 stays 0x8000)
+__device__ __forceinline__ uint32_t pk_abs_i16(uint32_t w)
+{
+#if defined(__AMDGCN__)
+    typedef short pk_s16 __attribute__((ext_vector_type(2)));
+    const pk_s16 v = __builtin_bit_cast(pk_s16, w);
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(v, (pk_s16)(0) - v));
+#else
+    const uint32_t lo = w & 0xFFFFu, hi = w >> 16;
+    const uint32_t nl = (0u - lo) & 0xFFFFu, nh = (0u - hi) & 0xFFFFu;
+    return ((lo & 0x8000u) ? nl : lo) | (((hi & 0x8000u) ? nh : hi) << 16);
+#endif
+}
+// bit 15 of each half of w at bit 0 of that half
+__device__ __forceinline__ uint32_t pk_sign_i16(uint32_t w)
+{
+#if defined(__AMDGCN__)
+    typedef unsigned short pk_u16 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(pk_u16, w) >> (pk_u16)(15));
+#else
+    return (w >> 15) & 0x00010001u;
+#endif
+}
+
 template <int MODE>
 __device__ __forceinline__ void enc_transpose_pass(const BpcArgs &a, int pass, uint32_t cbyte, uint32_t rstride,
                                                    uint32_t *pscr, uint32_t &ormag, U64 &sgL, U64 &sgR)
 {
+    constexpr bool PK16 = MODE == 2 && PICSONG_ENC_PROLOGUE_PK16 != 0;
     // byte `pass` of a magnitude: the lower / upper pair of a word's four rows
     const uint32_t sel_lo = pass == 0 ? 0x0c0c0400u : 0x0c0c0501u, sel_hi = pass == 0 ? 0x04000c0cu : 0x05010c0cu;
+    // (PK16: the same byte of the packed word's upper half, the right column's magnitude)
+    const uint32_t sel_lo_r = pass == 0 ? 0x0c0c0602u : 0x0c0c0703u, sel_hi_r = pass == 0 ? 0x06020c0cu : 0x07030c0cu;
+    uint32_t orpk = 0u;                                      // (PK16: the OR of the packed magnitudes)
     // (the two 32-row halves are a LOOP, not two copies: unrolled, the scheduler let the second half's loads run into the
     // first half's tail and the kernel carried 76 spilled dwords through its prologue -- 19 KB of private scratch a wave,
     // all of it L2 traffic; as a loop 26 dwords, the last group's loads go out together like the others, the coder's
@@ -1441,24 +1480,43 @@ __device__ __forceinline__ void enc_transpose_pass(const BpcArgs &a, int pass, u
 #pragma unroll
         for (int j = 7; j >= 0; j--) {                       // (descending: a row's sign is pushed in below the later rows')
             uint32_t m0[4], m1[4];
+            if constexpr (PK16) {
 #pragma unroll
-            for (int b = 0; b < 4; b++) {
-                int32_t v0, v1;
-                load_row_raw<MODE>(a, roff + (uint32_t)(8 * b) * rstride, v0, v1);
-                m0[b] = (uint32_t)(v0 < 0 ? -v0 : v0); m1[b] = (uint32_t)(v1 < 0 ? -v1 : v1);
-                ormag |= m0[b] | m1[b];
-                // acc = (acc << 1) | sign: one funnel shift; rows 8 b + 7 .. 8 b in turn leave row 8 b + j at bit j
-                sa0[b] = __builtin_amdgcn_alignbit(sa0[b], (uint32_t)v0, 31u);
-                sa1[b] = __builtin_amdgcn_alignbit(sa1[b], (uint32_t)v1, 31u);
+                for (int b = 0; b < 4; b++) {
+                    const uint32_t w = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(a.coeffs_in)
+                                                                           + (size_t)(roff + (uint32_t)(8 * b) * rstride));
+                    m0[b] = pk_abs_i16(w);
+                    orpk |= m0[b];
+                    // both columns' signs in one accumulator: row 8 b + j at bit j (left) and bit 16 + j (right)
+                    sa0[b] = (sa0[b] << 1) | pk_sign_i16(w);
+                }
+                roff -= rstride;
+                B0[j] = __builtin_amdgcn_perm(m0[1], m0[0], sel_lo) | __builtin_amdgcn_perm(m0[3], m0[2], sel_hi);
+                B1[j] = __builtin_amdgcn_perm(m0[1], m0[0], sel_lo_r) | __builtin_amdgcn_perm(m0[3], m0[2], sel_hi_r);
+            } else {
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    int32_t v0, v1;
+                    load_row_raw<MODE>(a, roff + (uint32_t)(8 * b) * rstride, v0, v1);
+                    m0[b] = (uint32_t)(v0 < 0 ? -v0 : v0); m1[b] = (uint32_t)(v1 < 0 ? -v1 : v1);
+                    ormag |= m0[b] | m1[b];
+                    // acc = (acc << 1) | sign: one funnel shift; rows 8 b + 7 .. 8 b in turn leave row 8 b + j at bit j
+                    sa0[b] = __builtin_amdgcn_alignbit(sa0[b], (uint32_t)v0, 31u);
+                    sa1[b] = __builtin_amdgcn_alignbit(sa1[b], (uint32_t)v1, 31u);
+                }
+                roff -= rstride;
+                B0[j] = __builtin_amdgcn_perm(m0[1], m0[0], sel_lo) | __builtin_amdgcn_perm(m0[3], m0[2], sel_hi);
+                B1[j] = __builtin_amdgcn_perm(m1[1], m1[0], sel_lo) | __builtin_amdgcn_perm(m1[3], m1[2], sel_hi);
             }
-            roff -= rstride;
-            B0[j] = __builtin_amdgcn_perm(m0[1], m0[0], sel_lo) | __builtin_amdgcn_perm(m0[3], m0[2], sel_hi);
-            B1[j] = __builtin_amdgcn_perm(m1[1], m1[0], sel_lo) | __builtin_amdgcn_perm(m1[3], m1[2], sel_hi);
             // eight rows (16 registers) in flight, not all 32: the loop is unrolled for its constant word indices,
             // and the scheduler would otherwise hoist every load to the top and spill
             if ((j & 1) == 0) sched_fence();
         }
-        {
+        if constexpr (PK16) {                               // bytes 0 (left) / 2 (right) of the four accumulators
+            const uint32_t s0 = __builtin_amdgcn_perm(sa0[1], sa0[0], 0x0c0c0400u) | __builtin_amdgcn_perm(sa0[3], sa0[2], 0x04000c0cu);
+            const uint32_t s1 = __builtin_amdgcn_perm(sa0[1], sa0[0], 0x0c0c0602u) | __builtin_amdgcn_perm(sa0[3], sa0[2], 0x06020c0cu);
+            if (hw == 0) { sgL.lo = s0; sgR.lo = s1; } else { sgL.hi = s0; sgR.hi = s1; }
+        } else {
             const uint32_t s0 = sa0[0] | (sa0[1] << 8) | (sa0[2] << 16) | (sa0[3] << 24);
             const uint32_t s1 = sa1[0] | (sa1[1] << 8) | (sa1[2] << 16) | (sa1[3] << 24);
             if (hw == 0) { sgL.lo = s0; sgR.lo = s1; } else { sgL.hi = s0; sgR.hi = s1; }
@@ -1469,6 +1527,7 @@ __device__ __forceinline__ void enc_transpose_pass(const BpcArgs &a, int pass, u
 #pragma unroll
         for (int k = 0; k < kEncPassPlanes; k++) { q[k * kEncPlaneDwords] = B0[k]; q[k * kEncPlaneDwords + 128] = B1[k]; }
     }
+    if constexpr (PK16) ormag |= (orpk & 0xFFFFu) | (orpk >> 16);
 }
 
 // (Round 3 tried the scan of a frame's codeblock lengths by the LAST wave of the launch to finish -- sizes stored with

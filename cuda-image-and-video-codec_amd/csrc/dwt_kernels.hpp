@@ -728,6 +728,24 @@ constexpr int kF2Useful = kStripCols - 8 * kF2Edge;          // 232 columns writ
 #ifndef PICSONG_DWT_F2_WAVES_LOSSY
 #define PICSONG_DWT_F2_WAVES_LOSSY PICSONG_DWT_F2_WAVES
 #endif
+// the 5/3 head's interior strips without edge selects (dwt_fwd2_kernel); 0 = every strip through the EDGE instantiation
+#ifndef PICSONG_DWT_F2_EDGE53
+#define PICSONG_DWT_F2_EDGE53 1
+#endif
+// the 5/3 int16 head of a call that carries more than one frame (grid.z > 1): level-1 row pairs per band.  Two of a
+// band's NB + 2 iterations are run-in, recomputed arithmetic and re-read rows: 20 % at 8, 11 % at 16.  A band longer than
+// kF2Pairs keeps only PICSONG_DWT_F2_AHEAD iterations' raw rows in flight (the RGB head's ring), not the whole band's.
+// A lone frame keeps kF2Pairs: its head is bound by latency and HBM, and half as many waves fill the GPU worse.
+// = PICSONG_DWT_F2_PAIRS: no instantiation of its own.  That is the DEFAULT: 16 is built and bit-identical on the
+// emulator (tests/test_fwd2_interior.py compiles its driver with it: 49 registers, no scratch), but has not been
+// timed against 8 on the GPU yet, and longer bands lost for a lone frame (round 2, below); profiles/NOTES.md.
+#ifndef PICSONG_DWT_F2_PAIRS_BATCH
+#define PICSONG_DWT_F2_PAIRS_BATCH 8
+#endif
+#ifndef PICSONG_DWT_F2_AHEAD
+#define PICSONG_DWT_F2_AHEAD 3
+#endif
+constexpr int kF2PairsBatch = PICSONG_DWT_F2_PAIRS_BATCH, kF2Ahead = PICSONG_DWT_F2_AHEAD;
 constexpr int kF2Pairs = PICSONG_DWT_F2_PAIRS, kF2PairsLossy = PICSONG_DWT_F2_PAIRS_LOSSY;
 struct DwtFwd2Args { DwtFwdArgs l0, l1; };
 
@@ -895,7 +913,9 @@ __device__ __forceinline__ void dwt_fwd2_band(const DwtFwdArgs &a, const DwtFwdA
     // RGB: the rows of all three planes -- three times the registers -- so only kF2RgbAhead iterations' rows are in
     // flight, the rows of iteration i + kF2RgbAhead going out in iteration i BEFORE its stores (the synthesis kernels'
     // scheme): 36 raw registers instead of 3 x 4 x kIters, which is what lets that form run whole 32-row bands too.
-    constexpr int kRing = RGB ? (kF2RgbAhead < kIters ? kF2RgbAhead : kIters) : kIters;
+    // (likewise the 5/3 bands longer than kF2Pairs, the batched calls' kF2PairsBatch: kF2Ahead iterations' rows)
+    constexpr int kAhead = RGB ? kF2RgbAhead : (!LOSSY && NB > kF2Pairs ? kF2Ahead : kIters);
+    constexpr int kRing = kAhead < kIters ? kAhead : kIters;
     RawRow<true> r0, raw[kRing][4];
     uint32_t g0 = 0u, b0 = 0u, rawG[RGB ? kRing : 1][4], rawB[RGB ? kRing : 1][4];
     const RowBuf ing = rowbuf(RGB ? a.src_g : a.src), inb = rowbuf(RGB ? a.src_b : a.src);
@@ -938,7 +958,7 @@ __device__ __forceinline__ void dwt_fwd2_band(const DwtFwdArgs &a, const DwtFwdA
             if constexpr (RGB) unpack_rgb(raw[i % kRing][q].w, rawG[i % kRing][q], rawB[i % kRing][q], x[q]);
             else unpack_row<T, true>(raw[i % kRing][q], x[q]);
         }
-        if (i + kRing < kIters) load_iter(i + kRing);        // (RGB only: the ring's next rows, ahead of this iteration's stores)
+        if (i + kRing < kIters) load_iter(i + kRing);        // (ringed bands only: the ring's next rows, ahead of this iteration's stores)
         const int rel = 2 * i - kRel0;                       // (compile-time after unrolling)
         T LA[4], HA[4], LB[4], HB[4];
         vstep<T, LOSSY, 4>(xe, st0, x[0], x[1], LA, HA);
@@ -1041,12 +1061,16 @@ __global__ __launch_bounds__(256, RGB ? PICSONG_DWT_F2_RGB_WAVES : (LOSSY ? PICS
     dwt_fwd_select_frame(a2.l1, bz);
     // the wave's 256 columns start at strip * kF2Useful - 4 * kF2Edge: does it hold column 0 or W - 4?
     const int first = strip * kF2Useful - 4 * kF2Edge;
-    // (only the 9/7 kernel, which is bound by vector instructions, gets the second instantiation)
+    // The second instantiation, for the strips that hold neither: no mirror selects, and the neighbour reads fold into
+    // the additions.  The 9/7 kernel always had it; the 5/3 one (PICSONG_DWT_F2_EDGE53, 0 = one instantiation) has it
+    // because frames in flight are bound by vector-instruction issue across all of their kernels, so the head's
+    // instructions compete with the coder's (a lone head is HBM-bound and does not care).  The RGB 5/3 head keeps one.
+    constexpr bool kInterior = LOSSY || (PICSONG_DWT_F2_EDGE53 != 0 && !RGB);
     static_assert(U8IN, "the fused head ingests u8 frames");
     if (strip * kF2Useful >= a2.l0.W) return;               // whole wave idle (no cross-lane use)
-    if (!LOSSY || first <= 0 || first + kStripCols >= a2.l0.W)
+    if (!kInterior || first <= 0 || first + kStripCols >= a2.l0.W)
         dwt_fwd2_band<T, LOSSY, NB, true, C16, RGB>(a2.l0, a2.l1, strip, lane, by, bz);
-    else dwt_fwd2_band<T, LOSSY, NB, LOSSY ? false : true, C16, RGB>(a2.l0, a2.l1, strip, lane, by, bz);
+    else dwt_fwd2_band<T, LOSSY, NB, !kInterior, C16, RGB>(a2.l0, a2.l1, strip, lane, by, bz);
 }
 
 // ---- the small levels of the forward transform ---------------------------------------------------------

@@ -48,8 +48,10 @@ inline FwdKernel select_fwd(bool lossy, const FwdLaunch &f)
 // ---- the fused forward head, levels 0 and 1 (256 threads, grid f2.gx x f2.gy x frames)
 // c16: coded subbands as int16 (DwtFwdArgs::c16); rgb: the colour transform in the load stage, grid.z = component
 // (RCT on the integer head, ICT on the 9/7 one; plan_dwt_fwd2 with kF2PairsRgb, always 16-bit)
-inline Fwd2Kernel select_fwd2(bool lossy, bool c16, bool rgb = false)
+// nb: the plan's nb_override (f2_pairs_batched: the 5/3 int16 head's longer bands for calls of several frames)
+inline Fwd2Kernel select_fwd2(bool lossy, bool c16, bool rgb = false, int nb = 0)
 {
+    if (nb == kF2PairsBatch && !lossy && c16 && !rgb) return dwt_fwd2_kernel<int, false, true, kF2PairsBatch, true>;
     if (rgb) return lossy ? dwt_fwd2_kernel<float, true, true, kF2PairsRgb, true, true> : dwt_fwd2_kernel<int, false, true, kF2PairsRgb, true, true>;
     if (c16) return lossy ? dwt_fwd2_kernel<float, true, true, kF2PairsLossy, true> : dwt_fwd2_kernel<int, false, true, kF2Pairs, true>;
     return lossy ? dwt_fwd2_kernel<float, true, true, kF2PairsLossy> : dwt_fwd2_kernel<int, false, true, kF2Pairs>;

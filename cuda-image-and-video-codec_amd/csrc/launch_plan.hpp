@@ -238,6 +238,14 @@ inline bool plan_dwt_fwd2(const std::vector<FwdLaunch> &plan, Fwd2Launch &f, boo
     return true;
 }
 
+// nb_override of a call that carries `frames` frames: the 5/3 int16 head's longer bands (kF2PairsBatch) where a call has
+// more than one frame and the level-1 row pairs are whole bands of that length; 0 = the transform's own band length
+inline int f2_pairs_batched(const std::vector<FwdLaunch> &plan, bool lossy, unsigned frames)
+{
+    if (lossy || frames < 2 || kF2PairsBatch == kF2Pairs || !plan_is_c16(plan)) return 0;
+    return ((plan[0].a.H >> 2) % kF2PairsBatch) == 0 ? kF2PairsBatch : 0;
+}
+
 // the 16-bit form exists in the vector-only kernel instantiations: every level of the frame on the vector path
 // (lo > 0: a reduced-resolution decode, which runs the synthesis levels lo .. wl - 1 only)
 inline bool dwt_c16_geometry_ok(int aw, int ah, int wl, int lo = 0)

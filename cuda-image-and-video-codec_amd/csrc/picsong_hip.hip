@@ -123,9 +123,10 @@ static int launch_fwd_plan(const picsong_ctx *c, const std::vector<FwdLaunch> &p
 {
     const bool lossy = c->p.lossy != 0;
     Fwd2Launch f2;
-    const bool fused01 = plan_dwt_fwd2(plan, f2, true, lossy);
+    const int nb = f2_pairs_batched(plan, lossy, frames);
+    const bool fused01 = plan_dwt_fwd2(plan, f2, true, lossy, nb);
     if (fused01) {
-        select_fwd2(lossy, f2.a.l0.c16 != 0)<<<dim3(f2.gx, f2.gy, frames), 256, 0, s>>>(f2.a);
+        select_fwd2(lossy, f2.a.l0.c16 != 0, false, nb)<<<dim3(f2.gx, f2.gy, frames), 256, 0, s>>>(f2.a);
         HIP_TRY(hipGetLastError());
     }
     return launch_fwd_levels(c, plan, fused01 ? 2 : 0, s, frames);
