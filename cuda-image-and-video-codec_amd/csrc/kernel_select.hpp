@@ -1,7 +1,9 @@
 // kernel_select.hpp -- which template instantiation of a kernel a planned launch takes, with its grid and its scratch
 // (pure host code, no device code: functions from a plan's fields or a coder's mode flags to a kernel function pointer).
-// The one copy of that policy: the C-ABI implementation (picsong_hip.hip) writes select_x(...)<<<grid, block, 0, s>>>(args),
-// the CPU wave-emulator drivers (tests/hipemu/) emu::launch(grid, block, [&] { k(args); }) on the same pointer.
+// The one copy of that policy.  Its callers are the launch sequences of launch_seq.hpp, which the C-ABI implementation
+// (picsong_hip.hip) and the CPU wave-emulator drivers (tests/hipemu/) both run, each through its own launcher; a single
+// launch whose arguments come from a helper here (select_stats / stats_args, select_quantise / quantise_args) goes
+// through that launcher directly.
 // What the environment says arrives as a parameter (lean97, the coders' `compact`): each caller reads its switches at
 // the moment it always did.
 #pragma once
@@ -179,6 +181,9 @@ inline BpcLaunch select_decoder(bool cp3, bool bulk, bool compact, bool from_str
     if (from_stream) return bpc_launch(bpc_decode_kernel<false, kDecSmallPlanes, true>, kBpcDecWgWaves, waves);
     return bpc_launch(bpc_decode_kernel<false, kDecSmallPlanes>, kBpcDecWgWaves, waves);
 }
+// the dwords of plane scratch a coder launch of `waves` waves needs (what a caller sizes BpcArgs::plane_scratch by)
+inline size_t encoder_scratch_dwords(bool cp3, bool bulk, unsigned waves) { return select_encoder(cp3, bulk, false, waves).scratch_dwords; }
+inline size_t decoder_scratch_dwords(bool cp3, bool bulk, unsigned waves) { return select_decoder(cp3, bulk, false, false, false, waves).scratch_dwords; }
 
 // ---- helpers of both sides
 // geo: the nine fields in LutGeo's order (the emulator's entry points take them so)

@@ -1,6 +1,6 @@
 // launch_plan.hpp -- host-side launch geometry for the per-level DWT kernels (pure host code,
 // shared by the C-ABI implementation and by the CPU wave-emulator tests so both walk the levels
-// the same way).  Level order and scratch offsets follow DWTEngine::DWTForward / DWTReverse
+// the same way; launch_seq.hpp launches the plans).  Level order and scratch offsets follow DWTEngine::DWTForward / DWTReverse
 // (reference DWT/DWTGenerator.cu:1268-1424).
 #pragma once
 #include <stddef.h>
@@ -336,6 +336,48 @@ inline std::vector<InvLaunch> plan_dwt_inverse_reduced(const int32_t *d_in, void
     for (const InvLaunch &f : v) all_vec = all_vec && f.vec;
     for (InvLaunch &f : v) f.a.c16 = c16 && all_vec ? 1 : 0;
     return v;
+}
+
+// The Mallat work buffer's elements beyond the frame's P: the LL arrays of levels 1 .. wl - 1 (picsong_dwt_extra)
+inline size_t dwt_extra(int aw, int ah, int wl)
+{
+    size_t e = 0;
+    for (int l = 1; l < wl; l++) e += (size_t)(aw >> l) * (size_t)(ah >> l);
+    return e;
+}
+
+// The frame paths' synthesis plan.  d_pixels != nullptr: the finest level writes clamped u8 pixels there (level shift
+// `off` + clamp fused, when its vector kernel applies) instead of T samples into d_out; *fused says so.
+// frames > 1 (picsong_decode_frames): grid.z = frame; frame z's coded coefficients at d_in + z * P coefficients, its
+// work buffer at d_out + z * (P + extra) elements, its pixels at d_pixels + z * pix_stride bytes.
+// want_c16: the decoder may write 16-bit coefficients (picsong_ctx::c16_dec) -- the plan says whether this call's
+// pointers allow it (plan_inv_is_c16), BEFORE the decoder is launched: this plan, then the decoder, then run_inverse.
+// (the grey frame paths take the 16-bit form only with the fused pixel store; planes_out: an RGB frame's components,
+// whose finest level writes T samples for the inverse colour transform, take it too)
+// reduce > 0: the levels wl - 1 .. reduce only (plan_dwt_inverse_reduced), level `reduce` the one that writes the pixels
+inline std::vector<InvLaunch> plan_inverse_frames(const int32_t *d_in, void *d_out, uint8_t *d_pixels, bool *fused, unsigned frames,
+                                                  size_t pix_stride, bool want_c16, bool planes_out, int reduce, int aw, int ah,
+                                                  int wl, float qs, bool fast_div, int off, size_t P, size_t extra)
+{
+    if (fused) *fused = false;
+    const bool px = d_pixels && (((uintptr_t)d_pixels) & 3u) == 0 && (pix_stride & 3u) == 0;
+    std::vector<InvLaunch> plan = plan_dwt_inverse_reduced(d_in, d_out, aw, ah, wl, qs, fast_div, want_c16 && (px || planes_out), reduce);
+    if (px && !plan.empty() && plan.back().vec) {
+        plan.back().a.dst_u8 = d_pixels;
+        plan.back().a.off = off;
+        if (fused) *fused = true;
+    }
+    if (frames > 1) {
+        const unsigned long long in_z = (unsigned long long)P * (plan_inv_is_c16(plan) ? 2ull : 4ull);
+        const unsigned long long wrk_z = (unsigned long long)(P + extra) * 4ull;
+        for (InvLaunch &f : plan) {
+            f.a.mallat_z = in_z;
+            f.a.ll_z = f.a.first ? in_z : wrk_z;            // the coarsest level's LL comes from the coded array
+            f.a.dst_z = wrk_z;
+            f.a.u8_z = (unsigned long long)pix_stride;
+        }
+    }
+    return plan;
 }
 
 // ---- window decode (picsong_decode_frame_window and its mirrors; no reference counterpart).  The window R_r =

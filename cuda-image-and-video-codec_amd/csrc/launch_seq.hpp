@@ -1,0 +1,259 @@
+// launch_seq.hpp -- the launch sequences of the frame pipeline (pure host code): which kernels a call launches, in what
+// order, with what arguments wired between them, and which fused form it takes.  The one copy: the C-ABI implementation
+// (picsong_hip.hip) and the CPU wave-emulator drivers (tests/hipemu/) both run these, each through its launcher
+//     go(kernel, dim3 grid, unsigned threads, args...) -> int, 0 = ok
+// -- the library's holds the stream and does kernel<<<grid, threads, 0, s>>>(args...), the emulator's emu::launch.
+// A sequence takes plain values (geometry, plans, pointers, booleans), never a context; what the environment says
+// arrives as a parameter (kernel_select.hpp), read by each caller where and when it always was -- and the callers
+// differ, on purpose left so: the library reads PICSONG_DWT_INV97 once per process for the synthesis levels
+// (lean97_levels) but per call, with PICSONG_RGB_NOFUSE, for the RGB tail (decode_rgb_impl); emu_driver.cpp reads it
+// at every call (emu_lean97: the tests flip it); emu_decode_reduced passes a constant true; and emu_fast_div
+// re-derives per (qs, wl) what a context stores at its creation.
+#pragma once
+#include "kernel_select.hpp"
+
+namespace picsong {
+
+// A workspace of the frame pipeline.  The context keeps two: a single frame's, and a batch's with every array n times
+// as long, frame after frame; the drivers fill one with pointers into their own arrays.
+struct Workspace {
+    void *coef;               // T[P + extra]: the transform's work buffer
+    int32_t *staging;         // int32[P] (the encoders' 16-bit staging lives in it too)
+    int32_t *sizes;           // int32[nCB]
+    int32_t *offsets;         // int32[nCB]
+    int32_t *total;           // 1
+    uint32_t *plane_scratch;  // the coders' bit-planes below the 8 held in registers, 8 KB per wave
+    int32_t *coef_i;          // int32[P]: decoded coefficients
+};
+
+// ---- element-wise kernels: n4 groups of four samples (level_shift_inv: n samples), `off` the level shift
+template <class Go>
+int level_shift_fwd(const Go &go, bool lossy, const uint8_t *in, void *out, size_t n4, int off)
+{
+    const dim3 grid(elementwise_blocks(n4, 4096));
+    return lossy ? go(level_shift_fwd_kernel<float>, grid, 256u, in, (float *)out, n4, off)
+                 : go(level_shift_fwd_kernel<int32_t>, grid, 256u, in, (int32_t *)out, n4, off);
+}
+template <class Go>
+int level_shift_inv(const Go &go, bool lossy, void *data, size_t n, int off)
+{
+    const dim3 grid(elementwise_blocks(n));
+    return lossy ? go(level_shift_inv_f32_kernel, grid, 256u, (float *)data, n, (float)off)
+                 : go(level_shift_inv_i32_kernel, grid, 256u, (int32_t *)data, n, off);
+}
+// samples of a synthesis that did not write its pixels itself: level shift + clamp
+template <class Go>
+int clamp_pixels(const Go &go, bool lossy, const void *img, uint8_t *out, size_t n4, int off)
+{
+    const dim3 grid(elementwise_blocks(n4));
+    return lossy ? go(clamp_to_u8_f32_kernel, grid, 256u, (const float *)img, out, n4, (float)off)
+                 : go(clamp_to_u8_i32_kernel, grid, 256u, (const int32_t *)img, out, n4, off);
+}
+template <class Go>
+int rgb_forward(const Go &go, bool lossy, const uint8_t *r, const uint8_t *g, const uint8_t *b, void *c0, void *c1, void *c2,
+                size_t n4, int off)
+{
+    const dim3 grid(elementwise_blocks(n4));
+    return lossy ? go(rgb_forward_kernel<float>, grid, 256u, r, g, b, (float *)c0, (float *)c1, (float *)c2, n4, off)
+                 : go(rgb_forward_kernel<int32_t>, grid, 256u, r, g, b, (int32_t *)c0, (int32_t *)c1, (int32_t *)c2, n4, off);
+}
+template <class Go>
+int rgb_inverse(const Go &go, bool lossy, const void *c0, const void *c1, const void *c2, uint8_t *r, uint8_t *g, uint8_t *b,
+                size_t n4, int off)
+{
+    const dim3 grid(elementwise_blocks(n4));
+    return lossy ? go(rgb_inverse_kernel<float>, grid, 256u, (const float *)c0, (const float *)c1, (const float *)c2, r, g, b, n4, off)
+                 : go(rgb_inverse_kernel<int32_t>, grid, 256u, (const int32_t *)c0, (const int32_t *)c1, (const int32_t *)c2, r, g, b, n4, off);
+}
+
+// ---- forward transform.  Levels [from, end) of a plan, one launch each; `frames` = grid.z of a batched call.
+template <class Go>
+int launch_fwd_levels(const Go &go, bool lossy, const std::vector<FwdLaunch> &plan, size_t from, unsigned frames = 1)
+{
+    for (size_t l = from; l < plan.size(); l++) {
+        const FwdLaunch &f = plan[l];
+        if (int rc = go(select_fwd(lossy, f), dim3(f.gx, f.gy, frames), 256u, f.a)) return rc;
+    }
+    return 0;
+}
+// A forward plan, levels 0 and 1 in one launch where plan_dwt_fwd2 allows it (LL1 stays in registers); *fused01 says so
+template <class Go>
+int launch_fwd_plan(const Go &go, bool lossy, const std::vector<FwdLaunch> &plan, unsigned frames = 1, bool *fused01 = nullptr)
+{
+    Fwd2Launch f2;
+    const int nb = f2_pairs_batched(plan, lossy, frames);
+    const bool fused = plan_dwt_fwd2(plan, f2, true, lossy, nb);
+    if (fused01) *fused01 = fused;
+    if (fused)
+        if (int rc = go(select_fwd2(lossy, f2.a.l0.c16 != 0, false, nb), dim3(f2.gx, f2.gy, frames), 256u, f2.a)) return rc;
+    return launch_fwd_levels(go, lossy, plan, fused ? 2 : 0, frames);
+}
+// a batched forward plan: level 0 reads frame z at + z * src_z0 bytes, every level works in frame z's buffer of coef_z bytes
+inline void plan_frame_strides(std::vector<FwdLaunch> &plan, unsigned long long src_z0, unsigned long long coef_z)
+{
+    for (size_t l = 0; l < plan.size(); l++) {
+        plan[l].a.src_z = l == 0 ? src_z0 : coef_z;
+        plan[l].a.dst_z = coef_z;
+    }
+}
+// An RGB frame's colour transform (level shift fused) and the forward transform of its three components, component k's
+// coefficients coef_z bytes after component k - 1's.  plan_of(src, u8in) makes the caller's plan: plan_dwt_forward with
+// its c16 choice (head_c16: the fused head is the frame paths' 16-bit one and wants such a plan) or the rate calls'
+// plan_dwt_forward_unit (the 32-bit float head, select_fwd2_rgb_f32).
+// fuse (the caller's switches: planes 16-byte aligned, no PICSONG_RGB_NOFUSE, its c16 choice): the colour transform in
+// the head's load stage -- the head reads the three u8 planes and delivers component blockIdx.z, no component plane is
+// ever written (the separate transform kernel reads 100 MB and writes 400 MB of them per 8K frame, and level 0 reads
+// them back).  Else, or where plan_dwt_fwd2 refuses: the colour transform into `planes` (three of P samples), then the
+// levels of all three per launch.  *c16: the coefficient form delivered; *fused: the first form ran.
+template <class Go, class PlanOf>
+int rgb_forward_transform(const Go &go, bool lossy, bool fuse, PlanOf plan_of, bool head_c16, const uint8_t *r, const uint8_t *g,
+                          const uint8_t *b, void *planes, size_t P, int off, unsigned long long coef_z, bool *c16 = nullptr,
+                          bool *fused = nullptr)
+{
+    if (fused) *fused = false;
+    if (fuse) {
+        std::vector<FwdLaunch> plan = plan_of(r, true);
+        plan_frame_strides(plan, 0, coef_z);                 // level 0: every component reads the three planes
+        plan[0].a.src_g = g; plan[0].a.src_b = b;
+        Fwd2Launch f2;
+        if (plan_is_c16(plan) == head_c16 && plan_dwt_fwd2(plan, f2, true, lossy, kF2PairsRgb)) {
+            // (RCT on the integer head, ICT on the 9/7 ones)
+            if (int rc = go(head_c16 ? select_fwd2(lossy, true, true) : select_fwd2_rgb_f32(), dim3(f2.gx, f2.gy, 3u), 256u, f2.a)) return rc;
+            if (c16) *c16 = head_c16;
+            if (fused) *fused = true;
+            return launch_fwd_levels(go, lossy, plan, 2, 3u);
+        }
+    }
+    char *p = (char *)planes;
+    if (int rc = rgb_forward(go, lossy, r, g, b, p, p + P * 4, p + 2 * P * 4, P / 4, off)) return rc;
+    std::vector<FwdLaunch> plan = plan_of(planes, false);
+    if (c16) *c16 = plan_is_c16(plan);
+    plan_frame_strides(plan, (unsigned long long)P * 4ull, coef_z);
+    return launch_fwd_levels(go, lossy, plan, 0, 3u);
+}
+
+// ---- synthesis.  The first n levels of a plan (plan_inverse_frames), one launch each
+template <class Go>
+int launch_inv_levels(const Go &go, bool lossy, bool lean97, const std::vector<InvLaunch> &plan, size_t n, unsigned frames)
+{
+    for (size_t l = 0; l < n; l++) {
+        const InvLaunch &f = plan[l];
+        if (int rc = go(select_inv(lossy, lean97, f), dim3(f.gx, f.gy, frames), 256u, f.a)) return rc;
+    }
+    return 0;
+}
+// A synthesis plan; 16-bit coefficients in, pixels out: levels 1 and 0 as one launch (dwt_inv2_kernel), LL0 in
+// registers, where plan_dwt_inv2 allows it -- *fused10 says so
+template <class Go>
+int run_inverse(const Go &go, bool lossy, bool lean97, const std::vector<InvLaunch> &plan, unsigned frames = 1, bool *fused10 = nullptr)
+{
+    Inv2Launch f2;
+    const bool fused = plan_dwt_inv2(plan, f2, lossy);
+    if (fused10) *fused10 = fused;
+    if (int rc = launch_inv_levels(go, lossy, lean97, plan, fused ? plan.size() - 2 : plan.size(), frames)) return rc;
+    return fused ? go(select_inv2(lossy, f2.a.l0.one_div != 0), dim3(f2.gx, f2.gy, frames), 256u, f2.a) : 0;
+}
+// An RGB frame's synthesis with 16-bit coefficients (plan_inverse_frames over three components, planes_out): the levels
+// above the finest, then the finest level of the three components and the inverse colour transform as ONE launch
+// (select_inv_rgb).  5/3: the 32-bit planes are never written (dwt_inv_rgb_kernel).  9/7, the lean kernel's domain: the
+// three components as the three waves of a workgroup, a row pair exchanged through LDS, the inverse ICT at the stores
+// (dwt_inv97_rgb_kernel).  inv_rgb_tail_ok: may the plan take that form?  (9/7: the caller's lean97 switch permitting)
+inline bool inv_rgb_tail_ok(const std::vector<InvLaunch> &plan, bool lossy)
+{
+    return plan_inv_is_c16(plan) && plan.size() >= 2 && plan.back().vec && (!lossy || plan.back().fast);
+}
+template <class Go>
+int run_inverse_rgb(const Go &go, bool lossy, bool lean97, const std::vector<InvLaunch> &plan, int off, uint8_t *r, uint8_t *g, uint8_t *b)
+{
+    if (int rc = launch_inv_levels(go, lossy, lean97, plan, plan.size() - 1, 3u)) return rc;
+    DwtInvArgs fa = plan.back().a;
+    fa.off = off;
+    const InvRgbLaunch l = select_inv_rgb(lossy, plan.back());
+    return go(l.kernel, dim3(l.gx, l.gy, 1), l.threads, fa, r, g, b);
+}
+
+// ---- the windowed synthesis (window_kernels.hpp) of `frames` frames, grid.z = frame: frame z's coefficients at coef_i +
+// z * coef_z bytes, its scratch (T[P + extra]) at work + z * work_z bytes.  u8 != nullptr: level r writes frame z's
+// window at u8 + z * u8_z, row stride pitch; else level r's samples stay at frame z's `work` (compact, row stride w).
+template <class Go>
+int run_window(const Go &go, bool lossy, const WindowPlan &w, const int32_t *coef_i, void *work, size_t P, int aw, int ah, float qs,
+               int off, unsigned frames, unsigned long long coef_z, unsigned long long work_z, uint8_t *u8, size_t pitch,
+               unsigned long long u8_z)
+{
+    for (WinLaunch &f : plan_window_synthesis(w, coef_i, work, P, aw, ah, qs, u8, pitch, off)) {
+        f.a.mallat_z = coef_z; f.a.ll_z = work_z; f.a.dst_z = work_z; f.a.u8_z = u8_z;
+        f.grid.z = frames;
+        if (int rc = go(select_window(lossy, f.u8), f.grid, 256u, f.a)) return rc;
+    }
+    return 0;
+}
+// its RGB epilogue: the inverse RCT / ICT over the w x h window of three components z bytes apart at `work`
+template <class Go>
+int window_rgb(const Go &go, bool lossy, const void *work, unsigned long long z, int w, int h, uint8_t *r, uint8_t *g, uint8_t *b,
+               size_t pitch, int off)
+{
+    const dim3 grid((unsigned)((w + 255) / 256), (unsigned)h);
+    return lossy ? go(window_rgb_kernel<float>, grid, 256u, (const float *)work, z, w, h, r, g, b, pitch, off)
+                 : go(window_rgb_kernel<int>, grid, 256u, (const int *)work, z, w, h, r, g, b, pitch, off);
+}
+
+// ---- stream intake: the codeblock lengths of n streams `stride` shorts apart into w.sizes, their scan into w.offsets
+// and w.total -- `direct`, one launch, for a decoder that reads the streams itself; else the codewords unpacked into
+// w.staging (frame f's at + f * P words) as well (-k > 0 through the staging, -cp 3, PICSONG_DEC_STAGING)
+template <class Go>
+int stream_intake(const Go &go, const uint16_t *streams, unsigned n, size_t stride, bool direct, int ncb, size_t P,
+                  const Workspace &w, int *flag)
+{
+    if (direct) return go(scan_stream_kernel, dim3(n), scan_threads(ncb), streams, ncb, w.sizes, w.offsets, w.total, flag, stride);
+    if (int rc = go(read_sizes_kernel, dim3((unsigned)((ncb + 255) / 256), n), 256u, streams, ncb, w.sizes, flag, stride)) return rc;
+    if (int rc = go(scan_sizes_kernel, dim3(n), scan_threads(ncb), w.sizes, ncb, w.offsets, w.total)) return rc;
+    return go(unpack_kernel, dim3((unsigned)ncb, n), 256u, streams, w.sizes, w.offsets, ncb, w.staging, stride, P);
+}
+
+// ---- the coders.  kLaunchRefused: no kernel exists for what the caller asks (nothing launched)
+constexpr int kLaunchRefused = -1000;
+// The decoder launch of every path: `waves` waves over w's sizes, staging and plane scratch, coefficients into w.coef_i.
+// streams != nullptr (k = 0 or -k > 0, -cp 2): the codewords come from the packed streams, `stride` shorts apart and at
+// most cw16_max long, at w.offsets (stream_intake's scan); w.staging is then not read
+// c16 (with streams): the coefficients leave as int16 Mallat arrays (bpc_decode_kernel's C16 form)
+// compact: the tables of the launch take the COMPACT copies (-k > 0, bulk_compact)
+template <class Go>
+int launch_decoder(const Go &go, BpcArgs &a, bool cp3, unsigned waves, bool compact, const Workspace &w, const uint16_t *streams,
+                   size_t stride, uint32_t cw16_max, bool c16)
+{
+    const BpcLaunch l = select_decoder(cp3, a.k > 0.0f, compact, streams != nullptr, c16, waves);
+    if (!l.kernel) return kLaunchRefused;
+    a.coeffs_out = w.coef_i; a.staging = w.staging; a.sizes = w.sizes; a.plane_scratch = w.plane_scratch;
+    if (streams) { a.cw16 = streams; a.cw16_offsets = w.offsets; a.cw16_total = w.total; a.cw16_stride = stride; a.cw16_max = cw16_max; }
+    return go(l.kernel, dim3(l.wgs), l.threads, a);
+}
+// The encoder launch of every path: `waves` waves (a codeblock pair each), the caller's `a` complete but for the kernel's choice
+template <class Go>
+int launch_encoder(const Go &go, const BpcArgs &a, bool cp3, bool compact_pipelined, unsigned waves)
+{
+    const BpcLaunch l = select_encoder(cp3, a.k > 0.0f, a.k > 0.0f && compact_pipelined, waves);
+    return go(l.kernel, dim3(l.wgs), l.threads, a);
+}
+// the stage API's int32 array from the encoders' 16-bit staging: words 0 .. len - 1 of codeblocks [cb_base, cb_base + n)
+template <class Go>
+int widen_staging(const Go &go, const uint16_t *staging16, const int32_t *sizes, int cb_base, int n, int32_t *staging)
+{
+    return go(widen_staging_kernel, dim3((unsigned)n), 256u, staging16, sizes, cb_base, staging);
+}
+
+// ---- the pack of n frames' codeblocks, frame after frame in w (sizes, offsets, totals) and in the staging (P words a
+// frame): the header argument, the scan of the lengths, the copy into streams `stream_stride` shorts apart.
+// W: uint16_t = the encoders' own staging (the frame paths), int32_t = a caller's array (picsong_bitstream_pack)
+// h_header != nullptr: the populated header, on the frames `has` names (HeaderArg::has, pack_kernels.hpp)
+template <typename W, class Go>
+int pack_frames(const Go &go, const W *staging, const Workspace &w, int ncb, unsigned n, const uint16_t *h_header, int has,
+                uint16_t *streams, size_t P, size_t stream_stride)
+{
+    HeaderArg h;
+    memset(&h, 0, sizeof h);
+    if (h_header) { memcpy(h.h, h_header, sizeof h.h); h.has = has; }
+    if (int rc = go(scan_sizes_kernel, dim3(n), scan_threads(ncb), w.sizes, ncb, w.offsets, w.total)) return rc;
+    return go(pack_kernel<W>, dim3(pack_blocks<W>(ncb), n), 256u, staging, w.sizes, w.offsets, w.total, ncb, h, streams, P, stream_stride);
+}
+
+}  // namespace picsong

@@ -1,6 +1,7 @@
 // picsong_hip.hip -- C-ABI implementation (include/picsong_hip.h): host launch logic for the
 // gfx950 kernels in dwt_kernels.hpp / bpc_kernels.hpp / pack_kernels.hpp / window_kernels.hpp.  Which instantiation a
-// launch takes, its grid and its scratch: kernel_select.hpp, shared with the emulator drivers of tests/hipemu/.
+// launch takes, its grid and its scratch (kernel_select.hpp) and the launch sequences themselves (launch_seq.hpp) are
+// shared with the emulator drivers of tests/hipemu/; here: argument checks, allocation, bookkeeping and the launcher.
 // No CPU fallback exists: without a GPU every device entry point returns PICSONG_ERR_NODEVICE.
 #include "../../include/picsong_hip.h"
 
@@ -17,7 +18,7 @@
 #include <string>
 #include <vector>
 
-#include "kernel_select.hpp"
+#include "launch_seq.hpp"
 
 using namespace picsong;
 
@@ -42,20 +43,19 @@ int fail(int code, const char *fmt, ...)
                         __FILE__, __LINE__);                                               \
     } while (0)
 
+// The library's launcher (launch_seq.hpp): kernel k over grid x threads on the stream it holds
+struct HipGo {
+    hipStream_t s;
+    template <typename... P, typename... A>
+    int operator()(void (*k)(P...), dim3 grid, unsigned threads, const A &...args) const
+    {
+        k<<<grid, threads, 0, s>>>(args...);
+        HIP_TRY(hipGetLastError());
+        return PICSONG_OK;
+    }
+};
 
 }  // namespace
-
-// A workspace of the frame pipeline.  The context keeps two: a single frame's, and a batch's with every array n times
-// as long, frame after frame.
-struct Workspace {
-    void *coef;               // T[P + extra]: the transform's work buffer
-    int32_t *staging;         // int32[P] (the encoders' 16-bit staging lives in it too)
-    int32_t *sizes;           // int32[nCB]
-    int32_t *offsets;         // int32[nCB]
-    int32_t *total;           // 1
-    uint32_t *plane_scratch;  // the coders' bit-planes below the 8 held in registers, 8 KB per wave
-    int32_t *coef_i;          // int32[P]: decoded coefficients
-};
 
 struct picsong_ctx {
     picsong_params p;
@@ -106,32 +106,7 @@ static bool lean97_levels()
     return lean97;
 }
 
-// Levels [from, end) of a forward plan, one launch each.  `frames` = grid.z of a batched call.
-static int launch_fwd_levels(const picsong_ctx *c, const std::vector<FwdLaunch> &plan, size_t from, hipStream_t s,
-                             unsigned frames = 1)
-{
-    for (size_t l = from; l < plan.size(); l++) {
-        const FwdLaunch &f = plan[l];
-        select_fwd(c->p.lossy != 0, f)<<<dim3(f.gx, f.gy, frames), 256, 0, s>>>(f.a);
-        HIP_TRY(hipGetLastError());
-    }
-    return PICSONG_OK;
-}
-
-// A forward plan, levels 0 and 1 in one launch where plan_dwt_fwd2 allows it (LL1 stays in registers)
-static int launch_fwd_plan(const picsong_ctx *c, const std::vector<FwdLaunch> &plan, hipStream_t s, unsigned frames = 1)
-{
-    const bool lossy = c->p.lossy != 0;
-    Fwd2Launch f2;
-    const int nb = f2_pairs_batched(plan, lossy, frames);
-    const bool fused01 = plan_dwt_fwd2(plan, f2, true, lossy, nb);
-    if (fused01) {
-        select_fwd2(lossy, f2.a.l0.c16 != 0, false, nb)<<<dim3(f2.gx, f2.gy, frames), 256, 0, s>>>(f2.a);
-        HIP_TRY(hipGetLastError());
-    }
-    return launch_fwd_levels(c, plan, fused01 ? 2 : 0, s, frames);
-}
-
+static int level_off(const picsong_ctx *c) { return 1 << (c->p.bit_depth - 1); }
 
 extern "C" {
 
@@ -142,9 +117,7 @@ int picsong_pad_dim(int v) { return ((v + PICSONG_CB - 1) / PICSONG_CB) * PICSON
 
 size_t picsong_dwt_extra(int aw, int ah, int wl)
 {
-    size_t e = 0;
-    for (int l = 1; l < wl; l++) e += (size_t)(aw >> l) * (size_t)(ah >> l);
-    return e;
+    return dwt_extra(aw, ah, wl);
 }
 
 size_t picsong_max_stream_shorts(int aw, int ah)
@@ -489,9 +462,7 @@ static int plane_img_from_host(picsong_ctx *c, int comp, const picsong_lut_info 
 static int plane_img_refresh(picsong_ctx *c, int comp, hipStream_t s)
 {
     if (!ctx_uses_plane_img(c) || !c->lut_borrowed[comp]) return PICSONG_OK;
-    plane_img_kernel<<<1, 256, 0, s>>>(c->d_lut[comp], lut_geo(c->li[comp]), c->p.wl, c->d_img[comp]);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    return HipGo{ s }(plane_img_kernel, dim3(1), 256u, c->d_lut[comp], lut_geo(c->li[comp]), c->p.wl, c->d_img[comp]);
 }
 
 int picsong_ctx_set_lut_component(picsong_ctx *c, int comp, const picsong_lut_info *info, const int32_t *host_table)
@@ -605,26 +576,13 @@ int picsong_ctx_padded_dims(const picsong_ctx *c, int *aw, int *ah, int *ncb)
 int picsong_level_shift_fwd(picsong_ctx *c, const uint8_t *d_in, void *d_out, void *stream)
 {
     if (!c || !d_in || !d_out) return fail(PICSONG_ERR_ARG, "level_shift_fwd: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n4 = c->P / 4;
-    const int off = 1 << (c->p.bit_depth - 1);
-    const unsigned grid = elementwise_blocks(n4, 4096);
-    if (c->p.lossy) level_shift_fwd_kernel<float><<<grid, 256, 0, s>>>(d_in, (float *)d_out, n4, off);
-    else level_shift_fwd_kernel<int32_t><<<grid, 256, 0, s>>>(d_in, (int32_t *)d_out, n4, off);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    return level_shift_fwd(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, d_in, d_out, c->P / 4, level_off(c));
 }
 
 int picsong_level_shift_inv(picsong_ctx *c, void *d_data, void *stream)
 {
     if (!c || !d_data) return fail(PICSONG_ERR_ARG, "level_shift_inv: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    const int off = 1 << (c->p.bit_depth - 1);
-    const unsigned grid = elementwise_blocks(c->P);
-    if (c->p.lossy) level_shift_inv_f32_kernel<<<grid, 256, 0, s>>>((float *)d_data, c->P, (float)off);
-    else level_shift_inv_i32_kernel<<<grid, 256, 0, s>>>((int32_t *)d_data, c->P, off);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    return level_shift_inv(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, d_data, c->P, level_off(c));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -640,7 +598,7 @@ static int dwt_forward_impl(picsong_ctx *c, const void *d_in, bool u8in, void *d
     const std::vector<FwdLaunch> plan = plan_dwt_forward(d_in, u8in, d_out, c->aw, c->ah, c->p.wl, c->p.qs, want_c16);
     if (got_c16) *got_c16 = plan_is_c16(plan);
     else if (want_c16 && !plan_is_c16(plan)) return fail(PICSONG_ERR_ARG, "the 16-bit coefficient form needs the vector kernels on every level");
-    return launch_fwd_plan(c, plan, s);
+    return launch_fwd_plan(HipGo{ s }, c->p.lossy != 0, plan);
 }
 
 int picsong_dwt_forward(picsong_ctx *c, const void *d_in, void *d_out, void *stream)
@@ -663,7 +621,7 @@ int picsong_dwt_forward_band(picsong_ctx *c, const uint8_t *d_frame, int row0, i
     std::vector<FwdLaunch> plan = plan_dwt_forward(d_frame, true, d_out, c->aw, c->ah, c->p.wl, c->p.qs);
     plan_restrict_band(plan[0], row0, rows);
     plan.resize(1);
-    return launch_fwd_levels(c, plan, 0, (hipStream_t)stream);
+    return launch_fwd_levels(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, plan, 0);
 }
 
 int picsong_dwt_forward_tail(picsong_ctx *c, void *d_out, void *stream)
@@ -671,60 +629,20 @@ int picsong_dwt_forward_tail(picsong_ctx *c, void *d_out, void *stream)
     if (!c || !d_out) return fail(PICSONG_ERR_ARG, "dwt_forward_tail: null argument");
     // (the level-0 source is irrelevant here: only the launches of levels >= 1 are used)
     const std::vector<FwdLaunch> plan = plan_dwt_forward(d_out, false, d_out, c->aw, c->ah, c->p.wl, c->p.qs);
-    return launch_fwd_levels(c, plan, 1, (hipStream_t)stream);
+    return launch_fwd_levels(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, plan, 1);
 }
 
-// The frame paths' synthesis.  d_pixels != nullptr: the finest level writes clamped u8 pixels there (level shift +
-// clamp fused, when its vector kernel applies) instead of T samples into d_out; *fused says so.
-// frames > 1 (picsong_decode_frames): grid.z = frame; frame z's coded coefficients at d_in + z * P coefficients, its
-// work buffer at d_out + z * (P + extra) elements, its pixels at d_pixels + z * pix_stride bytes.
-// want_c16: the decoder may write 16-bit coefficients (picsong_ctx::c16_dec) -- the plan says whether this call's
-// pointers allow it (plan_inv_is_c16), BEFORE the decoder is launched: inverse_plan, then the decoder, then run_inverse.
-// (the grey frame paths take the 16-bit form only with the fused pixel store; planes_out: an RGB frame's components,
-// whose finest level writes T samples for the inverse colour transform, take it too)
-// reduce > 0: the levels wl - 1 .. reduce only (plan_dwt_inverse_reduced), level `reduce` the one that writes the pixels
+// The frame paths' synthesis plan (plan_inverse_frames, launch_plan.hpp) of this context, and its launches
 static std::vector<InvLaunch> inverse_plan(picsong_ctx *c, const int32_t *d_in, void *d_out, uint8_t *d_pixels, bool *fused,
                                            unsigned frames, size_t pix_stride, bool want_c16, bool planes_out = false,
                                            int reduce = 0)
 {
-    if (fused) *fused = false;
-    const bool px = d_pixels && (((uintptr_t)d_pixels) & 3u) == 0 && (pix_stride & 3u) == 0;
-    std::vector<InvLaunch> plan = plan_dwt_inverse_reduced(d_in, d_out, c->aw, c->ah, c->p.wl, c->p.qs, c->fast_div,
-                                                           want_c16 && (px || planes_out), reduce);
-    if (px && !plan.empty() && plan.back().vec) {
-        plan.back().a.dst_u8 = d_pixels;
-        plan.back().a.off = 1 << (c->p.bit_depth - 1);
-        if (fused) *fused = true;
-    }
-    if (frames > 1) {
-        const unsigned long long in_z = (unsigned long long)c->P * (plan_inv_is_c16(plan) ? 2ull : 4ull);
-        const unsigned long long wrk_z = (unsigned long long)(c->P + c->extra) * 4ull;
-        for (InvLaunch &f : plan) {
-            f.a.mallat_z = in_z;
-            f.a.ll_z = f.a.first ? in_z : wrk_z;            // the coarsest level's LL comes from the coded array
-            f.a.dst_z = wrk_z;
-            f.a.u8_z = (unsigned long long)pix_stride;
-        }
-    }
-    return plan;
+    return plan_inverse_frames(d_in, d_out, d_pixels, fused, frames, pix_stride, want_c16, planes_out, reduce, c->aw, c->ah,
+                               c->p.wl, c->p.qs, c->fast_div, level_off(c), c->P, c->extra);
 }
-
 static int run_inverse(picsong_ctx *c, const std::vector<InvLaunch> &plan, hipStream_t s, unsigned frames = 1)
 {
-    // 16-bit coefficients in, pixels out: synthesis levels 1 and 0 as one launch (dwt_inv2_kernel), LL0 in registers
-    Inv2Launch f2;
-    const bool fused10 = plan_dwt_inv2(plan, f2, c->p.lossy != 0);
-    const size_t n = fused10 ? plan.size() - 2 : plan.size();
-    for (size_t l = 0; l < n; l++) {
-        const InvLaunch &f = plan[l];
-        select_inv(c->p.lossy != 0, lean97_levels(), f)<<<dim3(f.gx, f.gy, frames), 256, 0, s>>>(f.a);
-        HIP_TRY(hipGetLastError());
-    }
-    if (fused10) {
-        select_inv2(c->p.lossy != 0, f2.a.l0.one_div != 0)<<<dim3(f2.gx, f2.gy, frames), 256, 0, s>>>(f2.a);
-        HIP_TRY(hipGetLastError());
-    }
-    return PICSONG_OK;
+    return picsong::run_inverse(HipGo{ s }, c->p.lossy != 0, lean97_levels(), plan, frames);
 }
 
 int picsong_dwt_inverse(picsong_ctx *c, const int32_t *d_in, void *d_out, void *stream)
@@ -783,10 +701,7 @@ static int launch_encoder(picsong_ctx *c, const BpcArgs &a, unsigned waves, int 
     const bool bulk = a.k > 0.0f;
     if (!bulk)
         for (int k = comp; k < comp + ncomp; k++) if (int rc = plane_img_refresh(c, k, s)) return rc;
-    const BpcLaunch l = select_encoder(c->p.cp == 3, bulk, bulk && bulk_compact(c, comp, ncomp) && c->pipelined, waves);
-    l.kernel<<<l.wgs, l.threads, 0, s>>>(a);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    return picsong::launch_encoder(HipGo{ s }, a, c->p.cp == 3, bulk && bulk_compact(c, comp, ncomp) && c->pipelined, waves);
 }
 
 // d_stage16: the encoders' 16-bit staging, uint16[nCB * 4096] (BpcArgs::staging16) -- the context's own staging
@@ -820,9 +735,7 @@ static int bpc_encode_widened(picsong_ctx *c, const void *d_coeffs, int32_t *d_s
     HIP_TRY(hipMemsetAsync(d_staging, 0xFF, c->P * sizeof(int32_t), s));
     int rc = bpc_encode_impl(c, d_coeffs, st16, d_sizes, s, 0, -1, comp);
     if (rc) return rc;
-    widen_staging_kernel<<<(unsigned)c->ncb, 256, 0, s>>>(st16, d_sizes, 0, d_staging);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    return widen_staging(HipGo{ s }, st16, d_sizes, 0, c->ncb, d_staging);
 }
 
 int picsong_bpc_encode(picsong_ctx *c, const void *d_coeffs, int32_t *d_staging, int32_t *d_sizes, void *stream)
@@ -851,44 +764,20 @@ static bool dec_from_stream(const picsong_ctx *c)
     return !staged && c->p.cp != 3;
 }
 
-// Stream intake: the codeblock lengths of n streams `stride` shorts apart into w.sizes, their scan into w.offsets and
-// w.total -- `direct`, one launch, for a decoder that reads the streams itself; else the codewords unpacked into
-// w.staging as well (-k > 0 through the staging, -cp 3, PICSONG_DEC_STAGING)
+// Stream intake (launch_seq.hpp) of n streams `stride` shorts apart into w
 static int stream_intake(picsong_ctx *c, const uint16_t *d_streams, unsigned n, size_t stride, bool direct, const Workspace &w,
                          hipStream_t s)
 {
-    if (direct) {
-        scan_stream_kernel<<<n, scan_threads(c->ncb), 0, s>>>(d_streams, c->ncb, w.sizes, w.offsets, w.total, c->d_flag, stride);
-        HIP_TRY(hipGetLastError());
-        return PICSONG_OK;
-    }
-    read_sizes_kernel<<<dim3((unsigned)((c->ncb + 255) / 256), n), 256, 0, s>>>(d_streams, c->ncb, w.sizes, c->d_flag, stride);
-    HIP_TRY(hipGetLastError());
-    scan_sizes_kernel<<<n, scan_threads(c->ncb), 0, s>>>(w.sizes, c->ncb, w.offsets, w.total);
-    HIP_TRY(hipGetLastError());
-    unpack_kernel<<<dim3((unsigned)c->ncb, n), 256, 0, s>>>(d_streams, w.sizes, w.offsets, c->ncb, w.staging, stride, c->P);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    return picsong::stream_intake(HipGo{ s }, d_streams, n, stride, direct, c->ncb, c->P, w, c->d_flag);
 }
 
-// The decoder launch of every path: `waves` waves over w's sizes, staging and plane scratch, coefficients into w.coef_i.
-// d_streams != nullptr (k = 0 or -k > 0, -cp 2): the codewords come from the packed streams, `stride` shorts apart, at
-// w.offsets (stream_intake's scan); w.staging is then not read
-// c16 (with d_streams): the coefficients leave as int16 Mallat arrays (bpc_decode_kernel's C16 form)
-// compact: the tables of the launch take the COMPACT copies (-k > 0, bulk_compact)
+// The decoder launch of every path (launch_seq.hpp): `waves` waves over w, from the packed streams where d_streams is set
 static int launch_decoder(picsong_ctx *c, BpcArgs &a, unsigned waves, bool compact, const Workspace &w,
                           const uint16_t *d_streams, size_t stride, bool c16, hipStream_t s)
 {
-    const BpcLaunch l = select_decoder(c->p.cp == 3, a.k > 0.0f, compact, d_streams != nullptr, c16, waves);
-    if (!l.kernel) return fail(PICSONG_ERR_ARG, "the 16-bit coefficient form decodes from the stream itself");
-    a.coeffs_out = w.coef_i; a.staging = w.staging; a.sizes = w.sizes; a.plane_scratch = w.plane_scratch;
-    if (d_streams) {
-        a.cw16 = d_streams; a.cw16_offsets = w.offsets; a.cw16_total = w.total; a.cw16_stride = stride;
-        a.cw16_max = (uint32_t)picsong_max_stream_shorts(c->aw, c->ah);
-    }
-    l.kernel<<<l.wgs, l.threads, 0, s>>>(a);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    const int rc = picsong::launch_decoder(HipGo{ s }, a, c->p.cp == 3, waves, compact, w, d_streams, stride,
+                                           (uint32_t)picsong_max_stream_shorts(c->aw, c->ah), c16);
+    return rc == kLaunchRefused ? fail(PICSONG_ERR_ARG, "the 16-bit coefficient form decodes from the stream itself") : rc;
 }
 
 // One frame's decoder over the context's own scratch: d_staging / d_sizes / d_coeffs may be the caller's arrays
@@ -948,10 +837,10 @@ int picsong_selftest_lds_order(int device, int *mismatches)
     uint32_t *d = nullptr, h = 0;
     HIP_TRY(hipMalloc(&d, sizeof(uint32_t)));
     HIP_TRY(hipMemset(d, 0, sizeof(uint32_t)));
-    lds_order_selftest_kernel<<<2048, 256>>>(2000, 0x5EED1234u, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
+    const int rc = HipGo{ nullptr }(lds_order_selftest_kernel, dim3(2048), 256u, 2000, 0x5EED1234u, d);
+    const hipError_t e = rc ? hipSuccess : hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
     (void)hipFree(d);
+    if (rc) return rc;
     if (e != hipSuccess) return fail(PICSONG_ERR_HIP, "selftest: %s", hipGetErrorString(e));
     *mismatches = (int)h;
     return PICSONG_OK;
@@ -981,25 +870,7 @@ int picsong_last_total(picsong_ctx *c, void *stream, int *h_total)
     return PICSONG_OK;
 }
 
-// The pack of n frames' codeblocks, frame after frame in w (sizes, offsets, totals) and in the staging: the header
-// argument, the scan of the lengths, the copy into streams `stream_stride` shorts apart.
-// W: uint16_t = the encoders' own staging (the frame paths), int32_t = a caller's array (picsong_bitstream_pack)
-// h_header != nullptr: the populated header, on the frames `has` names (HeaderArg::has, pack_kernels.hpp)
 extern "C++" {
-template <typename W>
-static int pack_frames(picsong_ctx *c, const W *d_staging, const Workspace &w, int ncb, unsigned n, const uint16_t *h_header,
-                       int has, uint16_t *d_streams, size_t stream_stride, hipStream_t s)
-{
-    HeaderArg h;
-    memset(&h, 0, sizeof h);
-    if (h_header) { memcpy(h.h, h_header, sizeof h.h); h.has = has; }
-    scan_sizes_kernel<<<n, scan_threads(ncb), 0, s>>>(w.sizes, ncb, w.offsets, w.total);
-    HIP_TRY(hipGetLastError());
-    pack_kernel<W><<<dim3(pack_blocks<W>(ncb), n), 256, 0, s>>>(d_staging, w.sizes, w.offsets, w.total, ncb, h, d_streams, c->P,
-                                                              stream_stride);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
-}
 // codeblocks [cb_begin, cb_begin + n) of one frame out of the context's own offsets and total
 template <typename W>
 static int pack_range(picsong_ctx *c, const W *d_staging, const int32_t *d_sizes, int n,
@@ -1008,7 +879,7 @@ static int pack_range(picsong_ctx *c, const W *d_staging, const int32_t *d_sizes
     c->last_batch = 0;                                      // the most recent total is one.total (picsong_copy_last_totals)
     Workspace w = c->one;
     w.sizes = const_cast<int32_t *>(d_sizes);
-    return pack_frames(c, d_staging, w, n, 1u, h_header, 1, d_stream, 0, s);
+    return pack_frames(HipGo{ s }, d_staging, w, n, 1u, h_header, 1, d_stream, c->P, 0);
 }
 }  // extern "C++"
 
@@ -1122,33 +993,13 @@ static int reduced_args_ok(const picsong_ctx *c, int reduce, const char *who)
     return PICSONG_OK;
 }
 
-// The windowed synthesis (window_kernels.hpp) of `frames` frames, grid.z = frame: frame z's coefficients at coef_i +
-// z * coef_z bytes, its scratch (T[P + extra]) at work + z * work_z bytes.  u8 != nullptr: level r writes frame z's
-// window at u8 + z * u8_z, row stride pitch; else level r's samples stay at frame z's `work` (compact, row stride w).
+// The windowed synthesis (run_window, launch_seq.hpp) of `frames` frames of this context
 static int run_window(picsong_ctx *c, const WindowPlan &w, const int32_t *coef_i, void *work, unsigned frames,
                       unsigned long long coef_z, unsigned long long work_z, uint8_t *u8, size_t pitch,
                       unsigned long long u8_z, hipStream_t s)
 {
-    std::vector<WinLaunch> plan = plan_window_synthesis(w, coef_i, work, c->P, c->aw, c->ah, c->p.qs, u8, pitch,
-                                                        1 << (c->p.bit_depth - 1));
-    for (WinLaunch &f : plan) {
-        f.a.mallat_z = coef_z; f.a.ll_z = work_z; f.a.dst_z = work_z; f.a.u8_z = u8_z;
-        f.grid.z = frames;
-        select_window(c->p.lossy != 0, f.u8)<<<f.grid, 256, 0, s>>>(f.a);
-        HIP_TRY(hipGetLastError());
-    }
-    return PICSONG_OK;
-}
-
-// n4 * 4 samples of a synthesis that did not write its pixels itself: level shift + clamp
-static int clamp_pixels(picsong_ctx *c, const void *img, uint8_t *d_out, size_t n4, hipStream_t s)
-{
-    const int off = 1 << (c->p.bit_depth - 1);
-    const unsigned grid = elementwise_blocks(n4);
-    if (c->p.lossy) clamp_to_u8_f32_kernel<<<grid, 256, 0, s>>>((const float *)img, d_out, n4, (float)off);
-    else clamp_to_u8_i32_kernel<<<grid, 256, 0, s>>>((const int32_t *)img, d_out, n4, off);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    return picsong::run_window(HipGo{ s }, c->p.lossy != 0, w, coef_i, work, c->P, c->aw, c->ah, c->p.qs, level_off(c), frames,
+                               coef_z, work_z, u8, pitch, u8_z);
 }
 
 // picsong_decode_frame (reduce = 0) and picsong_decode_frame_reduced: the pixels of level `reduce`, row stride AW >> reduce
@@ -1171,7 +1022,8 @@ static int decode_frame_impl(picsong_ctx *c, const uint16_t *d_stream, uint8_t *
     if ((rc = run_inverse(c, plan, s))) return rc;
     if (fused) return PICSONG_OK;            // the finest level wrote the pixels itself
     // (level `reduce`'s samples, packed: c->extra elements in when reduce = 0)
-    return clamp_pixels(c, plan.back().a.dst, d_frame_out, (size_t)(c->aw >> reduce) * (size_t)(c->ah >> reduce) / 4, s);
+    return clamp_pixels(HipGo{ s }, c->p.lossy != 0, plan.back().a.dst, d_frame_out,
+                        (size_t)(c->aw >> reduce) * (size_t)(c->ah >> reduce) / 4, level_off(c));
 }
 
 int picsong_decode_frame(picsong_ctx *c, const uint16_t *d_stream, uint8_t *d_frame_out, void *stream)
@@ -1305,15 +1157,6 @@ static int ensure_coef_i(picsong_ctx *c, int n)
     return PICSONG_OK;
 }
 
-// a batched forward plan: level 0 reads frame z at + z * src_z0 bytes, every level works in frame z's buffer of coef_z bytes
-static void plan_frame_strides(std::vector<FwdLaunch> &plan, unsigned long long src_z0, unsigned long long coef_z)
-{
-    for (size_t l = 0; l < plan.size(); l++) {
-        plan[l].a.src_z = l == 0 ? src_z0 : coef_z;
-        plan[l].a.dst_z = coef_z;
-    }
-}
-
 int picsong_encode_frames(picsong_ctx *c, int n, const uint8_t *d_frames, size_t frame_stride, int first_iter,
                           uint16_t *d_streams, size_t stream_stride, void *stream)
 {
@@ -1340,7 +1183,7 @@ int picsong_encode_frames(picsong_ctx *c, int n, const uint8_t *d_frames, size_t
     std::vector<FwdLaunch> plan = plan_dwt_forward(d_frames, true, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16);
     a.c16 = plan_is_c16(plan) ? 1 : 0;
     plan_frame_strides(plan, frame_stride, coef_z);
-    if ((rc = launch_fwd_plan(c, plan, s, (unsigned)n))) return rc;
+    if ((rc = launch_fwd_plan(HipGo{ s }, c->p.lossy != 0, plan, (unsigned)n))) return rc;
 
     if (ev) HIP_TRY(hipEventRecord(ev[1], s));
     // ---- coder: one grid over the n frames' codeblock pairs
@@ -1358,8 +1201,8 @@ int picsong_encode_frames(picsong_ctx *c, int n, const uint8_t *d_frames, size_t
     uint16_t hdr[PICSONG_HDR_SHORTS];
     const bool has0 = first_iter <= 0 && first_iter + n > 0;
     if (has0) picsong_header_pack(&c->p, hdr);
-    if ((rc = pack_frames(c, a.staging16, c->batch, c->ncb, (unsigned)n, has0 ? hdr : nullptr, -first_iter + 1, d_streams,
-                          stream_stride, s))) return rc;
+    if ((rc = pack_frames(HipGo{ s }, a.staging16, c->batch, c->ncb, (unsigned)n, has0 ? hdr : nullptr, -first_iter + 1, d_streams,
+                          c->P, stream_stride))) return rc;
     if (ev) HIP_TRY(hipEventRecord(ev[3], s));
     c->last_batch = n;
     return PICSONG_OK;
@@ -1432,7 +1275,7 @@ static int decode_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, 
     for (int f = 0; f < n; f++) {
         // (level `reduce`'s samples of frame f: c->extra elements into its work buffer when reduce = 0)
         const void *img = (const char *)plan.back().a.dst + (size_t)f * (c->P + c->extra) * 4;
-        if ((rc = clamp_pixels(c, img, d_frames_out + (size_t)f * frame_stride, px / 4, s))) return rc;
+        if ((rc = clamp_pixels(HipGo{ s }, c->p.lossy != 0, img, d_frames_out + (size_t)f * frame_stride, px / 4, level_off(c)))) return rc;
     }
     return PICSONG_OK;
 }
@@ -1482,33 +1325,14 @@ int picsong_rgb_forward(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, 
                         void *d_c1, void *d_c2, void *stream)
 {
     if (!c || !d_r || !d_g || !d_b || !d_c0 || !d_c1 || !d_c2) return fail(PICSONG_ERR_ARG, "rgb_forward: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n4 = c->P / 4;
-    const int off = 1 << (c->p.bit_depth - 1);
-    const unsigned grid = elementwise_blocks(n4);
-    if (c->p.lossy) rgb_forward_kernel<float><<<grid, 256, 0, s>>>(d_r, d_g, d_b, (float *)d_c0, (float *)d_c1, (float *)d_c2, n4, off);
-    else rgb_forward_kernel<int32_t><<<grid, 256, 0, s>>>(d_r, d_g, d_b, (int32_t *)d_c0, (int32_t *)d_c1, (int32_t *)d_c2, n4, off);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
-}
-
-// the inverse colour transform of n4 * 4 samples (picsong_rgb_inverse: the padded frame's P)
-static int rgb_inverse_n(picsong_ctx *c, const void *d_c0, const void *d_c1, const void *d_c2, uint8_t *d_r, uint8_t *d_g,
-                         uint8_t *d_b, size_t n4, hipStream_t s)
-{
-    const int off = 1 << (c->p.bit_depth - 1);
-    const unsigned grid = elementwise_blocks(n4);
-    if (c->p.lossy) rgb_inverse_kernel<float><<<grid, 256, 0, s>>>((const float *)d_c0, (const float *)d_c1, (const float *)d_c2, d_r, d_g, d_b, n4, off);
-    else rgb_inverse_kernel<int32_t><<<grid, 256, 0, s>>>((const int32_t *)d_c0, (const int32_t *)d_c1, (const int32_t *)d_c2, d_r, d_g, d_b, n4, off);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    return rgb_forward(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, d_r, d_g, d_b, d_c0, d_c1, d_c2, c->P / 4, level_off(c));
 }
 
 int picsong_rgb_inverse(picsong_ctx *c, const void *d_c0, const void *d_c1, const void *d_c2, uint8_t *d_r,
                         uint8_t *d_g, uint8_t *d_b, void *stream)
 {
     if (!c || !d_r || !d_g || !d_b || !d_c0 || !d_c1 || !d_c2) return fail(PICSONG_ERR_ARG, "rgb_inverse: null argument");
-    return rgb_inverse_n(c, d_c0, d_c1, d_c2, d_r, d_g, d_b, c->P / 4, (hipStream_t)stream);
+    return rgb_inverse(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, d_c0, d_c1, d_c2, d_r, d_g, d_b, c->P / 4, level_off(c));
 }
 
 int picsong_encode_plane(picsong_ctx *c, const void *d_plane, int comp, int with_header, uint16_t *d_stream, void *stream)
@@ -1561,46 +1385,19 @@ static int bpc_args_rgb(picsong_ctx *c, BpcArgs &a)
     return PICSONG_OK;
 }
 
-// An RGB frame's colour transform (level shift fused) and the forward transform of its three components, component k's
-// coefficients into c->batch.coef + k * (P + extra) * 4 bytes (ensure_batch(3) and ensure_coef_i(3) done); *c16: the
-// coefficient form this call's plan delivers.  The head of picsong_encode_rgb_frame and picsong_train_rgb_frame.
+// An RGB frame's colour transform and the forward transform of its three components (rgb_forward_transform,
+// launch_seq.hpp), component k's coefficients into c->batch.coef + k * (P + extra) * 4 bytes (ensure_batch(3) and
+// ensure_coef_i(3) done); *c16: the coefficient form this call's plan delivers.  The head of picsong_encode_rgb_frame
+// and picsong_train_rgb_frame.
+// (the fused head's buffer loads want all three planes 16-byte aligned like a grey frame's)
+static bool rgb_planes_aligned(const uint8_t *r, const uint8_t *g, const uint8_t *b) { return ((((uintptr_t)r) | ((uintptr_t)g) | ((uintptr_t)b)) & 15u) == 0; }
 static int rgb_forward_transform(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, hipStream_t s,
                                  bool *c16)
 {
-    *c16 = false;
-    int rc;
-    const size_t coef_z = (c->P + c->extra) * 4;
-    char *planes = (char *)c->batch.coef_i;
-    // ---- lossless: the colour transform in the fused head's load stage (dwt_fwd2_kernel<..., RGB>): the head reads the
-    // three u8 planes and delivers component blockIdx.z -- no component plane is ever written (the separate transform
-    // kernel reads 100 MB and writes 400 MB of them per 8K frame, and level 0 reads them back)
-    bool fused_rgb = false;
-    // (the fused head's buffer loads want all three planes 16-byte aligned like a grey frame's; others take the
-    // separate colour transform below)
-    const bool planes_aligned = ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 15u) == 0;
-    if (c->c16 && planes_aligned && !getenv("PICSONG_RGB_NOFUSE")) {
-        std::vector<FwdLaunch> plan = plan_dwt_forward(d_r, true, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, true);
-        plan_frame_strides(plan, 0, coef_z);                 // level 0: every component reads the three planes
-        plan[0].a.src_g = d_g; plan[0].a.src_b = d_b;
-        Fwd2Launch f2;
-        if (plan_is_c16(plan) && plan_dwt_fwd2(plan, f2, true, c->p.lossy != 0, kF2PairsRgb)) {
-            // (RCT on the integer head, ICT on the 9/7 one: the component planes are never written)
-            select_fwd2(c->p.lossy != 0, true, true)<<<dim3(f2.gx, f2.gy, 3u), 256, 0, s>>>(f2.a);
-            HIP_TRY(hipGetLastError());
-            if ((rc = launch_fwd_levels(c, plan, 2, s, 3u))) return rc;
-            *c16 = true;
-            fused_rgb = true;
-        }
-    }
-    if (!fused_rgb) {
-    // ---- colour transform (level shift fused) into three planes, then the transform of all three per launch
-    if ((rc = picsong_rgb_forward(c, d_r, d_g, d_b, planes, planes + c->P * 4, planes + 2 * c->P * 4, (void *)s))) return rc;
-    std::vector<FwdLaunch> plan = plan_dwt_forward(planes, false, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16);
-    *c16 = plan_is_c16(plan);
-    plan_frame_strides(plan, (unsigned long long)c->P * 4ull, coef_z);
-    if ((rc = launch_fwd_levels(c, plan, 0, s, 3u))) return rc;
-    }
-    return PICSONG_OK;
+    const bool lossy = c->p.lossy != 0;
+    auto plan_of = [c](const void *src, bool u8in) { return plan_dwt_forward(src, u8in, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16); };
+    return picsong::rgb_forward_transform(HipGo{ s }, lossy, c->c16 && rgb_planes_aligned(d_r, d_g, d_b) && !getenv("PICSONG_RGB_NOFUSE"),
+                                          plan_of, true, d_r, d_g, d_b, c->batch.coef_i, c->P, level_off(c), (c->P + c->extra) * 4, c16);
 }
 
 int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
@@ -1629,8 +1426,8 @@ int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *
     // ---- pack: the populated header on the components of header_mask
     uint16_t hdr[PICSONG_HDR_SHORTS];
     if (header_mask & 7) picsong_header_pack(&c->p, hdr);
-    if ((rc = pack_frames(c, a.staging16, c->batch, c->ncb, 3u, (header_mask & 7) ? hdr : nullptr, -(header_mask & 7), d_streams,
-                          stream_stride, s))) return rc;
+    if ((rc = pack_frames(HipGo{ s }, a.staging16, c->batch, c->ncb, 3u, (header_mask & 7) ? hdr : nullptr, -(header_mask & 7), d_streams,
+                          c->P, stream_stride))) return rc;
     c->last_batch = 3;
     return PICSONG_OK;
 }
@@ -1677,30 +1474,16 @@ static int ensure_rate(picsong_ctx *c, int frames)
 // step 1: the unquantised coefficients of the job's frames (RGB: of the three components), array f at rate_coef + f * rate_z
 static int rate_transform(picsong_ctx *c, const RateJob &job, hipStream_t s)
 {
-    int rc;
+    const bool lossy = c->p.lossy != 0;
     if (!c->p.is_rgb) {
         std::vector<FwdLaunch> plan = plan_dwt_forward_unit(job.frames, true, c->rate_coef, c->aw, c->ah, c->p.wl);
         plan_frame_strides(plan, job.frame_stride, c->rate_z);
-        return launch_fwd_plan(c, plan, s, (unsigned)job.n);
+        return launch_fwd_plan(HipGo{ s }, lossy, plan, (unsigned)job.n);
     }
     // the ICT in the fused head's load stage where the planes allow it (as rgb_forward_transform), 32-bit float form
-    const bool planes_aligned = ((((uintptr_t)job.r) | ((uintptr_t)job.g) | ((uintptr_t)job.b)) & 15u) == 0;
-    if (planes_aligned && !getenv("PICSONG_RGB_NOFUSE")) {
-        std::vector<FwdLaunch> plan = plan_dwt_forward_unit(job.r, true, c->rate_coef, c->aw, c->ah, c->p.wl);
-        plan_frame_strides(plan, 0, c->rate_z);
-        plan[0].a.src_g = job.g; plan[0].a.src_b = job.b;
-        Fwd2Launch f2;
-        if (plan_dwt_fwd2(plan, f2, true, true, kF2PairsRgb)) {
-            select_fwd2_rgb_f32()<<<dim3(f2.gx, f2.gy, 3u), 256, 0, s>>>(f2.a);
-            HIP_TRY(hipGetLastError());
-            return launch_fwd_levels(c, plan, 2, s, 3u);
-        }
-    }
-    char *planes = (char *)c->batch.coef_i;
-    if ((rc = picsong_rgb_forward(c, job.r, job.g, job.b, planes, planes + c->P * 4, planes + 2 * c->P * 4, (void *)s))) return rc;
-    std::vector<FwdLaunch> plan = plan_dwt_forward_unit(planes, false, c->rate_coef, c->aw, c->ah, c->p.wl);
-    plan_frame_strides(plan, (unsigned long long)c->P * 4ull, c->rate_z);
-    return launch_fwd_levels(c, plan, 0, s, 3u);
+    auto plan_of = [c](const void *src, bool u8in) { return plan_dwt_forward_unit(src, u8in, c->rate_coef, c->aw, c->ah, c->p.wl); };
+    return picsong::rgb_forward_transform(HipGo{ s }, lossy, rgb_planes_aligned(job.r, job.g, job.b) && !getenv("PICSONG_RGB_NOFUSE"), plan_of,
+                                          false, job.r, job.g, job.b, c->batch.coef_i, c->P, level_off(c), c->rate_z);
 }
 
 // step 2's launches for the candidates js[0 .. m): quantise, coder, size scan; the m * nf totals are then in batch.total
@@ -1715,8 +1498,7 @@ static int rate_probe(picsong_ctx *c, BpcArgs a, int nf, int m, const int *js, h
     const unsigned long long dst_z = (unsigned long long)c->P * 4ull;
     const QuantArgs qa = quantise_args(c->rate_coef, c->rate_z, c->batch.coef, dst_z, c->aw, c->ah, c->p.wl, nf, m, js, forms);
     const QuantLaunch ql = select_quantise(m, nf, c->ah);
-    ql.kernel<<<ql.wgs, 256, 0, s>>>(qa);
-    HIP_TRY(hipGetLastError());
+    if ((rc = HipGo{ s }(ql.kernel, dim3(ql.wgs), 256u, qa))) return rc;
     a.c16 = c16 ? 1 : 0; a.is_float = 1;
     a.coeffs_in = c->batch.coef; a.coef_z = dst_z;
     a.staging16 = reinterpret_cast<uint16_t *>(c->batch.staging);
@@ -1728,9 +1510,7 @@ static int rate_probe(picsong_ctx *c, BpcArgs a, int nf, int m, const int *js, h
         a.frames = m * nf; a.waves_per_frame = (c->ncb + 1) / 2;
         if ((rc = launch_encoder(c, a, (unsigned)(m * nf) * (unsigned)a.waves_per_frame, 0, 1, s))) return rc;
     }
-    scan_sizes_kernel<<<(unsigned)(m * nf), scan_threads(c->ncb), 0, s>>>(c->batch.sizes, c->ncb, c->batch.offsets, c->batch.total);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    return HipGo{ s }(scan_sizes_kernel, dim3((unsigned)(m * nf)), scan_threads(c->ncb), c->batch.sizes, c->ncb, c->batch.offsets, c->batch.total);
 }
 
 static int rate_impl(picsong_ctx *c, const RateJob &job, size_t target_shorts, int j_min, int j_max, hipStream_t s, int *h_j,
@@ -1792,7 +1572,7 @@ static int rate_impl(picsong_ctx *c, const RateJob &job, size_t target_shorts, i
     picsong_header_pack(&hp, hdr);
     const bool has_hdr = rgb ? (job.header_mask & 7) != 0 : (job.first_iter <= 0 && job.first_iter + job.n > 0);
     const int has = rgb ? -(job.header_mask & 7) : -job.first_iter + 1;
-    if ((rc = pack_frames(c, st16, w, c->ncb, (unsigned)nf, has_hdr ? hdr : nullptr, has, job.d_streams, job.stream_stride, s))) return rc;
+    if ((rc = pack_frames(HipGo{ s }, st16, w, c->ncb, (unsigned)nf, has_hdr ? hdr : nullptr, has, job.d_streams, c->P, job.stream_stride))) return rc;
     // (the lengths where the plain calls leave theirs: picsong_last_total(s) / picsong_copy_last_totals cover a rate call)
     if (slot > 0) HIP_TRY(hipMemcpyAsync(c->batch.total, w.total, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     if (job.single) HIP_TRY(hipMemcpyAsync(c->one.total, w.total, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
@@ -1880,36 +1660,19 @@ static int decode_rgb_impl(picsong_ctx *c, const uint16_t *d_streams, size_t str
         const unsigned long long z = (unsigned long long)(c->P + c->extra) * 4ull;
         if ((rc = run_window(c, *win, c->batch.coef_i, c->batch.coef, 3u, (unsigned long long)c->P * 4ull, z, nullptr, 0, 0, s))) return rc;
         const IRect &o = win->R[reduce];
-        const int w = o.x1 - o.x0, h = o.y1 - o.y0, off = 1 << (c->p.bit_depth - 1);
-        const dim3 grid((unsigned)((w + 255) / 256), (unsigned)h);
-        if (c->p.lossy) window_rgb_kernel<float><<<grid, 256, 0, s>>>((const float *)c->batch.coef, z, w, h, d_r, d_g, d_b, pitch, off);
-        else window_rgb_kernel<int><<<grid, 256, 0, s>>>((const int *)c->batch.coef, z, w, h, d_r, d_g, d_b, pitch, off);
-        HIP_TRY(hipGetLastError());
-        return PICSONG_OK;
+        return window_rgb(HipGo{ s }, c->p.lossy != 0, c->batch.coef, z, o.x1 - o.x0, o.y1 - o.y0, d_r, d_g, d_b, pitch, level_off(c));
     }
     // 16-bit coefficients: the finest level of the three components and the inverse colour transform as ONE launch
-    // (select_inv_rgb; PICSONG_RGB_NOFUSE=1 keeps the two).  5/3: the 32-bit planes are never written (dwt_inv_rgb_kernel).
-    // 9/7, the lean kernel's domain: the three components as the three waves of a workgroup, a row pair exchanged
-    // through LDS, the inverse ICT at the stores (dwt_inv97_rgb_kernel).
+    // (run_inverse_rgb; PICSONG_RGB_NOFUSE=1 keeps the two; 9/7: the lean kernel's domain)
     const bool px_aligned = ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 3u) == 0;
-    bool tail = c16 && plan.size() >= 2 && plan.back().vec && px_aligned && !getenv("PICSONG_RGB_NOFUSE");
-    if (tail && c->p.lossy)
-        tail = plan.back().fast && !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0);
-    if (tail) {
-        std::vector<InvLaunch> head(plan.begin(), plan.end() - 1);
-        if ((rc = run_inverse(c, head, s, 3u))) return rc;
-        DwtInvArgs fa = plan.back().a;
-        fa.off = 1 << (c->p.bit_depth - 1);
-        const InvRgbLaunch l = select_inv_rgb(c->p.lossy != 0, plan.back());
-        l.kernel<<<dim3(l.gx, l.gy, 1), l.threads, 0, s>>>(fa, d_r, d_g, d_b);
-        HIP_TRY(hipGetLastError());
-        return PICSONG_OK;
-    }
+    bool tail = inv_rgb_tail_ok(plan, c->p.lossy != 0) && px_aligned && !getenv("PICSONG_RGB_NOFUSE");
+    if (tail && c->p.lossy) tail = !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0);
+    if (tail) return run_inverse_rgb(HipGo{ s }, c->p.lossy != 0, lean97_levels(), plan, level_off(c), d_r, d_g, d_b);
     if ((rc = run_inverse(c, plan, s, 3u))) return rc;
     const char *img = (const char *)plan.back().a.dst;      // (level `reduce`: c->extra elements in when reduce = 0)
     const size_t z = (c->P + c->extra) * 4;
-    return rgb_inverse_n(c, img, img + z, img + 2 * z, d_r, d_g, d_b,
-                         (size_t)(c->aw >> reduce) * (size_t)(c->ah >> reduce) / 4, s);
+    return rgb_inverse(HipGo{ s }, c->p.lossy != 0, img, img + z, img + 2 * z, d_r, d_g, d_b,
+                       (size_t)(c->aw >> reduce) * (size_t)(c->ah >> reduce) / 4, level_off(c));
 }
 
 int picsong_decode_rgb_frame(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_r, uint8_t *d_g,
@@ -2034,9 +1797,7 @@ static int launch_stats(picsong_ctx *c, int comp, const void *d_coeffs, bool c16
     }
     const BpcArgs a = stats_args(c->aw, c->ah, c->p.wl, lut_geo(c->train_li), c->d_flag, d_coeffs, c->p.lossy != 0 && !c16, c16,
                                  frames, coef_z, c->train_scratch);
-    l.kernel<<<l.wgs, l.threads, 0, s>>>(a, c->d_train[comp], (int)pairs);
-    HIP_TRY(hipGetLastError());
-    return PICSONG_OK;
+    return HipGo{ s }(l.kernel, dim3(l.wgs), l.threads, a, c->d_train[comp], (int)pairs);
 }
 
 int picsong_train_coeffs(picsong_ctx *c, int comp, const void *d_coeffs, void *stream)
@@ -2066,13 +1827,13 @@ int picsong_train_frames(picsong_ctx *c, int n, const uint8_t *d_frames, size_t 
         std::vector<FwdLaunch> plan = plan_dwt_forward(d_frames, true, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16);
         c16 = plan_is_c16(plan);
         plan_frame_strides(plan, frame_stride, coef_z);
-        if ((rc = launch_fwd_plan(c, plan, s, (unsigned)n))) return rc;
+        if ((rc = launch_fwd_plan(HipGo{ s }, c->p.lossy != 0, plan, (unsigned)n))) return rc;
     } else {
         // ---- frames whose alignment differs from one another: a plan each, the 32-bit arrays for all of them
         for (int f = 0; f < n; f++) {
             const std::vector<FwdLaunch> plan = plan_dwt_forward(d_frames + (size_t)f * frame_stride, true, (char *)c->batch.coef + (size_t)f * coef_z,
                                                                  c->aw, c->ah, c->p.wl, c->p.qs, false);
-            if ((rc = launch_fwd_plan(c, plan, s))) return rc;
+            if ((rc = launch_fwd_plan(HipGo{ s }, c->p.lossy != 0, plan))) return rc;
         }
     }
     return launch_stats(c, 0, c->batch.coef, c16, n, coef_z, s);

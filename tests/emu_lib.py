@@ -8,22 +8,33 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU_DIR = os.path.join(ROOT, "tests", "hipemu")
-SO_PATH = os.path.join(EMU_DIR, "_build", "libpicsong_emu.so")
 # PICSONG_EMU_SO: run the emulated tests on another build of the same sources (tools/sanitize_emu.sh:
 # -fsanitize=undefined / address builds, with the sanitizer runtime preloaded)
 SO_OVERRIDE = os.environ.get("PICSONG_EMU_SO")
 _lib = None
 
 
+def driver_lib(so_name, sources, extra_flags=()):
+    """The one build recipe of the emulator drivers: tests/hipemu/_build/<so_name> from `sources` (names in
+    tests/hipemu) with the CXXFLAGS of tests/hipemu/Makefile and `extra_flags`, rebuilt when it is older than a source,
+    the Makefile, the emulator's header or any csrc/*.hpp; returns it loaded."""
+    so = os.path.join(EMU_DIR, "_build", so_name)
+    srcs = [os.path.join(EMU_DIR, f) for f in sources]
+    csrc = os.path.join(ROOT, "cuda-image-and-video-codec_amd", "csrc")
+    makefile = os.path.join(EMU_DIR, "Makefile")
+    deps = srcs + [makefile, os.path.join(EMU_DIR, "hip", "hip_runtime.h")] + \
+        [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
+        flags = next(ln.split("=", 1)[1].split() for ln in open(makefile) if ln.startswith("CXXFLAGS"))
+        os.makedirs(os.path.dirname(so), exist_ok=True)
+        subprocess.check_call([os.environ.get("CXX", "g++")] + flags + list(extra_flags) + ["-I", EMU_DIR, "-shared", "-o", so] + srcs)
+    return C.CDLL(so)
+
+
 def lib():
     global _lib
     if _lib is None:
-        if SO_OVERRIDE:
-            _lib = C.CDLL(SO_OVERRIDE)
-            _lib.emu_pack.restype = C.c_int
-            return _lib
-        subprocess.check_call(["make", "-C", EMU_DIR, "-s"])
-        _lib = C.CDLL(SO_PATH)
+        _lib = C.CDLL(SO_OVERRIDE) if SO_OVERRIDE else driver_lib("libpicsong_emu.so", ("emu_driver.cpp", "emu_runtime.cpp"))
         _lib.emu_pack.restype = C.c_int
     return _lib
 

@@ -1,11 +1,13 @@
 // TEST INFRASTRUCTURE ONLY -- the forward transform of a call that carries several frames (picsong_encode_frames: frame
-// 0's plan with grid.z = frames) on the CPU wave emulator, in the frame paths' int16 form, following launch_fwd_plan
-// (picsong_hip.hip): the plan, the band length (f2_pairs_batched) and the kernel (select_fwd2) are the library's own.
+// 0's plan with grid.z = frames) on the CPU wave emulator, in the frame paths' int16 form, through the library's own
+// launch_fwd_plan (launch_seq.hpp): the plan, the band length (f2_pairs_batched) and the head's kernel are its choice.
 #include <hip/hip_runtime.h>
 
-#include "../../cuda-image-and-video-codec_amd/csrc/kernel_select.hpp"
+#include "../../cuda-image-and-video-codec_amd/csrc/launch_seq.hpp"
 
 using namespace picsong;
+
+static const emu::Go go{};
 
 extern "C" {
 
@@ -17,18 +19,10 @@ int emu_dwt_forward_frames(const uint8_t *in, unsigned long long in_z, void *out
 {
     std::vector<FwdLaunch> plan = plan_dwt_forward(in, true, out, aw, ah, wl, qs, true);
     if (!plan_is_c16(plan)) return 0;
-    for (size_t l = 0; l < plan.size(); l++) { plan[l].a.src_z = l == 0 ? in_z : out_z; plan[l].a.dst_z = out_z; }
-    Fwd2Launch f2;
+    plan_frame_strides(plan, in_z, out_z);
+    bool fused01 = false;
+    launch_fwd_plan(go, lossy != 0, plan, (unsigned)frames, &fused01);
     const int nb = f2_pairs_batched(plan, lossy != 0, (unsigned)frames);
-    const bool fused01 = plan_dwt_fwd2(plan, f2, true, lossy != 0, nb);
-    if (fused01) {
-        const Fwd2Kernel k = select_fwd2(lossy != 0, true, false, nb);
-        emu::launch(dim3(f2.gx, f2.gy, (unsigned)frames), dim3(256), [&] { k(f2.a); });
-    }
-    for (size_t l = fused01 ? 2 : 0; l < plan.size(); l++) {
-        const FwdKernel k = select_fwd(lossy != 0, plan[l]);
-        emu::launch(dim3(plan[l].gx, plan[l].gy, (unsigned)frames), dim3(256), [&] { k(plan[l].a); });
-    }
     return 4 | (fused01 ? 1 : 0) | (fused01 && nb > 0 && nb != kF2Pairs ? 2 : 0);
 }
 

@@ -1,13 +1,15 @@
 // TEST INFRASTRUCTURE ONLY -- the k = 0 encoder's plane records (bpc_kernels.hpp: plane_record, plane_img_kernel,
-// plane_lut_img) and the one-wave-a-codeblock pack on the CPU wave emulator, launched as picsong_hip.hip launches them
-// (kernel_select.hpp: the encoder's kernel, grid and scratch).
+// plane_lut_img) and the one-wave-a-codeblock pack on the CPU wave emulator, launched by the sequences picsong_hip.hip
+// launches them by (launch_seq.hpp: launch_encoder, widen_staging, pack_frames) through the emulator's launcher.
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
-#include "../../cuda-image-and-video-codec_amd/csrc/kernel_select.hpp"
+#include "../../cuda-image-and-video-codec_amd/csrc/launch_seq.hpp"
 
 using namespace picsong;
+
+static const emu::Go go{};
 
 extern "C" int emu_plane_img_recs(int wl) { return plane_img_recs(wl); }
 
@@ -16,7 +18,7 @@ extern "C" void emu_plane_img_build(const int32_t *lut, const int *geo, int wl, 
 {
     const LutGeo g = lut_geo(geo);
     PlaneRec *img = reinterpret_cast<PlaneRec *>(out);
-    if (by_kernel) emu::launch(dim3(1), dim3(256), [&] { plane_img_kernel(lut, g, wl, img); });
+    if (by_kernel) go(plane_img_kernel, dim3(1), 256u, lut, g, wl, img);
     else for (int i = 0; i < plane_img_recs(wl); i++) img[i] = plane_record(lut, g, i / kMaxPlanes, i % kMaxPlanes);
 }
 
@@ -65,15 +67,12 @@ extern "C" void emu_bpc_encode_img(const int32_t *coeffs, int aw, int ah, int wl
         for (int f = 0; f < frames && f < 3; f++) { a.lut_c[f] = luts[f]; a.img_c[f] = imgs[f].data(); }
         waves = (unsigned)(frames * a.waves_per_frame);
     }
-    const BpcLaunch enc = select_encoder(false, false, false, waves);
-    std::vector<uint32_t> plane_scratch(enc.scratch_dwords, 0xDEADBEEFu);
+    std::vector<uint32_t> plane_scratch(encoder_scratch_dwords(false, false, waves), 0xDEADBEEFu);
     a.plane_scratch = plane_scratch.data();
-    emu::launch(dim3(enc.wgs), dim3(enc.threads), [&] { enc.kernel(a); });
+    launch_encoder(go, a, false, false, waves);
     memset(staging, 0xFF, (size_t)frames * (size_t)aw * (size_t)ah * 4);
     for (int f = 0; f < frames; f++)
-        emu::launch(dim3((unsigned)ncb), dim3(256), [&] {
-            widen_staging_kernel(st16.data() + (size_t)f * aw * ah, sizes + (size_t)f * ncb, 0, staging + (size_t)f * aw * ah);
-        });
+        widen_staging(go, st16.data() + (size_t)f * aw * ah, sizes + (size_t)f * ncb, 0, ncb, staging + (size_t)f * aw * ah);
 }
 
 // scan + pack of `frames` frames from 16-bit staging with the library's grid: pack_blocks<uint16_t>(ncb) workgroups of
@@ -82,12 +81,7 @@ extern "C" int emu_pack16_frames(const uint16_t *staging16, const int32_t *sizes
                                  uint16_t *out, size_t out_stride, int32_t *totals)
 {
     std::vector<int32_t> offsets((size_t)ncb * frames);
-    HeaderArg h;
-    memset(&h, 0, sizeof h);
-    if (header) { memcpy(h.h, header, sizeof h.h); h.has = 1; }
-    emu::launch(dim3((unsigned)frames), dim3(scan_threads(ncb)), [&] { scan_sizes_kernel(sizes, ncb, offsets.data(), totals); });
-    emu::launch(dim3(pack_blocks<uint16_t>(ncb), (unsigned)frames), dim3(256), [&] {
-        pack_kernel<uint16_t>(staging16, sizes, offsets.data(), totals, ncb, h, out, (size_t)ncb * 4096u, out_stride);
-    });
+    const Workspace w = { nullptr, nullptr, const_cast<int32_t *>(sizes), offsets.data(), totals, nullptr, nullptr };
+    pack_frames(go, staging16, w, ncb, (unsigned)frames, header, 1, out, (size_t)ncb * 4096u, out_stride);
     return totals[0];
 }

@@ -1,21 +1,15 @@
 // TEST INFRASTRUCTURE ONLY -- the rate calls' pieces on the CPU wave emulator: the search (rate_search.hpp, the very
-// stepper picsong_hip.hip walks), the unquantised forward transform (plan_dwt_forward_unit, launched the way
-// launch_fwd_plan / rate_transform do) and quantise_kernel with the launch and the arguments kernel_select.hpp gives it.
+// stepper picsong_hip.hip walks), the unquantised forward transform (plan_dwt_forward_unit through rate_transform's
+// sequences: launch_fwd_plan, rgb_forward_transform, launch_seq.hpp) and quantise_kernel with the launch and the
+// arguments kernel_select.hpp gives it.
 // Built by tests/test_rate_emulated.py with the flags of tests/hipemu/Makefile.
 #include <hip/hip_runtime.h>
 
-#include "../../cuda-image-and-video-codec_amd/csrc/kernel_select.hpp"
+#include "../../cuda-image-and-video-codec_amd/csrc/launch_seq.hpp"
 
 using namespace picsong;
 
-static void emu_fwd_levels(const std::vector<FwdLaunch> &plan, size_t from, unsigned frames)
-{
-    for (size_t l = from; l < plan.size(); l++) {
-        const FwdLaunch &f = plan[l];
-        const FwdKernel k = select_fwd(true, f);
-        emu::launch(dim3(f.gx, f.gy, frames), dim3(256), [&] { k(f.a); });
-    }
-}
+static const emu::Go go{};
 
 extern "C" {
 
@@ -60,14 +54,9 @@ int emu_rate_unit_forward(const void *in, int u8in, unsigned long long in_z, voi
                           int ah, int wl, int frames)
 {
     std::vector<FwdLaunch> plan = plan_dwt_forward_unit(in, u8in != 0, out, aw, ah, wl);
-    for (size_t l = 0; l < plan.size(); l++) { plan[l].a.src_z = l == 0 ? in_z : out_z; plan[l].a.dst_z = out_z; }
-    Fwd2Launch f2;
-    const bool fused01 = plan_dwt_fwd2(plan, f2, true, true);
-    if (fused01) {
-        const Fwd2Kernel k = select_fwd2(true, false);
-        emu::launch(dim3(f2.gx, f2.gy, (unsigned)frames), dim3(256), [&] { k(f2.a); });
-    }
-    emu_fwd_levels(plan, fused01 ? 2 : 0, (unsigned)frames);
+    plan_frame_strides(plan, in_z, out_z);
+    bool fused01 = false;
+    launch_fwd_plan(go, true, plan, (unsigned)frames, &fused01);
     return fused01 ? 1 : 0;
 }
 
@@ -76,15 +65,12 @@ int emu_rate_unit_forward(const void *in, int u8in, unsigned long long in_z, voi
 int emu_rate_unit_forward_rgb(const uint8_t *r, const uint8_t *g, const uint8_t *b, void *out, unsigned long long out_z,
                               int aw, int ah, int wl)
 {
-    std::vector<FwdLaunch> plan = plan_dwt_forward_unit(r, true, out, aw, ah, wl);
-    for (size_t l = 0; l < plan.size(); l++) { plan[l].a.src_z = l == 0 ? 0ull : out_z; plan[l].a.dst_z = out_z; }
-    plan[0].a.src_g = g; plan[0].a.src_b = b;
-    Fwd2Launch f2;
-    if (!plan_dwt_fwd2(plan, f2, true, true, kF2PairsRgb)) return 0;
-    const Fwd2Kernel k = select_fwd2_rgb_f32();
-    emu::launch(dim3(f2.gx, f2.gy, 3u), dim3(256), [&] { k(f2.a); });
-    emu_fwd_levels(plan, 2, 3u);
-    return 1;
+    const size_t P = (size_t)aw * ah;
+    std::vector<float> planes(3 * P);
+    auto plan_of = [&](const void *src, bool u8in) { return plan_dwt_forward_unit(src, u8in, out, aw, ah, wl); };
+    bool fused = false;
+    rgb_forward_transform(go, true, true, plan_of, false, r, g, b, planes.data(), P, 128, out_z, nullptr, &fused);
+    return fused ? 1 : 0;
 }
 
 // quantise_kernel over n float arrays for the K candidates js (candidate c as int16 where c16[c]); max_wgs > 0 caps the
@@ -97,7 +83,7 @@ void emu_rate_quantise(const void *src, unsigned long long src_z, void *dst, uns
     const QuantArgs a = quantise_args(src, src_z, dst, dst_z, aw, ah, wl, n, K, js, forms);
     QuantLaunch l = select_quantise(K, n, ah);
     if (max_wgs > 0 && l.wgs > (unsigned)max_wgs) l.wgs = (unsigned)max_wgs;
-    emu::launch(dim3(l.wgs), dim3(256), [&] { l.kernel(a); });
+    go(l.kernel, dim3(l.wgs), 256u, a);
 }
 
 int emu_rate_coef16_ok(int wl, int j, int in_max, int aw, int ah)

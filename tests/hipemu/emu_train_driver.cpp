@@ -1,12 +1,14 @@
 // TEST INFRASTRUCTURE ONLY -- the training statistics (picsong_train_coeffs) on the CPU wave emulator: bpc_stats_kernel
 // with the grid, the scratch and the arguments picsong_hip.hip gives it (select_stats / stats_args, kernel_select.hpp)
-// and the same kernel source (train_kernels.hpp).
+// and the same kernel source (train_kernels.hpp), run through the emulator's launcher.
 // Built by tests/test_train_emulated.py with the flags of tests/hipemu/Makefile.
 #include <hip/hip_runtime.h>
 
-#include "../../cuda-image-and-video-codec_amd/csrc/kernel_select.hpp"
+#include "../../cuda-image-and-video-codec_amd/csrc/launch_seq.hpp"
 
 using namespace picsong;
+
+static const emu::Go go{};
 
 extern "C" {
 
@@ -28,7 +30,7 @@ int emu_train_counts(const void *coef, int form, int aw, int ah, int wl, const i
     }
     std::vector<uint32_t> ps(l.scratch_dwords, 0xDEADBEEFu);
     const BpcArgs a = stats_args(aw, ah, wl, g, flag, coef, form == 1, form == 2, frames, coef_z, ps.data());
-    emu::launch(dim3(l.wgs), dim3(l.threads), [&] { l.kernel(a, counts, (int)pairs); });
+    go(l.kernel, dim3(l.wgs), l.threads, a, counts, (int)pairs);
     return total;
 }
 

@@ -1,13 +1,16 @@
 // TEST INFRASTRUCTURE ONLY -- the window decode (picsong_decode_frame_window) on the CPU wave emulator: the decoder over
-// the rectangle table of window_plan and the cone's synthesis (dwt_window_kernel), through the same plan functions
-// (launch_plan.hpp, window_kernels.hpp), the same choice of kernel, grid and scratch (kernel_select.hpp) and the same
-// kernel sources as cuda-image-and-video-codec_amd/csrc/picsong_hip.hip.
+// the rectangle table of window_plan and the cone's synthesis (dwt_window_kernel), through the same launch sequences
+// (launch_seq.hpp: stream_intake, launch_decoder, run_window), plan functions (launch_plan.hpp, window_kernels.hpp),
+// choice of kernel, grid and scratch (kernel_select.hpp) and kernel sources as
+// cuda-image-and-video-codec_amd/csrc/picsong_hip.hip, run through the emulator's launcher.
 // Built by tests/test_window_decode_emulated.py with the flags of tests/hipemu/Makefile.
 #include <hip/hip_runtime.h>
 
-#include "../../cuda-image-and-video-codec_amd/csrc/kernel_select.hpp"
+#include "../../cuda-image-and-video-codec_amd/csrc/launch_seq.hpp"
 
 using namespace picsong;
+
+static const emu::Go go{};
 
 extern "C" {
 
@@ -36,40 +39,20 @@ int emu_decode_window(const uint16_t *stream, unsigned stream_shorts, int aw, in
     const int ncb = (aw / 64) * (ah / 64);
     const WindowPlan plan = window_plan(aw, ah, wl, lossy != 0, r, x, y, w, h);
     const size_t P = (size_t)aw * ah;
-    const size_t extra = [&] { size_t e = 0; for (int l = 1; l < wl; l++) e += (size_t)(aw >> l) * (size_t)(ah >> l); return e; }();
-    std::vector<float> work(P + extra, std::nanf(""));
-
-    std::vector<int32_t> sizes(ncb), offsets(ncb), stage;
+    std::vector<float> work(P + dwt_extra(aw, ah, wl), std::nanf(""));
+    std::vector<int32_t> sizes(ncb), offsets(ncb), stage(staging ? (size_t)ncb * 4096 : 0, 0);
     int32_t total = 0;
-    int bad = 0, res = 0;
+    int bad = 0;
     BpcArgs a = bpc_frame_args(aw, ah, wl, lut, lut_geo(geo), flag);
-    a.sizes = sizes.data(); a.coeffs_out = coef;
     a.k = k; a.n_tables = n_tables;
     const unsigned waves = (unsigned)window_bpc_table(a, plan);
-    if (staging) {
-        stage.assign((size_t)ncb * 4096, 0);
-        emu::launch(dim3((unsigned)((ncb + 255) / 256)), dim3(256), [&] { read_sizes_kernel(stream, ncb, sizes.data(), &bad); });
-        emu::launch(dim3(1), dim3(scan_threads(ncb)), [&] { scan_sizes_kernel(sizes.data(), ncb, offsets.data(), &total); });
-        emu::launch(dim3((unsigned)ncb), dim3(256), [&] { unpack_kernel(stream, sizes.data(), offsets.data(), ncb, stage.data()); });
-        a.staging = stage.data();
-    } else {
-        emu::launch(dim3(1), dim3(scan_threads(ncb)), [&] { scan_stream_kernel(stream, ncb, sizes.data(), offsets.data(), &total, &bad, 0); });
-        a.cw16 = stream; a.cw16_offsets = offsets.data(); a.cw16_total = &total; a.cw16_max = stream_shorts;
-    }
-    if (bad) res |= 8;
+    std::vector<uint32_t> ps(decoder_scratch_dwords(false, k > 0.0f, waves), 0xDEADBEEFu);
+    const Workspace ws = { work.data(), stage.data(), sizes.data(), offsets.data(), &total, ps.data(), coef };
+    stream_intake(go, stream, 1u, 0, !staging, ncb, P, ws, &bad);
     // (32-bit coefficients: a window's synthesis reads no 16-bit ones)
-    const BpcLaunch dec = select_decoder(false, k > 0.0f, k > 0.0f && bulk_compact(aw, ah, wl, a.g), !staging, false, waves);
-    std::vector<uint32_t> ps(dec.scratch_dwords, 0xDEADBEEFu);
-    a.plane_scratch = ps.data();
-    emu::launch(dim3(dec.wgs), dim3(dec.threads), [&] { dec.kernel(a); });
-
-    // ---- the cone's synthesis (run_window)
-    std::vector<WinLaunch> syn = plan_window_synthesis(plan, coef, work.data(), P, aw, ah, qs, pixels, pitch, 128);
-    for (const WinLaunch &f : syn) {
-        const WinKernel kw = select_window(lossy != 0, f.u8);
-        emu::launch(f.grid, dim3(256), [&] { kw(f.a); });
-    }
-    return res;
+    launch_decoder(go, a, false, waves, k > 0.0f && bulk_compact(aw, ah, wl, a.g), ws, staging ? nullptr : stream, 0, stream_shorts, false);
+    run_window(go, lossy != 0, plan, coef, work.data(), P, aw, ah, qs, 128, 1u, 0, 0, pixels, pitch, 0);
+    return bad ? 8 : 0;
 }
 
 }  // extern "C"

@@ -76,6 +76,15 @@ enum Op { OP_DPP_SHR, OP_DPP_SHL, OP_BALLOT, OP_SHFL_XOR, OP_SHFL_UP, OP_READFIR
 uint64_t collective(Op op, uint64_t in, unsigned aux, uint64_t old);
 void barrier();
 void launch(dim3 grid, dim3 block, const std::function<void()> &body);
+// the drivers' launcher of the product's launch sequences (launch_seq.hpp): go(kernel, grid, threads, args...) -> 0
+struct Go {
+    template <typename K, typename... A>
+    int operator()(K k, dim3 grid, unsigned threads, const A &...args) const
+    {
+        launch(grid, dim3(threads), [&] { k(args...); });
+        return 0;
+    }
+};
 
 }  // namespace emu
 

@@ -8,23 +8,15 @@ frame, a dense one in which many groups hold context 8, and a sparse one in whic
 gate.  The context-8 sites of the dense and the sparse input are counted from the oracle's coefficients beside it, so a
 test cannot pass by never reaching the gated lookup, or by never skipping it.  With one (-m gpu): the same inputs as
 pixels through picsong_encode_frame / picsong_encode_frames against the oracle's codestreams, and one 9/7 frame."""
-import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import emu_lib as E
 import oracle_lib as orc
-from emu_lib import EMU_DIR, _p
+from emu_lib import _p, driver_lib
 
-OUT = os.path.join(EMU_DIR, "_build")
-SO = os.path.join(OUT, "libpicsong_emu_subband.so")
-# the flags of tests/hipemu/Makefile
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-strict-aliasing", "-march=x86-64-v3", "-Wall",
-            "-Wno-unused-variable", "-Wno-unused-parameter", "-Wno-unknown-pragmas", "-Wno-unused-but-set-variable"]
-CSRC = os.path.join(os.path.dirname(EMU_DIR), "..", "cuda-image-and-video-codec_amd", "csrc")
 _lib = None
 
 
@@ -32,13 +24,7 @@ def lib():
     global _lib
     if _lib is None:
         orc.lib()
-        srcs = [os.path.join(EMU_DIR, f) for f in ("emu_subband_driver.cpp", "emu_runtime.cpp")]
-        deps = srcs + [os.path.join(EMU_DIR, "hip", "hip_runtime.h")] + \
-            [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-            os.makedirs(OUT, exist_ok=True)
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + ["-I", EMU_DIR, "-shared", "-o", SO] + srcs)
-        _lib = C.CDLL(SO)
+        _lib = driver_lib("libpicsong_emu_subband.so", ("emu_subband_driver.cpp", "emu_runtime.cpp"))
     return _lib
 
 

@@ -11,36 +11,21 @@ oracle's transform, at the geometries where its two newer forms can go wrong:
 
 wl 2 (level 1 is the transform's last: its LL is a coded int16 subband) and wl 3 (its LL goes on to level 2 as 32 bits)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import emu_lib as E
 import oracle_lib as orc
-from emu_lib import EMU_DIR, _p
+from emu_lib import _p, driver_lib
 
-OUT = os.path.join(EMU_DIR, "_build")
-SO = os.path.join(OUT, "libpicsong_emu_fwd2.so")
-# the flags of tests/hipemu/Makefile
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-strict-aliasing", "-march=x86-64-v3", "-Wall",
-            "-Wno-unused-variable", "-Wno-unused-parameter", "-Wno-unknown-pragmas", "-Wno-unused-but-set-variable",
-            "-Wno-attributes", "-DPICSONG_DWT_F2_PAIRS_BATCH=16"]
-CSRC = os.path.join(os.path.dirname(EMU_DIR), "..", "cuda-image-and-video-codec_amd", "csrc")
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        srcs = [os.path.join(EMU_DIR, f) for f in ("emu_fwd2_driver.cpp", "emu_runtime.cpp")]
-        deps = srcs + [os.path.join(EMU_DIR, "hip", "hip_runtime.h")] + \
-            [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-            os.makedirs(OUT, exist_ok=True)
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + ["-I", EMU_DIR, "-shared", "-o", SO] + srcs)
-        _lib = C.CDLL(SO)
+        _lib = driver_lib("libpicsong_emu_fwd2.so", ("emu_fwd2_driver.cpp", "emu_runtime.cpp"), ("-Wno-attributes", "-DPICSONG_DWT_F2_PAIRS_BATCH=16"))
     return _lib
 
 

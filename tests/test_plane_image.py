@@ -5,34 +5,20 @@ On the CPU wave emulator (tests/hipemu/emu_plane_img_driver.cpp): the image agai
 encoder reading the image against the oracle, the pack against po_bitstream_pack.  On the GPU (-m gpu): the context's
 own images -- host tables, caller device tables, three tables in one launch, a table replaced between calls."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as orc
-from emu_lib import EMU_DIR, _geo, _p
+from emu_lib import _geo, _p, driver_lib
 
-OUT = os.path.join(EMU_DIR, "_build")
-SO = os.path.join(OUT, "libpicsong_emu_plane_img.so")
-# the flags of tests/hipemu/Makefile
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-strict-aliasing", "-march=x86-64-v3", "-Wall",
-            "-Wno-unused-variable", "-Wno-unused-parameter", "-Wno-unknown-pragmas", "-Wno-unused-but-set-variable"]
-CSRC = os.path.join(os.path.dirname(EMU_DIR), "..", "cuda-image-and-video-codec_amd", "csrc")
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        srcs = [os.path.join(EMU_DIR, f) for f in ("emu_plane_img_driver.cpp", "emu_runtime.cpp")]
-        deps = srcs + [os.path.join(EMU_DIR, "hip", "hip_runtime.h")] + \
-            [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-            os.makedirs(OUT, exist_ok=True)
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + ["-I", EMU_DIR, "-shared", "-o", SO] + srcs)
-        _lib = C.CDLL(SO)
+        _lib = driver_lib("libpicsong_emu_plane_img.so", ("emu_plane_img_driver.cpp", "emu_runtime.cpp"))
     return _lib
 
 

@@ -3,7 +3,6 @@ rate_search.hpp against the reference procedure (rate_ref.bisect), and the unqua
 quantise_kernel against the oracle's fused transform at q(j), bit for bit in both coefficient forms."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,28 +10,15 @@ import pytest
 import emu_lib as E
 import oracle_lib as orc
 import rate_ref as rr
-from emu_lib import EMU_DIR, _p
+from emu_lib import _p, driver_lib
 
-OUT = os.path.join(EMU_DIR, "_build")
-SO = os.path.join(OUT, "libpicsong_emu_rate.so")
-# the flags of tests/hipemu/Makefile
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-strict-aliasing", "-march=x86-64-v3", "-Wall",
-            "-Wno-unused-variable", "-Wno-unused-parameter", "-Wno-unknown-pragmas", "-Wno-unused-but-set-variable",
-            "-Wno-attributes"]
-CSRC = os.path.join(os.path.dirname(EMU_DIR), "..", "cuda-image-and-video-codec_amd", "csrc")
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        srcs = [os.path.join(EMU_DIR, f) for f in ("emu_rate_driver.cpp", "emu_runtime.cpp")]
-        deps = srcs + [os.path.join(EMU_DIR, "hip", "hip_runtime.h")] + \
-            [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-            os.makedirs(OUT, exist_ok=True)
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + ["-I", EMU_DIR, "-shared", "-o", SO] + srcs)
-        _lib = C.CDLL(SO)
+        _lib = driver_lib("libpicsong_emu_rate.so", ("emu_rate_driver.cpp", "emu_runtime.cpp"), ("-Wno-attributes",))
         _lib.emu_rate_q.restype = C.c_float
     return _lib
 

@@ -1,35 +1,21 @@
 """The training statistics kernel (bpc_stats_kernel, picsong_train_coeffs) on the CPU wave emulator
 (tests/hipemu/emu_train_driver.cpp) against the reference model (train_ref.py): equal counts, [entry][2], exactly."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import train_cases as tc
 import train_ref as tr
-from emu_lib import EMU_DIR, _p
+from emu_lib import _p, driver_lib
 
-OUT = os.path.join(EMU_DIR, "_build")
-SO = os.path.join(OUT, "libpicsong_emu_train.so")
-# the flags of tests/hipemu/Makefile
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-strict-aliasing", "-march=x86-64-v3", "-Wall",
-            "-Wno-unused-variable", "-Wno-unused-parameter", "-Wno-unknown-pragmas", "-Wno-unused-but-set-variable"]
-CSRC = os.path.join(os.path.dirname(EMU_DIR), "..", "cuda-image-and-video-codec_amd", "csrc")
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        srcs = [os.path.join(EMU_DIR, f) for f in ("emu_train_driver.cpp", "emu_runtime.cpp")]
-        deps = srcs + [os.path.join(EMU_DIR, "hip", "hip_runtime.h")] + \
-            [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-            os.makedirs(OUT, exist_ok=True)
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + ["-I", EMU_DIR, "-shared", "-o", SO] + srcs)
-        _lib = C.CDLL(SO)
+        _lib = driver_lib("libpicsong_emu_train.so", ("emu_train_driver.cpp", "emu_runtime.cpp"))
     return _lib
 
 

@@ -1,8 +1,6 @@
 """The window decode on the CPU wave emulator (tests/hipemu/emu_window_driver.cpp): the decoder over the window's
 codeblock table and the cone's synthesis (dwt_window_kernel), against the oracle's crop of LL_r."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,14 +8,8 @@ import pytest
 import oracle_lib as orc
 import reduced_ref as rr
 import window_ref as wr
-from emu_lib import EMU_DIR, _geo, _p
+from emu_lib import _geo, _p, driver_lib
 
-OUT = os.path.join(EMU_DIR, "_build")
-SO = os.path.join(OUT, "libpicsong_emu_window.so")
-# the flags of tests/hipemu/Makefile
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-strict-aliasing", "-march=x86-64-v3", "-Wall",
-            "-Wno-unused-variable", "-Wno-unused-parameter", "-Wno-unknown-pragmas", "-Wno-unused-but-set-variable"]
-CSRC = os.path.join(os.path.dirname(EMU_DIR), "..", "cuda-image-and-video-codec_amd", "csrc")
 FILL = 0x3A5A5A5A
 _lib = None
 
@@ -25,13 +17,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        srcs = [os.path.join(EMU_DIR, f) for f in ("emu_window_driver.cpp", "emu_runtime.cpp")]
-        deps = srcs + [os.path.join(EMU_DIR, "hip", "hip_runtime.h")] + \
-            [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-            os.makedirs(OUT, exist_ok=True)
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + ["-I", EMU_DIR, "-shared", "-o", SO] + srcs)
-        _lib = C.CDLL(SO)
+        _lib = driver_lib("libpicsong_emu_window.so", ("emu_window_driver.cpp", "emu_runtime.cpp"))
     return _lib
 
 
