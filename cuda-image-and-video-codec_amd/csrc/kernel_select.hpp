@@ -13,6 +13,7 @@
 #include "dwt_kernels.hpp"
 #include "launch_plan.hpp"
 #include "pack_kernels.hpp"
+#include "quality_kernels.hpp"
 #include "rate_kernels.hpp"
 #include "rate_search.hpp"
 #include "train_kernels.hpp"
@@ -29,6 +30,7 @@ using WinKernel = void (*)(WinSynArgs);
 using BpcKernel = void (*)(BpcArgs);
 using StatsKernel = void (*)(BpcArgs, unsigned long long *, int);
 using QuantKernel = void (*)(QuantArgs);
+using SseKernel = void (*)(SseArgs);
 
 // ---- forward transform: one level (256 threads, grid f.gx x f.gy x frames)
 template <int BAND, bool VEC>
@@ -244,10 +246,12 @@ inline bool bulk_compact(int aw, int ah, int wl, const LutGeo &g)
 // ---- the rate calls' quantisation pass (quantise_kernel, rate_kernels.hpp): K = 1..3 candidate gains over the
 // unquantised float arrays of n frames, a workgroup (256 threads) a row at a time
 struct QuantLaunch { QuantKernel kernel; unsigned wgs; };
-inline QuantLaunch select_quantise(int K, int n, int ah)
+// i32 (the quality calls' probes): the int32 form, one candidate a launch
+inline QuantLaunch select_quantise(int K, int n, int ah, bool i32 = false)
 {
     const size_t rows = (size_t)n * (size_t)ah;
     const unsigned wgs = (unsigned)(rows > 8192 ? 8192 : rows);
+    if (i32) return { quantise_kernel<1, true>, wgs };
     return { K >= 3 ? quantise_kernel<3> : (K == 2 ? quantise_kernel<2> : quantise_kernel<1>), wgs };
 }
 // its arguments: the gains q(j) of `js`, candidate c as int16 where c16[c]; frames src_z / dst_z bytes apart
@@ -265,6 +269,29 @@ inline QuantArgs quantise_args(const void *src, unsigned long long src_z, void *
     for (int l = 0; l < 10; l++)
         for (int k = 0; k < 4; k++) a.q[l][k] = kQSteps[l][k];
     return a;
+}
+
+// ---- the distortion measurement (sse_kernel, quality_kernels.hpp): the visible w x h samples of n pairs of padded
+// arrays, 256 threads, a tile of 256 * kSseTileLoads vectors a workgroup and step, grid-stride beyond kSseMaxWgs.
+// The vector form where both sides' pointers, pitches and strides are 16-byte aligned, else the per-byte one.
+struct SseLaunch { SseKernel kernel; unsigned wgs; };
+inline SseArgs sse_args(const uint8_t *a, size_t a_pitch, unsigned long long a_z, const uint8_t *b, size_t b_pitch,
+                        unsigned long long b_z, int w, int h, int n, unsigned long long *out)
+{
+    SseArgs s;
+    memset(&s, 0, sizeof s);
+    s.a = a; s.a_z = a_z; s.a_pitch = (uint32_t)a_pitch;
+    s.b = b; s.b_z = b_z; s.b_pitch = (uint32_t)b_pitch;
+    s.out = out; s.W = w; s.H = h; s.n = n;
+    return s;
+}
+inline SseLaunch select_sse(const SseArgs &s)
+{
+    const bool vec = ((((uintptr_t)s.a) | ((uintptr_t)s.b) | s.a_z | s.b_z | s.a_pitch | s.b_pitch) & 15u) == 0;
+    const size_t items = (size_t)((s.W + 15) / 16) * (size_t)s.H, tile = 256u * (size_t)kSseTileLoads;
+    const size_t tiles = (items + tile - 1) / tile * (size_t)s.n;
+    const unsigned wgs = (unsigned)(tiles > kSseMaxWgs ? kSseMaxWgs : (tiles < 1 ? 1 : tiles));
+    return { vec ? sse_kernel<true> : sse_kernel<false>, wgs };
 }
 
 // workgroups (256 threads) of the element-wise kernels -- level shift, clamp, RGB transforms -- over n items, grid-stride

@@ -256,4 +256,68 @@ int pack_frames(const Go &go, const W *staging, const Workspace &w, int ncb, uns
     return go(pack_kernel<W>, dim3(pack_blocks<W>(ncb), n), 256u, staging, w.sizes, w.offsets, w.total, ncb, h, streams, P, stream_stride);
 }
 
+// ---- distortion (quality_kernels.hpp): out[0 .. n) = the SSE over the visible w x h samples of n pairs of padded
+// arrays, zeroed on the launcher's stream first
+template <class Go>
+int frames_sse(const Go &go, const uint8_t *a, size_t a_pitch, unsigned long long a_z, const uint8_t *b, size_t b_pitch,
+               unsigned long long b_z, int w, int h, int n, unsigned long long *out)
+{
+    if (int rc = go(sse_zero_kernel, dim3(1), 64u, out, n)) return rc;
+    const SseArgs s = sse_args(a, a_pitch, a_z, b, b_pitch, b_z, w, h, n, out);
+    return go(select_sse(s).kernel, dim3(select_sse(s).wgs), 256u, s);
+}
+
+// ---- a probe of the quality calls (picsong_encode_frame_quality and its mirrors): the distortion of the nf coded arrays
+// at q(j), without the coder -- it is lossless over the quantised coefficients, so the decoder's pixels follow from them:
+//   quantise_kernel's int32 form over the unquantised float arrays (unit, unit_z bytes apart) into coef_i (P words each);
+//   the synthesis at qs = q(j) with the DIVIDING kernels (fast = false: no per-qs verification of reciprocals, which
+//   costs far more host time than the probe's GPU time; every reciprocal form is verified against these), grid.z = array,
+//   work buffers of (P + extra) floats each, the clamped u8 pixels into `pix` (P bytes each);
+//   sse_kernel against the input into out[0 .. nf).
+// Grey (r == nullptr): nf frames at `frames`, frame_stride bytes apart.  RGB (nf = 3): the components' planes leave the
+// synthesis as float samples (the fused 9/7 RGB tail is the lean kernel's and wants the verified reciprocals:
+// inv_rgb_tail_ok), the inverse ICT kernel writes R, G, B into pix, each compared with its input plane.
+struct QualityProbe {
+    const void *unit; unsigned long long unit_z;
+    int32_t *coef_i; void *work; uint8_t *pix;
+    int aw, ah, wl, w, h, off;
+    size_t P, extra;
+    int nf;
+    const uint8_t *frames; size_t frame_stride;
+    const uint8_t *r, *g, *b;
+};
+// mark(k): called after the quantise pass (1), after the synthesis' last launch (2) and after the SSE (3) -- the
+// library's stage timers; returns 0
+struct NoMark { int operator()(int) const { return 0; } };
+template <class Go, class Mark = NoMark>
+int quality_probe(const Go &go, const QualityProbe &p, int j, unsigned long long *out, const Mark &mark = Mark())
+{
+    const bool rgb = p.r != nullptr;
+    const bool forms[kQuantMaxK] = { false, false, false };
+    const QuantArgs qa = quantise_args(p.unit, p.unit_z, p.coef_i, (unsigned long long)p.P * 4ull, p.aw, p.ah, p.wl, p.nf, 1, &j, forms);
+    if (int rc = go(select_quantise(1, p.nf, p.ah, true).kernel, dim3(select_quantise(1, p.nf, p.ah, true).wgs), 256u, qa)) return rc;
+    if (int rc = mark(1)) return rc;
+    bool fused = false;
+    const std::vector<InvLaunch> plan = plan_inverse_frames(p.coef_i, p.work, rgb ? nullptr : p.pix, &fused, (unsigned)p.nf, p.P, false, rgb,
+                                                            0, p.aw, p.ah, p.wl, rate_q(j), false, p.off, p.P, p.extra);
+    if (int rc = run_inverse(go, true, false, plan, (unsigned)p.nf)) return rc;
+    const char *img = (const char *)plan.back().a.dst;       // (the finest level's samples where it did not write pixels)
+    const size_t z = (p.P + p.extra) * 4;
+    if (rgb) {
+        if (int rc = rgb_inverse(go, true, img, img + z, img + 2 * z, p.pix, p.pix + p.P, p.pix + 2 * p.P, p.P / 4, p.off)) return rc;
+        if (int rc = mark(2)) return rc;
+        const uint8_t *in[3] = { p.r, p.g, p.b };
+        for (int k = 0; k < 3; k++)
+            if (int rc = frames_sse(go, p.pix + (size_t)k * p.P, (size_t)p.aw, 0, in[k], (size_t)p.aw, 0, p.w, p.h, 1, out + k)) return rc;
+        return mark(3);
+    }
+    if (!fused)
+        for (int f = 0; f < p.nf; f++)
+            if (int rc = clamp_pixels(go, true, img + (size_t)f * z, p.pix + (size_t)f * p.P, p.P / 4, p.off)) return rc;
+    if (int rc = mark(2)) return rc;
+    if (int rc = frames_sse(go, p.pix, (size_t)p.aw, (unsigned long long)p.P, p.frames, (size_t)p.aw, (unsigned long long)p.frame_stride,
+                            p.w, p.h, p.nf, out)) return rc;
+    return mark(3);
+}
+
 }  // namespace picsong

@@ -97,6 +97,10 @@ struct picsong_ctx {
     void *rate_coef;
     int rate_cap;
     size_t rate_z;
+    // quality calls: the probes' clamped pixels (q_cap planes of P bytes), the candidates' sums on the device and pinned
+    uint8_t *q_pix;
+    int q_cap;
+    unsigned long long *d_sse, *h_sse;      // kQualitySlots each (lazy)
 };
 
 // PICSONG_DWT_INV97=0 keeps the 9/7 synthesis levels off the lean kernel (select_inv): read once per process
@@ -395,6 +399,9 @@ void picsong_ctx_destroy(picsong_ctx *c)
     for (int k = 0; k < 3; k++) if (c->d_train[k]) (void)hipFree(c->d_train[k]);
     if (c->train_scratch) (void)hipFree(c->train_scratch);
     if (c->rate_coef) (void)hipFree(c->rate_coef);
+    if (c->q_pix) (void)hipFree(c->q_pix);
+    if (c->d_sse) (void)hipFree(c->d_sse);
+    if (c->h_sse) (void)hipHostFree(c->h_sse);
     if (c->prof_ev) {
         for (hipEvent_t e : *c->prof_ev) (void)hipEventDestroy(e);
         delete c->prof_ev;
@@ -1513,6 +1520,33 @@ static int rate_probe(picsong_ctx *c, BpcArgs a, int nf, int m, const int *js, h
     return HipGo{ s }(scan_sizes_kernel, dim3((unsigned)(m * nf)), scan_threads(c->ncb), c->batch.sizes, c->ncb, c->batch.offsets, c->batch.total);
 }
 
+// step 3: the pack of the result j, coded as candidate `slot` of the batch buffers by rate_probe, with its gain in the
+// header; the lengths to h_totals and where the plain calls leave theirs.  Synchronises the stream.
+static int rate_finish(picsong_ctx *c, const RateJob &job, int nf, int j, int slot, hipStream_t s, int *h_totals)
+{
+    int rc;
+    const bool rgb = c->p.is_rgb != 0;
+    Workspace w = c->batch;
+    w.sizes += (size_t)slot * (size_t)nf * (size_t)c->ncb; w.offsets += (size_t)slot * (size_t)nf * (size_t)c->ncb;
+    w.total += (size_t)slot * (size_t)nf;
+    const uint16_t *st16 = reinterpret_cast<const uint16_t *>(c->batch.staging) + (size_t)slot * (size_t)nf * c->P;
+    picsong_params hp = c->p;
+    hp.qs = rate_q(j);
+    uint16_t hdr[PICSONG_HDR_SHORTS];
+    picsong_header_pack(&hp, hdr);
+    const bool has_hdr = rgb ? (job.header_mask & 7) != 0 : (job.first_iter <= 0 && job.first_iter + job.n > 0);
+    const int has = rgb ? -(job.header_mask & 7) : -job.first_iter + 1;
+    if ((rc = pack_frames(HipGo{ s }, st16, w, c->ncb, (unsigned)nf, has_hdr ? hdr : nullptr, has, job.d_streams, c->P, job.stream_stride))) return rc;
+    // (the lengths where the plain calls leave theirs: picsong_last_total(s) / picsong_copy_last_totals cover a rate call)
+    if (slot > 0) HIP_TRY(hipMemcpyAsync(c->batch.total, w.total, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (job.single) HIP_TRY(hipMemcpyAsync(c->one.total, w.total, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->h_totals, w.total, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int f = 0; f < nf; f++) h_totals[f] = c->h_totals[f];
+    c->last_batch = job.single ? 0 : nf;
+    return PICSONG_OK;
+}
+
 static int rate_impl(picsong_ctx *c, const RateJob &job, size_t target_shorts, int j_min, int j_max, hipStream_t s, int *h_j,
                      int *h_totals, const char *who)
 {
@@ -1562,24 +1596,7 @@ static int rate_impl(picsong_ctx *c, const RateJob &job, size_t target_shorts, i
         if ((rc = rate_probe(c, a, nf, 1, &j, s))) return rc;
         slot = 0;
     }
-    Workspace w = c->batch;
-    w.sizes += (size_t)slot * (size_t)nf * (size_t)c->ncb; w.offsets += (size_t)slot * (size_t)nf * (size_t)c->ncb;
-    w.total += (size_t)slot * (size_t)nf;
-    const uint16_t *st16 = reinterpret_cast<const uint16_t *>(c->batch.staging) + (size_t)slot * (size_t)nf * c->P;
-    picsong_params hp = c->p;
-    hp.qs = rate_q(j);
-    uint16_t hdr[PICSONG_HDR_SHORTS];
-    picsong_header_pack(&hp, hdr);
-    const bool has_hdr = rgb ? (job.header_mask & 7) != 0 : (job.first_iter <= 0 && job.first_iter + job.n > 0);
-    const int has = rgb ? -(job.header_mask & 7) : -job.first_iter + 1;
-    if ((rc = pack_frames(HipGo{ s }, st16, w, c->ncb, (unsigned)nf, has_hdr ? hdr : nullptr, has, job.d_streams, c->P, job.stream_stride))) return rc;
-    // (the lengths where the plain calls leave theirs: picsong_last_total(s) / picsong_copy_last_totals cover a rate call)
-    if (slot > 0) HIP_TRY(hipMemcpyAsync(c->batch.total, w.total, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    if (job.single) HIP_TRY(hipMemcpyAsync(c->one.total, w.total, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->h_totals, w.total, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int f = 0; f < nf; f++) h_totals[f] = c->h_totals[f];
-    c->last_batch = job.single ? 0 : nf;
+    if ((rc = rate_finish(c, job, nf, j, slot, s, h_totals))) return rc;
     *h_j = j;
     return PICSONG_OK;
 }
@@ -1621,6 +1638,167 @@ int picsong_encode_rgb_frame_rate(picsong_ctx *c, const uint8_t *d_r, const uint
     if ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 3u) return fail(PICSONG_ERR_ARG, "%s: the planes need 4-byte alignment", who);
     const RateJob job = { 1, nullptr, 0, d_r, d_g, d_b, 0, header_mask, d_streams, stream_stride, false };
     return rate_impl(c, job, target_shorts, j_min, j_max, (hipStream_t)stream, h_j, h_totals, who);
+}
+
+// ---------------------------------------------------------------------------------------------
+// quality calls: encode to a target distortion (rate_search.hpp: QualityStepper; quality_kernels.hpp: sse_kernel;
+// launch_seq.hpp: frames_sse and quality_probe, the sequences the emulator driver of the tests runs too)
+//   1. the unit-step transform, once (rate_transform);
+//   2. per round: quality_probe for each of the round's candidates, back to back over ONE set of nf-frame buffers
+//      (batch.coef_i, batch.coef, q_pix), candidate i's sums in slots i * nf .. of d_sse; ONE read-back through pinned
+//      memory.  No coder launch;
+//   3. the result is quantised, coded and packed as the rate calls' final step (rate_probe of it alone, rate_finish).
+// PICSONG_RATE_K=1 keeps one candidate a round here too.
+// ---------------------------------------------------------------------------------------------
+constexpr int kQualitySlots = kRateMaxK * 16;
+
+int picsong_psnr_to_sse(double psnr_db, uint64_t samples, uint64_t *max_sse)
+{
+    if (!max_sse) return fail(PICSONG_ERR_ARG, "psnr_to_sse: null argument");
+    if (samples == 0) return fail(PICSONG_ERR_ARG, "psnr_to_sse: no samples");
+    if (!std::isfinite(psnr_db)) return fail(PICSONG_ERR_ARG, "psnr_to_sse: the PSNR must be finite");
+    const double v = std::floor(65025.0 * (double)samples / std::pow(10.0, psnr_db / 10.0));
+    *max_sse = v >= 18446744073709551615.0 ? UINT64_MAX : (uint64_t)v;
+    return PICSONG_OK;
+}
+
+int picsong_sse_to_psnr(uint64_t sse, uint64_t samples, double *psnr_db)
+{
+    if (!psnr_db) return fail(PICSONG_ERR_ARG, "sse_to_psnr: null argument");
+    if (samples == 0) return fail(PICSONG_ERR_ARG, "sse_to_psnr: no samples");
+    *psnr_db = sse == 0 ? HUGE_VAL : 10.0 * std::log10(65025.0 * (double)samples / (double)sse);
+    return PICSONG_OK;
+}
+
+int picsong_frames_sse(picsong_ctx *c, int n, const uint8_t *d_a, size_t a_stride, const uint8_t *d_b, size_t b_stride,
+                       uint64_t *d_sse, void *stream)
+{
+    if (!c || !d_a || !d_b || !d_sse) return fail(PICSONG_ERR_ARG, "frames_sse: null argument");
+    if (n < 1 || n > kSseMaxFrames) return fail(PICSONG_ERR_ARG, "frames_sse: %d frames outside 1..%d", n, kSseMaxFrames);
+    if (n > 1 && (a_stride < c->P || b_stride < c->P)) return fail(PICSONG_ERR_ARG, "frames_sse: strides smaller than a padded frame");
+    HIP_TRY(hipSetDevice(c->device));
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the kernel's sums are the interface's");
+    return frames_sse(HipGo{ (hipStream_t)stream }, d_a, (size_t)c->aw, n > 1 ? a_stride : 0, d_b, (size_t)c->aw, n > 1 ? b_stride : 0,
+                      c->p.width, c->p.height, n, reinterpret_cast<unsigned long long *>(d_sse));
+}
+
+static int ensure_quality(picsong_ctx *c, int frames)
+{
+    if (!c->d_sse) HIP_TRY(hipMalloc(&c->d_sse, kQualitySlots * sizeof(unsigned long long)));
+    if (!c->h_sse) HIP_TRY(hipHostMalloc(&c->h_sse, kQualitySlots * sizeof(unsigned long long)));
+    if (frames <= c->q_cap) return PICSONG_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    if (c->q_pix) (void)hipFree(c->q_pix);
+    c->q_pix = nullptr; c->q_cap = 0;
+    HIP_TRY(hipMalloc(&c->q_pix, (size_t)frames * c->P));
+    c->q_cap = frames;
+    return PICSONG_OK;
+}
+
+static int quality_impl(picsong_ctx *c, const RateJob &job, uint64_t max_sse, int j_min, int j_max, hipStream_t s, int *h_j,
+                        int *h_totals, uint64_t *h_sse, const char *who)
+{
+    // (the callers have made the null, context-kind, stride and alignment checks)
+    if (!c->p.lossy) return fail(PICSONG_ERR_ARG, "%s: a lossless context has no quantiser to search", who);
+    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 3 contexts have no quality control", who);
+    if (!rate_range_ok(j_min, j_max))
+        return fail(PICSONG_ERR_ARG, "%s: range [%d, %d] is neither 0, 0 (the whole grid) nor inside 1..%d", who, j_min, j_max, kRateJMax);
+    const std::vector<int> grid = rate_grid(j_min, j_max);
+    if (grid.empty()) return fail(PICSONG_ERR_ARG, "%s: no header-exact quantiser in [%d, %d]", who, j_min, j_max);
+    HIP_TRY(hipSetDevice(c->device));
+    const bool rgb = c->p.is_rgb != 0;
+    const int nf = rgb ? 3 : job.n;
+    int K = kRateMaxK;
+    if (const char *e = getenv("PICSONG_RATE_K")) if (atoi(e) == 1) K = 1;
+    BpcArgs a;
+    int rc = rgb ? bpc_args_rgb(c, a) : bpc_args(c, a, 0);   // (the final encode's table: refused before anything is launched)
+    if (rc) return rc;
+    if ((rc = ensure_batch(c, nf))) return rc;
+    if ((rc = ensure_coef_i(c, nf))) return rc;
+    if ((rc = ensure_rate(c, nf))) return rc;
+    if ((rc = ensure_quality(c, nf))) return rc;
+    c->last_batch = -1;                                     // (until the result is packed: no totals to hand out)
+    if ((rc = rate_transform(c, job, s))) return rc;
+
+    const QualityProbe probe = { c->rate_coef, (unsigned long long)c->rate_z, c->batch.coef_i, c->batch.coef, c->q_pix,
+                                 c->aw, c->ah, c->p.wl, c->p.width, c->p.height, level_off(c), c->P, c->extra, nf,
+                                 job.frames, job.frame_stride, job.r, job.g, job.b };
+    QualityStepper st((int)grid.size(), (unsigned long long)max_sse, K);
+    std::vector<int> seen_j;                                // every probe made, with its per-array sums
+    std::vector<unsigned long long> seen_sse;
+    int idx[kRateMaxK], m = 0;
+    while ((m = st.next(idx)) > 0) {
+        for (int i = 0; i < m; i++) {
+            // stage timers (picsong_profile_begin): a probe records quantise, synthesis and SSE where a frame records
+            // transform, coder and pack
+            hipEvent_t *ev = nullptr;
+            if (c->prof_cap > 0 && c->prof_n < c->prof_cap) ev = c->prof_ev->data() + 4 * (c->prof_n++);
+            if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+            auto mark = [ev, s](int k) -> int {
+                if (ev) HIP_TRY(hipEventRecord(ev[k], s));
+                return PICSONG_OK;
+            };
+            if ((rc = quality_probe(HipGo{ s }, probe, grid[(size_t)idx[i]], c->d_sse + i * nf, mark))) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(c->h_sse, c->d_sse, (size_t)(m * nf) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        unsigned long long sums[kRateMaxK] = { 0, 0, 0 };
+        for (int i = 0; i < m; i++) {
+            seen_j.push_back(grid[(size_t)idx[i]]);
+            for (int f = 0; f < nf; f++) { sums[i] += c->h_sse[i * nf + f]; seen_sse.push_back(c->h_sse[i * nf + f]); }
+        }
+        st.take(sums);
+    }
+    *h_j = 0;
+    if (st.result() < 0)
+        return fail(PICSONG_ERR_QUALITY, "%s: no quantiser of the search range meets an SSE of %llu", who, (unsigned long long)max_sse);
+    const int j = grid[(size_t)st.result()];
+    // ---- the result's encode: quantise, coder, pack, as the rate calls' final step
+    if ((rc = rate_probe(c, a, nf, 1, &j, s))) return rc;
+    if ((rc = rate_finish(c, job, nf, j, 0, s, h_totals))) return rc;
+    for (size_t i = 0; i < seen_j.size(); i++)              // (the result is a probe the procedure made)
+        if (seen_j[i] == j) for (int f = 0; f < nf; f++) h_sse[f] = (uint64_t)seen_sse[i * (size_t)nf + (size_t)f];
+    *h_j = j;
+    return PICSONG_OK;
+}
+
+int picsong_encode_frames_quality(picsong_ctx *c, int n, const uint8_t *d_frames, size_t frame_stride, int first_iter,
+                                  uint64_t max_sse, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
+                                  void *stream, int *h_j, int *h_totals, uint64_t *h_sse)
+{
+    const char *who = "encode_frames_quality";
+    if (!c || !d_frames || !d_streams || !h_j || !h_totals || !h_sse) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (n < 1 || n > 16) return fail(PICSONG_ERR_ARG, "%s: %d frames outside 1..16", who, n);
+    if (c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: grey contexts only (an RGB frame: picsong_encode_rgb_frame_quality)", who);
+    if (n > 1 && (frame_stride < c->P || stream_stride < picsong_max_stream_shorts(c->aw, c->ah)))
+        return fail(PICSONG_ERR_ARG, "%s: strides smaller than a padded frame / a worst-case codestream", who);
+    if (((uintptr_t)d_frames | frame_stride) & 15u) return fail(PICSONG_ERR_ARG, "%s: frames must be 16-byte aligned", who);
+    const RateJob job = { n, d_frames, frame_stride, nullptr, nullptr, nullptr, first_iter, 0, d_streams, stream_stride, false };
+    return quality_impl(c, job, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_totals, h_sse, who);
+}
+
+int picsong_encode_frame_quality(picsong_ctx *c, const uint8_t *d_frame, int iter, uint64_t max_sse, int j_min, int j_max,
+                                 uint16_t *d_stream, void *stream, int *h_j, int *h_total, uint64_t *h_sse)
+{
+    const char *who = "encode_frame_quality";
+    if (!c || !d_frame || !d_stream || !h_j || !h_total || !h_sse) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: grey contexts only (an RGB frame: picsong_encode_rgb_frame_quality)", who);
+    // (any alignment, as picsong_encode_frame_rate: the transform and sse_kernel have their per-byte forms)
+    const RateJob job = { 1, d_frame, 0, nullptr, nullptr, nullptr, iter == 0 ? 0 : 1, 0, d_stream, 0, true };
+    return quality_impl(c, job, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_total, h_sse, who);
+}
+
+int picsong_encode_rgb_frame_quality(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
+                                     uint64_t max_sse, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
+                                     void *stream, int *h_j, int *h_totals, uint64_t *h_sse)
+{
+    const char *who = "encode_rgb_frame_quality";
+    if (!c || !d_r || !d_g || !d_b || !d_streams || !h_j || !h_totals || !h_sse) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: the context is not an RGB one", who);
+    if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah)) return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
+    if ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 3u) return fail(PICSONG_ERR_ARG, "%s: the planes need 4-byte alignment", who);
+    const RateJob job = { 1, nullptr, 0, d_r, d_g, d_b, 0, header_mask, d_streams, stream_stride, false };
+    return quality_impl(c, job, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_totals, h_sse, who);
 }
 
 // picsong_decode_rgb_frame (reduce = 0) and picsong_decode_rgb_frame_reduced: the three components' level `reduce`,

@@ -1,0 +1,155 @@
+// quality_kernels.hpp -- the distortion measurement of the quality calls (picsong_frames_sse,
+// picsong_encode_frame_quality and its mirrors): the sum of squared differences of two u8 images.
+//
+// sse_kernel compares the VISIBLE W x H samples of n pairs of padded arrays -- each side with its own row pitch and its
+// own frame stride -- and adds one uint64 per frame to out[f] (zeroed on the stream before it: sse_zero_kernel, the
+// frames_sse sequence of launch_seq.hpp).  The sums are integers: exact, and the same from run to run whatever order
+// the atomics land in.
+//
+// A bandwidth-bound stream shaped like quantise_kernel: 256 threads, 16 bytes a lane and load.  The work of a frame is
+// its H * ceil(W / 16) vectors FLATTENED (an 8K row is 480 vectors: a row a pass would leave the second pass of 256
+// lanes half empty), cut into tiles of kSseTileLoads loads a lane; tiles are dealt grid-stride over all frames, so a
+// workgroup's frame only ever grows and it makes ONE 64-bit atomic add per frame it touched.  A lane divides once a
+// tile (its first vector's row) and steps (row, vector) from there.
+//
+// The squares: sum (a - b)^2 = sum a^2 + sum b^2 - 2 sum a b, three v_dot4_u32_u8 per four samples with the
+// accumulation in the instruction -- no unpacking, no per-byte |a - b| (which has no packed form on CDNA).  The two
+// accumulators wrap modulo 2^32 on their own; their combination acc_sq - 2 acc_ab is the run's SSE modulo 2^32, so it
+// is exact while the RUN's SSE stays below 2^32: one load adds at most 16 * 255^2 = 1 040 400, a run is at most
+// kSseRunLoads = 4128 loads (4128 * 1 040 400 < 2^32 <= 4129 * 1 040 400), then the lane widens into its 64-bit sum.
+// Samples outside the image -- the columns [W, pitch) in a row's last vector -- are masked to 0 on both sides per byte.
+//
+// VEC: both pointers, pitches and strides 16-byte aligned: dwordx4 loads.  Else the per-byte form: the same items, the
+// sixteen bytes of a vector loaded one by one (bounds-checked against W), the same arithmetic.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#ifndef __HIP_MEMORY_SCOPE_AGENT
+#define __HIP_MEMORY_SCOPE_AGENT 4          // (CPU wave-emulator build: its atomics are plain read-modify-writes)
+#endif
+
+namespace picsong {
+
+constexpr int kSseTileLoads = 4;            // loads a lane and tile
+constexpr int kSseRunLoads = 4128;          // loads a lane may accumulate in 32 bits
+constexpr unsigned kSseMaxWgs = 2048;       // 8 workgroups a CU
+constexpr int kSseMaxFrames = 64;
+static_assert(kSseRunLoads % kSseTileLoads == 0, "a run is whole tiles");
+static_assert((unsigned long long)kSseRunLoads * 16ull * 255ull * 255ull < (1ull << 32), "a run's SSE fits 32 bits");
+
+struct SseArgs {
+    const uint8_t *a;               // frame f at a + f * a_z, row y at + y * a_pitch
+    unsigned long long a_z;
+    const uint8_t *b;
+    unsigned long long b_z;
+    unsigned long long *out;        // out[f] += the frame's sum
+    uint32_t a_pitch, b_pitch;
+    int W, H, n;
+};
+
+// c + the dot product of the four bytes of a and b (wraps modulo 2^32)
+__device__ __forceinline__ uint32_t dot4_u8(uint32_t a, uint32_t b, uint32_t c)
+{
+#if defined(__HIP__)
+    return __builtin_amdgcn_udot4(a, b, c, false);
+#else   // (CPU wave-emulator build)
+    for (int i = 0; i < 4; i++) c += ((a >> (8 * i)) & 0xFFu) * ((b >> (8 * i)) & 0xFFu);
+    return c;
+#endif
+}
+
+__global__ __launch_bounds__(64) void sse_zero_kernel(unsigned long long *out, int n)
+{
+    for (int i = (int)threadIdx.x; i < n; i += (int)blockDim.x) out[i] = 0ull;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void sse_kernel(SseArgs s)
+{
+    __shared__ unsigned long long wave_sum[4];
+    const uint32_t vpr = ((uint32_t)s.W + 15u) >> 4;                        // vectors a row
+    const uint32_t items = vpr * (uint32_t)s.H;                             // vectors a frame
+    constexpr uint32_t kTile = 256u * (uint32_t)kSseTileLoads;
+    const uint32_t tpf = (items + kTile - 1u) / kTile, tiles = tpf * (uint32_t)s.n;
+    const uint32_t step_rows = 256u / vpr, step_vecs = 256u - step_rows * vpr;   // (row, vector) of item + 256
+    const uint32_t tail = (uint32_t)s.W - 16u * (vpr - 1u);                 // visible bytes of a row's last vector, 1..16
+
+    uint32_t acc_sq = 0u, acc_ab = 0u;                                      // the run: sum a^2 + b^2, sum a b
+    int run = 0;
+    unsigned long long sum = 0ull;
+    uint32_t cur = tiles ? blockIdx.x / tpf : 0u;                           // the frame `sum` belongs to (workgroup-uniform)
+
+    for (uint32_t t = blockIdx.x; ; t += gridDim.x) {
+        const bool more = t < tiles;
+        const uint32_t f = more ? t / tpf : cur + 1u;
+        if (f != cur) {
+            // ---- frame `cur` is done here: the waves reduce, the workgroup adds once
+            sum += (unsigned long long)(acc_sq - 2u * acc_ab);
+            acc_sq = acc_ab = 0u; run = 0;
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
+            if ((threadIdx.x & 63u) == 0u) wave_sum[threadIdx.x >> 6] = sum;
+            __syncthreads();
+            if (threadIdx.x == 0u) {
+                const unsigned long long v = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+                if (v) (void)__hip_atomic_fetch_add(&s.out[cur], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __syncthreads();
+            sum = 0ull;
+            cur = f;
+        }
+        if (!more) break;
+        if (run + kSseTileLoads > kSseRunLoads) {                           // (uniform: every lane counts every tile)
+            sum += (unsigned long long)(acc_sq - 2u * acc_ab);
+            acc_sq = acc_ab = 0u; run = 0;
+        }
+        run += kSseTileLoads;
+        const uint8_t *const fa = s.a + (unsigned long long)f * s.a_z;
+        const uint8_t *const fb = s.b + (unsigned long long)f * s.b_z;
+        uint32_t i = (t - f * tpf) * kTile + threadIdx.x;
+        uint32_t y = i / vpr, v = i - y * vpr;
+#pragma unroll
+        for (int k = 0; k < kSseTileLoads; k++) {
+            if (i < items) {
+                const uint32_t rem = v == vpr - 1u ? tail : 16u;
+                const size_t oa = (size_t)y * s.a_pitch + 16u * (size_t)v, ob = (size_t)y * s.b_pitch + 16u * (size_t)v;
+                uint32_t wa[4], wb[4];
+                if (VEC) {
+                    const uint4 xa = *reinterpret_cast<const uint4 *>(fa + oa), xb = *reinterpret_cast<const uint4 *>(fb + ob);
+                    wa[0] = xa.x; wa[1] = xa.y; wa[2] = xa.z; wa[3] = xa.w;
+                    wb[0] = xb.x; wb[1] = xb.y; wb[2] = xb.z; wb[3] = xb.w;
+                    if (rem < 16u) {
+#pragma unroll
+                        for (uint32_t d = 0; d < 4u; d++) {
+                            const uint32_t m = rem >= 4u * d + 4u ? 0xFFFFFFFFu : (rem <= 4u * d ? 0u : (1u << (8u * (rem - 4u * d))) - 1u);
+                            wa[d] &= m; wb[d] &= m;
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (uint32_t d = 0; d < 4u; d++) {
+                        wa[d] = wb[d] = 0u;
+#pragma unroll
+                        for (uint32_t e = 0; e < 4u; e++) {
+                            if (4u * d + e < rem) {
+                                wa[d] |= (uint32_t)fa[oa + 4u * d + e] << (8u * e);
+                                wb[d] |= (uint32_t)fb[ob + 4u * d + e] << (8u * e);
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int d = 0; d < 4; d++) {
+                    acc_sq = dot4_u8(wa[d], wa[d], acc_sq);
+                    acc_sq = dot4_u8(wb[d], wb[d], acc_sq);
+                    acc_ab = dot4_u8(wa[d], wb[d], acc_ab);
+                }
+            }
+            i += 256u; y += step_rows; v += step_vecs;
+            if (v >= vpr) { v -= vpr; y++; }
+        }
+    }
+}
+
+}  // namespace picsong

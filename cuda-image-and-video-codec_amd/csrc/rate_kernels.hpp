@@ -9,6 +9,8 @@
 // array the coder takes: int16 through pack_c16's conversion (toward zero, as the coder's own load of a float) or the
 // float product itself, per candidate.  Candidate c of frame f lands at dst + (c * n + f) * dst_z: "frame" c * n + f of a
 // batched coder launch.
+// I32 (the quality calls' probes, picsong_encode_frame_quality): every candidate leaves as an int32 Mallat array, the
+// float product truncated toward zero -- what the coder codes and the decoder returns, the form the synthesis reads.
 //
 // A bandwidth-bound stream: 256 threads, 16 bytes a lane and load, a workgroup a row at a time (grid-stride over the
 // n * AH rows), so a wave's row and with it the vertical half of the subband search is uniform.  Subband edges are not
@@ -27,7 +29,7 @@ constexpr int kQuantMaxK = 3;
 struct QuantArgs {
     const void *src;                // n float Mallat arrays (row stride AW), src_z bytes apart
     unsigned long long src_z;
-    void *dst;                      // candidate c of frame f: dst + (c * n + f) * dst_z bytes, int16 or float [AH x AW]
+    void *dst;                      // candidate c of frame f: dst + (c * n + f) * dst_z bytes, int16, float or int32 [AH x AW]
     unsigned long long dst_z;
     int AW, AH, wl, n;
     int c16[kQuantMaxK];            // candidate c leaves as int16 (else float)
@@ -39,7 +41,7 @@ struct QuantArgs {
 // when there is none).  With lx the same for x and AW: lx < ly -> HL of level lx; lx == ly < wl -> HH; lx > ly -> LH of
 // level ly; both wl -> LL, which takes row wl - 1, column 0.  rs[l]: the step of the columns [AW >> (l + 1), AW >> l) of
 // this row; low: that of the columns below AW >> wl.
-template <int K>
+template <int K, bool I32 = false>
 __global__ __launch_bounds__(256) void quantise_kernel(QuantArgs a)
 {
     static_assert(K >= 1 && K <= kQuantMaxK, "one to three candidates a launch");
@@ -83,7 +85,11 @@ __global__ __launch_bounds__(256) void quantise_kernel(QuantArgs a)
 #pragma unroll
                 for (int e = 0; e < 4; e++) t[e] = (x[e] * st[e]) * vqs[c];     // emit_pair's operations, in its order
                 char *const base = (char *)a.dst + (unsigned long long)((uint32_t)c * (uint32_t)a.n + f) * a.dst_z;
-                if (a.c16[c]) {
+                if (I32) {
+                    uint4 w;
+                    w.x = (uint32_t)(int)t[0]; w.y = (uint32_t)(int)t[1]; w.z = (uint32_t)(int)t[2]; w.w = (uint32_t)(int)t[3];
+                    reinterpret_cast<uint4 *>(base)[(size_t)y * groups + g] = w;
+                } else if (a.c16[c]) {
                     uint2 w;
                     w.x = pack_c16(t[0], t[1]); w.y = pack_c16(t[2], t[3]);
                     reinterpret_cast<uint2 *>(base)[(size_t)y * groups + g] = w;

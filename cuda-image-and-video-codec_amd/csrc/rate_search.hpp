@@ -87,4 +87,54 @@ private:
     int rounds_ = 0, probes_ = 0;
 };
 
+// ---- the quality calls (picsong_encode_frame_quality and its mirrors): the mirror search over the same grid.  SSE
+// against j is not monotone either (a finer quantiser can decode a few squares worse), so the result is again what a
+// procedure returns, over G' = the entries of G inside [j_min, j_max]:
+//     lo = -1, hi = len(G');  while hi - lo > 1: mid = (lo + hi) / 2;  sse(G'[mid]) <= max_sse ? hi = mid : lo = mid
+//     result = G'[hi]   (hi == len(G'): nothing meets the limit)
+// -- the coarsest quantiser the bisection finds that meets the quality.  QualityStepper walks it as RateStepper walks
+// its own: K = 3 probes the midpoint and the midpoints either outcome leads to; the one not led to is ignored.
+class QualityStepper {
+public:
+    // n = len(G'), limit = max_sse, K = 1 or 3 probes a round
+    QualityStepper(int n, unsigned long long limit, int K) : lo_(-1), hi_(n), len_(n), limit_(limit), K_(K < 3 ? 1 : 3), n_(0) {}
+    bool done() const { return hi_ - lo_ <= 1; }
+    int result() const { return hi_ < len_ ? hi_ : -1; }   // index into G', -1: nothing meets the limit
+    int rounds() const { return rounds_; }
+    int probes() const { return probes_; }                  // probes the procedure used (the ignored ones not counted)
+    // The indices (into G') to probe this round, ascending: idx[0 .. return value); 0 when done.
+    int next(int idx[kRateMaxK])
+    {
+        n_ = 0; mid_ = left_ = right_ = -1;
+        if (done()) return 0;
+        const int mid = (lo_ + hi_) / 2;
+        if (K_ == 3 && mid - lo_ > 1) { left_ = n_; idx[n_++] = (lo_ + mid) / 2; }      // follows from "mid meets the limit"
+        mid_ = n_; idx[n_++] = mid;
+        if (K_ == 3 && hi_ - mid > 1) { right_ = n_; idx[n_++] = (mid + hi_) / 2; }     // follows from "mid does not"
+        for (int i = 0; i < n_; i++) cand_[i] = idx[i];
+        return n_;
+    }
+    // sse[i]: the distortion at idx[i] of the last next()
+    void take(const unsigned long long *sse)
+    {
+        if (n_ == 0) return;
+        rounds_++;
+        const bool meets = sse[mid_] <= limit_;
+        probes_++;
+        if (meets) hi_ = cand_[mid_]; else lo_ = cand_[mid_];
+        const int second = meets ? left_ : right_;
+        if (second >= 0) {
+            probes_++;
+            if (sse[second] <= limit_) hi_ = cand_[second]; else lo_ = cand_[second];
+        }
+        n_ = 0;
+    }
+
+private:
+    int lo_, hi_, len_;
+    unsigned long long limit_;
+    int K_, n_, mid_ = -1, left_ = -1, right_ = -1, cand_[kRateMaxK] = { 0, 0, 0 };
+    int rounds_ = 0, probes_ = 0;
+};
+
 }  // namespace picsong

@@ -53,6 +53,9 @@ struct Options {
     std::string train;                          // -train <outFolder>: count the input's coding decisions, write a LUT folder
     float rate = 0.0f;                          // -rate <bpp>: choose qs so that the output meets that many bits per pixel
     bool has_rate = false, has_qs = false;
+    double psnr = 0.0;                          // -psnr <dB>: choose qs so that the searched frames decode to at least that PSNR
+    bool has_psnr = false;
+    std::string compare;                        // -compare <raw file>: decoding, the PSNR of the output against that file
 };
 
 [[noreturn]] void die(const std::string &msg)
@@ -115,7 +118,13 @@ void help()
         " -rate <bpp>         coding, -type 1: choose -qs so that a frame takes at most bpp bits per pixel (floor(bpp W H / 16)\n"
         "                     shorts; an RGB frame's three components share it).  A video gets ONE qs (its stream has one header):\n"
         "                     the search runs on the first min(frames, 16) frames and their summed target, the whole video is\n"
-        "                     coded at the result.  Not with -qs, -type 0 or -cp 3\n";
+        "                     coded at the result.  Not with -qs, -type 0 or -cp 3\n"
+        " -psnr <dB>          coding, -type 1: choose -qs so that the PSNR over the visible samples of the searched frames is at\n"
+        "                     least dB (an SSE of at most floor(65025 samples / 10^(dB/10)), samples = W H frames components).  A\n"
+        "                     video as with -rate: the search runs on the first min(frames, 16) frames (an RGB video: its first\n"
+        "                     frame).  Not with -qs, -rate, -type 0, -cp 3 or -train\n"
+        " -compare <file>     decoding: after the output is written, print its PSNR and SSE against that raw (or PGM) file of the\n"
+        "                     same geometry and planar layout.  Not with -reduce or -window\n";
 }
 
 template <typename T> void echo(const char *flag, const T &v)
@@ -156,6 +165,22 @@ Options parse(const Args &a)
         getf("-rate", o.rate);
         o.has_rate = true;
         if (!(o.rate > 0.0f)) die("Incorrect parameters. -rate takes a positive number of bits per pixel.");
+    }
+    if (a.has("-psnr")) {
+        if (o.cd != 0) die("Incorrect parameters. -psnr applies to coding (-cd 0) only.");
+        const std::string v = a.get("-psnr");
+        char *end = nullptr;
+        o.psnr = std::strtod(v.c_str(), &end);
+        o.has_psnr = true;
+        if (v.empty() || *end != '\0' || !std::isfinite(o.psnr)) die("Incorrect parameters. -psnr takes a PSNR in dB.");
+        echo("-psnr", v);
+    }
+    if (a.has("-compare")) {
+        if (o.cd != 1) die("Incorrect parameters. -compare applies to decoding (-cd 1) only.");
+        if (a.has("-reduce") || a.has("-window")) die("Incorrect parameters. -compare does not apply to -reduce or -window.");
+        o.compare = a.get("-compare");
+        if (o.compare.empty()) die("Incorrect parameters. -compare takes the file to compare with.");
+        echo("-compare", o.compare);
     }
     o.has_qs = a.has("-qs");
     if (o.cd == 0) {
@@ -243,6 +268,9 @@ picsong_params make_params(const Options &o)
     return p;
 }
 
+// ---- -psnr <dB>: what the search chose and what it achieved (the two console lines; --metrics carries them too)
+struct QualityReport { bool reported = false; int j = 0; float qs = 0; uint64_t max_sse = 0, sse = 0, samples = 0; long frames = 0; double psnr = 0; } g_quality;
+
 void write_metrics(const Options &o, const char *mode, long frames, double seconds, double dwt, double bpc,
                    double pack, long shorts)
 {
@@ -255,6 +283,10 @@ void write_metrics(const Options &o, const char *mode, long frames, double secon
     // decoding: the size of the images written (1/2^reduce of the frame's, -reduce)
     if (std::string(mode).compare(0, 6, "decode") == 0)
         m << ", \"width\": " << o.x << ", \"height\": " << o.y << ", \"reduce\": " << o.reduce;
+    if (g_quality.reported)
+        m << ", \"psnr_target\": " << o.psnr << ", \"psnr_j\": " << g_quality.j << ", \"psnr_qs\": " << g_quality.qs
+          << ", \"psnr_max_sse\": " << g_quality.max_sse << ", \"psnr_frames_searched\": " << g_quality.frames
+          << ", \"psnr_sse\": " << g_quality.sse << ", \"psnr_achieved\": " << g_quality.psnr;
     if (o.win)
         m << ", \"window\": [" << o.wx << ", " << o.wy << ", " << o.ww << ", " << o.wh << "], \"codeblocks\": " << o.win_cb;
     m << "}\n";
@@ -279,6 +311,30 @@ void rate_report_achieved(const Options &o, long total_shorts, long nframes)
 [[noreturn]] void rate_die(int rc, const char *call)
 {
     if (rc == PICSONG_ERR_RATE) die(std::string("-rate: no quantiser meets the target size (") + picsong_last_error() + ")");
+    die(std::string(call) + " failed: " + picsong_last_error());
+}
+
+// the limit of a -psnr search over `frames` frames of `components` planes
+uint64_t quality_limit(const Options &o, long frames, int components, uint64_t *samples)
+{
+    uint64_t lim = 0;
+    *samples = (uint64_t)o.x * (uint64_t)o.y * (uint64_t)frames * (uint64_t)components;
+    CK(picsong_psnr_to_sse(o.psnr, *samples, &lim));
+    return lim;
+}
+void quality_report(int j, float qs, uint64_t max_sse, uint64_t samples, long nframes_searched, const uint64_t *sse, int n)
+{
+    QualityReport &r = g_quality;
+    r.reported = true; r.j = j; r.qs = qs; r.max_sse = max_sse; r.samples = samples; r.frames = nframes_searched; r.sse = 0;
+    for (int i = 0; i < n; i++) r.sse += sse[i];
+    CK(picsong_sse_to_psnr(r.sse, samples, &r.psnr));
+    std::cout << "Quality control: qs " << qs << " (j = " << j << ") chosen for an SSE of at most " << max_sse << " over "
+              << nframes_searched << " frame(s)" << std::endl;
+    std::cout << "Quality control: achieved " << r.psnr << " dB (SSE " << r.sse << ") over the frames searched" << std::endl;
+}
+[[noreturn]] void quality_die(int rc, const char *call)
+{
+    if (rc == PICSONG_ERR_QUALITY) die(std::string("-psnr: no quantiser meets the target quality (") + picsong_last_error() + ")");
     die(std::string(call) + " failed: " + picsong_last_error());
 }
 
@@ -333,6 +389,17 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
             CK(picsong_rate_qs(j, &q));
             CK(picsong_ctx_set_qs(ctx, q));
             rate_report_choice(j, q, rate_target_shorts(o), 1);
+        } else if (o.has_psnr && f == 0) {
+            int j = 0;
+            float q = 0.0f;
+            uint64_t samples = 0, sse[3] = { 0, 0, 0 };
+            const uint64_t lim = quality_limit(o, 1, 3, &samples);
+            const int rc = picsong_encode_rgb_frame_quality(ctx, d_in[0], d_in[1], d_in[2], o.video ? 7 : 1, lim, 0, 0, d_out, max_shorts,
+                                                            s, &j, totals, sse);
+            if (rc != PICSONG_OK) quality_die(rc, "picsong_encode_rgb_frame_quality");
+            CK(picsong_rate_qs(j, &q));
+            CK(picsong_ctx_set_qs(ctx, q));
+            quality_report(j, q, lim, samples, 1, sse, 3);
         } else if (batched) {
             CK(picsong_encode_rgb_frame(ctx, d_in[0], d_in[1], d_in[2], o.video ? (f == 0 ? 7 : 0) : 1, d_out, max_shorts, s));
             CK(picsong_last_totals(ctx, s, 3, totals));
@@ -476,6 +543,13 @@ int run_encode(Options o)
         if (o.cp == 3) die("Incorrect parameters. -rate does not apply to -cp 3.");
         if (!o.train.empty()) die("Incorrect parameters. -rate does not apply to -train.");
     }
+    if (o.has_psnr) {
+        if (o.has_qs) die("Incorrect parameters. -psnr chooses the quantiser: it cannot be combined with -qs.");
+        if (o.has_rate) die("Incorrect parameters. -psnr cannot be combined with -rate.");
+        if (o.type != 1) die("Incorrect parameters. -psnr applies to lossy coding (-type 1) only.");
+        if (o.cp == 3) die("Incorrect parameters. -psnr does not apply to -cp 3.");
+        if (!o.train.empty()) die("Incorrect parameters. -psnr does not apply to -train.");
+    }
     if (!o.train.empty()) {
         if (o.k > 0) die("Incorrect parameters. -train counts the two-pass coder's decisions (-k must be 0).");
         if (o.cp == 3) die("Incorrect parameters. -train does not apply to -cp 3.");
@@ -538,7 +612,7 @@ int run_encode(Options o)
     }
     const int fd = open(o.input.c_str(), O_RDONLY);
     if (fd < 0) die("Cannot open input file " + o.input);
-    if (o.has_rate && o.video) {
+    if ((o.has_rate || o.has_psnr) && o.video) {
         // -rate on a video: the first slot's context (rank 0 of -gpus N) searches on the first min(frames, 16) frames and
         // their summed target, then every context takes the chosen qs: the stream has one header, hence one qs
         const int n = (int)std::min<long>(nframes, 16);
@@ -563,12 +637,22 @@ int run_encode(Options o)
         HIPCK(hipMemcpyAsync(d_f, h_f, P * (size_t)n, hipMemcpyHostToDevice, k.stream));
         int j = 0, totals[16];
         float q = 0.0f;
+        if (o.has_psnr) {               // -psnr mirrors -rate: the same frames, the same contexts, the limit over all of them
+            uint64_t samples = 0, sse[16];
+            const uint64_t lim = quality_limit(o, n, 1, &samples);
+            const int rc = picsong_encode_frames_quality(k.ctx, n, d_f, P, 0, lim, 0, 0, d_s, max_shorts, k.stream, &j, totals, sse);
+            if (rc != PICSONG_OK) quality_die(rc, "picsong_encode_frames_quality");
+            CK(picsong_rate_qs(j, &q));
+            for (auto &x : w) CK(picsong_ctx_set_qs(x.ctx, q));
+            quality_report(j, q, lim, samples, n, sse, n);
+        } else {
         const size_t target = rate_target_shorts(o) * (size_t)n;
         const int rc = picsong_encode_frames_rate(k.ctx, n, d_f, P, 0, target, 0, 0, d_s, max_shorts, k.stream, &j, totals);
         if (rc != PICSONG_OK) rate_die(rc, "picsong_encode_frames_rate");
         CK(picsong_rate_qs(j, &q));
         for (auto &x : w) CK(picsong_ctx_set_qs(x.ctx, q));
         rate_report_choice(j, q, target, n);
+        }
         (void)hipHostFree(h_f); (void)hipFree(d_f); (void)hipFree(d_s);
     }
     // image: one truncating write (IOManager.ipp:615-620); video: append + _SIZE (:176-190)
@@ -732,6 +816,19 @@ int run_encode(Options o)
             if (rc == PICSONG_ERR_RATE) err = std::string("-rate: no quantiser meets the target size (") + picsong_last_error() + ")";
             else if (rc != PICSONG_OK || picsong_rate_qs(j, &q) != PICSONG_OK) err = picsong_last_error();
             else rate_report_choice(j, q, rate_target_shorts(o), 1);
+        }
+        else if (o.has_psnr && !o.video) {
+            // an image: one quality call (synchronous); its length is the context's last total, as after picsong_encode_frame
+            int j = 0, total = 0;
+            float q = 0.0f;
+            uint64_t samples = 0, sse = 0, lim = 0;
+            if (picsong_psnr_to_sse(o.psnr, samples = (uint64_t)o.x * (uint64_t)o.y, &lim) != PICSONG_OK) err = picsong_last_error();
+            else {
+                const int rc = picsong_encode_frame_quality(k.ctx, k.d_in, 0, lim, 0, 0, k.d_out, k.stream, &j, &total, &sse);
+                if (rc == PICSONG_ERR_QUALITY) err = std::string("-psnr: no quantiser meets the target quality (") + picsong_last_error() + ")";
+                else if (rc != PICSONG_OK || picsong_rate_qs(j, &q) != PICSONG_OK) err = picsong_last_error();
+                else quality_report(j, q, lim, samples, 1, &sse, 1);
+            }
         }
         else if (B == 1) { if (picsong_encode_frame(k.ctx, k.d_in, g == 0 ? 0 : 1, k.d_out, k.stream) != PICSONG_OK) err = picsong_last_error(); }
         else if (picsong_encode_frames(k.ctx, n, k.d_in, P, (int)(g * B), k.d_out, max_shorts, k.stream) != PICSONG_OK) err = picsong_last_error();
@@ -1134,6 +1231,65 @@ int run_decode(const Options &o)
     return 0;
 }
 
+// ---- -cd 1 -compare <file>: the PSNR and SSE of the decoded output, as written, against a file of the same geometry
+// and planar layout (raw, or a PGM whose header is skipped), plane by plane through picsong_frames_sse
+int run_compare(const Options &o)
+{
+    std::ifstream in(o.input, std::ios::binary);
+    uint16_t hdr[PICSONG_HDR_SHORTS];
+    in.read(reinterpret_cast<char *>(hdr), sizeof hdr);
+    picsong_params p;
+    CK(picsong_header_unpack(hdr, &p));
+    const long planes = (o.video ? (long)p.frames : 1) * (long)p.components;
+    const size_t plane_bytes = (size_t)p.width * (size_t)p.height;
+    auto open_planes = [&](const std::string &name, std::ifstream &f, size_t &base) {
+        f.open(name, std::ios::binary);
+        if (!f) die("Cannot open " + name);
+        f.seekg(0, std::ios::end);
+        const size_t size = (size_t)f.tellg();
+        if (size < plane_bytes * (size_t)planes) die(name + " is shorter than the decoded output's planes.");
+        const Pgm pgm = sniff_pgm(name);
+        base = pgm.is_pgm ? pgm.offset : 0;
+        if (size - base != plane_bytes * (size_t)planes) die(name + " does not have the decoded output's geometry.");
+    };
+    std::ifstream fa, fb;
+    size_t base_a = 0, base_b = 0;
+    open_planes(o.output, fa, base_a);
+    open_planes(o.compare, fb, base_b);
+    HIPCK(hipSetDevice(o.device));
+    picsong_ctx *ctx = nullptr;
+    create_decode_ctx(p, o.device, &ctx);
+    int aw, ah, ncb;
+    CK(picsong_ctx_padded_dims(ctx, &aw, &ah, &ncb));
+    const size_t P = (size_t)aw * ah;
+    uint8_t *h = nullptr, *d = nullptr;
+    uint64_t *d_sse = nullptr, *h_sse = nullptr;
+    HIPCK(hipHostMalloc(&h, 2 * P));
+    HIPCK(hipMalloc(&d, 2 * P));
+    HIPCK(hipMalloc(&d_sse, sizeof(uint64_t)));
+    HIPCK(hipHostMalloc(&h_sse, sizeof(uint64_t)));
+    std::vector<uint8_t> raw(plane_bytes);
+    uint64_t sse = 0;
+    for (long i = 0; i < planes; i++) {
+        if (!read_frame(fa, base_a, (size_t)i, p.width, p.height, raw.data())) die("Cannot read back " + o.output);
+        CK(picsong_pad_frame_host(raw.data(), p.width, p.height, h, aw, ah));
+        if (!read_frame(fb, base_b, (size_t)i, p.width, p.height, raw.data())) die("Cannot read " + o.compare);
+        CK(picsong_pad_frame_host(raw.data(), p.width, p.height, h + P, aw, ah));
+        HIPCK(hipMemcpyAsync(d, h, 2 * P, hipMemcpyHostToDevice, nullptr));
+        CK(picsong_frames_sse(ctx, 1, d, 0, d + P, 0, d_sse, nullptr));
+        HIPCK(hipMemcpyAsync(h_sse, d_sse, sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
+        HIPCK(hipStreamSynchronize(nullptr));
+        sse += *h_sse;
+    }
+    double psnr = 0.0;
+    CK(picsong_sse_to_psnr(sse, (uint64_t)plane_bytes * (uint64_t)planes, &psnr));
+    std::cout << "Compare: PSNR " << psnr << " dB, SSE " << sse << " over " << planes << " plane(s) of " << p.width << "x" << p.height
+              << std::endl;
+    picsong_ctx_destroy(ctx);
+    (void)hipHostFree(h); (void)hipFree(d); (void)hipFree(d_sse); (void)hipHostFree(h_sse);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -1144,7 +1300,7 @@ int main(int argc, char **argv)
     Options o = parse(a);
     int rc;
     if (o.cd == 0) rc = run_encode(o);
-    else if (o.cd == 1) rc = run_decode(o);
+    else if (o.cd == 1) { rc = run_decode(o); if (rc == 0 && !o.compare.empty()) rc = run_compare(o); }
     else die("Incorrect parameters. Please choose valid values.");
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
     std::cout << "The time spent with the app is: " << sec << std::endl;

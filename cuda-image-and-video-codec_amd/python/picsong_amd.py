@@ -14,6 +14,7 @@ SO_PATH = os.environ.get("PICSONG_SO", os.path.join(PKG, "csrc", "libpicsong_hip
 
 PICSONG_OK = 0
 PICSONG_ERR_RATE = -7
+PICSONG_ERR_QUALITY = -8
 
 
 class Params(C.Structure):
@@ -54,6 +55,8 @@ EXPORTS = [
     "picsong_lut_save",
     "picsong_rate_qs", "picsong_ctx_set_qs", "picsong_encode_frame_rate", "picsong_encode_frames_rate",
     "picsong_encode_rgb_frame_rate",
+    "picsong_psnr_to_sse", "picsong_sse_to_psnr", "picsong_frames_sse", "picsong_encode_frame_quality",
+    "picsong_encode_frames_quality", "picsong_encode_rgb_frame_quality",
 ]
 
 _lib = None
@@ -160,6 +163,16 @@ def load():
                                                  C.POINTER(i), C.POINTER(i)]
         L.picsong_encode_rgb_frame_rate.argtypes = [vp, vp, vp, vp, i, C.c_size_t, i, i, vp, C.c_size_t, vp,
                                                     C.POINTER(i), C.POINTER(i)]
+    if hasattr(L, "picsong_frames_sse"):
+        u64 = C.c_uint64
+        L.picsong_psnr_to_sse.argtypes = [C.c_double, u64, C.POINTER(u64)]
+        L.picsong_sse_to_psnr.argtypes = [u64, u64, C.POINTER(C.c_double)]
+        L.picsong_frames_sse.argtypes = [vp, i, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
+        L.picsong_encode_frame_quality.argtypes = [vp, vp, i, u64, i, i, vp, vp, C.POINTER(i), C.POINTER(i), C.POINTER(u64)]
+        L.picsong_encode_frames_quality.argtypes = [vp, i, vp, C.c_size_t, i, u64, i, i, vp, C.c_size_t, vp,
+                                                    C.POINTER(i), C.POINTER(i), C.POINTER(u64)]
+        L.picsong_encode_rgb_frame_quality.argtypes = [vp, vp, vp, vp, i, u64, i, i, vp, C.c_size_t, vp,
+                                                       C.POINTER(i), C.POINTER(i), C.POINTER(u64)]
     _lib = L
     return L
 
@@ -181,6 +194,30 @@ def _check_rate(rc):
     if rc == PICSONG_ERR_RATE:
         raise RateError(load().picsong_last_error().decode())
     _check(rc)
+
+
+class QualityError(PicsongError):
+    """No quantiser of the search range meets the distortion limit (PICSONG_ERR_QUALITY)."""
+
+
+def _check_quality(rc):
+    if rc == PICSONG_ERR_QUALITY:
+        raise QualityError(load().picsong_last_error().decode())
+    _check(rc)
+
+
+def psnr_to_sse(psnr_db, samples):
+    """The largest SSE over `samples` 8-bit samples whose PSNR is at least psnr_db (picsong_psnr_to_sse)."""
+    v = C.c_uint64()
+    _check(load().picsong_psnr_to_sse(psnr_db, samples, C.byref(v)))
+    return v.value
+
+
+def sse_to_psnr(sse, samples):
+    """The PSNR (dB) of an SSE over `samples` 8-bit samples; inf for sse = 0 (picsong_sse_to_psnr)."""
+    v = C.c_double()
+    _check(load().picsong_sse_to_psnr(sse, samples, C.byref(v)))
+    return v.value
 
 
 def rate_qs(j):
@@ -354,6 +391,51 @@ class Codec:
                                                          target_shorts, j_min, j_max, self._p(out), out.stride(0),
                                                          self._stream(), C.byref(j), t))
         return j.value, [out[k, :t[k]] for k in range(3)]
+
+    # ---- quality control: distortion measurement, and the 9/7 encode calls with qs chosen to meet an SSE limit ----
+    def frames_sse(self, a, b, out=None):
+        """a, b: uint8 padded frames [n, AH*AW] (or one frame [AH*AW]); returns an int64 device tensor [n] holding the SSE
+        over the visible samples of each pair (picsong_frames_sse, asynchronous)."""
+        if a.dim() == 1:
+            a, b = a[None], b[None]
+        n = a.shape[0]
+        assert b.shape[0] == n and a.stride(-1) == 1 and b.stride(-1) == 1
+        if out is None:
+            out = self.torch.empty(n, dtype=self.torch.int64, device=self.dev)
+        _check(self.L.picsong_frames_sse(self.h, n, self._p(a), a.stride(0), self._p(b), b.stride(0), self._p(out),
+                                         self._stream()))
+        return out
+
+    def encode_frame_quality(self, frame_u8_padded, max_sse, j_min=0, j_max=0, iter_=0, out=None):
+        """Returns (j, codestream, sse): the stream of picsong_encode_frame at qs = rate_qs(j), j the quantiser search's
+        result for max_sse; raises QualityError when nothing of the range meets it."""
+        if out is None:
+            out = self.torch.empty(self.max_stream_shorts(), dtype=self.torch.int16, device=self.dev)
+        j, t, e = C.c_int(), C.c_int(), C.c_uint64()
+        _check_quality(self.L.picsong_encode_frame_quality(self.h, self._p(frame_u8_padded), iter_, max_sse, j_min, j_max,
+                                                           self._p(out), self._stream(), C.byref(j), C.byref(t), C.byref(e)))
+        return j.value, out[:t.value], e.value
+
+    def encode_frames_quality(self, frames_u8_padded, max_sse, j_min=0, j_max=0, first_iter=0):
+        """frames_u8_padded: uint8 [n, AH*AW], n <= 16; max_sse for the sum over the n frames.  Returns (j, streams, the
+        per-frame SSE)."""
+        n = frames_u8_padded.shape[0]
+        assert frames_u8_padded.stride(-1) == 1
+        out = self.torch.empty((n, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        j, t, e = C.c_int(), (C.c_int * n)(), (C.c_uint64 * n)()
+        _check_quality(self.L.picsong_encode_frames_quality(self.h, n, self._p(frames_u8_padded), frames_u8_padded.stride(0),
+                                                            first_iter, max_sse, j_min, j_max, self._p(out), out.stride(0),
+                                                            self._stream(), C.byref(j), t, e))
+        return j.value, [out[f, :t[f]] for f in range(n)], [int(v) for v in e]
+
+    def encode_rgb_frame_quality(self, r, g, b, max_sse, j_min=0, j_max=0, header_mask=1):
+        """max_sse for the sum over the three planes.  Returns (j, the three codestreams, the SSE of R, G, B)."""
+        out = self.torch.empty((3, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        j, t, e = C.c_int(), (C.c_int * 3)(), (C.c_uint64 * 3)()
+        _check_quality(self.L.picsong_encode_rgb_frame_quality(self.h, self._p(r), self._p(g), self._p(b), header_mask,
+                                                               max_sse, j_min, j_max, self._p(out), out.stride(0),
+                                                               self._stream(), C.byref(j), t, e))
+        return j.value, [out[k, :t[k]] for k in range(3)], [int(v) for v in e]
 
     # ---- training: the statistics a probability table is made from (k = 0, -cp 2 contexts; no table needed) ----
     def train_begin(self, **geometry):

@@ -34,6 +34,7 @@ extern "C" {
 #define PICSONG_ERR_RANGE (-5)      /* a codeblock exceeded the supported magnitude range */
 #define PICSONG_ERR_NODEVICE (-6)   /* no usable GPU: the product has no CPU fallback */
 #define PICSONG_ERR_RATE (-7)       /* no quantiser of the search range meets the target size */
+#define PICSONG_ERR_QUALITY (-8)    /* no quantiser of the search range meets the distortion limit */
 
 #define PICSONG_CB 64               /* codeblock edge, BPC/BPCEngine.cuh:29-36 */
 #define PICSONG_CB_WORDS 4096       /* staging ints per codeblock */
@@ -418,6 +419,52 @@ int picsong_encode_rgb_frame_rate(picsong_ctx *ctx, const uint8_t *d_r, const ui
                                   size_t target_shorts, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
                                   void *stream, int *h_j, int *h_totals);
 
+/* ---- encode to a target quality (OpenJPEG -q / Kakadu's quality targets; the reference has no counterpart): the 9/7
+ *      calls with the quantiser gain qs CHOSEN so that the decoded frames stay within a distortion limit.
+ *      The measure is the SSE, the sum of squared differences over the VISIBLE W x H samples (padding is not counted),
+ *      an exact integer.  picsong_psnr_to_sse / picsong_sse_to_psnr (host only) convert for 8-bit samples:
+ *      max_sse = floor(65025 * samples / 10^(dB / 10)) in double arithmetic, PSNR = 10 log10(65025 * samples / sse), HUGE_VAL
+ *      for sse = 0; PICSONG_ERR_ARG for null pointers, samples = 0 and a PSNR that is not finite.
+ *      picsong_frames_sse measures: d_sse[f] = the SSE of frame f of d_a against frame f of d_b, n = 1..64 padded frames
+ *      (row stride AW) a_stride / b_stride bytes apart; d_sse is a device uint64[n], overwritten.  ASYNCHRONOUS on
+ *      `stream`, any pointer alignment (16-byte aligned pointers and strides take the vector loads, same result), any
+ *      context -- lossless, -cp 3, grey or RGB: only its geometry is used; an RGB frame is three planes, n = 3.  Refused
+ *      (PICSONG_ERR_ARG, nothing launched): null pointers, n outside 1..64, a stride below a padded frame when n > 1.
+ *      The search runs over the grid G and the sub-ranges of the rate calls above.  SSE against j is not monotone either
+ *      (a finer quantiser can decode a few squares worse), so the result is again a procedure's, the mirror of the rate
+ *      one: with G' = the entries of G inside [j_min, j_max],
+ *          lo = -1, hi = len(G');  while hi - lo > 1: mid = (lo + hi) / 2;  sse(G'[mid]) <= max_sse ? hi = mid : lo = mid
+ *      and the result is G'[hi], the coarsest quantiser the bisection finds that meets the limit; sse(j) = the SSE between
+ *      the input and what picsong_decode_frame / picsong_decode_rgb_frame return for the stream coded at q(j), summed
+ *      over the call's frames / the three planes.  13 or 14 probes over the whole grid.  max_sse = 0 is a legal request.
+ *      On success *h_j is the result, the streams are BYTE-IDENTICAL to the plain encode calls' on a context at q(*h_j)
+ *      (the header carries that qs), h_total(s) receive their lengths and h_sse the SSE per frame / per plane R, G, B
+ *      (1, n and 3 of each).  When nothing meets the limit (hi = len(G')) the call returns PICSONG_ERR_QUALITY with
+ *      *h_j = 0; the streams are then unspecified, and no short beyond picsong_max_stream_shorts per stream is written.
+ *      How.  The coder is lossless over the quantised coefficients, so a probe needs no coder launch: the transform runs
+ *      once with unit steps; per candidate the quantise pass writes int32 coefficients, the synthesis at q(j) -- the
+ *      dividing kernels, whose pixels every reciprocal form is verified against -- writes clamped pixels, and the SSE
+ *      kernel compares them with the input.  Up to three candidates a round (two steps of the procedure), back to back
+ *      over one set of n-frame buffers; one read-back through pinned memory per round.  The result is then quantised,
+ *      coded and packed as the rate calls' final step.  The calls are SYNCHRONOUS on `stream`.  The lengths stay where the
+ *      plain calls leave theirs.  The context's own qs is NOT changed (picsong_ctx_set_qs).  picsong_range_flag sees only
+ *      the result's own encode.  n = 1..16; strides and alignment as the matching rate call; any -k.
+ *      Refused (PICSONG_ERR_ARG, nothing launched, outputs untouched): lossless and -cp 3 contexts, the grey calls on an
+ *      RGB context and the RGB call on a grey one, a bad range or one without a grid entry, the null / stride / alignment
+ *      checks of the matching rate call (h_j, h_total(s) and h_sse must not be null), a context without its table. ---- */
+int picsong_psnr_to_sse(double psnr_db, uint64_t samples, uint64_t *max_sse);
+int picsong_sse_to_psnr(uint64_t sse, uint64_t samples, double *psnr_db);
+int picsong_frames_sse(picsong_ctx *ctx, int n, const uint8_t *d_a, size_t a_stride, const uint8_t *d_b, size_t b_stride,
+                       uint64_t *d_sse, void *stream);
+int picsong_encode_frame_quality(picsong_ctx *ctx, const uint8_t *d_frame, int iter, uint64_t max_sse, int j_min, int j_max,
+                                 uint16_t *d_stream, void *stream, int *h_j, int *h_total, uint64_t *h_sse);
+int picsong_encode_frames_quality(picsong_ctx *ctx, int n, const uint8_t *d_frames, size_t frame_stride, int first_iter,
+                                  uint64_t max_sse, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
+                                  void *stream, int *h_j, int *h_totals, uint64_t *h_sse);
+int picsong_encode_rgb_frame_quality(picsong_ctx *ctx, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
+                                     uint64_t max_sse, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
+                                     void *stream, int *h_j, int *h_totals, uint64_t *h_sse);
+
 /* ---- intra-frame sharding (BASELINE config 5): codeblocks are independent
  *      (correctCBBorders zeroes outside neighbours, BPC/BPCEngine.cu:465-484), so a rank can code
  *      the stripe [cb_begin, cb_begin + cb_count) of the frame's raster-ordered codeblocks.  The
@@ -458,7 +505,9 @@ int picsong_pad_frame_host(const uint8_t *in, int w, int h, uint8_t *out, int aw
  *      BPC/BPCEngine.cu:2318-2422, "BPC acum time").  profile_begin(capacity) arms a ring of event
  *      sets; every later encode_frame records into the next set without synchronising;
  *      profile_read synchronises the last set and returns, per recorded frame, 3 floats:
- *      {dwt_ms (all levels), bpc_ms (bpc_kernel), pack_ms (scan + pack)}.  capacity 0 disarms. ---- */
+ *      {dwt_ms (all levels), bpc_ms (bpc_kernel), pack_ms (scan + pack)}.  capacity 0 disarms.
+ *      A quality call (picsong_encode_frame_quality and its mirrors) records one set per PROBE instead:
+ *      {quantise_ms, synthesis_ms, sse_ms}. ---- */
 int picsong_profile_begin(picsong_ctx *ctx, int capacity);
 int picsong_profile_read(picsong_ctx *ctx, int *n_frames, float *ms, int ms_capacity_frames);
 
