@@ -989,6 +989,30 @@ __device__ __forceinline__ void enc_spp_coeff(EncCoder &c, uint32_t rowbit, uint
         enc_site2<J>(c, onem, onem & __builtin_amdgcn_ballot_w64((s2 & rowbit) != 0u), Q4, prec, upper_mask);
 }
 
+// ---- fully visited significance half-passes of the k = 0 encoder (PICSONG_ENC_SPP_DENSE, default 1) ------------------
+// A half-pass in which every one of the 32 rows has a lane with work (rows == 0xFFFFFFFF: on a photographic frame nearly
+// every half-pass of the first planes below a codeblock's msb) visits its rows in order, so a row's three lane masks are
+// the carries of the column's bit-reversed words (shl_carry, as in the refinement pass's dense half-passes): xa = A, xn =
+// N, xs = N & s2, row 0 at bit 31.  Per row and column that is three half-rate instructions where the row-bit tests take
+// three ands and three compares, and no row bit exists: no move per row, no test of `sub` per row, the eight groups a
+// counted loop.  All three words shift at every row whether or not its sites run, so they stay aligned.  The sign word is
+// a subset of N, N of ~A (an idle half: A all ones, N = 0), so the sites take the carries as they come.  The sites and
+// their order are the generic body's.  A half-pass with a row nobody codes takes the generic body, which skips it: no
+// row pays for shifts it does not use (what made this form lose as the only one, see shl_carry).  =0: the generic body
+// alone, and the first plane's row-bit tests.
+#ifndef PICSONG_ENC_SPP_DENSE
+#define PICSONG_ENC_SPP_DENSE 1
+#endif
+template <int J>
+__device__ __forceinline__ void enc_spp_coeff_dense(EncCoder &c, uint32_t &xa, uint32_t &xn, uint32_t &xs,
+                                                    uint32_t P4, uint32_t Q4, uint32_t prec, uint32_t upper_mask)
+{
+    const uint64_t onm = ~shl_carry(xa), onem = shl_carry(xn), sgn = shl_carry(xs);
+    if (onm == 0ull) return;
+    enc_site2<J>(c, onm, onem, P4, prec, upper_mask);
+    if (onem != 0ull) enc_site2<J>(c, onem, sgn, Q4, prec, upper_mask);
+}
+
 // ---- the first plane of the k = 0 encoder (PICSONG_ENC_FIRST_PLANE, default 1) -----------------------------------------
 // Step 0 of a wave codes plane `msb` of each half's own codeblock: nothing is significant yet (A = 0, N = B), and the
 // generic plane body pays for much that cannot happen there.  Every coded lane codes at every significance site, so the
@@ -1013,6 +1037,15 @@ __device__ __forceinline__ void enc_spp_coeff_first(EncCoder &c, uint32_t rowbit
     if (onem != 0ull)
         enc_site2<J>(c, onem, onem & __builtin_amdgcn_ballot_w64((s2 & rowbit) != 0u), Q4, prec, upper_mask);
 }
+// the same off the carries of the bit-reversed B and B & s2 (PICSONG_ENC_SPP_DENSE): step 0 visits every row in order
+template <int J>
+__device__ __forceinline__ void enc_spp_coeff_first_dense(EncCoder &c, uint64_t onm, uint32_t &xb, uint32_t &xs,
+                                                          uint32_t P4, uint32_t Q4, uint32_t prec, uint32_t upper_mask)
+{
+    const uint64_t onem = shl_carry(xb), sgn = shl_carry(xs);
+    enc_site2<J>(c, onm, onem, P4, prec, upper_mask);
+    if (onem != 0ull) enc_site2<J>(c, onem, sgn, Q4, prec, upper_mask);
+}
 // The significance pass of rows 32 HW .. 32 HW + 31 at step 0.  BL / BR: the plane's bits of the lane's columns (0 in an
 // idle half), BPL / BNL: lane-1's right and lane+1's left column, sgNL: lane+1's left sign column; onm != 0.
 template <int HW>
@@ -1026,12 +1059,22 @@ __device__ __forceinline__ void enc_spp_first_half(EncCoder &c, uint64_t onm, co
                                  up_of(BR, HW), up_of(sgR, HW), 0u, 0u,
                                  w_of(BL, HW), w_of(sgL, HW), w_of(BNL, HW), w_of(sgNL, HW), w_of(sgR, HW));
     const uint32_t bl = w_of(BL, HW), br = w_of(BR, HW);
+#if PICSONG_ENC_SPP_DENSE
+    uint32_t xbl = bitrev32(bl), xsl = bitrev32(bl & cpL.s2), xbr = bitrev32(br), xsr = bitrev32(br & cpR.s2);
+#endif
 #pragma unroll 1
     for (uint32_t g4 = 0u; g4 < 32u; g4 += 4u) {
         // left column: contexts 0..3 (the first table word) and sign contexts 0 / 1
         const uint32_t selL = bfi32(0x01010101u, spread4_raw<0>(cpL.n0, g4), spread4_raw<1>(cpL.n1, g4)) & 0x03030303u;
         const uint32_t P4L = __builtin_amdgcn_perm(0u, pl.sig0, selL), P4R = sig_probs4_07(cpR, pl, g4);
         const uint32_t Q4L = __builtin_amdgcn_perm(0u, pl.sign, spread4(cpL.c1, g4)), Q4R = sign_probs4(cpR, pl, g4);
+#if PICSONG_ENC_SPP_DENSE
+#define PS_SPP_ROW(J)                                                                                    \
+        {                                                                                                 \
+            enc_spp_coeff_first_dense<J>(c, onm, xbl, xsl, P4L, Q4L, prec, upper_mask);                   \
+            enc_spp_coeff_first_dense<J>(c, onm, xbr, xsr, P4R, Q4R, prec, upper_mask);                   \
+        }
+#else
         const uint32_t gbit = 1u << g4;
 #define PS_SPP_ROW(J)                                                                                    \
         {                                                                                                 \
@@ -1039,6 +1082,7 @@ __device__ __forceinline__ void enc_spp_first_half(EncCoder &c, uint64_t onm, co
             enc_spp_coeff_first<J>(c, rowbit, onm, bl, cpL.s2, P4L, Q4L, prec, upper_mask);               \
             enc_spp_coeff_first<J>(c, rowbit, onm, br, cpR.s2, P4R, Q4R, prec, upper_mask);               \
         }
+#endif
         PS_SPP_ROW(0) PS_SPP_ROW(1) PS_SPP_ROW(2) PS_SPP_ROW(3)
 #undef PS_SPP_ROW
     }
@@ -1756,6 +1800,28 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
                 constexpr bool GATE8 = PICSONG_ENC_CTX8_GATE && !BULK;
                 uint32_t m8 = 0xFFFFFFFFu;
                 if (GATE8 && rows) m8 = wave_or32(cpL.n3 | cpR.n3);
+                if constexpr (!BULK && PICSONG_ENC_SPP_DENSE != 0) {
+                    if (rows == 0xFFFFFFFFu) {
+                        // every row has work: the rows in order, their lane masks off the carries (enc_spp_coeff_dense)
+                        uint32_t xal = bitrev32(al), xnl = bitrev32(nl), xsl = bitrev32(nl & cpL.s2);
+                        uint32_t xar = bitrev32(ar), xnr = bitrev32(nr), xsr = bitrev32(nr & cpR.s2);
+#pragma unroll 1
+                        for (uint32_t g4 = 0u; g4 < 32u; g4 += 4u) {
+                            uint32_t P4L, P4R;
+                            if constexpr (GATE8) {
+                                P4L = sig_probs4_07(cpL, pl, g4); P4R = sig_probs4_07(cpR, pl, g4);
+                                if ((m8 >> g4) & 0xFu) { P4L = sig_probs4_fix8(cpL, pl, g4, P4L); P4R = sig_probs4_fix8(cpR, pl, g4, P4R); }
+                            } else { P4L = sig_probs4(cpL, pl, g4); P4R = sig_probs4(cpR, pl, g4); }
+                            const uint32_t Q4L = sign_probs4(cpL, pl, g4), Q4R = sign_probs4(cpR, pl, g4);
+#define PS_SPP_ROW(J)                                                                                    \
+                            enc_spp_coeff_dense<J>(c, xal, xnl, xsl, P4L, Q4L, prec, upper_mask);         \
+                            enc_spp_coeff_dense<J>(c, xar, xnr, xsr, P4R, Q4R, prec, upper_mask);
+                            PS_SPP_ROW(0) PS_SPP_ROW(1) PS_SPP_ROW(2) PS_SPP_ROW(3)
+#undef PS_SPP_ROW
+                        }
+                        rows = 0u;
+                    }
+                }
                 while (rows) {
                     // a group of four rows: their probabilities are gathered together (sig_probs4_07 / _fix8)
                     const uint32_t g4 = (uint32_t)__builtin_ctz(rows) & ~3u;
@@ -1878,9 +1944,14 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
     // codeword store of the block, the lanes' first-reservation stores to word 0 included
     wave_stores_issued();
     if (valid && size == 4096u) {
+        // (PICSONG_ENC_SPP_DENSE: with a third significance body the lane's byte offset into the coefficient array, kept
+        // for this fallback alone, was reloaded from the wave's scratch in every half-pass: formed again here instead)
+        uint32_t cbytee = cbyte;
+        if constexpr (PEEL && PICSONG_ENC_SPP_DENSE != 0)
+            cbytee = (uint32_t)((cbe / a.ncx * 64) * a.AW + cbe % a.ncx * 64 + 2 * (int)te) * esz;
         for (int i = 0; i < 64; i++) {
             uint32_t m0, m1, n0, n1;
-            load_row(a, cbyte + (uint32_t)i * rstride, m0, m1, n0, n1);
+            load_row(a, cbytee + (uint32_t)i * rstride, m0, m1, n0, n1);
             const uint32_t w0 = ((m0 << 1) + n0) & 0xFFFFu, w1 = ((m1 << 1) + n1) & 0xFFFFu;
             *reinterpret_cast<uint32_t *>(ste + te * 128u + 2u * (uint32_t)i) = w0 | (w1 << 16);
         }
