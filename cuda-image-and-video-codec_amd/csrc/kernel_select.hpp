@@ -12,6 +12,7 @@
 #include "bpc_kernels.hpp"
 #include "dwt_kernels.hpp"
 #include "launch_plan.hpp"
+#include "layout_kernels.hpp"
 #include "pack_kernels.hpp"
 #include "quality_kernels.hpp"
 #include "rate_kernels.hpp"
@@ -31,6 +32,7 @@ using BpcKernel = void (*)(BpcArgs);
 using StatsKernel = void (*)(BpcArgs, unsigned long long *, int);
 using QuantKernel = void (*)(QuantArgs);
 using SseKernel = void (*)(SseArgs);
+using LayoutKernel = void (*)(LayoutArgs);
 
 // ---- forward transform: one level (256 threads, grid f.gx x f.gy x frames)
 template <int BAND, bool VEC>
@@ -293,6 +295,71 @@ inline SseLaunch select_sse(const SseArgs &s)
     const unsigned wgs = (unsigned)(tiles > kSseMaxWgs ? kSseMaxWgs : (tiles < 1 ? 1 : tiles));
     return { vec ? sse_kernel<true> : sse_kernel<false>, wgs };
 }
+
+// ---- pixel layouts (ingest_kernel / emit_kernel, layout_kernels.hpp).  bytes a pixel, planes of the padded side
+inline int layout_bpp(int layout) { return layout < kLayoutRgb24 ? 1 : (layout < kLayoutRgba32 ? 3 : 4); }
+inline int layout_planes(int layout) { return layout == kLayoutGrey8 ? 1 : 3; }
+// What picsong_ingest_frames / picsong_emit_frames (and the whole-frame calls over them) refuse, as a message; nullptr:
+// the arguments are fine.  `data`, pitch, plane_stride: the picsong_image's; n frames frame_stride bytes apart; the
+// padded side at `padded`, frames padded_stride apart.
+inline const char *layout_refusal(int layout, const void *data, size_t pitch, size_t plane_stride, size_t frame_stride,
+                                  const void *padded, size_t padded_stride, int n, int W, int H, int AW, int AH)
+{
+    if (!data || !padded) return "null pointer";
+    if (layout < 0 || layout >= kLayoutCount) return "unknown layout";
+    if (n < 1 || n > kLayoutMaxFrames) return "n outside 1..64";
+    if (W < 1 || H < 1 || AW < W || AH < H) return "bad geometry";
+    if (AW - W > W || AH - H > H) return "the mirror padding adds more columns / rows than the frame has";
+    const size_t row = (size_t)W * (size_t)layout_bpp(layout);
+    if (pitch < row) return "pitch smaller than a row of pixels";
+    size_t span = (size_t)(H - 1) * pitch + row;                        // the bytes one plane (one interleaved frame) spans
+    if (layout == kLayoutPlanar3) {
+        if (plane_stride < span) return "plane_stride smaller than a plane";
+        span += 2 * plane_stride;
+    }
+    if (n > 1 && frame_stride < span) return "frame_stride smaller than a frame";
+    if (n > 1 && padded_stride < (size_t)layout_planes(layout) * (size_t)AW * (size_t)AH) return "padded_stride smaller than a frame's padded planes";
+    return nullptr;
+}
+// The launch: grid.x = the row batches of a plane (layout_rows), grid.y = the planes of a planar layout, grid.z = frame;
+// the vector form where the image side is 4-byte and the padded side 16-byte aligned, else the per-byte one.
+struct LayoutLaunch { LayoutKernel kernel; dim3 grid; bool vec; };
+inline LayoutArgs layout_args(int layout, const void *data, size_t pitch, size_t plane_stride, size_t frame_stride, const void *padded,
+                              size_t padded_stride, int n, int W, int H, int AW, int AH)
+{
+    LayoutArgs a;
+    memset(&a, 0, sizeof a);
+    a.img = (uint8_t *)data; a.pitch = pitch;
+    a.plane_stride = layout == kLayoutPlanar3 ? plane_stride : 0; a.frame_stride = n > 1 ? frame_stride : 0;
+    a.pad = (uint8_t *)padded; a.pad_stride = n > 1 ? padded_stride : 0; a.P = (unsigned long long)AW * (unsigned long long)AH;
+    a.W = W; a.H = H; a.AW = AW; a.AH = AH;
+    a.a16 = ((((uintptr_t)a.img) | a.pitch | a.plane_stride | a.frame_stride) & 15u) == 0 ? 1 : 0;
+    return a;
+}
+template <template <int, bool> class K>
+inline LayoutLaunch select_layout(int layout, const LayoutArgs &a)
+{
+    const bool vec = ((((uintptr_t)a.img) | a.pitch | a.plane_stride | a.frame_stride) & 3u) == 0 &&
+                     ((((uintptr_t)a.pad) | a.pad_stride) & 15u) == 0;
+    const unsigned ppt = layout < kLayoutRgb24 ? 16u : 4u, max_rows = layout < kLayoutRgb24 ? 64u : 21u;
+    const unsigned rows = layout_rows(((unsigned)a.W + ppt - 1u) / ppt, max_rows);
+    const dim3 grid(((unsigned)a.H + rows - 1u) / rows, layout == kLayoutPlanar3 ? 3u : 1u, 1u);
+    LayoutKernel k = nullptr;
+    switch (layout) {
+    case kLayoutGrey8:   k = vec ? K<kLayoutGrey8, true>::fn() : K<kLayoutGrey8, false>::fn(); break;
+    case kLayoutPlanar3: k = vec ? K<kLayoutPlanar3, true>::fn() : K<kLayoutPlanar3, false>::fn(); break;
+    case kLayoutRgb24:   k = vec ? K<kLayoutRgb24, true>::fn() : K<kLayoutRgb24, false>::fn(); break;
+    case kLayoutBgr24:   k = vec ? K<kLayoutBgr24, true>::fn() : K<kLayoutBgr24, false>::fn(); break;
+    case kLayoutRgba32:  k = vec ? K<kLayoutRgba32, true>::fn() : K<kLayoutRgba32, false>::fn(); break;
+    case kLayoutBgra32:  k = vec ? K<kLayoutBgra32, true>::fn() : K<kLayoutBgra32, false>::fn(); break;
+    }
+    return { k, grid, vec };
+}
+template <int L, bool VEC> struct IngestOf { static LayoutKernel fn() { return ingest_kernel<L, VEC>; } };
+template <int L, bool VEC> struct EmitOf { static LayoutKernel fn() { return emit_kernel<L, VEC>; } };
+static_assert(LayoutTraits<kLayoutGrey8>::max_rows == 64 && LayoutTraits<kLayoutRgb24>::max_rows == 21, "select_layout's rows are the kernels'");
+inline LayoutLaunch select_ingest(int layout, const LayoutArgs &a) { return select_layout<IngestOf>(layout, a); }
+inline LayoutLaunch select_emit(int layout, const LayoutArgs &a) { return select_layout<EmitOf>(layout, a); }
 
 // workgroups (256 threads) of the element-wise kernels -- level shift, clamp, RGB transforms -- over n items, grid-stride
 // beyond `cap`

@@ -267,6 +267,29 @@ int frames_sse(const Go &go, const uint8_t *a, size_t a_pitch, unsigned long lon
     return go(select_sse(s).kernel, dim3(select_sse(s).wgs), 256u, s);
 }
 
+// ---- pixel layouts (layout_kernels.hpp): n frames of W x H pixels at a pitch into padded planar planes, and back.  The
+// arguments have passed layout_refusal.  *vec: the vector form ran
+template <class Go>
+int ingest_frames(const Go &go, int layout, const void *data, size_t pitch, size_t plane_stride, size_t frame_stride, uint8_t *padded,
+                  size_t padded_stride, int n, int W, int H, int AW, int AH, bool *vec = nullptr)
+{
+    const LayoutArgs a = layout_args(layout, data, pitch, plane_stride, frame_stride, padded, padded_stride, n, W, H, AW, AH);
+    LayoutLaunch l = select_ingest(layout, a);
+    l.grid.z = (unsigned)n;
+    if (vec) *vec = l.vec;
+    return go(l.kernel, l.grid, 256u, a);
+}
+template <class Go>
+int emit_frames(const Go &go, int layout, const uint8_t *padded, size_t padded_stride, void *data, size_t pitch, size_t plane_stride,
+                size_t frame_stride, int n, int W, int H, int AW, int AH, bool *vec = nullptr)
+{
+    const LayoutArgs a = layout_args(layout, data, pitch, plane_stride, frame_stride, padded, padded_stride, n, W, H, AW, AH);
+    LayoutLaunch l = select_emit(layout, a);
+    l.grid.z = (unsigned)n;
+    if (vec) *vec = l.vec;
+    return go(l.kernel, l.grid, 256u, a);
+}
+
 // ---- a probe of the quality calls (picsong_encode_frame_quality and its mirrors): the distortion of the nf coded arrays
 // at q(j), without the coder -- it is lossless over the quantised coefficients, so the decoder's pixels follow from them:
 //   quantise_kernel's int32 form over the unquantised float arrays (unit, unit_z bytes apart) into coef_i (P words each);

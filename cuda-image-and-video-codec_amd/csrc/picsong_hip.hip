@@ -101,6 +101,9 @@ struct picsong_ctx {
     uint8_t *q_pix;
     int q_cap;
     unsigned long long *d_sse, *h_sse;      // kQualitySlots each (lazy)
+    // image calls (picsong_encode_images and its mirrors): the padded planes between the layout kernels and the frame sequences
+    uint8_t *lay_buf;
+    size_t lay_cap;                         // bytes
 };
 
 // PICSONG_DWT_INV97=0 keeps the 9/7 synthesis levels off the lean kernel (select_inv): read once per process
@@ -402,6 +405,7 @@ void picsong_ctx_destroy(picsong_ctx *c)
     if (c->q_pix) (void)hipFree(c->q_pix);
     if (c->d_sse) (void)hipFree(c->d_sse);
     if (c->h_sse) (void)hipHostFree(c->h_sse);
+    if (c->lay_buf) (void)hipFree(c->lay_buf);
     if (c->prof_ev) {
         for (hipEvent_t e : *c->prof_ev) (void)hipEventDestroy(e);
         delete c->prof_ev;
@@ -2114,6 +2118,127 @@ int picsong_lut_save(const char *folder_c, int component, const picsong_lut_info
         if (fclose(f) != 0) return fail(PICSONG_ERR_IO, "lut_save: writing %s failed", path.c_str());
     }
     return PICSONG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// frames as applications hold them (layout_kernels.hpp): pitched, unpadded, interleaved images to and from the padded
+// planar planes, on the device; the whole-frame calls run the plain frame sequences behind / before them
+// ---------------------------------------------------------------------------------------------
+static int layout_args_ok(const picsong_ctx *c, int n, const picsong_image *img, size_t frame_stride, const void *d_padded,
+                          size_t padded_stride, const char *who)
+{
+    if (!c || !img) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (const char *why = layout_refusal(img->layout, img->data, img->pitch, img->plane_stride, frame_stride, d_padded, padded_stride, n,
+                                         c->p.width, c->p.height, c->aw, c->ah))
+        return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+    return PICSONG_OK;
+}
+
+int picsong_ingest_frames(picsong_ctx *c, int n, const picsong_image *src, size_t frame_stride, uint8_t *d_padded,
+                          size_t padded_stride, void *stream)
+{
+    if (int rc = layout_args_ok(c, n, src, frame_stride, d_padded, padded_stride, "ingest_frames")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return ingest_frames(HipGo{ (hipStream_t)stream }, src->layout, src->data, src->pitch, src->plane_stride, frame_stride, d_padded,
+                         padded_stride, n, c->p.width, c->p.height, c->aw, c->ah);
+}
+
+int picsong_emit_frames(picsong_ctx *c, int n, const uint8_t *d_padded, size_t padded_stride, const picsong_image *dst,
+                        size_t frame_stride, void *stream)
+{
+    if (int rc = layout_args_ok(c, n, dst, frame_stride, d_padded, padded_stride, "emit_frames")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return emit_frames(HipGo{ (hipStream_t)stream }, dst->layout, d_padded, padded_stride, dst->data, dst->pitch, dst->plane_stride,
+                       frame_stride, n, c->p.width, c->p.height, c->aw, c->ah);
+}
+
+// the context's padded planes for the image calls: `planes` of P bytes (hipMalloc: 256-byte aligned)
+static int ensure_layout(picsong_ctx *c, size_t planes)
+{
+    if (planes * c->P <= c->lay_cap) return PICSONG_OK;
+    HIP_TRY(hipDeviceSynchronize());                 // an earlier call may still be running on the old buffer
+    if (c->lay_buf) (void)hipFree(c->lay_buf);
+    c->lay_buf = nullptr; c->lay_cap = 0;
+    HIP_TRY(hipMalloc(&c->lay_buf, planes * c->P));
+    c->lay_cap = planes * c->P;
+    return PICSONG_OK;
+}
+// what the image calls check before anything is launched: the layout arguments (the padded side is the context's own
+// buffer) and the layout against the context's colour mode
+static int image_args_ok(const picsong_ctx *c, int n, const picsong_image *img, size_t frame_stride, const void *d_streams, bool rgb,
+                         const char *who)
+{
+    if (!c || !img || !d_streams) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    // (the padded side is the context's buffer, allocated later: any non-null address stands for it, its stride a frame's planes)
+    if (int rc = layout_args_ok(c, n, img, frame_stride, c, (size_t)3 * c->P, who)) return rc;
+    if (rgb != (c->p.is_rgb != 0)) return fail(PICSONG_ERR_ARG, "%s: the context is %s", who, rgb ? "not an RGB one" : "an RGB one");
+    if (rgb != (img->layout != kLayoutGrey8))
+        return fail(PICSONG_ERR_ARG, "%s: layout %d on %s context", who, img->layout, rgb ? "an RGB" : "a grey");
+    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 2 contexts only, as the frame call behind it", who);
+    return PICSONG_OK;
+}
+
+int picsong_encode_images(picsong_ctx *c, int n, const picsong_image *src, size_t frame_stride, int first_iter, uint16_t *d_streams,
+                          size_t stream_stride, void *stream)
+{
+    const char *who = "encode_images";
+    if (int rc = image_args_ok(c, n, src, frame_stride, d_streams, false, who)) return rc;
+    if (n > 1 && stream_stride < picsong_max_stream_shorts(c->aw, c->ah))
+        return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
+    BpcArgs a;
+    if (int rc = bpc_args(c, a, 0)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_layout(c, (size_t)n)) return rc;
+    if (int rc = ingest_frames(HipGo{ (hipStream_t)stream }, src->layout, src->data, src->pitch, src->plane_stride, frame_stride, c->lay_buf,
+                               c->P, n, c->p.width, c->p.height, c->aw, c->ah)) return rc;
+    return picsong_encode_frames(c, n, c->lay_buf, c->P, first_iter, d_streams, stream_stride, stream);
+}
+
+int picsong_decode_images(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, const picsong_image *dst,
+                          size_t frame_stride, void *stream)
+{
+    const char *who = "decode_images";
+    if (int rc = image_args_ok(c, n, dst, frame_stride, d_streams, false, who)) return rc;
+    if (n > 1 && stream_stride < picsong_max_stream_shorts(c->aw, c->ah))
+        return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
+    BpcArgs a;
+    if (int rc = bpc_args(c, a, 0)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_layout(c, (size_t)n)) return rc;
+    if (int rc = picsong_decode_frames(c, n, d_streams, stream_stride, c->lay_buf, c->P, stream)) return rc;
+    return emit_frames(HipGo{ (hipStream_t)stream }, dst->layout, c->lay_buf, c->P, dst->data, dst->pitch, dst->plane_stride, frame_stride,
+                       n, c->p.width, c->p.height, c->aw, c->ah);
+}
+
+int picsong_encode_rgb_image(picsong_ctx *c, const picsong_image *src, int header_mask, uint16_t *d_streams, size_t stream_stride,
+                             void *stream)
+{
+    const char *who = "encode_rgb_image";
+    if (int rc = image_args_ok(c, 1, src, 0, d_streams, true, who)) return rc;
+    if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah))
+        return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
+    BpcArgs a;
+    if (int rc = bpc_args_rgb(c, a)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_layout(c, 3)) return rc;
+    if (int rc = ingest_frames(HipGo{ (hipStream_t)stream }, src->layout, src->data, src->pitch, src->plane_stride, 0, c->lay_buf, 0, 1,
+                               c->p.width, c->p.height, c->aw, c->ah)) return rc;
+    return picsong_encode_rgb_frame(c, c->lay_buf, c->lay_buf + c->P, c->lay_buf + 2 * c->P, header_mask, d_streams, stream_stride, stream);
+}
+
+int picsong_decode_rgb_image(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, const picsong_image *dst, void *stream)
+{
+    const char *who = "decode_rgb_image";
+    if (int rc = image_args_ok(c, 1, dst, 0, d_streams, true, who)) return rc;
+    if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah))
+        return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
+    BpcArgs a;
+    if (int rc = bpc_args_rgb(c, a)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_layout(c, 3)) return rc;
+    if (int rc = picsong_decode_rgb_frame(c, d_streams, stream_stride, c->lay_buf, c->lay_buf + c->P, c->lay_buf + 2 * c->P, stream)) return rc;
+    return emit_frames(HipGo{ (hipStream_t)stream }, dst->layout, c->lay_buf, 0, dst->data, dst->pitch, dst->plane_stride, 0, 1,
+                       c->p.width, c->p.height, c->aw, c->ah);
 }
 
 int picsong_pad_frame_host(const uint8_t *in, int w, int h, uint8_t *out, int aw, int ah)

@@ -56,6 +56,7 @@ struct Options {
     double psnr = 0.0;                          // -psnr <dB>: choose qs so that the searched frames decode to at least that PSNR
     bool has_psnr = false;
     std::string compare;                        // -compare <raw file>: decoding, the PSNR of the output against that file
+    int layout = -1;                            // -layout: the pixel layout of the raw file (PICSONG_LAYOUT_*), -1: not given
 };
 
 [[noreturn]] void die(const std::string &msg)
@@ -124,7 +125,14 @@ void help()
         "                     video as with -rate: the search runs on the first min(frames, 16) frames (an RGB video: its first\n"
         "                     frame).  Not with -qs, -rate, -type 0, -cp 3 or -train\n"
         " -compare <file>     decoding: after the output is written, print its PSNR and SSE against that raw (or PGM) file of the\n"
-        "                     same geometry and planar layout.  Not with -reduce or -window\n";
+        "                     same geometry and planar layout.  Not with -reduce or -window\n"
+        " -layout grey|planar|rgb|bgr|rgba|bgra\n"
+        "                     the pixel layout of the raw file: the input's when coding, the output's when decoding; rows of\n"
+        "                     W * bpp bytes (1, 1, 3, 3, 4, 4 bytes a pixel; planar: the R, G, B planes one after the other;\n"
+        "                     alpha is ignored when coding and written as 255 when decoding).  grey for -components 1, the\n"
+        "                     others for -isRGB 1.  The frame is then uploaded as it is and padded / split (cropped /\n"
+        "                     interleaved) on the GPU: no host pass.  grey and planar give the files the flag's absence\n"
+        "                     gives.  Not with -reduce, -window, -train or (interleaved layouts) -compare\n";
 }
 
 template <typename T> void echo(const char *flag, const T &v)
@@ -182,6 +190,15 @@ Options parse(const Args &a)
         if (o.compare.empty()) die("Incorrect parameters. -compare takes the file to compare with.");
         echo("-compare", o.compare);
     }
+    if (a.has("-layout")) {
+        static const char *const names[] = { "grey", "planar", "rgb", "bgr", "rgba", "bgra" };
+        const std::string v = a.get("-layout");
+        for (int i = 0; i < 6; i++) if (v == names[i]) o.layout = i;
+        if (o.layout < 0) die("Incorrect parameters. -layout takes grey, planar, rgb, bgr, rgba or bgra.");
+        if (a.has("-reduce") || a.has("-window")) die("Incorrect parameters. -layout does not apply to -reduce or -window.");
+        if (a.has("-compare") && o.layout >= PICSONG_LAYOUT_RGB24) die("Incorrect parameters. -compare reads planar files: not with an interleaved -layout.");
+        echo("-layout", v);
+    }
     o.has_qs = a.has("-qs");
     if (o.cd == 0) {
         geti("-xSize", o.x); geti("-ySize", o.y); geti("-cbWidth", o.cb_width); geti("-cbHeight", o.cb_height);
@@ -224,6 +241,27 @@ bool read_frame(std::ifstream &f, size_t base, size_t frame, int w, int h, uint8
     return (size_t)f.gcount() == (size_t)w * (size_t)h;
 }
 
+// ---- -layout: the raw file's frames as they are.  Bytes a pixel, bytes a frame of the file (rows of W * bpp bytes, planar:
+// three planes), and the picsong_image of such a frame at a device address
+int layout_bpp(int layout) { return layout < PICSONG_LAYOUT_RGB24 ? 1 : (layout < PICSONG_LAYOUT_RGBA32 ? 3 : 4); }
+size_t layout_frame_bytes(int layout, int w, int h)
+{
+    return (size_t)w * (size_t)h * (size_t)layout_bpp(layout) * (layout == PICSONG_LAYOUT_PLANAR3 ? 3u : 1u);
+}
+picsong_image layout_image(int layout, void *d, int w, int h)
+{
+    picsong_image im;
+    im.data = d; im.pitch = (size_t)w * (size_t)layout_bpp(layout); im.plane_stride = (size_t)w * (size_t)h; im.layout = layout;
+    return im;
+}
+void layout_check_context(int layout, bool rgb)
+{
+    if (layout < 0) return;
+    if (rgb != (layout != PICSONG_LAYOUT_GREY8))
+        die(rgb ? "Incorrect parameters. -layout grey describes a one-component file: an RGB one is planar, rgb, bgr, rgba or bgra."
+                : "Incorrect parameters. A one-component file is -layout grey (the colour layouts need -isRGB 1 -components 3).");
+}
+
 struct Worker {
     picsong_ctx *ctx = nullptr;
     hipStream_t stream = nullptr;
@@ -231,6 +269,7 @@ struct Worker {
     uint8_t *h_in = nullptr, *d_in = nullptr;      // padded frame, pinned / device
     uint16_t *h_out = nullptr, *d_out = nullptr;   // codestream, pinned / device
     uint8_t *h_raw = nullptr;                      // unpadded frame (host)
+    uint8_t *d_raw = nullptr;                      // -layout: the unpadded frames as read, on the device
     long frame = -1;
 };
 
@@ -354,11 +393,16 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
     load_lut(ctx, o, o.wl, 3, o.k, o.cp);
     hipStream_t s;
     HIPCK(hipStreamCreate(&s));
-    uint8_t *h_in, *d_in[3];
+    uint8_t *h_in, *d_in[3], *d_raw = nullptr;
     void *d_c[3];
     uint16_t *h_out, *d_out;
-    HIPCK(hipHostMalloc(&h_in, P));
-    for (int c = 0; c < 3; c++) { HIPCK(hipMalloc(&d_in[c], P)); HIPCK(hipMalloc(&d_c[c], P * 4)); }
+    // -layout: the frame of the file as it is, pinned and on the device; the three padded planes are made there
+    const size_t raw_bytes = o.layout >= 0 ? layout_frame_bytes(o.layout, o.x, o.y) : 0;
+    HIPCK(hipHostMalloc(&h_in, raw_bytes > P ? raw_bytes : P));
+    HIPCK(hipMalloc(&d_in[0], 3 * P));
+    d_in[1] = d_in[0] + P; d_in[2] = d_in[0] + 2 * P;
+    if (o.layout >= 0) HIPCK(hipMalloc(&d_raw, raw_bytes));
+    for (int c = 0; c < 3; c++) HIPCK(hipMalloc(&d_c[c], P * 4));
     // the three components of a frame through ONE launch per stage (picsong_encode_rgb_frame) wherever the library
     // offers it: -cp 2, k = 0; otherwise plane by plane
     const bool batched = o.cp != 3;
@@ -372,7 +416,17 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
     long total_shorts = 0;
     auto t0 = std::chrono::steady_clock::now();
     for (long f = 0; f < nframes; f++) {
-        for (int c = 0; c < 3; c++) {
+        if (o.layout >= 0) {
+            in.clear();
+            in.seekg((std::streamoff)(file_base + (size_t)f * raw_bytes));
+            in.read(reinterpret_cast<char *>(h_in), (std::streamsize)raw_bytes);
+            if ((size_t)in.gcount() != raw_bytes) die("Input file is shorter than the requested frames.");
+            HIPCK(hipMemcpyAsync(d_raw, h_in, raw_bytes, hipMemcpyHostToDevice, s));
+            const picsong_image im = layout_image(o.layout, d_raw, o.x, o.y);
+            CK(picsong_ingest_frames(ctx, 1, &im, 0, d_in[0], 0, s));
+            HIPCK(hipStreamSynchronize(s));              // h_in is reused for the next frame
+        }
+        for (int c = 0; c < 3 && o.layout < 0; c++) {
             if (!read_frame(in, file_base, (size_t)(f * 3 + c), o.x, o.y, raw.data())) die("Input file is shorter than the requested frames.");
             CK(picsong_pad_frame_host(raw.data(), o.x, o.y, h_in, aw, ah));
             HIPCK(hipMemcpyAsync(d_in[c], h_in, P, hipMemcpyHostToDevice, s));
@@ -427,7 +481,9 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
     picsong_ctx_destroy(ctx);
     (void)hipStreamDestroy(s);
     (void)hipHostFree(h_in); (void)hipHostFree(h_out); (void)hipFree(d_out);
-    for (int c = 0; c < 3; c++) { (void)hipFree(d_in[c]); (void)hipFree(d_c[c]); }
+    (void)hipFree(d_in[0]);
+    if (d_raw) (void)hipFree(d_raw);
+    for (int c = 0; c < 3; c++) (void)hipFree(d_c[c]);
     return 0;
 }
 
@@ -550,6 +606,8 @@ int run_encode(Options o)
         if (o.cp == 3) die("Incorrect parameters. -psnr does not apply to -cp 3.");
         if (!o.train.empty()) die("Incorrect parameters. -psnr does not apply to -train.");
     }
+    layout_check_context(o.layout, o.is_rgb != 0);
+    if (o.layout >= 0 && !o.train.empty()) die("Incorrect parameters. -layout does not apply to -train.");
     if (!o.train.empty()) {
         if (o.k > 0) die("Incorrect parameters. -train counts the two-pass coder's decisions (-k must be 0).");
         if (o.cp == 3) die("Incorrect parameters. -train does not apply to -cp 3.");
@@ -606,6 +664,7 @@ int run_encode(Options o)
         HIPCK(hipHostMalloc(&k.h_out, max_shorts * 2 * B));
         HIPCK(hipMalloc(&k.d_out, max_shorts * 2 * B));
         k.h_raw = (uint8_t *)malloc(frame_bytes);
+        if (o.layout >= 0) HIPCK(hipMalloc(&k.d_raw, frame_bytes * (size_t)B));
         // stage timers (HIP events): at most kProfFrames launches per slot are timed, so the event count does
         // not grow with the video; "BPC acum time" scales their mean to all frames
         CK(picsong_profile_begin(k.ctx, (int)std::min<long>((ngroups + nstreams - 1) / nstreams, kProfFrames)));
@@ -632,9 +691,20 @@ int run_encode(Options o)
                 got += (size_t)m;
             }
             if (got != frame_bytes) die("Input file is shorter than the requested frames.");
-            CK(picsong_pad_frame_host(raw.data(), o.x, o.y, h_f + (size_t)f * P, aw, ah));
+            if (o.layout >= 0) memcpy(h_f + (size_t)f * frame_bytes, raw.data(), frame_bytes);
+            else CK(picsong_pad_frame_host(raw.data(), o.x, o.y, h_f + (size_t)f * P, aw, ah));
         }
-        HIPCK(hipMemcpyAsync(d_f, h_f, P * (size_t)n, hipMemcpyHostToDevice, k.stream));
+        if (o.layout >= 0) {            // the frames as read, padded on the device
+            uint8_t *d_r = nullptr;
+            HIPCK(hipMalloc(&d_r, frame_bytes * (size_t)n));
+            HIPCK(hipMemcpyAsync(d_r, h_f, frame_bytes * (size_t)n, hipMemcpyHostToDevice, k.stream));
+            const picsong_image im = layout_image(o.layout, d_r, o.x, o.y);
+            CK(picsong_ingest_frames(k.ctx, n, &im, frame_bytes, d_f, P, k.stream));
+            HIPCK(hipStreamSynchronize(k.stream));
+            (void)hipFree(d_r);
+        } else {
+            HIPCK(hipMemcpyAsync(d_f, h_f, P * (size_t)n, hipMemcpyHostToDevice, k.stream));
+        }
         int j = 0, totals[16];
         float q = 0.0f;
         if (o.has_psnr) {               // -psnr mirrors -rate: the same frames, the same contexts, the limit over all of them
@@ -695,7 +765,8 @@ int run_encode(Options o)
             std::string err;
             for (int j = 0; j < n && err.empty(); j++) {
                 const long f = g * B + j;
-                uint8_t *dst = padded_already ? k.h_in + (size_t)j * P : k.h_raw;
+                // (-layout: the frames as they are, back to back in the pinned buffer; the GPU pads them)
+                uint8_t *dst = o.layout >= 0 ? k.h_in + (size_t)j * frame_bytes : padded_already ? k.h_in + (size_t)j * P : k.h_raw;
                 size_t got = 0;
                 while (got < frame_bytes) {
                     ssize_t m = pread(fd, dst + got, frame_bytes - got, (off_t)(file_base + (size_t)f * frame_bytes + got));
@@ -703,7 +774,7 @@ int run_encode(Options o)
                     got += (size_t)m;
                 }
                 if (got != frame_bytes) err = "Input file is shorter than the requested frames.";
-                else if (!padded_already && picsong_pad_frame_host(k.h_raw, o.x, o.y, k.h_in + (size_t)j * P, aw, ah) != PICSONG_OK)
+                else if (o.layout < 0 && !padded_already && picsong_pad_frame_host(k.h_raw, o.x, o.y, k.h_in + (size_t)j * P, aw, ah) != PICSONG_OK)
                     err = picsong_last_error();
             }
             t_read[(size_t)r] += secs(tr0, now());
@@ -806,8 +877,11 @@ int run_encode(Options o)
         Worker &k = w[si];
         const int n = st[si].n;
         std::string err;
+        const picsong_image im = layout_image(o.layout, k.d_raw, o.x, o.y);
         if (hipSetDevice(k.device) != hipSuccess ||
-            hipMemcpyAsync(k.d_in, k.h_in, P * (size_t)n, hipMemcpyHostToDevice, k.stream) != hipSuccess) err = "HIP error in the frame upload";
+            (o.layout >= 0 ? hipMemcpyAsync(k.d_raw, k.h_in, frame_bytes * (size_t)n, hipMemcpyHostToDevice, k.stream)
+                           : hipMemcpyAsync(k.d_in, k.h_in, P * (size_t)n, hipMemcpyHostToDevice, k.stream)) != hipSuccess) err = "HIP error in the frame upload";
+        else if (o.layout >= 0 && picsong_ingest_frames(k.ctx, n, &im, frame_bytes, k.d_in, P, k.stream) != PICSONG_OK) err = picsong_last_error();
         else if (o.has_rate && !o.video) {
             // an image: one rate call (synchronous); its length is the context's last total, as after picsong_encode_frame
             int j = 0, total = 0;
@@ -875,6 +949,7 @@ int run_encode(Options o)
         picsong_ctx_destroy(k.ctx);
         (void)hipStreamDestroy(k.stream);
         (void)hipHostFree(k.h_in); (void)hipFree(k.d_in); (void)hipHostFree(k.h_out); (void)hipFree(k.d_out);
+        if (k.d_raw) (void)hipFree(k.d_raw);
         free(k.h_raw);
     }
     return 0;
@@ -921,8 +996,14 @@ int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, 
     const bool batched = p.cp != 3;      // (picsong_decode_rgb_frame: one launch per stage for the three components)
     HIPCK(hipHostMalloc(&h_in, max_shorts * 2));
     HIPCK(hipMalloc(&d_in, max_shorts * 2 * (batched ? 3 : 1)));
-    HIPCK(hipHostMalloc(&h_pix, P));
-    for (int c = 0; c < 3; c++) { HIPCK(hipMalloc(&d_pix[c], P)); HIPCK(hipMalloc(&d_plane[c], (P + extra) * 4)); }
+    // -layout: the three padded planes are cropped and interleaved on the device, the frame comes back as the file takes it
+    const size_t raw_bytes = o.layout >= 0 ? layout_frame_bytes(o.layout, p.width, p.height) : 0;
+    uint8_t *d_emit = nullptr;
+    HIPCK(hipHostMalloc(&h_pix, raw_bytes > P ? raw_bytes : P));
+    HIPCK(hipMalloc(&d_pix[0], 3 * P));
+    d_pix[1] = d_pix[0] + P; d_pix[2] = d_pix[0] + 2 * P;
+    if (o.layout >= 0) HIPCK(hipMalloc(&d_emit, raw_bytes));
+    for (int c = 0; c < 3; c++) HIPCK(hipMalloc(&d_plane[c], (P + extra) * 4));
     std::vector<uint8_t> crop((size_t)od.w * od.h);
     { std::ofstream trunc(o.output, std::ios::binary | std::ios::trunc); }
     auto t0 = std::chrono::steady_clock::now();
@@ -951,7 +1032,14 @@ int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, 
             CK(picsong_rgb_inverse(ctx, d_plane[0] + extra * 4, d_plane[1] + extra * 4, d_plane[2] + extra * 4, d_pix[0],
                                    d_pix[1], d_pix[2], s));
         std::ofstream out(o.output, std::ios::binary | std::ios::app);
-        for (int c = 0; c < 3; c++) {
+        if (o.layout >= 0) {
+            const picsong_image im = layout_image(o.layout, d_emit, p.width, p.height);
+            CK(picsong_emit_frames(ctx, 1, d_pix[0], 0, &im, 0, s));
+            HIPCK(hipMemcpyAsync(h_pix, d_emit, raw_bytes, hipMemcpyDeviceToHost, s));
+            HIPCK(hipStreamSynchronize(s));
+            out.write(reinterpret_cast<const char *>(h_pix), (std::streamsize)raw_bytes);
+        }
+        for (int c = 0; c < 3 && o.layout < 0; c++) {
             HIPCK(hipMemcpyAsync(h_pix, d_pix[c], (size_t)od.pw * od.ph, hipMemcpyDeviceToHost, s));
             HIPCK(hipStreamSynchronize(s));
             for (int y = 0; y < od.h; y++) memcpy(&crop[(size_t)y * od.w], h_pix + (size_t)y * od.pw, (size_t)od.w);
@@ -963,7 +1051,9 @@ int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, 
     picsong_ctx_destroy(ctx);
     (void)hipStreamDestroy(s);
     (void)hipHostFree(h_in); (void)hipFree(d_in); (void)hipHostFree(h_pix);
-    for (int c = 0; c < 3; c++) { (void)hipFree(d_pix[c]); (void)hipFree(d_plane[c]); }
+    (void)hipFree(d_pix[0]);
+    if (d_emit) (void)hipFree(d_emit);
+    for (int c = 0; c < 3; c++) (void)hipFree(d_plane[c]);
     return 0;
 }
 
@@ -991,6 +1081,7 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
     struct Slot {
         picsong_ctx *ctx = nullptr; hipStream_t stream = nullptr;
         uint16_t *h_in = nullptr, *d_in = nullptr; uint8_t *h_pix = nullptr, *d_pix = nullptr;
+        uint8_t *d_emit = nullptr;                       // -layout: the frames cropped on the device, frame_bytes apart
         std::vector<uint8_t> crop;
         int state = 0; long expect = 0;
     };
@@ -1005,7 +1096,8 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
         HIPCK(hipMalloc(&k.d_in, max_shorts * 2 * B));
         HIPCK(hipHostMalloc(&k.h_pix, P * B));
         HIPCK(hipMalloc(&k.d_pix, P * B));
-        if (od.pw != od.w) k.crop.resize(frame_bytes);
+        if (o.layout >= 0) HIPCK(hipMalloc(&k.d_emit, frame_bytes * (size_t)B));
+        else if (od.pw != od.w) k.crop.resize(frame_bytes);
         k.expect = i;
     }
     std::vector<size_t> in_off((size_t)nframes + 1, 0);
@@ -1061,8 +1153,8 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
             std::string err;
             if (hipStreamSynchronize(k.stream) != hipSuccess) err = "HIP error while decoding a frame";
             for (long f = g * B; err.empty() && f < nframes && f < (g + 1) * B; f++) {
-                const uint8_t *pix = k.h_pix + (size_t)(f - g * B) * P, *src = pix;
-                if (od.pw != od.w) {
+                const uint8_t *pix = k.h_pix + (size_t)(f - g * B) * (o.layout >= 0 ? frame_bytes : P), *src = pix;
+                if (o.layout < 0 && od.pw != od.w) {
                     for (int y = 0; y < od.h; y++) memcpy(&k.crop[(size_t)y * od.w], pix + (size_t)y * od.pw, (size_t)od.w);
                     src = k.crop.data();
                 }
@@ -1107,6 +1199,12 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
                   : od.r > 0 ? picsong_decode_frames_reduced(k.ctx, n, k.d_in, max_shorts, od.r, k.d_pix, P, k.stream)
                              : picsong_decode_frames(k.ctx, n, k.d_in, max_shorts, k.d_pix, P, k.stream)) != PICSONG_OK)
             err = picsong_last_error();
+        else if (o.layout >= 0) {
+            const picsong_image im = layout_image(o.layout, k.d_emit, od.w, od.h);
+            if (picsong_emit_frames(k.ctx, n, k.d_pix, P, &im, frame_bytes, k.stream) != PICSONG_OK) err = picsong_last_error();
+            else if (hipMemcpyAsync(k.h_pix, k.d_emit, frame_bytes * (size_t)n, hipMemcpyDeviceToHost, k.stream) != hipSuccess)
+                err = "HIP error in the frame download";
+        }
         else if (hipMemcpyAsync(k.h_pix, k.d_pix, P * (size_t)n, hipMemcpyDeviceToHost, k.stream) != hipSuccess)
             err = "HIP error in the frame download";
         std::lock_guard<std::mutex> lk(mu);
@@ -1127,6 +1225,7 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
         picsong_ctx_destroy(k.ctx);
         (void)hipStreamDestroy(k.stream);
         (void)hipHostFree(k.h_in); (void)hipFree(k.d_in); (void)hipHostFree(k.h_pix); (void)hipFree(k.d_pix);
+        if (k.d_emit) (void)hipFree(k.d_emit);
     }
     return 0;
 }
@@ -1143,6 +1242,7 @@ int run_decode(const Options &o)
     CK(picsong_header_unpack(hdr, &p));
     if (!((p.components == 1 && !p.is_rgb) || (p.components == 3 && p.is_rgb)))
         die("This stream uses a component layout not built here.");
+    layout_check_context(o.layout, p.is_rgb != 0);
     if (o.reduce < 0 || o.reduce > p.wl - 1)
         die("Incorrect parameters. -reduce must lie in 0.." + std::to_string(p.wl - 1) + " (the stream has " +
             std::to_string(p.wl) + " wavelet levels).");
@@ -1193,6 +1293,8 @@ int run_decode(const Options &o)
     HIPCK(hipMalloc(&d_in, max_shorts * 2));
     HIPCK(hipHostMalloc(&h_pix, P));
     HIPCK(hipMalloc(&d_pix, P));
+    uint8_t *d_emit = nullptr;                           // -layout grey: the frame cropped on the device
+    if (o.layout >= 0) HIPCK(hipMalloc(&d_emit, (size_t)od.w * od.h));
     std::vector<uint8_t> crop((size_t)od.w * od.h);
     if (o.video) { std::ofstream trunc(o.output, std::ios::binary | std::ios::app); }
     auto t0 = std::chrono::steady_clock::now();
@@ -1209,9 +1311,16 @@ int run_decode(const Options &o)
         if (od.win) CK(picsong_decode_frame_window(ctx, d_in, od.r, od.x, od.y, od.w, od.h, d_pix, (size_t)od.pw, s));
         else if (od.r > 0) CK(picsong_decode_frame_reduced(ctx, d_in, od.r, d_pix, s));
         else CK(picsong_decode_frame(ctx, d_in, d_pix, s));
+        if (o.layout >= 0) {
+            const picsong_image im = layout_image(o.layout, d_emit, od.w, od.h);
+            CK(picsong_emit_frames(ctx, 1, d_pix, 0, &im, 0, s));
+            HIPCK(hipMemcpyAsync(crop.data(), d_emit, crop.size(), hipMemcpyDeviceToHost, s));
+            HIPCK(hipStreamSynchronize(s));
+        } else {
         HIPCK(hipMemcpyAsync(h_pix, d_pix, P, hipMemcpyDeviceToHost, s));
         HIPCK(hipStreamSynchronize(s));
         for (int y = 0; y < od.h; y++) memcpy(&crop[(size_t)y * od.w], h_pix + (size_t)y * od.pw, (size_t)od.w);
+        }
         if (o.video) {
             // IOManager::writeDecodedFrame IO/IOManager.ipp:214-231: raw W*H bytes appended
             std::ofstream out(o.output, std::ios::binary | std::ios::app);
@@ -1228,6 +1337,7 @@ int run_decode(const Options &o)
     picsong_ctx_destroy(ctx);
     (void)hipStreamDestroy(s);
     (void)hipHostFree(h_in); (void)hipFree(d_in); (void)hipHostFree(h_pix); (void)hipFree(d_pix);
+    if (d_emit) (void)hipFree(d_emit);
     return 0;
 }
 

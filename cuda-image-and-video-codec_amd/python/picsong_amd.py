@@ -24,6 +24,15 @@ class Params(C.Structure):
                 ("components", C.c_int), ("is_rgb", C.c_int)]
 
 
+class Image(C.Structure):
+    """picsong_image: W x H pixels (the context's) on the device at a byte pitch, in one of the LAYOUT_* layouts."""
+    _fields_ = [("data", C.c_void_p), ("pitch", C.c_size_t), ("plane_stride", C.c_size_t), ("layout", C.c_int)]
+
+
+LAYOUT_GREY8, LAYOUT_PLANAR3, LAYOUT_RGB24, LAYOUT_BGR24, LAYOUT_RGBA32, LAYOUT_BGRA32 = range(6)
+LAYOUT_BPP = (1, 1, 3, 3, 4, 4)
+
+
 class LutInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n_bitplanes", "n_subbands", "ctx_ref", "ctx_sign", "ctx_sig",
                                        "precision", "n_files", "n_bp_files", "n_ref", "n_sig", "n_sign",
@@ -57,6 +66,8 @@ EXPORTS = [
     "picsong_encode_rgb_frame_rate",
     "picsong_psnr_to_sse", "picsong_sse_to_psnr", "picsong_frames_sse", "picsong_encode_frame_quality",
     "picsong_encode_frames_quality", "picsong_encode_rgb_frame_quality",
+    "picsong_ingest_frames", "picsong_emit_frames", "picsong_encode_images", "picsong_decode_images",
+    "picsong_encode_rgb_image", "picsong_decode_rgb_image",
 ]
 
 _lib = None
@@ -173,6 +184,14 @@ def load():
                                                     C.POINTER(i), C.POINTER(i), C.POINTER(u64)]
         L.picsong_encode_rgb_frame_quality.argtypes = [vp, vp, vp, vp, i, u64, i, i, vp, C.c_size_t, vp,
                                                        C.POINTER(i), C.POINTER(i), C.POINTER(u64)]
+    if hasattr(L, "picsong_ingest_frames"):
+        img = C.POINTER(Image)
+        L.picsong_ingest_frames.argtypes = [vp, i, img, C.c_size_t, vp, C.c_size_t, vp]
+        L.picsong_emit_frames.argtypes = [vp, i, vp, C.c_size_t, img, C.c_size_t, vp]
+        L.picsong_encode_images.argtypes = [vp, i, img, C.c_size_t, i, vp, C.c_size_t, vp]
+        L.picsong_decode_images.argtypes = [vp, i, vp, C.c_size_t, img, C.c_size_t, vp]
+        L.picsong_encode_rgb_image.argtypes = [vp, img, i, vp, C.c_size_t, vp]
+        L.picsong_decode_rgb_image.argtypes = [vp, vp, C.c_size_t, img, vp]
     _lib = L
     return L
 
@@ -355,6 +374,53 @@ class Codec:
         table = np.ascontiguousarray(table, np.int32)
         _check(self.L.picsong_ctx_set_lut_component(self.h, component, C.byref(info),
                                                     table.ctypes.data_as(C.c_void_p)))
+
+    # ---- frames as applications hold them: pitched, unpadded, interleaved RGB(A) (picsong_image) ----
+    def image(self, t, layout, pitch=None, plane_stride=0, offset=0):
+        """The picsong_image of the uint8 CUDA tensor `t` (any shape; its storage from byte `offset` on is the frame):
+        rows `pitch` bytes apart (default: packed, W * bpp), PLANAR3 planes plane_stride bytes apart."""
+        assert t.dtype == self.torch.uint8 and t.is_cuda
+        pitch = self.params.width * LAYOUT_BPP[layout] if pitch is None else pitch
+        return Image(data=t.data_ptr() + offset, pitch=pitch, plane_stride=plane_stride, layout=layout)
+
+    def ingest_frames(self, img, n=1, frame_stride=0, out=None):
+        """n frames of `img` (an Image; frame f frame_stride bytes behind frame 0) to padded planar planes on the device:
+        uint8 [n, planes, AH, AW] (planes: 1 for GREY8, else R, G, B), mirror-padded as picsong_pad_frame_host pads."""
+        planes = 1 if img.layout == LAYOUT_GREY8 else 3
+        if out is None:
+            out = self.torch.empty((n, planes, self.ah, self.aw), dtype=self.torch.uint8, device=self.dev)
+        _check(self.L.picsong_ingest_frames(self.h, n, C.byref(img), frame_stride, self._p(out), out.stride(0), self._stream()))
+        return out
+
+    def emit_frames(self, padded, img, n=1, frame_stride=0):
+        """The inverse: uint8 [n, planes, AH, AW] padded planes cropped and interleaved into the frames of `img`."""
+        assert padded.stride(-1) == 1
+        _check(self.L.picsong_emit_frames(self.h, n, self._p(padded), padded.stride(0) if padded.dim() == 4 else 0, C.byref(img),
+                                          frame_stride, self._stream()))
+
+    def encode_images(self, img, n=1, frame_stride=0, first_iter=0):
+        """n grey frames of `img` ingested on the device and coded as encode_frames codes host-padded ones."""
+        out = self.torch.empty((n, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        _check(self.L.picsong_encode_images(self.h, n, C.byref(img), frame_stride, first_iter, self._p(out), out.stride(0),
+                                            self._stream()))
+        return [out[k, :t] for k, t in enumerate(self.last_totals(n))]
+
+    def decode_images(self, streams, img, frame_stride=0):
+        """streams: int16 [n, >= max_stream_shorts()]; the W x H frames land in `img` (frame f frame_stride bytes on)."""
+        assert streams.stride(-1) == 1
+        _check(self.L.picsong_decode_images(self.h, streams.shape[0], self._p(streams), streams.stride(0), C.byref(img), frame_stride,
+                                            self._stream()))
+
+    def encode_rgb_image(self, img, header_mask=1):
+        """One RGB frame of `img` (any colour layout) as encode_rgb_frame codes its host-padded planes."""
+        out = self.torch.empty((3, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        _check(self.L.picsong_encode_rgb_image(self.h, C.byref(img), header_mask, self._p(out), out.stride(0), self._stream()))
+        totals = self.last_totals(3)
+        return [out[k, :totals[k]] for k in range(3)]
+
+    def decode_rgb_image(self, streams, img):
+        """streams: int16 [3, >= max_stream_shorts()]; the W x H pixels land in `img`, alpha (if any) 255."""
+        _check(self.L.picsong_decode_rgb_image(self.h, self._p(streams), streams.stride(0), C.byref(img), self._stream()))
 
     # ---- rate control: the 9/7 encode calls with qs chosen to meet a size (synchronous) ----
     def set_qs(self, qs):

@@ -189,7 +189,8 @@ int picsong_last_total(picsong_ctx *ctx, void *stream, int *h_total);
 /* ---- whole frame: the grey call sequences of CodingEngine::runImage/runVideo
  *      (Engines/CodingEngine.cu:634-674,819-872) and DecodingEngine::runImage
  *      (Engines/DecodingEngine.cu:770-794).  d_frame: padded u8[AW*AH] (caller pads as
- *      IOManager::loadFrameCAdaptedSizes does, or uses picsong_pad_frame_host).  iter == 0
+ *      IOManager::loadFrameCAdaptedSizes does, uses picsong_pad_frame_host, or has picsong_ingest_frames make it on
+ *      the device from the unpadded frame; picsong_encode_images takes that frame directly).  iter == 0
  *      writes the populated header.  Asynchronous; length via picsong_last_total().
  *      picsong_decode_frame reads the stream's own shorts and nothing beyond them (-cp 2: the coder
  *      takes its codewords from d_stream itself; -cp 3 through the staging, as
@@ -464,6 +465,58 @@ int picsong_encode_frames_quality(picsong_ctx *ctx, int n, const uint8_t *d_fram
 int picsong_encode_rgb_frame_quality(picsong_ctx *ctx, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
                                      uint64_t max_sse, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
                                      void *stream, int *h_j, int *h_totals, uint64_t *h_sse);
+
+/* ---- frames as applications hold them (the reference reads files only, IO/IOManager.ipp:72-112; nvJPEG2000 and
+ *      friends take a pitched image descriptor): W x H pixels (the context's unpadded -xSize / -ySize) at a byte pitch,
+ *      one byte a pixel or interleaved RGB(A), converted ON THE DEVICE to and from the padded planar u8 planes every
+ *      other call takes -- no host pad, no caller-written kernels.
+ *      picsong_image: `data` is the DEVICE address of the first pixel, row y at data + y * pitch (pitch >= W * bpp, any
+ *      value: rows need not be packed).  PLANAR3: the R, G, B planes plane_stride bytes apart (plane_stride is ignored
+ *      by the other layouts).  Frame f of a call at data + f * frame_stride.
+ *      The padded side: `planes` planes of P = AW * AH bytes back to back per frame (1 for GREY8, 3 -- R, G, B -- for
+ *      every other layout), row stride AW, frames padded_stride bytes apart.
+ *      picsong_ingest_frames pads with the mirror rule of picsong_pad_frame_host (column W + j = column W - 1 - j,
+ *      padded row H + r = padded row H - 1 - r) and de-interleaves in the same pass; the alpha byte is ignored.  It
+ *      reads no byte outside [y * pitch, y * pitch + W * bpp) of rows 0 .. H - 1.  picsong_emit_frames crops and
+ *      interleaves; alpha is written as 255; it writes no byte outside those ranges (not the pitch gap, not past the last
+ *      row).  Both are ASYNCHRONOUS on `stream`, take any context (only its geometry is used) and n = 1..64 frames.
+ *      Alignment: none required.  An image side whose pointer, pitch and strides are 4-byte aligned with a padded side
+ *      whose pointer and stride are 16-byte aligned takes the vector kernels (dword / dwordx4 accesses; an RGB24 group of
+ *      four pixels is three dwords repacked with byte permutes); anything else the per-byte kernels: same bytes, slower.
+ *      After an ingest every existing call composes unchanged on the padded planes: picsong_encode_frame(s), the rate,
+ *      quality and training calls, the stripes; an emit takes what any decode call wrote at full size.
+ *      Whole-frame calls: ingest into a 16-byte aligned buffer the context grows (so the vector kernels run whenever
+ *      the image side allows), then the plain frame sequence -- and the mirror for decoding.
+ *        picsong_encode_images (grey contexts, n = 1..64): byte-identical to picsong_encode_frames on host-padded frames.
+ *        picsong_encode_rgb_image (RGB contexts, one frame): byte-identical to picsong_encode_rgb_frame.
+ *        picsong_decode_images / picsong_decode_rgb_image: the W x H crop of picsong_decode_frames' /
+ *        picsong_decode_rgb_frame's output, in the layout of `dst`.
+ *      Lengths are reported where the plain calls leave them (picsong_last_totals / picsong_copy_last_totals); -cp 3 is
+ *      accepted wherever the underlying plain call accepts it (none of these four does).
+ *      Refused (PICSONG_ERR_ARG, nothing launched, outputs untouched): null pointers; an unknown layout; pitch < W * bpp;
+ *      plane_stride (PLANAR3) below (H - 1) * pitch + W; with n > 1 a frame_stride below the bytes a frame spans or a
+ *      padded_stride below planes * P; n outside 1..64; AW - W > W or AH - H > H (the rule picsong_pad_frame_host
+ *      refuses); in the whole-frame calls also a colour layout on a grey context, GREY8 on an RGB one, and what the
+ *      plain call refuses (stream strides, -cp 3). ---- */
+#define PICSONG_LAYOUT_GREY8   0   /* 1 byte a pixel; grey contexts */
+#define PICSONG_LAYOUT_PLANAR3 1   /* R, G, B planes plane_stride bytes apart, each at `pitch` */
+#define PICSONG_LAYOUT_RGB24   2
+#define PICSONG_LAYOUT_BGR24   3
+#define PICSONG_LAYOUT_RGBA32  4   /* A ignored on input, 255 on output */
+#define PICSONG_LAYOUT_BGRA32  5
+typedef struct picsong_image { void *data; size_t pitch; size_t plane_stride; int layout; } picsong_image;
+int picsong_ingest_frames(picsong_ctx *ctx, int n, const picsong_image *src, size_t frame_stride, uint8_t *d_padded,
+                          size_t padded_stride, void *stream);
+int picsong_emit_frames(picsong_ctx *ctx, int n, const uint8_t *d_padded, size_t padded_stride, const picsong_image *dst,
+                        size_t frame_stride, void *stream);
+int picsong_encode_images(picsong_ctx *ctx, int n, const picsong_image *src, size_t frame_stride, int first_iter,
+                          uint16_t *d_streams, size_t stream_stride, void *stream);
+int picsong_decode_images(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride, const picsong_image *dst,
+                          size_t frame_stride, void *stream);
+int picsong_encode_rgb_image(picsong_ctx *ctx, const picsong_image *src, int header_mask, uint16_t *d_streams,
+                             size_t stream_stride, void *stream);
+int picsong_decode_rgb_image(picsong_ctx *ctx, const uint16_t *d_streams, size_t stream_stride, const picsong_image *dst,
+                             void *stream);
 
 /* ---- intra-frame sharding (BASELINE config 5): codeblocks are independent
  *      (correctCBBorders zeroes outside neighbours, BPC/BPCEngine.cu:465-484), so a rank can code
