@@ -1444,14 +1444,21 @@ int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *
 }
 
 // ---------------------------------------------------------------------------------------------
-// rate calls: encode to a target size (rate_search.hpp: the grid and the procedure; rate_kernels.hpp: the quantise pass)
-//   1. the UNQUANTISED transform of the n frames (plan_dwt_forward_unit), once, into float Mallat arrays;
-//   2. per round of the search: quantise_kernel writes the coefficients of the round's K candidates as K * n "frames" of
-//      the batch buffers, ONE batched coder launch codes them, the size scan totals them, ONE read-back through pinned
-//      memory brings the K * n totals to the stepper -- no pack;
-//   3. the winner is packed (from the last round's staging when it was coded there, else after one more quantise + coder
-//      launch of it alone) with a header whose qs field is the result.
-// PICSONG_RATE_K=1 keeps one candidate a round (the measurements of tools/rate_bench.py compare both).
+// rate calls (encode to a target size) and quality calls (encode to a target distortion): ONE driver, search_impl, over
+// rate_search.hpp's grid and walk (bisect_walk); rate_kernels.hpp: the quantise pass; quality_kernels.hpp: sse_kernel;
+// launch_seq.hpp: frames_sse and quality_probe, the sequences the emulator driver of the tests runs too
+//   1. the UNQUANTISED (unit-step) transform of the n frames (plan_dwt_forward_unit), once, into float Mallat arrays
+//      (rate_transform);
+//   2. per round of the search, the round's K candidates are measured and ONE read-back through pinned memory brings
+//      their figures to the stepper:
+//      size:    quantise_kernel writes the candidates' coefficients as K * n "frames" of the batch buffers, ONE batched
+//               coder launch codes them, the size scan totals them -- no pack (rate_probe);
+//      quality: quality_probe for each candidate, back to back over ONE set of nf-frame buffers (batch.coef_i,
+//               batch.coef, q_pix), candidate i's sums in slots i * nf .. of d_sse.  No coder launch;
+//   3. the winner is packed with a header whose qs field is the result (rate_finish): a size search packs it from the
+//      last round's staging when it was coded there, else, as a quality search always, after one more quantise + coder
+//      launch of it alone (rate_probe).
+// PICSONG_RATE_K=1 keeps one candidate a round in both kinds (the measurements of tools/rate_bench.py compare both).
 // ---------------------------------------------------------------------------------------------
 struct RateJob {
     int n;                                  // frames (RGB: 1 frame, three components)
@@ -1462,10 +1469,13 @@ struct RateJob {
     bool single;                            // picsong_encode_frame_rate: the length also where picsong_encode_frame leaves it
 };
 
-static int rate_candidates(const picsong_ctx *c)
+enum SearchKind { kSearchSize, kSearchQuality };
+
+static int search_candidates(const picsong_ctx *c, SearchKind kind)
 {
-    // an RGB frame's coder launch maps frame f to table f for its three components only: one candidate a round
-    if (c->p.is_rgb) return 1;
+    // an RGB frame's coder launch maps frame f to table f for its three components only: a size search codes one
+    // candidate a round there (a quality search's probes launch no coder)
+    if (kind == kSearchSize && c->p.is_rgb) return 1;
     if (const char *e = getenv("PICSONG_RATE_K")) if (atoi(e) == 1) return 1;
     return kRateMaxK;
 }
@@ -1551,109 +1561,7 @@ static int rate_finish(picsong_ctx *c, const RateJob &job, int nf, int j, int sl
     return PICSONG_OK;
 }
 
-static int rate_impl(picsong_ctx *c, const RateJob &job, size_t target_shorts, int j_min, int j_max, hipStream_t s, int *h_j,
-                     int *h_totals, const char *who)
-{
-    // (the callers have made the null, context-kind, stride and alignment checks)
-    if (!c->p.lossy) return fail(PICSONG_ERR_ARG, "%s: a lossless context has no quantiser to search", who);
-    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 3 contexts have no rate control", who);
-    if (target_shorts == 0) return fail(PICSONG_ERR_ARG, "%s: target_shorts must be positive", who);
-    if (!rate_range_ok(j_min, j_max))
-        return fail(PICSONG_ERR_ARG, "%s: range [%d, %d] is neither 0, 0 (the whole grid) nor inside 1..%d", who, j_min, j_max, kRateJMax);
-    const std::vector<int> grid = rate_grid(j_min, j_max);
-    if (grid.empty()) return fail(PICSONG_ERR_ARG, "%s: no header-exact quantiser in [%d, %d]", who, j_min, j_max);
-    HIP_TRY(hipSetDevice(c->device));
-    const bool rgb = c->p.is_rgb != 0;
-    const int nf = rgb ? 3 : job.n, K = rate_candidates(c);
-    BpcArgs a;
-    int rc = rgb ? bpc_args_rgb(c, a) : bpc_args(c, a, 0);
-    if (rc) return rc;
-    if ((rc = ensure_batch(c, K * nf))) return rc;
-    if (rgb && (rc = ensure_coef_i(c, 3))) return rc;
-    if ((rc = ensure_rate(c, nf))) return rc;
-    c->last_batch = -1;                                     // (until the result is packed: no totals to hand out)
-    if ((rc = rate_transform(c, job, s))) return rc;
-
-    const long long target = target_shorts > (size_t)1 << 62 ? (long long)1 << 62 : (long long)target_shorts;
-    RateStepper st((int)grid.size(), target, K);
-    int idx[kRateMaxK], js[kRateMaxK], m = 0, last_js[kRateMaxK] = { 0, 0, 0 }, last_m = 0;
-    while ((m = st.next(idx)) > 0) {
-        for (int i = 0; i < m; i++) js[i] = grid[(size_t)idx[i]];
-        if ((rc = rate_probe(c, a, nf, m, js, s))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->h_totals, c->batch.total, (size_t)(m * nf) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        long long sizes[kRateMaxK] = { 0, 0, 0 };
-        for (int i = 0; i < m; i++)
-            for (int f = 0; f < nf; f++) sizes[i] += c->h_totals[i * nf + f];
-        st.take(sizes);
-        for (int i = 0; i < m; i++) last_js[i] = js[i];
-        last_m = m;
-    }
-    *h_j = 0;
-    if (st.result() < 0)
-        return fail(PICSONG_ERR_RATE, "%s: no quantiser of the search range meets %zu shorts", who, target_shorts);
-    const int j = grid[(size_t)st.result()];
-    // ---- the winner's staging: candidate `slot` of the last round, or coded once more on its own
-    int slot = -1;
-    for (int i = 0; i < last_m; i++) if (last_js[i] == j) slot = i;
-    if (slot < 0) {
-        if ((rc = rate_probe(c, a, nf, 1, &j, s))) return rc;
-        slot = 0;
-    }
-    if ((rc = rate_finish(c, job, nf, j, slot, s, h_totals))) return rc;
-    *h_j = j;
-    return PICSONG_OK;
-}
-
-int picsong_encode_frames_rate(picsong_ctx *c, int n, const uint8_t *d_frames, size_t frame_stride, int first_iter,
-                               size_t target_shorts, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
-                               void *stream, int *h_j, int *h_totals)
-{
-    const char *who = "encode_frames_rate";
-    if (!c || !d_frames || !d_streams || !h_j || !h_totals) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
-    if (n < 1 || n > 16) return fail(PICSONG_ERR_ARG, "%s: %d frames outside 1..16", who, n);
-    if (c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: grey contexts only (an RGB frame: picsong_encode_rgb_frame_rate)", who);
-    if (n > 1 && (frame_stride < c->P || stream_stride < picsong_max_stream_shorts(c->aw, c->ah)))
-        return fail(PICSONG_ERR_ARG, "%s: strides smaller than a padded frame / a worst-case codestream", who);
-    if (((uintptr_t)d_frames | frame_stride) & 15u) return fail(PICSONG_ERR_ARG, "%s: frames must be 16-byte aligned", who);
-    const RateJob job = { n, d_frames, frame_stride, nullptr, nullptr, nullptr, first_iter, 0, d_streams, stream_stride, false };
-    return rate_impl(c, job, target_shorts, j_min, j_max, (hipStream_t)stream, h_j, h_totals, who);
-}
-
-int picsong_encode_frame_rate(picsong_ctx *c, const uint8_t *d_frame, int iter, size_t target_shorts, int j_min, int j_max,
-                              uint16_t *d_stream, void *stream, int *h_j, int *h_total)
-{
-    const char *who = "encode_frame_rate";
-    if (!c || !d_frame || !d_stream || !h_j || !h_total) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
-    if (c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: grey contexts only (an RGB frame: picsong_encode_rgb_frame_rate)", who);
-    // (any alignment, as picsong_encode_frame: an unaligned frame takes the per-column transform kernels)
-    const RateJob job = { 1, d_frame, 0, nullptr, nullptr, nullptr, iter == 0 ? 0 : 1, 0, d_stream, 0, true };
-    return rate_impl(c, job, target_shorts, j_min, j_max, (hipStream_t)stream, h_j, h_total, who);
-}
-
-int picsong_encode_rgb_frame_rate(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
-                                  size_t target_shorts, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
-                                  void *stream, int *h_j, int *h_totals)
-{
-    const char *who = "encode_rgb_frame_rate";
-    if (!c || !d_r || !d_g || !d_b || !d_streams || !h_j || !h_totals) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
-    if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: the context is not an RGB one", who);
-    if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah)) return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
-    if ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 3u) return fail(PICSONG_ERR_ARG, "%s: the planes need 4-byte alignment", who);
-    const RateJob job = { 1, nullptr, 0, d_r, d_g, d_b, 0, header_mask, d_streams, stream_stride, false };
-    return rate_impl(c, job, target_shorts, j_min, j_max, (hipStream_t)stream, h_j, h_totals, who);
-}
-
-// ---------------------------------------------------------------------------------------------
-// quality calls: encode to a target distortion (rate_search.hpp: QualityStepper; quality_kernels.hpp: sse_kernel;
-// launch_seq.hpp: frames_sse and quality_probe, the sequences the emulator driver of the tests runs too)
-//   1. the unit-step transform, once (rate_transform);
-//   2. per round: quality_probe for each of the round's candidates, back to back over ONE set of nf-frame buffers
-//      (batch.coef_i, batch.coef, q_pix), candidate i's sums in slots i * nf .. of d_sse; ONE read-back through pinned
-//      memory.  No coder launch;
-//   3. the result is quantised, coded and packed as the rate calls' final step (rate_probe of it alone, rate_finish).
-// PICSONG_RATE_K=1 keeps one candidate a round here too.
-// ---------------------------------------------------------------------------------------------
+// ---- the quality calls' conversions, picsong_frames_sse and probe buffers
 constexpr int kQualitySlots = kRateMaxK * 16;
 
 int picsong_psnr_to_sse(double psnr_db, uint64_t samples, uint64_t *max_sse)
@@ -1699,39 +1607,49 @@ static int ensure_quality(picsong_ctx *c, int frames)
     return PICSONG_OK;
 }
 
-static int quality_impl(picsong_ctx *c, const RateJob &job, uint64_t max_sse, int j_min, int j_max, hipStream_t s, int *h_j,
-                        int *h_totals, uint64_t *h_sse, const char *who)
+static int search_impl(picsong_ctx *c, const RateJob &job, SearchKind kind, uint64_t limit, int j_min, int j_max, hipStream_t s,
+                       int *h_j, int *h_totals, uint64_t *h_sse, const char *who)
 {
-    // (the callers have made the null, context-kind, stride and alignment checks)
+    // (search_args_ok has made the null, context-kind, stride and alignment checks)
+    const bool size = kind == kSearchSize;
     if (!c->p.lossy) return fail(PICSONG_ERR_ARG, "%s: a lossless context has no quantiser to search", who);
-    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 3 contexts have no quality control", who);
+    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 3 contexts have no %s control", who, size ? "rate" : "quality");
+    if (size && limit == 0) return fail(PICSONG_ERR_ARG, "%s: target_shorts must be positive", who);
     if (!rate_range_ok(j_min, j_max))
         return fail(PICSONG_ERR_ARG, "%s: range [%d, %d] is neither 0, 0 (the whole grid) nor inside 1..%d", who, j_min, j_max, kRateJMax);
     const std::vector<int> grid = rate_grid(j_min, j_max);
     if (grid.empty()) return fail(PICSONG_ERR_ARG, "%s: no header-exact quantiser in [%d, %d]", who, j_min, j_max);
     HIP_TRY(hipSetDevice(c->device));
     const bool rgb = c->p.is_rgb != 0;
-    const int nf = rgb ? 3 : job.n;
-    int K = kRateMaxK;
-    if (const char *e = getenv("PICSONG_RATE_K")) if (atoi(e) == 1) K = 1;
+    const int nf = rgb ? 3 : job.n, K = search_candidates(c, kind);
     BpcArgs a;
-    int rc = rgb ? bpc_args_rgb(c, a) : bpc_args(c, a, 0);   // (the final encode's table: refused before anything is launched)
+    int rc = rgb ? bpc_args_rgb(c, a) : bpc_args(c, a, 0);   // (the encodes' table: refused before anything is launched)
     if (rc) return rc;
-    if ((rc = ensure_batch(c, nf))) return rc;
-    if ((rc = ensure_coef_i(c, nf))) return rc;
+    // (a size round codes K candidates; a quality round measures them one after the other over nf-frame buffers)
+    if ((rc = ensure_batch(c, size ? K * nf : nf))) return rc;
+    if ((rgb || !size) && (rc = ensure_coef_i(c, nf))) return rc;
     if ((rc = ensure_rate(c, nf))) return rc;
-    if ((rc = ensure_quality(c, nf))) return rc;
+    if (!size && (rc = ensure_quality(c, nf))) return rc;
     c->last_batch = -1;                                     // (until the result is packed: no totals to hand out)
     if ((rc = rate_transform(c, job, s))) return rc;
 
-    const QualityProbe probe = { c->rate_coef, (unsigned long long)c->rate_z, c->batch.coef_i, c->batch.coef, c->q_pix,
-                                 c->aw, c->ah, c->p.wl, c->p.width, c->p.height, level_off(c), c->P, c->extra, nf,
-                                 job.frames, job.frame_stride, job.r, job.g, job.b };
-    QualityStepper st((int)grid.size(), (unsigned long long)max_sse, K);
-    std::vector<int> seen_j;                                // every probe made, with its per-array sums
-    std::vector<unsigned long long> seen_sse;
-    int idx[kRateMaxK], m = 0;
-    while ((m = st.next(idx)) > 0) {
+    // A round's measure: the launches of its m candidates, ONE read-back, ONE synchronise; values[i] = candidate i's total.
+    // Size: one launch sequence codes all m (rate_probe).
+    auto measure_size = [&](int m, const int *js, uint64_t *values) -> int {
+        if (int e = rate_probe(c, a, nf, m, js, s)) return e;
+        HIP_TRY(hipMemcpyAsync(c->h_totals, c->batch.total, (size_t)(m * nf) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int i = 0; i < m; i++)
+            for (int f = 0; f < nf; f++) values[i] += (uint64_t)c->h_totals[i * nf + f];
+        return PICSONG_OK;
+    };
+    // Quality: quality_probe per candidate, back to back; every probe made is kept with its per-array sums for h_sse.
+    std::vector<int> seen_j;
+    std::vector<uint64_t> seen_sse;
+    auto measure_quality = [&](int m, const int *js, uint64_t *values) -> int {
+        const QualityProbe probe = { c->rate_coef, (unsigned long long)c->rate_z, c->batch.coef_i, c->batch.coef, c->q_pix,
+                                     c->aw, c->ah, c->p.wl, c->p.width, c->p.height, level_off(c), c->P, c->extra, nf,
+                                     job.frames, job.frame_stride, job.r, job.g, job.b };
         for (int i = 0; i < m; i++) {
             // stage timers (picsong_profile_begin): a probe records quantise, synthesis and SSE where a frame records
             // transform, coder and pack
@@ -1742,28 +1660,90 @@ static int quality_impl(picsong_ctx *c, const RateJob &job, uint64_t max_sse, in
                 if (ev) HIP_TRY(hipEventRecord(ev[k], s));
                 return PICSONG_OK;
             };
-            if ((rc = quality_probe(HipGo{ s }, probe, grid[(size_t)idx[i]], c->d_sse + i * nf, mark))) return rc;
+            if (int e = quality_probe(HipGo{ s }, probe, js[i], c->d_sse + i * nf, mark)) return e;
         }
         HIP_TRY(hipMemcpyAsync(c->h_sse, c->d_sse, (size_t)(m * nf) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        unsigned long long sums[kRateMaxK] = { 0, 0, 0 };
         for (int i = 0; i < m; i++) {
-            seen_j.push_back(grid[(size_t)idx[i]]);
-            for (int f = 0; f < nf; f++) { sums[i] += c->h_sse[i * nf + f]; seen_sse.push_back(c->h_sse[i * nf + f]); }
+            seen_j.push_back(js[i]);
+            for (int f = 0; f < nf; f++) { values[i] += c->h_sse[i * nf + f]; seen_sse.push_back(c->h_sse[i * nf + f]); }
         }
-        st.take(sums);
-    }
+        return PICSONG_OK;
+    };
+    const BisectWalk w = size ? bisect_walk(grid, limit, K, Bisect::Largest, measure_size)
+                              : bisect_walk(grid, limit, K, Bisect::Smallest, measure_quality);
+    if (w.rc) return w.rc;
     *h_j = 0;
-    if (st.result() < 0)
-        return fail(PICSONG_ERR_QUALITY, "%s: no quantiser of the search range meets an SSE of %llu", who, (unsigned long long)max_sse);
-    const int j = grid[(size_t)st.result()];
-    // ---- the result's encode: quantise, coder, pack, as the rate calls' final step
-    if ((rc = rate_probe(c, a, nf, 1, &j, s))) return rc;
-    if ((rc = rate_finish(c, job, nf, j, 0, s, h_totals))) return rc;
-    for (size_t i = 0; i < seen_j.size(); i++)              // (the result is a probe the procedure made)
-        if (seen_j[i] == j) for (int f = 0; f < nf; f++) h_sse[f] = (uint64_t)seen_sse[i * (size_t)nf + (size_t)f];
+    if (w.result < 0)
+        return size ? fail(PICSONG_ERR_RATE, "%s: no quantiser of the search range meets %llu shorts", who, (unsigned long long)limit)
+                    : fail(PICSONG_ERR_QUALITY, "%s: no quantiser of the search range meets an SSE of %llu", who, (unsigned long long)limit);
+    const int j = grid[(size_t)w.result];
+    // ---- the winner's staging: candidate `slot` of a size search's last round, or coded once more on its own
+    int slot = -1;
+    if (size) for (int i = 0; i < w.m; i++) if (w.js[i] == j) slot = i;
+    if (slot < 0) {
+        if ((rc = rate_probe(c, a, nf, 1, &j, s))) return rc;
+        slot = 0;
+    }
+    if ((rc = rate_finish(c, job, nf, j, slot, s, h_totals))) return rc;
+    for (size_t i = 0; i < seen_j.size(); i++)              // (a quality search's result is a probe the procedure made)
+        if (seen_j[i] == j) for (int f = 0; f < nf; f++) h_sse[f] = seen_sse[i * (size_t)nf + (size_t)f];
     *h_j = j;
     return PICSONG_OK;
+}
+
+// The entry points' own refusals, over the job they made.  form: which of the three inputs the entry takes; outs: its
+// host pointers are all there.  (kOneFrame takes a frame of any alignment, as picsong_encode_frame: an unaligned one
+// runs the per-column transform kernels and sse_kernel's per-byte form.)
+enum SearchForm { kFrames, kOneFrame, kRgbFrame };
+
+static int search_args_ok(const picsong_ctx *c, const RateJob &job, SearchForm form, SearchKind kind, bool outs, const char *who)
+{
+    const bool rgb = form == kRgbFrame;
+    if (!c || !job.d_streams || !outs || (rgb ? !job.r || !job.g || !job.b : !job.frames)) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (job.n < 1 || job.n > 16) return fail(PICSONG_ERR_ARG, "%s: %d frames outside 1..16", who, job.n);
+    const size_t max_shorts = picsong_max_stream_shorts(c->aw, c->ah);
+    if (rgb) {
+        if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: the context is not an RGB one", who);
+        if (job.stream_stride < max_shorts) return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
+        if ((((uintptr_t)job.r) | ((uintptr_t)job.g) | ((uintptr_t)job.b)) & 3u) return fail(PICSONG_ERR_ARG, "%s: the planes need 4-byte alignment", who);
+        return PICSONG_OK;
+    }
+    if (c->p.is_rgb)
+        return fail(PICSONG_ERR_ARG, "%s: grey contexts only (an RGB frame: picsong_encode_rgb_frame_%s)", who, kind == kSearchSize ? "rate" : "quality");
+    if (job.n > 1 && (job.frame_stride < c->P || job.stream_stride < max_shorts))
+        return fail(PICSONG_ERR_ARG, "%s: strides smaller than a padded frame / a worst-case codestream", who);
+    if (form == kFrames && (((uintptr_t)job.frames | job.frame_stride) & 15u)) return fail(PICSONG_ERR_ARG, "%s: frames must be 16-byte aligned", who);
+    return PICSONG_OK;
+}
+
+int picsong_encode_frames_rate(picsong_ctx *c, int n, const uint8_t *d_frames, size_t frame_stride, int first_iter,
+                               size_t target_shorts, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
+                               void *stream, int *h_j, int *h_totals)
+{
+    const char *who = "encode_frames_rate";
+    const RateJob job = { n, d_frames, frame_stride, nullptr, nullptr, nullptr, first_iter, 0, d_streams, stream_stride, false };
+    if (int rc = search_args_ok(c, job, kFrames, kSearchSize, h_j && h_totals, who)) return rc;
+    return search_impl(c, job, kSearchSize, target_shorts, j_min, j_max, (hipStream_t)stream, h_j, h_totals, nullptr, who);
+}
+
+int picsong_encode_frame_rate(picsong_ctx *c, const uint8_t *d_frame, int iter, size_t target_shorts, int j_min, int j_max,
+                              uint16_t *d_stream, void *stream, int *h_j, int *h_total)
+{
+    const char *who = "encode_frame_rate";
+    const RateJob job = { 1, d_frame, 0, nullptr, nullptr, nullptr, iter == 0 ? 0 : 1, 0, d_stream, 0, true };
+    if (int rc = search_args_ok(c, job, kOneFrame, kSearchSize, h_j && h_total, who)) return rc;
+    return search_impl(c, job, kSearchSize, target_shorts, j_min, j_max, (hipStream_t)stream, h_j, h_total, nullptr, who);
+}
+
+int picsong_encode_rgb_frame_rate(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
+                                  size_t target_shorts, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
+                                  void *stream, int *h_j, int *h_totals)
+{
+    const char *who = "encode_rgb_frame_rate";
+    const RateJob job = { 1, nullptr, 0, d_r, d_g, d_b, 0, header_mask, d_streams, stream_stride, false };
+    if (int rc = search_args_ok(c, job, kRgbFrame, kSearchSize, h_j && h_totals, who)) return rc;
+    return search_impl(c, job, kSearchSize, target_shorts, j_min, j_max, (hipStream_t)stream, h_j, h_totals, nullptr, who);
 }
 
 int picsong_encode_frames_quality(picsong_ctx *c, int n, const uint8_t *d_frames, size_t frame_stride, int first_iter,
@@ -1771,25 +1751,18 @@ int picsong_encode_frames_quality(picsong_ctx *c, int n, const uint8_t *d_frames
                                   void *stream, int *h_j, int *h_totals, uint64_t *h_sse)
 {
     const char *who = "encode_frames_quality";
-    if (!c || !d_frames || !d_streams || !h_j || !h_totals || !h_sse) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
-    if (n < 1 || n > 16) return fail(PICSONG_ERR_ARG, "%s: %d frames outside 1..16", who, n);
-    if (c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: grey contexts only (an RGB frame: picsong_encode_rgb_frame_quality)", who);
-    if (n > 1 && (frame_stride < c->P || stream_stride < picsong_max_stream_shorts(c->aw, c->ah)))
-        return fail(PICSONG_ERR_ARG, "%s: strides smaller than a padded frame / a worst-case codestream", who);
-    if (((uintptr_t)d_frames | frame_stride) & 15u) return fail(PICSONG_ERR_ARG, "%s: frames must be 16-byte aligned", who);
     const RateJob job = { n, d_frames, frame_stride, nullptr, nullptr, nullptr, first_iter, 0, d_streams, stream_stride, false };
-    return quality_impl(c, job, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_totals, h_sse, who);
+    if (int rc = search_args_ok(c, job, kFrames, kSearchQuality, h_j && h_totals && h_sse, who)) return rc;
+    return search_impl(c, job, kSearchQuality, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_totals, h_sse, who);
 }
 
 int picsong_encode_frame_quality(picsong_ctx *c, const uint8_t *d_frame, int iter, uint64_t max_sse, int j_min, int j_max,
                                  uint16_t *d_stream, void *stream, int *h_j, int *h_total, uint64_t *h_sse)
 {
     const char *who = "encode_frame_quality";
-    if (!c || !d_frame || !d_stream || !h_j || !h_total || !h_sse) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
-    if (c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: grey contexts only (an RGB frame: picsong_encode_rgb_frame_quality)", who);
-    // (any alignment, as picsong_encode_frame_rate: the transform and sse_kernel have their per-byte forms)
     const RateJob job = { 1, d_frame, 0, nullptr, nullptr, nullptr, iter == 0 ? 0 : 1, 0, d_stream, 0, true };
-    return quality_impl(c, job, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_total, h_sse, who);
+    if (int rc = search_args_ok(c, job, kOneFrame, kSearchQuality, h_j && h_total && h_sse, who)) return rc;
+    return search_impl(c, job, kSearchQuality, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_total, h_sse, who);
 }
 
 int picsong_encode_rgb_frame_quality(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
@@ -1797,12 +1770,9 @@ int picsong_encode_rgb_frame_quality(picsong_ctx *c, const uint8_t *d_r, const u
                                      void *stream, int *h_j, int *h_totals, uint64_t *h_sse)
 {
     const char *who = "encode_rgb_frame_quality";
-    if (!c || !d_r || !d_g || !d_b || !d_streams || !h_j || !h_totals || !h_sse) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
-    if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: the context is not an RGB one", who);
-    if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah)) return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
-    if ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 3u) return fail(PICSONG_ERR_ARG, "%s: the planes need 4-byte alignment", who);
     const RateJob job = { 1, nullptr, 0, d_r, d_g, d_b, 0, header_mask, d_streams, stream_stride, false };
-    return quality_impl(c, job, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_totals, h_sse, who);
+    if (int rc = search_args_ok(c, job, kRgbFrame, kSearchQuality, h_j && h_totals && h_sse, who)) return rc;
+    return search_impl(c, job, kSearchQuality, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_totals, h_sse, who);
 }
 
 // picsong_decode_rgb_frame (reduce = 0) and picsong_decode_rgb_frame_reduced: the three components' level `reduce`,

@@ -347,20 +347,6 @@ void rate_report_achieved(const Options &o, long total_shorts, long nframes)
     std::cout << "Rate control: achieved " << (double)total_shorts * 16.0 / ((double)o.x * o.y * (double)nframes)
               << " bits per pixel over the whole output (target " << o.rate << ")" << std::endl;
 }
-[[noreturn]] void rate_die(int rc, const char *call)
-{
-    if (rc == PICSONG_ERR_RATE) die(std::string("-rate: no quantiser meets the target size (") + picsong_last_error() + ")");
-    die(std::string(call) + " failed: " + picsong_last_error());
-}
-
-// the limit of a -psnr search over `frames` frames of `components` planes
-uint64_t quality_limit(const Options &o, long frames, int components, uint64_t *samples)
-{
-    uint64_t lim = 0;
-    *samples = (uint64_t)o.x * (uint64_t)o.y * (uint64_t)frames * (uint64_t)components;
-    CK(picsong_psnr_to_sse(o.psnr, *samples, &lim));
-    return lim;
-}
 void quality_report(int j, float qs, uint64_t max_sse, uint64_t samples, long nframes_searched, const uint64_t *sse, int n)
 {
     QualityReport &r = g_quality;
@@ -371,10 +357,39 @@ void quality_report(int j, float qs, uint64_t max_sse, uint64_t samples, long nf
               << nframes_searched << " frame(s)" << std::endl;
     std::cout << "Quality control: achieved " << r.psnr << " dB (SSE " << r.sse << ") over the frames searched" << std::endl;
 }
-[[noreturn]] void quality_die(int rc, const char *call)
+
+// ---- the search step of -rate / -psnr: the search `o` asks for over an input on the device, into d_out; the choice and
+// its console lines.  The input: n padded grey frames `stride` bytes apart (n = 0: an image, through the one-frame
+// calls) or, with rgb_mask != 0, the R, G and B planes of a frame, which must lie at d, d + stride and d + 2 * stride
+// (run_encode_rgb carves them out of one allocation so), coded with that header mask.  Returns the failure
+// (empty: none); re-tuning contexts to the choice is the caller's.
+struct SearchInput { const uint8_t *d; size_t stride; int n, rgb_mask; };
+struct SearchChoice { int j = 0; float qs = 0.0f; int totals[16] = { 0 }; };
+std::string search_step(const Options &o, picsong_ctx *ctx, hipStream_t s, const SearchInput &in, uint16_t *d_out, size_t out_stride,
+                        SearchChoice &r)
 {
-    if (rc == PICSONG_ERR_QUALITY) die(std::string("-psnr: no quantiser meets the target quality (") + picsong_last_error() + ")");
-    die(std::string(call) + " failed: " + picsong_last_error());
+    const int frames = in.n ? in.n : 1, arrays = in.rgb_mask ? 3 : frames;
+    const uint8_t *g = in.d + in.stride, *b = g + in.stride;
+    const size_t target = rate_target_shorts(o) * (size_t)frames;
+    const uint64_t samples = (uint64_t)o.x * (uint64_t)o.y * (uint64_t)arrays;
+    uint64_t lim = 0, sse[16] = { 0 };
+    if (o.has_psnr && picsong_psnr_to_sse(o.psnr, samples, &lim) != PICSONG_OK) return std::string("-psnr: ") + picsong_last_error();
+    int rc;
+    if (in.rgb_mask)
+        rc = o.has_psnr ? picsong_encode_rgb_frame_quality(ctx, in.d, g, b, in.rgb_mask, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse)
+                        : picsong_encode_rgb_frame_rate(ctx, in.d, g, b, in.rgb_mask, target, 0, 0, d_out, out_stride, s, &r.j, r.totals);
+    else if (in.n)
+        rc = o.has_psnr ? picsong_encode_frames_quality(ctx, in.n, in.d, in.stride, 0, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse)
+                        : picsong_encode_frames_rate(ctx, in.n, in.d, in.stride, 0, target, 0, 0, d_out, out_stride, s, &r.j, r.totals);
+    else
+        rc = o.has_psnr ? picsong_encode_frame_quality(ctx, in.d, 0, lim, 0, 0, d_out, s, &r.j, r.totals, sse)
+                        : picsong_encode_frame_rate(ctx, in.d, 0, target, 0, 0, d_out, s, &r.j, r.totals);
+    if (rc == PICSONG_ERR_RATE) return std::string("-rate: no quantiser meets the target size (") + picsong_last_error() + ")";
+    if (rc == PICSONG_ERR_QUALITY) return std::string("-psnr: no quantiser meets the target quality (") + picsong_last_error() + ")";
+    if (rc != PICSONG_OK || picsong_rate_qs(r.j, &r.qs) != PICSONG_OK) return std::string("The quantiser search failed: ") + picsong_last_error();
+    if (o.has_psnr) quality_report(r.j, r.qs, lim, samples, frames, sse, arrays);
+    else rate_report_choice(r.j, r.qs, target, frames);
+    return std::string();
 }
 
 // ---- RGB coding (CodingEngine::runImage / runVideo, RGB branches: CodingEngine.cu:598-633,676-712,
@@ -433,27 +448,13 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
             HIPCK(hipStreamSynchronize(s));          // h_in is reused for the next plane
         }
         int totals[3] = { 0, 0, 0 };
-        if (o.has_rate && f == 0) {
+        if ((o.has_rate || o.has_psnr) && f == 0) {
             // the search on the first frame (an image: the frame); the rest of a video is coded at the result
-            int j = 0;
-            float q = 0.0f;
-            const int rc = picsong_encode_rgb_frame_rate(ctx, d_in[0], d_in[1], d_in[2], o.video ? 7 : 1, rate_target_shorts(o), 0, 0,
-                                                         d_out, max_shorts, s, &j, totals);
-            if (rc != PICSONG_OK) rate_die(rc, "picsong_encode_rgb_frame_rate");
-            CK(picsong_rate_qs(j, &q));
-            CK(picsong_ctx_set_qs(ctx, q));
-            rate_report_choice(j, q, rate_target_shorts(o), 1);
-        } else if (o.has_psnr && f == 0) {
-            int j = 0;
-            float q = 0.0f;
-            uint64_t samples = 0, sse[3] = { 0, 0, 0 };
-            const uint64_t lim = quality_limit(o, 1, 3, &samples);
-            const int rc = picsong_encode_rgb_frame_quality(ctx, d_in[0], d_in[1], d_in[2], o.video ? 7 : 1, lim, 0, 0, d_out, max_shorts,
-                                                            s, &j, totals, sse);
-            if (rc != PICSONG_OK) quality_die(rc, "picsong_encode_rgb_frame_quality");
-            CK(picsong_rate_qs(j, &q));
-            CK(picsong_ctx_set_qs(ctx, q));
-            quality_report(j, q, lim, samples, 1, sse, 3);
+            SearchChoice r;
+            const std::string err = search_step(o, ctx, s, { d_in[0], P, 1, o.video ? 7 : 1 }, d_out, max_shorts, r);
+            if (!err.empty()) die(err);
+            CK(picsong_ctx_set_qs(ctx, r.qs));
+            std::copy(r.totals, r.totals + 3, totals);
         } else if (batched) {
             CK(picsong_encode_rgb_frame(ctx, d_in[0], d_in[1], d_in[2], o.video ? (f == 0 ? 7 : 0) : 1, d_out, max_shorts, s));
             CK(picsong_last_totals(ctx, s, 3, totals));
@@ -705,24 +706,10 @@ int run_encode(Options o)
         } else {
             HIPCK(hipMemcpyAsync(d_f, h_f, P * (size_t)n, hipMemcpyHostToDevice, k.stream));
         }
-        int j = 0, totals[16];
-        float q = 0.0f;
-        if (o.has_psnr) {               // -psnr mirrors -rate: the same frames, the same contexts, the limit over all of them
-            uint64_t samples = 0, sse[16];
-            const uint64_t lim = quality_limit(o, n, 1, &samples);
-            const int rc = picsong_encode_frames_quality(k.ctx, n, d_f, P, 0, lim, 0, 0, d_s, max_shorts, k.stream, &j, totals, sse);
-            if (rc != PICSONG_OK) quality_die(rc, "picsong_encode_frames_quality");
-            CK(picsong_rate_qs(j, &q));
-            for (auto &x : w) CK(picsong_ctx_set_qs(x.ctx, q));
-            quality_report(j, q, lim, samples, n, sse, n);
-        } else {
-        const size_t target = rate_target_shorts(o) * (size_t)n;
-        const int rc = picsong_encode_frames_rate(k.ctx, n, d_f, P, 0, target, 0, 0, d_s, max_shorts, k.stream, &j, totals);
-        if (rc != PICSONG_OK) rate_die(rc, "picsong_encode_frames_rate");
-        CK(picsong_rate_qs(j, &q));
-        for (auto &x : w) CK(picsong_ctx_set_qs(x.ctx, q));
-        rate_report_choice(j, q, target, n);
-        }
+        SearchChoice r;                 // the target, or the limit, over all n frames
+        const std::string err = search_step(o, k.ctx, k.stream, { d_f, P, n, 0 }, d_s, max_shorts, r);
+        if (!err.empty()) die(err);
+        for (auto &x : w) CK(picsong_ctx_set_qs(x.ctx, r.qs));
         (void)hipHostFree(h_f); (void)hipFree(d_f); (void)hipFree(d_s);
     }
     // image: one truncating write (IOManager.ipp:615-620); video: append + _SIZE (:176-190)
@@ -882,27 +869,10 @@ int run_encode(Options o)
             (o.layout >= 0 ? hipMemcpyAsync(k.d_raw, k.h_in, frame_bytes * (size_t)n, hipMemcpyHostToDevice, k.stream)
                            : hipMemcpyAsync(k.d_in, k.h_in, P * (size_t)n, hipMemcpyHostToDevice, k.stream)) != hipSuccess) err = "HIP error in the frame upload";
         else if (o.layout >= 0 && picsong_ingest_frames(k.ctx, n, &im, frame_bytes, k.d_in, P, k.stream) != PICSONG_OK) err = picsong_last_error();
-        else if (o.has_rate && !o.video) {
-            // an image: one rate call (synchronous); its length is the context's last total, as after picsong_encode_frame
-            int j = 0, total = 0;
-            float q = 0.0f;
-            const int rc = picsong_encode_frame_rate(k.ctx, k.d_in, 0, rate_target_shorts(o), 0, 0, k.d_out, k.stream, &j, &total);
-            if (rc == PICSONG_ERR_RATE) err = std::string("-rate: no quantiser meets the target size (") + picsong_last_error() + ")";
-            else if (rc != PICSONG_OK || picsong_rate_qs(j, &q) != PICSONG_OK) err = picsong_last_error();
-            else rate_report_choice(j, q, rate_target_shorts(o), 1);
-        }
-        else if (o.has_psnr && !o.video) {
-            // an image: one quality call (synchronous); its length is the context's last total, as after picsong_encode_frame
-            int j = 0, total = 0;
-            float q = 0.0f;
-            uint64_t samples = 0, sse = 0, lim = 0;
-            if (picsong_psnr_to_sse(o.psnr, samples = (uint64_t)o.x * (uint64_t)o.y, &lim) != PICSONG_OK) err = picsong_last_error();
-            else {
-                const int rc = picsong_encode_frame_quality(k.ctx, k.d_in, 0, lim, 0, 0, k.d_out, k.stream, &j, &total, &sse);
-                if (rc == PICSONG_ERR_QUALITY) err = std::string("-psnr: no quantiser meets the target quality (") + picsong_last_error() + ")";
-                else if (rc != PICSONG_OK || picsong_rate_qs(j, &q) != PICSONG_OK) err = picsong_last_error();
-                else quality_report(j, q, lim, samples, 1, &sse, 1);
-            }
+        else if ((o.has_rate || o.has_psnr) && !o.video) {
+            // an image: one search call (synchronous); its length is the context's last total, as after picsong_encode_frame
+            SearchChoice r;
+            err = search_step(o, k.ctx, k.stream, { k.d_in, 0, 0, 0 }, k.d_out, 0, r);
         }
         else if (B == 1) { if (picsong_encode_frame(k.ctx, k.d_in, g == 0 ? 0 : 1, k.d_out, k.stream) != PICSONG_OK) err = picsong_last_error(); }
         else if (picsong_encode_frames(k.ctx, n, k.d_in, P, (int)(g * B), k.d_out, max_shorts, k.stream) != PICSONG_OK) err = picsong_last_error();

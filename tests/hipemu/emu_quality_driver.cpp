@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE ONLY -- the quality calls' pieces on the CPU wave emulator: sse_kernel with the launch and the
-// arguments kernel_select.hpp gives it, the search (QualityStepper, rate_search.hpp: the very stepper picsong_hip.hip
-// walks), quantise_kernel's int32 form, and the probe sequence of launch_seq.hpp (quality_probe) behind the unit-step
-// transform, as quality_impl runs them.
+// arguments kernel_select.hpp gives it, the search (bisect_walk of rate_search.hpp, the very loop picsong_hip.hip's
+// search_impl runs), quantise_kernel's int32 form, and the probe sequence of launch_seq.hpp (quality_probe) behind the
+// unit-step transform, as search_impl runs them.
 // Built by tests/test_quality_emulated.py with the flags of tests/hipemu/Makefile.
 #include <hip/hip_runtime.h>
 
@@ -30,28 +30,25 @@ int emu_sse(const uint8_t *a, unsigned long long a_pitch, unsigned long long a_z
     return l.kernel == (SseKernel)sse_kernel<true> ? 1 : 0;
 }
 
-// The search as quality_impl runs it, over a synthetic distortion given as a table sse_by_j[0 .. 16383].  Returns the
-// result j, 0 when nothing meets the limit, -1 for a range without a grid entry.  stats: { rounds, probes used, probes
-// made }; probed (capacity 64): the j of every probe made, round by round.
+// The walk the quality calls run (bisect_walk, rate_search.hpp) with a table lookup as its measure: a synthetic
+// distortion sse_by_j[0 .. 16383].  Returns the result j, 0 when nothing meets the limit, -1 for a range without a grid
+// entry.  stats: { rounds, probes used, probes made }; probed (capacity 64): the j of every probe made, round by round.
 int emu_quality_search(const unsigned long long *sse_by_j, unsigned long long limit, int j_min, int j_max, int K, int *stats,
                        int *probed)
 {
     if (!rate_range_ok(j_min, j_max)) return -1;
     const std::vector<int> grid = rate_grid(j_min, j_max);
     if (grid.empty()) return -1;
-    QualityStepper st((int)grid.size(), limit, K);
-    int idx[kRateMaxK], m, made = 0;
-    while ((m = st.next(idx)) > 0) {
-        unsigned long long v[kRateMaxK] = { 0, 0, 0 };
-        for (int i = 0; i < m; i++) {
-            v[i] = sse_by_j[grid[(size_t)idx[i]]];
-            if (probed && made < 64) probed[made] = grid[(size_t)idx[i]];
-            made++;
+    int made = 0;
+    const BisectWalk w = bisect_walk(grid, (uint64_t)limit, K, Bisect::Smallest, [&](int m, const int *js, uint64_t *v) {
+        for (int i = 0; i < m; i++, made++) {
+            v[i] = (uint64_t)sse_by_j[js[i]];
+            if (probed && made < 64) probed[made] = js[i];
         }
-        st.take(v);
-    }
-    if (stats) { stats[0] = st.rounds(); stats[1] = st.probes(); stats[2] = made; }
-    return st.result() < 0 ? 0 : grid[(size_t)st.result()];
+        return 0;
+    });
+    if (stats) { stats[0] = w.rounds; stats[1] = w.probes; stats[2] = made; }
+    return w.result < 0 ? 0 : grid[(size_t)w.result];
 }
 
 // the unit-step transform of `frames` u8 frames (in_z bytes apart) into float work buffers out_z bytes apart

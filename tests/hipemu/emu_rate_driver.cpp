@@ -1,5 +1,5 @@
-// TEST INFRASTRUCTURE ONLY -- the rate calls' pieces on the CPU wave emulator: the search (rate_search.hpp, the very
-// stepper picsong_hip.hip walks), the unquantised forward transform (plan_dwt_forward_unit through rate_transform's
+// TEST INFRASTRUCTURE ONLY -- the rate calls' pieces on the CPU wave emulator: the search (bisect_walk of
+// rate_search.hpp, the very loop picsong_hip.hip's search_impl runs), the unquantised forward transform (plan_dwt_forward_unit through rate_transform's
 // sequences: launch_fwd_plan, rgb_forward_transform, launch_seq.hpp) and quantise_kernel with the launch and the
 // arguments kernel_select.hpp gives it.
 // Built by tests/test_rate_emulated.py with the flags of tests/hipemu/Makefile.
@@ -25,27 +25,25 @@ int emu_rate_grid(int j_min, int j_max, int *out, int cap)
     return (int)g.size();
 }
 
-// The search as rate_impl runs it, over a synthetic size function given as a table size_by_j[0 .. 16383].  Returns the
-// result j, 0 when nothing fits, -1 for a range without a grid entry.  stats: { rounds, probes used, probes made };
-// probed (capacity 64): the j of every probe made, round by round.
+// The walk the rate calls run (bisect_walk, rate_search.hpp) with a table lookup as its measure: a synthetic size
+// function size_by_j[0 .. 16383] (the tests' tables and targets are positive, as the coder's totals are: the library's cast).
+// Returns the result j, 0 when nothing fits, -1 for a range without a grid entry.  stats: { rounds, probes used, probes
+// made }; probed (capacity 64): the j of every probe made, round by round.
 int emu_rate_search(const long long *size_by_j, long long target, int j_min, int j_max, int K, int *stats, int *probed)
 {
     if (!rate_range_ok(j_min, j_max)) return -1;
     const std::vector<int> grid = rate_grid(j_min, j_max);
     if (grid.empty()) return -1;
-    RateStepper st((int)grid.size(), target, K);
-    int idx[kRateMaxK], m, made = 0;
-    while ((m = st.next(idx)) > 0) {
-        long long sizes[kRateMaxK] = { 0, 0, 0 };
-        for (int i = 0; i < m; i++) {
-            sizes[i] = size_by_j[grid[(size_t)idx[i]]];
-            if (probed && made < 64) probed[made] = grid[(size_t)idx[i]];
-            made++;
+    int made = 0;
+    const BisectWalk w = bisect_walk(grid, (uint64_t)target, K, Bisect::Largest, [&](int m, const int *js, uint64_t *v) {
+        for (int i = 0; i < m; i++, made++) {
+            v[i] = (uint64_t)size_by_j[js[i]];
+            if (probed && made < 64) probed[made] = js[i];
         }
-        st.take(sizes);
-    }
-    if (stats) { stats[0] = st.rounds(); stats[1] = st.probes(); stats[2] = made; }
-    return st.result() < 0 ? 0 : grid[(size_t)st.result()];
+        return 0;
+    });
+    if (stats) { stats[0] = w.rounds; stats[1] = w.probes; stats[2] = made; }
+    return w.result < 0 ? 0 : grid[(size_t)w.result];
 }
 
 // the unquantised transform of `frames` frames (u8 with the level shift fused, or float), frame z at in + z * in_z bytes,

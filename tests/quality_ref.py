@@ -51,6 +51,11 @@ def bisect(sse_fn, max_sse, j_min=0, j_max=0):
                   seen.get(prev) if prev is not None else None, probes)
 
 
+def rounds3(sse_fn, max_sse, j_min=0, j_max=0):
+    """The K = 3 round of the quality calls: rate_ref.rounds3 with a pass moving hi."""
+    return rr.rounds3(sse_fn, max_sse, j_min, j_max, pass_moves_lo=False)
+
+
 def coder_free_frame(img, wl, j):
     """The decoder's pixels without the coder: the oracle's fused transform at q(j), truncated toward zero, its
     synthesis at q(j), level shift and clamp; the visible part."""

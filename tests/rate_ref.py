@@ -60,6 +60,34 @@ def bisect(size_fn, target, j_min=0, j_max=0):
                   probed.get(nxt) if nxt is not None else None, probes, size(g[0]))
 
 
+def rounds3(value_fn, limit, j_min=0, j_max=0, pass_moves_lo=True):
+    """The K = 3 round: every j probed, round by round.  A round's candidates, ascending, are (lo+mid)//2 when
+    mid - lo > 1, mid, and (mid+hi)//2 when hi - mid > 1; then two levels of the procedure are applied (the midpoint,
+    and the candidate its outcome leads to where there is one).  A pass (value <= limit) moves lo (the rate calls) or
+    hi (the quality calls, pass_moves_lo = False)."""
+    g = grid(j_min, j_max)
+    lo, hi = -1, len(g)
+    probed = []
+
+    def level(i):
+        nonlocal lo, hi
+        if (int(value_fn(g[i])) <= limit) == pass_moves_lo:
+            lo = i
+        else:
+            hi = i
+
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        left = (lo + mid) // 2 if mid - lo > 1 else None
+        right = (mid + hi) // 2 if hi - mid > 1 else None
+        probed += [g[i] for i in (left, mid, right) if i is not None]
+        level(mid)
+        second = right if lo == mid else left
+        if second is not None:
+            level(second)
+    return probed
+
+
 def frames_size_fn(imgs, wl, lut, k=0.0):
     """size(j) of grey frames: the sum of the oracle's codestream lengths (shorts, header and terminator included)."""
     def fn(j):

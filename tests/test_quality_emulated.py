@@ -1,5 +1,5 @@
 """The quality calls' pieces on the CPU wave emulator (tests/hipemu/emu_quality_driver.cpp): sse_kernel against numpy,
-the search stepper of rate_search.hpp (QualityStepper) against the reference procedure (quality_ref.bisect),
+the search of rate_search.hpp (bisect_walk, smallest passing index) against the reference procedure (quality_ref.bisect),
 quantise_kernel's int32 form against the oracle's fused transform truncated, and the probe sequence of launch_seq.hpp
 (unit transform, quantise, synthesis, SSE) against the oracle's decode of its own encode."""
 import ctypes as C
@@ -148,8 +148,9 @@ def _check(table, limit, j_min=0, j_max=0):
         if K == 1:
             assert rounds == made == used and probed == [p[0] for p in ref.probes]
         else:
-            assert rounds == (used + 1) // 2 and made <= 3 * rounds
-            assert set(p[0] for p in ref.probes) <= set(probed)
+            want = qr.rounds3(lambda j: table[j], limit, j_min, j_max)
+            assert rounds == (used + 1) // 2 and made == len(want) <= 3 * rounds
+            assert probed == want and set(p[0] for p in ref.probes) <= set(probed)
     return ref
 
 

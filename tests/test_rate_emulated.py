@@ -64,8 +64,9 @@ def _check(table, target, j_min=0, j_max=0):
         if K == 1:
             assert rounds == made == used and probed == [p[0] for p in ref.probes]
         else:
-            assert rounds == (used + 1) // 2 and made <= 3 * rounds
-            assert set(p[0] for p in ref.probes) <= set(probed)
+            want = rr.rounds3(lambda j: table[j], target, j_min, j_max)
+            assert rounds == (used + 1) // 2 and made == len(want) <= 3 * rounds
+            assert probed == want and set(p[0] for p in ref.probes) <= set(probed)
     return ref
 
 
