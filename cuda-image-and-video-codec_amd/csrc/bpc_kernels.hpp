@@ -82,8 +82,9 @@ struct BpcArgs {
     // 0 / 1 frames = a single frame (waves_per_frame unused)
     int frames, waves_per_frame;
     unsigned long long coef_z;
-    // the frames of a batched launch are the three COMPONENTS of one RGB frame (picsong_encode_rgb_frame): frame f
-    // codes with table lut_c[f] (same geometry); waves_per_frame is then a whole number of workgroups, a workgroup's
+    // the frames of a batched launch are the three COMPONENTS of each of frames / 3 RGB frames (picsong_encode_rgb_frame,
+    // picsong_encode_rgb_frames): frame f is component f % 3 of RGB frame f / 3 and
+    // codes with table lut_c[f % 3] (same geometry); waves_per_frame is then a whole number of workgroups, a workgroup's
     // LDS copy of the table being its frame's.  lut_c[0] = nullptr: every frame uses `lut`
     const int32_t *lut_c[3];
     // k = 0 encoder: the table's plane records (plane_record: picsong_ctx_set_lut* builds them), plane_img_recs(wl) of
@@ -1628,9 +1629,11 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
             a.staging16 += (size_t)f * (size_t)a.AW * (size_t)a.AH;
             a.sizes += (size_t)f * (size_t)(a.nCB - a.cb_base);
             // (scalar selects: indexing the argument struct with f would move all of it to scratch memory)
+            // (frame f of an RGB launch is component f % 3 of frame f / 3: f is a scalar here, so is the modulo)
             if (a.lut_c[0]) {
-                a.lut = f == 0 ? a.lut_c[0] : (f == 1 ? a.lut_c[1] : a.lut_c[2]);
-                a.plane_img = f == 0 ? a.img_c[0] : (f == 1 ? a.img_c[1] : a.img_c[2]);
+                const int c = f % 3;
+                a.lut = c == 0 ? a.lut_c[0] : (c == 1 ? a.lut_c[1] : a.lut_c[2]);
+                a.plane_img = c == 0 ? a.img_c[0] : (c == 1 ? a.img_c[1] : a.img_c[2]);
             }
         }
     }
@@ -2365,7 +2368,11 @@ void bpc_decode_kernel(BpcArgs a)
             a.sizes += (size_t)f * (size_t)(a.nCB - a.cb_base);
             if (S16) { a.cw16 += (size_t)f * (size_t)a.cw16_stride; a.cw16_offsets += (size_t)f * (size_t)a.nCB; a.cw16_total += f; }
             // (scalar selects: indexing the argument struct with f would move all of it to scratch memory)
-            if (a.lut_c[0]) a.lut = f == 0 ? a.lut_c[0] : (f == 1 ? a.lut_c[1] : a.lut_c[2]);
+            // (frame f of an RGB launch is component f % 3 of frame f / 3; the modulo once a wave, on the scalar side)
+            if (a.lut_c[0]) {
+                const int c = (int)__builtin_amdgcn_readfirstlane((uint32_t)f) % 3;
+                a.lut = c == 0 ? a.lut_c[0] : (c == 1 ? a.lut_c[1] : a.lut_c[2]);
+            }
         }
     }
     // (each half maps on its own: with an odd rectangle width a wave's two codeblocks may lie in two rows or rectangles)

@@ -91,7 +91,8 @@ struct DwtFwdArgs {
     // launch_plan.hpp: 8-bit samples); the stage-by-stage API keeps the reference's T arrays.
     int c16;
     // fused head, RGB frames (dwt_fwd2_kernel<..., RGB>): `src` is the R plane, these the G and B planes (padded u8,
-    // same stride); the launch's blockIdx.z is the COMPONENT the RCT delivers (src_z = 0: every component reads all three)
+    // same stride); plane blockIdx.z of the launch is COMPONENT z % 3, which the RCT delivers from the three planes of
+    // frame z / 3, src_z bytes after frame 0's (level 0's src_z: every component of a frame reads all three)
     const void *src_g, *src_b;
 };
 
@@ -1048,17 +1049,32 @@ __global__ __launch_bounds__(256, RGB ? PICSONG_DWT_F2_RGB_WAVES : (LOSSY ? PICS
         // the slowest) a tile's three workgroups run a third of the launch apart, wherever their indices fall, and
         // every plane comes from the memory side three times.  Re-indexed so that they are 8 apart -- same XCD, in
         // flight together -- the second and third read hit that XCD's L2 (8K: head 118.6 -> see profiles/NOTES.md).
+        // Several frames a launch (gridDim.z = 3 n, picsong_encode_rgb_frames): plane z is component z % 3 of frame z / 3.
+        // A frame's 3 * tiles workgroups are consecutive in linear order and, tiles being a multiple of 8, start at a
+        // multiple of 8: the index within the frame has the launch's low three bits, so the pairing holds frame by frame.
         const unsigned tiles = gridDim.x * gridDim.y;
-        if ((tiles & 7u) == 0u && gridDim.z == 3u) {
-            const unsigned L = bx + gridDim.x * (by + gridDim.y * bz);
+        const unsigned frame = bz / 3u;
+        unsigned comp = bz - 3u * frame;
+        if ((tiles & 7u) == 0u) {
+            const unsigned L = bx + gridDim.x * (by + gridDim.y * comp);      // linear index within the frame
             const unsigned tile = (L / 24u) * 8u + (L & 7u);
-            bz = (L >> 3) % 3u;
+            comp = (L >> 3) % 3u;
             bx = tile % gridDim.x; by = tile / gridDim.x;
         }
+        // frame `frame`'s three planes src_z bytes after frame 0's; component comp's coefficients in plane 3 frame + comp
+        const unsigned long long fz = (unsigned long long)frame * a2.l0.src_z;
+        a2.l0.src = (const char *)a2.l0.src + fz;
+        a2.l0.src_g = (const char *)a2.l0.src_g + fz;
+        a2.l0.src_b = (const char *)a2.l0.src_b + fz;
+        a2.l0.src_z = 0; a2.l1.src_z = 0;
+        dwt_fwd_select_frame(a2.l0, 3u * frame + comp);
+        dwt_fwd_select_frame(a2.l1, 3u * frame + comp);
+        bz = comp;                                           // (dwt_fwd2_band: the row of the colour transform)
+    } else {
+        dwt_fwd_select_frame(a2.l0, bz);
+        dwt_fwd_select_frame(a2.l1, bz);
     }
     const int strip = (int)bx * 4 + wave;
-    dwt_fwd_select_frame(a2.l0, bz);
-    dwt_fwd_select_frame(a2.l1, bz);
     // the wave's 256 columns start at strip * kF2Useful - 4 * kF2Edge: does it hold column 0 or W - 4?
     const int first = strip * kF2Useful - 4 * kF2Edge;
     // The second instantiation, for the strips that hold neither: no mirror selects, and the neighbour reads fold into
@@ -1383,12 +1399,22 @@ __device__ __forceinline__ void store_rgb_row4(uint8_t *dr, uint8_t *dg, uint8_t
 #ifndef PICSONG_DWT_INV_RGB_WAVES
 #define PICSONG_DWT_INV_RGB_WAVES 3
 #endif
+// frame blockIdx.z of the fused RGB tails (picsong_decode_rgb_frames): its three components are planes 3 z .. 3 z + 2 of
+// the plan's arrays, its pixel planes a.u8_z bytes after frame z - 1's (scalar arithmetic; z = 0: nothing moves)
+__device__ __forceinline__ void inv_rgb_select_frame(DwtInvArgs &a, uint8_t *&dr, uint8_t *&dg, uint8_t *&db)
+{
+    const unsigned long long z = blockIdx.z;
+    a.mallat = (const int32_t *)((const char *)a.mallat + 3ull * z * a.mallat_z);
+    a.ll = (const char *)a.ll + 3ull * z * a.ll_z;
+    dr += z * a.u8_z; dg += z * a.u8_z; db += z * a.u8_z;
+}
 template <int BAND>
 __global__ __launch_bounds__(256, PICSONG_DWT_INV_RGB_WAVES) void dwt_inv_rgb_kernel(DwtInvArgs a, uint8_t *dr, uint8_t *dg, uint8_t *db)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int strip = blockIdx.x * 4 + wave;
     if (strip * kStripUseful >= a.W) return;
+    inv_rgb_select_frame(a, dr, dg, db);
     const int c0 = strip * kStripUseful - 4 * kEdgeLanes + 4 * lane;
     const int pc = c0 >> 1;
     const int hW = a.W >> 1, hH = a.H >> 1;
@@ -1769,6 +1795,7 @@ __global__ __launch_bounds__(192, PICSONG_DWT_INV97_WAVES) void dwt_inv97_rgb_ke
     const int strip = blockIdx.x;
     if (strip * kStripUseful >= a.W) return;                 // (the whole workgroup: one strip)
     if (threadIdx.x == 0) again_any = 0;
+    inv_rgb_select_frame(a, dr, dg, db);
     a.mallat = (const int32_t *)((const char *)a.mallat + (unsigned long long)comp * a.mallat_z);
     a.ll = (const char *)a.ll + (unsigned long long)comp * a.ll_z;
     Rgb97Out o;

@@ -185,6 +185,14 @@ inline BpcLaunch select_decoder(bool cp3, bool bulk, bool compact, bool from_str
     if (from_stream) return bpc_launch(bpc_decode_kernel<false, kDecSmallPlanes, true>, kBpcDecWgWaves, waves);
     return bpc_launch(bpc_decode_kernel<false, kDecSmallPlanes>, kBpcDecWgWaves, waves);
 }
+// The planes of an RGB launch (component z % 3 of frame z / 3, table z % 3): a plane's waves_per_frame for wpf codeblock
+// pairs -- k = 0: whole workgroups, so that a workgroup (its LDS table copy) never spans two planes; -k > 0 (one-wave
+// workgroups): exactly its waves.
+inline int rgb_component_waves(bool bulk, int wpf)
+{
+    static_assert(kBpcEncWgWaves == kBpcDecWgWaves, "one layout serves the launches of both directions");
+    return bulk ? wpf : (wpf + kBpcEncWgWaves - 1) / kBpcEncWgWaves * kBpcEncWgWaves;
+}
 // the dwords of plane scratch a coder launch of `waves` waves needs (what a caller sizes BpcArgs::plane_scratch by)
 inline size_t encoder_scratch_dwords(bool cp3, bool bulk, unsigned waves) { return select_encoder(cp3, bulk, false, waves).scratch_dwords; }
 inline size_t decoder_scratch_dwords(bool cp3, bool bulk, unsigned waves) { return select_decoder(cp3, bulk, false, false, false, waves).scratch_dwords; }
@@ -319,6 +327,44 @@ inline const char *layout_refusal(int layout, const void *data, size_t pitch, si
     }
     if (n > 1 && frame_stride < span) return "frame_stride smaller than a frame";
     if (n > 1 && padded_stride < (size_t)layout_planes(layout) * (size_t)AW * (size_t)AH) return "padded_stride smaller than a frame's padded planes";
+    return nullptr;
+}
+// What picsong_encode_rgb_frames / picsong_decode_rgb_frames refuse, as a message; nullptr: the arguments are fine.
+// n RGB frames a call, 3 n planes a launch (the batched grid takes 64): r / g / b frame 0's padded planes of P bytes,
+// frame f's frame_stride bytes after them; the streams stream_stride shorts apart, a worst-case one max_stream shorts.
+// same_geometry: the three component tables agree in geometry (the coder launch has one LutGeo).
+constexpr int kRgbMaxFrames = 21;
+inline const char *rgb_frames_refusal(bool ctx_rgb, int cp, bool same_geometry, int n, const void *r, const void *g, const void *b,
+                                      const void *streams, size_t frame_stride, size_t stream_stride, size_t P, size_t max_stream)
+{
+    if (!r || !g || !b || !streams) return "null pointer";
+    if (!ctx_rgb) return "the context is not an RGB one";
+    if (cp == 3) return "-cp 3 codes its planes one by one";
+    if (n < 1 || n > kRgbMaxFrames) return "n outside 1..21";
+    if (stream_stride < max_stream) return "stream stride smaller than a worst-case codestream";
+    if (!same_geometry) return "the components' tables differ in geometry: code the planes one by one";
+    if (n > 1) {
+        if (frame_stride < P) return "frame_stride smaller than a padded plane";
+        // plane x of frame f against plane y of frame f + d: the starts (y - x) + d * frame_stride apart, P bytes each
+        const uintptr_t pl[3] = { (uintptr_t)r, (uintptr_t)g, (uintptr_t)b };
+        for (int d = 1; d < n; d++)
+            for (int x = 0; x < 3; x++)
+                for (int y = 0; y < 3; y++) {
+                    const long long gap = (long long)(pl[y] - pl[x]) + (long long)d * (long long)frame_stride;
+                    if (gap > -(long long)P && gap < (long long)P) return "frame_stride makes a frame's planes overlap the next frame's";
+                }
+    }
+    return nullptr;
+}
+// ... and picsong_encode_rgb_images / picsong_decode_rgb_images, ahead of the check above: everything layout_refusal
+// refuses (the padded side is the context's own buffer, 3 P bytes a frame), a grey layout, n beyond 21
+inline const char *rgb_images_refusal(int layout, const void *data, size_t pitch, size_t plane_stride, size_t frame_stride, int n, int W,
+                                      int H, int AW, int AH)
+{
+    if (n < 1 || n > kRgbMaxFrames) return "n outside 1..21";
+    const size_t P = (size_t)AW * (size_t)AH;
+    if (const char *why = layout_refusal(layout, data, pitch, plane_stride, frame_stride, data, 3 * P, n, W, H, AW, AH)) return why;
+    if (layout == kLayoutGrey8) return "a grey layout on an RGB call";
     return nullptr;
 }
 // The launch: grid.x = the row batches of a plane (layout_rows), grid.y = the planes of a planar layout, grid.z = frame;

@@ -101,35 +101,42 @@ inline void plan_frame_strides(std::vector<FwdLaunch> &plan, unsigned long long 
 // its c16 choice (head_c16: the fused head is the frame paths' 16-bit one and wants such a plan) or the rate calls'
 // plan_dwt_forward_unit (the 32-bit float head, select_fwd2_rgb_f32).
 // fuse (the caller's switches: planes 16-byte aligned, no PICSONG_RGB_NOFUSE, its c16 choice): the colour transform in
-// the head's load stage -- the head reads the three u8 planes and delivers component blockIdx.z, no component plane is
+// the head's load stage -- the head reads the three u8 planes and delivers component blockIdx.z % 3, no component plane is
 // ever written (the separate transform kernel reads 100 MB and writes 400 MB of them per 8K frame, and level 0 reads
-// them back).  Else, or where plan_dwt_fwd2 refuses: the colour transform into `planes` (three of P samples), then the
-// levels of all three per launch.  *c16: the coefficient form delivered; *fused: the first form ran.
+// them back).  Else, or where plan_dwt_fwd2 refuses: the colour transform into `planes` (three of P samples a frame),
+// then the levels of all planes per launch.  *c16: the coefficient form delivered; *fused: the first form ran.
+// n frames (picsong_encode_rgb_frames): frame f's planes frame_stride bytes after frame f - 1's, its component k's
+// coefficients in plane 3 f + k; every launch but the separate colour transform's (one a frame) covers the 3 n planes.
 template <class Go, class PlanOf>
 int rgb_forward_transform(const Go &go, bool lossy, bool fuse, PlanOf plan_of, bool head_c16, const uint8_t *r, const uint8_t *g,
                           const uint8_t *b, void *planes, size_t P, int off, unsigned long long coef_z, bool *c16 = nullptr,
-                          bool *fused = nullptr)
+                          bool *fused = nullptr, unsigned n = 1, unsigned long long frame_stride = 0)
 {
     if (fused) *fused = false;
+    if (n <= 1) frame_stride = 0;
     if (fuse) {
         std::vector<FwdLaunch> plan = plan_of(r, true);
-        plan_frame_strides(plan, 0, coef_z);                 // level 0: every component reads the three planes
+        plan_frame_strides(plan, frame_stride, coef_z);      // level 0: every component of a frame reads its three planes
         plan[0].a.src_g = g; plan[0].a.src_b = b;
         Fwd2Launch f2;
         if (plan_is_c16(plan) == head_c16 && plan_dwt_fwd2(plan, f2, true, lossy, kF2PairsRgb)) {
             // (RCT on the integer head, ICT on the 9/7 ones)
-            if (int rc = go(head_c16 ? select_fwd2(lossy, true, true) : select_fwd2_rgb_f32(), dim3(f2.gx, f2.gy, 3u), 256u, f2.a)) return rc;
+            if (int rc = go(head_c16 ? select_fwd2(lossy, true, true) : select_fwd2_rgb_f32(), dim3(f2.gx, f2.gy, 3u * n), 256u, f2.a)) return rc;
             if (c16) *c16 = head_c16;
             if (fused) *fused = true;
-            return launch_fwd_levels(go, lossy, plan, 2, 3u);
+            return launch_fwd_levels(go, lossy, plan, 2, 3u * n);
         }
     }
     char *p = (char *)planes;
-    if (int rc = rgb_forward(go, lossy, r, g, b, p, p + P * 4, p + 2 * P * 4, P / 4, off)) return rc;
+    for (unsigned f = 0; f < n; f++) {
+        char *q = p + (size_t)f * 3 * P * 4;
+        const size_t at = (size_t)f * (size_t)frame_stride;
+        if (int rc = rgb_forward(go, lossy, r + at, g + at, b + at, q, q + P * 4, q + 2 * P * 4, P / 4, off)) return rc;
+    }
     std::vector<FwdLaunch> plan = plan_of(planes, false);
     if (c16) *c16 = plan_is_c16(plan);
     plan_frame_strides(plan, (unsigned long long)P * 4ull, coef_z);
-    return launch_fwd_levels(go, lossy, plan, 0, 3u);
+    return launch_fwd_levels(go, lossy, plan, 0, 3u * n);
 }
 
 // ---- synthesis.  The first n levels of a plan (plan_inverse_frames), one launch each
@@ -162,14 +169,18 @@ inline bool inv_rgb_tail_ok(const std::vector<InvLaunch> &plan, bool lossy)
 {
     return plan_inv_is_c16(plan) && plan.size() >= 2 && plan.back().vec && (!lossy || plan.back().fast);
 }
+// n frames (picsong_decode_rgb_frames; the plan over 3 n planes): grid.z = 3 n above the finest level, = frame in the tail,
+// frame f's pixel planes frame_stride bytes after frame f - 1's
 template <class Go>
-int run_inverse_rgb(const Go &go, bool lossy, bool lean97, const std::vector<InvLaunch> &plan, int off, uint8_t *r, uint8_t *g, uint8_t *b)
+int run_inverse_rgb(const Go &go, bool lossy, bool lean97, const std::vector<InvLaunch> &plan, int off, uint8_t *r, uint8_t *g, uint8_t *b,
+                    unsigned n = 1, unsigned long long frame_stride = 0)
 {
-    if (int rc = launch_inv_levels(go, lossy, lean97, plan, plan.size() - 1, 3u)) return rc;
+    if (int rc = launch_inv_levels(go, lossy, lean97, plan, plan.size() - 1, 3u * n)) return rc;
     DwtInvArgs fa = plan.back().a;
     fa.off = off;
+    fa.u8_z = n > 1 ? frame_stride : 0;
     const InvRgbLaunch l = select_inv_rgb(lossy, plan.back());
-    return go(l.kernel, dim3(l.gx, l.gy, 1), l.threads, fa, r, g, b);
+    return go(l.kernel, dim3(l.gx, l.gy, n), l.threads, fa, r, g, b);
 }
 
 // ---- the windowed synthesis (window_kernels.hpp) of `frames` frames, grid.z = frame: frame z's coefficients at coef_i +
@@ -244,16 +255,28 @@ int widen_staging(const Go &go, const uint16_t *staging16, const int32_t *sizes,
 // ---- the pack of n frames' codeblocks, frame after frame in w (sizes, offsets, totals) and in the staging (P words a
 // frame): the header argument, the scan of the lengths, the copy into streams `stream_stride` shorts apart.
 // W: uint16_t = the encoders' own staging (the frame paths), int32_t = a caller's array (picsong_bitstream_pack)
-// h_header != nullptr: the populated header, on the frames `has` names (HeaderArg::has, pack_kernels.hpp)
+// h_header != nullptr: the populated header, on the frames `has` and `base` name (HeaderArg, pack_kernels.hpp)
 template <typename W, class Go>
 int pack_frames(const Go &go, const W *staging, const Workspace &w, int ncb, unsigned n, const uint16_t *h_header, int has,
-                uint16_t *streams, size_t P, size_t stream_stride)
+                uint16_t *streams, size_t P, size_t stream_stride, int base = 0)
 {
     HeaderArg h;
     memset(&h, 0, sizeof h);
-    if (h_header) { memcpy(h.h, h_header, sizeof h.h); h.has = has; }
+    if (h_header) { memcpy(h.h, h_header, sizeof h.h); h.has = has; h.base = base; }
     if (int rc = go(scan_sizes_kernel, dim3(n), scan_threads(ncb), w.sizes, ncb, w.offsets, w.total)) return rc;
     return go(pack_kernel<W>, dim3(pack_blocks<W>(ncb), n), 256u, staging, w.sizes, w.offsets, w.total, ncb, h, streams, P, stream_stride);
+}
+
+// the pack of n RGB frames' 3 n planes (picsong_encode_rgb_frames): the populated header h_header on the components
+// header_mask names (bits 0..2) of the frame f with first_iter + f == 0, where the call holds it; none anywhere else
+template <class Go>
+int pack_rgb_frames(const Go &go, const uint16_t *staging, const Workspace &w, int ncb, unsigned n, const uint16_t *h_header,
+                    int first_iter, int header_mask, uint16_t *streams, size_t P, size_t stream_stride)
+{
+    const int f0 = -first_iter;
+    const bool has0 = f0 >= 0 && f0 < (int)n && (header_mask & 7) != 0;
+    return pack_frames(go, staging, w, ncb, 3u * n, has0 ? h_header : nullptr, -(header_mask & 7), streams, P, stream_stride,
+                       has0 ? 3 * f0 : 0);
 }
 
 // ---- distortion (quality_kernels.hpp): out[0 .. n) = the SSE over the visible w x h samples of n pairs of padded

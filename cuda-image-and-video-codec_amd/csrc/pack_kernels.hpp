@@ -19,7 +19,9 @@
 
 namespace picsong {
 
-struct HeaderArg { uint16_t h[9]; int has; };
+// has > 0: frame has - 1 of the launch carries the populated header; has = 0: none; has < 0: -has is a bit mask over the
+// three planes base .. base + 2 (the components of ONE RGB frame of a launch over 3 n planes; base = 0: a lone frame's)
+struct HeaderArg { uint16_t h[9]; int has; int base; };
 
 // offsets[cb] = sum_{i<cb} (sizes[i] - 1); *total = 9 + 2n + sum(sizes - 1) + 1
 // (BitStreamBuilder.cu:300-305).  One block of 1024 threads per frame (blockIdx.x = frame of a batched
@@ -93,7 +95,7 @@ __global__ __launch_bounds__(1024) void scan_sizes_kernel(const int32_t *sizes, 
 // one codeblock per workgroup (W = int32_t) or per WAVE (W = uint16_t); buildBitStreamLUTBS BitStreamBuilder.cu:106-137
 // layout; blockIdx.y = frame of a batched launch (staging advances by frame_words, sizes / offsets by n, total by 1, out by
 // out_stride shorts; only the frame hdr.has - 1 == blockIdx.y carries the populated header -- has = 0: none;
-// has < 0: -has is a bit mask of the frames that carry it (the components of an RGB frame))
+// has < 0: -has is a bit mask over the planes hdr.base .. hdr.base + 2 (the components of an RGB frame))
 // W = the staging's word: uint16_t, the encoders' own (BpcArgs::staging16: the frame paths), or int32_t, the reference's
 // array as a caller of picsong_bitstream_pack holds it
 constexpr int kPack16Waves = 4;                            // 16-bit staging: codeblocks (waves) a workgroup
@@ -114,7 +116,8 @@ __global__ __launch_bounds__(256) void pack_kernel(const W *staging, const int32
     {
         const size_t f = blockIdx.y;
         staging += f * frame_words; sizes += f * (size_t)n; offsets += f * (size_t)n; total += f; out += f * out_stride;
-        hdr.has = hdr.has < 0 ? (int)(((unsigned)(-hdr.has) >> f) & 1u) : ((hdr.has != 0 && (size_t)(hdr.has - 1) == f) ? 1 : 0);
+        const size_t r = f - (size_t)hdr.base;              // (a plane before `base` wraps far above 2)
+        hdr.has = hdr.has < 0 ? (r < 3u ? (int)(((unsigned)(-hdr.has) >> r) & 1u) : 0) : ((hdr.has != 0 && (size_t)(hdr.has - 1) == f) ? 1 : 0);
     }
     const W *st = staging + (size_t)cb * 4096u;
     const int len = sizes[cb];

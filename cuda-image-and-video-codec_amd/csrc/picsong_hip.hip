@@ -1374,11 +1374,7 @@ int picsong_decode_plane(picsong_ctx *c, const uint16_t *d_stream, int comp, voi
 // The three component tables of an RGB context for ONE coder grid: same geometry, every frame f of the batched
 // launch coding with table f; k = 0: a component's waves_per_frame are whole workgroups; -k > 0 (one-wave workgroups):
 // exactly its waves.
-static int rgb_component_waves(const BpcArgs &a, int wpf)
-{
-    static_assert(kBpcEncWgWaves == kBpcDecWgWaves, "one layout serves the launches of both directions");
-    return a.k > 0.0f ? wpf : (wpf + kBpcEncWgWaves - 1) / kBpcEncWgWaves * kBpcEncWgWaves;
-}
+static int rgb_component_waves(const BpcArgs &a, int wpf) { return picsong::rgb_component_waves(a.k > 0.0f, wpf); }
 static int bpc_args_rgb(picsong_ctx *c, BpcArgs &a)
 {
     int rc = bpc_args(c, a, 0);
@@ -1473,8 +1469,8 @@ enum SearchKind { kSearchSize, kSearchQuality };
 
 static int search_candidates(const picsong_ctx *c, SearchKind kind)
 {
-    // an RGB frame's coder launch maps frame f to table f for its three components only: a size search codes one
-    // candidate a round there (a quality search's probes launch no coder)
+    // an RGB frame's size search codes one candidate a round (a quality search's probes launch no coder): the coder launch
+    // maps plane z to table z % 3 since the batched RGB calls, so several candidates a round are possible; left as it was
     if (kind == kSearchSize && c->p.is_rgb) return 1;
     if (const char *e = getenv("PICSONG_RATE_K")) if (atoi(e) == 1) return 1;
     return kRateMaxK;
@@ -2209,6 +2205,130 @@ int picsong_decode_rgb_image(picsong_ctx *c, const uint16_t *d_streams, size_t s
     if (int rc = picsong_decode_rgb_frame(c, d_streams, stream_stride, c->lay_buf, c->lay_buf + c->P, c->lay_buf + 2 * c->P, stream)) return rc;
     return emit_frames(HipGo{ (hipStream_t)stream }, dst->layout, c->lay_buf, 0, dst->data, dst->pitch, dst->plane_stride, 0, 1,
                        c->p.width, c->p.height, c->aw, c->ah);
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched RGB frames: n colour frames through ONE launch per stage, 3 n planes a launch -- plane z = component z % 3 of
+// frame z / 3 (the sequences: rgb_forward_transform and run_inverse_rgb with n, launch_seq.hpp; the argument check:
+// rgb_frames_refusal, kernel_select.hpp).  n = 1 launches what picsong_encode_rgb_frame / picsong_decode_rgb_frame launch.
+// ---------------------------------------------------------------------------------------------
+static int rgb_frames_args(picsong_ctx *c, int n, const void *r, const void *g, const void *b, const void *streams, size_t frame_stride,
+                           size_t stream_stride, const char *who, BpcArgs &a)
+{
+    if (!c) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (const char *why = rgb_frames_refusal(c->p.is_rgb != 0, c->p.cp, true, n, r, g, b, streams, frame_stride, stream_stride, c->P,
+                                             picsong_max_stream_shorts(c->aw, c->ah)))
+        return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+    if (int rc = bpc_args_rgb(c, a)) return rc;             // (the tables' geometry)
+    a.frames = 3 * n;
+    return PICSONG_OK;
+}
+
+int picsong_encode_rgb_frames(picsong_ctx *c, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, size_t frame_stride,
+                              int first_iter, int header_mask, uint16_t *d_streams, size_t stream_stride, void *stream)
+{
+    BpcArgs a;
+    int rc = rgb_frames_args(c, n, d_r, d_g, d_b, d_streams, frame_stride, stream_stride, "encode_rgb_frames", a);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const unsigned np = 3u * (unsigned)n;
+    if ((rc = ensure_batch(c, (int)np))) return rc;
+    if ((rc = ensure_coef_i(c, (int)np))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t coef_z = (c->P + c->extra) * 4;
+    const bool lossy = c->p.lossy != 0;
+    // (the fused head: all three planes 16-byte aligned, and every frame's with them)
+    const bool fuse = c->c16 && rgb_planes_aligned(d_r, d_g, d_b) && (n == 1 || (frame_stride & 15u) == 0) && !getenv("PICSONG_RGB_NOFUSE");
+    auto plan_of = [c](const void *src, bool u8in) { return plan_dwt_forward(src, u8in, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16); };
+    bool c16 = false;
+    if ((rc = picsong::rgb_forward_transform(HipGo{ s }, lossy, fuse, plan_of, true, d_r, d_g, d_b, c->batch.coef_i, c->P, level_off(c), coef_z,
+                                             &c16, nullptr, (unsigned)n, frame_stride))) return rc;
+    a.c16 = c16 ? 1 : 0;
+    // ---- coder: one grid over the 3 n planes' codeblock pairs, plane z with table z % 3
+    a.coeffs_in = c->batch.coef; a.is_float = lossy ? 1 : 0;
+    a.staging16 = reinterpret_cast<uint16_t *>(c->batch.staging);
+    a.sizes = c->batch.sizes; a.plane_scratch = c->batch.plane_scratch; a.coef_z = coef_z;
+    if ((rc = launch_encoder(c, a, np * (unsigned)a.waves_per_frame, 0, 3, s))) return rc;
+    // ---- pack: the populated header on the components of header_mask, on the video's frame 0 where the call holds it
+    uint16_t hdr[PICSONG_HDR_SHORTS];
+    picsong_header_pack(&c->p, hdr);
+    if ((rc = pack_rgb_frames(HipGo{ s }, a.staging16, c->batch, c->ncb, (unsigned)n, hdr, first_iter, header_mask, d_streams, c->P,
+                              stream_stride))) return rc;
+    c->last_batch = (int)np;
+    return PICSONG_OK;
+}
+
+int picsong_decode_rgb_frames(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_r, uint8_t *d_g,
+                              uint8_t *d_b, size_t frame_stride, void *stream)
+{
+    BpcArgs a;
+    int rc = rgb_frames_args(c, n, d_r, d_g, d_b, d_streams, frame_stride, stream_stride, "decode_rgb_frames", a);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const unsigned np = 3u * (unsigned)n;
+    if (n == 1) frame_stride = 0;
+    if ((rc = ensure_batch(c, (int)np))) return rc;
+    if ((rc = ensure_coef_i(c, (int)np))) return rc;
+    c->last_batch = -1;
+    hipStream_t s = (hipStream_t)stream;
+    const bool lossy = c->p.lossy != 0, direct = dec_from_stream(c);
+    if ((rc = stream_intake(c, d_streams, np, stream_stride, direct, c->batch, s))) return rc;
+    const std::vector<InvLaunch> plan = inverse_plan(c, c->batch.coef_i, c->batch.coef, nullptr, nullptr, np, 0, c->c16_dec && direct, true, 0);
+    const bool c16 = plan_inv_is_c16(plan);
+    a.coef_z = (unsigned long long)c->P * (c16 ? 2ull : 4ull);
+    if ((rc = launch_decoder(c, a, np * (unsigned)a.waves_per_frame, a.k > 0.0f && bulk_compact(c, 0, 3), c->batch,
+                             direct ? d_streams : nullptr, stream_stride, c16, s))) return rc;
+    // the fused tails (grid.z = frame) where picsong_decode_rgb_frame takes them and every frame's planes are 4-byte aligned
+    const bool px_aligned = ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b) | frame_stride) & 3u) == 0;
+    bool tail = inv_rgb_tail_ok(plan, lossy) && px_aligned && !getenv("PICSONG_RGB_NOFUSE");
+    if (tail && lossy) tail = !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0);
+    if (tail) return run_inverse_rgb(HipGo{ s }, lossy, lean97_levels(), plan, level_off(c), d_r, d_g, d_b, (unsigned)n, frame_stride);
+    if ((rc = run_inverse(c, plan, s, np))) return rc;
+    const size_t z = (c->P + c->extra) * 4;
+    for (int f = 0; f < n; f++) {                           // the separate inverse colour transform: one launch a frame
+        const char *img = (const char *)plan.back().a.dst + (size_t)(3 * f) * z;
+        const size_t at = (size_t)f * frame_stride;
+        if ((rc = rgb_inverse(HipGo{ s }, lossy, img, img + z, img + 2 * z, d_r + at, d_g + at, d_b + at, c->P / 4, level_off(c)))) return rc;
+    }
+    return PICSONG_OK;
+}
+
+static int rgb_images_args(picsong_ctx *c, int n, const picsong_image *img, size_t frame_stride, const void *d_streams, size_t stream_stride,
+                           const char *who, BpcArgs &a)
+{
+    if (!c || !img || !d_streams) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (const char *why = rgb_images_refusal(img->layout, img->data, img->pitch, img->plane_stride, frame_stride, n, c->p.width, c->p.height,
+                                             c->aw, c->ah))
+        return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+    // (the padded side is the context's buffer, allocated later: any non-null address P bytes apart stands for its planes)
+    const uint8_t *stand_in = (const uint8_t *)(uintptr_t)4096;
+    return rgb_frames_args(c, n, stand_in, stand_in + c->P, stand_in + 2 * c->P, d_streams, 3 * c->P, stream_stride, who, a);
+}
+
+int picsong_encode_rgb_images(picsong_ctx *c, int n, const picsong_image *src, size_t frame_stride, int first_iter, int header_mask,
+                              uint16_t *d_streams, size_t stream_stride, void *stream)
+{
+    BpcArgs a;
+    if (int rc = rgb_images_args(c, n, src, frame_stride, d_streams, stream_stride, "encode_rgb_images", a)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_layout(c, (size_t)3 * (size_t)n)) return rc;
+    if (int rc = ingest_frames(HipGo{ (hipStream_t)stream }, src->layout, src->data, src->pitch, src->plane_stride, frame_stride, c->lay_buf,
+                               3 * c->P, n, c->p.width, c->p.height, c->aw, c->ah)) return rc;
+    return picsong_encode_rgb_frames(c, n, c->lay_buf, c->lay_buf + c->P, c->lay_buf + 2 * c->P, 3 * c->P, first_iter, header_mask, d_streams,
+                                     stream_stride, stream);
+}
+
+int picsong_decode_rgb_images(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, const picsong_image *dst,
+                              size_t frame_stride, void *stream)
+{
+    BpcArgs a;
+    if (int rc = rgb_images_args(c, n, dst, frame_stride, d_streams, stream_stride, "decode_rgb_images", a)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_layout(c, (size_t)3 * (size_t)n)) return rc;
+    if (int rc = picsong_decode_rgb_frames(c, n, d_streams, stream_stride, c->lay_buf, c->lay_buf + c->P, c->lay_buf + 2 * c->P, 3 * c->P,
+                                           stream)) return rc;
+    return emit_frames(HipGo{ (hipStream_t)stream }, dst->layout, c->lay_buf, 3 * c->P, dst->data, dst->pitch, dst->plane_stride, frame_stride,
+                       n, c->p.width, c->p.height, c->aw, c->ah);
 }
 
 int picsong_pad_frame_host(const uint8_t *in, int w, int h, uint8_t *out, int aw, int ah)

@@ -108,7 +108,8 @@ void help()
         " -gpus N             video coding: groups of frames sharded round-robin over devices D .. D+N-1 of this node\n"
         "                     (--devices a,b,c names them explicitly); every device copies its codestreams to the\n"
         "                     writer's pinned ring over its own host link, the output file is the 1-GPU file\n"
-        " -framesPerLaunch B  frames coded / decoded per launch (default: 4 up to 4K frames, 1 above)\n"
+        " -framesPerLaunch B  frames coded / decoded per launch (default: 4 up to 4K frames, 1 above; an RGB video:\n"
+        "                     the same rule on a frame's three planes, at most 21)\n"
         " --lut-fill V        value of LUT entries the loader never writes (default 0)\n"
         " -reduce r           decoding: the image at 1/2^r of its size, r in 0..wl-1 (resolution reduction)\n"
         " -window x,y,w,h     decoding: only the w x h rectangle at (x, y) of the image (at 1/2^r with -reduce r), from the\n"
@@ -392,6 +393,71 @@ std::string search_step(const Options &o, picsong_ctx *ctx, hipStream_t s, const
     return std::string();
 }
 
+// ---- frames a call of an RGB video (-framesPerLaunch B, else the grey path's rule on a frame's three planes), at most the
+// 21 a call of picsong_encode_rgb_frames / picsong_decode_rgb_frames takes and the frames there are
+int rgb_group_frames(const Options &o, size_t P, long nframes)
+{
+    long B = o.frames_per_launch > 0 ? o.frames_per_launch : (3 * P <= (size_t)3840 * 2176 ? 4 : 1);
+    if (B > 21) B = 21;
+    if (B > nframes) B = nframes;
+    return (int)(B < 1 ? 1 : B);
+}
+
+// The frames [f0, nframes) of an RGB video (-cp 2) in groups of B through ONE call each: picsong_encode_rgb_frames on
+// host-padded planes, or, -layout, picsong_encode_rgb_images on the frames as the file holds them -- one pinned staging
+// area and one upload a group, one read-back of the group's 3 n streams.  Streams and _SIZE entries as frame by frame.
+void encode_rgb_groups(const Options &o, picsong_ctx *ctx, hipStream_t s, std::ifstream &in, size_t file_base, long f0, long nframes,
+                       std::ofstream &out, std::ofstream &sizes, long &total_shorts)
+{
+    const int aw = picsong_pad_dim(o.x), ah = picsong_pad_dim(o.y);
+    const size_t P = (size_t)aw * ah, max_shorts = picsong_max_stream_shorts(aw, ah);
+    const int B = rgb_group_frames(o, P, nframes - f0);
+    const size_t raw_bytes = o.layout >= 0 ? layout_frame_bytes(o.layout, o.x, o.y) : 0;
+    const size_t frame_bytes = o.layout >= 0 ? raw_bytes : 3 * P;        // a frame of the staging area
+    uint8_t *h_in = nullptr, *d_in = nullptr;
+    uint16_t *h_out = nullptr, *d_out = nullptr;
+    HIPCK(hipHostMalloc(&h_in, frame_bytes * (size_t)B));
+    HIPCK(hipMalloc(&d_in, frame_bytes * (size_t)B));
+    HIPCK(hipHostMalloc(&h_out, max_shorts * 2 * 3 * (size_t)B));
+    HIPCK(hipMalloc(&d_out, max_shorts * 2 * 3 * (size_t)B));
+    std::vector<uint8_t> raw((size_t)o.x * o.y);
+    std::vector<int> totals(3 * (size_t)B);
+    for (long f = f0; f < nframes; f += B) {
+        const int n = (int)std::min<long>(B, nframes - f);
+        if (o.layout >= 0) {
+            in.clear();
+            in.seekg((std::streamoff)(file_base + (size_t)f * raw_bytes));
+            in.read(reinterpret_cast<char *>(h_in), (std::streamsize)(raw_bytes * (size_t)n));
+            if ((size_t)in.gcount() != raw_bytes * (size_t)n) die("Input file is shorter than the requested frames.");
+        } else {
+            for (int j = 0; j < 3 * n; j++) {
+                if (!read_frame(in, file_base, (size_t)(f * 3 + j), o.x, o.y, raw.data())) die("Input file is shorter than the requested frames.");
+                CK(picsong_pad_frame_host(raw.data(), o.x, o.y, h_in + (size_t)j * P, aw, ah));
+            }
+        }
+        HIPCK(hipMemcpyAsync(d_in, h_in, frame_bytes * (size_t)n, hipMemcpyHostToDevice, s));
+        if (o.layout >= 0) {
+            const picsong_image im = layout_image(o.layout, d_in, o.x, o.y);
+            CK(picsong_encode_rgb_images(ctx, n, &im, raw_bytes, (int)f, 7, d_out, max_shorts, s));
+        } else {
+            CK(picsong_encode_rgb_frames(ctx, n, d_in, d_in + P, d_in + 2 * P, 3 * P, (int)f, 7, d_out, max_shorts, s));
+        }
+        CK(picsong_last_totals(ctx, s, 3 * n, totals.data()));
+        size_t at = 0;                                   // the group's streams back to back in the pinned buffer
+        for (int j = 0; j < 3 * n; j++) {
+            HIPCK(hipMemcpyAsync(h_out + at, d_out + (size_t)j * max_shorts, (size_t)totals[(size_t)j] * 2, hipMemcpyDeviceToHost, s));
+            at += (size_t)totals[(size_t)j];
+        }
+        HIPCK(hipStreamSynchronize(s));                  // (h_in is free for the next group too)
+        out.write(reinterpret_cast<const char *>(h_out), (std::streamsize)(at * 2));
+        for (int j = 0; j < 3 * n; j++) {
+            if (f == 0 && j == 0) sizes << totals[(size_t)j]; else sizes << "," << totals[(size_t)j];
+            total_shorts += totals[(size_t)j];
+        }
+    }
+    (void)hipHostFree(h_in); (void)hipFree(d_in); (void)hipHostFree(h_out); (void)hipFree(d_out);
+}
+
 // ---- RGB coding (CodingEngine::runImage / runVideo, RGB branches: CodingEngine.cu:598-633,676-712,
 // 760-818,873-930): the input holds planar R, G, B planes per frame; RCT / ICT with the level shift
 // fused, then every component is coded as a frame of its own with its own LUT and appended to <o>,
@@ -430,7 +496,11 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
     std::ofstream sizes(o.output + "_SIZE", std::ios::binary | std::ios::app);
     long total_shorts = 0;
     auto t0 = std::chrono::steady_clock::now();
-    for (long f = 0; f < nframes; f++) {
+    // a video (-cp 2): groups of frames through one call each (encode_rgb_groups) -- behind the first frame where that one
+    // carries the -rate / -psnr search; an image and -cp 3: frame by frame, here
+    const bool grouped = o.video && batched;
+    const long nloop = grouped ? ((o.has_rate || o.has_psnr) ? 1 : 0) : nframes;
+    for (long f = 0; f < nloop; f++) {
         if (o.layout >= 0) {
             in.clear();
             in.seekg((std::streamoff)(file_base + (size_t)f * raw_bytes));
@@ -475,6 +545,7 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
             total_shorts += total;
         }
     }
+    if (grouped && nloop < nframes) encode_rgb_groups(o, ctx, s, in, file_base, nloop, nframes, out, sizes, total_shorts);
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::cout << "The time spent with the app without considering allocation periods is: " << sec << std::endl;
     if (o.has_rate) rate_report_achieved(o, total_shorts, nframes);
@@ -953,6 +1024,67 @@ void write_pgm(const std::string &path, const uint8_t *pix, int w, int h, int bi
 // (x, y) of the image at 1/2^r, rows pw = w bytes apart (ph = h).
 struct OutDims { int r, w, h, pw, ph, win = 0, x = 0, y = 0; };
 
+// The frames of an RGB video (-cp 2, full size) in groups of B through ONE call each: picsong_decode_rgb_frames into padded
+// planes, cropped on the host, or, -layout, picsong_decode_rgb_images into the frames as the file takes them -- one pinned
+// staging area, one upload and one read-back a group.  The output as frame by frame.
+void decode_rgb_groups(const Options &o, const picsong_params &p, picsong_ctx *ctx, hipStream_t s, std::ifstream &in,
+                       const std::vector<long> &shorts, long nframes, int aw, int ah)
+{
+    const size_t P = (size_t)aw * ah, max_shorts = picsong_max_stream_shorts(aw, ah);
+    Options og = o;
+    og.x = p.width; og.y = p.height;
+    const int B = rgb_group_frames(og, P, nframes);
+    const size_t raw_bytes = o.layout >= 0 ? layout_frame_bytes(o.layout, p.width, p.height) : 0;
+    const size_t frame_bytes = o.layout >= 0 ? raw_bytes : 3 * P;        // a frame of the pixel side
+    uint16_t *h_in = nullptr, *d_in = nullptr;
+    uint8_t *h_pix = nullptr, *d_pix = nullptr;
+    HIPCK(hipHostMalloc(&h_in, max_shorts * 2 * 3 * (size_t)B));
+    HIPCK(hipMalloc(&d_in, max_shorts * 2 * 3 * (size_t)B));
+    HIPCK(hipHostMalloc(&h_pix, frame_bytes * (size_t)B));
+    HIPCK(hipMalloc(&d_pix, frame_bytes * (size_t)B));
+    std::vector<uint8_t> crop((size_t)p.width * p.height);
+    std::ofstream out(o.output, std::ios::binary | std::ios::app);
+    size_t pos = 0;
+    for (long f = 0; f < nframes; f += B) {
+        const int n = (int)std::min<long>(B, nframes - f);
+        // the group's 3 n streams are consecutive in the file: one read, a copy each to its place on the device
+        size_t group = 0;
+        for (int j = 0; j < 3 * n; j++) {
+            const size_t len = (size_t)shorts[(size_t)(f * 3 + j)];
+            if (len > max_shorts) die("Component codestream longer than the maximum for this geometry.");
+            group += len;
+        }
+        in.clear();
+        in.seekg((std::streamoff)(pos * 2));
+        in.read(reinterpret_cast<char *>(h_in), (std::streamsize)(group * 2));
+        if ((size_t)in.gcount() != group * 2) die("Input file is shorter than its _SIZE sidecar says.");
+        pos += group;
+        size_t at = 0;
+        for (int j = 0; j < 3 * n; j++) {
+            const size_t len = (size_t)shorts[(size_t)(f * 3 + j)];
+            HIPCK(hipMemcpyAsync(d_in + (size_t)j * max_shorts, h_in + at, len * 2, hipMemcpyHostToDevice, s));
+            at += len;
+        }
+        if (o.layout >= 0) {
+            const picsong_image im = layout_image(o.layout, d_pix, p.width, p.height);
+            CK(picsong_decode_rgb_images(ctx, n, d_in, max_shorts, &im, raw_bytes, s));
+        } else {
+            CK(picsong_decode_rgb_frames(ctx, n, d_in, max_shorts, d_pix, d_pix + P, d_pix + 2 * P, 3 * P, s));
+        }
+        HIPCK(hipMemcpyAsync(h_pix, d_pix, frame_bytes * (size_t)n, hipMemcpyDeviceToHost, s));
+        HIPCK(hipStreamSynchronize(s));
+        if (o.layout >= 0) {
+            out.write(reinterpret_cast<const char *>(h_pix), (std::streamsize)(raw_bytes * (size_t)n));
+            continue;
+        }
+        for (int j = 0; j < 3 * n; j++) {
+            for (int y = 0; y < p.height; y++) memcpy(&crop[(size_t)y * p.width], h_pix + (size_t)j * P + (size_t)y * aw, (size_t)p.width);
+            out.write(reinterpret_cast<const char *>(crop.data()), (std::streamsize)crop.size());
+        }
+    }
+    (void)hipHostFree(h_in); (void)hipFree(d_in); (void)hipHostFree(h_pix); (void)hipFree(d_pix);
+}
+
 int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, std::ifstream &in,
                    const std::vector<long> &shorts, long nframes, int aw, int ah, const OutDims &od)
 {
@@ -978,7 +1110,10 @@ int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, 
     { std::ofstream trunc(o.output, std::ios::binary | std::ios::trunc); }
     auto t0 = std::chrono::steady_clock::now();
     size_t pos = 0;
-    for (long f = 0; f < nframes; f++) {
+    // a video at full size (-cp 2): groups of frames through one call each; everything else frame by frame, here
+    const bool grouped = o.video && batched && !od.win && od.r == 0;
+    if (grouped) decode_rgb_groups(o, p, ctx, s, in, shorts, nframes, aw, ah);
+    for (long f = grouped ? nframes : 0; f < nframes; f++) {
         for (int c = 0; c < 3; c++) {
             const size_t n = (size_t)shorts[(size_t)(f * 3 + c)];
             if (n > max_shorts) die("Component codestream longer than the maximum for this geometry.");

@@ -68,6 +68,7 @@ EXPORTS = [
     "picsong_encode_frames_quality", "picsong_encode_rgb_frame_quality",
     "picsong_ingest_frames", "picsong_emit_frames", "picsong_encode_images", "picsong_decode_images",
     "picsong_encode_rgb_image", "picsong_decode_rgb_image",
+    "picsong_encode_rgb_frames", "picsong_decode_rgb_frames", "picsong_encode_rgb_images", "picsong_decode_rgb_images",
 ]
 
 _lib = None
@@ -192,6 +193,10 @@ def load():
         L.picsong_decode_images.argtypes = [vp, i, vp, C.c_size_t, img, C.c_size_t, vp]
         L.picsong_encode_rgb_image.argtypes = [vp, img, i, vp, C.c_size_t, vp]
         L.picsong_decode_rgb_image.argtypes = [vp, vp, C.c_size_t, img, vp]
+        L.picsong_encode_rgb_frames.argtypes = [vp, i, vp, vp, vp, C.c_size_t, i, i, vp, C.c_size_t, vp]
+        L.picsong_decode_rgb_frames.argtypes = [vp, i, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp]
+        L.picsong_encode_rgb_images.argtypes = [vp, i, img, C.c_size_t, i, i, vp, C.c_size_t, vp]
+        L.picsong_decode_rgb_images.argtypes = [vp, i, vp, C.c_size_t, img, C.c_size_t, vp]
     _lib = L
     return L
 
@@ -576,6 +581,47 @@ class Codec:
         _check(self.L.picsong_decode_rgb_frame(self.h, self._p(streams), streams.stride(0), self._p(outs[0]),
                                                self._p(outs[1]), self._p(outs[2]), self._stream()))
         return outs
+
+    # ---- batched RGB frames: n colour frames through one launch per stage, 3 n planes a launch ----
+    def encode_rgb_frames(self, r, g, b, n=None, frame_stride=None, first_iter=0, header_mask=7):
+        """n RGB frames; r / g / b: uint8 [n, AH, AW] tensors (frame f at stride(0) bytes behind frame 0, the same for all
+        three), or frame 0's planes with n and frame_stride given.  Returns the 3 n codestreams, frame f's component c at
+        index 3 f + c; the populated header on the components of header_mask of the frame with first_iter + f == 0."""
+        if n is None:
+            n = r.shape[0]
+        if frame_stride is None:
+            frame_stride = r.stride(0) if n > 1 else 0
+            assert n == 1 or (g.stride(0) == frame_stride and b.stride(0) == frame_stride)
+        out = self.torch.empty((3 * n, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        _check(self.L.picsong_encode_rgb_frames(self.h, n, self._p(r), self._p(g), self._p(b), frame_stride, first_iter, header_mask,
+                                                self._p(out), out.stride(0), self._stream()))
+        return [out[k, :t] for k, t in enumerate(self.last_totals(3 * n))]
+
+    def decode_rgb_frames(self, streams, outs=None, frame_stride=None):
+        """streams: int16 [3 n, >= max_stream_shorts()]; returns the R, G, B planes as three uint8 [n, AH, AW] tensors
+        (or writes frame f's planes frame_stride bytes behind outs[0..2], frame 0's)."""
+        assert streams.stride(-1) == 1 and streams.shape[0] % 3 == 0
+        n = streams.shape[0] // 3
+        if outs is None:
+            outs = [self.torch.empty((n, self.ah, self.aw), dtype=self.torch.uint8, device=self.dev) for _ in range(3)]
+            frame_stride = outs[0].stride(0)
+        _check(self.L.picsong_decode_rgb_frames(self.h, n, self._p(streams), streams.stride(0), self._p(outs[0]), self._p(outs[1]),
+                                                self._p(outs[2]), frame_stride or 0, self._stream()))
+        return outs
+
+    def encode_rgb_images(self, img, n=1, frame_stride=0, first_iter=0, header_mask=7):
+        """n RGB frames of `img` (any colour layout; frame f frame_stride bytes behind frame 0), ingested on the device in
+        one launch and coded as encode_rgb_frames codes their host-padded planes."""
+        out = self.torch.empty((3 * n, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        _check(self.L.picsong_encode_rgb_images(self.h, n, C.byref(img), frame_stride, first_iter, header_mask, self._p(out),
+                                                out.stride(0), self._stream()))
+        return [out[k, :t] for k, t in enumerate(self.last_totals(3 * n))]
+
+    def decode_rgb_images(self, streams, img, frame_stride=0):
+        """streams: int16 [3 n, >= max_stream_shorts()]; the n W x H frames land in `img`, alpha (if any) 255."""
+        assert streams.stride(-1) == 1 and streams.shape[0] % 3 == 0
+        _check(self.L.picsong_decode_rgb_images(self.h, streams.shape[0] // 3, self._p(streams), streams.stride(0), C.byref(img),
+                                                frame_stride, self._stream()))
 
     def decode_plane(self, stream, component):
         out = self.torch.empty(self.P + self.extra, dtype=self.dtype, device=self.dev)

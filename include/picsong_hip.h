@@ -518,6 +518,39 @@ int picsong_encode_rgb_image(picsong_ctx *ctx, const picsong_image *src, int hea
 int picsong_decode_rgb_image(picsong_ctx *ctx, const uint16_t *d_streams, size_t stream_stride, const picsong_image *dst,
                              void *stream);
 
+/* ---- batched RGB frames: n = 1..21 colour frames through ONE launch per stage (3 n <= 64, the batched grid's limit).
+ *      Every stage launches once over 3 n planes: plane z is component z % 3 of frame z / 3, component c codes with
+ *      table c.  Every stream is byte-identical to what picsong_encode_rgb_frame writes for that frame, every decoded
+ *      plane to picsong_decode_rgb_frame's.
+ *      Addressing: d_r / d_g / d_b are frame 0's padded u8[AW*AH] planes, frame f's lie f * frame_stride bytes after
+ *      each of them -- three separate arrays (frame_stride >= P) and R, G, B back to back per frame (frame_stride = 3 P)
+ *      alike; frame_stride is ignored for n = 1.  The stream of frame f, component c lands at (is read from)
+ *      d_streams + (3 f + c) * stream_stride shorts, stream_stride >= picsong_max_stream_shorts.
+ *      Headers: header_mask (bits 0..2) names the components that carry the populated header on the frame with
+ *      first_iter + f == 0; every other frame carries none (a video: mask 7; an image: mask 1).
+ *      Lengths: the 3 n of them through picsong_last_totals(ctx, stream, 3 n, ..) / picsong_copy_last_totals.
+ *      Alignment: as the single-frame call -- the fused head runs when all three planes are 16-byte aligned and
+ *      frame_stride is a multiple of 16, else the separate colour-transform kernel (one launch a frame: same streams,
+ *      slower); decoding, planes and frame_stride 4-byte aligned take the fused tails (grid.z = frame), anything else the
+ *      separate inverse colour transform (one launch a frame).
+ *      -cp 2 RGB contexts, any -k, both coefficient forms, 5/3 and 9/7.
+ *      picsong_encode_rgb_images / picsong_decode_rgb_images: n frames in a colour layout of picsong_image, frame f at
+ *      data + f * frame_stride -- ONE ingest (emit) into (from) the context's aligned buffer, 3 planes a frame, then the
+ *      calls above.
+ *      Refused (PICSONG_ERR_ARG, nothing launched, outputs untouched): null pointers; a grey context; -cp 3; n outside
+ *      1..21; with n > 1 a frame_stride below a padded plane or one that makes a frame's planes overlap the next
+ *      frame's; a stream stride below a worst-case stream; component tables of different geometry; the image calls also
+ *      everything the layout calls refuse, and GREY8. ---- */
+int picsong_encode_rgb_frames(picsong_ctx *ctx, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b,
+                              size_t frame_stride, int first_iter, int header_mask,
+                              uint16_t *d_streams, size_t stream_stride, void *stream);
+int picsong_decode_rgb_frames(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride,
+                              uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, size_t frame_stride, void *stream);
+int picsong_encode_rgb_images(picsong_ctx *ctx, int n, const picsong_image *src, size_t frame_stride, int first_iter,
+                              int header_mask, uint16_t *d_streams, size_t stream_stride, void *stream);
+int picsong_decode_rgb_images(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride,
+                              const picsong_image *dst, size_t frame_stride, void *stream);
+
 /* ---- intra-frame sharding (BASELINE config 5): codeblocks are independent
  *      (correctCBBorders zeroes outside neighbours, BPC/BPCEngine.cu:465-484), so a rank can code
  *      the stripe [cb_begin, cb_begin + cb_count) of the frame's raster-ordered codeblocks.  The
