@@ -407,6 +407,103 @@ static_assert(LayoutTraits<kLayoutGrey8>::max_rows == 64 && LayoutTraits<kLayout
 inline LayoutLaunch select_ingest(int layout, const LayoutArgs &a) { return select_layout<IngestOf>(layout, a); }
 inline LayoutLaunch select_emit(int layout, const LayoutArgs &a) { return select_layout<EmitOf>(layout, a); }
 
+// ---- the n-frame RGB proxy calls (picsong_decode_rgb_frames_reduced / _window, picsong_decode_rgb_images_reduced /
+// _window): what they refuse, as a message; nullptr: the arguments are fine.  The context's side as rgb_frames_refusal
+// takes it, wl and the padded size aw x ah with it.
+// A window [x, x + w) x [y, y + h) of the padded image at 1/2^reduce: what picsong_decode_rgb_frame_window refuses
+inline const char *proxy_window_refusal(int aw, int ah, int wl, int reduce, int x, int y, int w, int h)
+{
+    if (!reduce_ok(wl, reduce)) return "reduce outside 0..wl - 1";
+    if (w < 1 || h < 1) return "the window is empty";
+    if (!window_ok(aw >> reduce, ah >> reduce, x, y, w, h)) return "the window is not inside the padded image at this reduce";
+    return nullptr;
+}
+// picsong_decode_rgb_frames_reduced: frame f's three planes of (aw >> reduce) x (ah >> reduce) bytes frame_stride bytes
+// after r / g / b -- rgb_frames_refusal's rules with that span in place of P
+inline const char *rgb_frames_reduced_refusal(bool ctx_rgb, int cp, bool same_geometry, int n, const void *r, const void *g, const void *b,
+                                              const void *streams, size_t frame_stride, size_t stream_stride, size_t max_stream, int aw,
+                                              int ah, int wl, int reduce)
+{
+    if (!r || !g || !b || !streams) return "null pointer";
+    if (!reduce_ok(wl, reduce)) return "reduce outside 0..wl - 1";
+    const size_t span = (size_t)(aw >> reduce) * (size_t)(ah >> reduce);
+    return rgb_frames_refusal(ctx_rgb, cp, same_geometry, n, r, g, b, streams, frame_stride, stream_stride, span, max_stream);
+}
+// picsong_decode_rgb_frames_window: row i of frame f's windows at r / g / b + f * frame_stride + i * pitch, w bytes; a
+// plane spans (h - 1) * pitch + w bytes
+inline const char *rgb_frames_window_refusal(bool ctx_rgb, int cp, bool same_geometry, int n, const void *r, const void *g, const void *b,
+                                             const void *streams, size_t pitch, size_t frame_stride, size_t stream_stride, size_t max_stream,
+                                             int aw, int ah, int wl, int reduce, int x, int y, int w, int h)
+{
+    if (!r || !g || !b || !streams) return "null pointer";
+    if (const char *why = proxy_window_refusal(aw, ah, wl, reduce, x, y, w, h)) return why;
+    if (pitch < (size_t)w) return "out_pitch smaller than the window's width";
+    const size_t span = (size_t)(h - 1) * pitch + (size_t)w;
+    return rgb_frames_refusal(ctx_rgb, cp, same_geometry, n, r, g, b, streams, frame_stride, stream_stride, span, max_stream);
+}
+// picsong_decode_rgb_images_window (and _reduced, its window (0, 0, rw, rh)): the w x h window in a colour layout of
+// picsong_image -- layout_refusal's rules on a w x h image, no grey layout
+inline const char *rgb_images_window_refusal(bool ctx_rgb, int cp, bool same_geometry, int n, const void *streams, size_t stream_stride,
+                                             size_t max_stream, int aw, int ah, int wl, int reduce, int x, int y, int w, int h, int layout,
+                                             const void *data, size_t pitch, size_t plane_stride, size_t frame_stride)
+{
+    if (!data || !streams) return "null pointer";
+    if (!ctx_rgb) return "the context is not an RGB one";
+    if (cp == 3) return "-cp 3 codes its planes one by one";
+    if (n < 1 || n > kRgbMaxFrames) return "n outside 1..21";
+    if (const char *why = proxy_window_refusal(aw, ah, wl, reduce, x, y, w, h)) return why;
+    if (stream_stride < max_stream) return "stream stride smaller than a worst-case codestream";
+    if (!same_geometry) return "the components' tables differ in geometry: code the planes one by one";
+    if (layout == kLayoutGrey8) return "a grey layout on an RGB call";
+    return layout_refusal(layout, data, pitch, plane_stride, frame_stride, data, 3 * (size_t)w * (size_t)h, n, w, h, w, h);
+}
+
+// picsong_decode_rgb_images_reduced's route: the reduced sequence into aligned planar planes, then emit_frames with the
+// geometry (rw, rh, paw, pah), where every group emit_kernel loads lies within a row of paw bytes and is aligned -- paw a
+// multiple of 16 (any 4K or 8K frame up to r = 4); else the window (0, 0, rw, rh).  The bytes are the same.
+inline bool reduced_emit_ok(int aw, int reduce) { return ((aw >> reduce) & 15) == 0; }
+
+// Their epilogue (window_rgb_image_kernel, window_kernels.hpp): 256 threads, a thread four adjacent pixels of a row,
+// grid.x over the rows' groups, grid.z = frame.  d0 .. d2: frame 0's R, G, B planes (kLayoutPlanar3) or d0 its pixels.
+// The vector form where every store address is 4-byte aligned: pointers, pitch and, n > 1, the frame stride.
+using WinRgbKernel = void (*)(WinRgbArgs);
+struct WinRgbLaunch { WinRgbKernel kernel; dim3 grid; bool vec; };
+inline WinRgbArgs window_rgb_args(int layout, const void *work, unsigned long long z_stride, int w, int h, uint8_t *d0, uint8_t *d1,
+                                  uint8_t *d2, size_t pitch, size_t frame_stride, unsigned n, int off)
+{
+    WinRgbArgs a;
+    memset(&a, 0, sizeof a);
+    a.work = work; a.z_stride = z_stride; a.w = w; a.h = h;
+    a.src16 = (w & 3) == 0 && ((((uintptr_t)work) | z_stride) & 15u) == 0 ? 1 : 0;
+    a.dst[0] = d0;
+    a.dst[1] = layout == kLayoutPlanar3 ? d1 : d0;
+    a.dst[2] = layout == kLayoutPlanar3 ? d2 : d0;
+    a.pitch = pitch; a.frame_stride = n > 1 ? frame_stride : 0; a.off = off;
+    a.a16 = ((((uintptr_t)a.dst[0]) | ((uintptr_t)a.dst[1]) | ((uintptr_t)a.dst[2]) | a.pitch | a.frame_stride) & 15u) == 0 ? 1 : 0;
+    return a;
+}
+template <int L>
+inline WinRgbKernel window_rgb_kernel_of(bool lossy, bool vec)
+{
+    if (lossy) return vec ? window_rgb_image_kernel<float, L, true> : window_rgb_image_kernel<float, L, false>;
+    return vec ? window_rgb_image_kernel<int, L, true> : window_rgb_image_kernel<int, L, false>;
+}
+inline WinRgbLaunch select_window_rgb(bool lossy, int layout, const WinRgbArgs &a, unsigned n)
+{
+    const bool vec = ((((uintptr_t)a.dst[0]) | ((uintptr_t)a.dst[1]) | ((uintptr_t)a.dst[2]) | a.pitch | a.frame_stride) & 3u) == 0;
+    const size_t groups = (size_t)((a.w + 3) / 4) * (size_t)a.h;
+    const dim3 grid((unsigned)((groups + 255) / 256), 1u, n);
+    WinRgbKernel k = nullptr;
+    switch (layout) {
+    case kLayoutPlanar3: k = window_rgb_kernel_of<kLayoutPlanar3>(lossy, vec); break;
+    case kLayoutRgb24:   k = window_rgb_kernel_of<kLayoutRgb24>(lossy, vec); break;
+    case kLayoutBgr24:   k = window_rgb_kernel_of<kLayoutBgr24>(lossy, vec); break;
+    case kLayoutRgba32:  k = window_rgb_kernel_of<kLayoutRgba32>(lossy, vec); break;
+    case kLayoutBgra32:  k = window_rgb_kernel_of<kLayoutBgra32>(lossy, vec); break;
+    }
+    return { k, grid, vec };
+}
+
 // workgroups (256 threads) of the element-wise kernels -- level shift, clamp, RGB transforms -- over n items, grid-stride
 // beyond `cap`
 inline unsigned elementwise_blocks(size_t n, unsigned cap = 8192)

@@ -252,6 +252,90 @@ int widen_staging(const Go &go, const uint16_t *staging16, const int32_t *sizes,
     return go(widen_staging_kernel, dim3((unsigned)n), 256u, staging16, sizes, cb_base, staging);
 }
 
+// ---- the n-frame RGB proxy calls: n colour frames at 1/2^reduce, or a window of them, every stage ONE launch over the 3 n
+// planes (plane z = component z % 3 of frame z / 3, table z % 3).  What a context holds for them:
+struct RgbProxyCtx {
+    int aw, ah, wl, ncb;
+    bool lossy; float qs; bool fast_div; int off;
+    size_t P, extra;
+    bool direct;              // the decoder reads the streams itself (else: through the staging)
+    bool compact;             // -k > 0: the launch takes the COMPACT table copies
+    uint32_t max_stream;      // a worst-case stream's shorts
+    int *flag;                // the intake's damage flag
+};
+// `a`: the three tables on one coder grid (bpc_args_rgb); w: a workspace of 3 n planes.
+// picsong_decode_rgb_frames_reduced (reduce = 0: picsong_decode_rgb_frames): the intake of the 3 n streams, the decoder
+// over the reduced corner's codeblocks of every plane, the synthesis down to level `reduce`, the inverse colour transform
+// -- in the finest level's launch (run_inverse_rgb, grid.z = frame) where the single-frame call takes that form and every
+// frame's planes are 4-byte aligned (fuse_tail: the caller's switches permitting), else on its own, one launch a frame.
+// Frame f's planes of (aw >> reduce) x (ah >> reduce) bytes at r / g / b + f * frame_stride.  *fused: the first form ran.
+template <class Go>
+int decode_rgb_frames_reduced(const Go &go, const RgbProxyCtx &c, BpcArgs a, const Workspace &w, unsigned n, const uint16_t *streams,
+                              size_t stream_stride, int reduce, bool want_c16, bool lean97, bool fuse_tail, uint8_t *r, uint8_t *g,
+                              uint8_t *b, unsigned long long frame_stride, bool *fused = nullptr)
+{
+    const unsigned np = 3u * n;
+    if (n <= 1) frame_stride = 0;
+    if (fused) *fused = false;
+    if (int rc = stream_intake(go, streams, np, stream_stride, c.direct, c.ncb, c.P, w, c.flag)) return rc;
+    int wpf = (c.ncb + 1) / 2;
+    if (reduce > 0) {
+        const ReducedRect q = reduced_rect(c.aw, c.ah, reduce);
+        a.ncx_r = q.ncx_r; a.ncb_r = q.ncx_r * q.ncy_r;
+        wpf = reduced_waves(q);
+    }
+    a.cb_base = 0; a.nCB = c.ncb;
+    a.frames = (int)np; a.waves_per_frame = rgb_component_waves(a.k > 0.0f, wpf);
+    // (the synthesis is planned first: it says whether this call's coefficients can travel as int16)
+    const std::vector<InvLaunch> plan = plan_inverse_frames(w.coef_i, w.coef, nullptr, nullptr, np, 0, want_c16 && c.direct, true, reduce,
+                                                            c.aw, c.ah, c.wl, c.qs, c.fast_div, c.off, c.P, c.extra);
+    const bool c16 = plan_inv_is_c16(plan);
+    a.coef_z = (unsigned long long)c.P * (c16 ? 2ull : 4ull);
+    if (int rc = launch_decoder(go, a, false, np * (unsigned)a.waves_per_frame, c.compact, w, c.direct ? streams : nullptr, stream_stride,
+                                c.max_stream, c16)) return rc;
+    const bool px_aligned = ((((uintptr_t)r) | ((uintptr_t)g) | ((uintptr_t)b) | frame_stride) & 3u) == 0;
+    if (fuse_tail && px_aligned && inv_rgb_tail_ok(plan, c.lossy)) {
+        if (fused) *fused = true;
+        return run_inverse_rgb(go, c.lossy, lean97, plan, c.off, r, g, b, n, frame_stride);
+    }
+    if (int rc = run_inverse(go, c.lossy, lean97, plan, np)) return rc;
+    const size_t z = (c.P + c.extra) * 4, n4 = (size_t)(c.aw >> reduce) * (size_t)(c.ah >> reduce) / 4;
+    for (unsigned f = 0; f < n; f++) {
+        // (level `reduce`'s samples of frame f's components: c.extra elements into their work buffers when reduce = 0)
+        const char *img = (const char *)plan.back().a.dst + (size_t)(3 * f) * z;
+        const size_t at = (size_t)f * (size_t)frame_stride;
+        if (int rc = rgb_inverse(go, c.lossy, img, img + z, img + 2 * z, r + at, g + at, b + at, n4, c.off)) return rc;
+    }
+    return 0;
+}
+// picsong_decode_rgb_frames_window and picsong_decode_rgb_images_window: the intake, the decoder over the window plan's
+// rectangle table of every plane (32-bit coefficients: what the cone's synthesis reads), run_window with frames = 3 n,
+// level r's samples left compact in the planes' work buffers, and the epilogue (window_rgb_image_kernel, grid.z = frame)
+// that stores them in `layout`: d0 .. d2 frame 0's R, G, B planes (kLayoutPlanar3), or d0 its interleaved pixels; rows
+// `pitch`, frames frame_stride bytes apart.  *vec: the epilogue's vector form ran.
+template <class Go>
+int decode_rgb_frames_window(const Go &go, const RgbProxyCtx &c, BpcArgs a, const Workspace &w, unsigned n, const uint16_t *streams,
+                             size_t stream_stride, const WindowPlan &win, int layout, uint8_t *d0, uint8_t *d1, uint8_t *d2, size_t pitch,
+                             size_t frame_stride, bool *vec = nullptr)
+{
+    const unsigned np = 3u * n;
+    if (int rc = stream_intake(go, streams, np, stream_stride, c.direct, c.ncb, c.P, w, c.flag)) return rc;
+    const int wpf = window_bpc_table(a, win);
+    a.cb_base = 0; a.nCB = c.ncb;
+    a.frames = (int)np; a.waves_per_frame = rgb_component_waves(a.k > 0.0f, wpf);
+    a.coef_z = (unsigned long long)c.P * 4ull;
+    if (int rc = launch_decoder(go, a, false, np * (unsigned)a.waves_per_frame, c.compact, w, c.direct ? streams : nullptr, stream_stride,
+                                c.max_stream, false)) return rc;
+    const unsigned long long z = (unsigned long long)(c.P + c.extra) * 4ull;
+    if (int rc = run_window(go, c.lossy, win, w.coef_i, w.coef, c.P, c.aw, c.ah, c.qs, c.off, np, (unsigned long long)c.P * 4ull, z, nullptr,
+                            0, 0)) return rc;
+    const IRect &o = win.R[win.r];
+    const WinRgbArgs ra = window_rgb_args(layout, w.coef, z, o.x1 - o.x0, o.y1 - o.y0, d0, d1, d2, pitch, frame_stride, n, c.off);
+    const WinRgbLaunch l = select_window_rgb(c.lossy, layout, ra, n);
+    if (vec) *vec = l.vec;
+    return go(l.kernel, l.grid, 256u, ra);
+}
+
 // ---- the pack of n frames' codeblocks, frame after frame in w (sizes, offsets, totals) and in the staging (P words a
 // frame): the header argument, the scan of the lengths, the copy into streams `stream_stride` shorts apart.
 // W: uint16_t = the encoders' own staging (the frame paths), int32_t = a caller's array (picsong_bitstream_pack)
@@ -311,6 +395,21 @@ int emit_frames(const Go &go, int layout, const uint8_t *padded, size_t padded_s
     l.grid.z = (unsigned)n;
     if (vec) *vec = l.vec;
     return go(l.kernel, l.grid, 256u, a);
+}
+
+// picsong_decode_rgb_images_reduced where reduced_emit_ok: decode_rgb_frames_reduced into `lay` -- 3 n planes of paw x pah
+// bytes, R, G, B back to back per frame, 16-byte aligned, so the fused tail runs where the plan has it -- then ONE emit of
+// the visible rw x rh pixels of the n frames into the caller's layout
+template <class Go>
+int decode_rgb_images_reduced(const Go &go, const RgbProxyCtx &c, const BpcArgs &a, const Workspace &w, unsigned n, const uint16_t *streams,
+                              size_t stream_stride, int reduce, bool want_c16, bool lean97, bool fuse_tail, uint8_t *lay, int layout,
+                              void *data, size_t pitch, size_t plane_stride, size_t frame_stride, int rw, int rh)
+{
+    const int paw = c.aw >> reduce, pah = c.ah >> reduce;
+    const size_t pp = (size_t)paw * (size_t)pah;
+    if (int rc = decode_rgb_frames_reduced(go, c, a, w, n, streams, stream_stride, reduce, want_c16, lean97, fuse_tail, lay, lay + pp,
+                                           lay + 2 * pp, 3ull * pp)) return rc;
+    return emit_frames(go, layout, lay, 3 * pp, data, pitch, plane_stride, frame_stride, (int)n, rw, rh, paw, pah);
 }
 
 // ---- a probe of the quality calls (picsong_encode_frame_quality and its mirrors): the distortion of the nf coded arrays

@@ -2209,8 +2209,9 @@ int picsong_decode_rgb_image(picsong_ctx *c, const uint16_t *d_streams, size_t s
 
 // ---------------------------------------------------------------------------------------------
 // batched RGB frames: n colour frames through ONE launch per stage, 3 n planes a launch -- plane z = component z % 3 of
-// frame z / 3 (the sequences: rgb_forward_transform and run_inverse_rgb with n, launch_seq.hpp; the argument check:
-// rgb_frames_refusal, kernel_select.hpp).  n = 1 launches what picsong_encode_rgb_frame / picsong_decode_rgb_frame launch.
+// frame z / 3 (the sequences: rgb_forward_transform, decode_rgb_frames_reduced and decode_rgb_frames_window, launch_seq.hpp; the
+// argument checks: rgb_frames_refusal and its proxy forms, kernel_select.hpp).  n = 1 launches what picsong_encode_rgb_frame /
+// picsong_decode_rgb_frame launch.
 // ---------------------------------------------------------------------------------------------
 static int rgb_frames_args(picsong_ctx *c, int n, const void *r, const void *g, const void *b, const void *streams, size_t frame_stride,
                            size_t stream_stride, const char *who, BpcArgs &a)
@@ -2258,39 +2259,136 @@ int picsong_encode_rgb_frames(picsong_ctx *c, int n, const uint8_t *d_r, const u
     return PICSONG_OK;
 }
 
+// What the n-frame RGB decode sequences (launch_seq.hpp) take from a context of 3 n planes: the tables on one coder grid, the
+// batch workspace grown to the call, the context's geometry and switches.  The arguments have passed their refusal.
+static int rgb_proxy_begin(picsong_ctx *c, int n, BpcArgs &a, RgbProxyCtx &g)
+{
+    if (int rc = bpc_args_rgb(c, a)) return rc;             // (the tables' geometry)
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_batch(c, 3 * n)) return rc;
+    if (int rc = ensure_coef_i(c, 3 * n)) return rc;
+    c->last_batch = -1;
+    g.aw = c->aw; g.ah = c->ah; g.wl = c->p.wl; g.ncb = c->ncb;
+    g.lossy = c->p.lossy != 0; g.qs = c->p.qs; g.fast_div = c->fast_div; g.off = level_off(c);
+    g.P = c->P; g.extra = c->extra;
+    g.direct = dec_from_stream(c);
+    g.compact = a.k > 0.0f && bulk_compact(c, 0, 3);
+    g.max_stream = (uint32_t)picsong_max_stream_shorts(c->aw, c->ah);
+    g.flag = c->d_flag;
+    return PICSONG_OK;
+}
+static int proxy_rc(int rc)
+{
+    return rc == kLaunchRefused ? fail(PICSONG_ERR_ARG, "the 16-bit coefficient form decodes from the stream itself") : rc;
+}
+
+// picsong_decode_rgb_frames (reduce = 0) and picsong_decode_rgb_frames_reduced
+static int decode_rgb_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, uint8_t *d_r,
+                                  uint8_t *d_g, uint8_t *d_b, size_t frame_stride, void *stream, const char *who)
+{
+    if (!c) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (const char *why = rgb_frames_reduced_refusal(c->p.is_rgb != 0, c->p.cp, true, n, d_r, d_g, d_b, d_streams, frame_stride, stream_stride,
+                                                     picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce))
+        return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+    BpcArgs a;
+    RgbProxyCtx g;
+    if (int rc = rgb_proxy_begin(c, n, a, g)) return rc;
+    // the fused tails (grid.z = frame) where the single-frame call takes them (PICSONG_RGB_NOFUSE=1 keeps the two launches;
+    // 9/7: the lean kernel's domain)
+    bool tail = !getenv("PICSONG_RGB_NOFUSE");
+    if (tail && g.lossy) tail = !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0);
+    return proxy_rc(picsong::decode_rgb_frames_reduced(HipGo{ (hipStream_t)stream }, g, a, c->batch, (unsigned)n, d_streams, stream_stride,
+                                                       reduce, dec_c16_reduced(c, reduce), lean97_levels(), tail, d_r, d_g, d_b,
+                                                       frame_stride));
+}
+
 int picsong_decode_rgb_frames(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_r, uint8_t *d_g,
                               uint8_t *d_b, size_t frame_stride, void *stream)
 {
+    return decode_rgb_frames_impl(c, n, d_streams, stream_stride, 0, d_r, d_g, d_b, frame_stride, stream, "decode_rgb_frames");
+}
+
+int picsong_decode_rgb_frames_reduced(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, uint8_t *d_r,
+                                      uint8_t *d_g, uint8_t *d_b, size_t frame_stride, void *stream)
+{
+    return decode_rgb_frames_impl(c, n, d_streams, stream_stride, reduce, d_r, d_g, d_b, frame_stride, stream, "decode_rgb_frames_reduced");
+}
+
+// the window calls, their arguments checked: the window's plan against the decoder's scratch, then the sequence
+static int decode_rgb_window_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y, int w,
+                                  int h, int layout, uint8_t *d0, uint8_t *d1, uint8_t *d2, size_t pitch, size_t frame_stride, void *stream,
+                                  const char *who)
+{
+    WindowPlan plan;
+    if (int rc = window_args_ok(c, reduce, x, y, w, h, who, &plan)) return rc;
     BpcArgs a;
-    int rc = rgb_frames_args(c, n, d_r, d_g, d_b, d_streams, frame_stride, stream_stride, "decode_rgb_frames", a);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const unsigned np = 3u * (unsigned)n;
-    if (n == 1) frame_stride = 0;
-    if ((rc = ensure_batch(c, (int)np))) return rc;
-    if ((rc = ensure_coef_i(c, (int)np))) return rc;
-    c->last_batch = -1;
-    hipStream_t s = (hipStream_t)stream;
-    const bool lossy = c->p.lossy != 0, direct = dec_from_stream(c);
-    if ((rc = stream_intake(c, d_streams, np, stream_stride, direct, c->batch, s))) return rc;
-    const std::vector<InvLaunch> plan = inverse_plan(c, c->batch.coef_i, c->batch.coef, nullptr, nullptr, np, 0, c->c16_dec && direct, true, 0);
-    const bool c16 = plan_inv_is_c16(plan);
-    a.coef_z = (unsigned long long)c->P * (c16 ? 2ull : 4ull);
-    if ((rc = launch_decoder(c, a, np * (unsigned)a.waves_per_frame, a.k > 0.0f && bulk_compact(c, 0, 3), c->batch,
-                             direct ? d_streams : nullptr, stream_stride, c16, s))) return rc;
-    // the fused tails (grid.z = frame) where picsong_decode_rgb_frame takes them and every frame's planes are 4-byte aligned
-    const bool px_aligned = ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b) | frame_stride) & 3u) == 0;
-    bool tail = inv_rgb_tail_ok(plan, lossy) && px_aligned && !getenv("PICSONG_RGB_NOFUSE");
-    if (tail && lossy) tail = !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0);
-    if (tail) return run_inverse_rgb(HipGo{ s }, lossy, lean97_levels(), plan, level_off(c), d_r, d_g, d_b, (unsigned)n, frame_stride);
-    if ((rc = run_inverse(c, plan, s, np))) return rc;
-    const size_t z = (c->P + c->extra) * 4;
-    for (int f = 0; f < n; f++) {                           // the separate inverse colour transform: one launch a frame
-        const char *img = (const char *)plan.back().a.dst + (size_t)(3 * f) * z;
-        const size_t at = (size_t)f * frame_stride;
-        if ((rc = rgb_inverse(HipGo{ s }, lossy, img, img + z, img + 2 * z, d_r + at, d_g + at, d_b + at, c->P / 4, level_off(c)))) return rc;
-    }
-    return PICSONG_OK;
+    RgbProxyCtx g;
+    if (int rc = rgb_proxy_begin(c, n, a, g)) return rc;
+    return proxy_rc(picsong::decode_rgb_frames_window(HipGo{ (hipStream_t)stream }, g, a, c->batch, (unsigned)n, d_streams, stream_stride,
+                                                      plan, layout, d0, d1, d2, pitch, frame_stride));
+}
+
+int picsong_decode_rgb_frames_window(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
+                                     int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, size_t out_pitch, size_t frame_stride,
+                                     void *stream)
+{
+    const char *who = "decode_rgb_frames_window";
+    if (!c) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (const char *why = rgb_frames_window_refusal(c->p.is_rgb != 0, c->p.cp, true, n, d_r, d_g, d_b, d_streams, out_pitch, frame_stride,
+                                                    stream_stride, picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce,
+                                                    x, y, w, h))
+        return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+    return decode_rgb_window_impl(c, n, d_streams, stream_stride, reduce, x, y, w, h, kLayoutPlanar3, d_r, d_g, d_b, out_pitch, frame_stride,
+                                  stream, who);
+}
+
+static int decode_rgb_images_window_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
+                                         int w, int h, const picsong_image *dst, size_t frame_stride, void *stream, const char *who)
+{
+    if (const char *why = rgb_images_window_refusal(c->p.is_rgb != 0, c->p.cp, true, n, d_streams, stream_stride,
+                                                    picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce, x, y, w, h,
+                                                    dst->layout, dst->data, dst->pitch, dst->plane_stride, frame_stride))
+        return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+    uint8_t *const d = (uint8_t *)dst->data;
+    return decode_rgb_window_impl(c, n, d_streams, stream_stride, reduce, x, y, w, h, dst->layout, d, d + dst->plane_stride,
+                                  d + 2 * dst->plane_stride, dst->pitch, frame_stride, stream, who);
+}
+
+int picsong_decode_rgb_images_window(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
+                                     int w, int h, const picsong_image *dst, size_t frame_stride, void *stream)
+{
+    const char *who = "decode_rgb_images_window";
+    if (!c || !dst) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    return decode_rgb_images_window_impl(c, n, d_streams, stream_stride, reduce, x, y, w, h, dst, frame_stride, stream, who);
+}
+
+// the visible rw x rh pixels at 1/2^reduce.  Two routes, the same bytes: the reduced sequence -- 16-bit
+// coefficients, the lean synthesis, the fused tail -- into the context's aligned layout buffer and one emit with the geometry
+// (rw, rh, paw, pah), where emit_kernel's group loads fit the reduced rows (reduced_emit_ok); else the window (0, 0, rw, rh)
+int picsong_decode_rgb_images_reduced(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                      const picsong_image *dst, size_t frame_stride, void *stream)
+{
+    const char *who = "decode_rgb_images_reduced";
+    if (!c || !dst) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (!reduce_ok(c->p.wl, reduce)) return fail(PICSONG_ERR_ARG, "%s: reduce %d outside 0..%d (wl - 1)", who, reduce, c->p.wl - 1);
+    int d[5];
+    reduced_dims(c->p.width, c->p.height, c->aw, c->ah, reduce, d);
+    if (!reduced_emit_ok(c->aw, reduce))
+        return decode_rgb_images_window_impl(c, n, d_streams, stream_stride, reduce, 0, 0, d[0], d[1], dst, frame_stride, stream, who);
+    if (const char *why = rgb_images_window_refusal(c->p.is_rgb != 0, c->p.cp, true, n, d_streams, stream_stride,
+                                                    picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce, 0, 0, d[0], d[1],
+                                                    dst->layout, dst->data, dst->pitch, dst->plane_stride, frame_stride))
+        return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+    BpcArgs a;
+    RgbProxyCtx g;
+    if (int rc = rgb_proxy_begin(c, n, a, g)) return rc;
+    const size_t pp = (size_t)d[2] * (size_t)d[3];
+    if (int rc = ensure_layout(c, ((size_t)3 * (size_t)n * pp + c->P - 1) / c->P)) return rc;
+    bool tail = !getenv("PICSONG_RGB_NOFUSE");
+    if (tail && g.lossy) tail = !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0);
+    return proxy_rc(picsong::decode_rgb_images_reduced(HipGo{ (hipStream_t)stream }, g, a, c->batch, (unsigned)n, d_streams, stream_stride,
+                                                       reduce, dec_c16_reduced(c, reduce), lean97_levels(), tail, c->lay_buf, dst->layout,
+                                                       dst->data, dst->pitch, dst->plane_stride, frame_stride, d[0], d[1]));
 }
 
 static int rgb_images_args(picsong_ctx *c, int n, const picsong_image *img, size_t frame_stride, const void *d_streams, size_t stream_stride,

@@ -12,7 +12,8 @@
 // vertical, a barrier between steps.  9/7 divides as the oracle does -- ((m * s) / q) / qs on the read, x / N1 and
 // x / N2 with true divisions (div_n1<true>, div_n2<true>), explicit fmaf in po_97_inv_1d's operation order.
 // Intermediate levels store R_l as T (row stride its width); level r stores pixels into the caller's window through
-// to_pixel (grey), or T that window_rgb_kernel turns into the three pixel planes (RGB).
+// to_pixel (grey), or T that window_rgb_kernel turns into the three pixel planes (RGB; n frames in any colour layout:
+// window_rgb_image_kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,6 +23,7 @@
 #include "bpc_kernels.hpp"
 #include "dwt_kernels.hpp"
 #include "launch_plan.hpp"
+#include "layout_kernels.hpp"
 
 namespace picsong {
 
@@ -179,34 +181,134 @@ __global__ __launch_bounds__(256) void dwt_window_kernel(WinSynArgs a)
         }
 }
 
+// The inverse RCT / ICT of one pixel's three component samples, level shift and clamp -- rgb_inverse_kernel's arithmetic
+template <typename T>
+__device__ __forceinline__ void window_rgb_px(T yy, T cb, T cr, int off, uint32_t &r, uint32_t &g, uint32_t &b)
+{
+    int R, G, B;
+    if constexpr (std::is_integral<T>::value) {
+        G = (int)yy - (((int)cb + (int)cr) >> 2);
+        R = (int)cr + G;
+        B = (int)cb + G;
+    } else {
+        const float M[3][3] = { { 1.0f, 0.0f, 1.402f }, { 1.0f, -0.344136f, -0.714136f }, { 1.0f, 1.772f, 0.0f } };
+        R = (int)rintf(fmaf(M[0][2], cr, fmaf(M[0][1], cb, M[0][0] * yy)) + 0.01f);
+        G = (int)rintf(fmaf(M[1][2], cr, fmaf(M[1][1], cb, M[1][0] * yy)) + 0.01f);
+        B = (int)rintf(fmaf(M[2][2], cr, fmaf(M[2][1], cb, M[2][0] * yy)) + 0.01f);
+    }
+    r = (uint32_t)clamp_u8(R + off);
+    g = (uint32_t)clamp_u8(G + off);
+    b = (uint32_t)clamp_u8(B + off);
+}
+
 // RGB window calls: the inverse RCT / ICT of the three components' level-r samples (compact, w x h, row stride w, the
-// components z_stride bytes apart), level shift and clamp -- rgb_inverse_kernel's arithmetic -- into the three pixel
-// planes, row i at r / g / b + i * pitch
+// components z_stride bytes apart), level shift and clamp into the three pixel planes, row i at r / g / b + i * pitch
 template <typename T>
 __global__ __launch_bounds__(256) void window_rgb_kernel(const T *c0, unsigned long long z_stride, int w, int h, uint8_t *r,
                                                          uint8_t *g, uint8_t *b, unsigned long long pitch, int off)
 {
     const T *c1 = (const T *)((const char *)c0 + z_stride), *c2 = (const T *)((const char *)c0 + 2 * z_stride);
-    const float M[3][3] = { { 1.0f, 0.0f, 1.402f }, { 1.0f, -0.344136f, -0.714136f }, { 1.0f, 1.772f, 0.0f } };
     const int y = (int)blockIdx.y;
     for (int x = (int)(blockIdx.x * blockDim.x + threadIdx.x); x < w; x += (int)(gridDim.x * blockDim.x)) {
         const size_t i = (size_t)y * (size_t)w + (size_t)x;
-        int R, G, B;
-        if constexpr (std::is_integral<T>::value) {
-            const int yy = (int)c0[i], cb = (int)c1[i], cr = (int)c2[i];
-            G = yy - ((cb + cr) >> 2);
-            R = cr + G;
-            B = cb + G;
-        } else {
-            const float yy = c0[i], cb = c1[i], cr = c2[i];
-            R = (int)rintf(fmaf(M[0][2], cr, fmaf(M[0][1], cb, M[0][0] * yy)) + 0.01f);
-            G = (int)rintf(fmaf(M[1][2], cr, fmaf(M[1][1], cb, M[1][0] * yy)) + 0.01f);
-            B = (int)rintf(fmaf(M[2][2], cr, fmaf(M[2][1], cb, M[2][0] * yy)) + 0.01f);
-        }
+        uint32_t R, G, B;
+        window_rgb_px<T>(c0[i], c1[i], c2[i], off, R, G, B);
         const size_t o = (size_t)y * (size_t)pitch + (size_t)x;
-        r[o] = (uint8_t)clamp_u8(R + off);
-        g[o] = (uint8_t)clamp_u8(G + off);
-        b[o] = (uint8_t)clamp_u8(B + off);
+        r[o] = (uint8_t)R;
+        g[o] = (uint8_t)G;
+        b[o] = (uint8_t)B;
+    }
+}
+
+// The epilogue of the n-frame RGB proxy calls (picsong_decode_rgb_frames_window, picsong_decode_rgb_images_window and
+// _reduced): the same arithmetic over the w x h windows of n frames, grid.z = frame, stored in the caller's pixel layout
+// -- kLayoutPlanar3 (three plane pointers) or an interleaved layout of layout_kernels.hpp, alpha 255.  There is no planar
+// intermediate and no emit pass.
+//   A thread converts four adjacent pixels of a row: it reads 3 x 16 bytes (one dwordx4 a component where the source rows
+//   are 16-byte aligned: w a multiple of 4) and stores one dword a plane, three dwords (RGB24 / BGR24, repacked with
+//   byte permutes: layout_store_vec) or 16 bytes (RGBA32 / BGRA32; one dwordx4 where a16).  Threads run along the rows of
+//   the window, row after row, so a narrow window still fills its waves; the kernel holds no LDS and few registers, its
+//   occupancy is the grid's.
+//   VEC: every store address is 4-byte aligned (pointers, pitch, frame stride).  The row's last, partial group and every
+//   destination that is not so aligned are stored per byte; the bytes are the same.  No byte outside
+//   [i * pitch, i * pitch + w * bpp) of rows 0 .. h - 1 is written.
+struct WinRgbArgs {
+    const void *work;                   // frame z's component c: T[w * h], row stride w, at work + (3 z + c) * z_stride
+    unsigned long long z_stride;
+    int w, h;
+    int src16;                          // the component rows take dwordx4 loads
+    uint8_t *dst[3];                    // frame 0 -- planar: the R, G, B planes; interleaved: dst[0], the pixels
+    unsigned long long pitch, frame_stride;
+    int off;                            // level shift
+    int a16;                            // VEC: the destination is 16-byte aligned as well
+};
+
+template <typename T>
+__device__ __forceinline__ void win_load4(const T *p, bool vec, uint32_t nvis, T (&v)[4])
+{
+    if (vec) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(p);
+        const uint32_t w[4] = { q.x, q.y, q.z, q.w };
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if constexpr (std::is_integral<T>::value) v[k] = (T)(int)w[k];
+            else v[k] = __uint_as_float(w[k]);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = (uint32_t)k < nvis ? p[k] : (T)0;
+    }
+}
+
+template <typename T, int L, bool VEC>
+__global__ __launch_bounds__(256) void window_rgb_image_kernel(WinRgbArgs a)
+{
+    using LT = LayoutTraits<L>;
+    static_assert(L == kLayoutPlanar3 || LT::inter, "a colour layout");
+    const uint32_t w = (uint32_t)a.w, gpr = (w + 3u) / 4u;                  // groups of four pixels a row
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= gpr * (uint32_t)a.h) return;
+    const uint32_t y = t / gpr, x0 = (t - y * gpr) * 4u, nvis = w - x0 < 4u ? w - x0 : 4u;
+    const unsigned long long z = blockIdx.z;
+    const char *const src = (const char *)a.work + 3ull * z * a.z_stride;
+    const size_t i = (size_t)y * (size_t)w + (size_t)x0;
+    T c[3][4];
+#pragma unroll
+    for (int k = 0; k < 3; k++) win_load4<T>((const T *)(src + (unsigned long long)k * a.z_stride) + i, a.src16 != 0, nvis, c[k]);
+    uint32_t p[3][1] = { { 0u }, { 0u }, { 0u } };                          // four pixels of R, G, B, a byte each
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        uint32_t R, G, B;
+        window_rgb_px<T>(c[0][k], c[1][k], c[2][k], a.off, R, G, B);
+        p[0][0] |= R << (8 * k); p[1][0] |= G << (8 * k); p[2][0] |= B << (8 * k);
+    }
+    const size_t row = (size_t)z * a.frame_stride + (size_t)y * a.pitch;
+    if constexpr (!LT::inter) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            uint8_t *const q = a.dst[k] + row + x0;
+            if (VEC && nvis == 4u) {
+                *reinterpret_cast<uint32_t *>(q) = p[k][0];
+            } else {
+#pragma unroll
+                for (uint32_t j = 0; j < 4u; j++)
+                    if (j < nvis) q[j] = (uint8_t)(p[k][0] >> (8u * j));
+            }
+        }
+    } else {
+        uint8_t *const q = a.dst[0] + row + (size_t)x0 * LT::bpp;
+        if (VEC && nvis == 4u) {
+            layout_store_vec<L>(q, a.a16 != 0, p);
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; j++) {
+                if (j < nvis) {
+#pragma unroll
+                    for (int k = 0; k < 3; k++) q[j * LT::bpp + layout_chan<L>(k)] = (uint8_t)(p[k][0] >> (8u * j));
+                    if (LT::bpp == 4) q[j * LT::bpp + 3u] = 0xFFu;
+                }
+            }
+        }
     }
 }
 

@@ -109,9 +109,11 @@ void help()
         "                     (--devices a,b,c names them explicitly); every device copies its codestreams to the\n"
         "                     writer's pinned ring over its own host link, the output file is the 1-GPU file\n"
         " -framesPerLaunch B  frames coded / decoded per launch (default: 4 up to 4K frames, 1 above; an RGB video:\n"
-        "                     the same rule on a frame's three planes, at most 21)\n"
+        "                     the same rule on a frame's three planes -- decoding with -reduce / -window: on the three\n"
+        "                     planes it writes -- at most 21)\n"
         " --lut-fill V        value of LUT entries the loader never writes (default 0)\n"
-        " -reduce r           decoding: the image at 1/2^r of its size, r in 0..wl-1 (resolution reduction)\n"
+        " -reduce r           decoding: the image at 1/2^r of its size, r in 0..wl-1 (resolution reduction); an RGB video\n"
+        "                     goes through groups of -framesPerLaunch frames, as at full size (-window too)\n"
         " -window x,y,w,h     decoding: only the w x h rectangle at (x, y) of the image (at 1/2^r with -reduce r), from the\n"
         "                     codeblocks it depends on (spatial random access)\n"
         " -train <outFolder>  coding (-cd 0, -cp 2, -k 0): code nothing; count the input's coding decisions and write the\n"
@@ -393,8 +395,9 @@ std::string search_step(const Options &o, picsong_ctx *ctx, hipStream_t s, const
     return std::string();
 }
 
-// ---- frames a call of an RGB video (-framesPerLaunch B, else the grey path's rule on a frame's three planes), at most the
-// 21 a call of picsong_encode_rgb_frames / picsong_decode_rgb_frames takes and the frames there are
+// ---- frames a call of an RGB video (-framesPerLaunch B, else the grey path's rule on a frame's three planes of P bytes -- a
+// reduced or windowed decode: the planes it writes), at most the 21 a call of picsong_encode_rgb_frames /
+// picsong_decode_rgb_frames and the proxy calls takes and the frames there are
 int rgb_group_frames(const Options &o, size_t P, long nframes)
 {
     long B = o.frames_per_launch > 0 ? o.frames_per_launch : (3 * P <= (size_t)3840 * 2176 ? 4 : 1);
@@ -1024,13 +1027,14 @@ void write_pgm(const std::string &path, const uint8_t *pix, int w, int h, int bi
 // (x, y) of the image at 1/2^r, rows pw = w bytes apart (ph = h).
 struct OutDims { int r, w, h, pw, ph, win = 0, x = 0, y = 0; };
 
-// The frames of an RGB video (-cp 2, full size) in groups of B through ONE call each: picsong_decode_rgb_frames into padded
-// planes, cropped on the host, or, -layout, picsong_decode_rgb_images into the frames as the file takes them -- one pinned
+// The frames of an RGB video (-cp 2) in groups of B through ONE call each: picsong_decode_rgb_frames (-reduce r:
+// picsong_decode_rgb_frames_reduced; -window: picsong_decode_rgb_frames_window) into planes of od.pw x od.ph bytes, cropped
+// on the host, or, -layout (full size only), picsong_decode_rgb_images into the frames as the file takes them -- one pinned
 // staging area, one upload and one read-back a group.  The output as frame by frame.
 void decode_rgb_groups(const Options &o, const picsong_params &p, picsong_ctx *ctx, hipStream_t s, std::ifstream &in,
-                       const std::vector<long> &shorts, long nframes, int aw, int ah)
+                       const std::vector<long> &shorts, long nframes, int aw, int ah, const OutDims &od)
 {
-    const size_t P = (size_t)aw * ah, max_shorts = picsong_max_stream_shorts(aw, ah);
+    const size_t P = (size_t)od.pw * od.ph, max_shorts = picsong_max_stream_shorts(aw, ah);      // (P: a plane as this call writes it)
     Options og = o;
     og.x = p.width; og.y = p.height;
     const int B = rgb_group_frames(og, P, nframes);
@@ -1042,7 +1046,7 @@ void decode_rgb_groups(const Options &o, const picsong_params &p, picsong_ctx *c
     HIPCK(hipMalloc(&d_in, max_shorts * 2 * 3 * (size_t)B));
     HIPCK(hipHostMalloc(&h_pix, frame_bytes * (size_t)B));
     HIPCK(hipMalloc(&d_pix, frame_bytes * (size_t)B));
-    std::vector<uint8_t> crop((size_t)p.width * p.height);
+    std::vector<uint8_t> crop((size_t)od.w * od.h);
     std::ofstream out(o.output, std::ios::binary | std::ios::app);
     size_t pos = 0;
     for (long f = 0; f < nframes; f += B) {
@@ -1068,6 +1072,11 @@ void decode_rgb_groups(const Options &o, const picsong_params &p, picsong_ctx *c
         if (o.layout >= 0) {
             const picsong_image im = layout_image(o.layout, d_pix, p.width, p.height);
             CK(picsong_decode_rgb_images(ctx, n, d_in, max_shorts, &im, raw_bytes, s));
+        } else if (od.win) {
+            CK(picsong_decode_rgb_frames_window(ctx, n, d_in, max_shorts, od.r, od.x, od.y, od.w, od.h, d_pix, d_pix + P, d_pix + 2 * P,
+                                                (size_t)od.pw, 3 * P, s));
+        } else if (od.r > 0) {
+            CK(picsong_decode_rgb_frames_reduced(ctx, n, d_in, max_shorts, od.r, d_pix, d_pix + P, d_pix + 2 * P, 3 * P, s));
         } else {
             CK(picsong_decode_rgb_frames(ctx, n, d_in, max_shorts, d_pix, d_pix + P, d_pix + 2 * P, 3 * P, s));
         }
@@ -1078,7 +1087,7 @@ void decode_rgb_groups(const Options &o, const picsong_params &p, picsong_ctx *c
             continue;
         }
         for (int j = 0; j < 3 * n; j++) {
-            for (int y = 0; y < p.height; y++) memcpy(&crop[(size_t)y * p.width], h_pix + (size_t)j * P + (size_t)y * aw, (size_t)p.width);
+            for (int y = 0; y < od.h; y++) memcpy(&crop[(size_t)y * od.w], h_pix + (size_t)j * P + (size_t)y * od.pw, (size_t)od.w);
             out.write(reinterpret_cast<const char *>(crop.data()), (std::streamsize)crop.size());
         }
     }
@@ -1110,9 +1119,10 @@ int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, 
     { std::ofstream trunc(o.output, std::ios::binary | std::ios::trunc); }
     auto t0 = std::chrono::steady_clock::now();
     size_t pos = 0;
-    // a video at full size (-cp 2): groups of frames through one call each; everything else frame by frame, here
-    const bool grouped = o.video && batched && !od.win && od.r == 0;
-    if (grouped) decode_rgb_groups(o, p, ctx, s, in, shorts, nframes, aw, ah);
+    // a video (-cp 2), at full size, reduced or windowed: groups of frames through one call each; everything else frame by
+    // frame, here
+    const bool grouped = o.video && batched;
+    if (grouped) decode_rgb_groups(o, p, ctx, s, in, shorts, nframes, aw, ah, od);
     for (long f = grouped ? nframes : 0; f < nframes; f++) {
         for (int c = 0; c < 3; c++) {
             const size_t n = (size_t)shorts[(size_t)(f * 3 + c)];

@@ -69,6 +69,8 @@ EXPORTS = [
     "picsong_ingest_frames", "picsong_emit_frames", "picsong_encode_images", "picsong_decode_images",
     "picsong_encode_rgb_image", "picsong_decode_rgb_image",
     "picsong_encode_rgb_frames", "picsong_decode_rgb_frames", "picsong_encode_rgb_images", "picsong_decode_rgb_images",
+    "picsong_decode_rgb_frames_reduced", "picsong_decode_rgb_frames_window", "picsong_decode_rgb_images_reduced",
+    "picsong_decode_rgb_images_window",
 ]
 
 _lib = None
@@ -197,6 +199,12 @@ def load():
         L.picsong_decode_rgb_frames.argtypes = [vp, i, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp]
         L.picsong_encode_rgb_images.argtypes = [vp, i, img, C.c_size_t, i, i, vp, C.c_size_t, vp]
         L.picsong_decode_rgb_images.argtypes = [vp, i, vp, C.c_size_t, img, C.c_size_t, vp]
+    if hasattr(L, "picsong_decode_rgb_frames_reduced"):
+        img = C.POINTER(Image)
+        L.picsong_decode_rgb_frames_reduced.argtypes = [vp, i, vp, C.c_size_t, i, vp, vp, vp, C.c_size_t, vp]
+        L.picsong_decode_rgb_frames_window.argtypes = [vp, i, vp, C.c_size_t, i, i, i, i, i, vp, vp, vp, C.c_size_t, C.c_size_t, vp]
+        L.picsong_decode_rgb_images_reduced.argtypes = [vp, i, vp, C.c_size_t, i, img, C.c_size_t, vp]
+        L.picsong_decode_rgb_images_window.argtypes = [vp, i, vp, C.c_size_t, i, i, i, i, i, img, C.c_size_t, vp]
     _lib = L
     return L
 
@@ -852,3 +860,44 @@ class Codec:
                                                       self._p(outs[0]), self._p(outs[1]), self._p(outs[2]),
                                                       outs[0].stride(0), self._stream()))
         return outs
+
+    # ---- colour proxies: n RGB frames at 1/2^r, or a window of them, through one launch per stage ----
+    def decode_rgb_frames_reduced(self, streams, r, outs=None, frame_stride=None):
+        """streams: int16 [3 n, >= max_stream_shorts()]; returns the reduced R, G, B planes as three uint8
+        [n, AH >> r, AW >> r] tensors (or writes frame f's planes frame_stride bytes behind outs[0..2], frame 0's)."""
+        assert streams.stride(-1) == 1 and streams.shape[0] % 3 == 0
+        n = streams.shape[0] // 3
+        if outs is None:
+            outs = [self.torch.empty((n, self.ah >> r, self.aw >> r), dtype=self.torch.uint8, device=self.dev) for _ in range(3)]
+            frame_stride = outs[0].stride(0)
+        _check(self.L.picsong_decode_rgb_frames_reduced(self.h, n, self._p(streams), streams.stride(0), r, self._p(outs[0]),
+                                                        self._p(outs[1]), self._p(outs[2]), frame_stride or 0, self._stream()))
+        return outs
+
+    def decode_rgb_frames_window(self, streams, x, y, w, h, r=0, outs=None):
+        """streams: int16 [3 n, >= max_stream_shorts()]; returns the R, G, B windows as three uint8 [n, h, w] tensors (or
+        fills `outs`, three 3-D uint8 views with the same frame stride, stride(0), and pitch, stride(1))."""
+        assert streams.stride(-1) == 1 and streams.shape[0] % 3 == 0
+        n = streams.shape[0] // 3
+        if outs is None:
+            outs = [self.torch.empty((n, h, w), dtype=self.torch.uint8, device=self.dev) for _ in range(3)]
+        for o in outs:
+            assert o.dtype == self.torch.uint8 and tuple(o.shape) == (n, h, w) and o.stride(2) == 1
+            assert o.stride(0) == outs[0].stride(0) and o.stride(1) == outs[0].stride(1)
+        _check(self.L.picsong_decode_rgb_frames_window(self.h, n, self._p(streams), streams.stride(0), r, x, y, w, h, self._p(outs[0]),
+                                                       self._p(outs[1]), self._p(outs[2]), outs[0].stride(1), outs[0].stride(0),
+                                                       self._stream()))
+        return outs
+
+    def decode_rgb_images_reduced(self, streams, r, img, frame_stride=0):
+        """streams: int16 [3 n, >= max_stream_shorts()]; the visible rw x rh pixels (reduced_dims) of the n frames at 1/2^r
+        land in `img` (any colour layout; frame f frame_stride bytes behind frame 0), alpha (if any) 255."""
+        assert streams.stride(-1) == 1 and streams.shape[0] % 3 == 0
+        _check(self.L.picsong_decode_rgb_images_reduced(self.h, streams.shape[0] // 3, self._p(streams), streams.stride(0), r,
+                                                        C.byref(img), frame_stride, self._stream()))
+
+    def decode_rgb_images_window(self, streams, x, y, w, h, img, r=0, frame_stride=0):
+        """... and the w x h window at (x, y) of the padded image at 1/2^r, in the layout of `img`."""
+        assert streams.stride(-1) == 1 and streams.shape[0] % 3 == 0
+        _check(self.L.picsong_decode_rgb_images_window(self.h, streams.shape[0] // 3, self._p(streams), streams.stride(0), r, x, y, w,
+                                                       h, C.byref(img), frame_stride, self._stream()))

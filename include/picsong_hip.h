@@ -551,6 +551,45 @@ int picsong_encode_rgb_images(picsong_ctx *ctx, int n, const picsong_image *src,
 int picsong_decode_rgb_images(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride,
                               const picsong_image *dst, size_t frame_stride, void *stream);
 
+/* ---- colour proxies: n = 1..21 RGB frames at 1/2^reduce, or a window of them, through ONE launch per stage over the
+ *      3 n planes -- thumbnails, previews and editing proxies of a colour video, whose launches are too small to run
+ *      one frame a call.  Streams as picsong_decode_rgb_frames reads them: frame f, component c at d_streams +
+ *      (3 f + c) * stream_stride shorts.  Asynchronous on `stream`; -cp 2 RGB contexts, any -k, 5/3 and 9/7, reduce in
+ *      0..wl-1; picsong_range_flag covers the codeblocks a call decodes; the context grows its batch workspace to 3 n
+ *      planes.  frame_stride is ignored for n = 1.
+ *      picsong_decode_rgb_frames_reduced: frame f's planes, paw x pah bytes each (picsong_reduced_dims), at d_r / d_g /
+ *      d_b + f * frame_stride, byte-identical to picsong_decode_rgb_frame_reduced of that frame; no byte beyond them is
+ *      written; reduce = 0 is picsong_decode_rgb_frames.  Planes and frame_stride 4-byte aligned take the fused tail
+ *      (finest synthesis level + inverse RCT / ICT in one launch, grid.z = frame) where the single-frame call takes it,
+ *      anything else the separate inverse colour transform (one launch a frame).
+ *      picsong_decode_rgb_frames_window: frame f's three windows, byte-identical to picsong_decode_rgb_frame_window; row
+ *      i goes to d_x + f * frame_stride + i * out_pitch, w bytes, and nothing else is written.  Any alignment.  Only the
+ *      codeblocks of the window's cone are decoded (picsong_window_codeblocks: per frame and component).
+ *      picsong_decode_rgb_images_window: the same windows in a colour layout of picsong_image -- PLANAR3, RGB24, BGR24,
+ *      RGBA32, BGRA32 --: pixel (j, i) of frame f's window at dst->data + f * frame_stride + i * dst->pitch + j * bpp,
+ *      alpha 255; no byte outside [i * pitch, i * pitch + w * bpp) of rows 0..h-1 is written.  The bytes are those of
+ *      picsong_decode_rgb_frames_window interleaved as picsong_emit_frames interleaves; the epilogue kernel writes the
+ *      layout itself (dword / dwordx4 stores where data, pitch and frame_stride are 4-byte aligned, per byte otherwise).
+ *      picsong_decode_rgb_images_reduced: the visible rw x rh pixels (picsong_reduced_dims) of each frame at
+ *      1/2^reduce, the bytes of picsong_decode_rgb_images_window with the window (0, 0, rw, rh).  Where paw is a
+ *      multiple of 16 it runs picsong_decode_rgb_frames_reduced into the context's aligned buffer and ONE emit of the
+ *      n frames (the faster route: 16-bit coefficients, the fused tail), else that window call.
+ *      Refused (PICSONG_ERR_ARG, nothing launched, outputs untouched): null pointers; a grey context; -cp 3; n outside
+ *      1..21; reduce outside 0..wl-1; a stream stride below a worst-case stream; component tables of different
+ *      geometry.  The frames calls with n > 1: a frame_stride below one plane's span (paw * pah; (h - 1) * out_pitch +
+ *      w) or one that makes a frame's planes overlap the next frame's.  The window calls: everything
+ *      picsong_decode_rgb_frame_window refuses.  The image calls: an unknown layout or GREY8, pitch < w * bpp, a
+ *      PLANAR3 plane_stride below a plane's span, with n > 1 a frame_stride below a frame's span. ---- */
+int picsong_decode_rgb_frames_reduced(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                      uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, size_t frame_stride, void *stream);
+int picsong_decode_rgb_frames_window(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                     int x, int y, int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b,
+                                     size_t out_pitch, size_t frame_stride, void *stream);
+int picsong_decode_rgb_images_reduced(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                      const picsong_image *dst, size_t frame_stride, void *stream);
+int picsong_decode_rgb_images_window(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                     int x, int y, int w, int h, const picsong_image *dst, size_t frame_stride, void *stream);
+
 /* ---- intra-frame sharding (BASELINE config 5): codeblocks are independent
  *      (correctCBBorders zeroes outside neighbours, BPC/BPCEngine.cu:465-484), so a rank can code
  *      the stripe [cb_begin, cb_begin + cb_count) of the frame's raster-ordered codeblocks.  The
