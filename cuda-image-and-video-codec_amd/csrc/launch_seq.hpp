@@ -6,8 +6,8 @@
 // A sequence takes plain values (geometry, plans, pointers, booleans), never a context; what the environment says
 // arrives as a parameter (kernel_select.hpp), read by each caller where and when it always was -- and the callers
 // differ, on purpose left so: the library reads PICSONG_DWT_INV97 once per process for the synthesis levels
-// (lean97_levels) but per call, with PICSONG_RGB_NOFUSE, for the RGB tail (decode_rgb_impl); emu_driver.cpp reads it
-// at every call (emu_lean97: the tests flip it); emu_decode_reduced passes a constant true; and emu_fast_div
+// (lean97_levels) but per call, with PICSONG_RGB_NOFUSE, for the RGB tail (rgb_tail_switch, picsong_hip.hip); emu_driver.cpp reads it
+// at every call (emu_lean97: the tests flip it); the frame-decode drivers pass a constant true; and emu_fast_div
 // re-derives per (qs, wl) what a context stores at its creation.
 #pragma once
 #include "kernel_select.hpp"
@@ -198,15 +198,6 @@ int run_window(const Go &go, bool lossy, const WindowPlan &w, const int32_t *coe
     }
     return 0;
 }
-// its RGB epilogue: the inverse RCT / ICT over the w x h window of three components z bytes apart at `work`
-template <class Go>
-int window_rgb(const Go &go, bool lossy, const void *work, unsigned long long z, int w, int h, uint8_t *r, uint8_t *g, uint8_t *b,
-               size_t pitch, int off)
-{
-    const dim3 grid((unsigned)((w + 255) / 256), (unsigned)h);
-    return lossy ? go(window_rgb_kernel<float>, grid, 256u, (const float *)work, z, w, h, r, g, b, pitch, off)
-                 : go(window_rgb_kernel<int>, grid, 256u, (const int *)work, z, w, h, r, g, b, pitch, off);
-}
 
 // ---- stream intake: the codeblock lengths of n streams `stride` shorts apart into w.sizes, their scan into w.offsets
 // and w.total -- `direct`, one launch, for a decoder that reads the streams itself; else the codewords unpacked into
@@ -252,88 +243,151 @@ int widen_staging(const Go &go, const uint16_t *staging16, const int32_t *sizes,
     return go(widen_staging_kernel, dim3((unsigned)n), 256u, staging16, sizes, cb_base, staging);
 }
 
-// ---- the n-frame RGB proxy calls: n colour frames at 1/2^reduce, or a window of them, every stage ONE launch over the 3 n
-// planes (plane z = component z % 3 of frame z / 3, table z % 3).  What a context holds for them:
-struct RgbProxyCtx {
+// ---- THE decode sequence of every frame call -- grey or RGB, 1 or n frames, whole, at 1/2^reduce or a window: the
+// intake of the streams, the decoder over the call's codeblocks, the synthesis, its tail; every stage ONE launch over the
+// call's planes.  Grey: a plane a frame.  Colour: 3 n planes, plane z = component z % 3 of frame z / 3, table z % 3.
+// n = 1 sets BpcArgs::frames = 1 (colour: 3), the single-frame launch.  What a context holds for it:
+struct DecodeCtx {
     int aw, ah, wl, ncb;
     bool lossy; float qs; bool fast_div; int off;
     size_t P, extra;
+    bool rgb = false;         // colour: `a` holds the three tables on one coder grid (bpc_args_rgb), w 3 n planes
+    bool cp3 = false;         // -cp 3 (picsong_decode_frame alone, through the staging)
     bool direct;              // the decoder reads the streams itself (else: through the staging)
     bool compact;             // -k > 0: the launch takes the COMPACT table copies
     uint32_t max_stream;      // a worst-case stream's shorts
     int *flag;                // the intake's damage flag
 };
-// `a`: the three tables on one coder grid (bpc_args_rgb); w: a workspace of 3 n planes.
-// picsong_decode_rgb_frames_reduced (reduce = 0: picsong_decode_rgb_frames): the intake of the 3 n streams, the decoder
-// over the reduced corner's codeblocks of every plane, the synthesis down to level `reduce`, the inverse colour transform
-// -- in the finest level's launch (run_inverse_rgb, grid.z = frame) where the single-frame call takes that form and every
-// frame's planes are 4-byte aligned (fuse_tail: the caller's switches permitting), else on its own, one launch a frame.
-// Frame f's planes of (aw >> reduce) x (ah >> reduce) bytes at r / g / b + f * frame_stride.  *fused: the first form ran.
+// what a call took, for those who ask (the drivers' return bits)
+struct DecodeReport {
+    bool pixels;              // grey: the finest level wrote the pixels itself
+    bool c16;                 // the coefficients travelled as int16
+    bool fused10;             // levels reduce + 1 and reduce ran as one launch (run_inverse)
+    bool rgb_tail;            // colour: the fused tail ran (run_inverse_rgb)
+    bool vec;                 // colour window: the epilogue's vector form ran
+};
+// The head: the intake, the call's rectangle (every codeblock, the reduced corner, or win's table), the synthesis plan
+// (none for a window: the cone's synthesis reads 32-bit coefficients) -- planned ahead of the decoder, for it says
+// whether this call's coefficients can travel as int16 -- and the decoder's one grid.  pixels: the grey destination
+// (frames pix_stride bytes apart) the finest level may write itself.
 template <class Go>
-int decode_rgb_frames_reduced(const Go &go, const RgbProxyCtx &c, BpcArgs a, const Workspace &w, unsigned n, const uint16_t *streams,
-                              size_t stream_stride, int reduce, bool want_c16, bool lean97, bool fuse_tail, uint8_t *r, uint8_t *g,
-                              uint8_t *b, unsigned long long frame_stride, bool *fused = nullptr)
+int decode_head(const Go &go, const DecodeCtx &c, BpcArgs &a, const Workspace &w, unsigned n, const uint16_t *streams, size_t stream_stride,
+                int reduce, const WindowPlan *win, bool want_c16, uint8_t *pixels, size_t pix_stride, std::vector<InvLaunch> &plan,
+                DecodeReport &rep)
 {
-    const unsigned np = 3u * n;
-    if (n <= 1) frame_stride = 0;
-    if (fused) *fused = false;
+    const unsigned np = c.rgb ? 3u * n : n;
+    rep = DecodeReport();
     if (int rc = stream_intake(go, streams, np, stream_stride, c.direct, c.ncb, c.P, w, c.flag)) return rc;
     int wpf = (c.ncb + 1) / 2;
-    if (reduce > 0) {
+    if (win) {
+        wpf = window_bpc_table(a, *win);
+    } else if (reduce > 0) {
         const ReducedRect q = reduced_rect(c.aw, c.ah, reduce);
         a.ncx_r = q.ncx_r; a.ncb_r = q.ncx_r * q.ncy_r;
         wpf = reduced_waves(q);
     }
     a.cb_base = 0; a.nCB = c.ncb;
-    a.frames = (int)np; a.waves_per_frame = rgb_component_waves(a.k > 0.0f, wpf);
-    // (the synthesis is planned first: it says whether this call's coefficients can travel as int16)
-    const std::vector<InvLaunch> plan = plan_inverse_frames(w.coef_i, w.coef, nullptr, nullptr, np, 0, want_c16 && c.direct, true, reduce,
-                                                            c.aw, c.ah, c.wl, c.qs, c.fast_div, c.off, c.P, c.extra);
-    const bool c16 = plan_inv_is_c16(plan);
-    a.coef_z = (unsigned long long)c.P * (c16 ? 2ull : 4ull);
-    if (int rc = launch_decoder(go, a, false, np * (unsigned)a.waves_per_frame, c.compact, w, c.direct ? streams : nullptr, stream_stride,
-                                c.max_stream, c16)) return rc;
-    const bool px_aligned = ((((uintptr_t)r) | ((uintptr_t)g) | ((uintptr_t)b) | frame_stride) & 3u) == 0;
-    if (fuse_tail && px_aligned && inv_rgb_tail_ok(plan, c.lossy)) {
-        if (fused) *fused = true;
-        return run_inverse_rgb(go, c.lossy, lean97, plan, c.off, r, g, b, n, frame_stride);
-    }
-    if (int rc = run_inverse(go, c.lossy, lean97, plan, np)) return rc;
+    a.frames = (int)np; a.waves_per_frame = c.rgb ? rgb_component_waves(a.k > 0.0f, wpf) : wpf;
+    if (!win)
+        plan = plan_inverse_frames(w.coef_i, w.coef, pixels, &rep.pixels, np, pix_stride, want_c16 && c.direct, c.rgb, reduce, c.aw, c.ah,
+                                   c.wl, c.qs, c.fast_div, c.off, c.P, c.extra);
+    rep.c16 = plan_inv_is_c16(plan);
+    a.coef_z = (unsigned long long)c.P * (rep.c16 ? 2ull : 4ull);
+    return launch_decoder(go, a, c.cp3, np * (unsigned)a.waves_per_frame, c.compact, w, c.direct ? streams : nullptr, stream_stride,
+                          c.max_stream, rep.c16);
+}
+// The grey calls (picsong_decode_frame, picsong_decode_frames, their _reduced and _window forms): frame f's pixels of
+// level `reduce`, row stride aw >> reduce, at out + f * frame_stride -- written by the finest level where its vector
+// kernel applies, else by a clamp a frame; win: frame f's window of that level, row stride pitch.
+template <class Go>
+int decode_frames(const Go &go, const DecodeCtx &c, BpcArgs a, const Workspace &w, unsigned n, const uint16_t *streams, size_t stream_stride,
+                  int reduce, const WindowPlan *win, bool want_c16, bool lean97, uint8_t *out, size_t frame_stride, size_t pitch,
+                  DecodeReport *report = nullptr)
+{
+    DecodeReport mine, &rep = report ? *report : mine;
+    std::vector<InvLaunch> plan;
+    if (n <= 1) frame_stride = 0;
+    if (int rc = decode_head(go, c, a, w, n, streams, stream_stride, reduce, win, want_c16, out, frame_stride, plan, rep)) return rc;
     const size_t z = (c.P + c.extra) * 4, n4 = (size_t)(c.aw >> reduce) * (size_t)(c.ah >> reduce) / 4;
+    if (win) return run_window(go, c.lossy, *win, w.coef_i, w.coef, c.P, c.aw, c.ah, c.qs, c.off, n, (unsigned long long)c.P * 4ull, z, out, pitch, frame_stride);
+    if (int rc = run_inverse(go, c.lossy, lean97, plan, n, &rep.fused10)) return rc;
+    // (level `reduce`'s samples of frame f: c.extra elements into its work buffer when reduce = 0)
+    for (unsigned f = 0; f < n && !rep.pixels; f++)
+        if (int rc = clamp_pixels(go, c.lossy, (const char *)plan.back().a.dst + f * z, out + f * frame_stride, n4, c.off)) return rc;
+    return 0;
+}
+// The colour calls (picsong_decode_rgb_frame, picsong_decode_rgb_frames, their _reduced and _window forms, the image
+// calls over them), frames frame_stride bytes apart.
+// win == nullptr: frame f's planes of (aw >> reduce) x (ah >> reduce) bytes at d0 / d1 / d2 + f * frame_stride.  The inverse
+// colour transform in the finest level's launch (run_inverse_rgb, grid.z = frame) where the plan has that form and every
+// frame's planes are 4-byte aligned (fuse_tail: the caller's switches permitting), else on its own, one launch a frame.
+// win: run_window with frames = 3 n, level r's samples left compact in the planes' work buffers, and the epilogue
+// (window_rgb_image_kernel, grid.z = frame) that stores them in `layout`: d0 .. d2 frame 0's R, G, B planes
+// (kLayoutPlanar3), or d0 its interleaved pixels; rows `pitch` bytes apart.  One frame into planar planes: window_rgb_kernel.
+template <class Go>
+int decode_rgb_frames(const Go &go, const DecodeCtx &c, BpcArgs a, const Workspace &w, unsigned n, const uint16_t *streams,
+                      size_t stream_stride, int reduce, const WindowPlan *win, bool want_c16, bool lean97, bool fuse_tail, int layout,
+                      uint8_t *d0, uint8_t *d1, uint8_t *d2, size_t pitch, size_t frame_stride, DecodeReport *report = nullptr)
+{
+    DecodeReport mine, &rep = report ? *report : mine;
+    std::vector<InvLaunch> plan;
+    if (n <= 1) frame_stride = 0;
+    if (int rc = decode_head(go, c, a, w, n, streams, stream_stride, reduce, win, want_c16, nullptr, 0, plan, rep)) return rc;
+    const size_t z = (c.P + c.extra) * 4, n4 = (size_t)(c.aw >> reduce) * (size_t)(c.ah >> reduce) / 4;
+    if (win) {
+        if (int rc = run_window(go, c.lossy, *win, w.coef_i, w.coef, c.P, c.aw, c.ah, c.qs, c.off, 3u * n, (unsigned long long)c.P * 4ull, z,
+                                nullptr, 0, 0)) return rc;
+        const IRect &o = win->R[win->r];
+        // (one frame into planar planes keeps the per-pixel epilogue: measured against the n-frame one, profiles/NOTES.md)
+        if (n == 1 && layout == kLayoutPlanar3) {
+            const dim3 grid((unsigned)((o.x1 - o.x0 + 255) / 256), (unsigned)(o.y1 - o.y0));
+            return c.lossy ? go(window_rgb_kernel<float>, grid, 256u, (const float *)w.coef, (unsigned long long)z, o.x1 - o.x0, o.y1 - o.y0, d0, d1, d2, (unsigned long long)pitch, c.off)
+                           : go(window_rgb_kernel<int>, grid, 256u, (const int *)w.coef, (unsigned long long)z, o.x1 - o.x0, o.y1 - o.y0, d0, d1, d2, (unsigned long long)pitch, c.off);
+        }
+        const WinRgbArgs ra = window_rgb_args(layout, w.coef, z, o.x1 - o.x0, o.y1 - o.y0, d0, d1, d2, pitch, frame_stride, n, c.off);
+        const WinRgbLaunch l = select_window_rgb(c.lossy, layout, ra, n);
+        rep.vec = l.vec;
+        return go(l.kernel, l.grid, 256u, ra);
+    }
+    const bool px_aligned = ((((uintptr_t)d0) | ((uintptr_t)d1) | ((uintptr_t)d2) | frame_stride) & 3u) == 0;
+    rep.rgb_tail = fuse_tail && px_aligned && inv_rgb_tail_ok(plan, c.lossy);
+    if (rep.rgb_tail) return run_inverse_rgb(go, c.lossy, lean97, plan, c.off, d0, d1, d2, n, frame_stride);
+    if (int rc = run_inverse(go, c.lossy, lean97, plan, 3u * n, &rep.fused10)) return rc;
     for (unsigned f = 0; f < n; f++) {
         // (level `reduce`'s samples of frame f's components: c.extra elements into their work buffers when reduce = 0)
         const char *img = (const char *)plan.back().a.dst + (size_t)(3 * f) * z;
-        const size_t at = (size_t)f * (size_t)frame_stride;
-        if (int rc = rgb_inverse(go, c.lossy, img, img + z, img + 2 * z, r + at, g + at, b + at, n4, c.off)) return rc;
+        const size_t at = (size_t)f * frame_stride;
+        if (int rc = rgb_inverse(go, c.lossy, img, img + z, img + 2 * z, d0 + at, d1 + at, d2 + at, n4, c.off)) return rc;
     }
     return 0;
 }
-// picsong_decode_rgb_frames_window and picsong_decode_rgb_images_window: the intake, the decoder over the window plan's
-// rectangle table of every plane (32-bit coefficients: what the cone's synthesis reads), run_window with frames = 3 n,
-// level r's samples left compact in the planes' work buffers, and the epilogue (window_rgb_image_kernel, grid.z = frame)
-// that stores them in `layout`: d0 .. d2 frame 0's R, G, B planes (kLayoutPlanar3), or d0 its interleaved pixels; rows
-// `pitch`, frames frame_stride bytes apart.  *vec: the epilogue's vector form ran.
+// The colour sequence's two forms under the names and signatures the n-frame RGB proxy calls introduced them with, for
+// callers written against those (a context they filled says nothing of colour or -cp 3: set here).  *fused: the fused tail
+// ran; *vec: the epilogue's vector form ran.
+using RgbProxyCtx = DecodeCtx;
 template <class Go>
-int decode_rgb_frames_window(const Go &go, const RgbProxyCtx &c, BpcArgs a, const Workspace &w, unsigned n, const uint16_t *streams,
+int decode_rgb_frames_reduced(const Go &go, RgbProxyCtx c, const BpcArgs &a, const Workspace &w, unsigned n, const uint16_t *streams,
+                              size_t stream_stride, int reduce, bool want_c16, bool lean97, bool fuse_tail, uint8_t *r, uint8_t *g,
+                              uint8_t *b, unsigned long long frame_stride, bool *fused = nullptr)
+{
+    DecodeReport rep = DecodeReport();
+    c.rgb = true; c.cp3 = false;
+    const int rc = decode_rgb_frames(go, c, a, w, n, streams, stream_stride, reduce, nullptr, want_c16, lean97, fuse_tail, kLayoutPlanar3, r, g,
+                                     b, 0, (size_t)frame_stride, &rep);
+    if (fused) *fused = rep.rgb_tail;
+    return rc;
+}
+template <class Go>
+int decode_rgb_frames_window(const Go &go, RgbProxyCtx c, const BpcArgs &a, const Workspace &w, unsigned n, const uint16_t *streams,
                              size_t stream_stride, const WindowPlan &win, int layout, uint8_t *d0, uint8_t *d1, uint8_t *d2, size_t pitch,
                              size_t frame_stride, bool *vec = nullptr)
 {
-    const unsigned np = 3u * n;
-    if (int rc = stream_intake(go, streams, np, stream_stride, c.direct, c.ncb, c.P, w, c.flag)) return rc;
-    const int wpf = window_bpc_table(a, win);
-    a.cb_base = 0; a.nCB = c.ncb;
-    a.frames = (int)np; a.waves_per_frame = rgb_component_waves(a.k > 0.0f, wpf);
-    a.coef_z = (unsigned long long)c.P * 4ull;
-    if (int rc = launch_decoder(go, a, false, np * (unsigned)a.waves_per_frame, c.compact, w, c.direct ? streams : nullptr, stream_stride,
-                                c.max_stream, false)) return rc;
-    const unsigned long long z = (unsigned long long)(c.P + c.extra) * 4ull;
-    if (int rc = run_window(go, c.lossy, win, w.coef_i, w.coef, c.P, c.aw, c.ah, c.qs, c.off, np, (unsigned long long)c.P * 4ull, z, nullptr,
-                            0, 0)) return rc;
-    const IRect &o = win.R[win.r];
-    const WinRgbArgs ra = window_rgb_args(layout, w.coef, z, o.x1 - o.x0, o.y1 - o.y0, d0, d1, d2, pitch, frame_stride, n, c.off);
-    const WinRgbLaunch l = select_window_rgb(c.lossy, layout, ra, n);
-    if (vec) *vec = l.vec;
-    return go(l.kernel, l.grid, 256u, ra);
+    DecodeReport rep = DecodeReport();
+    c.rgb = true; c.cp3 = false;
+    const int rc = decode_rgb_frames(go, c, a, w, n, streams, stream_stride, win.r, &win, false, false, false, layout, d0, d1, d2, pitch,
+                                     frame_stride, &rep);
+    if (vec) *vec = rep.vec;
+    return rc;
 }
 
 // ---- the pack of n frames' codeblocks, frame after frame in w (sizes, offsets, totals) and in the staging (P words a
@@ -401,7 +455,7 @@ int emit_frames(const Go &go, int layout, const uint8_t *padded, size_t padded_s
 // bytes, R, G, B back to back per frame, 16-byte aligned, so the fused tail runs where the plan has it -- then ONE emit of
 // the visible rw x rh pixels of the n frames into the caller's layout
 template <class Go>
-int decode_rgb_images_reduced(const Go &go, const RgbProxyCtx &c, const BpcArgs &a, const Workspace &w, unsigned n, const uint16_t *streams,
+int decode_rgb_images_reduced(const Go &go, const DecodeCtx &c, const BpcArgs &a, const Workspace &w, unsigned n, const uint16_t *streams,
                               size_t stream_stride, int reduce, bool want_c16, bool lean97, bool fuse_tail, uint8_t *lay, int layout,
                               void *data, size_t pitch, size_t plane_stride, size_t frame_stride, int rw, int rh)
 {

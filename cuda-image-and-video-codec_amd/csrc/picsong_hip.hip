@@ -643,24 +643,12 @@ int picsong_dwt_forward_tail(picsong_ctx *c, void *d_out, void *stream)
     return launch_fwd_levels(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, plan, 1);
 }
 
-// The frame paths' synthesis plan (plan_inverse_frames, launch_plan.hpp) of this context, and its launches
-static std::vector<InvLaunch> inverse_plan(picsong_ctx *c, const int32_t *d_in, void *d_out, uint8_t *d_pixels, bool *fused,
-                                           unsigned frames, size_t pix_stride, bool want_c16, bool planes_out = false,
-                                           int reduce = 0)
-{
-    return plan_inverse_frames(d_in, d_out, d_pixels, fused, frames, pix_stride, want_c16, planes_out, reduce, c->aw, c->ah,
-                               c->p.wl, c->p.qs, c->fast_div, level_off(c), c->P, c->extra);
-}
-static int run_inverse(picsong_ctx *c, const std::vector<InvLaunch> &plan, hipStream_t s, unsigned frames = 1)
-{
-    return picsong::run_inverse(HipGo{ s }, c->p.lossy != 0, lean97_levels(), plan, frames);
-}
-
 int picsong_dwt_inverse(picsong_ctx *c, const int32_t *d_in, void *d_out, void *stream)
 {
     if (!c || !d_in || !d_out) return fail(PICSONG_ERR_ARG, "dwt_inverse: null argument");
     // (32-bit coefficients, no pixels: a launch per level, plan_dwt_inv2 never applies)
-    return run_inverse(c, plan_dwt_inverse(d_in, d_out, c->aw, c->ah, c->p.wl, c->p.qs, c->fast_div), (hipStream_t)stream);
+    return run_inverse(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, lean97_levels(),
+                       plan_dwt_inverse(d_in, d_out, c->aw, c->ah, c->p.wl, c->p.qs, c->fast_div));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -755,18 +743,6 @@ int picsong_bpc_encode(picsong_ctx *c, const void *d_coeffs, int32_t *d_staging,
     return bpc_encode_widened(c, d_coeffs, d_staging, d_sizes, (hipStream_t)stream, 0);
 }
 
-// The decoder's codeblocks in a call at 1/2^reduce resolution (reduced_rect; reduce = 0: every codeblock, the fields
-// stay 0): sets BpcArgs::ncx_r / ncb_r and returns the waves of one frame.
-// win != nullptr (window calls): the plan's rectangle table instead (BpcArgs::win_n, window_bpc_table)
-static int decode_rect(const picsong_ctx *c, BpcArgs &a, int reduce, const WindowPlan *win = nullptr)
-{
-    if (win) return window_bpc_table(a, *win);
-    if (reduce == 0) return (c->ncb + 1) / 2;
-    const ReducedRect q = reduced_rect(c->aw, c->ah, reduce);
-    a.ncx_r = q.ncx_r; a.ncb_r = q.ncx_r * q.ncy_r;
-    return reduced_waves(q);
-}
-
 // PICSONG_DEC_STAGING=1: the frame paths unpack into the 32-bit staging first, as picsong_bitstream_unpack +
 // picsong_bpc_decode do (A/B of the decoder that reads the stream itself)
 static bool dec_from_stream(const picsong_ctx *c)
@@ -782,20 +758,16 @@ static int stream_intake(picsong_ctx *c, const uint16_t *d_streams, unsigned n, 
     return picsong::stream_intake(HipGo{ s }, d_streams, n, stride, direct, c->ncb, c->P, w, c->d_flag);
 }
 
-// The decoder launch of every path (launch_seq.hpp): `waves` waves over w, from the packed streams where d_streams is set
-static int launch_decoder(picsong_ctx *c, BpcArgs &a, unsigned waves, bool compact, const Workspace &w,
-                          const uint16_t *d_streams, size_t stride, bool c16, hipStream_t s)
+// a decoder launch refused (kLaunchRefused, launch_seq.hpp) as the ABI's error
+static int refused_rc(int rc)
 {
-    const int rc = picsong::launch_decoder(HipGo{ s }, a, c->p.cp == 3, waves, compact, w, d_streams, stride,
-                                           (uint32_t)picsong_max_stream_shorts(c->aw, c->ah), c16);
     return rc == kLaunchRefused ? fail(PICSONG_ERR_ARG, "the 16-bit coefficient form decodes from the stream itself") : rc;
 }
 
-// One frame's decoder over the context's own scratch: d_staging / d_sizes / d_coeffs may be the caller's arrays
-// reduce > 0: only the codeblocks of the 1/2^reduce image's corner (decode_rect); win: only a window's (decode_rect)
+// One plane's decoder (the stage calls, picsong_decode_plane) over the context's own scratch: every codeblock, 32-bit
+// coefficients; d_staging / d_sizes / d_coeffs may be the caller's arrays; d_stream16: from the packed stream itself
 static int bpc_decode_impl(picsong_ctx *c, const int32_t *d_staging, const int32_t *d_sizes, int32_t *d_coeffs,
-                           hipStream_t s, int comp = 0, const uint16_t *d_stream16 = nullptr, bool c16 = false,
-                           int reduce = 0, const WindowPlan *win = nullptr)
+                           hipStream_t s, int comp = 0, const uint16_t *d_stream16 = nullptr)
 {
     BpcArgs a;
     int rc = bpc_args(c, a, comp);
@@ -803,17 +775,8 @@ static int bpc_decode_impl(picsong_ctx *c, const int32_t *d_staging, const int32
     if (int rc2 = ensure_plane_scratch(c)) return rc2;      // the decoder parks its finished planes there too
     Workspace w = c->one;
     w.staging = const_cast<int32_t *>(d_staging); w.sizes = const_cast<int32_t *>(d_sizes); w.coef_i = d_coeffs;
-    const unsigned waves = (unsigned)decode_rect(c, a, reduce, win);
-    return launch_decoder(c, a, waves, a.k > 0.0f && bulk_compact(c, comp), w, d_stream16, 0, c16, s);
-}
-
-// a frame path's decoder: the stream's intake, then the coder -- reading the stream itself, or the staging
-static int decode_stream_impl(picsong_ctx *c, const uint16_t *d_stream, int32_t *d_coeffs, hipStream_t s, int comp,
-                              bool c16 = false, int reduce = 0, const WindowPlan *win = nullptr)
-{
-    const bool direct = dec_from_stream(c);
-    if (int rc = stream_intake(c, d_stream, 1u, 0, direct, c->one, s)) return rc;
-    return bpc_decode_impl(c, c->one.staging, c->one.sizes, d_coeffs, s, comp, direct ? d_stream : nullptr, c16, reduce, win);
+    return refused_rc(launch_decoder(HipGo{ s }, a, c->p.cp == 3, (unsigned)(c->ncb + 1) / 2, a.k > 0.0f && bulk_compact(c, comp), w,
+                                     d_stream16, 0, (uint32_t)picsong_max_stream_shorts(c->aw, c->ah), false));
 }
 
 int picsong_bpc_decode(picsong_ctx *c, const int32_t *d_staging, const int32_t *d_sizes, int32_t *d_coeffs,
@@ -1004,45 +967,6 @@ static int reduced_args_ok(const picsong_ctx *c, int reduce, const char *who)
     return PICSONG_OK;
 }
 
-// The windowed synthesis (run_window, launch_seq.hpp) of `frames` frames of this context
-static int run_window(picsong_ctx *c, const WindowPlan &w, const int32_t *coef_i, void *work, unsigned frames,
-                      unsigned long long coef_z, unsigned long long work_z, uint8_t *u8, size_t pitch,
-                      unsigned long long u8_z, hipStream_t s)
-{
-    return picsong::run_window(HipGo{ s }, c->p.lossy != 0, w, coef_i, work, c->P, c->aw, c->ah, c->p.qs, level_off(c), frames,
-                               coef_z, work_z, u8, pitch, u8_z);
-}
-
-// picsong_decode_frame (reduce = 0) and picsong_decode_frame_reduced: the pixels of level `reduce`, row stride AW >> reduce
-// win != nullptr (picsong_decode_frame_window): the window of level `reduce`, row stride pitch
-static int decode_frame_impl(picsong_ctx *c, const uint16_t *d_stream, uint8_t *d_frame_out, hipStream_t s, int reduce,
-                             const WindowPlan *win = nullptr, size_t pitch = 0)
-{
-    int rc = ensure_workspace(c, true);
-    if (rc) return rc;
-    if (win) {      // the decoder over the window's codeblocks (32-bit coefficients), then the cone's synthesis
-        if ((rc = decode_stream_impl(c, d_stream, c->one.coef_i, s, 0, false, reduce, win))) return rc;
-        return run_window(c, *win, c->one.coef_i, c->one.coef, 1u, 0, 0, d_frame_out, pitch, 0, s);
-    }
-    // (16-bit coefficients between the decoder and the synthesis where the context's magnitudes are bounded and this
-    // call's pointers take the vector kernels: c->c16_dec, plan_inv_is_c16)
-    bool fused = false;
-    const std::vector<InvLaunch> plan = inverse_plan(c, c->one.coef_i, c->one.coef, d_frame_out, &fused, 1, 0,
-                                                     dec_c16_reduced(c, reduce) && dec_from_stream(c), false, reduce);
-    if ((rc = decode_stream_impl(c, d_stream, c->one.coef_i, s, 0, plan_inv_is_c16(plan), reduce))) return rc;
-    if ((rc = run_inverse(c, plan, s))) return rc;
-    if (fused) return PICSONG_OK;            // the finest level wrote the pixels itself
-    // (level `reduce`'s samples, packed: c->extra elements in when reduce = 0)
-    return clamp_pixels(HipGo{ s }, c->p.lossy != 0, plan.back().a.dst, d_frame_out,
-                        (size_t)(c->aw >> reduce) * (size_t)(c->ah >> reduce) / 4, level_off(c));
-}
-
-int picsong_decode_frame(picsong_ctx *c, const uint16_t *d_stream, uint8_t *d_frame_out, void *stream)
-{
-    if (!c || !d_frame_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame: null argument");
-    return decode_frame_impl(c, d_stream, d_frame_out, (hipStream_t)stream, 0);
-}
-
 int picsong_reduced_dims(const picsong_ctx *c, int reduce, int *rw, int *rh, int *paw, int *pah, int *n_codeblocks)
 {
     if (!c || !rw || !rh || !paw || !pah || !n_codeblocks) return fail(PICSONG_ERR_ARG, "reduced_dims: null argument");
@@ -1052,13 +976,6 @@ int picsong_reduced_dims(const picsong_ctx *c, int reduce, int *rw, int *rh, int
     reduced_dims(c->p.width, c->p.height, c->aw, c->ah, reduce, d);
     *rw = d[0]; *rh = d[1]; *paw = d[2]; *pah = d[3]; *n_codeblocks = d[4];
     return PICSONG_OK;
-}
-
-int picsong_decode_frame_reduced(picsong_ctx *c, const uint16_t *d_stream, int reduce, uint8_t *d_out, void *stream)
-{
-    if (!c || !d_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame_reduced: null argument");
-    if (int rc = reduced_args_ok(c, reduce, "decode_frame_reduced")) return rc;
-    return decode_frame_impl(c, d_stream, d_out, (hipStream_t)stream, reduce);
 }
 
 // the refusals the window calls share (nothing is launched); sets *plan
@@ -1083,16 +1000,6 @@ int picsong_window_codeblocks(const picsong_ctx *c, int reduce, int x, int y, in
     if (int rc = window_args_ok(c, reduce, x, y, w, h, "window_codeblocks", &plan)) return rc;
     *n_codeblocks = plan.n_cb;
     return PICSONG_OK;
-}
-
-int picsong_decode_frame_window(picsong_ctx *c, const uint16_t *d_stream, int reduce, int x, int y, int w, int h,
-                                uint8_t *d_out, size_t out_pitch, void *stream)
-{
-    if (!c || !d_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame_window: null argument");
-    WindowPlan plan;
-    if (int rc = window_args_ok(c, reduce, x, y, w, h, "decode_frame_window", &plan)) return rc;
-    if (out_pitch < (size_t)w) return fail(PICSONG_ERR_ARG, "decode_frame_window: out_pitch %zu < w %d", out_pitch, w);
-    return decode_frame_impl(c, d_stream, d_out, (hipStream_t)stream, reduce, &plan, out_pitch);
 }
 
 int picsong_encode_stripe_coded(picsong_ctx *c, const void *d_coeffs, int cb_begin, int cb_count, uint16_t *d_stream,
@@ -1231,8 +1138,47 @@ int picsong_last_totals(picsong_ctx *c, void *stream, int n, int *h_totals)
     return PICSONG_OK;
 }
 
-// n frames decoded through ONE launch per stage: the mirror of picsong_encode_frames (unpack with blockIdx.y =
-// frame, one decoder grid over n x nCB codeblocks, grid.z = frame for the inverse transform's levels)
+// What the decode sequences (decode_frames and decode_rgb_frames, launch_seq.hpp) take from a context: its geometry and
+// switches, the tables of `a` (grey: component 0's; rgb: the three, bpc_args_rgb)
+static DecodeCtx decode_ctx(picsong_ctx *c, const BpcArgs &a, bool rgb)
+{
+    DecodeCtx g;
+    g.aw = c->aw; g.ah = c->ah; g.wl = c->p.wl; g.ncb = c->ncb;
+    g.lossy = c->p.lossy != 0; g.qs = c->p.qs; g.fast_div = c->fast_div; g.off = level_off(c);
+    g.P = c->P; g.extra = c->extra;
+    g.rgb = rgb; g.cp3 = c->p.cp == 3;
+    g.direct = dec_from_stream(c);
+    g.compact = a.k > 0.0f && bulk_compact(c, 0, rgb ? 3 : 1);
+    g.max_stream = (uint32_t)picsong_max_stream_shorts(c->aw, c->ah);
+    g.flag = c->d_flag;
+    return g;
+}
+
+// n grey frames decoded through ONE launch per stage (decode_frames, launch_seq.hpp): the mirror of picsong_encode_frames.
+// n = 1: on the frame's own workspace, what the single-frame calls have always used (and picsong_last_total reads);
+// n > 1: on the batch's.  The arguments have passed the caller's checks.
+static int decode_grey(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_out, size_t frame_stride,
+                       void *stream, int reduce, const WindowPlan *win = nullptr, size_t pitch = 0)
+{
+    int rc;
+    if (n == 1) {
+        if ((rc = ensure_workspace(c, true))) return rc;
+        if ((rc = ensure_plane_scratch(c))) return rc;      // the decoder parks its finished planes there too
+    } else {
+        HIP_TRY(hipSetDevice(c->device));
+        if ((rc = ensure_batch(c, n))) return rc;
+        c->last_batch = -1;                                 // the batch buffers hold a decode now: no encode totals to hand out
+        if ((rc = ensure_coef_i(c, n))) return rc;
+    }
+    BpcArgs a;
+    if ((rc = bpc_args(c, a, 0))) return rc;
+    // (16-bit coefficients between the decoder and the synthesis where the context's magnitudes are bounded and this
+    // call's pointers take the vector kernels: dec_c16_reduced, plan_inv_is_c16)
+    return refused_rc(decode_frames(HipGo{ (hipStream_t)stream }, decode_ctx(c, a, false), a, n == 1 ? c->one : c->batch, (unsigned)n,
+                                    d_streams, stream_stride, reduce, win, dec_c16_reduced(c, reduce), lean97_levels(), d_out,
+                                    frame_stride, pitch));
+}
+
 // picsong_decode_frames (reduce = 0) and picsong_decode_frames_reduced: frame f's pixels of level `reduce` at
 // d_frames_out + f * frame_stride, row stride AW >> reduce
 // win != nullptr (picsong_decode_frames_window): frame f's window of level `reduce` at d_frames_out + f * frame_stride,
@@ -1252,43 +1198,32 @@ static int decode_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, 
     const size_t span = win ? (size_t)(win->R[reduce].y1 - win->R[reduce].y0 - 1) * pitch + (size_t)(win->R[reduce].x1 - win->R[reduce].x0) : px;
     if (n > 1 && (stream_stride < picsong_max_stream_shorts(c->aw, c->ah) || frame_stride < span))
         return fail(PICSONG_ERR_ARG, "%s: strides %zu shorts / %zu bytes too small", who, stream_stride, frame_stride);
-    if (n == 1) return decode_frame_impl(c, d_streams, d_frames_out, (hipStream_t)stream, reduce, win, pitch);
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_batch(c, n);
-    if (rc) return rc;
-    c->last_batch = -1;                                     // the batch buffers hold a decode now: no encode totals to hand out
-    if ((rc = ensure_coef_i(c, n))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    // ---- intake: lengths, offsets (and, when the coder does not read the streams itself, codewords) of the n streams
-    const bool direct = dec_from_stream(c);
-    if ((rc = stream_intake(c, d_streams, (unsigned)n, stream_stride, direct, c->batch, s))) return rc;
-    // ---- decoder: one grid over the n frames' codeblock pairs, both plane-count classes
-    BpcArgs a;
-    if ((rc = bpc_args(c, a, 0))) return rc;
-    const int wpf = decode_rect(c, a, reduce, win);
-    a.cb_base = 0; a.nCB = c->ncb;
-    // (the synthesis is planned first: it says whether this call's coefficients can travel as int16; a window's
-    // synthesis reads 32-bit ones)
-    bool fused = false;
-    const std::vector<InvLaunch> plan = win ? std::vector<InvLaunch>()
-                                            : inverse_plan(c, c->batch.coef_i, c->batch.coef, d_frames_out, &fused, (unsigned)n,
-                                                           frame_stride, dec_c16_reduced(c, reduce) && direct, false, reduce);
-    const bool c16 = plan_inv_is_c16(plan);
-    a.frames = n; a.waves_per_frame = wpf; a.coef_z = (unsigned long long)c->P * (c16 ? 2ull : 4ull);
-    if ((rc = launch_decoder(c, a, (unsigned)n * (unsigned)wpf, a.k > 0.0f && bulk_compact(c, 0), c->batch,
-                             direct ? d_streams : nullptr, stream_stride, c16, s))) return rc;
-    if (win)
-        return run_window(c, *win, c->batch.coef_i, c->batch.coef, (unsigned)n, (unsigned long long)c->P * 4ull,
-                          (unsigned long long)(c->P + c->extra) * 4ull, d_frames_out, pitch, frame_stride, s);
-    // ---- inverse transform, pixels out of the finest level where its vector kernel applies
-    if ((rc = run_inverse(c, plan, s, (unsigned)n))) return rc;
-    if (fused) return PICSONG_OK;
-    for (int f = 0; f < n; f++) {
-        // (level `reduce`'s samples of frame f: c->extra elements into its work buffer when reduce = 0)
-        const void *img = (const char *)plan.back().a.dst + (size_t)f * (c->P + c->extra) * 4;
-        if ((rc = clamp_pixels(HipGo{ s }, c->p.lossy != 0, img, d_frames_out + (size_t)f * frame_stride, px / 4, level_off(c)))) return rc;
-    }
-    return PICSONG_OK;
+    return decode_grey(c, n, d_streams, stream_stride, d_frames_out, frame_stride, stream, reduce, win, pitch);
+}
+
+// The single-frame calls: the n = 1 case of the same sequence, on the frame's own workspace.  picsong_decode_frame takes
+// what a context holds, -cp 3 through the staging included.
+int picsong_decode_frame(picsong_ctx *c, const uint16_t *d_stream, uint8_t *d_frame_out, void *stream)
+{
+    if (!c || !d_frame_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame: null argument");
+    return decode_grey(c, 1, d_stream, 0, d_frame_out, 0, stream, 0);
+}
+
+int picsong_decode_frame_reduced(picsong_ctx *c, const uint16_t *d_stream, int reduce, uint8_t *d_out, void *stream)
+{
+    if (!c || !d_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame_reduced: null argument");
+    if (int rc = reduced_args_ok(c, reduce, "decode_frame_reduced")) return rc;
+    return decode_grey(c, 1, d_stream, 0, d_out, 0, stream, reduce);
+}
+
+int picsong_decode_frame_window(picsong_ctx *c, const uint16_t *d_stream, int reduce, int x, int y, int w, int h,
+                                uint8_t *d_out, size_t out_pitch, void *stream)
+{
+    if (!c || !d_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame_window: null argument");
+    WindowPlan plan;
+    if (int rc = window_args_ok(c, reduce, x, y, w, h, "decode_frame_window", &plan)) return rc;
+    if (out_pitch < (size_t)w) return fail(PICSONG_ERR_ARG, "decode_frame_window: out_pitch %zu < w %d", out_pitch, w);
+    return decode_grey(c, 1, d_stream, 0, d_out, 0, stream, reduce, &plan, out_pitch);
 }
 
 int picsong_decode_frames(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_frames_out,
@@ -1366,7 +1301,10 @@ int picsong_decode_plane(picsong_ctx *c, const uint16_t *d_stream, int comp, voi
     int rc = ensure_workspace(c, true);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = decode_stream_impl(c, d_stream, c->one.coef_i, s, comp))) return rc;
+    // (the stream's intake, then the coder -- reading the stream itself, or the staging)
+    const bool direct = dec_from_stream(c);
+    if ((rc = stream_intake(c, d_stream, 1u, 0, direct, c->one, s))) return rc;
+    if ((rc = bpc_decode_impl(c, c->one.staging, c->one.sizes, c->one.coef_i, s, comp, direct ? d_stream : nullptr))) return rc;
     return picsong_dwt_inverse(c, c->one.coef_i, d_plane_out, stream);
 }
 
@@ -1392,51 +1330,19 @@ static int bpc_args_rgb(picsong_ctx *c, BpcArgs &a)
     return PICSONG_OK;
 }
 
-// An RGB frame's colour transform and the forward transform of its three components (rgb_forward_transform,
-// launch_seq.hpp), component k's coefficients into c->batch.coef + k * (P + extra) * 4 bytes (ensure_batch(3) and
-// ensure_coef_i(3) done); *c16: the coefficient form this call's plan delivers.  The head of picsong_encode_rgb_frame
-// and picsong_train_rgb_frame.
-// (the fused head's buffer loads want all three planes 16-byte aligned like a grey frame's)
+// The colour transform and the forward transform of n RGB frames' 3 n components (rgb_forward_transform, launch_seq.hpp),
+// plane z's coefficients into c->batch.coef + z * (P + extra) * 4 bytes (ensure_batch(3 n) and ensure_coef_i(3 n) done);
+// *c16: the coefficient form this call's plan delivers.  The head of picsong_encode_rgb_frames and picsong_train_rgb_frame.
+// (the fused head's buffer loads want all three planes, and every frame's with them, 16-byte aligned like a grey frame's)
 static bool rgb_planes_aligned(const uint8_t *r, const uint8_t *g, const uint8_t *b) { return ((((uintptr_t)r) | ((uintptr_t)g) | ((uintptr_t)b)) & 15u) == 0; }
 static int rgb_forward_transform(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, hipStream_t s,
-                                 bool *c16)
+                                 bool *c16, int n = 1, size_t frame_stride = 0)
 {
     const bool lossy = c->p.lossy != 0;
+    const bool fuse = c->c16 && rgb_planes_aligned(d_r, d_g, d_b) && (n == 1 || (frame_stride & 15u) == 0) && !getenv("PICSONG_RGB_NOFUSE");
     auto plan_of = [c](const void *src, bool u8in) { return plan_dwt_forward(src, u8in, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16); };
-    return picsong::rgb_forward_transform(HipGo{ s }, lossy, c->c16 && rgb_planes_aligned(d_r, d_g, d_b) && !getenv("PICSONG_RGB_NOFUSE"),
-                                          plan_of, true, d_r, d_g, d_b, c->batch.coef_i, c->P, level_off(c), (c->P + c->extra) * 4, c16);
-}
-
-int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
-                             uint16_t *d_streams, size_t stream_stride, void *stream)
-{
-    if (!c || !d_r || !d_g || !d_b || !d_streams) return fail(PICSONG_ERR_ARG, "encode_rgb_frame: null argument");
-    if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "encode_rgb_frame: the context is not an RGB one");
-    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "encode_rgb_frame: -cp 3 codes its planes one by one (picsong_encode_plane)");
-    if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah)) return fail(PICSONG_ERR_ARG, "encode_rgb_frame: stream stride smaller than a worst-case codestream");
-    HIP_TRY(hipSetDevice(c->device));
-    BpcArgs a;
-    int rc = bpc_args_rgb(c, a);
-    if (rc) return rc;
-    if ((rc = ensure_batch(c, 3))) return rc;
-    if ((rc = ensure_coef_i(c, 3))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t coef_z = (c->P + c->extra) * 4;
-    bool c16 = false;
-    if ((rc = rgb_forward_transform(c, d_r, d_g, d_b, s, &c16))) return rc;
-    a.c16 = c16 ? 1 : 0;
-    // ---- coder: one grid over the three components' codeblock pairs, component f with table f
-    a.coeffs_in = c->batch.coef; a.is_float = c->p.lossy ? 1 : 0;
-    a.staging16 = reinterpret_cast<uint16_t *>(c->batch.staging);
-    a.sizes = c->batch.sizes; a.plane_scratch = c->batch.plane_scratch; a.coef_z = coef_z;
-    if ((rc = launch_encoder(c, a, 3u * (unsigned)a.waves_per_frame, 0, 3, s))) return rc;
-    // ---- pack: the populated header on the components of header_mask
-    uint16_t hdr[PICSONG_HDR_SHORTS];
-    if (header_mask & 7) picsong_header_pack(&c->p, hdr);
-    if ((rc = pack_frames(HipGo{ s }, a.staging16, c->batch, c->ncb, 3u, (header_mask & 7) ? hdr : nullptr, -(header_mask & 7), d_streams,
-                          c->P, stream_stride))) return rc;
-    c->last_batch = 3;
-    return PICSONG_OK;
+    return picsong::rgb_forward_transform(HipGo{ s }, lossy, fuse, plan_of, true, d_r, d_g, d_b, c->batch.coef_i, c->P, level_off(c),
+                                          (c->P + c->extra) * 4, c16, nullptr, (unsigned)n, frame_stride);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1769,81 +1675,6 @@ int picsong_encode_rgb_frame_quality(picsong_ctx *c, const uint8_t *d_r, const u
     const RateJob job = { 1, nullptr, 0, d_r, d_g, d_b, 0, header_mask, d_streams, stream_stride, false };
     if (int rc = search_args_ok(c, job, kRgbFrame, kSearchQuality, h_j && h_totals && h_sse, who)) return rc;
     return search_impl(c, job, kSearchQuality, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_totals, h_sse, who);
-}
-
-// picsong_decode_rgb_frame (reduce = 0) and picsong_decode_rgb_frame_reduced: the three components' level `reduce`,
-// then the inverse colour transform over its (AW >> reduce) x (AH >> reduce) samples
-// win != nullptr (picsong_decode_rgb_frame_window): the window of level `reduce`, the planes' row stride pitch
-static int decode_rgb_impl(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_r, uint8_t *d_g,
-                           uint8_t *d_b, void *stream, int reduce, const char *who, const WindowPlan *win = nullptr,
-                           size_t pitch = 0)
-{
-    if (!c || !d_streams || !d_r || !d_g || !d_b) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
-    if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "%s: the context is not an RGB one", who);
-    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 3 decodes its planes one by one (picsong_decode_plane)", who);
-    if (!reduce_ok(c->p.wl, reduce))
-        return fail(PICSONG_ERR_ARG, "%s: reduce %d outside 0..%d (wl - 1)", who, reduce, c->p.wl - 1);
-    if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah)) return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
-    HIP_TRY(hipSetDevice(c->device));
-    BpcArgs a;
-    int rc = bpc_args_rgb(c, a);
-    if (rc) return rc;
-    a.waves_per_frame = rgb_component_waves(a, decode_rect(c, a, reduce, win));
-    if ((rc = ensure_batch(c, 3))) return rc;
-    if ((rc = ensure_coef_i(c, 3))) return rc;
-    c->last_batch = -1;
-    hipStream_t s = (hipStream_t)stream;
-    const bool direct = dec_from_stream(c);
-    if ((rc = stream_intake(c, d_streams, 3u, stream_stride, direct, c->batch, s))) return rc;
-    // (16-bit coefficients between the decoder and the synthesis where the context's magnitudes are bounded: the
-    // plan says whether this call's arrays take the vector kernels; a window's synthesis reads 32-bit ones)
-    const std::vector<InvLaunch> plan = win ? std::vector<InvLaunch>()
-                                            : inverse_plan(c, c->batch.coef_i, c->batch.coef, nullptr, nullptr, 3u, 0,
-                                                           dec_c16_reduced(c, reduce) && direct, true, reduce);
-    const bool c16 = plan_inv_is_c16(plan);
-    a.coef_z = (unsigned long long)c->P * (c16 ? 2ull : 4ull);
-    if ((rc = launch_decoder(c, a, 3u * (unsigned)a.waves_per_frame, a.k > 0.0f && bulk_compact(c, 0, 3), c->batch,
-                             direct ? d_streams : nullptr, stream_stride, c16, s))) return rc;
-    if (win) {      // the three components' cones (grid.z = component), then the inverse RCT / ICT over the window
-        const unsigned long long z = (unsigned long long)(c->P + c->extra) * 4ull;
-        if ((rc = run_window(c, *win, c->batch.coef_i, c->batch.coef, 3u, (unsigned long long)c->P * 4ull, z, nullptr, 0, 0, s))) return rc;
-        const IRect &o = win->R[reduce];
-        return window_rgb(HipGo{ s }, c->p.lossy != 0, c->batch.coef, z, o.x1 - o.x0, o.y1 - o.y0, d_r, d_g, d_b, pitch, level_off(c));
-    }
-    // 16-bit coefficients: the finest level of the three components and the inverse colour transform as ONE launch
-    // (run_inverse_rgb; PICSONG_RGB_NOFUSE=1 keeps the two; 9/7: the lean kernel's domain)
-    const bool px_aligned = ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 3u) == 0;
-    bool tail = inv_rgb_tail_ok(plan, c->p.lossy != 0) && px_aligned && !getenv("PICSONG_RGB_NOFUSE");
-    if (tail && c->p.lossy) tail = !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0);
-    if (tail) return run_inverse_rgb(HipGo{ s }, c->p.lossy != 0, lean97_levels(), plan, level_off(c), d_r, d_g, d_b);
-    if ((rc = run_inverse(c, plan, s, 3u))) return rc;
-    const char *img = (const char *)plan.back().a.dst;      // (level `reduce`: c->extra elements in when reduce = 0)
-    const size_t z = (c->P + c->extra) * 4;
-    return rgb_inverse(HipGo{ s }, c->p.lossy != 0, img, img + z, img + 2 * z, d_r, d_g, d_b,
-                       (size_t)(c->aw >> reduce) * (size_t)(c->ah >> reduce) / 4, level_off(c));
-}
-
-int picsong_decode_rgb_frame(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_r, uint8_t *d_g,
-                             uint8_t *d_b, void *stream)
-{
-    return decode_rgb_impl(c, d_streams, stream_stride, d_r, d_g, d_b, stream, 0, "decode_rgb_frame");
-}
-
-int picsong_decode_rgb_frame_reduced(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, int reduce, uint8_t *d_r,
-                                     uint8_t *d_g, uint8_t *d_b, void *stream)
-{
-    return decode_rgb_impl(c, d_streams, stream_stride, d_r, d_g, d_b, stream, reduce, "decode_rgb_frame_reduced");
-}
-
-int picsong_decode_rgb_frame_window(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
-                                    int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, size_t out_pitch, void *stream)
-{
-    const char *who = "decode_rgb_frame_window";
-    if (!c || !d_streams || !d_r || !d_g || !d_b) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
-    WindowPlan plan;
-    if (int rc = window_args_ok(c, reduce, x, y, w, h, who, &plan)) return rc;
-    if (out_pitch < (size_t)w) return fail(PICSONG_ERR_ARG, "%s: out_pitch %zu < w %d", who, out_pitch, w);
-    return decode_rgb_impl(c, d_streams, stream_stride, d_r, d_g, d_b, stream, reduce, who, &plan, out_pitch);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2209,9 +2040,9 @@ int picsong_decode_rgb_image(picsong_ctx *c, const uint16_t *d_streams, size_t s
 
 // ---------------------------------------------------------------------------------------------
 // batched RGB frames: n colour frames through ONE launch per stage, 3 n planes a launch -- plane z = component z % 3 of
-// frame z / 3 (the sequences: rgb_forward_transform, decode_rgb_frames_reduced and decode_rgb_frames_window, launch_seq.hpp; the
-// argument checks: rgb_frames_refusal and its proxy forms, kernel_select.hpp).  n = 1 launches what picsong_encode_rgb_frame /
-// picsong_decode_rgb_frame launch.
+// frame z / 3 (the sequences: rgb_forward_transform and decode_rgb_frames, launch_seq.hpp; the argument checks:
+// rgb_frames_refusal and its proxy forms, kernel_select.hpp).  The single-frame calls (picsong_encode_rgb_frame,
+// picsong_decode_rgb_frame and its _reduced and _window forms) are the n = 1 case: frame_stride 0, first_iter 0.
 // ---------------------------------------------------------------------------------------------
 static int rgb_frames_args(picsong_ctx *c, int n, const void *r, const void *g, const void *b, const void *streams, size_t frame_stride,
                            size_t stream_stride, const char *who, BpcArgs &a)
@@ -2225,30 +2056,24 @@ static int rgb_frames_args(picsong_ctx *c, int n, const void *r, const void *g, 
     return PICSONG_OK;
 }
 
-int picsong_encode_rgb_frames(picsong_ctx *c, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, size_t frame_stride,
-                              int first_iter, int header_mask, uint16_t *d_streams, size_t stream_stride, void *stream)
+static int encode_rgb_frames_impl(picsong_ctx *c, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, size_t frame_stride,
+                                  int first_iter, int header_mask, uint16_t *d_streams, size_t stream_stride, void *stream, const char *who)
 {
     BpcArgs a;
-    int rc = rgb_frames_args(c, n, d_r, d_g, d_b, d_streams, frame_stride, stream_stride, "encode_rgb_frames", a);
+    int rc = rgb_frames_args(c, n, d_r, d_g, d_b, d_streams, frame_stride, stream_stride, who, a);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const unsigned np = 3u * (unsigned)n;
     if ((rc = ensure_batch(c, (int)np))) return rc;
     if ((rc = ensure_coef_i(c, (int)np))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const size_t coef_z = (c->P + c->extra) * 4;
-    const bool lossy = c->p.lossy != 0;
-    // (the fused head: all three planes 16-byte aligned, and every frame's with them)
-    const bool fuse = c->c16 && rgb_planes_aligned(d_r, d_g, d_b) && (n == 1 || (frame_stride & 15u) == 0) && !getenv("PICSONG_RGB_NOFUSE");
-    auto plan_of = [c](const void *src, bool u8in) { return plan_dwt_forward(src, u8in, c->batch.coef, c->aw, c->ah, c->p.wl, c->p.qs, c->c16); };
     bool c16 = false;
-    if ((rc = picsong::rgb_forward_transform(HipGo{ s }, lossy, fuse, plan_of, true, d_r, d_g, d_b, c->batch.coef_i, c->P, level_off(c), coef_z,
-                                             &c16, nullptr, (unsigned)n, frame_stride))) return rc;
+    if ((rc = rgb_forward_transform(c, d_r, d_g, d_b, s, &c16, n, frame_stride))) return rc;
     a.c16 = c16 ? 1 : 0;
     // ---- coder: one grid over the 3 n planes' codeblock pairs, plane z with table z % 3
-    a.coeffs_in = c->batch.coef; a.is_float = lossy ? 1 : 0;
+    a.coeffs_in = c->batch.coef; a.is_float = c->p.lossy ? 1 : 0;
     a.staging16 = reinterpret_cast<uint16_t *>(c->batch.staging);
-    a.sizes = c->batch.sizes; a.plane_scratch = c->batch.plane_scratch; a.coef_z = coef_z;
+    a.sizes = c->batch.sizes; a.plane_scratch = c->batch.plane_scratch; a.coef_z = (c->P + c->extra) * 4;
     if ((rc = launch_encoder(c, a, np * (unsigned)a.waves_per_frame, 0, 3, s))) return rc;
     // ---- pack: the populated header on the components of header_mask, on the video's frame 0 where the call holds it
     uint16_t hdr[PICSONG_HDR_SHORTS];
@@ -2259,30 +2084,49 @@ int picsong_encode_rgb_frames(picsong_ctx *c, int n, const uint8_t *d_r, const u
     return PICSONG_OK;
 }
 
-// What the n-frame RGB decode sequences (launch_seq.hpp) take from a context of 3 n planes: the tables on one coder grid, the
-// batch workspace grown to the call, the context's geometry and switches.  The arguments have passed their refusal.
-static int rgb_proxy_begin(picsong_ctx *c, int n, BpcArgs &a, RgbProxyCtx &g)
+int picsong_encode_rgb_frames(picsong_ctx *c, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, size_t frame_stride,
+                              int first_iter, int header_mask, uint16_t *d_streams, size_t stream_stride, void *stream)
+{
+    return encode_rgb_frames_impl(c, n, d_r, d_g, d_b, frame_stride, first_iter, header_mask, d_streams, stream_stride, stream,
+                                  "encode_rgb_frames");
+}
+
+int picsong_encode_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
+                             uint16_t *d_streams, size_t stream_stride, void *stream)
+{
+    return encode_rgb_frames_impl(c, 1, d_r, d_g, d_b, 0, 0, header_mask, d_streams, stream_stride, stream, "encode_rgb_frame");
+}
+
+// The colour decode calls, their arguments past their refusal: the tables on one coder grid and the batch workspace grown
+// to the 3 n planes ...
+static int decode_rgb_begin(picsong_ctx *c, int n, BpcArgs &a)
 {
     if (int rc = bpc_args_rgb(c, a)) return rc;             // (the tables' geometry)
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_batch(c, 3 * n)) return rc;
     if (int rc = ensure_coef_i(c, 3 * n)) return rc;
     c->last_batch = -1;
-    g.aw = c->aw; g.ah = c->ah; g.wl = c->p.wl; g.ncb = c->ncb;
-    g.lossy = c->p.lossy != 0; g.qs = c->p.qs; g.fast_div = c->fast_div; g.off = level_off(c);
-    g.P = c->P; g.extra = c->extra;
-    g.direct = dec_from_stream(c);
-    g.compact = a.k > 0.0f && bulk_compact(c, 0, 3);
-    g.max_stream = (uint32_t)picsong_max_stream_shorts(c->aw, c->ah);
-    g.flag = c->d_flag;
     return PICSONG_OK;
 }
-static int proxy_rc(int rc)
+// ... the fused tails (grid.z = frame), read per call: PICSONG_RGB_NOFUSE=1 keeps the two launches; 9/7: the lean kernel's domain
+static bool rgb_tail_switch(const picsong_ctx *c)
 {
-    return rc == kLaunchRefused ? fail(PICSONG_ERR_ARG, "the 16-bit coefficient form decodes from the stream itself") : rc;
+    if (getenv("PICSONG_RGB_NOFUSE")) return false;
+    return !c->p.lossy || !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0);
+}
+// ... then the sequence (decode_rgb_frames, launch_seq.hpp): whole or at 1/2^reduce into the planes d0 .. d2, or win's
+// window in `layout`
+static int decode_rgb(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, const WindowPlan *win, int layout,
+                      uint8_t *d0, uint8_t *d1, uint8_t *d2, size_t pitch, size_t frame_stride, void *stream)
+{
+    BpcArgs a;
+    if (int rc = decode_rgb_begin(c, n, a)) return rc;
+    return refused_rc(decode_rgb_frames(HipGo{ (hipStream_t)stream }, decode_ctx(c, a, true), a, c->batch, (unsigned)n, d_streams,
+                                        stream_stride, reduce, win, dec_c16_reduced(c, reduce), lean97_levels(), rgb_tail_switch(c), layout,
+                                        d0, d1, d2, pitch, frame_stride));
 }
 
-// picsong_decode_rgb_frames (reduce = 0) and picsong_decode_rgb_frames_reduced
+// picsong_decode_rgb_frames (reduce = 0), picsong_decode_rgb_frames_reduced and their n = 1 forms
 static int decode_rgb_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, uint8_t *d_r,
                                   uint8_t *d_g, uint8_t *d_b, size_t frame_stride, void *stream, const char *who)
 {
@@ -2290,16 +2134,7 @@ static int decode_rgb_frames_impl(picsong_ctx *c, int n, const uint16_t *d_strea
     if (const char *why = rgb_frames_reduced_refusal(c->p.is_rgb != 0, c->p.cp, true, n, d_r, d_g, d_b, d_streams, frame_stride, stream_stride,
                                                      picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce))
         return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
-    BpcArgs a;
-    RgbProxyCtx g;
-    if (int rc = rgb_proxy_begin(c, n, a, g)) return rc;
-    // the fused tails (grid.z = frame) where the single-frame call takes them (PICSONG_RGB_NOFUSE=1 keeps the two launches;
-    // 9/7: the lean kernel's domain)
-    bool tail = !getenv("PICSONG_RGB_NOFUSE");
-    if (tail && g.lossy) tail = !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0);
-    return proxy_rc(picsong::decode_rgb_frames_reduced(HipGo{ (hipStream_t)stream }, g, a, c->batch, (unsigned)n, d_streams, stream_stride,
-                                                       reduce, dec_c16_reduced(c, reduce), lean97_levels(), tail, d_r, d_g, d_b,
-                                                       frame_stride));
+    return decode_rgb(c, n, d_streams, stream_stride, reduce, nullptr, kLayoutPlanar3, d_r, d_g, d_b, 0, frame_stride, stream);
 }
 
 int picsong_decode_rgb_frames(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_r, uint8_t *d_g,
@@ -2314,6 +2149,18 @@ int picsong_decode_rgb_frames_reduced(picsong_ctx *c, int n, const uint16_t *d_s
     return decode_rgb_frames_impl(c, n, d_streams, stream_stride, reduce, d_r, d_g, d_b, frame_stride, stream, "decode_rgb_frames_reduced");
 }
 
+int picsong_decode_rgb_frame(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, uint8_t *d_r, uint8_t *d_g,
+                             uint8_t *d_b, void *stream)
+{
+    return decode_rgb_frames_impl(c, 1, d_streams, stream_stride, 0, d_r, d_g, d_b, 0, stream, "decode_rgb_frame");
+}
+
+int picsong_decode_rgb_frame_reduced(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, int reduce, uint8_t *d_r,
+                                     uint8_t *d_g, uint8_t *d_b, void *stream)
+{
+    return decode_rgb_frames_impl(c, 1, d_streams, stream_stride, reduce, d_r, d_g, d_b, 0, stream, "decode_rgb_frame_reduced");
+}
+
 // the window calls, their arguments checked: the window's plan against the decoder's scratch, then the sequence
 static int decode_rgb_window_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y, int w,
                                   int h, int layout, uint8_t *d0, uint8_t *d1, uint8_t *d2, size_t pitch, size_t frame_stride, void *stream,
@@ -2321,18 +2168,13 @@ static int decode_rgb_window_impl(picsong_ctx *c, int n, const uint16_t *d_strea
 {
     WindowPlan plan;
     if (int rc = window_args_ok(c, reduce, x, y, w, h, who, &plan)) return rc;
-    BpcArgs a;
-    RgbProxyCtx g;
-    if (int rc = rgb_proxy_begin(c, n, a, g)) return rc;
-    return proxy_rc(picsong::decode_rgb_frames_window(HipGo{ (hipStream_t)stream }, g, a, c->batch, (unsigned)n, d_streams, stream_stride,
-                                                      plan, layout, d0, d1, d2, pitch, frame_stride));
+    return decode_rgb(c, n, d_streams, stream_stride, reduce, &plan, layout, d0, d1, d2, pitch, frame_stride, stream);
 }
 
-int picsong_decode_rgb_frames_window(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
-                                     int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, size_t out_pitch, size_t frame_stride,
-                                     void *stream)
+static int decode_rgb_frames_window_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
+                                         int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, size_t out_pitch, size_t frame_stride,
+                                         void *stream, const char *who)
 {
-    const char *who = "decode_rgb_frames_window";
     if (!c) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     if (const char *why = rgb_frames_window_refusal(c->p.is_rgb != 0, c->p.cp, true, n, d_r, d_g, d_b, d_streams, out_pitch, frame_stride,
                                                     stream_stride, picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce,
@@ -2340,6 +2182,21 @@ int picsong_decode_rgb_frames_window(picsong_ctx *c, int n, const uint16_t *d_st
         return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
     return decode_rgb_window_impl(c, n, d_streams, stream_stride, reduce, x, y, w, h, kLayoutPlanar3, d_r, d_g, d_b, out_pitch, frame_stride,
                                   stream, who);
+}
+
+int picsong_decode_rgb_frames_window(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
+                                     int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, size_t out_pitch, size_t frame_stride,
+                                     void *stream)
+{
+    return decode_rgb_frames_window_impl(c, n, d_streams, stream_stride, reduce, x, y, w, h, d_r, d_g, d_b, out_pitch, frame_stride, stream,
+                                         "decode_rgb_frames_window");
+}
+
+int picsong_decode_rgb_frame_window(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
+                                    int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, size_t out_pitch, void *stream)
+{
+    return decode_rgb_frames_window_impl(c, 1, d_streams, stream_stride, reduce, x, y, w, h, d_r, d_g, d_b, out_pitch, 0, stream,
+                                         "decode_rgb_frame_window");
 }
 
 static int decode_rgb_images_window_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
@@ -2380,15 +2237,12 @@ int picsong_decode_rgb_images_reduced(picsong_ctx *c, int n, const uint16_t *d_s
                                                     dst->layout, dst->data, dst->pitch, dst->plane_stride, frame_stride))
         return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
     BpcArgs a;
-    RgbProxyCtx g;
-    if (int rc = rgb_proxy_begin(c, n, a, g)) return rc;
+    if (int rc = decode_rgb_begin(c, n, a)) return rc;
     const size_t pp = (size_t)d[2] * (size_t)d[3];
     if (int rc = ensure_layout(c, ((size_t)3 * (size_t)n * pp + c->P - 1) / c->P)) return rc;
-    bool tail = !getenv("PICSONG_RGB_NOFUSE");
-    if (tail && g.lossy) tail = !(getenv("PICSONG_DWT_INV97") && atoi(getenv("PICSONG_DWT_INV97")) == 0);
-    return proxy_rc(picsong::decode_rgb_images_reduced(HipGo{ (hipStream_t)stream }, g, a, c->batch, (unsigned)n, d_streams, stream_stride,
-                                                       reduce, dec_c16_reduced(c, reduce), lean97_levels(), tail, c->lay_buf, dst->layout,
-                                                       dst->data, dst->pitch, dst->plane_stride, frame_stride, d[0], d[1]));
+    return refused_rc(decode_rgb_images_reduced(HipGo{ (hipStream_t)stream }, decode_ctx(c, a, true), a, c->batch, (unsigned)n, d_streams,
+                                                stream_stride, reduce, dec_c16_reduced(c, reduce), lean97_levels(), rgb_tail_switch(c),
+                                                c->lay_buf, dst->layout, dst->data, dst->pitch, dst->plane_stride, frame_stride, d[0], d[1]));
 }
 
 static int rgb_images_args(picsong_ctx *c, int n, const picsong_image *img, size_t frame_stride, const void *d_streams, size_t stream_stride,

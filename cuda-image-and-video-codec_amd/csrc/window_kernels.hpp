@@ -201,8 +201,9 @@ __device__ __forceinline__ void window_rgb_px(T yy, T cb, T cr, int off, uint32_
     b = (uint32_t)clamp_u8(B + off);
 }
 
-// RGB window calls: the inverse RCT / ICT of the three components' level-r samples (compact, w x h, row stride w, the
-// components z_stride bytes apart), level shift and clamp into the three pixel planes, row i at r / g / b + i * pitch
+// RGB window calls, one frame into planar planes (decode_rgb_frames, launch_seq.hpp): the inverse RCT / ICT of the three
+// components' level-r samples (compact, w x h, row stride w, the components z_stride bytes apart), level shift and clamp
+// into the three pixel planes, row i at r / g / b + i * pitch
 template <typename T>
 __global__ __launch_bounds__(256) void window_rgb_kernel(const T *c0, unsigned long long z_stride, int w, int h, uint8_t *r,
                                                          uint8_t *g, uint8_t *b, unsigned long long pitch, int off)
@@ -220,10 +221,10 @@ __global__ __launch_bounds__(256) void window_rgb_kernel(const T *c0, unsigned l
     }
 }
 
-// The epilogue of the n-frame RGB proxy calls (picsong_decode_rgb_frames_window, picsong_decode_rgb_images_window and
-// _reduced): the same arithmetic over the w x h windows of n frames, grid.z = frame, stored in the caller's pixel layout
-// -- kLayoutPlanar3 (three plane pointers) or an interleaved layout of layout_kernels.hpp, alpha 255.  There is no planar
-// intermediate and no emit pass.
+// The epilogue of every other RGB window call (n frames, or an interleaved layout: picsong_decode_rgb_frames_window,
+// picsong_decode_rgb_images_window and _reduced): the same arithmetic over the w x h windows of n frames, grid.z = frame,
+// stored in the caller's pixel layout -- kLayoutPlanar3 (three plane pointers) or an interleaved layout of
+// layout_kernels.hpp, alpha 255.  There is no planar intermediate and no emit pass.
 //   A thread converts four adjacent pixels of a row: it reads 3 x 16 bytes (one dwordx4 a component where the source rows
 //   are 16-byte aligned: w a multiple of 4) and stores one dword a plane, three dwords (RGB24 / BGR24, repacked with
 //   byte permutes: layout_store_vec) or 16 bytes (RGBA32 / BGRA32; one dwordx4 where a16).  Threads run along the rows of

@@ -17,13 +17,13 @@ _lib = None
 def driver_lib(so_name, sources, extra_flags=()):
     """The one build recipe of the emulator drivers: tests/hipemu/_build/<so_name> from `sources` (names in
     tests/hipemu) with the CXXFLAGS of tests/hipemu/Makefile and `extra_flags`, rebuilt when it is older than a source,
-    the Makefile, the emulator's header or any csrc/*.hpp; returns it loaded."""
+    the Makefile, the emulator's header, a driver header (tests/hipemu/*.hpp) or any csrc/*.hpp; returns it loaded."""
     so = os.path.join(EMU_DIR, "_build", so_name)
     srcs = [os.path.join(EMU_DIR, f) for f in sources]
     csrc = os.path.join(ROOT, "cuda-image-and-video-codec_amd", "csrc")
     makefile = os.path.join(EMU_DIR, "Makefile")
     deps = srcs + [makefile, os.path.join(EMU_DIR, "hip", "hip_runtime.h")] + \
-        [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
+        [os.path.join(d, f) for d in (csrc, EMU_DIR) for f in os.listdir(d) if f.endswith(".hpp")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
         flags = next(ln.split("=", 1)[1].split() for ln in open(makefile) if ln.startswith("CXXFLAGS"))
         os.makedirs(os.path.dirname(so), exist_ok=True)

@@ -31,9 +31,18 @@ def decode_reduced(stream, AW, AH, wl, lossy, qs, lut, r, k=0.0, c16=True, stagi
     geo = _geo(lut)
     res = lib().emu_decode_reduced(_p(stream), int(stream.size), AW, AH, wl, int(lossy), C.c_float(qs), _p(tab), _p(geo),
                                    C.c_float(k), int(lut.n_tables), int(c16), int(staging), r, _p(coef),
-                                   C.c_void_p(buf.ctypes.data + base), _p(flag))
+                                   C.c_void_p(buf.ctypes.data + base), _p(flag), 1, C.c_size_t(0))
     assert np.all(buf[:base] == 0xA5) and np.all(buf[base + n:] == 0xA5), "bytes written outside the reduced image"
     return buf[base:base + n].reshape(AH >> r, AW >> r), res, int(flag[0]), coef
+
+
+def stack_streams(streams):
+    """The streams as rows of one array, its row length their stride: (array, stride in shorts)."""
+    stride = max(s.size for s in streams)
+    out = np.zeros((len(streams), stride), np.uint16)
+    for i, s in enumerate(streams):
+        out[i, :s.size] = s
+    return out, stride
 
 
 def _stream(W, H, wl, lossy, qs, k, seed=0):
@@ -117,3 +126,43 @@ def test_reduced_decoder_touches_only_the_rectangle(k):
     assert not (written & ~inside).any()
     _, _, flag0, _ = decode_reduced(bad, W, H, wl, False, 1.0, lut, 0, k=k, c16=False)
     assert flag0 == 1                                 # the full decode reads that codeblock
+
+
+# The smallest frame of FRAMES, 9 codeblock columns (every frame of FRAMES is a padded size, a multiple of 64): an odd
+# count, so a wave's two codeblocks straddle codeblock rows and frames; the frame stride is not the frame's size.
+N_FRAMES = (576, 320, 3)
+
+
+@pytest.mark.parametrize("lossy,qs", [(False, 1.0), (True, 0.5)])
+@pytest.mark.parametrize("r", [0, 1])
+def test_reduced_two_grey_frames(lossy, qs, r):
+    """picsong_decode_frames_reduced's n = 2 path through the library's sequence: each frame against the oracle, nothing
+    written between the frames, and the launches counted -- the intake (1), the decoder (1), a synthesis level a launch
+    (wl - r; one fewer where levels r + 1 and r ran as one), and a clamp a frame where level r did not write the
+    pixels itself (a frame stride that is no multiple of 4)."""
+    W, H, wl = N_FRAMES
+    n = 2
+    pairs = [_stream(W, H, wl, lossy, qs, 0.0, seed=s) for s in range(n)]
+    lut = pairs[0][1]
+    streams, stride = stack_streams([p[0] for p in pairs])
+    want = [rr.reduced_pixels(p[0], W, H, wl, lossy, qs, lut, r) for p in pairs]
+    assert not np.array_equal(want[0], want[1])
+    px = (W >> r) * (H >> r)
+    tab, geo = np.ascontiguousarray(lut.table, np.int32), _geo(lut)
+    for gap in (64, 3):
+        fs = px + gap
+        coef = np.full((n, H, W), 0x7A5A5A5A, np.int32)
+        buf = np.full(n * fs + 128, 0xA5, np.uint8)
+        base = (-buf.ctypes.data) % 64
+        flag = np.zeros(1, np.int32)
+        lib().emu_reduce_reset()
+        res = lib().emu_decode_reduced(_p(streams), stride, W, H, wl, int(lossy), C.c_float(qs), _p(tab), _p(geo), C.c_float(0.0),
+                                       int(lut.n_tables), 1, 0, r, _p(coef), C.c_void_p(buf.ctypes.data + base), _p(flag), n,
+                                       C.c_size_t(fs))
+        assert res >= 0 and not res & 8 and flag[0] == 0
+        expect = np.full(buf.size, 0xA5, np.uint8)
+        for f in range(n):
+            expect[base + f * fs:base + f * fs + px] = want[f].ravel()
+        assert np.array_equal(buf, expect), (gap, res)
+        assert bool(res & 1) == (gap % 4 == 0), (gap, res)      # both forms are taken: these levels take the vector kernels
+        assert lib().emu_reduce_launches() == 2 + (wl - r) - (1 if res & 4 else 0) + (0 if res & 1 else n), (gap, res)

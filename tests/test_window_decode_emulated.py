@@ -44,7 +44,7 @@ def decode_window(stream, AW, AH, wl, lossy, qs, lut, r, x, y, w, h, k=0.0, stag
     tab = np.ascontiguousarray(lut.table, np.int32)
     res = lib().emu_decode_window(_p(stream), int(stream.size), AW, AH, wl, int(lossy), C.c_float(qs), _p(tab),
                                   _p(_geo(lut)), C.c_float(k), int(lut.n_tables), int(staging), r, x, y, w, h, _p(coef),
-                                  C.c_void_p(buf.ctypes.data + misalign), C.c_size_t(pitch), _p(flag))
+                                  C.c_void_p(buf.ctypes.data + misalign), C.c_size_t(pitch), _p(flag), 1, C.c_size_t(0))
     full = np.full((h, pitch), 0xA5, np.uint8).reshape(-1)[:n].copy()
     got = buf[misalign:misalign + n]
     mask = np.zeros(n, bool)
@@ -155,3 +155,43 @@ def test_window_decoder_touches_only_the_set(k):
     bad[9 + 2 * (cy * ncx + cx)] = 20
     _, _, flag, _, _ = decode_window(bad, W, H, wl, False, 1.0, lut, r, x, y, w, h, k=k)
     assert flag == 1
+
+
+@pytest.mark.parametrize("lossy,qs", [(False, 1.0), (True, 0.5)])
+def test_window_two_grey_frames(lossy, qs):
+    """picsong_decode_frames_window's n = 2 path through the library's sequence, on the smallest frame of the reduced
+    tests (9 codeblock columns) at r = 1, a window that crosses codeblock boundaries in both directions: each frame's
+    window against the oracle's crop, no byte outside the windows written, and the launches counted -- the intake (1),
+    the decoder (1), a level of the cone a launch (wl - r), whatever n."""
+    W, H, wl, r, n = 576, 320, 3, 1, 2
+    x, y, w, h = 50, 50, 40, 30
+    pairs = [_stream(W, H, wl, lossy, qs, 0.0, seed=s) for s in range(n)]
+    lut = pairs[0][1]
+    stride = max(p[0].size for p in pairs)
+    streams = np.zeros((n, stride), np.uint16)
+    for i, p in enumerate(pairs):
+        streams[i, :p[0].size] = p[0]
+    cbs = wr.window_codeblocks(W, H, wl, lossy, r, x, y, w, h)
+    assert len({cx for cx, _ in cbs}) > 1 and len({cy for _, cy in cbs}) > 1
+    pitch = w + 5
+    span = (h - 1) * pitch + w
+    fs = span + 7
+    coef = np.full((n, H, W), FILL, np.int32)
+    buf = np.full(n * fs + 64, 0xA5, np.uint8)
+    flag = np.zeros(1, np.int32)
+    tab = np.ascontiguousarray(lut.table, np.int32)
+    lib().emu_window_reset()
+    res = lib().emu_decode_window(_p(streams), stride, W, H, wl, int(lossy), C.c_float(qs), _p(tab), _p(_geo(lut)), C.c_float(0.0),
+                                  int(lut.n_tables), 0, r, x, y, w, h, _p(coef), _p(buf), C.c_size_t(pitch), _p(flag), n,
+                                  C.c_size_t(fs))
+    assert res == 0 and flag[0] == 0
+    expect = np.full(buf.size, 0xA5, np.uint8)
+    for f in range(n):
+        full = rr.reduced_pixels(pairs[f][0], W, H, wl, lossy, qs, lut, r)
+        for i in range(h):
+            expect[f * fs + i * pitch:f * fs + i * pitch + w] = full[y + i, x:x + w]
+    assert np.array_equal(buf, expect)
+    for f in range(n):
+        written = (coef[f] != FILL).reshape(H // 64, 64, W // 64, 64).any(axis=(1, 3))
+        assert {(int(cx), int(cy)) for cy, cx in zip(*np.nonzero(written))} <= cbs
+    assert lib().emu_window_launches() == 2 + (wl - r)
