@@ -1049,10 +1049,13 @@ __device__ __forceinline__ void enc_spp_coeff_first_dense(EncCoder &c, uint64_t 
 }
 // The significance pass of rows 32 HW .. 32 HW + 31 at step 0.  BL / BR: the plane's bits of the lane's columns (0 in an
 // idle half), BPL / BNL: lane-1's right and lane+1's left column, sgNL: lane+1's left sign column; onm != 0.
-template <int HW>
+// AT (PICSONG_ENC_OCC8=2): `pl0` is not used; a 4-row group reads the plane's record at byte `recoff` of the image `img`.
+__device__ __forceinline__ PlaneLut plane_lut_at(const uint8_t *img, uint32_t off);
+template <int HW, bool AT = false>
 __device__ __forceinline__ void enc_spp_first_half(EncCoder &c, uint64_t onm, const U64 &BL, const U64 &BR, const U64 &BPL,
                                                    const U64 &BNL, const U64 &sgL, const U64 &sgR, const U64 &sgNL,
-                                                   const PlaneLut &pl, uint32_t prec, uint32_t upper_mask)
+                                                   const PlaneLut &pl0, uint32_t prec, uint32_t upper_mask,
+                                                   const uint8_t *img = nullptr, uint32_t recoff = 0u)
 {
     const ColHalf cpL = make_col(up_of(BPL, HW), up_of(BL, HW), up_of(BR, HW), 0u, 0u, 0u, 0u, 0u,
                                  up_of(BL, HW), up_of(sgL, HW), 0u, 0u, 0u, 0u, 0u, 0u, w_of(sgL, HW));
@@ -1065,6 +1068,9 @@ __device__ __forceinline__ void enc_spp_first_half(EncCoder &c, uint64_t onm, co
 #endif
 #pragma unroll 1
     for (uint32_t g4 = 0u; g4 < 32u; g4 += 4u) {
+        PlaneLut plg = pl0;
+        if constexpr (AT) plg = plane_lut_at(img, recoff);
+        const PlaneLut &pl = plg;
         // left column: contexts 0..3 (the first table word) and sign contexts 0 / 1
         const uint32_t selL = bfi32(0x01010101u, spread4_raw<0>(cpL.n0, g4), spread4_raw<1>(cpL.n1, g4)) & 0x03030303u;
         const uint32_t P4L = __builtin_amdgcn_perm(0u, pl.sig0, selL), P4R = sig_probs4_07(cpR, pl, g4);
@@ -1364,6 +1370,25 @@ __device__ __forceinline__ int bulk_setup(const BpcArgs &a, bool coded, int msb,
 // Gpixel/s while the prologue's halves were two unrolled copies (6 it was), and 190.7 (5) / 195.0 (6) / 203.0 (7) / 194.7 (8)
 // once they were a loop (enc_transpose_pass).  The -k > 0 instantiation asks for 6 (it gets 4: its planes live in registers;
 // the request alone takes a lone frame from 0.536 to 0.465 ms at k = 0.5).
+// PICSONG_ENC_OCC8: the register diet of the k = 0 two-pass encoder (bpc_encode_kernel<false, false>), the eight registers
+// between 72 and 64, in two levels.  =0: every kernel as before.
+// =1 (the default): the neighbour lanes' columns are moved a half-pass at a time, as moves of the shifted words the lane
+// forms for its own columns anyway, not held as whole columns through the plane (two lane moves more a plane); and the next
+// plane's four words leave the scratch after the refinement's first half, not before the pass.
+// =2: also, a plane's probabilities are not held through the plane: the lane keeps the byte offset of its plane record in
+// the LDS image and reads the record where it is used -- one read at the head of a 4-row group of the significance pass
+// (sig0, sig1, sign; sig8 only where the context-8 gate is open), one ds_read_u8 of `ref` at the head of a refinement
+// half-pass.  Nothing is added at a call site or per row at either level.
+// At =2 the kernel fits eight waves a SIMD (64 registers, 112 bytes of scratch, 3 scratch instructions in the plane loops;
+// without the diet 124 bytes and 24; tests/test_encoder_occ8.py holds it there) -- and eight waves LOSE: 8K lossless, six
+// alternating runs, parent 230.8, =2 at eight waves 229.1 Gpixel/s, a lone 8K frame 0.288 / 0.295 ms.  The probe's
+// occupancy curve (tools/valu_probe: +5.6 % from seven to eight waves for the call sites' mix) does not carry over to the
+// coder.  At seven waves =2 costs a lone frame 3 % (0.295 against 0.287 ms: the LDS round trip at every group head is in a
+// lone wave's dependent chain), =1 costs it nothing and gives the headline +2.4 % (233.4 against 228.0 Gpixel/s; the
+// coder's launch 737 -> 720 us with three calls in flight).  Seven waves and =1 it is (profiles/NOTES.md).
+#ifndef PICSONG_ENC_OCC8
+#define PICSONG_ENC_OCC8 1
+#endif
 #ifndef PICSONG_BPC_ENC_WAVES
 #define PICSONG_BPC_ENC_WAVES 7
 #endif
@@ -1404,6 +1429,28 @@ __device__ __forceinline__ void opaque32(uint32_t &x)
 #else
     (void)x;
 #endif
+}
+// PICSONG_ENC_OCC8: the plane record at byte offset `off` of the LDS image, read HERE: no load is moved across the
+// compiler-level memory fence, so the read is not hoisted out of the loop it sits in and its registers kept after all.
+// (The fence is no instruction.  An opaque move of the offset did the same for a v_mov at every group head.)
+__device__ __forceinline__ void read_here(uint32_t off)
+{
+#if defined(__AMDGCN__)
+    asm volatile("" :: "v"(off) : "memory");
+#else
+    (void)off;
+#endif
+}
+__device__ __forceinline__ PlaneLut plane_lut_at(const uint8_t *img, uint32_t off)
+{
+    read_here(off);
+    return plane_lut_img(reinterpret_cast<const PlaneRec *>(img + off), 0, 0);
+}
+// ... and the record's refinement probability alone (byte 0 of its fourth word)
+__device__ __forceinline__ uint32_t plane_ref_at(const uint8_t *img, uint32_t off)
+{
+    read_here(off);
+    return img[off + 12u];
 }
 // the lane's number in its wave, from no register (threadIdx.x & 63 asks for one to be kept, or spilled and reloaded)
 __device__ __forceinline__ uint32_t lane_number()
@@ -1697,6 +1744,9 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
     const LutView lv = { lds_lut + (BULK ? half * kTab : 0u), a.lut, a.g.nRef + a.g.nSig + a.g.nSign,
                          (a.g.nRef + a.g.nSig + a.g.nSign) * (BULK ? a.n_tables : 1), loff };
     const PlaneRec *const recs = reinterpret_cast<const PlaneRec *>(lds_lut) + (level * 3 + sb) * kMaxPlanes;   // k = 0: the lane's group
+    constexpr bool OCC8 = !BULK && PICSONG_ENC_OCC8 != 0;    // neighbour columns a half-pass at a time, the next plane loaded late
+    constexpr bool OCC8R = !BULK && PICSONG_ENC_OCC8 >= 2;   // ... and the plane's record read where it is used (plane_lut_at)
+    const uint32_t recs_off = (uint32_t)((level * 3 + sb) * kMaxPlanes) * (uint32_t)sizeof(PlaneRec);   // ... from this byte offset on
 
     int np = coded ? (msb + 1 - cbp > 0 ? msb + 1 - cbp : 0) : 0;
     { int o = __shfl_xor(np, 32); np = np > o ? np : o; }
@@ -1740,11 +1790,18 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
             const U64 BL = BLn, BR = BRn;
             if (np > 1) load_plane(1, BLn, BRn);
             PlaneLut pl = { 0u, 0u, 0u, 0u, 0u, 0u };
-            if (coded) pl = plane_lut_img(recs, 0, msb);
+            if constexpr (!OCC8R) { if (coded) pl = plane_lut_img(recs, 0, msb); }
             const uint64_t onm = __builtin_amdgcn_ballot_w64(coded);
             const U64 BPL = u_prev(BR, t), BNL = u_next(BL, t), sgNL = u_next(sgL, t);
-            enc_spp_first_half<0>(c, onm, BL, BR, BPL, BNL, sgL, sgR, sgNL, pl, prec, upper_mask);
-            enc_spp_first_half<1>(c, onm, BL, BR, BPL, BNL, sgL, sgR, sgNL, pl, prec, upper_mask);
+            if constexpr (OCC8R) {
+                // (an idle lane reads record 0 of its group: it codes nothing with it)
+                const uint32_t recoff = recs_off + (coded ? (uint32_t)msb : 0u) * (uint32_t)sizeof(PlaneRec);
+                enc_spp_first_half<0, true>(c, onm, BL, BR, BPL, BNL, sgL, sgR, sgNL, pl, prec, upper_mask, lds_lut, recoff);
+                enc_spp_first_half<1, true>(c, onm, BL, BR, BPL, BNL, sgL, sgR, sgNL, pl, prec, upper_mask, lds_lut, recoff);
+            } else {
+                enc_spp_first_half<0>(c, onm, BL, BR, BPL, BNL, sgL, sgR, sgNL, pl, prec, upper_mask);
+                enc_spp_first_half<1>(c, onm, BL, BR, BPL, BNL, sgL, sgR, sgNL, pl, prec, upper_mask);
+            }
             AL = BL; AR = BR;
             p0 = 1;
         }
@@ -1768,7 +1825,9 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
         const bool act = live && bp >= cbp;
 
         PlaneLut pl = { 0u, 0u, 0u, 0u, 0u, 0u };
-        if (act) { if constexpr (BULK) pl = plane_lut<false>(lv, gl, grpc, bp); else pl = plane_lut_img(recs, 0, bp); }
+        uint32_t recoff = recs_off;                          // OCC8: the plane's record (an idle lane: record 0 of its group)
+        if constexpr (OCC8R) { if (act) recoff += (uint32_t)bp * (uint32_t)sizeof(PlaneRec); }
+        if constexpr (!OCC8R) { if (act) { if constexpr (BULK) pl = plane_lut<false>(lv, gl, grpc, bp); else pl = plane_lut_img(recs, 0, bp); } }
 
         const U64 BL = BLn, BR = BRn;
         const U64 AL2 = u_or(AL, BL), AR2 = u_or(AR, BR);            // state after this plane's SPP
@@ -1787,14 +1846,32 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
             // wave still has an insignificant coefficient
 #pragma unroll
             for (int hw = 0; hw < 2; hw++) {
-                const ColHalf cpL = make_col(up_of(APL2, hw), up_of(AL2, hw), up_of(AR2, hw), w_of(APL, hw), w_of(AR, hw),
+                ColHalf cpL, cpR;
+                if constexpr (OCC8) {
+                    // The neighbour columns a half-pass at a time, as moves of what the lane forms for its own columns anyway
+                    // (a neighbour's shifted word is the shifted word's neighbour): nothing of lane-1's and lane+1's columns
+                    // but APL is held from one half-pass into the other -- nine registers of the first half-pass -- for
+                    // two lane moves more a plane (eight a half-pass where the whole columns took twelve a plane).
+                    const uint32_t upL2 = up_of(AL2, hw), upR2 = up_of(AR2, hw), dnL = dn_of(AL, hw), dnR = dn_of(AR, hw);
+                    const uint32_t wL2 = w_of(AL2, hw), nwL2 = from_next32(wL2, t);
+                    cpL = make_col(from_prev32(upR2, t), upL2, upR2, w_of(APL, hw), w_of(AR, hw),
+                                   dn_of(APL, hw), dnL, dnR,
+                                   upL2, up_of(sgL, hw), dnL, dn_of(sgL, hw),
+                                   w_of(APL, hw), from_prev32(w_of(sgR, hw), t), w_of(AR, hw), w_of(sgR, hw), w_of(sgL, hw));
+                    cpR = make_col(upL2, upR2, from_next32(upL2, t), wL2, nwL2,
+                                   dnL, dnR, from_next32(dnL, t),
+                                   upR2, up_of(sgR, hw), dnR, dn_of(sgR, hw),
+                                   wL2, w_of(sgL, hw), nwL2, from_next32(w_of(sgL, hw), t), w_of(sgR, hw));
+                } else {
+                cpL = make_col(up_of(APL2, hw), up_of(AL2, hw), up_of(AR2, hw), w_of(APL, hw), w_of(AR, hw),
                                              dn_of(APL, hw), dn_of(AL, hw), dn_of(AR, hw),
                                              up_of(AL2, hw), up_of(sgL, hw), dn_of(AL, hw), dn_of(sgL, hw),
                                              w_of(APL, hw), w_of(sgPL, hw), w_of(AR, hw), w_of(sgR, hw), w_of(sgL, hw));
-                const ColHalf cpR = make_col(up_of(AL2, hw), up_of(AR2, hw), up_of(ANL2, hw), w_of(AL2, hw), w_of(ANL2, hw),
+                cpR = make_col(up_of(AL2, hw), up_of(AR2, hw), up_of(ANL2, hw), w_of(AL2, hw), w_of(ANL2, hw),
                                              dn_of(AL, hw), dn_of(AR, hw), dn_of(ANL, hw),
                                              up_of(AR2, hw), up_of(sgR, hw), dn_of(AR, hw), dn_of(sgR, hw),
                                              w_of(AL2, hw), w_of(sgL, hw), w_of(ANL2, hw), w_of(sgNL, hw), w_of(sgR, hw));
+                }
                 const uint32_t al = act ? w_of(AL, hw) : 0xFFFFFFFFu, ar = act ? w_of(AR, hw) : 0xFFFFFFFFu;
                 const uint32_t nl = w_of(BL, hw) & ~al, nr = w_of(BR, hw) & ~ar;      // become significant in this plane
                 uint32_t rows = wave_or32(~(al & ar));
@@ -1811,11 +1888,14 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
 #pragma unroll 1
                         for (uint32_t g4 = 0u; g4 < 32u; g4 += 4u) {
                             uint32_t P4L, P4R;
+                            PlaneLut plat;                   // (OCC8: the record, read here)
+                            if constexpr (OCC8R) plat = plane_lut_at(lds_lut, recoff);
+                            const PlaneLut &plg = OCC8R ? plat : pl;
                             if constexpr (GATE8) {
-                                P4L = sig_probs4_07(cpL, pl, g4); P4R = sig_probs4_07(cpR, pl, g4);
-                                if ((m8 >> g4) & 0xFu) { P4L = sig_probs4_fix8(cpL, pl, g4, P4L); P4R = sig_probs4_fix8(cpR, pl, g4, P4R); }
-                            } else { P4L = sig_probs4(cpL, pl, g4); P4R = sig_probs4(cpR, pl, g4); }
-                            const uint32_t Q4L = sign_probs4(cpL, pl, g4), Q4R = sign_probs4(cpR, pl, g4);
+                                P4L = sig_probs4_07(cpL, plg, g4); P4R = sig_probs4_07(cpR, plg, g4);
+                                if ((m8 >> g4) & 0xFu) { P4L = sig_probs4_fix8(cpL, plg, g4, P4L); P4R = sig_probs4_fix8(cpR, plg, g4, P4R); }
+                            } else { P4L = sig_probs4(cpL, plg, g4); P4R = sig_probs4(cpR, plg, g4); }
+                            const uint32_t Q4L = sign_probs4(cpL, plg, g4), Q4R = sign_probs4(cpR, plg, g4);
 #define PS_SPP_ROW(J)                                                                                    \
                             enc_spp_coeff_dense<J>(c, xal, xnl, xsl, P4L, Q4L, prec, upper_mask);         \
                             enc_spp_coeff_dense<J>(c, xar, xnr, xsr, P4R, Q4R, prec, upper_mask);
@@ -1831,11 +1911,14 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
                     uint32_t sub = (rows >> g4) & 0xFu;
                     rows &= ~(0xFu << g4);
                     uint32_t P4L, P4R;
+                    PlaneLut plat;                   // (OCC8: the record, read here)
+                    if constexpr (OCC8R) plat = plane_lut_at(lds_lut, recoff);
+                    const PlaneLut &plg = OCC8R ? plat : pl;
                     if constexpr (GATE8) {
-                        P4L = sig_probs4_07(cpL, pl, g4); P4R = sig_probs4_07(cpR, pl, g4);
-                        if ((m8 >> g4) & 0xFu) { P4L = sig_probs4_fix8(cpL, pl, g4, P4L); P4R = sig_probs4_fix8(cpR, pl, g4, P4R); }
-                    } else { P4L = sig_probs4(cpL, pl, g4); P4R = sig_probs4(cpR, pl, g4); }
-                    const uint32_t Q4L = sign_probs4(cpL, pl, g4), Q4R = sign_probs4(cpR, pl, g4);
+                        P4L = sig_probs4_07(cpL, plg, g4); P4R = sig_probs4_07(cpR, plg, g4);
+                        if ((m8 >> g4) & 0xFu) { P4L = sig_probs4_fix8(cpL, plg, g4, P4L); P4R = sig_probs4_fix8(cpR, plg, g4, P4R); }
+                    } else { P4L = sig_probs4(cpL, plg, g4); P4R = sig_probs4(cpR, plg, g4); }
+                    const uint32_t Q4L = sign_probs4(cpL, plg, g4), Q4R = sign_probs4(cpR, plg, g4);
                     // the group's rows, unrolled: the byte of P4 / Q4 a row takes is then a constant of the
                     // instruction (SDWA), and a row costs two scalar instructions of loop control, not six
                     const uint32_t gbit = 1u << g4;
@@ -1851,13 +1934,18 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
             }
         }
         // the next plane is on its way from the scratch while the refinement pass runs
-        if (p + 1 < np) load_plane(p + 1, BLn, BRn);
+        // (OCC8: after the refinement's first half -- four registers fewer through it)
+        if constexpr (!OCC8) { if (p + 1 < np) load_plane(p + 1, BLn, BRn); }
         // ---- magnitude refinement pass: coefficients significant before this plane
 #pragma unroll
         for (int hw = 0; hw < 2; hw++) {
             const uint32_t ml = act ? w_of(AL, hw) : 0u, mr = act ? w_of(AR, hw) : 0u;
             const uint32_t bl = w_of(BL, hw) & ml, br = w_of(BR, hw) & mr;
             uint32_t rows = wave_or32(ml | mr);
+            if constexpr (OCC8) {
+                if (hw == 1 && p + 1 < np) load_plane(p + 1, BLn, BRn);
+                if constexpr (OCC8R) { if (rows) pl.ref = plane_ref_at(lds_lut, recoff); }
+            }
             const int last = rows ? 32 - __builtin_clz(rows) : 0;           // rows [0, last) hold every row with work
             if (5 * __builtin_popcount(rows) >= 3 * last && last > 0) {
                 // dense half-pass (most rows have work: the lower planes): every row in order, its lane masks
