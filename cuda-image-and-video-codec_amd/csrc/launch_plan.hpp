@@ -41,6 +41,8 @@ inline bool dwt_vec_ok(int W, int aw, const void *p0, const void *p1)
 // Band height per level: big levels want taller bands (less vertical halo re-read), small levels
 // want many short waves (a level with a handful of tall waves is bound by one wave's serial
 // instruction time, not by memory); PICSONG_DWT_BANDS="16,8,4,..." overrides per level.
+// tests/test_dwt_bands.py and tests/test_dwt_bands_gpu.py rely on the override (read at every plan) to run the 8-, 16-
+// and 32-row instantiations at small frames.
 inline int band_rows_override(int level)
 {
     if (const char *e = getenv("PICSONG_DWT_BANDS")) {

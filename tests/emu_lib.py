@@ -99,6 +99,60 @@ def dwt_vec_levels(AW, AH, wl):
     return lib().emu_dwt_vec_levels(_p(a), _p(b), AW, AH, wl)
 
 
+def dwt_plan_bands(AW, AH, wl, lossy=False, fast=False):
+    """What plan_dwt_forward and plan_dwt_inverse choose per level under the current environment: two lists of
+    (band, vec), level 0 first (`fast`: a 9/7 context's verified reciprocal divisions)."""
+    fwd = np.zeros(2 * wl, np.int32)
+    inv = np.zeros(2 * wl, np.int32)
+    lib().emu_dwt_plan_bands(AW, AH, wl, int(lossy), int(fast), _p(fwd), _p(inv))
+    return ([(int(fwd[2 * l]), bool(fwd[2 * l + 1])) for l in range(wl)],
+            [(int(inv[2 * l]), bool(inv[2 * l + 1])) for l in range(wl)])
+
+
+def launch_log_reset():
+    lib().emu_launch_log_reset()
+
+
+def launch_log():
+    """The distinct kernels (function pointers) this library has launched since the last reset."""
+    n = lib().emu_launch_log_read(None, 0)
+    ptrs = (C.c_void_p * max(n, 1))()
+    lib().emu_launch_log_read(ptrs, n)
+    return set(int(p or 0) for p in ptrs[:n])
+
+
+def dwt_selector_kernels():
+    """{function pointer: label} of every kernel select_fwd, select_inv and select_inv_rgb can return for a launch the
+    plans can form."""
+    cap, nb = 512, 128
+    ptrs = (C.c_void_p * cap)()
+    labels = C.create_string_buffer(cap * nb)
+    n = lib().emu_dwt_selector_kernels(ptrs, labels, nb, cap)
+    assert 0 < n <= cap
+    return {int(ptrs[i]): labels.raw[i * nb:(i + 1) * nb].split(b"\0", 1)[0].decode() for i in range(n)}
+
+
+def dwt_forward_n(frames, wl, lossy, qs=1.0, extra=0):
+    """`frames`: (n, AH, AW) uint8 / int32 / float32, one call with grid.z = n; returns (n, P + extra) buffers."""
+    n, AH, AW = frames.shape
+    x = aligned_copy(np.ascontiguousarray(frames))
+    out = aligned_zeros(n * (AW * AH + extra), np.float32 if lossy else np.int32)
+    dwt_forward_n.fused01 = bool(lib().emu_dwt_forward_n(_p(x), int(x.dtype == np.uint8), C.c_ulonglong(AW * AH * x.dtype.itemsize),
+                                                         _p(out), C.c_ulonglong((AW * AH + extra) * 4), AW, AH, wl, int(lossy),
+                                                         C.c_float(qs), n))
+    return out.reshape(n, AW * AH + extra)
+
+
+def dwt_inverse_u8_n(coefs, wl, lossy, qs=1.0, extra=0):
+    """`coefs`: (n, AH, AW) int32 Mallat arrays, one call with grid.z = n; returns (pixels (n, AH, AW), fused flag)."""
+    n, AH, AW = coefs.shape
+    coefs = aligned_copy(np.ascontiguousarray(coefs, np.int32))
+    scratch = aligned_zeros(n * (AW * AH + extra), np.float32 if lossy else np.int32)
+    pix = aligned_zeros(n * AW * AH, np.uint8)
+    fused = lib().emu_dwt_inverse_u8_n(_p(coefs), _p(scratch), _p(pix), AW, AH, wl, int(lossy), C.c_float(qs), n)
+    return pix.reshape(n, AH, AW), bool(fused)
+
+
 def dwt_forward(x, wl, lossy, qs=1.0, extra=0):
     """x: (AH, AW) uint8 (fused level shift) / int32 / float32."""
     AH, AW = x.shape
@@ -119,6 +173,20 @@ def dwt_forward_rgb(r, g, b, wl, extra, lossy=False, qs=1.0):
     if not lib().emu_dwt_forward_rgb(_p(r), _p(g), _p(b), _p(out), C.c_size_t(stride), AW, AH, wl, int(lossy), C.c_float(qs)):
         return None
     return [mallat16(out[k * (AW * AH + extra):(k + 1) * (AW * AH + extra)], AW, AH).copy() for k in range(3)]
+
+
+def dwt_forward_rgb_forms(r, g, b, wl, extra, lossy=False, qs=1.0):
+    """dwt_forward_rgb where the fused head may refuse (PICSONG_DWT_NOFUSE01=1: the colour transform on its own, then
+    every level through dwt_fwd_kernel): (the three components' Mallat arrays -- int16, or 32-bit ones where the plan left
+    the 16-bit form --, fused flag)."""
+    AH, AW = r.shape
+    r, g, b = (aligned_copy(np.ascontiguousarray(x, np.uint8)) for x in (r, g, b))
+    n = AW * AH + extra
+    out = aligned_zeros(3 * n, np.int32)
+    bits = lib().emu_dwt_forward_rgb_forms(_p(r), _p(g), _p(b), _p(out), C.c_size_t(n * 4), AW, AH, wl, int(lossy), C.c_float(qs))
+    if bits & 2:
+        return [mallat16(out[k * n:(k + 1) * n], AW, AH).copy() for k in range(3)], bool(bits & 1)
+    return [out[k * n:k * n + AW * AH].view(np.float32 if lossy else np.int32).reshape(AH, AW).copy() for k in range(3)], bool(bits & 1)
 
 
 def dwt_forward_band(x_u8, out, wl, lossy, qs, row0, rows):

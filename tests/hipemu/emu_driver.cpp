@@ -7,9 +7,33 @@
 
 #include "../../cuda-image-and-video-codec_amd/csrc/launch_seq.hpp"
 
+#include <string>
+
 using namespace picsong;
 
-static const emu::Go go{};
+// The launcher of this driver, in the idiom of CountGo (emu_decode_ctx.hpp): it notes WHICH kernel it is handed before it
+// forwards to emu::Go.  The log keeps every distinct function pointer once, in the order of its first launch, so that a
+// whole suite's launches do not grow it; tests/test_dwt_bands.py reads it against emu_dwt_selector_kernels.
+static std::vector<const void *> g_launch_log;
+struct RecordGo {
+    template <typename K, typename... A>
+    int operator()(K k, dim3 grid, unsigned threads, const A &...args) const
+    {
+        const void *p = reinterpret_cast<const void *>(k);
+        bool seen = false;
+        for (const void *q : g_launch_log) seen = seen || q == p;
+        if (!seen) g_launch_log.push_back(p);
+        return emu::Go{}(k, grid, threads, args...);
+    }
+};
+static const RecordGo go{};
+extern "C" void emu_launch_log_reset(void) { g_launch_log.clear(); }
+// the distinct kernels launched since the reset: the first `cap` of them into ptrs, their number returned
+extern "C" int emu_launch_log_read(const void **ptrs, int cap)
+{
+    for (int i = 0; i < cap && i < (int)g_launch_log.size(); i++) ptrs[i] = g_launch_log[(size_t)i];
+    return (int)g_launch_log.size();
+}
 
 // what picsong_ctx_create decides once per context (cached here per (qs, wl))
 static bool emu_fast_div(int lossy, float qs, int wl)
@@ -18,7 +42,9 @@ static bool emu_fast_div(int lossy, float qs, int wl)
     static int c_wl = -1;
     static bool c_ok = false;
     if (!lossy) return false;
-    if (getenv("PICSONG_DWT_EXACTDIV") || qs != c_qs || wl != c_wl) { c_ok = dequant_fast_ok(qs, wl); c_qs = qs; c_wl = wl; }
+    // (what the switch forces is not cached: a later call without it at the same qs and wl takes its own verdict)
+    if (getenv("PICSONG_DWT_EXACTDIV")) return dequant_fast_ok(qs, wl);
+    if (qs != c_qs || wl != c_wl) { c_ok = dequant_fast_ok(qs, wl); c_qs = qs; c_wl = wl; }
     return c_ok;
 }
 extern "C" int emu_dequant_fast_ok(float qs, int wl) { return dequant_fast_ok(qs, wl) ? 1 : 0; }
@@ -59,6 +85,77 @@ int emu_dwt_vec_levels(const void *in, void *out, int aw, int ah, int wl)
     return n;
 }
 
+// Host only, the twin of emu_dwt_vec_levels: what the plans choose per level under the current environment, out[2 l] =
+// the band height of level l and out[2 l + 1] = its vec flag, for plan_dwt_forward (u8 input) and for plan_dwt_inverse
+// (`fast`: the context's verified reciprocal divisions, 9/7 only -- what sends the plan to inv97_band_rows).  The plans
+// see 64-byte aligned pointers and dereference nothing.
+void emu_dwt_plan_bands(int aw, int ah, int wl, int lossy, int fast, int *out_fwd, int *out_inv)
+{
+    const void *in = (const void *)(uintptr_t)4096;
+    void *out = (void *)(uintptr_t)8192;
+    for (const FwdLaunch &f : plan_dwt_forward(in, true, out, aw, ah, wl, 1.0f)) {
+        out_fwd[2 * f.a.level] = f.band; out_fwd[2 * f.a.level + 1] = f.vec ? 1 : 0;
+    }
+    int l = wl - 1;
+    for (const InvLaunch &f : plan_dwt_inverse((const int32_t *)in, out, aw, ah, wl, 1.0f, lossy != 0 && fast != 0)) {
+        out_inv[2 * l] = f.band; out_inv[2 * l + 1] = f.vec ? 1 : 0;
+        l--;
+    }
+}
+
+// Host only: every kernel select_fwd, select_inv and select_inv_rgb (kernel_select.hpp) can return for a launch the plans
+// can form -- band 4 / 8 / 16 / 32; vec, u8, lossy; fast, lean97, c16, dst_u8, first, one_div.  What the plans never
+// form is left out: the 16-bit form and the pixel store off the vector kernels (plan_dwt_inverse, plan_inverse_frames),
+// fast without lossy, 9/7 16-bit coefficients without the verified divisions or on the coarsest level that also writes
+// pixels (dec_c16_ok).  The distinct pointers into ptrs, a label each (the first combination that gave it) into labels +
+// i * label_bytes; returns their number (beyond cap: counted, not written).
+int emu_dwt_selector_kernels(const void **ptrs, char *labels, int label_bytes, int cap)
+{
+    std::vector<const void *> seen;
+    auto add = [&](const void *p, const std::string &label) {
+        for (const void *q : seen) if (q == p) return;
+        if ((int)seen.size() < cap) {
+            ptrs[seen.size()] = p;
+            snprintf(labels + seen.size() * (size_t)label_bytes, (size_t)label_bytes, "%s", label.c_str());
+        }
+        seen.push_back(p);
+    };
+    auto s = [](const char *name, int v) { return std::string(" ") + name + "=" + std::to_string(v); };
+    static uint8_t pixel;
+    const int bands[4] = { 4, 8, 16, 32 };
+    for (int band : bands)
+        for (int lossy = 0; lossy < 2; lossy++) {
+            for (int vec = 0; vec < 2; vec++)
+                for (int u8 = 0; u8 < 2; u8++) {
+                    FwdLaunch f;
+                    memset(&f, 0, sizeof f);
+                    f.band = band; f.vec = vec != 0; f.u8 = u8 != 0;
+                    add(reinterpret_cast<const void *>(select_fwd(lossy != 0, f)), "fwd" + s("band", band) + s("lossy", lossy) + s("vec", vec) + s("u8", u8));
+                }
+            for (int bits = 0; bits < 128; bits++) {
+                const int vec = bits & 1, fast = (bits >> 1) & 1, lean97 = (bits >> 2) & 1, c16 = (bits >> 3) & 1;
+                const int u8out = (bits >> 4) & 1, first = (bits >> 5) & 1, one_div = (bits >> 6) & 1;
+                if ((c16 || u8out) && !vec) continue;
+                if (fast && !lossy) continue;
+                if (c16 && ((lossy && !(fast && lean97)) || (first && u8out))) continue;
+                InvLaunch f;
+                memset(&f, 0, sizeof f);
+                f.band = band; f.vec = vec != 0; f.fast = fast != 0;
+                f.a.c16 = c16; f.a.first = first; f.a.one_div = one_div; f.a.dst_u8 = u8out ? &pixel : nullptr;
+                add(reinterpret_cast<const void *>(select_inv(lossy != 0, lean97 != 0, f)),
+                    "inv" + s("band", band) + s("lossy", lossy) + s("vec", vec) + s("fast", fast) + s("lean97", lean97) + s("c16", c16) +
+                        s("dst_u8", u8out) + s("first", first) + s("one_div", one_div));
+            }
+            for (int one_div = 0; one_div < 2; one_div++) {
+                InvLaunch f;
+                memset(&f, 0, sizeof f);
+                f.band = band; f.vec = true; f.fast = lossy != 0; f.a.c16 = 1; f.a.one_div = one_div; f.a.W = 64;
+                add(reinterpret_cast<const void *>(select_inv_rgb(lossy != 0, f).kernel), "inv_rgb" + s("band", band) + s("lossy", lossy) + s("one_div", one_div));
+            }
+        }
+    return (int)seen.size();
+}
+
 // as dwt_forward_impl (picsong_hip.hip); returns 1 when levels 0 and 1 went through the fused kernel
 int emu_dwt_forward(const void *in, int u8in, void *out, int aw, int ah, int wl, int lossy, float qs)
 {
@@ -79,6 +176,20 @@ int emu_dwt_forward_rgb(const uint8_t *r, const uint8_t *g, const uint8_t *b, vo
     bool fused = false;
     rgb_forward_transform(go, lossy != 0, true, plan_of, true, r, g, b, planes.data(), P, 128, stride, nullptr, &fused);
     return fused ? 1 : 0;
+}
+// the same call where the fused head may refuse (PICSONG_DWT_NOFUSE01=1: the colour transform on its own, then every
+// level of the three components through dwt_fwd_kernel); returns bit 0: the fused form ran, bit 1: the coefficients
+// left as int16 Mallat arrays (else: 32-bit ones at the same places)
+int emu_dwt_forward_rgb_forms(const uint8_t *r, const uint8_t *g, const uint8_t *b, void *out, size_t stride, int aw, int ah, int wl,
+                              int lossy, float qs)
+{
+    const size_t P = (size_t)aw * ah;
+    std::vector<int32_t> store(3 * P + 16);
+    int32_t *const planes = (int32_t *)(((uintptr_t)store.data() + 63) & ~(uintptr_t)63);
+    auto plan_of = [&](const void *src, bool u8in) { return plan_dwt_forward(src, u8in, out, aw, ah, wl, qs, true); };
+    bool fused = false, c16 = false;
+    rgb_forward_transform(go, lossy != 0, true, plan_of, true, r, g, b, planes, P, 128, stride, &c16, &fused);
+    return (fused ? 1 : 0) | (c16 ? 2 : 0);
 }
 
 // picsong_dwt_forward_band / picsong_dwt_forward_tail
@@ -115,6 +226,30 @@ int emu_dwt_inverse_u8(const int32_t *in, void *scratch, uint8_t *pixels, int aw
     bool fused = false;
     run_inverse(go, lossy != 0, emu_lean97(), emu_inverse_plan(in, scratch, pixels, &fused, 1, false, aw, ah, wl, qs,
                                                                 emu_fast_div(lossy, qs, wl), (size_t)aw * ah, dwt_extra(aw, ah, wl)));
+    return fused ? 1 : 0;
+}
+
+// `frames` frames a call, grid.z = frame (picsong_encode_frames / picsong_decode_frames): frame z's input in_z bytes and
+// its coefficient buffer out_z bytes after frame z - 1's; returns 1 when levels 0 and 1 went through the fused kernel
+int emu_dwt_forward_n(const void *in, int u8in, unsigned long long in_z, void *out, unsigned long long out_z, int aw, int ah, int wl,
+                      int lossy, float qs, int frames)
+{
+    std::vector<FwdLaunch> plan = plan_dwt_forward(in, u8in != 0, out, aw, ah, wl, qs, g_c16 != 0);
+    plan_frame_strides(plan, in_z, out_z);
+    bool fused01 = false;
+    launch_fwd_plan(go, lossy != 0, plan, (unsigned)frames, &fused01);
+    return fused01 ? 1 : 0;
+}
+// ... frame z's 32-bit coefficients P words, its scratch P + extra words, its pixels P bytes after frame z - 1's; returns 1
+// when the finest level wrote the pixels (else nothing in `pixels` is defined)
+int emu_dwt_inverse_u8_n(const int32_t *in, void *scratch, uint8_t *pixels, int aw, int ah, int wl, int lossy, float qs, int frames)
+{
+    bool fused = false;
+    const size_t P = (size_t)aw * ah;
+    run_inverse(go, lossy != 0, emu_lean97(),
+                plan_inverse_frames(in, scratch, pixels, &fused, (unsigned)frames, P, false, false, 0, aw, ah, wl, qs,
+                                    emu_fast_div(lossy, qs, wl), 128, P, dwt_extra(aw, ah, wl)),
+                (unsigned)frames);
     return fused ? 1 : 0;
 }
 
