@@ -737,6 +737,15 @@ __device__ __forceinline__ void reserve_enc(Coder &c, bool need, uint64_t m, uin
 
 // the encoders' staging words are 16-bit (BpcArgs::staging16): bytes per word, bytes per codeblock
 constexpr uint32_t kStageBytes = 2u, kStageCb = 4096u * kStageBytes;
+// PICSONG_ENC_RESET64 (default 0): the k = 0 two-pass encoder resets a fresh codeword's interval with ONE 64-bit move of
+// the literal 0xFFFF (enc_reset: S the low word, L the high one) where `c.L = 0; c.S = 0xFFFF` is two moves, about 1100
+// times a wave.  The compiler holds S and L in an aligned register pair for it without a move or a spill more (104
+// vector instructions fewer in the kernel's text, 4.27 M fewer a frame by the counter), every other kernel that reserves
+// slots keeps its text -- and the headline LOSES 0.8 % against the two moves (profiles/NOTES.md): fewer vector
+// instructions, slower.  Off; =0: the two moves everywhere.
+#ifndef PICSONG_ENC_RESET64
+#define PICSONG_ENC_RESET64 0
+#endif
 struct EncCoder {
     uint32_t L, S, off;
     uint32_t slot;              // LDS form: raw pre-add value of the lane's reservation (clamped when used)
@@ -747,6 +756,9 @@ struct EncCoder {
     uint32_t lim;               // LDS form: slot0 + 2 * 4094, the byte offset of the codeblock's last slot
     uint32_t pone;              // 1 << prec: the "probability" that leaves an idle lane's interval alone
     char *stw;                  // staging of the wave's first codeblock (wave-uniform)
+#if PICSONG_ENC_RESET64
+    bool reset64 = false;       // a constant of the kernel: the k = 0 two-pass encoder resets S and L with one 64-bit move
+#endif
 };
 
 // Slot reservation for the lanes in m (!= 0): as reserve_enc, plus the store of the codeword the lane
@@ -756,6 +768,24 @@ struct EncCoder {
 // call site loses a compare-and-branch region of its own.  A lane's first reservation stores the L = 0
 // it starts with to word 0 of its codeblock's staging (off starts there), which the kernel's epilogue
 // overwrites with the MSB after the wave's stores have drained.
+// (enc_reset, PICSONG_ENC_RESET64: a 64-bit move's 32-bit literal is zero-extended -- the pair's low word takes 0xFFFF, its
+// high one 0)
+__device__ __forceinline__ void enc_reset(EncCoder &c)
+{
+#if PICSONG_ENC_RESET64
+    if (c.reset64) {
+        uint64_t sl;
+#if defined(__AMDGCN__)
+        asm volatile("v_mov_b64 %0, 0xffff" : "=v"(sl));
+#else
+        sl = 0xFFFFull;
+#endif
+        c.S = (uint32_t)sl; c.L = (uint32_t)(sl >> 32);
+        return;
+    }
+#endif
+    c.L = 0u; c.S = 0xFFFFu;
+}
 __device__ __forceinline__ void enc_reserve(EncCoder &c, uint64_t m, uint32_t upper_mask)
 {
 #if PS_ENC_LDS
@@ -775,7 +805,7 @@ __device__ __forceinline__ void enc_reserve(EncCoder &c, uint64_t m, uint32_t up
         const uint32_t sl = c.slot < c.lim ? c.slot : c.lim;
         *reinterpret_cast<uint16_t *>(c.stw + sl) = (uint16_t)c.L;
         c.slot = __hip_atomic_fetch_add(c.ldscnt, kStageBytes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        c.L = 0u; c.S = 0xFFFFu;
+        enc_reset(c);
     }
 #else
     const uint32_t mlo = (uint32_t)m, mhi = (uint32_t)(m >> 32);
@@ -786,7 +816,7 @@ __device__ __forceinline__ void enc_reserve(EncCoder &c, uint64_t m, uint32_t up
         uint32_t s = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, base));
         s = s > 4094u ? 4094u : s;
         c.off = s * kStageBytes + c.slot0;
-        c.L = 0u; c.S = 0xFFFFu;
+        enc_reset(c);
     }
     const uint32_t a = c.cnt_lo + nlo, b = c.cnt_hi + nhi;
     c.cnt_lo = __builtin_amdgcn_readfirstlane(a > 4095u ? 4095u : a);
@@ -1004,12 +1034,36 @@ __device__ __forceinline__ void enc_spp_coeff(EncCoder &c, uint32_t rowbit, uint
 #ifndef PICSONG_ENC_SPP_DENSE
 #define PICSONG_ENC_SPP_DENSE 1
 #endif
-template <int J>
+// PICSONG_ENC_DENSE_NOTEST (default 1): where EVERY visited row has work -- a significance half-pass with rows ==
+// 0xFFFFFFFF, a dense refinement half-pass with popcount(rows) == last -- the column's site is not tested for being
+// empty: enc_site2 with an empty mask reserves nothing and leaves S, L and emptym as they are (every instruction of
+// the update runs under exec = 0 but the last, and that one recomputes the same ballot), so the test guards nothing,
+// and it is a scalar compare and a branch at every site of a kernel whose scalar unit is two thirds busy.  An empty
+// site then costs the update's 7 vector instructions; on the 8K bench frame 0.22 % of those significance sites and
+// 0.40 % of those refinement sites are empty (tools/spp_near_stats.py).  The test around the sign site stays: it skips
+// a whole update and is taken.  A dense refinement half-pass with a row without work keeps its tests (a third of its
+// sites are empty).  =0: the tests everywhere.
+// PICSONG_ENC_SPP_NEAR (default 0): a half-pass in which at most PICSONG_ENC_SPP_NEAR_MAX of the 32 rows have no work takes
+// the carry-read body too, with its tests.  A row without work has no insignificant lane in either column, so its two
+// sites drop out at the empty test after the row's six shifts; a 4-row group with no row set skips its head and its
+// sites, and its words are shifted four rows on.  Off: on the bench frame 45 of 32 600 visited half-passes are within
+// four rows of full (a half-pass there is full or nearly empty), and the second copy of the dense body puts 13 scratch
+// instructions more into the plane loops (profiles/NOTES.md).  For frames whose planes thin out row by row.
+#ifndef PICSONG_ENC_SPP_NEAR
+#define PICSONG_ENC_SPP_NEAR 0
+#endif
+#ifndef PICSONG_ENC_SPP_NEAR_MAX
+#define PICSONG_ENC_SPP_NEAR_MAX 4
+#endif
+#ifndef PICSONG_ENC_DENSE_NOTEST
+#define PICSONG_ENC_DENSE_NOTEST 1
+#endif
+template <int J, bool TEST = true>
 __device__ __forceinline__ void enc_spp_coeff_dense(EncCoder &c, uint32_t &xa, uint32_t &xn, uint32_t &xs,
                                                     uint32_t P4, uint32_t Q4, uint32_t prec, uint32_t upper_mask)
 {
     const uint64_t onm = ~shl_carry(xa), onem = shl_carry(xn), sgn = shl_carry(xs);
-    if (onm == 0ull) return;
+    if constexpr (TEST) { if (onm == 0ull) return; }
     enc_site2<J>(c, onm, onem, P4, prec, upper_mask);
     if (onem != 0ull) enc_site2<J>(c, onem, sgn, Q4, prec, upper_mask);
 }
@@ -1770,6 +1824,9 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
     c.ldscnt = &lds_cnt[(threadIdx.x >> 6) * 2u + half];
     c.slot0 = half * kStageCb + kStageBytes; c.lim = c.slot0 + kStageBytes * 4094u; c.pone = 1u << prec;
     c.stw = reinterpret_cast<char *>(stw);
+#if PICSONG_ENC_RESET64
+    c.reset64 = !BULK;
+#endif
     U64 AL = { 0u, 0u }, AR = { 0u, 0u };                 // significant before the current plane
     // With two plane bodies the kernel has no register left for what a lane can form again with an instruction: slot 0's
     // offset comes from `lim`, which every reservation keeps in a register (one subtraction at the top of a plane, where it
@@ -1881,27 +1938,43 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
                 uint32_t m8 = 0xFFFFFFFFu;
                 if (GATE8 && rows) m8 = wave_or32(cpL.n3 | cpR.n3);
                 if constexpr (!BULK && PICSONG_ENC_SPP_DENSE != 0) {
-                    if (rows == 0xFFFFFFFFu) {
+                    constexpr bool NEAR = PICSONG_ENC_SPP_NEAR != 0, NOTEST = PICSONG_ENC_DENSE_NOTEST != 0;
+                    bool carries = rows == 0xFFFFFFFFu;
+                    if constexpr (NEAR) carries = __builtin_popcount(~rows) <= PICSONG_ENC_SPP_NEAR_MAX;
+                    if (carries) {
                         // every row has work: the rows in order, their lane masks off the carries (enc_spp_coeff_dense)
+                        // (NEAR: all but a few have; a row without drops out at its sites' empty test)
                         uint32_t xal = bitrev32(al), xnl = bitrev32(nl), xsl = bitrev32(nl & cpL.s2);
                         uint32_t xar = bitrev32(ar), xnr = bitrev32(nr), xsr = bitrev32(nr & cpR.s2);
-#pragma unroll 1
-                        for (uint32_t g4 = 0u; g4 < 32u; g4 += 4u) {
-                            uint32_t P4L, P4R;
-                            PlaneLut plat;                   // (OCC8: the record, read here)
-                            if constexpr (OCC8R) plat = plane_lut_at(lds_lut, recoff);
-                            const PlaneLut &plg = OCC8R ? plat : pl;
-                            if constexpr (GATE8) {
-                                P4L = sig_probs4_07(cpL, plg, g4); P4R = sig_probs4_07(cpR, plg, g4);
-                                if ((m8 >> g4) & 0xFu) { P4L = sig_probs4_fix8(cpL, plg, g4, P4L); P4R = sig_probs4_fix8(cpR, plg, g4, P4R); }
-                            } else { P4L = sig_probs4(cpL, plg, g4); P4R = sig_probs4(cpR, plg, g4); }
-                            const uint32_t Q4L = sign_probs4(cpL, plg, g4), Q4R = sign_probs4(cpR, plg, g4);
-#define PS_SPP_ROW(J)                                                                                    \
-                            enc_spp_coeff_dense<J>(c, xal, xnl, xsl, P4L, Q4L, prec, upper_mask);         \
-                            enc_spp_coeff_dense<J>(c, xar, xnr, xsr, P4R, Q4R, prec, upper_mask);
-                            PS_SPP_ROW(0) PS_SPP_ROW(1) PS_SPP_ROW(2) PS_SPP_ROW(3)
-#undef PS_SPP_ROW
+                        // the eight groups; TEST: the sites' empty tests, SKIP: a group with no row set only shifts its words
+#define PS_SPP_GROUPS(TEST, SKIP)                                                                                  \
+                        _Pragma("unroll 1")                                                                       \
+                        for (uint32_t g4 = 0u; g4 < 32u; g4 += 4u) {                                              \
+                            if (SKIP && ((rows >> g4) & 0xFu) == 0u) {                                            \
+                                xal <<= 4; xnl <<= 4; xsl <<= 4; xar <<= 4; xnr <<= 4; xsr <<= 4;                 \
+                                continue;                                                                         \
+                            }                                                                                     \
+                            uint32_t P4L, P4R;                                                                    \
+                            PlaneLut plat;                   /* (OCC8: the record, read here) */                  \
+                            if constexpr (OCC8R) plat = plane_lut_at(lds_lut, recoff);                            \
+                            const PlaneLut &plg = OCC8R ? plat : pl;                                              \
+                            if constexpr (GATE8) {                                                                \
+                                P4L = sig_probs4_07(cpL, plg, g4); P4R = sig_probs4_07(cpR, plg, g4);             \
+                                if ((m8 >> g4) & 0xFu) { P4L = sig_probs4_fix8(cpL, plg, g4, P4L); P4R = sig_probs4_fix8(cpR, plg, g4, P4R); } \
+                            } else { P4L = sig_probs4(cpL, plg, g4); P4R = sig_probs4(cpR, plg, g4); }            \
+                            const uint32_t Q4L = sign_probs4(cpL, plg, g4), Q4R = sign_probs4(cpR, plg, g4);      \
+                            PS_SPP_ROW(0, TEST) PS_SPP_ROW(1, TEST) PS_SPP_ROW(2, TEST) PS_SPP_ROW(3, TEST)       \
                         }
+#define PS_SPP_ROW(J, TEST)                                                                              \
+                            enc_spp_coeff_dense<J, TEST>(c, xal, xnl, xsl, P4L, Q4L, prec, upper_mask);   \
+                            enc_spp_coeff_dense<J, TEST>(c, xar, xnr, xsr, P4R, Q4R, prec, upper_mask);
+                        if constexpr (NEAR && NOTEST) {
+                            if (rows == 0xFFFFFFFFu) { PS_SPP_GROUPS(false, false) }
+                            else { PS_SPP_GROUPS(true, true) }
+                        } else if constexpr (NEAR) { PS_SPP_GROUPS(true, true) }
+                        else { PS_SPP_GROUPS(!NOTEST, false) }
+#undef PS_SPP_ROW
+#undef PS_SPP_GROUPS
                         rows = 0u;
                     }
                 }
@@ -1952,12 +2025,28 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
                 // the carries of the bit-reversed column masks -- 4 half-rate instructions a row where the
                 // row-bit tests take 4 ands, 4 compares and the row bit's move
                 uint32_t xml = bitrev32(ml), xbl = bitrev32(bl), xmr = bitrev32(mr), xbr = bitrev32(br);
+                bool tested = true;
+                if constexpr (!BULK && PICSONG_ENC_DENSE_NOTEST != 0) {
+                    if (__builtin_popcount(rows) == last) {
+                        // every visited row has work: the columns' sites without their empty tests (PICSONG_ENC_DENSE_NOTEST)
+#pragma unroll 1
+                        for (int ii = 0; ii < last; ii++) {
+                            const uint64_t mL = shl_carry(xml), oL = shl_carry(xbl);
+                            enc_site2(c, mL, oL, pl.ref, prec, upper_mask);
+                            const uint64_t mR = shl_carry(xmr), oR = shl_carry(xbr);
+                            enc_site2(c, mR, oR, pl.ref, prec, upper_mask);
+                        }
+                        tested = false;
+                    }
+                }
+                if (tested) {
 #pragma unroll 1
                 for (int ii = 0; ii < last; ii++) {
                     const uint64_t mL = shl_carry(xml), oL = shl_carry(xbl);
                     if (mL != 0ull) enc_site2(c, mL, oL, pl.ref, prec, upper_mask);
                     const uint64_t mR = shl_carry(xmr), oR = shl_carry(xbr);
                     if (mR != 0ull) enc_site2(c, mR, oR, pl.ref, prec, upper_mask);
+                }
                 }
                 rows = 0u;
             }
