@@ -746,6 +746,62 @@ constexpr uint32_t kStageBytes = 2u, kStageCb = 4096u * kStageBytes;
 #ifndef PICSONG_ENC_RESET64
 #define PICSONG_ENC_RESET64 0
 #endif
+// ---- wave-uniform tests of the k = 0 two-pass encoder kept scalar (profiles/NOTES.md, top section) ----------------------
+// The carry-read bodies take their lane masks from shl_carry, an asm statement with two outputs, and the compiler treats
+// what comes out of it as lane-dependent: a test on such a mask, and what hangs on the test, is compiled for divergence.
+// Four switches, each of which changes the text of bpc_encode_kernel<false, false> alone; all at 0: the text of before.
+// PICSONG_ENC_SIGN_TEST_SCALAR (default 1): `if (onem != 0)` around the sign site of a carry-read significance coefficient is a 64-bit
+// VECTOR compare of the SGPR pair with 0 plus an s_and with exec (32 in the kernel's text, one executed per dense
+// significance coefficient: 2.6 M vector instructions a frame of 96.6 M, VOP3 with scalar sources).  The mask goes
+// through an empty asm statement with one scalar operand (uniform_mask), which the compiler takes as wave-uniform: one
+// s_cmp_lg_u64 right before the branch, as the generic body's ballots get.  Measured: -2.60 M vector a frame, +1.7 % on the
+// headline alone.
+// PICSONG_ENC_SPP_ONM_CARRY (default 1): the dense significance body holds the bit-reversed COMPLEMENT of A in xa, so the carry is onm
+// itself and not its complement: an s_not_b64 fewer per dense significance coefficient (16 in the text, 2.08 M a frame).
+// An idle half has A all ones: its word is 0 and it is never on, as before.  The complement is one v_not a column a
+// half-pass.  Measured: -2.08 M scalar, +0.07 M vector a frame, +0.3 % alone.
+// PICSONG_ENC_REF_SCALAR_COUNT (default 0): the dense refinement loops count their rows in a vector register (v_add_co_u32 1, s_and
+// with exec, s_cbranch_vccnz: four loops in the text, a row of some 27 000 half-passes x 32 a frame); the counter goes
+// through the same kind of asm statement (uniform_count) and stays in an SGPR: s_add, s_cmp, s_cbranch_scc.  Measured:
+// -0.89 M vector for +0.93 M scalar a frame and +0.04 % on the headline, inside the noise: off.
+// PICSONG_ENC_RESERVE_ONE_TEST (default 1): enc_site2 tests `m != 0` in scalar code and enc_reserve opens its exec region with
+// s_and_saveexec + s_cbranch_execz right behind it -- the compiler keeps the second branch, the region holds a store, an
+// LDS atomic and a wait.  A site of the k = 0 two-pass encoder (EncCoder::one_test, a constant of the kernel like
+// reset64) enters enc_reserve without the first test: an empty m opens an empty region, which its own branch skips.  A site
+// that reserves costs 4 scalar + 2 branches before and 3 + 1 after, one that does not 2 + 1 before and 3 + 1 after; by the
+// counters 0.65 of the bench frame's 6.56 M sites reserve: -1.98 M scalar and -4.27 M branches a frame (of 50.6 M and
+// 16.6 M), +0.3 % on the headline alone.  The atomic, the wait and the store stay the compiler's (see enc_reserve).
+// ALONE it makes a lone frame 3 % slower (an exec write pair in the chain of every site that does not reserve); beside
+// the first two switches the lone frame is where it was (profiles/NOTES.md).
+#ifndef PICSONG_ENC_SIGN_TEST_SCALAR
+#define PICSONG_ENC_SIGN_TEST_SCALAR 1
+#endif
+#ifndef PICSONG_ENC_SPP_ONM_CARRY
+#define PICSONG_ENC_SPP_ONM_CARRY 1
+#endif
+#ifndef PICSONG_ENC_REF_SCALAR_COUNT
+#define PICSONG_ENC_REF_SCALAR_COUNT 0
+#endif
+#ifndef PICSONG_ENC_RESERVE_ONE_TEST
+#define PICSONG_ENC_RESERVE_ONE_TEST 1
+#endif
+// a wave-uniform mask / counter as a value the compiler knows to be uniform (AMDGCN only; the emulator's values are plain)
+__device__ __forceinline__ uint64_t uniform_mask(uint64_t m)
+{
+#if defined(__AMDGCN__)
+    asm volatile("" : "+s"(m));
+#endif
+    return m;
+}
+__device__ __forceinline__ int uniform_count(int n)
+{
+#if defined(__AMDGCN__)
+    asm volatile("" : "+s"(n));
+#endif
+    return n;
+}
+template <bool SCALAR>
+__device__ __forceinline__ int ref_row_next(int ii) { return SCALAR ? uniform_count(ii + 1) : ii + 1; }
 struct EncCoder {
     uint32_t L, S, off;
     uint32_t slot;              // LDS form: raw pre-add value of the lane's reservation (clamped when used)
@@ -759,9 +815,12 @@ struct EncCoder {
 #if PICSONG_ENC_RESET64
     bool reset64 = false;       // a constant of the kernel: the k = 0 two-pass encoder resets S and L with one 64-bit move
 #endif
+#if PICSONG_ENC_RESERVE_ONE_TEST
+    bool one_test = false;      // a constant of the kernel: the k = 0 two-pass encoder's sites do not pre-test a reservation
+#endif
 };
 
-// Slot reservation for the lanes in m (!= 0): as reserve_enc, plus the store of the codeword the lane
+// Slot reservation for the lanes in m (no lane, PICSONG_ENC_RESERVE_ONE_TEST: nothing is stored, counted or reset): as reserve_enc, plus the store of the codeword the lane
 // has just finished.  The reference stores L the moment the interval is exhausted (:395-397) and again
 // at the flush (:1719); a lane writes a slot only with the value it holds when it leaves the slot, so the
 // store can wait until the lane moves on -- here, where an exec-masked region exists anyway -- and the
@@ -884,6 +943,10 @@ __device__ __forceinline__ void enc_site2(EncCoder &c, uint64_t onm, uint64_t on
                                           uint32_t upper_mask)
 {
     const uint64_t m = c.emptym & onm;
+#if PICSONG_ENC_RESERVE_ONE_TEST
+    if (c.one_test) enc_reserve(c, m, upper_mask);          // an empty m: an empty region, skipped by its own branch
+    else
+#endif
     if (m != 0ull) enc_reserve(c, m, upper_mask);
     enc_update<J>(c, onm, onem, p, prec);
 }
@@ -1062,9 +1125,19 @@ template <int J, bool TEST = true>
 __device__ __forceinline__ void enc_spp_coeff_dense(EncCoder &c, uint32_t &xa, uint32_t &xn, uint32_t &xs,
                                                     uint32_t P4, uint32_t Q4, uint32_t prec, uint32_t upper_mask)
 {
-    const uint64_t onm = ~shl_carry(xa), onem = shl_carry(xn), sgn = shl_carry(xs);
+    // (PICSONG_ENC_SPP_ONM_CARRY: xa is the bit-reversed ~A, its carry the lanes that code)
+#if PICSONG_ENC_SPP_ONM_CARRY
+    const uint64_t onm = shl_carry(xa);
+#else
+    const uint64_t onm = ~shl_carry(xa);
+#endif
+    uint64_t onem = shl_carry(xn);
+    const uint64_t sgn = shl_carry(xs);
     if constexpr (TEST) { if (onm == 0ull) return; }
     enc_site2<J>(c, onm, onem, P4, prec, upper_mask);
+#if PICSONG_ENC_SIGN_TEST_SCALAR
+    onem = uniform_mask(onem);
+#endif
     if (onem != 0ull) enc_site2<J>(c, onem, sgn, Q4, prec, upper_mask);
 }
 
@@ -1097,8 +1170,12 @@ template <int J>
 __device__ __forceinline__ void enc_spp_coeff_first_dense(EncCoder &c, uint64_t onm, uint32_t &xb, uint32_t &xs,
                                                           uint32_t P4, uint32_t Q4, uint32_t prec, uint32_t upper_mask)
 {
-    const uint64_t onem = shl_carry(xb), sgn = shl_carry(xs);
+    uint64_t onem = shl_carry(xb);
+    const uint64_t sgn = shl_carry(xs);
     enc_site2<J>(c, onm, onem, P4, prec, upper_mask);
+#if PICSONG_ENC_SIGN_TEST_SCALAR
+    onem = uniform_mask(onem);
+#endif
     if (onem != 0ull) enc_site2<J>(c, onem, sgn, Q4, prec, upper_mask);
 }
 // The significance pass of rows 32 HW .. 32 HW + 31 at step 0.  BL / BR: the plane's bits of the lane's columns (0 in an
@@ -1827,6 +1904,9 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
 #if PICSONG_ENC_RESET64
     c.reset64 = !BULK;
 #endif
+#if PICSONG_ENC_RESERVE_ONE_TEST
+    c.one_test = !BULK;
+#endif
     U64 AL = { 0u, 0u }, AR = { 0u, 0u };                 // significant before the current plane
     // With two plane bodies the kernel has no register left for what a lane can form again with an instruction: slot 0's
     // offset comes from `lim`, which every reservation keeps in a register (one subtraction at the top of a plane, where it
@@ -1944,8 +2024,14 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
                     if (carries) {
                         // every row has work: the rows in order, their lane masks off the carries (enc_spp_coeff_dense)
                         // (NEAR: all but a few have; a row without drops out at its sites' empty test)
+                        // (PICSONG_ENC_SPP_ONM_CARRY: the complement of A -- 0 in an idle half -- so a carry is onm as it comes)
+#if PICSONG_ENC_SPP_ONM_CARRY
+                        uint32_t xal = bitrev32(~al), xnl = bitrev32(nl), xsl = bitrev32(nl & cpL.s2);
+                        uint32_t xar = bitrev32(~ar), xnr = bitrev32(nr), xsr = bitrev32(nr & cpR.s2);
+#else
                         uint32_t xal = bitrev32(al), xnl = bitrev32(nl), xsl = bitrev32(nl & cpL.s2);
                         uint32_t xar = bitrev32(ar), xnr = bitrev32(nr), xsr = bitrev32(nr & cpR.s2);
+#endif
                         // the eight groups; TEST: the sites' empty tests, SKIP: a group with no row set only shifts its words
 #define PS_SPP_GROUPS(TEST, SKIP)                                                                                  \
                         _Pragma("unroll 1")                                                                       \
@@ -2026,11 +2112,17 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
                 // row-bit tests take 4 ands, 4 compares and the row bit's move
                 uint32_t xml = bitrev32(ml), xbl = bitrev32(bl), xmr = bitrev32(mr), xbr = bitrev32(br);
                 bool tested = true;
+                // the row counter: PICSONG_ENC_REF_SCALAR_COUNT holds it in an SGPR in the k = 0 two-pass encoder
+#if PICSONG_ENC_REF_SCALAR_COUNT
+#define PS_REF_NEXT(ii) ii = ref_row_next<!BULK>(ii)
+#else
+#define PS_REF_NEXT(ii) ii++
+#endif
                 if constexpr (!BULK && PICSONG_ENC_DENSE_NOTEST != 0) {
                     if (__builtin_popcount(rows) == last) {
                         // every visited row has work: the columns' sites without their empty tests (PICSONG_ENC_DENSE_NOTEST)
 #pragma unroll 1
-                        for (int ii = 0; ii < last; ii++) {
+                        for (int ii = 0; ii < last; PS_REF_NEXT(ii)) {
                             const uint64_t mL = shl_carry(xml), oL = shl_carry(xbl);
                             enc_site2(c, mL, oL, pl.ref, prec, upper_mask);
                             const uint64_t mR = shl_carry(xmr), oR = shl_carry(xbr);
@@ -2041,13 +2133,14 @@ __global__ __launch_bounds__(BULK ? 64 : 64 * kBpcEncWgWaves, BULK ? PICSONG_BPC
                 }
                 if (tested) {
 #pragma unroll 1
-                for (int ii = 0; ii < last; ii++) {
+                for (int ii = 0; ii < last; PS_REF_NEXT(ii)) {
                     const uint64_t mL = shl_carry(xml), oL = shl_carry(xbl);
                     if (mL != 0ull) enc_site2(c, mL, oL, pl.ref, prec, upper_mask);
                     const uint64_t mR = shl_carry(xmr), oR = shl_carry(xbr);
                     if (mR != 0ull) enc_site2(c, mR, oR, pl.ref, prec, upper_mask);
                 }
                 }
+#undef PS_REF_NEXT
                 rows = 0u;
             }
             while (rows) {
