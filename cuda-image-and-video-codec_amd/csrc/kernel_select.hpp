@@ -303,6 +303,35 @@ inline SseLaunch select_sse(const SseArgs &s)
     const unsigned wgs = (unsigned)(tiles > kSseMaxWgs ? kSseMaxWgs : (tiles < 1 ? 1 : tiles));
     return { vec ? sse_kernel<true> : sse_kernel<false>, wgs };
 }
+// ---- the tail of an RGB quality probe (rgb_sse_kernel, quality_kernels.hpp): the inverse ICT of n frames' float
+// component planes (plane 3 f + k at c + (3 f + k) * c_z bytes, row pitch c_pitch floats) and the SSE of the visible
+// w x h samples against the input planes (frame f's in_z bytes after r / g / b, row pitch in_pitch) in one launch,
+// 256 threads, a tile of 256 * kRgbSseTileLoads groups of four pixels a workgroup and step, grid-stride beyond kSseMaxWgs.
+// kernel == nullptr: the arguments do not allow its loads (dwordx4 of the floats: c, c_z and the row pitch 16-byte
+// aligned; a dword of each input plane: r, g, b, in_z and in_pitch 4-byte aligned), or the caller's switch is off
+// (fused = false: PICSONG_RGB_SSE_FUSED=0) -- the caller runs rgb_inverse + frames_sse instead.
+using RgbSseKernel = void (*)(RgbSseArgs);
+struct RgbSseLaunch { RgbSseKernel kernel; unsigned wgs; };
+inline RgbSseArgs rgb_sse_args(const void *c, unsigned long long c_z, size_t c_pitch, const uint8_t *r, const uint8_t *g, const uint8_t *b,
+                               unsigned long long in_z, size_t in_pitch, int w, int h, int n, int off, unsigned long long *out)
+{
+    RgbSseArgs s;
+    memset(&s, 0, sizeof s);
+    s.c = (const float *)c; s.c_z = c_z; s.c_pitch = (uint32_t)c_pitch;
+    s.r = r; s.g = g; s.b = b; s.in_z = n > 1 ? in_z : 0; s.in_pitch = (uint32_t)in_pitch;
+    s.out = out; s.W = w; s.H = h; s.n = n; s.off = off;
+    return s;
+}
+inline RgbSseLaunch select_rgb_sse(const RgbSseArgs &s, bool fused = true)
+{
+    const bool c_ok = ((((uintptr_t)s.c) | s.c_z | ((unsigned long long)s.c_pitch * 4ull)) & 15u) == 0;
+    const bool in_ok = ((((uintptr_t)s.r) | ((uintptr_t)s.g) | ((uintptr_t)s.b) | s.in_z | s.in_pitch) & 3u) == 0;
+    const bool fits = s.W >= 1 && s.H >= 1 && s.n >= 1 && (size_t)s.W <= s.c_pitch && (size_t)s.W <= s.in_pitch;
+    if (!fused || !c_ok || !in_ok || !fits) return { nullptr, 0u };
+    const size_t items = (size_t)((s.W + 3) / 4) * (size_t)s.H, tile = 256u * (size_t)kRgbSseTileLoads;
+    const size_t tiles = (items + tile - 1) / tile * (size_t)s.n;
+    return { rgb_sse_kernel<kRgbSseRunLoads>, (unsigned)(tiles > kSseMaxWgs ? kSseMaxWgs : tiles) };
+}
 
 // ---- pixel layouts (ingest_kernel / emit_kernel, layout_kernels.hpp).  bytes a pixel, planes of the padded side
 inline int layout_bpp(int layout) { return layout < kLayoutRgb24 ? 1 : (layout < kLayoutRgba32 ? 3 : 4); }

@@ -473,9 +473,13 @@ int decode_rgb_images_reduced(const Go &go, const DecodeCtx &c, const BpcArgs &a
 //   costs far more host time than the probe's GPU time; every reciprocal form is verified against these), grid.z = array,
 //   work buffers of (P + extra) floats each, the clamped u8 pixels into `pix` (P bytes each);
 //   sse_kernel against the input into out[0 .. nf).
-// Grey (r == nullptr): nf frames at `frames`, frame_stride bytes apart.  RGB (nf = 3): the components' planes leave the
-// synthesis as float samples (the fused 9/7 RGB tail is the lean kernel's and wants the verified reciprocals:
-// inv_rgb_tail_ok), the inverse ICT kernel writes R, G, B into pix, each compared with its input plane.
+// Grey (r == nullptr): nf frames at `frames`, frame_stride bytes apart.  RGB (nf = 3 n, n frames' planes frame_stride
+// bytes after r / g / b): the components' planes leave the synthesis as float samples (the fused 9/7 RGB tail is the lean
+// kernel's and wants the verified reciprocals: inv_rgb_tail_ok), component k of frame f in plane 3 f + k; then
+//   rgb_sse_kernel: the inverse ICT and the SSE against the input planes in one launch, no pixel written, out[3 f + k];
+//   or, where select_rgb_sse refuses (the float planes not 16-byte aligned, rgb_sse_fused = false: the library's
+//   PICSONG_RGB_SSE_FUSED=0), the unfused tail: per frame the inverse ICT kernel writes R, G, B into pix (3 P bytes a
+//   frame), each compared with its input plane by frames_sse.
 struct QualityProbe {
     const void *unit; unsigned long long unit_z;
     int32_t *coef_i; void *work; uint8_t *pix;
@@ -484,10 +488,34 @@ struct QualityProbe {
     int nf;
     const uint8_t *frames; size_t frame_stride;
     const uint8_t *r, *g, *b;
+    bool rgb_sse_fused = true;
 };
 // mark(k): called after the quantise pass (1), after the synthesis' last launch (2) and after the SSE (3) -- the
-// library's stage timers; returns 0
+// library's stage timers; returns 0.  (RGB: the colour transform is in stage 2 on the unfused tail, in stage 3 on the
+// fused one -- compare the two stages summed.)
 struct NoMark { int operator()(int) const { return 0; } };
+inline std::vector<InvLaunch> quality_probe_plan(const QualityProbe &p, int j, bool *pixels = nullptr)
+{
+    const bool rgb = p.r != nullptr;
+    bool fused = false;
+    std::vector<InvLaunch> plan = plan_inverse_frames(p.coef_i, p.work, rgb ? nullptr : p.pix, &fused, (unsigned)p.nf, p.P, false, rgb,
+                                                      0, p.aw, p.ah, p.wl, rate_q(j), false, p.off, p.P, p.extra);
+    if (pixels) *pixels = fused;
+    return plan;
+}
+// the fused tail's launch over a probe's plan (kernel == nullptr: the unfused tail runs)
+inline RgbSseLaunch quality_probe_rgb_sse(const QualityProbe &p, const std::vector<InvLaunch> &plan, unsigned long long *out, RgbSseArgs *args = nullptr)
+{
+    const RgbSseArgs s = rgb_sse_args(plan.back().a.dst, (unsigned long long)(p.P + p.extra) * 4ull, (size_t)p.aw, p.r, p.g, p.b,
+                                      (unsigned long long)p.frame_stride, (size_t)p.aw, p.w, p.h, p.nf / 3, p.off, out);
+    if (args) *args = s;
+    return select_rgb_sse(s, p.rgb_sse_fused);
+}
+// does an RGB probe over these buffers take the fused tail?  (else it needs p.pix: 3 P bytes a frame)
+inline bool quality_probe_fuses(const QualityProbe &p)
+{
+    return p.r != nullptr && quality_probe_rgb_sse(p, quality_probe_plan(p, 1), nullptr).kernel != nullptr;
+}
 template <class Go, class Mark = NoMark>
 int quality_probe(const Go &go, const QualityProbe &p, int j, unsigned long long *out, const Mark &mark = Mark())
 {
@@ -497,17 +525,32 @@ int quality_probe(const Go &go, const QualityProbe &p, int j, unsigned long long
     if (int rc = go(select_quantise(1, p.nf, p.ah, true).kernel, dim3(select_quantise(1, p.nf, p.ah, true).wgs), 256u, qa)) return rc;
     if (int rc = mark(1)) return rc;
     bool fused = false;
-    const std::vector<InvLaunch> plan = plan_inverse_frames(p.coef_i, p.work, rgb ? nullptr : p.pix, &fused, (unsigned)p.nf, p.P, false, rgb,
-                                                            0, p.aw, p.ah, p.wl, rate_q(j), false, p.off, p.P, p.extra);
+    const std::vector<InvLaunch> plan = quality_probe_plan(p, j, &fused);
     if (int rc = run_inverse(go, true, false, plan, (unsigned)p.nf)) return rc;
     const char *img = (const char *)plan.back().a.dst;       // (the finest level's samples where it did not write pixels)
     const size_t z = (p.P + p.extra) * 4;
     if (rgb) {
-        if (int rc = rgb_inverse(go, true, img, img + z, img + 2 * z, p.pix, p.pix + p.P, p.pix + 2 * p.P, p.P / 4, p.off)) return rc;
+        const int n = p.nf / 3;
+        RgbSseArgs sa;
+        const RgbSseLaunch l = quality_probe_rgb_sse(p, plan, out, &sa);
+        if (l.kernel) {
+            if (int rc = mark(2)) return rc;
+            if (int rc = go(sse_zero_kernel, dim3(1), 64u, out, p.nf)) return rc;
+            if (int rc = go(l.kernel, dim3(l.wgs), 256u, sa)) return rc;
+            return mark(3);
+        }
+        for (int f = 0; f < n; f++) {
+            const char *c0 = img + (size_t)(3 * f) * z;
+            uint8_t *px = p.pix + (size_t)(3 * f) * p.P;
+            if (int rc = rgb_inverse(go, true, c0, c0 + z, c0 + 2 * z, px, px + p.P, px + 2 * p.P, p.P / 4, p.off)) return rc;
+        }
         if (int rc = mark(2)) return rc;
-        const uint8_t *in[3] = { p.r, p.g, p.b };
-        for (int k = 0; k < 3; k++)
-            if (int rc = frames_sse(go, p.pix + (size_t)k * p.P, (size_t)p.aw, 0, in[k], (size_t)p.aw, 0, p.w, p.h, 1, out + k)) return rc;
+        for (int f = 0; f < n; f++) {
+            const size_t at = n > 1 ? (size_t)f * p.frame_stride : 0;
+            const uint8_t *in[3] = { p.r + at, p.g + at, p.b + at };
+            for (int k = 0; k < 3; k++)
+                if (int rc = frames_sse(go, p.pix + (size_t)(3 * f + k) * p.P, (size_t)p.aw, 0, in[k], (size_t)p.aw, 0, p.w, p.h, 1, out + 3 * f + k)) return rc;
+        }
         return mark(3);
     }
     if (!fused)

@@ -1356,30 +1356,37 @@ static int rgb_forward_transform(picsong_ctx *c, const uint8_t *d_r, const uint8
 //      size:    quantise_kernel writes the candidates' coefficients as K * n "frames" of the batch buffers, ONE batched
 //               coder launch codes them, the size scan totals them -- no pack (rate_probe);
 //      quality: quality_probe for each candidate, back to back over ONE set of nf-frame buffers (batch.coef_i,
-//               batch.coef, q_pix), candidate i's sums in slots i * nf .. of d_sse.  No coder launch;
+//               batch.coef, and q_pix where the RGB probe's tail is the unfused one), candidate i's sums in slots
+//               i * nf .. of d_sse.  No coder launch;
 //   3. the winner is packed with a header whose qs field is the result (rate_finish): a size search packs it from the
 //      last round's staging when it was coded there, else, as a quality search always, after one more quantise + coder
 //      launch of it alone (rate_probe).
 // PICSONG_RATE_K=1 keeps one candidate a round in both kinds (the measurements of tools/rate_bench.py compare both).
+// RGB: nf = 3 n planes, plane 3 f + k component k of frame f.  The single-frame calls (n = 1) keep one candidate a
+// size round; the n-frame calls (RateJob::multi) take rgb_search_candidates (rate_search.hpp).
+// PICSONG_RGB_SSE_FUSED=0, read per call, keeps the RGB probe's unfused tail (rgb_inverse + frames_sse).
 // ---------------------------------------------------------------------------------------------
 struct RateJob {
-    int n;                                  // frames (RGB: 1 frame, three components)
+    int n;                                  // frames (RGB: three components each)
     const uint8_t *frames; size_t frame_stride;
-    const uint8_t *r, *g, *b;               // RGB planes (frames == nullptr)
+    const uint8_t *r, *g, *b;               // RGB planes of frame 0 (frames == nullptr), frame f's frame_stride bytes behind
     int first_iter, header_mask;
     uint16_t *d_streams; size_t stream_stride;
     bool single;                            // picsong_encode_frame_rate: the length also where picsong_encode_frame leaves it
+    bool multi = false;                     // the n-frame RGB calls (picsong_encode_rgb_frames_rate / _quality)
 };
 
 enum SearchKind { kSearchSize, kSearchQuality };
 
-static int search_candidates(const picsong_ctx *c, SearchKind kind)
+static int search_candidates(const picsong_ctx *c, SearchKind kind, const RateJob &job)
 {
-    // an RGB frame's size search codes one candidate a round (a quality search's probes launch no coder): the coder launch
-    // maps plane z to table z % 3 since the batched RGB calls, so several candidates a round are possible; left as it was
+    const char *e = getenv("PICSONG_RATE_K");
+    const bool one = e && atoi(e) == 1;
+    if (job.multi) return rgb_search_candidates(kind == kSearchSize, job.n, one);
+    // the single-frame RGB calls' size search codes one candidate a round, as it always has (a quality search's probes
+    // launch no coder)
     if (kind == kSearchSize && c->p.is_rgb) return 1;
-    if (const char *e = getenv("PICSONG_RATE_K")) if (atoi(e) == 1) return 1;
-    return kRateMaxK;
+    return one ? 1 : kRateMaxK;
 }
 
 static int ensure_rate(picsong_ctx *c, int frames)
@@ -1405,12 +1412,14 @@ static int rate_transform(picsong_ctx *c, const RateJob &job, hipStream_t s)
     }
     // the ICT in the fused head's load stage where the planes allow it (as rgb_forward_transform), 32-bit float form
     auto plan_of = [c](const void *src, bool u8in) { return plan_dwt_forward_unit(src, u8in, c->rate_coef, c->aw, c->ah, c->p.wl); };
-    return picsong::rgb_forward_transform(HipGo{ s }, lossy, rgb_planes_aligned(job.r, job.g, job.b) && !getenv("PICSONG_RGB_NOFUSE"), plan_of,
-                                          false, job.r, job.g, job.b, c->batch.coef_i, c->P, level_off(c), c->rate_z);
+    const bool fuse = rgb_planes_aligned(job.r, job.g, job.b) && (job.n == 1 || (job.frame_stride & 15u) == 0) && !getenv("PICSONG_RGB_NOFUSE");
+    return picsong::rgb_forward_transform(HipGo{ s }, lossy, fuse, plan_of, false, job.r, job.g, job.b, c->batch.coef_i, c->P, level_off(c),
+                                          c->rate_z, nullptr, nullptr, (unsigned)job.n, job.frame_stride);
 }
 
 // step 2's launches for the candidates js[0 .. m): quantise, coder, size scan; the m * nf totals are then in batch.total
-// (nf: coded arrays a candidate -- the n frames, or an RGB frame's three components)
+// (nf: coded arrays a candidate -- the n frames, or the 3 n components of n RGB frames; candidate i's plane z is plane
+// i * nf + z of the launch, and nf a multiple of 3 keeps it on table z % 3)
 static int rate_probe(picsong_ctx *c, BpcArgs a, int nf, int m, const int *js, hipStream_t s)
 {
     int rc;
@@ -1426,8 +1435,9 @@ static int rate_probe(picsong_ctx *c, BpcArgs a, int nf, int m, const int *js, h
     a.coeffs_in = c->batch.coef; a.coef_z = dst_z;
     a.staging16 = reinterpret_cast<uint16_t *>(c->batch.staging);
     a.sizes = c->batch.sizes; a.plane_scratch = c->batch.plane_scratch;
-    if (c->p.is_rgb) {                                      // (m == 1: component f codes with table f)
-        if ((rc = launch_encoder(c, a, 3u * (unsigned)a.waves_per_frame, 0, 3, s))) return rc;
+    if (c->p.is_rgb) {                                      // (plane z codes with table z % 3; waves_per_frame: bpc_args_rgb's)
+        a.frames = m * nf;
+        if ((rc = launch_encoder(c, a, (unsigned)(m * nf) * (unsigned)a.waves_per_frame, 0, 3, s))) return rc;
     } else {
         a.cb_base = 0; a.nCB = c->ncb;
         a.frames = m * nf; a.waves_per_frame = (c->ncb + 1) / 2;
@@ -1450,9 +1460,14 @@ static int rate_finish(picsong_ctx *c, const RateJob &job, int nf, int j, int sl
     hp.qs = rate_q(j);
     uint16_t hdr[PICSONG_HDR_SHORTS];
     picsong_header_pack(&hp, hdr);
-    const bool has_hdr = rgb ? (job.header_mask & 7) != 0 : (job.first_iter <= 0 && job.first_iter + job.n > 0);
-    const int has = rgb ? -(job.header_mask & 7) : -job.first_iter + 1;
-    if ((rc = pack_frames(HipGo{ s }, st16, w, c->ncb, (unsigned)nf, has_hdr ? hdr : nullptr, has, job.d_streams, c->P, job.stream_stride))) return rc;
+    if (rgb) {
+        if ((rc = pack_rgb_frames(HipGo{ s }, st16, w, c->ncb, (unsigned)job.n, hdr, job.first_iter, job.header_mask, job.d_streams, c->P,
+                                  job.stream_stride))) return rc;
+    } else {
+        const bool has_hdr = job.first_iter <= 0 && job.first_iter + job.n > 0;
+        if ((rc = pack_frames(HipGo{ s }, st16, w, c->ncb, (unsigned)nf, has_hdr ? hdr : nullptr, -job.first_iter + 1, job.d_streams, c->P,
+                              job.stream_stride))) return rc;
+    }
     // (the lengths where the plain calls leave theirs: picsong_last_total(s) / picsong_copy_last_totals cover a rate call)
     if (slot > 0) HIP_TRY(hipMemcpyAsync(c->batch.total, w.total, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     if (job.single) HIP_TRY(hipMemcpyAsync(c->one.total, w.total, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
@@ -1464,7 +1479,7 @@ static int rate_finish(picsong_ctx *c, const RateJob &job, int nf, int j, int sl
 }
 
 // ---- the quality calls' conversions, picsong_frames_sse and probe buffers
-constexpr int kQualitySlots = kRateMaxK * 16;
+constexpr int kQualitySlots = kRateMaxK * 3 * kRgbMaxFrames;   // (K candidates of 21 RGB frames' planes; 16 grey frames fit)
 
 int picsong_psnr_to_sse(double psnr_db, uint64_t samples, uint64_t *max_sse)
 {
@@ -1496,6 +1511,7 @@ int picsong_frames_sse(picsong_ctx *c, int n, const uint8_t *d_a, size_t a_strid
                       c->p.width, c->p.height, n, reinterpret_cast<unsigned long long *>(d_sse));
 }
 
+// frames: the planes of probe pixels (q_pix) the call needs -- 0 for an RGB probe on the fused tail, which writes none
 static int ensure_quality(picsong_ctx *c, int frames)
 {
     if (!c->d_sse) HIP_TRY(hipMalloc(&c->d_sse, kQualitySlots * sizeof(unsigned long long)));
@@ -1523,7 +1539,7 @@ static int search_impl(picsong_ctx *c, const RateJob &job, SearchKind kind, uint
     if (grid.empty()) return fail(PICSONG_ERR_ARG, "%s: no header-exact quantiser in [%d, %d]", who, j_min, j_max);
     HIP_TRY(hipSetDevice(c->device));
     const bool rgb = c->p.is_rgb != 0;
-    const int nf = rgb ? 3 : job.n, K = search_candidates(c, kind);
+    const int nf = rgb ? 3 * job.n : job.n, K = search_candidates(c, kind, job);
     BpcArgs a;
     int rc = rgb ? bpc_args_rgb(c, a) : bpc_args(c, a, 0);   // (the encodes' table: refused before anything is launched)
     if (rc) return rc;
@@ -1531,7 +1547,15 @@ static int search_impl(picsong_ctx *c, const RateJob &job, SearchKind kind, uint
     if ((rc = ensure_batch(c, size ? K * nf : nf))) return rc;
     if ((rgb || !size) && (rc = ensure_coef_i(c, nf))) return rc;
     if ((rc = ensure_rate(c, nf))) return rc;
-    if (!size && (rc = ensure_quality(c, nf))) return rc;
+    // (the probe of every round: PICSONG_RGB_SSE_FUSED and the buffers' alignment are the call's, not the round's)
+    const char *const fe = getenv("PICSONG_RGB_SSE_FUSED");
+    QualityProbe probe = { c->rate_coef, (unsigned long long)c->rate_z, c->batch.coef_i, c->batch.coef, nullptr,
+                           c->aw, c->ah, c->p.wl, c->p.width, c->p.height, level_off(c), c->P, c->extra, nf,
+                           job.frames, job.frame_stride, job.r, job.g, job.b, !(fe && atoi(fe) == 0) };
+    if (!size) {
+        if ((rc = ensure_quality(c, quality_probe_fuses(probe) ? 0 : nf))) return rc;
+        probe.pix = c->q_pix;
+    }
     c->last_batch = -1;                                     // (until the result is packed: no totals to hand out)
     if ((rc = rate_transform(c, job, s))) return rc;
 
@@ -1549,9 +1573,6 @@ static int search_impl(picsong_ctx *c, const RateJob &job, SearchKind kind, uint
     std::vector<int> seen_j;
     std::vector<uint64_t> seen_sse;
     auto measure_quality = [&](int m, const int *js, uint64_t *values) -> int {
-        const QualityProbe probe = { c->rate_coef, (unsigned long long)c->rate_z, c->batch.coef_i, c->batch.coef, c->q_pix,
-                                     c->aw, c->ah, c->p.wl, c->p.width, c->p.height, level_off(c), c->P, c->extra, nf,
-                                     job.frames, job.frame_stride, job.r, job.g, job.b };
         for (int i = 0; i < m; i++) {
             // stage timers (picsong_profile_begin): a probe records quantise, synthesis and SSE where a frame records
             // transform, coder and pack
@@ -1597,12 +1618,22 @@ static int search_impl(picsong_ctx *c, const RateJob &job, SearchKind kind, uint
 // The entry points' own refusals, over the job they made.  form: which of the three inputs the entry takes; outs: its
 // host pointers are all there.  (kOneFrame takes a frame of any alignment, as picsong_encode_frame: an unaligned one
 // runs the per-column transform kernels and sse_kernel's per-byte form.)
-enum SearchForm { kFrames, kOneFrame, kRgbFrame };
+// kRgbFrames: the n-frame RGB calls -- what picsong_encode_rgb_frames refuses (rgb_frames_refusal), and planes and a
+// stride that rgb_sse_kernel's dword loads can take.
+enum SearchForm { kFrames, kOneFrame, kRgbFrame, kRgbFrames };
 
 static int search_args_ok(const picsong_ctx *c, const RateJob &job, SearchForm form, SearchKind kind, bool outs, const char *who)
 {
-    const bool rgb = form == kRgbFrame;
+    const bool rgb = form == kRgbFrame || form == kRgbFrames;
     if (!c || !job.d_streams || !outs || (rgb ? !job.r || !job.g || !job.b : !job.frames)) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (form == kRgbFrames) {
+        if (const char *why = rgb_frames_refusal(c->p.is_rgb != 0, c->p.cp, true, job.n, job.r, job.g, job.b, job.d_streams, job.frame_stride,
+                                                 job.stream_stride, c->P, picsong_max_stream_shorts(c->aw, c->ah)))
+            return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+        if ((((uintptr_t)job.r) | ((uintptr_t)job.g) | ((uintptr_t)job.b)) & 3u) return fail(PICSONG_ERR_ARG, "%s: the planes need 4-byte alignment", who);
+        if (job.n > 1 && (job.frame_stride & 3u)) return fail(PICSONG_ERR_ARG, "%s: frame_stride must be a multiple of 4", who);
+        return PICSONG_OK;
+    }
     if (job.n < 1 || job.n > 16) return fail(PICSONG_ERR_ARG, "%s: %d frames outside 1..16", who, job.n);
     const size_t max_shorts = picsong_max_stream_shorts(c->aw, c->ah);
     if (rgb) {
@@ -1674,6 +1705,30 @@ int picsong_encode_rgb_frame_quality(picsong_ctx *c, const uint8_t *d_r, const u
     const char *who = "encode_rgb_frame_quality";
     const RateJob job = { 1, nullptr, 0, d_r, d_g, d_b, 0, header_mask, d_streams, stream_stride, false };
     if (int rc = search_args_ok(c, job, kRgbFrame, kSearchQuality, h_j && h_totals && h_sse, who)) return rc;
+    return search_impl(c, job, kSearchQuality, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_totals, h_sse, who);
+}
+
+// The n-frame RGB calls: frame f's planes frame_stride bytes after d_r / d_g / d_b, its component k's stream at
+// (3 f + k) * stream_stride; size(j) and sse(j) the sums over the 3 n planes.
+int picsong_encode_rgb_frames_rate(picsong_ctx *c, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, size_t frame_stride,
+                                   int first_iter, int header_mask, size_t target_shorts, int j_min, int j_max, uint16_t *d_streams,
+                                   size_t stream_stride, void *stream, int *h_j, int *h_totals)
+{
+    const char *who = "encode_rgb_frames_rate";
+    RateJob job = { n, nullptr, n > 1 ? frame_stride : 0, d_r, d_g, d_b, first_iter, header_mask, d_streams, stream_stride, false };
+    job.multi = true;
+    if (int rc = search_args_ok(c, job, kRgbFrames, kSearchSize, h_j && h_totals, who)) return rc;
+    return search_impl(c, job, kSearchSize, target_shorts, j_min, j_max, (hipStream_t)stream, h_j, h_totals, nullptr, who);
+}
+
+int picsong_encode_rgb_frames_quality(picsong_ctx *c, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, size_t frame_stride,
+                                      int first_iter, int header_mask, uint64_t max_sse, int j_min, int j_max, uint16_t *d_streams,
+                                      size_t stream_stride, void *stream, int *h_j, int *h_totals, uint64_t *h_sse)
+{
+    const char *who = "encode_rgb_frames_quality";
+    RateJob job = { n, nullptr, n > 1 ? frame_stride : 0, d_r, d_g, d_b, first_iter, header_mask, d_streams, stream_stride, false };
+    job.multi = true;
+    if (int rc = search_args_ok(c, job, kRgbFrames, kSearchQuality, h_j && h_totals && h_sse, who)) return rc;
     return search_impl(c, job, kSearchQuality, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_totals, h_sse, who);
 }
 
@@ -1835,6 +1890,31 @@ int picsong_train_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d
     // (a launch a component: a workgroup's on-chip copy of the counters belongs to one slot)
     for (int k = 0; k < 3; k++)
         if ((rc = launch_stats(c, k, (const char *)c->batch.coef + (size_t)k * coef_z, c16, 1, 0, s))) return rc;
+    return PICSONG_OK;
+}
+
+// n RGB frames: one transform of the 3 n planes, then a statistics launch a component over its n arrays (component k's
+// start at plane k, 3 planes apart).  The counts are those of n picsong_train_rgb_frame calls.
+int picsong_train_rgb_frames(picsong_ctx *c, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, size_t frame_stride,
+                             void *stream)
+{
+    if (int rc = train_ready(c, "train_rgb_frames")) return rc;
+    if (!d_r || !d_g || !d_b) return fail(PICSONG_ERR_ARG, "train_rgb_frames: null argument");
+    if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "train_rgb_frames: the context is not an RGB one");
+    if ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 3u) return fail(PICSONG_ERR_ARG, "train_rgb_frames: the planes need 4-byte alignment");
+    if (n < 1 || n > kRgbMaxFrames) return fail(PICSONG_ERR_ARG, "train_rgb_frames: %d frames outside 1..%d", n, kRgbMaxFrames);
+    if (n > 1 && (frame_stride < c->P || (frame_stride & 3u)))
+        return fail(PICSONG_ERR_ARG, "train_rgb_frames: frame_stride smaller than a padded plane, or no multiple of 4");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_batch(c, 3 * n))) return rc;
+    if ((rc = ensure_coef_i(c, 3 * n))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t coef_z = (c->P + c->extra) * 4;
+    bool c16 = false;
+    if ((rc = rgb_forward_transform(c, d_r, d_g, d_b, s, &c16, n, n > 1 ? frame_stride : 0))) return rc;
+    for (int k = 0; k < 3; k++)
+        if ((rc = launch_stats(c, k, (const char *)c->batch.coef + (size_t)k * coef_z, c16, n, 3ull * coef_z, s))) return rc;
     return PICSONG_OK;
 }
 

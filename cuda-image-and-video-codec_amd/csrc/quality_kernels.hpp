@@ -21,9 +21,19 @@
 //
 // VEC: both pointers, pitches and strides 16-byte aligned: dwordx4 loads.  Else the per-byte form: the same items, the
 // sixteen bytes of a vector loaded one by one (bounds-checked against W), the same arithmetic.
+//
+// rgb_sse_kernel is the tail of an RGB quality probe (quality_probe, launch_seq.hpp): the inverse ICT of the float
+// component planes the 9/7 synthesis leaves and the SSE against the caller's R, G, B planes in ONE pass -- the pixels are
+// wanted for their squared error only, so none is written (the unfused tail, rgb_inverse_kernel and three sse_kernel
+// launches, moves 21 P bytes a frame; this one reads 12 P of floats and 3 P of input).  out[3 f + c] += the SSE of plane c
+// of frame f.  The pixel arithmetic is rgb_inverse_kernel<float>'s, bit for bit; the squares are sse_kernel's identity
+// over the packed clamped pixels (3 v_lshl_or + 3 v_dot4 per four samples and channel against 4 byte extracts, 4
+// subtracts and 4 multiply-adds unpacked); the shape is sse_kernel's with groups of four pixels for its vectors.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "dwt_kernels.hpp"
 
 #ifndef __HIP_MEMORY_SCOPE_AGENT
 #define __HIP_MEMORY_SCOPE_AGENT 4          // (CPU wave-emulator build: its atomics are plain read-modify-writes)
@@ -148,6 +158,118 @@ __global__ __launch_bounds__(256) void sse_kernel(SseArgs s)
             }
             i += 256u; y += step_rows; v += step_vecs;
             if (v >= vpr) { v -= vpr; y++; }
+        }
+    }
+}
+
+// ---- inverse ICT + SSE of n RGB frames
+constexpr int kRgbSseTileLoads = 4;         // groups of four pixels a lane and tile
+constexpr int kRgbSseRunLoads = 16512;      // groups a lane may accumulate in 32 bits (a channel's sum)
+static_assert(kRgbSseRunLoads % kRgbSseTileLoads == 0, "a run is whole tiles");
+
+struct RgbSseArgs {
+    const float *c;                 // component k of frame f: plane 3 f + k at c + (3 f + k) * c_z bytes, row y at + y * c_pitch floats
+    unsigned long long c_z;
+    const uint8_t *r, *g, *b;       // frame f's input planes at + f * in_z bytes, row y at + y * in_pitch
+    unsigned long long in_z;
+    unsigned long long *out;        // out[3 f + k] += the SSE of plane k of frame f
+    uint32_t c_pitch, in_pitch;
+    int W, H, n, off;
+};
+
+// RUN: the groups a lane accumulates before it widens (the library: kRgbSseRunLoads; the emulator test: two tiles).
+// Wants c, c_z and c_pitch * 4 16-byte aligned, r, g, b, in_z and in_pitch 4-byte aligned (select_rgb_sse).
+template <int RUN>
+__global__ __launch_bounds__(256) void rgb_sse_kernel(RgbSseArgs s)
+{
+    static_assert(RUN >= kRgbSseTileLoads && RUN % kRgbSseTileLoads == 0, "a run is whole tiles");
+    static_assert((unsigned long long)RUN * 4ull * 255ull * 255ull < (1ull << 32), "a run's SSE fits 32 bits");
+    __shared__ unsigned long long wave_sum[3][4];
+    const uint32_t gpr = ((uint32_t)s.W + 3u) >> 2;                         // groups a row
+    const uint32_t items = gpr * (uint32_t)s.H;                             // groups a frame
+    constexpr uint32_t kTile = 256u * (uint32_t)kRgbSseTileLoads;
+    const uint32_t tpf = (items + kTile - 1u) / kTile, tiles = tpf * (uint32_t)s.n;
+    const uint32_t step_rows = 256u / gpr, step_groups = 256u - step_rows * gpr;   // (row, group) of item + 256
+    const uint32_t tail = (uint32_t)s.W - 4u * (gpr - 1u);                  // visible samples of a row's last group, 1..4
+    const uint32_t tail_mask = tail >= 4u ? 0xFFFFFFFFu : (1u << (8u * tail)) - 1u;
+    // rgb_inverse_kernel<float>'s matrix, the factors that are neither 0 nor 1 (from vector registers: rate_kernels.hpp)
+    const float m02 = in_vgpr(1.402f), m11 = in_vgpr(-0.344136f), m12 = in_vgpr(-0.714136f), m21 = in_vgpr(1.772f);
+
+    uint32_t acc_sq[3] = { 0u, 0u, 0u }, acc_ab[3] = { 0u, 0u, 0u };        // the run, per channel: sum a^2 + b^2, sum a b
+    int run = 0;
+    unsigned long long sum[3] = { 0ull, 0ull, 0ull };
+    uint32_t cur = tiles ? blockIdx.x / tpf : 0u;                           // the frame `sum` belongs to (workgroup-uniform)
+
+    for (uint32_t t = blockIdx.x; ; t += gridDim.x) {
+        const bool more = t < tiles;
+        const uint32_t f = more ? t / tpf : cur + 1u;
+        if (f != cur) {
+            // ---- frame `cur` is done here: the waves reduce, the workgroup adds once a channel
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                sum[k] += (unsigned long long)(acc_sq[k] - 2u * acc_ab[k]);
+                acc_sq[k] = acc_ab[k] = 0u;
+#pragma unroll
+                for (int m = 32; m >= 1; m >>= 1) sum[k] += __shfl_xor(sum[k], m);
+                if ((threadIdx.x & 63u) == 0u) wave_sum[k][threadIdx.x >> 6] = sum[k];
+                sum[k] = 0ull;
+            }
+            run = 0;
+            __syncthreads();
+            if (threadIdx.x < 3u) {
+                const unsigned long long v = wave_sum[threadIdx.x][0] + wave_sum[threadIdx.x][1] + wave_sum[threadIdx.x][2] +
+                                             wave_sum[threadIdx.x][3];
+                if (v) (void)__hip_atomic_fetch_add(&s.out[3u * cur + threadIdx.x], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __syncthreads();
+            cur = f;
+        }
+        if (!more) break;
+        if (run + kRgbSseTileLoads > RUN) {                                 // (uniform: every lane counts every tile)
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                sum[k] += (unsigned long long)(acc_sq[k] - 2u * acc_ab[k]);
+                acc_sq[k] = acc_ab[k] = 0u;
+            }
+            run = 0;
+        }
+        run += kRgbSseTileLoads;
+        const char *const fc = (const char *)s.c + (unsigned long long)(3u * f) * s.c_z;
+        const float *const c0 = (const float *)fc, *const c1 = (const float *)(fc + s.c_z), *const c2 = (const float *)(fc + 2ull * s.c_z);
+        const unsigned long long at = (unsigned long long)f * s.in_z;
+        uint32_t i = (t - f * tpf) * kTile + threadIdx.x;
+        uint32_t y = i / gpr, g = i - y * gpr;
+#pragma unroll
+        for (int l = 0; l < kRgbSseTileLoads; l++) {
+            if (i < items) {
+                const size_t oc = (size_t)y * s.c_pitch + 4u * (size_t)g, oi = at + (size_t)y * s.in_pitch + 4u * (size_t)g;
+                const float4 vy = *reinterpret_cast<const float4 *>(c0 + oc), vb = *reinterpret_cast<const float4 *>(c1 + oc),
+                             vr = *reinterpret_cast<const float4 *>(c2 + oc);
+                const uint32_t mask = g == gpr - 1u ? tail_mask : 0xFFFFFFFFu;
+                const uint32_t in[3] = { *reinterpret_cast<const uint32_t *>(s.r + oi) & mask, *reinterpret_cast<const uint32_t *>(s.g + oi) & mask,
+                                         *reinterpret_cast<const uint32_t *>(s.b + oi) & mask };
+                const float py[4] = { vy.x, vy.y, vy.z, vy.w }, pb[4] = { vb.x, vb.y, vb.z, vb.w }, pr[4] = { vr.x, vr.y, vr.z, vr.w };
+                uint32_t px[3] = { 0u, 0u, 0u };
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const float yy = py[e], cb = pb[e], cr = pr[e];
+                    const int R = (int)rintf(fmaf(m02, cr, fmaf(0.0f, cb, 1.0f * yy)) + 0.01f);
+                    const int G = (int)rintf(fmaf(m12, cr, fmaf(m11, cb, 1.0f * yy)) + 0.01f);
+                    const int B = (int)rintf(fmaf(0.0f, cr, fmaf(m21, cb, 1.0f * yy)) + 0.01f);
+                    px[0] |= clamp_u8(R + s.off) << (8 * e);
+                    px[1] |= clamp_u8(G + s.off) << (8 * e);
+                    px[2] |= clamp_u8(B + s.off) << (8 * e);
+                }
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const uint32_t p = px[k] & mask;
+                    acc_sq[k] = dot4_u8(p, p, acc_sq[k]);
+                    acc_sq[k] = dot4_u8(in[k], in[k], acc_sq[k]);
+                    acc_ab[k] = dot4_u8(p, in[k], acc_ab[k]);
+                }
+            }
+            i += 256u; y += step_rows; g += step_groups;
+            if (g >= gpr) { g -= gpr; y++; }
         }
     }
 }

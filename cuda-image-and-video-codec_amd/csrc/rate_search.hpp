@@ -49,6 +49,19 @@ inline std::vector<int> rate_grid(int j_min, int j_max)
     return g;
 }
 
+// Candidates a round of the n-frame RGB search calls (picsong_encode_rgb_frames_rate / _quality).  A size round codes
+// its K candidates in ONE coder launch, plane c * 3 n + 3 f + comp with table comp (the batched grid maps plane z to
+// table z % 3), and that grid takes 64 planes: 3 where 3 * 3 n <= 64 (n <= 7), else 1.  A quality round launches no
+// coder and measures its candidates back to back over one set of 3 n-plane buffers: 3.  force_one: PICSONG_RATE_K=1.
+// The result is the procedure's whatever this returns.
+constexpr int kRateMaxCoderPlanes = 64;
+inline int rgb_search_candidates(bool size_search, int n, bool force_one)
+{
+    if (force_one) return 1;
+    if (size_search && kRateMaxK * 3 * n > kRateMaxCoderPlanes) return 1;
+    return kRateMaxK;
+}
+
 // which passing index the procedure keeps: the largest (a pass moves lo: the rate calls) or the smallest (a pass moves
 // hi: the quality calls)
 enum class Bisect { Largest, Smallest };

@@ -55,6 +55,7 @@ struct Options {
     bool has_rate = false, has_qs = false;
     double psnr = 0.0;                          // -psnr <dB>: choose qs so that the searched frames decode to at least that PSNR
     bool has_psnr = false;
+    int search_frames = 0;                      // -searchFrames N: the frames of a video the -rate / -psnr search runs on (0: the default)
     std::string compare;                        // -compare <raw file>: decoding, the PSNR of the output against that file
     int layout = -1;                            // -layout: the pixel layout of the raw file (PICSONG_LAYOUT_*), -1: not given
 };
@@ -127,6 +128,9 @@ void help()
         "                     least dB (an SSE of at most floor(65025 samples / 10^(dB/10)), samples = W H frames components).  A\n"
         "                     video as with -rate: the search runs on the first min(frames, 16) frames (an RGB video: its first\n"
         "                     frame).  Not with -qs, -rate, -type 0, -cp 3 or -train\n"
+        " -searchFrames N     coding, -video 1 with -rate or -psnr: the search runs on the first min(N, frames) frames -- grey\n"
+        "                     N = 1..16, an RGB video N = 1..21 (one search call over the N colour frames, whose streams are\n"
+        "                     the search's own output).  Without it: grey min(frames, 16), an RGB video its first frame\n"
         " -compare <file>     decoding: after the output is written, print its PSNR and SSE against that raw (or PGM) file of the\n"
         "                     same geometry and planar layout.  Not with -reduce or -window\n"
         " -layout grey|planar|rgb|bgr|rgba|bgra\n"
@@ -185,6 +189,11 @@ Options parse(const Args &a)
         o.has_psnr = true;
         if (v.empty() || *end != '\0' || !std::isfinite(o.psnr)) die("Incorrect parameters. -psnr takes a PSNR in dB.");
         echo("-psnr", v);
+    }
+    if (a.has("-searchFrames")) {
+        if (o.cd != 0) die("Incorrect parameters. -searchFrames applies to coding (-cd 0) only.");
+        geti("-searchFrames", o.search_frames);
+        if (o.search_frames < 1) die("Incorrect parameters. -searchFrames takes a number of frames, 1 or more.");
     }
     if (a.has("-compare")) {
         if (o.cd != 1) die("Incorrect parameters. -compare applies to decoding (-cd 1) only.");
@@ -312,6 +321,7 @@ picsong_params make_params(const Options &o)
 
 // ---- -psnr <dB>: what the search chose and what it achieved (the two console lines; --metrics carries them too)
 struct QualityReport { bool reported = false; int j = 0; float qs = 0; uint64_t max_sse = 0, sse = 0, samples = 0; long frames = 0; double psnr = 0; } g_quality;
+long g_frames_searched = 0;             // the frames a -rate / -psnr search ran on (--metrics: "search_frames")
 
 void write_metrics(const Options &o, const char *mode, long frames, double seconds, double dwt, double bpc,
                    double pack, long shorts)
@@ -329,6 +339,7 @@ void write_metrics(const Options &o, const char *mode, long frames, double secon
         m << ", \"psnr_target\": " << o.psnr << ", \"psnr_j\": " << g_quality.j << ", \"psnr_qs\": " << g_quality.qs
           << ", \"psnr_max_sse\": " << g_quality.max_sse << ", \"psnr_frames_searched\": " << g_quality.frames
           << ", \"psnr_sse\": " << g_quality.sse << ", \"psnr_achieved\": " << g_quality.psnr;
+    if (g_frames_searched > 0) m << ", \"search_frames\": " << g_frames_searched;
     if (o.win)
         m << ", \"window\": [" << o.wx << ", " << o.wy << ", " << o.ww << ", " << o.wh << "], \"codeblocks\": " << o.win_cb;
     m << "}\n";
@@ -342,6 +353,7 @@ size_t rate_target_shorts(const Options &o)
 }
 void rate_report_choice(int j, float qs, size_t target, long nframes_searched)
 {
+    g_frames_searched = nframes_searched;
     std::cout << "Rate control: qs " << qs << " (j = " << j << ") chosen for " << target << " shorts over " << nframes_searched
               << " frame(s)" << std::endl;
 }
@@ -353,6 +365,7 @@ void rate_report_achieved(const Options &o, long total_shorts, long nframes)
 void quality_report(int j, float qs, uint64_t max_sse, uint64_t samples, long nframes_searched, const uint64_t *sse, int n)
 {
     QualityReport &r = g_quality;
+    g_frames_searched = nframes_searched;
     r.reported = true; r.j = j; r.qs = qs; r.max_sse = max_sse; r.samples = samples; r.frames = nframes_searched; r.sse = 0;
     for (int i = 0; i < n; i++) r.sse += sse[i];
     CK(picsong_sse_to_psnr(r.sse, samples, &r.psnr));
@@ -461,6 +474,73 @@ void encode_rgb_groups(const Options &o, picsong_ctx *ctx, hipStream_t s, std::i
     (void)hipHostFree(h_in); (void)hipFree(d_in); (void)hipHostFree(h_out); (void)hipFree(d_out);
 }
 
+// -searchFrames N on an RGB video (-cp 2): the -rate / -psnr search over the first n frames through ONE call
+// (picsong_encode_rgb_frames_rate / _quality) on host-padded planes or, -layout, on the planes one picsong_ingest_frames
+// makes of the frames as the file holds them.  The n frames' streams are the call's own output, written here with their
+// _SIZE entries; returns the chosen qs -- the caller re-tunes the context and continues behind frame n - 1.
+float rgb_search_frames(const Options &o, picsong_ctx *ctx, hipStream_t s, std::ifstream &in, size_t file_base, int n, std::ofstream &out,
+                        std::ofstream &sizes, long &total_shorts)
+{
+    const int aw = picsong_pad_dim(o.x), ah = picsong_pad_dim(o.y);
+    const size_t P = (size_t)aw * ah, max_shorts = picsong_max_stream_shorts(aw, ah);
+    const size_t raw_bytes = o.layout >= 0 ? layout_frame_bytes(o.layout, o.x, o.y) : 0;
+    const size_t frame_bytes = o.layout >= 0 ? raw_bytes : 3 * P;
+    uint8_t *h_in = nullptr, *d_raw = nullptr, *d_pad = nullptr;
+    uint16_t *h_out = nullptr, *d_out = nullptr;
+    HIPCK(hipHostMalloc(&h_in, frame_bytes * (size_t)n));
+    HIPCK(hipMalloc(&d_pad, 3 * P * (size_t)n));
+    HIPCK(hipHostMalloc(&h_out, max_shorts * 2 * 3 * (size_t)n));
+    HIPCK(hipMalloc(&d_out, max_shorts * 2 * 3 * (size_t)n));
+    if (o.layout >= 0) {
+        in.clear();
+        in.seekg((std::streamoff)file_base);
+        in.read(reinterpret_cast<char *>(h_in), (std::streamsize)(raw_bytes * (size_t)n));
+        if ((size_t)in.gcount() != raw_bytes * (size_t)n) die("Input file is shorter than the requested frames.");
+        HIPCK(hipMalloc(&d_raw, raw_bytes * (size_t)n));
+        HIPCK(hipMemcpyAsync(d_raw, h_in, raw_bytes * (size_t)n, hipMemcpyHostToDevice, s));
+        const picsong_image im = layout_image(o.layout, d_raw, o.x, o.y);
+        CK(picsong_ingest_frames(ctx, n, &im, raw_bytes, d_pad, 3 * P, s));
+    } else {
+        std::vector<uint8_t> raw((size_t)o.x * o.y);
+        for (int j = 0; j < 3 * n; j++) {
+            if (!read_frame(in, file_base, (size_t)j, o.x, o.y, raw.data())) die("Input file is shorter than the requested frames.");
+            CK(picsong_pad_frame_host(raw.data(), o.x, o.y, h_in + (size_t)j * P, aw, ah));
+        }
+        HIPCK(hipMemcpyAsync(d_pad, h_in, 3 * P * (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    const size_t target = rate_target_shorts(o) * (size_t)n;
+    const uint64_t samples = (uint64_t)o.x * (uint64_t)o.y * 3ull * (uint64_t)n;
+    uint64_t lim = 0;
+    if (o.has_psnr && picsong_psnr_to_sse(o.psnr, samples, &lim) != PICSONG_OK) die(std::string("-psnr: ") + picsong_last_error());
+    std::vector<int> totals(3 * (size_t)n, 0);
+    std::vector<uint64_t> sse(3 * (size_t)n, 0);
+    int j = 0;
+    float qs = 0.0f;
+    const int rc = o.has_psnr ? picsong_encode_rgb_frames_quality(ctx, n, d_pad, d_pad + P, d_pad + 2 * P, 3 * P, 0, 7, lim, 0, 0, d_out, max_shorts,
+                                                                  s, &j, totals.data(), sse.data())
+                              : picsong_encode_rgb_frames_rate(ctx, n, d_pad, d_pad + P, d_pad + 2 * P, 3 * P, 0, 7, target, 0, 0, d_out, max_shorts,
+                                                               s, &j, totals.data());
+    if (rc == PICSONG_ERR_RATE) die(std::string("-rate: no quantiser meets the target size (") + picsong_last_error() + ")");
+    if (rc == PICSONG_ERR_QUALITY) die(std::string("-psnr: no quantiser meets the target quality (") + picsong_last_error() + ")");
+    if (rc != PICSONG_OK || picsong_rate_qs(j, &qs) != PICSONG_OK) die(std::string("The quantiser search failed: ") + picsong_last_error());
+    if (o.has_psnr) quality_report(j, qs, lim, samples, n, sse.data(), 3 * n);
+    else rate_report_choice(j, qs, target, n);
+    size_t at = 0;
+    for (int z = 0; z < 3 * n; z++) {
+        HIPCK(hipMemcpyAsync(h_out + at, d_out + (size_t)z * max_shorts, (size_t)totals[(size_t)z] * 2, hipMemcpyDeviceToHost, s));
+        at += (size_t)totals[(size_t)z];
+    }
+    HIPCK(hipStreamSynchronize(s));
+    out.write(reinterpret_cast<const char *>(h_out), (std::streamsize)(at * 2));
+    for (int z = 0; z < 3 * n; z++) {
+        if (z == 0) sizes << totals[(size_t)z]; else sizes << "," << totals[(size_t)z];
+        total_shorts += totals[(size_t)z];
+    }
+    (void)hipHostFree(h_in); (void)hipFree(d_pad); (void)hipHostFree(h_out); (void)hipFree(d_out);
+    if (d_raw) (void)hipFree(d_raw);
+    return qs;
+}
+
 // ---- RGB coding (CodingEngine::runImage / runVideo, RGB branches: CodingEngine.cu:598-633,676-712,
 // 760-818,873-930): the input holds planar R, G, B planes per frame; RCT / ICT with the level shift
 // fused, then every component is coded as a frame of its own with its own LUT and appended to <o>,
@@ -502,7 +582,13 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
     // a video (-cp 2): groups of frames through one call each (encode_rgb_groups) -- behind the first frame where that one
     // carries the -rate / -psnr search; an image and -cp 3: frame by frame, here
     const bool grouped = o.video && batched;
-    const long nloop = grouped ? ((o.has_rate || o.has_psnr) ? 1 : 0) : nframes;
+    long nloop = grouped ? ((o.has_rate || o.has_psnr) ? 1 : 0) : nframes;
+    long searched = 0;                                   // -searchFrames: the frames the n-frame search call coded itself
+    if (grouped && o.search_frames > 0) {
+        searched = std::min<long>(o.search_frames, nframes);
+        CK(picsong_ctx_set_qs(ctx, rgb_search_frames(o, ctx, s, in, file_base, (int)searched, out, sizes, total_shorts)));
+        nloop = 0;
+    }
     for (long f = 0; f < nloop; f++) {
         if (o.layout >= 0) {
             in.clear();
@@ -548,7 +634,8 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
             total_shorts += total;
         }
     }
-    if (grouped && nloop < nframes) encode_rgb_groups(o, ctx, s, in, file_base, nloop, nframes, out, sizes, total_shorts);
+    if (grouped && std::max(nloop, searched) < nframes)
+        encode_rgb_groups(o, ctx, s, in, file_base, std::max(nloop, searched), nframes, out, sizes, total_shorts);
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::cout << "The time spent with the app without considering allocation periods is: " << sec << std::endl;
     if (o.has_rate) rate_report_achieved(o, total_shorts, nframes);
@@ -681,6 +768,12 @@ int run_encode(Options o)
         if (o.cp == 3) die("Incorrect parameters. -psnr does not apply to -cp 3.");
         if (!o.train.empty()) die("Incorrect parameters. -psnr does not apply to -train.");
     }
+    if (o.search_frames > 0) {
+        if (!o.video) die("Incorrect parameters. -searchFrames applies to a video (-video 1) only.");
+        if (!o.has_rate && !o.has_psnr) die("Incorrect parameters. -searchFrames needs -rate or -psnr: it sizes their search.");
+        if (o.search_frames > (o.is_rgb ? 21 : 16))
+            die(o.is_rgb ? "Incorrect parameters. -searchFrames takes 1..21 frames of an RGB video." : "Incorrect parameters. -searchFrames takes 1..16 grey frames.");
+    }
     layout_check_context(o.layout, o.is_rgb != 0);
     if (o.layout >= 0 && !o.train.empty()) die("Incorrect parameters. -layout does not apply to -train.");
     if (!o.train.empty()) {
@@ -749,7 +842,7 @@ int run_encode(Options o)
     if ((o.has_rate || o.has_psnr) && o.video) {
         // -rate on a video: the first slot's context (rank 0 of -gpus N) searches on the first min(frames, 16) frames and
         // their summed target, then every context takes the chosen qs: the stream has one header, hence one qs
-        const int n = (int)std::min<long>(nframes, 16);
+        const int n = (int)std::min<long>(nframes, o.search_frames > 0 ? o.search_frames : 16);
         Worker &k = w[0];
         HIPCK(hipSetDevice(k.device));
         uint8_t *h_f = nullptr, *d_f = nullptr;

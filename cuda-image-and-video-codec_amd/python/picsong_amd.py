@@ -71,6 +71,7 @@ EXPORTS = [
     "picsong_encode_rgb_frames", "picsong_decode_rgb_frames", "picsong_encode_rgb_images", "picsong_decode_rgb_images",
     "picsong_decode_rgb_frames_reduced", "picsong_decode_rgb_frames_window", "picsong_decode_rgb_images_reduced",
     "picsong_decode_rgb_images_window",
+    "picsong_encode_rgb_frames_rate", "picsong_encode_rgb_frames_quality", "picsong_train_rgb_frames",
 ]
 
 _lib = None
@@ -205,6 +206,13 @@ def load():
         L.picsong_decode_rgb_frames_window.argtypes = [vp, i, vp, C.c_size_t, i, i, i, i, i, vp, vp, vp, C.c_size_t, C.c_size_t, vp]
         L.picsong_decode_rgb_images_reduced.argtypes = [vp, i, vp, C.c_size_t, i, img, C.c_size_t, vp]
         L.picsong_decode_rgb_images_window.argtypes = [vp, i, vp, C.c_size_t, i, i, i, i, i, img, C.c_size_t, vp]
+    if hasattr(L, "picsong_encode_rgb_frames_rate"):
+        u64 = C.c_uint64
+        L.picsong_encode_rgb_frames_rate.argtypes = [vp, i, vp, vp, vp, C.c_size_t, i, i, C.c_size_t, i, i, vp, C.c_size_t, vp,
+                                                     C.POINTER(i), C.POINTER(i)]
+        L.picsong_encode_rgb_frames_quality.argtypes = [vp, i, vp, vp, vp, C.c_size_t, i, i, u64, i, i, vp, C.c_size_t, vp,
+                                                        C.POINTER(i), C.POINTER(i), C.POINTER(u64)]
+        L.picsong_train_rgb_frames.argtypes = [vp, i, vp, vp, vp, C.c_size_t, vp]
     _lib = L
     return L
 
@@ -604,6 +612,43 @@ class Codec:
         _check(self.L.picsong_encode_rgb_frames(self.h, n, self._p(r), self._p(g), self._p(b), frame_stride, first_iter, header_mask,
                                                 self._p(out), out.stride(0), self._stream()))
         return [out[k, :t] for k, t in enumerate(self.last_totals(3 * n))]
+
+    def _rgb_frames_span(self, r, g, b, n, frame_stride):
+        if n is None:
+            n = r.shape[0]
+        if frame_stride is None:
+            frame_stride = r.stride(0) if n > 1 else 0
+            assert n == 1 or (g.stride(0) == frame_stride and b.stride(0) == frame_stride)
+        return n, frame_stride
+
+    def encode_rgb_frames_rate(self, r, g, b, target_shorts, j_min=0, j_max=0, n=None, frame_stride=None, first_iter=0,
+                               header_mask=7):
+        """The quantiser search over n RGB frames (r / g / b as encode_rgb_frames takes them); target_shorts for the sum
+        of the 3 n streams.  Returns (j, the 3 n codestreams, frame f's component c at index 3 f + c)."""
+        n, frame_stride = self._rgb_frames_span(r, g, b, n, frame_stride)
+        out = self.torch.empty((3 * n, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        j, t = C.c_int(), (C.c_int * (3 * n))()
+        _check_rate(self.L.picsong_encode_rgb_frames_rate(self.h, n, self._p(r), self._p(g), self._p(b), frame_stride, first_iter,
+                                                          header_mask, target_shorts, j_min, j_max, self._p(out), out.stride(0),
+                                                          self._stream(), C.byref(j), t))
+        return j.value, [out[k, :t[k]] for k in range(3 * n)]
+
+    def encode_rgb_frames_quality(self, r, g, b, max_sse, j_min=0, j_max=0, n=None, frame_stride=None, first_iter=0,
+                                  header_mask=7):
+        """max_sse for the sum over the 3 n planes.  Returns (j, the 3 n codestreams, the SSE per plane: frame f's R, G, B
+        at 3 f ..)."""
+        n, frame_stride = self._rgb_frames_span(r, g, b, n, frame_stride)
+        out = self.torch.empty((3 * n, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        j, t, e = C.c_int(), (C.c_int * (3 * n))(), (C.c_uint64 * (3 * n))()
+        _check_quality(self.L.picsong_encode_rgb_frames_quality(self.h, n, self._p(r), self._p(g), self._p(b), frame_stride,
+                                                                first_iter, header_mask, max_sse, j_min, j_max, self._p(out),
+                                                                out.stride(0), self._stream(), C.byref(j), t, e))
+        return j.value, [out[k, :t[k]] for k in range(3 * n)], [int(v) for v in e]
+
+    def train_rgb_frames(self, r, g, b, n=None, frame_stride=None):
+        """n RGB frames' statistics, component c of every frame into slot c (picsong_train_rgb_frames)."""
+        n, frame_stride = self._rgb_frames_span(r, g, b, n, frame_stride)
+        _check(self.L.picsong_train_rgb_frames(self.h, n, self._p(r), self._p(g), self._p(b), frame_stride, self._stream()))
 
     def decode_rgb_frames(self, streams, outs=None, frame_stride=None):
         """streams: int16 [3 n, >= max_stream_shorts()]; returns the R, G, B planes as three uint8 [n, AH, AW] tensors

@@ -335,6 +335,8 @@ int picsong_decode_rgb_frame_window(picsong_ctx *ctx, const uint16_t *d_streams,
  *        form as picsong_encode_frames does; any other pointer or stride is accepted too (per-column kernels, 32-bit
  *        arrays, a transform launch a frame): same counts, slower.
  *      picsong_train_rgb_frame: RCT / ICT + transform as picsong_encode_rgb_frame; component c into slot c.
+ *      picsong_train_rgb_frames (declared with the n-frame RGB search calls below): n = 1..21 frames as
+ *        picsong_encode_rgb_frames addresses them, one transform and a statistics launch a component; the same counts.
  *      picsong_train_counts: synchronises `stream` and copies slot `component` to h_counts ([entry][2]: zeros, ones;
  *        capacity_entries >= the entry count); with h_counts == NULL it returns the entry count instead.
  *      All but picsong_train_counts are asynchronous on `stream` and accumulate across calls; picsong_train_reset
@@ -465,6 +467,48 @@ int picsong_encode_frames_quality(picsong_ctx *ctx, int n, const uint8_t *d_fram
 int picsong_encode_rgb_frame_quality(picsong_ctx *ctx, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, int header_mask,
                                      uint64_t max_sse, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
                                      void *stream, int *h_j, int *h_totals, uint64_t *h_sse);
+
+/* ---- the search over n RGB frames: a colour video has ONE header, so one qs for all its frames; these calls choose
+ *      it over the first n of them instead of over frame 0 alone.  The semantics are those of the two sections above,
+ *      unchanged -- the grid G, the sub-range G', the two bisection procedures that define the result -- with
+ *      size(j) = the sum of the 3 n stream lengths and sse(j) = the sum over the 3 n planes; target_shorts / max_sse apply
+ *      to those sums.  n = 1..21.  Addressing, first_iter, header_mask and the placement of the streams are
+ *      picsong_encode_rgb_frames': frame f's planes frame_stride bytes after d_r / d_g / d_b, its component c's stream at
+ *      d_streams + (3 f + c) * stream_stride, the populated header on the components of header_mask of the frame with
+ *      first_iter + f == 0.
+ *      On success *h_j is the result, the 3 n streams are BYTE-IDENTICAL to picsong_encode_rgb_frames' on a context at
+ *      q(*h_j) with the same first_iter and header_mask (the header carries that qs), h_totals[3 n] their lengths and
+ *      h_sse[3 n] the SSE per plane (frame f's R, G, B at 3 f ..); the lengths also stay where the plain call leaves
+ *      them (picsong_last_totals(3 n) / picsong_copy_last_totals).  Nothing fits: PICSONG_ERR_RATE / PICSONG_ERR_QUALITY
+ *      with *h_j = 0; no short beyond picsong_max_stream_shorts per stream is ever written.  SYNCHRONOUS on `stream`; the
+ *      context's own qs is NOT changed; any -k.
+ *      How.  A size round codes three candidates in one batched coder launch where 3 * 3 n <= 64 planes (n <= 7: plane
+ *      c * 3 n + 3 f + comp still meets table comp), else one.  A quality round measures three candidates back to back
+ *      over one set of 3 n-plane buffers; a probe is the quantise pass, ONE synthesis over the 3 n planes and ONE kernel
+ *      that applies the inverse ICT to the float planes and sums the squared error against the input without writing a
+ *      pixel (PICSONG_RGB_SSE_FUSED=0, read per call, keeps the separate colour transform and three SSE launches a frame:
+ *      same sums).  PICSONG_RATE_K=1 keeps one candidate a round.  The result is the procedure's whatever the number of
+ *      candidates.  picsong_range_flag ACCUMULATES OVER EVERY PROBE MADE by a size search -- with three candidates a
+ *      round that includes probes the procedure ignores, and probes finer than the result -- so it can be raised where
+ *      the result's own stream would not raise it; a quality search's probes run no coder and it sees the result's own
+ *      encode only.  The single-frame calls above keep one candidate a size round, and their results, range flag included.
+ *      picsong_train_rgb_frames (see the training section): n = 1..21 frames through one transform and three statistics
+ *      launches, component c of every frame into slot c; the counts of n picsong_train_rgb_frame calls.
+ *      Refused (PICSONG_ERR_ARG, nothing launched, outputs untouched): everything picsong_encode_rgb_frames refuses
+ *      (null pointers, a grey or -cp 3 context, n outside 1..21, a stream stride below the worst case, with n > 1 a
+ *      frame_stride below a padded plane or one that makes frames overlap, tables that differ in geometry); everything
+ *      the single-frame search calls refuse (lossless contexts, target_shorts = 0, a bad range or one without a grid
+ *      entry, null h_j / h_totals / h_sse, a context without its tables); planes that are not 4-byte aligned; with
+ *      n > 1 a frame_stride that is not a multiple of 4. ---- */
+int picsong_encode_rgb_frames_rate(picsong_ctx *ctx, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b,
+                                   size_t frame_stride, int first_iter, int header_mask, size_t target_shorts, int j_min,
+                                   int j_max, uint16_t *d_streams, size_t stream_stride, void *stream, int *h_j, int *h_totals);
+int picsong_encode_rgb_frames_quality(picsong_ctx *ctx, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b,
+                                      size_t frame_stride, int first_iter, int header_mask, uint64_t max_sse, int j_min,
+                                      int j_max, uint16_t *d_streams, size_t stream_stride, void *stream, int *h_j,
+                                      int *h_totals, uint64_t *h_sse);
+int picsong_train_rgb_frames(picsong_ctx *ctx, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b,
+                             size_t frame_stride, void *stream);
 
 /* ---- frames as applications hold them (the reference reads files only, IO/IOManager.ipp:72-112; nvJPEG2000 and
  *      friends take a pitched image descriptor): W x H pixels (the context's unpadded -xSize / -ySize) at a byte pitch,
