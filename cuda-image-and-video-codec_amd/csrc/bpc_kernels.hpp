@@ -115,6 +115,10 @@ struct BpcArgs {
     // are the one-rectangle case of the same mapping.  waves_per_frame counts the table's waves.  0: not used.
     int win_n;
     int win_x[kBpcWinRects], win_y[kBpcWinRects], win_w[kBpcWinRects], win_before[kBpcWinRects + 1];
+    // decoders, k = 0, -cp 2 (picsong_ctx_set_decode_drop): a codeblock whose corner lies in level `lv` (find_subband)
+    // decodes its planes down to d = max(0, drop - lv) and stops; the d planes below are not read, a significant
+    // coefficient gets the interval's midpoint 1 << (d - 1) for them (bpc_decode_drop_kernel).  0: every plane.
+    int drop;
 };
 
 // ---- cross-lane helpers ---------------------------------------------------------------------
@@ -2608,10 +2612,13 @@ constexpr int kDecSmallPlanes = 8;
 // kernels' C16 instantiations -- half the bytes the decoder writes and the transform reads.  Only in contexts whose
 // magnitudes are bounded below 2^15 (coef16_ok: an honest stream's codeblocks have MSB <= 14 there; a damaged table
 // that claims more raises the range flag and decodes to wrapped values -- "something", as every damaged stream does)
-template <bool BULK, int NP, bool S16 = false, bool C16 = false, bool COMPACT = false>
-__global__ __launch_bounds__(BULK ? 64 : 64 * kBpcDecWgWaves, !BULK ? PICSONG_BPC_DEC_WAVES8 : PICSONG_BPC_BULK_WAVES)
-void bpc_decode_kernel(BpcArgs a)
+// DROP (k = 0 only): the reduced-quality form (BpcArgs::drop) -- the half's cbp, elsewhere the constant 0, is its
+// codeblock's d; plane d - 1 comes back from the epilogue as the significance masks (the midpoint).  The body is shared
+// by two kernel names, bpc_decode_kernel (DROP = false: its code is what it was) and bpc_decode_drop_kernel.
+template <bool BULK, int NP, bool S16, bool C16, bool COMPACT, bool DROP>
+__device__ __forceinline__ void bpc_decode_body(BpcArgs a)
 {
+    static_assert(!DROP || !BULK, "planes below a -k > 0 codeblock's cbp are the bulk scan's: no drop form");
     static_assert(NP == kDecSmallPlanes, "one instantiation for every plane count (the planes are parked in the scratch)");
     // the int16 form stores a raw codeblock's (word & 0xFFFFFF) >> 1: only the packed stream's uint16 words (S16) keep
     // that within 0x7FFF; a staging word may carry more bits
@@ -2739,6 +2746,12 @@ void bpc_decode_kernel(BpcArgs a)
     M64 sigL = { 0u, 0u }, sigR = { 0u, 0u }, refL = { 0u, 0u }, refR = { 0u, 0u };
 
     int cbp = 0, loff = 0;
+    if constexpr (DROP) {
+        // per half, from the codeblock's corner and not the lane's own column: a codeblock that straddles subbands has one d
+        int lv0, sb0;
+        find_subband(cbx * 64, cby * 64, a.AW, a.AH, a.wl, lv0, sb0);
+        cbp = a.drop > lv0 ? a.drop - lv0 : 0;
+    }
     BulkLane bl;
     LutGeo gl = a.g;                                         // (COMPACT: the copy's own section sizes and the lane's group in it)
     int grpc = grp;
@@ -2847,11 +2860,23 @@ void bpc_decode_kernel(BpcArgs a)
     // its cbp: the bulk scan's -- were never written and read as zero.
     {
         const bool have = coded;
+        // DROP: the midpoint of the dropped planes is ONE plane, cbp - 1, set in every coefficient the decoded planes made
+        // significant -- the final significance row masks (X-form, as the planes are).  It is parked in the scratch like
+        // a decoded plane (the lane's own slot: read back below by the lane that wrote it) and the epilogue reads one plane
+        // further down; no register array is indexed with a run-time value.  MSB < cbp - 1: nothing significant, not read.
+        int plo = cbp;
+        if constexpr (DROP) {
+            plo = cbp - 1;
+            if (have && cbp >= 1) {
+                uint32_t *q = pscr + (size_t)(cbp - 1) * kEncPlaneDwords;
+                q[0] = sigL.lo; q[64] = sigL.hi; q[128] = sigR.lo; q[192] = sigR.hi;
+            }
+        }
         auto planes_of = [&](auto &A, auto &B, int hw, int n) {
 #pragma unroll
             for (int k = 0; k < (int)(sizeof(A) / sizeof(A[0])); k++) {
                 A[k] = 0u; B[k] = 0u;
-                if (k < n && have && k <= msb && k >= cbp) {
+                if (k < n && have && k <= msb && k >= plo) {
                     const uint32_t *q = pscr + (size_t)k * kEncPlaneDwords + hw * 64;
                     A[k] = q[0]; B[k] = q[128];
                 }
@@ -2920,6 +2945,20 @@ void bpc_decode_kernel(BpcArgs a)
             }
         }
     }
+}
+template <bool BULK, int NP, bool S16 = false, bool C16 = false, bool COMPACT = false>
+__global__ __launch_bounds__(BULK ? 64 : 64 * kBpcDecWgWaves, !BULK ? PICSONG_BPC_DEC_WAVES8 : PICSONG_BPC_BULK_WAVES)
+void bpc_decode_kernel(BpcArgs a)
+{
+    bpc_decode_body<BULK, NP, S16, C16, COMPACT, false>(a);
+}
+// The reduced-quality decode (BpcArgs::drop > 0) of the three k = 0 forms.  Kernel names of their own, not further
+// template parameters of bpc_decode_kernel: what counts and bounds that kernel's instantiations stays true of them.
+template <bool S16 = false, bool C16 = false>
+__global__ __launch_bounds__(64 * kBpcDecWgWaves, PICSONG_BPC_DEC_WAVES8)
+void bpc_decode_drop_kernel(BpcArgs a)
+{
+    bpc_decode_body<false, kDecSmallPlanes, S16, C16, false, true>(a);
 }
 
 

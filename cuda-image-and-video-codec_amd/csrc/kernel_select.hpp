@@ -171,9 +171,17 @@ inline BpcLaunch select_encoder(bool cp3, bool bulk, bool compact_pipelined, uns
 // (BpcArgs::cw16*), not the staging; c16 (with from_stream only): the coefficients leave as an int16 Mallat array.
 // kernel = nullptr: refused -- the 16-bit coefficient form decodes from the stream itself.
 // (-k > 0 is one launch: the two-pass planes are parked in the scratch whatever their number)
-inline BpcLaunch select_decoder(bool cp3, bool bulk, bool compact, bool from_stream, bool c16, unsigned waves)
+// drop (BpcArgs::drop > 0, k = 0 and -cp 2 only -- refused elsewhere): the reduced-quality kernels, one for each of the
+// three k = 0 forms, on the same grid and scratch; false: exactly the choice below, as ever
+inline BpcLaunch select_decoder(bool cp3, bool bulk, bool compact, bool from_stream, bool c16, unsigned waves, bool drop = false)
 {
     if (c16 && !from_stream) return { nullptr, 0, 0, 0 };
+    if (drop) {
+        if (cp3 || bulk) return { nullptr, 0, 0, 0 };
+        if (c16) return bpc_launch(bpc_decode_drop_kernel<true, true>, kBpcDecWgWaves, waves);
+        if (from_stream) return bpc_launch(bpc_decode_drop_kernel<true>, kBpcDecWgWaves, waves);
+        return bpc_launch(bpc_decode_drop_kernel<>, kBpcDecWgWaves, waves);
+    }
     if (cp3) return bpc_launch(bpc3_kernel<true>, kBpc3WgWaves, waves);
     if (bulk) {
         BpcKernel k = compact ? bpc_decode_kernel<true, kDecSmallPlanes, false, false, true> : bpc_decode_kernel<true, kDecSmallPlanes>;

@@ -307,6 +307,26 @@ inline std::vector<InvLaunch> plan_dwt_inverse(const int32_t *d_in, void *d_out,
 }
 inline bool plan_inv_is_c16(const std::vector<InvLaunch> &plan) { return !plan.empty() && plan[0].a.c16 != 0; }
 
+// ---- reduced-quality decode (picsong_ctx_set_decode_drop; no reference counterpart): the planes a codeblock leaves
+// undecoded under the context's `drop`.  The level of raster codeblock cb is that of its top-left sample (find_subband,
+// bpc_kernels.hpp: 0 the finest detail level, wl the LL band) -- one value a codeblock, also where it straddles subbands --
+// and it drops max(0, drop - level) planes: one plane more a level finer, about the growth of a coefficient's weight in
+// the image per synthesis level.
+constexpr int kDropMax = 15;
+inline bool drop_ok(int drop) { return drop >= 0 && drop <= kDropMax; }
+inline int codeblock_level(int aw, int ah, int wl, int cb)
+{
+    const int ncx = aw / 64, x = (cb % ncx) * 64, y = (cb / ncx) * 64;
+    for (int a = 1; a <= wl; a++)
+        if (x >= (aw >> a) || y >= (ah >> a)) return a - 1;
+    return wl;
+}
+inline int drop_planes_of(int aw, int ah, int wl, int drop, int cb)
+{
+    const int lv = codeblock_level(aw, ah, wl, cb);
+    return drop > lv ? drop - lv : 0;
+}
+
 // ---- reduced-resolution decode (picsong_decode_frame_reduced and its mirrors; no reference counterpart).  The image
 // at 1/2^r of the frame's size is LL_r, the synthesis stopped after level r.  Its inputs -- the subbands of levels
 // r + 1 .. wl and LL_wl -- fill the corner [0, AW >> r) x [0, AH >> r) of the Mallat array, so only the codeblocks that

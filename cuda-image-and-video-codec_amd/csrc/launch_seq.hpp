@@ -219,11 +219,12 @@ constexpr int kLaunchRefused = -1000;
 // most cw16_max long, at w.offsets (stream_intake's scan); w.staging is then not read
 // c16 (with streams): the coefficients leave as int16 Mallat arrays (bpc_decode_kernel's C16 form)
 // compact: the tables of the launch take the COMPACT copies (-k > 0, bulk_compact)
+// a.drop > 0 (picsong_ctx_set_decode_drop; k = 0, -cp 2): the reduced-quality kernels -- same grid, same arguments
 template <class Go>
 int launch_decoder(const Go &go, BpcArgs &a, bool cp3, unsigned waves, bool compact, const Workspace &w, const uint16_t *streams,
                    size_t stride, uint32_t cw16_max, bool c16)
 {
-    const BpcLaunch l = select_decoder(cp3, a.k > 0.0f, compact, streams != nullptr, c16, waves);
+    const BpcLaunch l = select_decoder(cp3, a.k > 0.0f, compact, streams != nullptr, c16, waves, a.drop > 0);
     if (!l.kernel) return kLaunchRefused;
     a.coeffs_out = w.coef_i; a.staging = w.staging; a.sizes = w.sizes; a.plane_scratch = w.plane_scratch;
     if (streams) { a.cw16 = streams; a.cw16_offsets = w.offsets; a.cw16_total = w.total; a.cw16_stride = stride; a.cw16_max = cw16_max; }

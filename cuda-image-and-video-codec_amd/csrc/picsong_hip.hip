@@ -68,6 +68,7 @@ struct picsong_ctx {
     bool c16_dec;         // decode frame paths: ... and between decoder and synthesis (dec_c16_ok)
     int bulk_compact[3];  // -k > 0: the component's table geometry lets every codeblock use the compact LDS copy (-1: not looked at yet)
     bool pipelined;       // picsong_ctx_set_pipelined: other frames share the GPU (throughput over latency)
+    int drop;             // picsong_ctx_set_decode_drop: the decoders' BpcArgs::drop (0: every plane)
     // LUT
     picsong_lut_info li[3];
     int32_t *d_lut[3];
@@ -551,6 +552,36 @@ int picsong_ctx_set_pipelined(picsong_ctx *c, int on)
     return PICSONG_OK;
 }
 
+int picsong_ctx_set_decode_drop(picsong_ctx *c, int drop)
+{
+    if (!c) return fail(PICSONG_ERR_ARG, "set_decode_drop: null context");
+    if (!drop_ok(drop)) return fail(PICSONG_ERR_ARG, "set_decode_drop: drop %d outside 0..%d", drop, kDropMax);
+    if (c->p.k > 0.0f) return fail(PICSONG_ERR_ARG, "set_decode_drop: a -k > 0 context codes the planes below cbp in its bulk scan");
+    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "set_decode_drop: a -cp 3 context codes a plane in three passes");
+    c->drop = drop;
+    return PICSONG_OK;
+}
+
+int picsong_ctx_get_decode_drop(const picsong_ctx *c, int *drop)
+{
+    if (!c || !drop) return fail(PICSONG_ERR_ARG, "get_decode_drop: null argument");
+    *drop = c->drop;
+    return PICSONG_OK;
+}
+
+int picsong_drop_planes(int aw, int ah, int wl, int drop, int cb, int *planes)
+{
+    if (!planes) return fail(PICSONG_ERR_ARG, "drop_planes: null argument");
+    if (aw < PICSONG_CB || ah < PICSONG_CB || aw % PICSONG_CB || ah % PICSONG_CB)
+        return fail(PICSONG_ERR_ARG, "drop_planes: %d x %d is no padded size (positive multiples of %d)", aw, ah, PICSONG_CB);
+    if (wl < 1 || wl > 7) return fail(PICSONG_ERR_ARG, "drop_planes: wl %d outside 1..7", wl);
+    if (!drop_ok(drop)) return fail(PICSONG_ERR_ARG, "drop_planes: drop %d outside 0..%d", drop, kDropMax);
+    if (cb < 0 || cb >= (aw / PICSONG_CB) * (ah / PICSONG_CB))
+        return fail(PICSONG_ERR_ARG, "drop_planes: codeblock %d outside 0..%d", cb, (aw / PICSONG_CB) * (ah / PICSONG_CB) - 1);
+    *planes = drop_planes_of(aw, ah, wl, drop, cb);
+    return PICSONG_OK;
+}
+
 int picsong_ctx_set_qs(picsong_ctx *c, float qs)
 {
     if (!c) return fail(PICSONG_ERR_ARG, "set_qs: null context");
@@ -662,6 +693,7 @@ static int bpc_args(picsong_ctx *c, BpcArgs &a, int comp = 0)
     a = bpc_frame_args(c->aw, c->ah, c->p.wl, c->d_lut[comp], lut_geo(li), c->d_flag);
     a.plane_img = ctx_uses_plane_img(c) ? c->d_img[comp] : nullptr;
     a.k = c->p.k; a.n_tables = li.n_tables > 0 ? li.n_tables : 1;
+    a.drop = c->drop;                                       // (the decoders' alone: launch_decoder)
     return PICSONG_OK;
 }
 

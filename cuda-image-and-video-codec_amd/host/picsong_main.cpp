@@ -49,6 +49,7 @@ struct Options {
     std::string metrics;
     int reduce = 0;                             // -reduce r: decode the image at 1/2^r of its size
     int win = 0, wx = 0, wy = 0, ww = 0, wh = 0; // -window x,y,w,h: decode that rectangle of the image at 1/2^r
+    int drop = 0;                               // -drop d: decode at reduced quality (picsong_ctx_set_decode_drop)
     int win_cb = 0;                             // (the codeblocks a window decodes, for --metrics)
     std::string train;                          // -train <outFolder>: count the input's coding decisions, write a LUT folder
     float rate = 0.0f;                          // -rate <bpp>: choose qs so that the output meets that many bits per pixel
@@ -117,6 +118,10 @@ void help()
         "                     goes through groups of -framesPerLaunch frames, as at full size (-window too)\n"
         " -window x,y,w,h     decoding: only the w x h rectangle at (x, y) of the image (at 1/2^r with -reduce r), from the\n"
         "                     codeblocks it depends on (spatial random access)\n"
+        " -drop d             decoding, -cp 2 streams coded at -k 0: the image at its full size from fewer bit-planes, d in 0..15\n"
+        "                     (quality reduction): a codeblock of wavelet level l (0 the finest) leaves its max(0, d - l)\n"
+        "                     lowest bit-planes undecoded, the coder's most expensive ones.  With -reduce, -window, -video,\n"
+        "                     -isRGB, -framesPerLaunch, -layout and -compare (the PSNR of the quick decode)\n"
         " -train <outFolder>  coding (-cd 0, -cp 2, -k 0): code nothing; count the input's coding decisions and write the\n"
         "                     probability tables fitted to them as a LUT folder for this -wl (no -o needed).  -LUTFolder,\n"
         "                     if given, is the prior: its geometry, and its values for entries the input never reaches\n"
@@ -160,6 +165,11 @@ Options parse(const Args &a)
     geti("-gpus", o.gpus); geti("-framesPerLaunch", o.frames_per_launch); gets("--devices", o.devices);
     geti("-reduce", o.reduce);
     if (a.has("-reduce") && o.cd != 1) die("Incorrect parameters. -reduce applies to decoding (-cd 1) only.");
+    if (a.has("-drop")) {
+        if (o.cd != 1) die("Incorrect parameters. -drop applies to decoding (-cd 1) only.");
+        geti("-drop", o.drop);
+        if (o.drop < 0 || o.drop > 15) die("Incorrect parameters. -drop takes a number of bit-planes in 0..15.");
+    }
     if (a.has("-window")) {
         if (o.cd != 1) die("Incorrect parameters. -window applies to decoding (-cd 1) only.");
         const std::string v = a.get("-window");
@@ -1094,12 +1104,14 @@ int run_encode(Options o)
 
 // A decode context from a stream's header.  picsong_ctx_create keeps the coding launcher's -qs range (0, 1]; a stream coded
 // by -rate may carry any gain the header stores (up to 1.6383): such a context is created at 1 and re-tuned.
-void create_decode_ctx(picsong_params p, int device, picsong_ctx **ctx)
+// drop (-drop d): the context's decode setting (picsong_ctx_set_decode_drop).
+void create_decode_ctx(picsong_params p, int device, picsong_ctx **ctx, int drop = 0)
 {
     const float qs = p.qs;
     if (p.lossy && qs > 1.0f) p.qs = 1.0f;
     CK(picsong_ctx_create(&p, device, ctx));
     if (p.lossy && qs > 1.0f) CK(picsong_ctx_set_qs(*ctx, qs));
+    if (drop > 0) CK(picsong_ctx_set_decode_drop(*ctx, drop));
 }
 
 // ---- decoding engine: DecodingEngine::runImage / runVideo call sequence -----------------------
@@ -1297,7 +1309,7 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
     std::vector<Slot> sl((size_t)nslots);
     for (int i = 0; i < nslots; i++) {
         Slot &k = sl[(size_t)i];
-        create_decode_ctx(p, o.device, &k.ctx);
+        create_decode_ctx(p, o.device, &k.ctx, o.drop);
         load_lut(k.ctx, o, p.wl, 1, p.k, p.cp);
         HIPCK(hipStreamCreate(&k.stream));
         HIPCK(hipHostMalloc(&k.h_in, max_shorts * 2 * B));
@@ -1454,6 +1466,9 @@ int run_decode(const Options &o)
     if (o.reduce < 0 || o.reduce > p.wl - 1)
         die("Incorrect parameters. -reduce must lie in 0.." + std::to_string(p.wl - 1) + " (the stream has " +
             std::to_string(p.wl) + " wavelet levels).");
+    if (o.drop > 0 && (p.k > 0.0f || p.cp == 3))
+        die("Incorrect parameters. -drop applies to -cp 2 streams coded at -k 0 (this one: -cp " + std::to_string(p.cp) + ", -k " +
+            std::to_string(p.k) + ").");
     const long nframes = o.video ? p.frames : 1;
     std::vector<long> frame_shorts;
     if (o.video || p.is_rgb) {
@@ -1469,7 +1484,7 @@ int run_decode(const Options &o)
     }
     HIPCK(hipSetDevice(o.device));
     picsong_ctx *ctx = nullptr;
-    create_decode_ctx(p, o.device, &ctx);
+    create_decode_ctx(p, o.device, &ctx, o.drop);
     Options lo = o;
     load_lut(ctx, lo, p.wl, p.components, p.k, p.cp);
     int aw, ah, ncb;

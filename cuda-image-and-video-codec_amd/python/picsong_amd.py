@@ -72,6 +72,7 @@ EXPORTS = [
     "picsong_decode_rgb_frames_reduced", "picsong_decode_rgb_frames_window", "picsong_decode_rgb_images_reduced",
     "picsong_decode_rgb_images_window",
     "picsong_encode_rgb_frames_rate", "picsong_encode_rgb_frames_quality", "picsong_train_rgb_frames",
+    "picsong_ctx_set_decode_drop", "picsong_ctx_get_decode_drop", "picsong_drop_planes",
 ]
 
 _lib = None
@@ -213,6 +214,10 @@ def load():
         L.picsong_encode_rgb_frames_quality.argtypes = [vp, i, vp, vp, vp, C.c_size_t, i, i, u64, i, i, vp, C.c_size_t, vp,
                                                         C.POINTER(i), C.POINTER(i), C.POINTER(u64)]
         L.picsong_train_rgb_frames.argtypes = [vp, i, vp, vp, vp, C.c_size_t, vp]
+    if hasattr(L, "picsong_ctx_set_decode_drop"):
+        L.picsong_ctx_set_decode_drop.argtypes = [vp, i]
+        L.picsong_ctx_get_decode_drop.argtypes = [vp, C.POINTER(i)]
+        L.picsong_drop_planes.argtypes = [i, i, i, i, i, C.POINTER(i)]
     _lib = L
     return L
 
@@ -266,6 +271,14 @@ def rate_qs(j):
     q = C.c_float()
     _check(load().picsong_rate_qs(j, C.byref(q)))
     return q.value
+
+
+def drop_planes(aw, ah, wl, drop, cb):
+    """d(cb) = max(0, drop - level(cb)): the bit-planes raster codeblock `cb` of an aw x ah padded frame of `wl` levels
+    leaves undecoded under Codec.set_decode_drop(drop) (picsong_drop_planes; host only)."""
+    d = C.c_int()
+    _check(load().picsong_drop_planes(aw, ah, wl, drop, cb, C.byref(d)))
+    return d.value
 
 
 def pad_dim(v):
@@ -395,6 +408,17 @@ class Codec:
         table = np.ascontiguousarray(table, np.int32)
         _check(self.L.picsong_ctx_set_lut_component(self.h, component, C.byref(info),
                                                     table.ctypes.data_as(C.c_void_p)))
+
+    def set_decode_drop(self, drop):
+        """Decode at reduced quality from now on: a codeblock of level lv leaves its max(0, drop - lv) lowest bit-planes
+        undecoded, significant coefficients get the midpoint (picsong_ctx_set_decode_drop).  0..15, 0 = the plain
+        decode; k = 0, -cp 2 contexts.  Every decode call of the context follows it; encodes and searches do not."""
+        _check(self.L.picsong_ctx_set_decode_drop(self.h, int(drop)))
+
+    def decode_drop(self):
+        d = C.c_int()
+        _check(self.L.picsong_ctx_get_decode_drop(self.h, C.byref(d)))
+        return d.value
 
     # ---- frames as applications hold them: pitched, unpadded, interleaved RGB(A) (picsong_image) ----
     def image(self, t, layout, pitch=None, plane_stride=0, offset=0):

@@ -315,6 +315,40 @@ int picsong_decode_rgb_frame_window(picsong_ctx *ctx, const uint16_t *d_streams,
                                     int x, int y, int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b,
                                     size_t out_pitch, void *stream);
 
+/* ---- reduced-quality decode (JPEG 2000's quality layers, OpenJPEG -l / Kakadu -layers; the reference has no
+ *      counterpart): the frame at its full size from fewer bit-planes, the third way to decode less than the whole
+ *      frame beside `reduce` and the window, and it composes with both.  A context carries a decode setting `drop`,
+ *      0..15, default 0.  A codeblock's codewords are coded plane after plane from its MSB down, so stopping early reads
+ *      a prefix of them and runs a prefix of the coder's work -- and the lowest planes are the expensive ones.
+ *      Planes dropped: codeblock cb of the padded Mallat array (raster index, 64 x 64) has the level of its top-left
+ *      sample -- 0 the finest detail level, wl the LL band -- and drops d(cb) = max(0, drop - level(cb)) planes: one
+ *      plane more a level finer, about the growth of a coefficient's weight in the image per synthesis level (the same
+ *      count in every subband costs ~5 dB more at the same drop).  One d a codeblock, also where a subband's width is no
+ *      multiple of 64 and the codeblock's columns lie in two subbands.  picsong_drop_planes gives d(cb) on the host, no
+ *      context needed.
+ *      A coded codeblock decodes its planes MSB .. d exactly as ever; planes d - 1 .. 0 are neither read nor decoded.
+ *      Every coefficient that became significant in the decoded planes gets its sign and the magnitude
+ *      (m >> d << d) | (1 << (d - 1)), its decoded bits and the midpoint of the interval they leave (JPEG 2000's
+ *      r = 1/2) for d >= 1; every other coefficient is 0.  MSB < d: the codeblock is all zero.  Raw codeblocks (the
+ *      expansion fallback, length 4096) hold words, not planes: copied whole.  All-zero codeblocks as ever.  An MSB > 15
+ *      still raises the range flag.  The midpoint sets no bit above a coefficient's own MSB: the int16 coefficient form
+ *      stays within its bound.
+ *      Everything after the coder is unchanged -- the de-quantisation and the synthesis run on these coefficients -- so a
+ *      reduced or window call under `drop` returns the LL_reduce, or the rectangle, that the full-size call under the
+ *      same `drop` computes on its way.
+ *      The setting applies to every decoder launch of the context from then on: picsong_bpc_decode(_component),
+ *      picsong_decode_plane and every frame decode call (single, n frames, _reduced, _window, grey, RGB -- the same drop
+ *      for the three components -- and the picsong_image forms).  Encoding, training and the rate / quality searches
+ *      ignore it: a quality search measures the full decode.  drop = 0 is the plain decode in every respect, the kernels
+ *      launched included; the setting is plain state, 0 after any value restores the plain decode.
+ *      Refused (PICSONG_ERR_ARG, the setting kept): drop outside 0..15; a -k > 0 context (its planes below cbp are the
+ *      bulk scan's) and a -cp 3 context (a plane in three passes): both code the low planes differently.
+ *      picsong_drop_planes refuses aw / ah that are no positive multiples of 64, wl outside 1..7, drop outside 0..15 and
+ *      cb outside the raster. ---- */
+int picsong_ctx_set_decode_drop(picsong_ctx *ctx, int drop);
+int picsong_ctx_get_decode_drop(const picsong_ctx *ctx, int *drop);
+int picsong_drop_planes(int aw, int ah, int wl, int drop, int cb, int *planes);
+
 /* ---- training: probability tables from a corpus (the reference ships four trained folders and no way to make one).
  *      The coder adapts nothing at run time: every binary decision is coded with the stationary probability of a table
  *      entry.  These calls count, for the two-pass coder at k = 0 (-cp 2, file _0 of ref / sig / sign), every decision
