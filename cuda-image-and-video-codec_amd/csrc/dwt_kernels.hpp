@@ -94,6 +94,9 @@ struct DwtFwdArgs {
     // same stride); plane blockIdx.z of the launch is COMPONENT z % 3, which the RCT delivers from the three planes of
     // frame z / 3, src_z bytes after frame 0's (level 0's src_z: every component of a frame reads all three)
     const void *src_g, *src_b;
+    // deep contexts (9- to 16-bit samples; the U16IN instantiations of dwt_fwd_kernel alone read it): level 0's `src` holds
+    // native uint16 samples, `off` = 2^(bit depth - 1) is the level shift its load stage subtracts.  0 everywhere else.
+    int off;
 };
 
 // two integer coefficients as one dword of int16 (v_cvt_pk_i16_i32: saturating, which coef16_ok's bound never needs)
@@ -146,6 +149,11 @@ struct DwtInvArgs {
     // what the decoder's C16 instantiation writes where every magnitude stays below 2^15 (coef16_ok); the C16
     // instantiations of the synthesis kernels read them.  The LL a level hands the next stays T in the scratch.
     int c16;
+    // deep contexts (the U16OUT instantiations of dwt_inv_kernel alone read them): the finest level stores its samples as
+    // native uint16 at dst_u16 (row stride W, frame z at + z * u8_z bytes), `off` added back and clamped to [0, px_max],
+    // px_max = 2^(bit depth) - 1.  nullptr / 0 everywhere else.
+    uint16_t *dst_u16;
+    int px_max;
 };
 
 // frame blockIdx.z of a batched launch
@@ -443,17 +451,30 @@ __device__ __forceinline__ void hinv(float v[4], bool le, bool re)
 
 // ---- forward --------------------------------------------------------------------------------
 // A row segment as it comes from memory (conversion deferred so that many loads can be in flight):
-// u8 input: one dword = 4 samples; T input: four dwords.
-template <bool U8IN> struct RawRow;
-template <> struct RawRow<true> { uint32_t w; };
-template <> struct RawRow<false> { uint32_t w[4]; };
+// u8 input: one dword = 4 samples; T input: four dwords; uint16 input (deep contexts): two dwords.
+// IN: the kind of the level's input -- kInT, kInU8 (= false / true of the kernels' U8IN) or kInU16
+constexpr int kInT = 0, kInU8 = 1, kInU16 = 2;
+template <int IN> struct RawRow;
+template <> struct RawRow<kInU8> { uint32_t w; };
+template <> struct RawRow<kInT> { uint32_t w[4]; };
+template <> struct RawRow<kInU16> { uint32_t w[2]; };
 
-template <typename T, bool U8IN, bool VEC>
-__device__ __forceinline__ RawRow<U8IN> load_raw(const DwtFwdArgs &a, int y, int c0)
+template <typename T, int IN, bool VEC>
+__device__ __forceinline__ RawRow<IN> load_raw(const DwtFwdArgs &a, int y, int c0)
 {
-    RawRow<U8IN> r;
+    RawRow<IN> r;
     const int ry = reflect(y, a.H);
-    if constexpr (U8IN) {
+    if constexpr (IN == kInU16) {
+        const uint16_t *p = (const uint16_t *)a.src + (size_t)ry * (size_t)a.src_stride;
+        if constexpr (VEC) {
+            // the lane's four samples: one 8-byte load (rows 8-byte aligned: 16-byte aligned frames, AW a multiple of 4)
+            const uint2 q = *reinterpret_cast<const uint2 *>(p + (uint32_t)c0);
+            r.w[0] = q.x; r.w[1] = q.y;
+        } else {
+            r.w[0] = (uint32_t)p[reflect(c0, a.W)] | ((uint32_t)p[reflect(c0 + 1, a.W)] << 16);
+            r.w[1] = (uint32_t)p[reflect(c0 + 2, a.W)] | ((uint32_t)p[reflect(c0 + 3, a.W)] << 16);
+        }
+    } else if constexpr (IN == kInU8) {
         const uint8_t *p = (const uint8_t *)a.src + (size_t)ry * (size_t)a.src_stride;
         if constexpr (VEC) {
             // uniform row base + unsigned 32-bit lane offset: the saddr addressing form, no 64-bit VALU
@@ -503,14 +524,20 @@ __device__ __forceinline__ float byte_to_float(uint32_t w)
     return (float)(int)((w >> (8 * N)) & 0xFFu);
 #endif
 }
-template <typename T, bool U8IN>
-__device__ __forceinline__ void unpack_row(const RawRow<U8IN> &r, T v[4])
+// off: the level shift of the uint16 stage (DwtFwdArgs::off); the u8 stage keeps its literal 128
+template <typename T, int IN>
+__device__ __forceinline__ void unpack_row(const RawRow<IN> &r, T v[4], int off = 0)
 {
-    if constexpr (U8IN && std::is_same<T, float>::value) {
+    if constexpr (IN == kInU16) {
+        // offsetImage with the depth as a parameter: the samples are UNSIGNED 16-bit words (65535 is never -1), and
+        // (T)v - (T)off is exact in both types (v < 2^16, off <= 2^15)
+        v[0] = (T)(int)(r.w[0] & 0xFFFFu) - (T)off; v[1] = (T)(int)(r.w[0] >> 16) - (T)off;
+        v[2] = (T)(int)(r.w[1] & 0xFFFFu) - (T)off; v[3] = (T)(int)(r.w[1] >> 16) - (T)off;
+    } else if constexpr (IN == kInU8 && std::is_same<T, float>::value) {
         // offsetImage Engines/CodingEngine.cu:581-588 fused: (T)u8 - 128
         v[0] = byte_to_float<0>(r.w) - 128.0f; v[1] = byte_to_float<1>(r.w) - 128.0f;
         v[2] = byte_to_float<2>(r.w) - 128.0f; v[3] = byte_to_float<3>(r.w) - 128.0f;
-    } else if constexpr (U8IN) {
+    } else if constexpr (IN == kInU8) {
         v[0] = (T)(int)(r.w & 0xFFu) - (T)128; v[1] = (T)(int)((r.w >> 8) & 0xFFu) - (T)128;
         v[2] = (T)(int)((r.w >> 16) & 0xFFu) - (T)128; v[3] = (T)(int)(r.w >> 24) - (T)128;
     } else {
@@ -582,9 +609,13 @@ __device__ __forceinline__ void emit_pair(const DwtFwdArgs &a, int m, int pc, bo
 #else
 #define PS_DWT_OCC
 #endif
-template <typename T, bool LOSSY, bool U8IN, int BAND, bool VEC>
+// U16IN (deep contexts, level 0): the input is native uint16 samples, the level shift DwtFwdArgs::off subtracted in the load
+// stage as the U8IN stage subtracts its 128
+template <typename T, bool LOSSY, bool U8IN, int BAND, bool VEC, bool U16IN = false>
 __global__ __launch_bounds__(256) PS_DWT_OCC void dwt_fwd_kernel(DwtFwdArgs a)
 {
+    static_assert(!(U8IN && U16IN), "one kind of sample input");
+    constexpr int IN = U16IN ? kInU16 : (U8IN ? kInU8 : kInT);
     constexpr int kFwdBandRows = BAND;
 #ifdef PICSONG_DWT_CHUNKED
     constexpr int kFwdChunk = BAND / 2 < 4 ? BAND / 2 : 4;
@@ -623,17 +654,17 @@ __global__ __launch_bounds__(256) PS_DWT_OCC void dwt_fwd_kernel(DwtFwdArgs a)
         // s[m] = x[2m] + ((d[m-1]+d[m]+2)>>2)
         constexpr int NCH = (kFwdBandRows / 2 + kFwdChunk - 1) / kFwdChunk;
         T xe[4], xo[4], xn[4], dp[4];
-        RawRow<U8IN> raw[2][2 * kFwdChunk];
+        RawRow<IN> raw[2][2 * kFwdChunk];
         __builtin_amdgcn_s_setprio(3);          // see above: loads go first
-        const RawRow<U8IN> r0 = load_raw<T, U8IN, VEC>(a, 2 * m0 - 2, cl);
-        const RawRow<U8IN> r1 = load_raw<T, U8IN, VEC>(a, 2 * m0 - 1, cl);
-        const RawRow<U8IN> r2 = load_raw<T, U8IN, VEC>(a, 2 * m0, cl);
+        const RawRow<IN> r0 = load_raw<T, IN, VEC>(a, 2 * m0 - 2, cl);
+        const RawRow<IN> r1 = load_raw<T, IN, VEC>(a, 2 * m0 - 1, cl);
+        const RawRow<IN> r2 = load_raw<T, IN, VEC>(a, 2 * m0, cl);
 #pragma unroll
-        for (int r = 0; r < 2 * kFwdChunk; r++) raw[0][r] = load_raw<T, U8IN, VEC>(a, 2 * m0 + 1 + r, cl);
+        for (int r = 0; r < 2 * kFwdChunk; r++) raw[0][r] = load_raw<T, IN, VEC>(a, 2 * m0 + 1 + r, cl);
         __builtin_amdgcn_s_setprio(0);
-        unpack_row<T, U8IN>(r0, xe);
-        unpack_row<T, U8IN>(r1, xo);
-        unpack_row<T, U8IN>(r2, xn);
+        unpack_row<T, IN>(r0, xe, a.off);
+        unpack_row<T, IN>(r1, xo, a.off);
+        unpack_row<T, IN>(r2, xn, a.off);
 #pragma unroll
         for (int k = 0; k < 4; k++) { dp[k] = xo[k] - ((xe[k] + xn[k]) >> 1); xe[k] = xn[k]; }
 #pragma unroll
@@ -642,13 +673,13 @@ __global__ __launch_bounds__(256) PS_DWT_OCC void dwt_fwd_kernel(DwtFwdArgs a)
             if (c + 1 < NCH) {
 #pragma unroll
                 for (int r = 0; r < 2 * kFwdChunk; r++)
-                    raw[(c + 1) & 1][r] = load_raw<T, U8IN, VEC>(a, 2 * (mc + kFwdChunk) + 1 + r, cl);
+                    raw[(c + 1) & 1][r] = load_raw<T, IN, VEC>(a, 2 * (mc + kFwdChunk) + 1 + r, cl);
             }
 #pragma unroll
             for (int q = 0; q < kFwdChunk; q++) {
                 const int m = mc + q;
-                unpack_row<T, U8IN>(raw[c & 1][2 * q], xo);
-                unpack_row<T, U8IN>(raw[c & 1][2 * q + 1], xn);
+                unpack_row<T, IN>(raw[c & 1][2 * q], xo, a.off);
+                unpack_row<T, IN>(raw[c & 1][2 * q + 1], xn, a.off);
                 T Lr[4], Hr[4];
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
@@ -666,26 +697,26 @@ __global__ __launch_bounds__(256) PS_DWT_OCC void dwt_fwd_kernel(DwtFwdArgs a)
         T xe[4], xo[4], xn[4], d1p[4], s1p[4], d2p[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) { d1p[k] = s1p[k] = d2p[k] = (T)0; }
-        RawRow<U8IN> raw[2][2 * kFwdChunk];
+        RawRow<IN> raw[2][2 * kFwdChunk];
         __builtin_amdgcn_s_setprio(3);
-        const RawRow<U8IN> r0 = load_raw<T, U8IN, VEC>(a, 2 * m0 - 4, cl);
+        const RawRow<IN> r0 = load_raw<T, IN, VEC>(a, 2 * m0 - 4, cl);
 #pragma unroll
-        for (int r = 0; r < 2 * kFwdChunk; r++) raw[0][r] = load_raw<T, U8IN, VEC>(a, 2 * (m0 - 2) + 1 + r, cl);
+        for (int r = 0; r < 2 * kFwdChunk; r++) raw[0][r] = load_raw<T, IN, VEC>(a, 2 * (m0 - 2) + 1 + r, cl);
         __builtin_amdgcn_s_setprio(0);
-        unpack_row<T, U8IN>(r0, xe);
+        unpack_row<T, IN>(r0, xe, a.off);
 #pragma unroll
         for (int c = 0; c < NCH; c++) {
             const int jc = m0 - 2 + c * kFwdChunk;
             if (c + 1 < NCH) {
 #pragma unroll
                 for (int r = 0; r < 2 * kFwdChunk; r++)
-                    raw[(c + 1) & 1][r] = load_raw<T, U8IN, VEC>(a, 2 * (jc + kFwdChunk) + 1 + r, cl);
+                    raw[(c + 1) & 1][r] = load_raw<T, IN, VEC>(a, 2 * (jc + kFwdChunk) + 1 + r, cl);
             }
 #pragma unroll
             for (int q = 0; q < kFwdChunk; q++) {
                 const int j = jc + q;
-                unpack_row<T, U8IN>(raw[c & 1][2 * q], xo);
-                unpack_row<T, U8IN>(raw[c & 1][2 * q + 1], xn);
+                unpack_row<T, IN>(raw[c & 1][2 * q], xo, a.off);
+                unpack_row<T, IN>(raw[c & 1][2 * q + 1], xn, a.off);
                 T Lr[4], Hr[4];
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
@@ -1245,14 +1276,42 @@ __device__ __forceinline__ void store_row4_u8(const DwtInvArgs &a, int y, int c0
     *reinterpret_cast<uint32_t *>(a.dst_u8 + (size_t)y * (size_t)a.W + (uint32_t)c0) = w;
 }
 
-template <typename T, bool LOSSY, int BAND, bool VEC, bool U8OUT = false, bool FAST = false, bool C16 = false>
+// Deep contexts: the same arithmetic with 255 replaced by px_max = 2^(bit depth) - 1 (the reference hard-codes 255), a
+// sample a 16-bit word.  The float form clamps with max / min, so a NaN leaves as 0 as the u8 conversion makes it.
+// Same arithmetic as clamp_to_u16_i32_kernel / clamp_to_u16_f32_kernel.
+__device__ __forceinline__ uint32_t to_sample16(int v, int off, int mx)
+{
+    const int t = v + off;
+    return (uint32_t)(t > mx ? mx : (t < 0 ? 0 : t));
+}
+__device__ __forceinline__ uint32_t to_sample16(float v, int off, int mx)
+{
+    float t = v + (float)off;
+    t = t + 0.01f;
+    const float r = fminf(fmaxf(rintf(t), 0.0f), (float)mx);
+    return (uint32_t)(int)r;
+}
+// four samples of a lane: one 8-byte store
+template <typename T>
+__device__ __forceinline__ void store_row4_u16(const DwtInvArgs &a, int y, int c0, const T v[4])
+{
+    uint2 w;
+    w.x = to_sample16(v[0], a.off, a.px_max) | (to_sample16(v[1], a.off, a.px_max) << 16);
+    w.y = to_sample16(v[2], a.off, a.px_max) | (to_sample16(v[3], a.off, a.px_max) << 16);
+    *reinterpret_cast<uint2 *>(a.dst_u16 + (size_t)y * (size_t)a.W + (uint32_t)c0) = w;
+}
+
+// U16OUT (deep contexts, the finest level of the frame path; vector form only, as U8OUT): uint16 samples to dst_u16
+template <typename T, bool LOSSY, int BAND, bool VEC, bool U8OUT = false, bool FAST = false, bool C16 = false, bool U16OUT = false>
 __global__ __launch_bounds__(256) void dwt_inv_kernel(DwtInvArgs a)
 {
+    static_assert(!U16OUT || (VEC && !U8OUT && !C16), "the uint16 store exists in the 32-bit vector kernels");
     constexpr int kInvBandRows = BAND;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int strip = blockIdx.x * 4 + wave;
     if (strip * kStripUseful >= a.W) return;
     dwt_inv_select_frame(a);
+    if constexpr (U16OUT) a.dst_u16 = (uint16_t *)((char *)a.dst_u16 + (unsigned long long)blockIdx.z * a.u8_z);
     const int c0 = strip * kStripUseful - 4 * kEdgeLanes + 4 * lane;
     const int pc = c0 >> 1;                                  // arithmetic shift: -4 -> -2
     const int hW = a.W >> 1, hH = a.H >> 1;
@@ -1312,7 +1371,10 @@ __global__ __launch_bounds__(256) void dwt_inv_kernel(DwtInvArgs a)
                 sp[k] = s; Hp[k] = Hr[k];
             }
             if (it >= 2 && j - 1 < m1 && wr) {
-                if constexpr (U8OUT) {
+                if constexpr (U16OUT) {
+                    store_row4_u16<T>(a, 2 * (j - 1), c0, ev);
+                    store_row4_u16<T>(a, 2 * (j - 1) + 1, c0, od);
+                } else if constexpr (U8OUT) {
                     store_row4_u8<T>(a, 2 * (j - 1), c0, ev);
                     store_row4_u8<T>(a, 2 * (j - 1) + 1, c0, od);
                 } else {
@@ -1359,7 +1421,10 @@ __global__ __launch_bounds__(256) void dwt_inv_kernel(DwtInvArgs a)
                 ddp[k] = (T)dd; s1p[k] = (T)s1; d1p[k] = (T)d1; s0p[k] = (T)s0;
             }
             if (it >= 4 && j - 2 < m1 && wr) {
-                if constexpr (U8OUT) {
+                if constexpr (U16OUT) {
+                    store_row4_u16<T>(a, 2 * (j - 2), c0, ev);
+                    store_row4_u16<T>(a, 2 * (j - 2) + 1, c0, od);
+                } else if constexpr (U8OUT) {
                     store_row4_u8<T>(a, 2 * (j - 2), c0, ev);
                     store_row4_u8<T>(a, 2 * (j - 2) + 1, c0, od);
                 } else {
@@ -2162,6 +2227,65 @@ __global__ __launch_bounds__(256) void clamp_to_u8_f32_kernel(const float *in, u
         reinterpret_cast<uint32_t *>(out)[i] = o;
     }
 }
+// ---- deep contexts (9- to 16-bit samples as native uint16): the element-wise forms of the two ends, for the stage calls
+// (picsong_level_shift_fwd16, picsong_level_shift_inv), pointers that the vector kernels cannot take, and
+// PICSONG_DEEP_NOFUSE=1.  Four samples a lane; `wide`: the uint16 side is 8-byte aligned (one 8-byte access), else four
+// 2-byte ones -- the same values.  The T side is a work buffer of the library's, always 16-byte aligned.
+template <typename T>
+__global__ __launch_bounds__(256) void level_shift_fwd_u16_kernel(const uint16_t *in, T *out, size_t n4, int off, int wide)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        uint32_t w0, w1;
+        if (wide) {
+            const uint2 q = reinterpret_cast<const uint2 *>(in)[i];
+            w0 = q.x; w1 = q.y;
+        } else {
+            w0 = (uint32_t)in[4 * i] | ((uint32_t)in[4 * i + 1] << 16);
+            w1 = (uint32_t)in[4 * i + 2] | ((uint32_t)in[4 * i + 3] << 16);
+        }
+        const T v[4] = { (T)(int)(w0 & 0xFFFFu) - (T)off, (T)(int)(w0 >> 16) - (T)off,
+                         (T)(int)(w1 & 0xFFFFu) - (T)off, (T)(int)(w1 >> 16) - (T)off };
+        uint4 o;
+        o.x = as_u32(v[0]); o.y = as_u32(v[1]); o.z = as_u32(v[2]); o.w = as_u32(v[3]);
+        reinterpret_cast<uint4 *>(out)[i] = o;
+    }
+}
+template <typename T>
+__device__ __forceinline__ void clamp_to_u16_body(const T *in, uint16_t *out, size_t n4, int off, int mx, int wide)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        const uint4 w = reinterpret_cast<const uint4 *>(in)[i];
+        const uint32_t s0 = to_sample16(from_u32<T>(w.x), off, mx), s1 = to_sample16(from_u32<T>(w.y), off, mx),
+                       s2 = to_sample16(from_u32<T>(w.z), off, mx), s3 = to_sample16(from_u32<T>(w.w), off, mx);
+        if (wide) {
+            uint2 o;
+            o.x = s0 | (s1 << 16); o.y = s2 | (s3 << 16);
+            reinterpret_cast<uint2 *>(out)[i] = o;
+        } else {
+            out[4 * i] = (uint16_t)s0; out[4 * i + 1] = (uint16_t)s1; out[4 * i + 2] = (uint16_t)s2; out[4 * i + 3] = (uint16_t)s3;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void clamp_to_u16_i32_kernel(const int32_t *in, uint16_t *out, size_t n4, int off, int mx, int wide)
+{
+    clamp_to_u16_body<int>(in, out, n4, off, mx, wide);
+}
+__global__ __launch_bounds__(256) void clamp_to_u16_f32_kernel(const float *in, uint16_t *out, size_t n4, int off, int mx, int wide)
+{
+    clamp_to_u16_body<float>(in, out, n4, off, mx, wide);
+}
+// picsong_level_shift_inv on a deep context: level_shift_inv_*_kernel's arithmetic with px_max in place of 255, in place
+__global__ __launch_bounds__(256) void level_shift_inv16_i32_kernel(int32_t *d, size_t n, int off, int mx)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        d[i] = (int32_t)to_sample16(d[i], off, mx);
+}
+__global__ __launch_bounds__(256) void level_shift_inv16_f32_kernel(float *d, size_t n, int off, int mx)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        d[i] = (float)to_sample16(d[i], off, mx);
+}
+
 // ---- colour transforms of the RGB path (RGBTransformLossless / RGBTransformLossy, reference
 // Engines/CodingEngine.cu:357-403 and Engines/DecodingEngine.cu:599-650), level shift fused, four
 // samples per lane.  RCT: c0 = floor((R+2G+B)/4), c1 = B-G, c2 = R-G.  ICT: 3x3 matrix, evaluated

@@ -41,8 +41,24 @@ inline FwdKernel fwd_kernel_of(bool lossy, bool u8)
     if (lossy) return u8 ? dwt_fwd_kernel<float, true, true, BAND, VEC> : dwt_fwd_kernel<float, true, false, BAND, VEC>;
     return u8 ? dwt_fwd_kernel<int, false, true, BAND, VEC> : dwt_fwd_kernel<int, false, false, BAND, VEC>;
 }
+// a deep context's level 0 (FwdLaunch::u16): the uint16 load stage
+template <int BAND, bool VEC>
+inline FwdKernel fwd16_kernel_of(bool lossy)
+{
+    return lossy ? dwt_fwd_kernel<float, true, false, BAND, VEC, true> : dwt_fwd_kernel<int, false, false, BAND, VEC, true>;
+}
+inline FwdKernel select_fwd16(bool lossy, const FwdLaunch &f)
+{
+    switch (f.band) {
+    case 32: return f.vec ? fwd16_kernel_of<32, true>(lossy) : fwd16_kernel_of<32, false>(lossy);
+    case 16: return f.vec ? fwd16_kernel_of<16, true>(lossy) : fwd16_kernel_of<16, false>(lossy);
+    case 8: return f.vec ? fwd16_kernel_of<8, true>(lossy) : fwd16_kernel_of<8, false>(lossy);
+    default: return f.vec ? fwd16_kernel_of<4, true>(lossy) : fwd16_kernel_of<4, false>(lossy);
+    }
+}
 inline FwdKernel select_fwd(bool lossy, const FwdLaunch &f)
 {
+    if (f.u16) return select_fwd16(lossy, f);
     switch (f.band) {
     case 32: return f.vec ? fwd_kernel_of<32, true>(lossy, f.u8) : fwd_kernel_of<32, false>(lossy, f.u8);
     case 16: return f.vec ? fwd_kernel_of<16, true>(lossy, f.u8) : fwd_kernel_of<16, false>(lossy, f.u8);
@@ -81,9 +97,19 @@ inline InvKernel inv_kernel_of(bool lossy, bool fast)
     if (lossy) return dwt_inv_kernel<float, true, BAND, VEC, U8OUT>;
     return dwt_inv_kernel<int, false, BAND, VEC, U8OUT>;
 }
+// a deep context's finest level (DwtInvArgs::dst_u16; a vector launch with 32-bit coefficients, plan_inverse_frames): the
+// uint16 store -- 5/3, 9/7 dividing and 9/7 FAST; never the lean kernel, which has no such form
+template <int BAND>
+inline InvKernel inv16_kernel_of(bool lossy, bool fast)
+{
+    if (lossy && fast) return dwt_inv_kernel<float, true, BAND, true, false, true, false, true>;
+    if (lossy) return dwt_inv_kernel<float, true, BAND, true, false, false, false, true>;
+    return dwt_inv_kernel<int, false, BAND, true, false, false, false, true>;
+}
 template <int BAND>
 inline InvKernel inv_level_of(bool lossy, bool lean97, const InvLaunch &f)
 {
+    if (f.a.dst_u16) return inv16_kernel_of<BAND>(lossy, f.fast);
     if (f.a.c16) {
         // the decode frame paths' 16-bit coefficients (dec_c16_ok: vector kernels, 9/7 through the lean kernel, the
         // coarsest level never the one that writes pixels)
@@ -342,16 +368,18 @@ inline RgbSseLaunch select_rgb_sse(const RgbSseArgs &s, bool fused = true)
 }
 
 // ---- pixel layouts (ingest_kernel / emit_kernel, layout_kernels.hpp).  bytes a pixel, planes of the padded side
-inline int layout_bpp(int layout) { return layout < kLayoutRgb24 ? 1 : (layout < kLayoutRgba32 ? 3 : 4); }
-inline int layout_planes(int layout) { return layout == kLayoutGrey8 ? 1 : 3; }
+inline int layout_bpp(int layout) { return layout == kLayoutGrey16 ? 2 : (layout < kLayoutRgb24 ? 1 : (layout < kLayoutRgba32 ? 3 : 4)); }
+inline int layout_planes(int layout) { return layout == kLayoutGrey8 || layout == kLayoutGrey16 ? 1 : 3; }
 // What picsong_ingest_frames / picsong_emit_frames (and the whole-frame calls over them) refuse, as a message; nullptr:
 // the arguments are fine.  `data`, pitch, plane_stride: the picsong_image's; n frames frame_stride bytes apart; the
 // padded side at `padded`, frames padded_stride apart.
+// deep (a context of 9- to 16-bit samples): GREY16 and nothing else; false: the six 8-bit layouts, as ever
 inline const char *layout_refusal(int layout, const void *data, size_t pitch, size_t plane_stride, size_t frame_stride,
-                                  const void *padded, size_t padded_stride, int n, int W, int H, int AW, int AH)
+                                  const void *padded, size_t padded_stride, int n, int W, int H, int AW, int AH, bool deep = false)
 {
     if (!data || !padded) return "null pointer";
-    if (layout < 0 || layout >= kLayoutCount) return "unknown layout";
+    if (deep && layout != kLayoutGrey16) return "the layout of a deep context (bit_depth 9..16) is GREY16";
+    if (!deep && (layout < 0 || layout >= kLayoutCount)) return "unknown layout";
     if (n < 1 || n > kLayoutMaxFrames) return "n outside 1..64";
     if (W < 1 || H < 1 || AW < W || AH < H) return "bad geometry";
     if (AW - W > W || AH - H > H) return "the mirror padding adds more columns / rows than the frame has";
@@ -363,6 +391,13 @@ inline const char *layout_refusal(int layout, const void *data, size_t pitch, si
         span += 2 * plane_stride;
     }
     if (n > 1 && frame_stride < span) return "frame_stride smaller than a frame";
+    if (layout == kLayoutGrey16) {
+        // (the padded side: uint16 planes, its stride in bytes)
+        if ((((uintptr_t)data) | pitch | (uintptr_t)padded) & 1u) return "16-bit samples need 2-byte aligned pointers and pitch";
+        if (n > 1 && ((frame_stride | padded_stride) & 1u)) return "16-bit samples need even strides";
+        if (n > 1 && padded_stride < 2 * (size_t)AW * (size_t)AH) return "padded_stride smaller than a frame's padded planes";
+        return nullptr;
+    }
     if (n > 1 && padded_stride < (size_t)layout_planes(layout) * (size_t)AW * (size_t)AH) return "padded_stride smaller than a frame's padded planes";
     return nullptr;
 }
@@ -419,6 +454,16 @@ inline LayoutArgs layout_args(int layout, const void *data, size_t pitch, size_t
     a.a16 = ((((uintptr_t)a.img) | a.pitch | a.plane_stride | a.frame_stride) & 15u) == 0 ? 1 : 0;
     return a;
 }
+// GREY16 (ingest16_kernel / emit16_kernel): a thread a group of 8 samples, 256 groups a workgroup over the padded
+// (ingest) or the visible (emit) rows; the vector form where the padded side is 16-byte and the image side 4-byte aligned
+inline LayoutLaunch select_layout16(bool ingest, const LayoutArgs &a)
+{
+    const bool vec = ((((uintptr_t)a.img) | a.pitch | a.frame_stride) & 3u) == 0 && ((((uintptr_t)a.pad) | a.pad_stride) & 15u) == 0;
+    const size_t groups = ingest ? (size_t)(a.AW / 8) * (size_t)a.AH : (size_t)((a.W + 7) / 8) * (size_t)a.H;
+    const dim3 grid((unsigned)((groups + 255) / 256), 1u, 1u);
+    if (ingest) return { vec ? ingest16_kernel<true> : ingest16_kernel<false>, grid, vec };
+    return { vec ? emit16_kernel<true> : emit16_kernel<false>, grid, vec };
+}
 template <template <int, bool> class K>
 inline LayoutLaunch select_layout(int layout, const LayoutArgs &a)
 {
@@ -441,8 +486,8 @@ inline LayoutLaunch select_layout(int layout, const LayoutArgs &a)
 template <int L, bool VEC> struct IngestOf { static LayoutKernel fn() { return ingest_kernel<L, VEC>; } };
 template <int L, bool VEC> struct EmitOf { static LayoutKernel fn() { return emit_kernel<L, VEC>; } };
 static_assert(LayoutTraits<kLayoutGrey8>::max_rows == 64 && LayoutTraits<kLayoutRgb24>::max_rows == 21, "select_layout's rows are the kernels'");
-inline LayoutLaunch select_ingest(int layout, const LayoutArgs &a) { return select_layout<IngestOf>(layout, a); }
-inline LayoutLaunch select_emit(int layout, const LayoutArgs &a) { return select_layout<EmitOf>(layout, a); }
+inline LayoutLaunch select_ingest(int layout, const LayoutArgs &a) { return layout == kLayoutGrey16 ? select_layout16(true, a) : select_layout<IngestOf>(layout, a); }
+inline LayoutLaunch select_emit(int layout, const LayoutArgs &a) { return layout == kLayoutGrey16 ? select_layout16(false, a) : select_layout<EmitOf>(layout, a); }
 
 // ---- the n-frame RGB proxy calls (picsong_decode_rgb_frames_reduced / _window, picsong_decode_rgb_images_reduced /
 // _window): what they refuse, as a message; nullptr: the arguments are fine.  The context's side as rgb_frames_refusal

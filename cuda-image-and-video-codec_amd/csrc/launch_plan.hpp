@@ -27,7 +27,8 @@ static const float kQSteps[10][4] = {
     { 1086.1624f, 550.43286f, 550.43286f, 278.94202f }
 };
 
-struct FwdLaunch { DwtFwdArgs a; unsigned gx, gy; bool u8; int band; bool vec; };
+// u16 (deep contexts, level 0 only): the input is uint16 samples (select_fwd: the U16IN instantiations); false: as ever
+struct FwdLaunch { DwtFwdArgs a; unsigned gx, gy; bool u8; int band; bool vec; bool u16; };
 struct InvLaunch { DwtInvArgs a; unsigned gx, gy; int band; bool vec; bool fast; };
 
 // The vector-only kernel instantiations need whole 4-column groups and 16-byte aligned rows
@@ -106,9 +107,9 @@ inline int bulk_max_span_bytes(int aw, int ah, int wl, int nBp, int nSub, int cR
 // transforms to the identity; the 5/3 floors move a sample by less than one per lifting step).  `in_max`: largest
 // sample magnitude after the level shift / colour transform (128 for a grey 8-bit frame, 255 for RCT chroma).
 // 2^15 with a margin for rounding; PICSONG_C16=0 keeps the 32-bit arrays (the tests cross-check both).
-inline bool coef16_ok(bool lossy, int wl, float qs, int in_max)
+// coef16_bound: the bound alone, whatever the environment says (picsong_depth_range_guaranteed)
+inline bool coef16_bound(bool lossy, int wl, float qs, int in_max)
 {
-    if (const char *e = getenv("PICSONG_C16")) if (atoi(e) == 0) return false;
     if (wl < 1 || wl > 10) return false;
     if (!lossy) return (double)in_max * 2.8601 * 2.8601 + 64.0 < 30000.0;
     if (!(qs > 0.0f)) return false;
@@ -120,6 +121,11 @@ inline bool coef16_ok(bool lossy, int wl, float qs, int in_max)
             worst = b > worst ? b : worst;
         }
     return worst < 30000.0;
+}
+inline bool coef16_ok(bool lossy, int wl, float qs, int in_max)
+{
+    if (const char *e = getenv("PICSONG_C16")) if (atoi(e) == 0) return false;
+    return coef16_bound(lossy, wl, qs, in_max);
 }
 
 inline std::vector<FwdLaunch> plan_dwt_forward(const void *d_in, bool u8in, void *d_out, int aw, int ah,
@@ -140,13 +146,14 @@ inline std::vector<FwdLaunch> plan_dwt_forward(const void *d_in, bool u8in, void
         a.ll_stride = last ? aw : (W >> 1);
         a.mallat = d_out; a.AW = aw; a.level = l; a.last = last ? 1 : 0; a.qs = qs;
         a.src_z = 0; a.dst_z = 0; a.pair_base = 0; a.pair_end = 0; a.c16 = c16 ? 1 : 0;
-        a.src_g = a.src_b = nullptr;
+        a.src_g = a.src_b = nullptr; a.off = 0;
         for (int k = 0; k < 4; k++) a.q[k] = kQSteps[l][k];
         const int strips = (W + kStripUseful - 1) / kStripUseful;
         f.band = fwd_band_rows(l, strips, H);
         f.gx = (unsigned)((strips + 3) / 4);
         f.gy = (unsigned)(((H >> 1) + f.band / 2 - 1) / (f.band / 2));
         f.u8 = u8in && l == 0;
+        f.u16 = false;
         // rows of every buffer this level touches start 16-byte aligned when W % 4 == 0: strides are
         // aw, W or W/2 (even), scratch offsets are sums of W*H (multiples of 16 elements)
         f.vec = dwt_vec_ok(W, aw, d_in, d_out) && (W >> 1) % 2 == 0;
@@ -162,6 +169,29 @@ inline std::vector<FwdLaunch> plan_dwt_forward(const void *d_in, bool u8in, void
     return v;
 }
 inline bool plan_is_c16(const std::vector<FwdLaunch> &plan) { return !plan.empty() && plan[0].a.c16 != 0; }
+
+// ---- deep contexts (bit_depth 9..16, grey, the 32-bit coefficient form): the two ends of the transform on uint16 samples.
+// PICSONG_DEEP_NOFUSE=1 (read per call): the element-wise level shift / clamp passes beside the T-input level 0 and the
+// T-output finest level, instead of the uint16 load and store stages of the kernels.  The bytes are the same.
+inline bool deep_nofuse()
+{
+    const char *e = getenv("PICSONG_DEEP_NOFUSE");
+    return e && atoi(e) != 0;
+}
+inline bool deep_depth_ok(int bit_depth) { return bit_depth >= 9 && bit_depth <= 16; }
+// The forward plan of n frames of uint16 samples at d_in, frame_stride bytes apart: level 0 reads the samples itself
+// (FwdLaunch::u16), level shift `off` = 2^(bit depth - 1) -- its vector form where the plan's level 0 has it and the frames
+// start 16-byte aligned (stride included), its per-column form otherwise.  Never the 16-bit coefficient form, never the
+// fused head (plan_dwt_fwd2 wants a u8 level 0).
+inline std::vector<FwdLaunch> plan_dwt_forward_u16(const uint16_t *d_in, size_t frame_stride, unsigned frames, void *d_out, int aw, int ah,
+                                                   int wl, float qs, int off)
+{
+    std::vector<FwdLaunch> v = plan_dwt_forward(d_in, false, d_out, aw, ah, wl, qs, false);
+    v[0].u16 = true;
+    v[0].a.off = off;
+    if (frames > 1 && (frame_stride & 15u)) v[0].vec = false;
+    return v;
+}
 
 // The UNQUANTISED 9/7 transform of the rate calls (picsong_encode_frame_rate): the same plan with every step and qs at
 // 1.0f -- x * 1.0f * 1.0f is x, the transform is exact -- in the 32-bit float form, so one frame lands in one float
@@ -278,6 +308,7 @@ inline std::vector<InvLaunch> plan_dwt_inverse(const int32_t *d_in, void *d_out,
         a.W = W; a.H = H;
         a.dst = (char *)d_out + write_off * 4;
         a.dst_u8 = nullptr; a.off = 0;
+        a.dst_u16 = nullptr; a.px_max = 0;
         a.mallat_z = a.ll_z = a.dst_z = a.u8_z = 0;
         {   // qs = 2^k: dividing by it is exact scaling, dwt_inv97_kernel folds it into the step
             int e = 0;
@@ -379,9 +410,32 @@ inline size_t dwt_extra(int aw, int ah, int wl)
 // reduce > 0: the levels wl - 1 .. reduce only (plan_dwt_inverse_reduced), level `reduce` the one that writes the pixels
 inline std::vector<InvLaunch> plan_inverse_frames(const int32_t *d_in, void *d_out, uint8_t *d_pixels, bool *fused, unsigned frames,
                                                   size_t pix_stride, bool want_c16, bool planes_out, int reduce, int aw, int ah,
-                                                  int wl, float qs, bool fast_div, int off, size_t P, size_t extra)
+                                                  int wl, float qs, bool fast_div, int off, size_t P, size_t extra, int px_max = 0)
 {
     if (fused) *fused = false;
+    if (px_max > 0) {
+        // a deep context: d_pixels holds uint16 samples, pix_stride bytes a frame.  32-bit coefficients; the finest level
+        // stores the clamped samples itself (dwt_inv_kernel's U16OUT form) where it is a vector launch, the samples start
+        // 16-byte aligned (stride included) and PICSONG_DEEP_NOFUSE is not set
+        const bool px16 = d_pixels && (((uintptr_t)d_pixels) & 15u) == 0 && (frames <= 1 || (pix_stride & 15u) == 0) && !deep_nofuse();
+        std::vector<InvLaunch> plan = plan_dwt_inverse_reduced(d_in, d_out, aw, ah, wl, qs, fast_div, false, reduce);
+        if (px16 && !plan.empty() && plan.back().vec) {
+            plan.back().a.dst_u16 = (uint16_t *)d_pixels;
+            plan.back().a.off = off;
+            plan.back().a.px_max = px_max;
+            if (fused) *fused = true;
+        }
+        if (frames > 1) {
+            const unsigned long long wrk_z = (unsigned long long)(P + extra) * 4ull;
+            for (InvLaunch &f : plan) {
+                f.a.mallat_z = (unsigned long long)P * 4ull;
+                f.a.ll_z = f.a.first ? f.a.mallat_z : wrk_z;
+                f.a.dst_z = wrk_z;
+                f.a.u8_z = (unsigned long long)pix_stride;
+            }
+        }
+        return plan;
+    }
     const bool px = d_pixels && (((uintptr_t)d_pixels) & 3u) == 0 && (pix_stride & 3u) == 0;
     std::vector<InvLaunch> plan = plan_dwt_inverse_reduced(d_in, d_out, aw, ah, wl, qs, fast_div, want_c16 && (px || planes_out), reduce);
     if (px && !plan.empty() && plan.back().vec) {

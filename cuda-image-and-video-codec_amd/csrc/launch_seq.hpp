@@ -49,6 +49,30 @@ int clamp_pixels(const Go &go, bool lossy, const void *img, uint8_t *out, size_t
     return lossy ? go(clamp_to_u8_f32_kernel, grid, 256u, (const float *)img, out, n4, (float)off)
                  : go(clamp_to_u8_i32_kernel, grid, 256u, (const int32_t *)img, out, n4, off);
 }
+// ---- deep contexts: uint16 samples (n4 groups of four; level_shift_inv16: n samples in place), px_max = 2^(bit depth) - 1
+template <class Go>
+int level_shift_fwd16(const Go &go, bool lossy, const uint16_t *in, void *out, size_t n4, int off)
+{
+    const dim3 grid(elementwise_blocks(n4, 4096));
+    const int wide = (((uintptr_t)in) & 7u) == 0 ? 1 : 0;
+    return lossy ? go(level_shift_fwd_u16_kernel<float>, grid, 256u, in, (float *)out, n4, off, wide)
+                 : go(level_shift_fwd_u16_kernel<int32_t>, grid, 256u, in, (int32_t *)out, n4, off, wide);
+}
+template <class Go>
+int level_shift_inv16(const Go &go, bool lossy, void *data, size_t n, int off, int px_max)
+{
+    const dim3 grid(elementwise_blocks(n));
+    return lossy ? go(level_shift_inv16_f32_kernel, grid, 256u, (float *)data, n, off, px_max)
+                 : go(level_shift_inv16_i32_kernel, grid, 256u, (int32_t *)data, n, off, px_max);
+}
+template <class Go>
+int clamp_pixels16(const Go &go, bool lossy, const void *img, uint16_t *out, size_t n4, int off, int px_max)
+{
+    const dim3 grid(elementwise_blocks(n4));
+    const int wide = (((uintptr_t)out) & 7u) == 0 ? 1 : 0;
+    return lossy ? go(clamp_to_u16_f32_kernel, grid, 256u, (const float *)img, out, n4, off, px_max, wide)
+                 : go(clamp_to_u16_i32_kernel, grid, 256u, (const int32_t *)img, out, n4, off, px_max, wide);
+}
 template <class Go>
 int rgb_forward(const Go &go, bool lossy, const uint8_t *r, const uint8_t *g, const uint8_t *b, void *c0, void *c1, void *c2,
                 size_t n4, int off)
@@ -96,6 +120,30 @@ inline void plan_frame_strides(std::vector<FwdLaunch> &plan, unsigned long long 
         plan[l].a.dst_z = coef_z;
     }
 }
+// The forward transform of n deep frames (picsong_encode_frames16, picsong_dwt_forward_u16): uint16 samples at `frames`,
+// frame_stride bytes apart, frame f's coefficients in its buffer of coef_z bytes at coef.  Level 0 reads the samples
+// itself (plan_dwt_forward_u16), or -- nofuse (PICSONG_DEEP_NOFUSE=1: the caller reads it) -- a level shift a frame into
+// `shifted` (P samples of T a frame, 16-byte aligned) and the T-input plan.  *in_kernel says which ran.
+template <class Go>
+int deep_forward(const Go &go, bool lossy, bool nofuse, const uint16_t *frames, size_t frame_stride, unsigned n, void *coef, void *shifted,
+                 int aw, int ah, int wl, float qs, int off, unsigned long long coef_z, bool *in_kernel = nullptr)
+{
+    const size_t P = (size_t)aw * (size_t)ah;
+    if (n <= 1) frame_stride = 0;
+    if (in_kernel) *in_kernel = !nofuse;
+    if (!nofuse) {
+        std::vector<FwdLaunch> plan = plan_dwt_forward_u16(frames, frame_stride, n, coef, aw, ah, wl, qs, off);
+        plan_frame_strides(plan, frame_stride, coef_z);
+        return launch_fwd_levels(go, lossy, plan, 0, n);
+    }
+    for (unsigned f = 0; f < n; f++)
+        if (int rc = level_shift_fwd16(go, lossy, (const uint16_t *)((const char *)frames + (size_t)f * frame_stride),
+                                       (char *)shifted + (size_t)f * P * 4, P / 4, off)) return rc;
+    std::vector<FwdLaunch> plan = plan_dwt_forward(shifted, false, coef, aw, ah, wl, qs, false);
+    plan_frame_strides(plan, (unsigned long long)P * 4ull, coef_z);
+    return launch_fwd_levels(go, lossy, plan, 0, n);
+}
+
 // An RGB frame's colour transform (level shift fused) and the forward transform of its three components, component k's
 // coefficients coef_z bytes after component k - 1's.  plan_of(src, u8in) makes the caller's plan: plan_dwt_forward with
 // its c16 choice (head_c16: the fused head is the frame paths' 16-bit one and wants such a plan) or the rate calls'
@@ -258,6 +306,7 @@ struct DecodeCtx {
     bool compact;             // -k > 0: the launch takes the COMPACT table copies
     uint32_t max_stream;      // a worst-case stream's shorts
     int *flag;                // the intake's damage flag
+    int px_max = 0;           // > 0: a deep context -- the grey calls' `out` holds uint16 samples, clamped to [0, px_max]
 };
 // what a call took, for those who ask (the drivers' return bits)
 struct DecodeReport {
@@ -291,7 +340,7 @@ int decode_head(const Go &go, const DecodeCtx &c, BpcArgs &a, const Workspace &w
     a.frames = (int)np; a.waves_per_frame = c.rgb ? rgb_component_waves(a.k > 0.0f, wpf) : wpf;
     if (!win)
         plan = plan_inverse_frames(w.coef_i, w.coef, pixels, &rep.pixels, np, pix_stride, want_c16 && c.direct, c.rgb, reduce, c.aw, c.ah,
-                                   c.wl, c.qs, c.fast_div, c.off, c.P, c.extra);
+                                   c.wl, c.qs, c.fast_div, c.off, c.P, c.extra, c.px_max);
     rep.c16 = plan_inv_is_c16(plan);
     a.coef_z = (unsigned long long)c.P * (rep.c16 ? 2ull : 4ull);
     return launch_decoder(go, a, c.cp3, np * (unsigned)a.waves_per_frame, c.compact, w, c.direct ? streams : nullptr, stream_stride,
@@ -313,8 +362,11 @@ int decode_frames(const Go &go, const DecodeCtx &c, BpcArgs a, const Workspace &
     if (win) return run_window(go, c.lossy, *win, w.coef_i, w.coef, c.P, c.aw, c.ah, c.qs, c.off, n, (unsigned long long)c.P * 4ull, z, out, pitch, frame_stride);
     if (int rc = run_inverse(go, c.lossy, lean97, plan, n, &rep.fused10)) return rc;
     // (level `reduce`'s samples of frame f: c.extra elements into its work buffer when reduce = 0)
-    for (unsigned f = 0; f < n && !rep.pixels; f++)
-        if (int rc = clamp_pixels(go, c.lossy, (const char *)plan.back().a.dst + f * z, out + f * frame_stride, n4, c.off)) return rc;
+    for (unsigned f = 0; f < n && !rep.pixels; f++) {
+        if (c.px_max > 0) {
+            if (int rc = clamp_pixels16(go, c.lossy, (const char *)plan.back().a.dst + f * z, (uint16_t *)(out + f * frame_stride), n4, c.off, c.px_max)) return rc;
+        } else if (int rc = clamp_pixels(go, c.lossy, (const char *)plan.back().a.dst + f * z, out + f * frame_stride, n4, c.off)) return rc;
+    }
     return 0;
 }
 // The colour calls (picsong_decode_rgb_frame, picsong_decode_rgb_frames, their _reduced and _window forms, the image

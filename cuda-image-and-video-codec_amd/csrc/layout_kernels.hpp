@@ -26,7 +26,8 @@
 namespace picsong {
 
 constexpr int kLayoutGrey8 = 0, kLayoutPlanar3 = 1, kLayoutRgb24 = 2, kLayoutBgr24 = 3, kLayoutRgba32 = 4, kLayoutBgra32 = 5;
-constexpr int kLayoutCount = 6;
+constexpr int kLayoutCount = 6;             // the layouts of 8-bit contexts
+constexpr int kLayoutGrey16 = 6;            // deep contexts' one layout: 2 bytes a pixel (native uint16), the padded side uint16 planes
 constexpr int kLayoutMaxFrames = 64;
 constexpr int kLayoutTail = 80;             // bytes a row and plane kept for the pad phase: 63 mirrored + 15 of a partial group
 constexpr int kLayoutLds = 64 * kLayoutTail;
@@ -278,6 +279,76 @@ __global__ __launch_bounds__(256) void emit_kernel(LayoutArgs s)
                 }
             }
         }
+    }
+}
+
+// ---- GREY16 (deep contexts): W x H native uint16 samples at a byte pitch, to and from a padded uint16 plane (row stride
+// AW samples; frame f at pad + f * pad_stride BYTES).  The mirror rule is picsong_pad_frame16_host's.
+// ingest16_kernel: a thread makes a group of 8 samples (16 bytes) of one PADDED row, from the source row that row
+// mirrors; only bytes [y * pitch, y * pitch + 2 W) of the source rows 0 .. H - 1 are read.  emit16_kernel crops: a thread
+// a group of 8 samples of a visible row, and no byte outside [y * pitch, y * pitch + 2 W) of rows 0 .. H - 1 is written.
+// VEC: the padded side 16-byte, the image side 4-byte aligned -- a dwordx4 on the padded side, dwords on the image side for a
+// group that lies wholly inside the row.  Else every sample on its own; the same bytes.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ingest16_kernel(LayoutArgs s)
+{
+    const uint32_t W = (uint32_t)s.W, H = (uint32_t)s.H, AW = (uint32_t)s.AW, AH = (uint32_t)s.AH;
+    const uint32_t gpr = AW / 8u;
+    const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (t >= (size_t)gpr * AH) return;
+    const uint32_t y = (uint32_t)(t / gpr), x0 = (uint32_t)(t % gpr) * 8u;
+    const uint32_t sy = y < H ? y : 2u * H - 1u - y;
+    const uint8_t *const src = s.img + (size_t)blockIdx.z * s.frame_stride + (size_t)sy * s.pitch;
+    uint8_t *const dst = s.pad + (size_t)blockIdx.z * s.pad_stride + ((size_t)y * AW + x0) * 2u;
+    uint32_t w[4];
+    if (VEC && x0 + 8u <= W) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k] = reinterpret_cast<const uint32_t *>(src + (size_t)x0 * 2u)[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t xa = x0 + 2u * k, xb = xa + 1u;
+            const uint32_t sa = xa < W ? xa : 2u * W - 1u - xa, sb = xb < W ? xb : 2u * W - 1u - xb;
+            w[k] = (uint32_t)reinterpret_cast<const uint16_t *>(src)[sa] | ((uint32_t)reinterpret_cast<const uint16_t *>(src)[sb] << 16);
+        }
+    }
+    if constexpr (VEC) {
+        uint4 v;
+        v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+        *reinterpret_cast<uint4 *>(dst) = v;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++) reinterpret_cast<uint16_t *>(dst)[i] = (uint16_t)(w[i / 2] >> (16 * (i % 2)));
+    }
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void emit16_kernel(LayoutArgs s)
+{
+    const uint32_t W = (uint32_t)s.W, H = (uint32_t)s.H, AW = (uint32_t)s.AW;
+    const uint32_t gpr = (W + 7u) / 8u;
+    const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (t >= (size_t)gpr * H) return;
+    const uint32_t y = (uint32_t)(t / gpr), x0 = (uint32_t)(t % gpr) * 8u;
+    const uint32_t nvis = W - x0 < 8u ? W - x0 : 8u;
+    // (a whole group of the padded row is always there: AW is a multiple of 64)
+    const uint8_t *const src = s.pad + (size_t)blockIdx.z * s.pad_stride + ((size_t)y * AW + x0) * 2u;
+    uint8_t *const dst = s.img + (size_t)blockIdx.z * s.frame_stride + (size_t)y * s.pitch + (size_t)x0 * 2u;
+    uint32_t w[4];
+    if constexpr (VEC) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(src);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            w[k] = (uint32_t)reinterpret_cast<const uint16_t *>(src)[2 * k] | ((uint32_t)reinterpret_cast<const uint16_t *>(src)[2 * k + 1] << 16);
+    }
+    if (VEC && nvis == 8u) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) reinterpret_cast<uint32_t *>(dst)[k] = w[k];
+    } else {
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++)
+            if (i < nvis) reinterpret_cast<uint16_t *>(dst)[i] = (uint16_t)(w[i / 2u] >> (16u * (i % 2u)));
     }
 }
 

@@ -115,6 +115,21 @@ static bool lean97_levels()
 }
 
 static int level_off(const picsong_ctx *c) { return 1 << (c->p.bit_depth - 1); }
+// a deep context: 9- to 16-bit samples, uint16 frames through the *16 calls; its largest sample
+static bool is_deep(const picsong_ctx *c) { return c->p.bit_depth > 8; }
+static int px_max(const picsong_ctx *c) { return (1 << c->p.bit_depth) - 1; }
+// the calls that take or return uint8_t frames, on a deep context (nothing launched)
+#define REFUSE_DEEP(c, who)                                                                                              \
+    do {                                                                                                                 \
+        if ((c) && is_deep(c))                                                                                           \
+            return fail(PICSONG_ERR_ARG, "%s: 8-bit frames on a %d-bit context (its frame calls: picsong_encode_frames16, " \
+                                         "picsong_decode_frames16, GREY16 images)", who, (c)->p.bit_depth);             \
+    } while (0)
+// ... and the uint16 calls on an 8-bit one
+#define REFUSE_SHALLOW(c, who)                                                                                           \
+    do {                                                                                                                 \
+        if ((c) && !is_deep(c)) return fail(PICSONG_ERR_ARG, "%s: uint16 samples on an 8-bit context", who);             \
+    } while (0)
 
 extern "C" {
 
@@ -325,7 +340,9 @@ int picsong_ctx_create(const picsong_params *p, int device, picsong_ctx **out)
     if (p->cp == 3 && p->k > 0.0f) return fail(PICSONG_ERR_ARG, "-cp 3 has no complexity-scalable mode (k must be 0)");
     if (!(p->k >= 0.0f && p->k <= 65.535f)) return fail(PICSONG_ERR_ARG, "k %g outside [0, 65.535]", p->k);
     if (p->lossy && !(p->qs > 0.0f && p->qs <= 1.0f)) return fail(PICSONG_ERR_ARG, "qs %g outside (0,1]", p->qs);
-    if (p->bit_depth != 8) return fail(PICSONG_ERR_ARG, "only 8-bit samples are implemented");
+    if (p->bit_depth < 8 || p->bit_depth > 16) return fail(PICSONG_ERR_ARG, "bit depth %d outside 8..16", p->bit_depth);
+    if (p->bit_depth > 8 && (p->components != 1 || p->is_rgb))
+        return fail(PICSONG_ERR_ARG, "%d-bit samples: grey contexts only (components 1, is_rgb 0)", p->bit_depth);
     if (!((p->components == 1 && !p->is_rgb) || (p->components == 3 && p->is_rgb)))
         return fail(PICSONG_ERR_ARG, "components must be 1 (grey) or 3 with is_rgb (got %d, is_rgb %d)", p->components,
                     p->is_rgb);
@@ -617,6 +634,7 @@ int picsong_ctx_padded_dims(const picsong_ctx *c, int *aw, int *ah, int *ncb)
 // ---------------------------------------------------------------------------------------------
 int picsong_level_shift_fwd(picsong_ctx *c, const uint8_t *d_in, void *d_out, void *stream)
 {
+    REFUSE_DEEP(c, "level_shift_fwd");
     if (!c || !d_in || !d_out) return fail(PICSONG_ERR_ARG, "level_shift_fwd: null argument");
     return level_shift_fwd(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, d_in, d_out, c->P / 4, level_off(c));
 }
@@ -624,6 +642,7 @@ int picsong_level_shift_fwd(picsong_ctx *c, const uint8_t *d_in, void *d_out, vo
 int picsong_level_shift_inv(picsong_ctx *c, void *d_data, void *stream)
 {
     if (!c || !d_data) return fail(PICSONG_ERR_ARG, "level_shift_inv: null argument");
+    if (is_deep(c)) return level_shift_inv16(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, d_data, c->P, level_off(c), px_max(c));
     return level_shift_inv(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, d_data, c->P, level_off(c));
 }
 
@@ -651,12 +670,14 @@ int picsong_dwt_forward(picsong_ctx *c, const void *d_in, void *d_out, void *str
 
 int picsong_dwt_forward_u8(picsong_ctx *c, const uint8_t *d_in, void *d_out, void *stream)
 {
+    REFUSE_DEEP(c, "dwt_forward_u8");
     if (!c || !d_in || !d_out) return fail(PICSONG_ERR_ARG, "dwt_forward_u8: null argument");
     return dwt_forward_impl(c, d_in, true, d_out, (hipStream_t)stream);
 }
 
 int picsong_dwt_forward_band(picsong_ctx *c, const uint8_t *d_frame, int row0, int rows, void *d_out, void *stream)
 {
+    REFUSE_DEEP(c, "dwt_forward_band");
     if (!c || !d_frame || !d_out) return fail(PICSONG_ERR_ARG, "dwt_forward_band: null argument");
     if (row0 < 0 || rows <= 0 || (row0 & 1) || (rows & 1) || row0 + rows > c->ah)
         return fail(PICSONG_ERR_ARG, "dwt_forward_band: rows [%d, %d) must be even and inside [0, %d)", row0, row0 + rows, c->ah);
@@ -955,6 +976,7 @@ int picsong_profile_read(picsong_ctx *c, int *n_frames, float *ms, int cap)
 
 int picsong_encode_frame(picsong_ctx *c, const uint8_t *d_frame, int iter, uint16_t *d_stream, void *stream)
 {
+    REFUSE_DEEP(c, "encode_frame");
     if (!c || !d_frame || !d_stream) return fail(PICSONG_ERR_ARG, "encode_frame: null argument");
     int rc = ensure_workspace(c, false);
     if (rc) return rc;
@@ -1053,6 +1075,7 @@ int picsong_encode_stripe_coded(picsong_ctx *c, const void *d_coeffs, int cb_beg
 int picsong_encode_frame_stripe(picsong_ctx *c, const uint8_t *d_frame, int cb_begin, int cb_count,
                                 uint16_t *d_stream, void *stream)
 {
+    REFUSE_DEEP(c, "encode_frame_stripe");
     if (!c || !d_frame || !d_stream) return fail(PICSONG_ERR_ARG, "encode_frame_stripe: null argument");
     if (cb_begin < 0 || cb_count <= 0 || cb_begin + cb_count > c->ncb)
         return fail(PICSONG_ERR_ARG, "encode_frame_stripe: codeblocks [%d, %d) outside [0, %d)", cb_begin,
@@ -1110,6 +1133,7 @@ static int ensure_coef_i(picsong_ctx *c, int n)
 int picsong_encode_frames(picsong_ctx *c, int n, const uint8_t *d_frames, size_t frame_stride, int first_iter,
                           uint16_t *d_streams, size_t stream_stride, void *stream)
 {
+    REFUSE_DEEP(c, "encode_frames");
     if (!c || !d_frames || !d_streams) return fail(PICSONG_ERR_ARG, "encode_frames: null argument");
     if (n < 1 || n > 64) return fail(PICSONG_ERR_ARG, "encode_frames: %d frames outside 1..64", n);
     if (n > 1 && (frame_stride < c->P || stream_stride < picsong_max_stream_shorts(c->aw, c->ah)))
@@ -1183,6 +1207,7 @@ static DecodeCtx decode_ctx(picsong_ctx *c, const BpcArgs &a, bool rgb)
     g.compact = a.k > 0.0f && bulk_compact(c, 0, rgb ? 3 : 1);
     g.max_stream = (uint32_t)picsong_max_stream_shorts(c->aw, c->ah);
     g.flag = c->d_flag;
+    g.px_max = is_deep(c) ? px_max(c) : 0;               // (a deep context's decode calls are the *16 ones)
     return g;
 }
 
@@ -1219,6 +1244,7 @@ static int decode_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, 
                               size_t frame_stride, void *stream, int reduce, const char *who,
                               const WindowPlan *win = nullptr, size_t pitch = 0)
 {
+    REFUSE_DEEP(c, who);
     if (!c || !d_streams || !d_frames_out) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     if (n < 1 || n > 64) return fail(PICSONG_ERR_ARG, "%s: n = %d outside 1..64", who, n);
     if (c->p.cp == 3 || c->p.is_rgb)
@@ -1237,12 +1263,14 @@ static int decode_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, 
 // what a context holds, -cp 3 through the staging included.
 int picsong_decode_frame(picsong_ctx *c, const uint16_t *d_stream, uint8_t *d_frame_out, void *stream)
 {
+    REFUSE_DEEP(c, "decode_frame");
     if (!c || !d_frame_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame: null argument");
     return decode_grey(c, 1, d_stream, 0, d_frame_out, 0, stream, 0);
 }
 
 int picsong_decode_frame_reduced(picsong_ctx *c, const uint16_t *d_stream, int reduce, uint8_t *d_out, void *stream)
 {
+    REFUSE_DEEP(c, "decode_frame_reduced");
     if (!c || !d_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame_reduced: null argument");
     if (int rc = reduced_args_ok(c, reduce, "decode_frame_reduced")) return rc;
     return decode_grey(c, 1, d_stream, 0, d_out, 0, stream, reduce);
@@ -1251,6 +1279,7 @@ int picsong_decode_frame_reduced(picsong_ctx *c, const uint16_t *d_stream, int r
 int picsong_decode_frame_window(picsong_ctx *c, const uint16_t *d_stream, int reduce, int x, int y, int w, int h,
                                 uint8_t *d_out, size_t out_pitch, void *stream)
 {
+    REFUSE_DEEP(c, "decode_frame_window");
     if (!c || !d_out || !d_stream) return fail(PICSONG_ERR_ARG, "decode_frame_window: null argument");
     WindowPlan plan;
     if (int rc = window_args_ok(c, reduce, x, y, w, h, "decode_frame_window", &plan)) return rc;
@@ -1274,6 +1303,7 @@ int picsong_decode_frames_reduced(picsong_ctx *c, int n, const uint16_t *d_strea
 int picsong_decode_frames_window(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x,
                                  int y, int w, int h, uint8_t *d_out, size_t out_pitch, size_t frame_stride, void *stream)
 {
+    REFUSE_DEEP(c, "decode_frames_window");
     const char *who = "decode_frames_window";
     if (!c || !d_streams || !d_out) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     WindowPlan plan;
@@ -1297,11 +1327,103 @@ int picsong_copy_last_totals(picsong_ctx *c, void *stream, int n, int32_t *d_tot
 }
 
 // ---------------------------------------------------------------------------------------------
+// deep contexts (bit_depth 9..16): uint16 samples at the transform's two ends, everything between as ever (32-bit
+// coefficient arrays, no fused head or tail).  PICSONG_DEEP_NOFUSE=1 (read per call): the element-wise passes.
+// ---------------------------------------------------------------------------------------------
+int picsong_depth_range_guaranteed(int bit_depth, int lossy, int wl, float qs, int *yes)
+{
+    if (!yes) return fail(PICSONG_ERR_ARG, "depth_range_guaranteed: null argument");
+    if (bit_depth < 8 || bit_depth > 16) return fail(PICSONG_ERR_ARG, "depth_range_guaranteed: bit depth %d outside 8..16", bit_depth);
+    if (wl < 1 || wl > 7) return fail(PICSONG_ERR_ARG, "depth_range_guaranteed: wl %d outside 1..7", wl);
+    if (lossy && !(qs > 0.0f && qs <= 1.0f)) return fail(PICSONG_ERR_ARG, "depth_range_guaranteed: qs %g outside (0,1]", qs);
+    *yes = coef16_bound(lossy != 0, wl, qs, 1 << (bit_depth - 1)) ? 1 : 0;
+    return PICSONG_OK;
+}
+
+int picsong_level_shift_fwd16(picsong_ctx *c, const uint16_t *d_in, void *d_out, void *stream)
+{
+    REFUSE_SHALLOW(c, "level_shift_fwd16");
+    if (!c || !d_in || !d_out) return fail(PICSONG_ERR_ARG, "level_shift_fwd16: null argument");
+    if (((uintptr_t)d_in) & 1u) return fail(PICSONG_ERR_ARG, "level_shift_fwd16: uint16 samples need a 2-byte aligned pointer");
+    return level_shift_fwd16(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, d_in, d_out, c->P / 4, level_off(c));
+}
+
+int picsong_dwt_forward_u16(picsong_ctx *c, const uint16_t *d_in, void *d_out, void *stream)
+{
+    REFUSE_SHALLOW(c, "dwt_forward_u16");
+    if (!c || !d_in || !d_out) return fail(PICSONG_ERR_ARG, "dwt_forward_u16: null argument");
+    if (((uintptr_t)d_in) & 1u) return fail(PICSONG_ERR_ARG, "dwt_forward_u16: uint16 samples need a 2-byte aligned pointer");
+    const bool nofuse = deep_nofuse();
+    if (nofuse) if (int rc = ensure_workspace(c, false)) return rc;      // (the shifted samples: the frame's staging)
+    return deep_forward(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, nofuse, d_in, 0, 1u, d_out, c->one.staging, c->aw, c->ah, c->p.wl,
+                        c->p.qs, level_off(c), 0);
+}
+
+// what the two frame calls refuse alike (nothing launched)
+static int frames16_args_ok(const picsong_ctx *c, int n, const void *d_frames, size_t frame_stride, const void *d_streams,
+                            size_t stream_stride, const char *who)
+{
+    REFUSE_SHALLOW(c, who);
+    if (!c || !d_frames || !d_streams) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (n < 1 || n > 64) return fail(PICSONG_ERR_ARG, "%s: %d frames outside 1..64", who, n);
+    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 2 contexts only", who);
+    if ((((uintptr_t)d_frames) | ((uintptr_t)d_streams)) & 1u) return fail(PICSONG_ERR_ARG, "%s: pointers need 2-byte alignment", who);
+    if (n > 1 && ((frame_stride & 1u) || frame_stride < 2 * c->P))
+        return fail(PICSONG_ERR_ARG, "%s: frame_stride %zu must be even and at least a padded frame's %zu bytes", who, frame_stride, 2 * c->P);
+    if (n > 1 && stream_stride < picsong_max_stream_shorts(c->aw, c->ah))
+        return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
+    return PICSONG_OK;
+}
+
+int picsong_encode_frames16(picsong_ctx *c, int n, const uint16_t *d_frames, size_t frame_stride, int first_iter,
+                            uint16_t *d_streams, size_t stream_stride, void *stream)
+{
+    int rc = frames16_args_ok(c, n, d_frames, frame_stride, d_streams, stream_stride, "encode_frames16");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    BpcArgs a;
+    if ((rc = bpc_args(c, a, 0))) return rc;
+    if ((rc = ensure_batch(c, n))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t coef_z = (c->P + c->extra) * 4;
+    // ---- DWT: level 0 reads the uint16 samples (grid.z = n); the batch's staging holds the shifted samples of the
+    // element-wise route until the coder overwrites it
+    if ((rc = deep_forward(HipGo{ s }, c->p.lossy != 0, deep_nofuse(), d_frames, frame_stride, (unsigned)n, c->batch.coef, c->batch.staging,
+                           c->aw, c->ah, c->p.wl, c->p.qs, level_off(c), coef_z))) return rc;
+    // ---- coder: one grid over the n frames' codeblock pairs, 32-bit coefficients
+    const int wpf = (c->ncb + 1) / 2;
+    a.c16 = 0;
+    a.cb_base = 0; a.nCB = c->ncb;
+    a.coeffs_in = c->batch.coef; a.is_float = c->p.lossy ? 1 : 0;
+    a.staging16 = reinterpret_cast<uint16_t *>(c->batch.staging);
+    a.sizes = c->batch.sizes; a.plane_scratch = c->batch.plane_scratch;
+    a.frames = n; a.waves_per_frame = wpf; a.coef_z = coef_z;
+    if ((rc = launch_encoder(c, a, (unsigned)n * (unsigned)wpf, 0, 1, s))) return rc;
+    // ---- pack: the populated header (both depth fields carry bit_depth) where the batch holds the video's frame 0
+    uint16_t hdr[PICSONG_HDR_SHORTS];
+    const bool has0 = first_iter <= 0 && first_iter + n > 0;
+    if (has0) picsong_header_pack(&c->p, hdr);
+    if ((rc = pack_frames(HipGo{ s }, a.staging16, c->batch, c->ncb, (unsigned)n, has0 ? hdr : nullptr, -first_iter + 1, d_streams,
+                          c->P, stream_stride))) return rc;
+    c->last_batch = n;
+    return PICSONG_OK;
+}
+
+int picsong_decode_frames16(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, uint16_t *d_frames_out,
+                            size_t frame_stride, void *stream)
+{
+    if (int rc = frames16_args_ok(c, n, d_frames_out, frame_stride, d_streams, stream_stride, "decode_frames16")) return rc;
+    // (decode_ctx hands the sequence px_max: uint16 samples at d_frames_out, frame_stride bytes apart)
+    return decode_grey(c, n, d_streams, stream_stride, reinterpret_cast<uint8_t *>(d_frames_out), frame_stride, stream, 0);
+}
+
+// ---------------------------------------------------------------------------------------------
 // RGB path
 // ---------------------------------------------------------------------------------------------
 int picsong_rgb_forward(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, void *d_c0,
                         void *d_c1, void *d_c2, void *stream)
 {
+    REFUSE_DEEP(c, "rgb_forward");
     if (!c || !d_r || !d_g || !d_b || !d_c0 || !d_c1 || !d_c2) return fail(PICSONG_ERR_ARG, "rgb_forward: null argument");
     return rgb_forward(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, d_r, d_g, d_b, d_c0, d_c1, d_c2, c->P / 4, level_off(c));
 }
@@ -1309,6 +1431,7 @@ int picsong_rgb_forward(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, 
 int picsong_rgb_inverse(picsong_ctx *c, const void *d_c0, const void *d_c1, const void *d_c2, uint8_t *d_r,
                         uint8_t *d_g, uint8_t *d_b, void *stream)
 {
+    REFUSE_DEEP(c, "rgb_inverse");
     if (!c || !d_r || !d_g || !d_b || !d_c0 || !d_c1 || !d_c2) return fail(PICSONG_ERR_ARG, "rgb_inverse: null argument");
     return rgb_inverse(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, d_c0, d_c1, d_c2, d_r, d_g, d_b, c->P / 4, level_off(c));
 }
@@ -1534,6 +1657,7 @@ int picsong_sse_to_psnr(uint64_t sse, uint64_t samples, double *psnr_db)
 int picsong_frames_sse(picsong_ctx *c, int n, const uint8_t *d_a, size_t a_stride, const uint8_t *d_b, size_t b_stride,
                        uint64_t *d_sse, void *stream)
 {
+    REFUSE_DEEP(c, "frames_sse");
     if (!c || !d_a || !d_b || !d_sse) return fail(PICSONG_ERR_ARG, "frames_sse: null argument");
     if (n < 1 || n > kSseMaxFrames) return fail(PICSONG_ERR_ARG, "frames_sse: %d frames outside 1..%d", n, kSseMaxFrames);
     if (n > 1 && (a_stride < c->P || b_stride < c->P)) return fail(PICSONG_ERR_ARG, "frames_sse: strides smaller than a padded frame");
@@ -1657,6 +1781,7 @@ enum SearchForm { kFrames, kOneFrame, kRgbFrame, kRgbFrames };
 static int search_args_ok(const picsong_ctx *c, const RateJob &job, SearchForm form, SearchKind kind, bool outs, const char *who)
 {
     const bool rgb = form == kRgbFrame || form == kRgbFrames;
+    REFUSE_DEEP(c, who);
     if (!c || !job.d_streams || !outs || (rgb ? !job.r || !job.g || !job.b : !job.frames)) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     if (form == kRgbFrames) {
         if (const char *why = rgb_frames_refusal(c->p.is_rgb != 0, c->p.cp, true, job.n, job.r, job.g, job.b, job.d_streams, job.frame_stride,
@@ -1877,6 +2002,7 @@ int picsong_train_coeffs(picsong_ctx *c, int comp, const void *d_coeffs, void *s
 
 int picsong_train_frames(picsong_ctx *c, int n, const uint8_t *d_frames, size_t frame_stride, void *stream)
 {
+    REFUSE_DEEP(c, "train_frames");
     if (int rc = train_ready(c, "train_frames")) return rc;
     if (!d_frames) return fail(PICSONG_ERR_ARG, "train_frames: null argument");
     if (n < 1 || n > 64) return fail(PICSONG_ERR_ARG, "train_frames: %d frames outside 1..64", n);
@@ -2038,7 +2164,7 @@ static int layout_args_ok(const picsong_ctx *c, int n, const picsong_image *img,
 {
     if (!c || !img) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     if (const char *why = layout_refusal(img->layout, img->data, img->pitch, img->plane_stride, frame_stride, d_padded, padded_stride, n,
-                                         c->p.width, c->p.height, c->aw, c->ah))
+                                         c->p.width, c->p.height, c->aw, c->ah, is_deep(c)))
         return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
     return PICSONG_OK;
 }
@@ -2080,6 +2206,11 @@ static int image_args_ok(const picsong_ctx *c, int n, const picsong_image *img, 
     if (!c || !img || !d_streams) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     // (the padded side is the context's buffer, allocated later: any non-null address stands for it, its stride a frame's planes)
     if (int rc = layout_args_ok(c, n, img, frame_stride, c, (size_t)3 * c->P, who)) return rc;
+    if (img->layout == kLayoutGrey16) {                     // (a deep context: layout_args_ok; grey by its creation)
+        if (rgb) return fail(PICSONG_ERR_ARG, "%s: the context is not an RGB one", who);
+        if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 2 contexts only, as the frame call behind it", who);
+        return PICSONG_OK;
+    }
     if (rgb != (c->p.is_rgb != 0)) return fail(PICSONG_ERR_ARG, "%s: the context is %s", who, rgb ? "not an RGB one" : "an RGB one");
     if (rgb != (img->layout != kLayoutGrey8))
         return fail(PICSONG_ERR_ARG, "%s: layout %d on %s context", who, img->layout, rgb ? "an RGB" : "a grey");
@@ -2097,9 +2228,12 @@ int picsong_encode_images(picsong_ctx *c, int n, const picsong_image *src, size_
     BpcArgs a;
     if (int rc = bpc_args(c, a, 0)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    if (int rc = ensure_layout(c, (size_t)n)) return rc;
+    const size_t bps = is_deep(c) ? 2 : 1;                  // bytes a padded sample
+    if (int rc = ensure_layout(c, (size_t)n * bps)) return rc;
     if (int rc = ingest_frames(HipGo{ (hipStream_t)stream }, src->layout, src->data, src->pitch, src->plane_stride, frame_stride, c->lay_buf,
-                               c->P, n, c->p.width, c->p.height, c->aw, c->ah)) return rc;
+                               bps * c->P, n, c->p.width, c->p.height, c->aw, c->ah)) return rc;
+    if (is_deep(c))
+        return picsong_encode_frames16(c, n, reinterpret_cast<const uint16_t *>(c->lay_buf), 2 * c->P, first_iter, d_streams, stream_stride, stream);
     return picsong_encode_frames(c, n, c->lay_buf, c->P, first_iter, d_streams, stream_stride, stream);
 }
 
@@ -2113,9 +2247,12 @@ int picsong_decode_images(picsong_ctx *c, int n, const uint16_t *d_streams, size
     BpcArgs a;
     if (int rc = bpc_args(c, a, 0)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    if (int rc = ensure_layout(c, (size_t)n)) return rc;
-    if (int rc = picsong_decode_frames(c, n, d_streams, stream_stride, c->lay_buf, c->P, stream)) return rc;
-    return emit_frames(HipGo{ (hipStream_t)stream }, dst->layout, c->lay_buf, c->P, dst->data, dst->pitch, dst->plane_stride, frame_stride,
+    const size_t bps = is_deep(c) ? 2 : 1;
+    if (int rc = ensure_layout(c, (size_t)n * bps)) return rc;
+    if (is_deep(c)) {
+        if (int rc = picsong_decode_frames16(c, n, d_streams, stream_stride, reinterpret_cast<uint16_t *>(c->lay_buf), 2 * c->P, stream)) return rc;
+    } else if (int rc = picsong_decode_frames(c, n, d_streams, stream_stride, c->lay_buf, c->P, stream)) return rc;
+    return emit_frames(HipGo{ (hipStream_t)stream }, dst->layout, c->lay_buf, bps * c->P, dst->data, dst->pitch, dst->plane_stride, frame_stride,
                        n, c->p.width, c->p.height, c->aw, c->ah);
 }
 
@@ -2408,6 +2545,20 @@ int picsong_pad_frame_host(const uint8_t *in, int w, int h, uint8_t *out, int aw
         for (int j = 0; j < aw - w; j++) out[(size_t)y * aw + w + j] = in[(size_t)y * w + (w - 1 - j)];
     }
     for (int r = 0; r < ah - h; r++) memcpy(out + (size_t)(h + r) * aw, out + (size_t)(h - 1 - r) * aw, (size_t)aw);
+    return PICSONG_OK;
+}
+
+// the same rule on 2-byte samples
+int picsong_pad_frame16_host(const uint16_t *in, int w, int h, uint16_t *out, int aw, int ah)
+{
+    if (!in || !out || w <= 0 || h <= 0 || aw < w || ah < h) return fail(PICSONG_ERR_ARG, "pad_frame16: bad argument");
+    if (aw - w > w || ah - h > h)
+        return fail(PICSONG_ERR_ARG, "pad_frame16: %dx%d -> %dx%d adds more columns/rows than the frame has", w, h, aw, ah);
+    for (int y = 0; y < h; y++) {
+        memcpy(out + (size_t)y * aw, in + (size_t)y * w, (size_t)w * 2);
+        for (int j = 0; j < aw - w; j++) out[(size_t)y * aw + w + j] = in[(size_t)y * w + (w - 1 - j)];
+    }
+    for (int r = 0; r < ah - h; r++) memcpy(out + (size_t)(h + r) * aw, out + (size_t)(h - 1 - r) * aw, (size_t)aw * 2);
     return PICSONG_OK;
 }
 

@@ -106,6 +106,10 @@ void help()
         " -numberOfStreams N  frames in flight (default 2)\n"
         " -isRGB 1 -components 3  planar R,G,B planes per frame (RCT lossless / ICT lossy)\n"
         " -k 0..65.535        complexity-scalable factor (needs the bit-plane LUT files _0.._14)\n"
+        " -bps 8..16          bits a sample (default 8).  9..16: ONE grey still image -- coding reads a raw file of W*H\n"
+        "                     little-endian 16-bit samples or a P5 PGM with maxval > 255 (big-endian samples), decoding\n"
+        "                     writes a P5 with maxval 2^bps - 1; -drop works; no video, RGB, -rate, -psnr, -train, -reduce,\n"
+        "                     -window, -gpus, or -layout other than grey\n"
         " -device D           GPU index (default 0);  --metrics <file>  JSON stage timings\n"
         " -gpus N             video coding: groups of frames sharded round-robin over devices D .. D+N-1 of this node\n"
         "                     (--devices a,b,c names them explicitly); every device copies its codestreams to the\n"
@@ -233,7 +237,7 @@ Options parse(const Args &a)
 }
 
 // ---- file helpers -----------------------------------------------------------------------------
-struct Pgm { bool is_pgm = false; int w = 0, h = 0; size_t offset = 0; };
+struct Pgm { bool is_pgm = false; int w = 0, h = 0, maxval = 0; size_t offset = 0; };
 
 Pgm sniff_pgm(const std::string &path)
 {
@@ -251,7 +255,7 @@ Pgm sniff_pgm(const std::string &path)
     }
     if (n < 3) return p;
     f.get();                                   // single whitespace after maxval
-    p.is_pgm = true; p.w = vals[0]; p.h = vals[1]; p.offset = (size_t)f.tellg();
+    p.is_pgm = true; p.w = vals[0]; p.h = vals[1]; p.maxval = vals[2]; p.offset = (size_t)f.tellg();
     return p;
 }
 
@@ -746,6 +750,76 @@ int run_train(const Options &o, size_t file_base, long nframes)
 
 constexpr long kProfFrames = 256;     // frames per pipeline slot whose stages are timed with HIP events
 
+// ---- -bps 9..16: ONE grey still image of 16-bit samples, coded (picsong_encode_images, GREY16) and decoded
+// (picsong_decode_images).  What every other mode says when it meets such a depth:
+const char *const kDeepBuilt =
+    "With -bps 9..16 this build codes one grey still image (-cd 0: a raw file of W*H little-endian 16-bit samples or a P5 PGM with "
+    "maxval > 255) and decodes it (-cd 1, -drop allowed): not -video, -isRGB, -rate, -psnr, -train, -reduce, -window, -gpus or a "
+    "-layout other than grey; -signedOrUnsigned 1 is not built.";
+void deep_check_mode(const Options &o, bool rgb, int bps)
+{
+    if (bps < 9 || bps > 16 || o.signed_or_unsigned != 0) die(std::string("Only unsigned samples of 8..16 bits are built. ") + kDeepBuilt);
+    if (o.video || rgb || o.has_rate || o.has_psnr || !o.train.empty() || o.reduce > 0 || o.win || o.gpus > 1 || !o.devices.empty() ||
+        o.layout > PICSONG_LAYOUT_GREY8 || !o.compare.empty() || o.search_frames > 0)
+        die(kDeepBuilt);
+}
+int run_encode_deep(const Options &o, const Pgm &pgm)
+{
+    deep_check_mode(o, o.is_rgb != 0, o.bps);
+    if (o.cp == 3) die(std::string("-cp 3 is not built for -bps 9..16. ") + kDeepBuilt);
+    if (pgm.is_pgm && pgm.maxval <= 255) die("Incorrect parameters. -bps " + std::to_string(o.bps) + " takes a P5 PGM with maxval > 255 (two bytes a sample).");
+    const size_t n = (size_t)o.x * (size_t)o.y;
+    std::vector<uint16_t> img(n);
+    {
+        std::ifstream in(o.input, std::ios::binary);
+        if (!in) die("Cannot open input file " + o.input);
+        in.seekg((std::streamoff)(pgm.is_pgm ? pgm.offset : 0));
+        in.read(reinterpret_cast<char *>(img.data()), (std::streamsize)(n * 2));
+        if ((size_t)in.gcount() != n * 2) die("Input file is shorter than the requested frames.");
+        // (Netpbm: a PGM's two-byte samples are big-endian; a raw file's are little-endian, the host's order)
+        if (pgm.is_pgm) for (uint16_t &v : img) v = (uint16_t)((v >> 8) | (v << 8));
+    }
+    HIPCK(hipSetDevice(o.device));
+    picsong_params p = make_params(o);
+    p.frames = 0;
+    picsong_ctx *ctx = nullptr;
+    CK(picsong_ctx_create(&p, o.device, &ctx));
+    load_lut(ctx, o, o.wl, 1, o.k, o.cp);
+    int aw, ah, ncb;
+    CK(picsong_ctx_padded_dims(ctx, &aw, &ah, &ncb));
+    const size_t max_shorts = picsong_max_stream_shorts(aw, ah);
+    hipStream_t s;
+    HIPCK(hipStreamCreate(&s));
+    uint16_t *d_raw = nullptr, *d_out = nullptr;
+    HIPCK(hipMalloc(&d_raw, n * 2));
+    HIPCK(hipMalloc(&d_out, max_shorts * 2));
+    std::vector<uint16_t> out(max_shorts);
+    auto t0 = std::chrono::steady_clock::now();
+    HIPCK(hipMemcpyAsync(d_raw, img.data(), n * 2, hipMemcpyHostToDevice, s));
+    picsong_image im;
+    im.data = d_raw; im.pitch = (size_t)o.x * 2; im.plane_stride = 0; im.layout = PICSONG_LAYOUT_GREY16;
+    CK(picsong_encode_images(ctx, 1, &im, 0, 0, d_out, max_shorts, s));
+    int total = 0, flag = 0;
+    CK(picsong_last_totals(ctx, s, 1, &total));
+    HIPCK(hipMemcpyAsync(out.data(), d_out, (size_t)total * 2, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    CK(picsong_range_flag(ctx, s, &flag));
+    double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (flag) die("A coefficient of this image reaches 2^15, beyond what the coder codes (picsong_depth_range_guaranteed says which "
+                  "depths never do): nothing written.");
+    {
+        std::ofstream f(o.output, std::ios::binary | std::ios::trunc);
+        if (!f) die("Cannot open output file " + o.output);
+        f.write(reinterpret_cast<const char *>(out.data()), (std::streamsize)((size_t)total * 2));
+    }
+    std::cout << "The time spent with the app without considering allocation periods is: " << sec << std::endl;
+    write_metrics(o, "encode", 1, sec, 0, 0, 0, total);
+    picsong_ctx_destroy(ctx);
+    (void)hipStreamDestroy(s);
+    (void)hipFree(d_raw); (void)hipFree(d_out);
+    return 0;
+}
+
 // ---- coding engine: CodingEngine::runImage / runVideo call sequence ---------------------------
 int run_encode(Options o)
 {
@@ -762,7 +836,7 @@ int run_encode(Options o)
     if (!((o.is_rgb && o.components == 3) || (!o.is_rgb && o.components == 1)))
         die("Incorrect parameters. Use -components 1, or -isRGB 1 -components 3 (planar R,G,B planes).");
     if (o.cp == 3 && o.k > 0) die("Incorrect parameters. -cp 3 has no complexity-scalable mode (-k must be 0).");
-    if (o.signed_or_unsigned != 0 || o.bps != 8) die("Only unsigned 8-bit samples are built in this MI355X hot-path build.");
+    if (o.signed_or_unsigned != 0 || o.bps != 8) return run_encode_deep(o, pgm);
     const long nframes = o.video ? o.frames : 1;
     if (nframes <= 0) die("Incorrect parameters. Please choose valid values. (-frames)");
     if (o.has_rate) {
@@ -1450,6 +1524,56 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
     return 0;
 }
 
+// -bps 9..16 (the stream's header says so): one grey still image through picsong_decode_images with GREY16, written as
+// the 8-bit path writes -- a P5 with maxval 2^bd - 1, its two-byte samples big-endian as Netpbm defines
+int run_decode_deep(const Options &o, const picsong_params &p, std::ifstream &in)
+{
+    deep_check_mode(o, p.is_rgb != 0, p.bit_depth);
+    if (p.cp == 3) die(std::string("-cp 3 is not built for -bps 9..16. ") + kDeepBuilt);
+    in.clear();
+    in.seekg(0, std::ios::end);
+    const size_t shorts = (size_t)in.tellg() / 2;
+    HIPCK(hipSetDevice(o.device));
+    picsong_ctx *ctx = nullptr;
+    create_decode_ctx(p, o.device, &ctx, o.drop);
+    load_lut(ctx, o, p.wl, 1, p.k, p.cp);
+    int aw, ah, ncb;
+    CK(picsong_ctx_padded_dims(ctx, &aw, &ah, &ncb));
+    const size_t max_shorts = picsong_max_stream_shorts(aw, ah), n = (size_t)p.width * (size_t)p.height;
+    if (shorts > max_shorts) die("Frame codestream longer than the maximum for this geometry.");
+    std::vector<uint16_t> stream(max_shorts, 0xFFFFu), img(n);
+    in.seekg(0);
+    in.read(reinterpret_cast<char *>(stream.data()), (std::streamsize)(shorts * 2));
+    hipStream_t s;
+    HIPCK(hipStreamCreate(&s));
+    uint16_t *d_in = nullptr, *d_pix = nullptr;
+    HIPCK(hipMalloc(&d_in, max_shorts * 2));
+    HIPCK(hipMalloc(&d_pix, n * 2));
+    auto t0 = std::chrono::steady_clock::now();
+    HIPCK(hipMemcpyAsync(d_in, stream.data(), max_shorts * 2, hipMemcpyHostToDevice, s));
+    picsong_image im;
+    im.data = d_pix; im.pitch = (size_t)p.width * 2; im.plane_stride = 0; im.layout = PICSONG_LAYOUT_GREY16;
+    CK(picsong_decode_images(ctx, 1, d_in, max_shorts, &im, 0, s));
+    HIPCK(hipMemcpyAsync(img.data(), d_pix, n * 2, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (uint16_t &v : img) v = (uint16_t)((v >> 8) | (v << 8));
+    {
+        std::ofstream f(o.output, std::ios::binary | std::ios::trunc);
+        if (!f) die("Cannot open output file " + o.output);
+        f << "P5\n" << p.width << " " << p.height << "\n" << ((1 << p.bit_depth) - 1) << "\n";
+        f.write(reinterpret_cast<const char *>(img.data()), (std::streamsize)(n * 2));
+    }
+    std::cout << "The time spent with the app without considering allocation periods and I/O is: " << sec << std::endl;
+    Options mo = o;
+    mo.x = p.width; mo.y = p.height;
+    write_metrics(mo, "decode", 1, sec, 0, 0, 0, (long)shorts);
+    picsong_ctx_destroy(ctx);
+    (void)hipStreamDestroy(s);
+    (void)hipFree(d_in); (void)hipFree(d_pix);
+    return 0;
+}
+
 int run_decode(const Options &o)
 {
     if (o.input.empty() || o.output.empty()) die("Incorrect parameters. Please choose valid values.");
@@ -1462,6 +1586,7 @@ int run_decode(const Options &o)
     CK(picsong_header_unpack(hdr, &p));
     if (!((p.components == 1 && !p.is_rgb) || (p.components == 3 && p.is_rgb)))
         die("This stream uses a component layout not built here.");
+    if (p.bit_depth != 8) return run_decode_deep(o, p, in);
     layout_check_context(o.layout, p.is_rgb != 0);
     if (o.reduce < 0 || o.reduce > p.wl - 1)
         die("Incorrect parameters. -reduce must lie in 0.." + std::to_string(p.wl - 1) + " (the stream has " +

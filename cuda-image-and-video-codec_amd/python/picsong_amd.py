@@ -29,8 +29,8 @@ class Image(C.Structure):
     _fields_ = [("data", C.c_void_p), ("pitch", C.c_size_t), ("plane_stride", C.c_size_t), ("layout", C.c_int)]
 
 
-LAYOUT_GREY8, LAYOUT_PLANAR3, LAYOUT_RGB24, LAYOUT_BGR24, LAYOUT_RGBA32, LAYOUT_BGRA32 = range(6)
-LAYOUT_BPP = (1, 1, 3, 3, 4, 4)
+LAYOUT_GREY8, LAYOUT_PLANAR3, LAYOUT_RGB24, LAYOUT_BGR24, LAYOUT_RGBA32, LAYOUT_BGRA32, LAYOUT_GREY16 = range(7)
+LAYOUT_BPP = (1, 1, 3, 3, 4, 4, 2)
 
 
 class LutInfo(C.Structure):
@@ -73,6 +73,8 @@ EXPORTS = [
     "picsong_decode_rgb_images_window",
     "picsong_encode_rgb_frames_rate", "picsong_encode_rgb_frames_quality", "picsong_train_rgb_frames",
     "picsong_ctx_set_decode_drop", "picsong_ctx_get_decode_drop", "picsong_drop_planes",
+    "picsong_depth_range_guaranteed", "picsong_pad_frame16_host", "picsong_level_shift_fwd16", "picsong_dwt_forward_u16",
+    "picsong_encode_frames16", "picsong_decode_frames16",
 ]
 
 _lib = None
@@ -218,6 +220,13 @@ def load():
         L.picsong_ctx_set_decode_drop.argtypes = [vp, i]
         L.picsong_ctx_get_decode_drop.argtypes = [vp, C.POINTER(i)]
         L.picsong_drop_planes.argtypes = [i, i, i, i, i, C.POINTER(i)]
+    if hasattr(L, "picsong_encode_frames16"):
+        L.picsong_depth_range_guaranteed.argtypes = [i, i, i, C.c_float, C.POINTER(i)]
+        L.picsong_pad_frame16_host.argtypes = [vp, i, i, vp, i, i]
+        L.picsong_level_shift_fwd16.argtypes = [vp, vp, vp, vp]
+        L.picsong_dwt_forward_u16.argtypes = [vp, vp, vp, vp]
+        L.picsong_encode_frames16.argtypes = [vp, i, vp, C.c_size_t, i, vp, C.c_size_t, vp]
+        L.picsong_decode_frames16.argtypes = [vp, i, vp, C.c_size_t, vp, C.c_size_t, vp]
     _lib = L
     return L
 
@@ -334,10 +343,27 @@ def lut_save(folder, component, info, wl, table):
     _check(load().picsong_lut_save(os.fsencode(folder), component, C.byref(info), wl, table.ctypes.data_as(C.c_void_p)))
 
 
-def make_params(width, height, wl=5, lossy=False, qs=1.0, frames=0, rgb=False, k=0.0, cp=2):
+def make_params(width, height, wl=5, lossy=False, qs=1.0, frames=0, rgb=False, k=0.0, cp=2, bit_depth=8):
     return Params(width=width, height=height, wl=wl, cp=cp, lossy=int(lossy), qs=qs, k=k,
-                  cb_width=64, cb_height=18, bit_depth=8, frames=frames, components=3 if rgb else 1,
+                  cb_width=64, cb_height=18, bit_depth=bit_depth, frames=frames, components=3 if rgb else 1,
                   is_rgb=int(rgb))
+
+
+def depth_range_guaranteed(bit_depth, lossy, wl, qs=1.0):
+    """Does every frame of `bit_depth`-bit samples keep its coefficients below the coders' 2^15
+    (picsong_depth_range_guaranteed)?  Where not, a frame that reaches it raises the range flag."""
+    yes = C.c_int()
+    _check(load().picsong_depth_range_guaranteed(bit_depth, int(lossy), wl, qs, C.byref(yes)))
+    return bool(yes.value)
+
+
+def pad_frame16(img_u16, aw, ah):
+    """picsong_pad_frame16_host: the (H, W) uint16 frame mirror-padded to (ah, aw)."""
+    img_u16 = np.ascontiguousarray(img_u16, np.uint16)
+    h, w = img_u16.shape
+    out = np.zeros((ah, aw), np.uint16)
+    _check(load().picsong_pad_frame16_host(img_u16.ctypes.data_as(C.c_void_p), w, h, out.ctypes.data_as(C.c_void_p), aw, ah))
+    return out
 
 
 def header_pack(params):
@@ -358,13 +384,14 @@ class Codec:
     objects + the LUT upload of Engine::initLUT).  All tensor arguments are torch CUDA tensors."""
 
     def __init__(self, width, height, wl=5, lossy=False, qs=1.0, lut_folder=None, lut_fill=0,
-                 device=0, frames=0, rgb=False, k=0.0, pipelined=False, cp=2):
+                 device=0, frames=0, rgb=False, k=0.0, pipelined=False, cp=2, bit_depth=8):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the picsong HIP path has no CPU fallback")
         self.torch = torch
         self.L = load()
-        self.params = make_params(width, height, wl, lossy, qs, frames, rgb, k, cp)
+        self.params = make_params(width, height, wl, lossy, qs, frames, rgb, k, cp, bit_depth)
+        self.bit_depth = bit_depth
         self.rgb = bool(rgb)
         self.device = device
         h = C.c_void_p()
@@ -424,23 +451,25 @@ class Codec:
     def image(self, t, layout, pitch=None, plane_stride=0, offset=0):
         """The picsong_image of the uint8 CUDA tensor `t` (any shape; its storage from byte `offset` on is the frame):
         rows `pitch` bytes apart (default: packed, W * bpp), PLANAR3 planes plane_stride bytes apart."""
-        assert t.dtype == self.torch.uint8 and t.is_cuda
+        assert (t.dtype == self.torch.uint8 or layout == LAYOUT_GREY16) and t.is_cuda
         pitch = self.params.width * LAYOUT_BPP[layout] if pitch is None else pitch
         return Image(data=t.data_ptr() + offset, pitch=pitch, plane_stride=plane_stride, layout=layout)
 
     def ingest_frames(self, img, n=1, frame_stride=0, out=None):
         """n frames of `img` (an Image; frame f frame_stride bytes behind frame 0) to padded planar planes on the device:
         uint8 [n, planes, AH, AW] (planes: 1 for GREY8, else R, G, B), mirror-padded as picsong_pad_frame_host pads."""
-        planes = 1 if img.layout == LAYOUT_GREY8 else 3
-        if out is None:
-            out = self.torch.empty((n, planes, self.ah, self.aw), dtype=self.torch.uint8, device=self.dev)
-        _check(self.L.picsong_ingest_frames(self.h, n, C.byref(img), frame_stride, self._p(out), out.stride(0), self._stream()))
+        planes = 1 if img.layout in (LAYOUT_GREY8, LAYOUT_GREY16) else 3
+        if out is None:                                  # (GREY16: int16 tensors holding the uint16 samples)
+            out = self.torch.empty((n, planes, self.ah, self.aw), dtype=self.torch.int16 if img.layout == LAYOUT_GREY16 else self.torch.uint8,
+                                   device=self.dev)
+        _check(self.L.picsong_ingest_frames(self.h, n, C.byref(img), frame_stride, self._p(out), out.stride(0) * out.element_size(),
+                                            self._stream()))
         return out
 
     def emit_frames(self, padded, img, n=1, frame_stride=0):
         """The inverse: uint8 [n, planes, AH, AW] padded planes cropped and interleaved into the frames of `img`."""
         assert padded.stride(-1) == 1
-        _check(self.L.picsong_emit_frames(self.h, n, self._p(padded), padded.stride(0) if padded.dim() == 4 else 0, C.byref(img),
+        _check(self.L.picsong_emit_frames(self.h, n, self._p(padded), padded.stride(0) * padded.element_size() if padded.dim() == 4 else 0, C.byref(img),
                                           frame_stride, self._stream()))
 
     def encode_images(self, img, n=1, frame_stride=0, first_iter=0):
@@ -774,6 +803,43 @@ class Codec:
         n = C.c_int()
         _check(self.L.picsong_profile_read(self.h, C.byref(n), ms.ctypes.data_as(C.c_void_p), capacity))
         return ms[:n.value]
+
+    # ---- deep contexts (bit_depth 9..16): uint16 samples, held in int16 tensors (torch's 16-bit integer type; the bits
+    # are the unsigned samples': numpy's .view(np.uint16) on the host) ----
+    def level_shift_fwd16(self, u16):
+        out = self.torch.empty(self.P, dtype=self.dtype, device=self.dev)
+        _check(self.L.picsong_level_shift_fwd16(self.h, self._p(u16), self._p(out), self._stream()))
+        return out
+
+    def dwt_forward_u16(self, u16):
+        out = self.torch.zeros(self.P + self.extra, dtype=self.dtype, device=self.dev)
+        _check(self.L.picsong_dwt_forward_u16(self.h, self._p(u16), self._p(out), self._stream()))
+        return out
+
+    def encode_frames16(self, frames_u16_padded, first_iter=0, frame_stride=None):
+        """frames_u16_padded: int16 [n, AH*AW] or [n, AH, AW] (frame f stride(0) elements behind frame 0, or frame_stride
+        BYTES where given); returns the n codestreams."""
+        n = frames_u16_padded.shape[0]
+        assert frames_u16_padded.element_size() == 2 and frames_u16_padded.stride(-1) == 1
+        if frame_stride is None:
+            frame_stride = 2 * frames_u16_padded.stride(0)
+        out = self.torch.empty((n, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        _check(self.L.picsong_encode_frames16(self.h, n, self._p(frames_u16_padded), frame_stride, first_iter, self._p(out),
+                                              out.stride(0), self._stream()))
+        return [out[k, :t] for k, t in enumerate(self.last_totals(n))]
+
+    def decode_frames16(self, streams, out=None, frame_stride=None):
+        """streams: int16 [n, >= max_stream_shorts()]; returns int16 [n, AH, AW] holding the uint16 samples (or writes frame
+        f frame_stride BYTES behind `out`)."""
+        n = streams.shape[0]
+        assert streams.stride(-1) == 1
+        if out is None:
+            out = self.torch.empty((n, self.ah, self.aw), dtype=self.torch.int16, device=self.dev)
+        if frame_stride is None:
+            frame_stride = 2 * out.stride(0)
+        _check(self.L.picsong_decode_frames16(self.h, n, self._p(streams), streams.stride(0), self._p(out), frame_stride,
+                                              self._stream()))
+        return out
 
     # ---- whole frame (asynchronous; last_total() synchronises) ----
     def encode_frame_async(self, frame_u8_padded, out_stream, iter_=0):

@@ -582,6 +582,7 @@ int picsong_train_rgb_frames(picsong_ctx *ctx, int n, const uint8_t *d_r, const 
 #define PICSONG_LAYOUT_BGR24   3
 #define PICSONG_LAYOUT_RGBA32  4   /* A ignored on input, 255 on output */
 #define PICSONG_LAYOUT_BGRA32  5
+#define PICSONG_LAYOUT_GREY16  6   /* 2 bytes a pixel, little-endian; deep contexts */
 typedef struct picsong_image { void *data; size_t pitch; size_t plane_stride; int layout; } picsong_image;
 int picsong_ingest_frames(picsong_ctx *ctx, int n, const picsong_image *src, size_t frame_stride, uint8_t *d_padded,
                           size_t padded_stride, void *stream);
@@ -595,6 +596,57 @@ int picsong_encode_rgb_image(picsong_ctx *ctx, const picsong_image *src, int hea
                              size_t stream_stride, void *stream);
 int picsong_decode_rgb_image(picsong_ctx *ctx, const uint16_t *d_streams, size_t stream_stride, const picsong_image *dst,
                              void *stream);
+
+/* ---- deep contexts: 9- to 16-bit grey samples (cinema, broadcast, medical, remote sensing).  A context created with
+ *      bit_depth 9..16 (components 1, is_rgb 0; an RGB one is refused) takes its frames as native (little-endian)
+ *      uint16_t samples v in [0, 2^bd - 1]; off = 2^(bd-1).  Only the transform's two ends differ from an 8-bit context:
+ *        forward   5/3: x = (int32)v - off;  9/7: x = (float)v - (float)off (offsetImage with the depth as a parameter).
+ *                  v is read UNSIGNED (65535 is never -1); a v above 2^bd - 1 is the caller's error: coded as it is,
+ *                  decoded clamped.
+ *        inverse   5/3: clamp(x + off, 0, 2^bd - 1);  9/7: clamp(rintf((x + off) + 0.01f), 0, 2^bd - 1), NaN -> 0: the
+ *                  8-bit arithmetic with 255 replaced by 2^bd - 1 (the reference hard-codes 255: this is the extension).
+ *        padding   the mirror rule of picsong_pad_frame_host on 2-byte samples (picsong_pad_frame16_host).
+ *        header    both depth fields carry bd; nothing else changes: a deep stream has the 8-bit stream's layout.
+ *      Between the ends a deep context ALWAYS has the 32-bit coefficient form, one launch a level, no fused head or
+ *      tail (the int16 form where the bound allows it, and fused deep ends, are follow-ups: DESIGN.md 4.17).
+ *      Range: the coders code magnitudes below 2^15.  picsong_depth_range_guaranteed (host only, no context) says
+ *      whether EVERY frame of that depth stays below: *yes = the bound the 16-bit coefficient form uses, with
+ *      max|sample| = 2^(bd-1) -- for 5/3 that is bd <= 12 (2048 x 2.8601^2 + 64 < 30000); for 9/7 it depends on qs and
+ *      wl.  Where it says no, the calls do not refuse: a frame whose coefficients reach 2^15 raises picsong_range_flag,
+ *      exactly as an out-of-range array through picsong_bpc_encode does (full-range 16-bit noise through 5/3 reaches
+ *      |c| ~ 10^5; smooth 14-bit content stays below 10^4).
+ *      Work unchanged on a deep context (they take T arrays): picsong_dwt_forward, picsong_dwt_inverse,
+ *      picsong_bpc_encode / _decode (_component), picsong_bitstream_pack / _unpack, picsong_train_coeffs,
+ *      picsong_last_total(s), picsong_copy_last_totals, picsong_range_flag; picsong_level_shift_inv clamps to 2^bd - 1
+ *      there; picsong_ctx_set_decode_drop stays allowed (its effect is the coder's).
+ *      Refused on a deep context (PICSONG_ERR_ARG, nothing launched, outputs untouched): every call that takes or
+ *      returns uint8_t frames -- picsong_encode_frame(s), picsong_decode_frame(s) and their _reduced / _window forms,
+ *      the stripe and band calls on frames, picsong_train_frames, the rate and quality calls, picsong_frames_sse,
+ *      picsong_level_shift_fwd, picsong_dwt_forward_u8, picsong_rgb_forward / _inverse -- and the 8-bit layouts in the
+ *      layout and image calls.  Refused on an 8-bit context: the three *16 device calls below and GREY16.
+ *      picsong_level_shift_fwd16: the level shift alone, uint16[P] -> T[P] (2-byte aligned d_in).
+ *      picsong_dwt_forward_u16: the mirror of picsong_dwt_forward_u8 -- level shift in level 0's load stage.
+ *      picsong_encode_frames16 / picsong_decode_frames16: n = 1..64 frames, ONE launch per stage (grid.z = frame).
+ *        Frame f is a padded uint16[AW*AH] at (char *)d_frames + f * frame_stride; frame_stride in BYTES, even,
+ *        >= 2 P, ignored for n = 1.  Streams, headers (first_iter), lengths and -cp 2 with any -k as
+ *        picsong_encode_frames / picsong_decode_frames; -cp 3 is refused.  Pointers need 2-byte alignment.  16-byte
+ *        aligned pointers and strides take the vector kernels (one 8-byte load / store of a lane's four samples);
+ *        anything else the per-column kernels (encode) or a separate clamp pass (decode): the same bytes.  Decoding
+ *        writes exactly the 2 P bytes of each frame.  PICSONG_DEEP_NOFUSE=1 (read per call) takes the element-wise
+ *        level shift / clamp passes beside the T-input level 0 / T-output finest level instead: the same bytes.
+ *      GREY16 in picsong_ingest_frames / picsong_emit_frames: the padded side is uint16 planes, passed through the
+ *        uint8_t * parameter, padded_stride in bytes (>= 2 P); pitch >= 2 W; data, pitch and the strides need 2-byte
+ *        alignment (refused otherwise); no byte outside [y * pitch, y * pitch + 2 W) of rows 0 .. H - 1 is read or
+ *        written.  picsong_encode_images / picsong_decode_images accept GREY16 on deep contexts, byte-identical to the
+ *        *16 frame calls on host-padded frames. ---- */
+int picsong_depth_range_guaranteed(int bit_depth, int lossy, int wl, float qs, int *yes);              /* host only */
+int picsong_pad_frame16_host(const uint16_t *in, int w, int h, uint16_t *out, int aw, int ah);         /* host only */
+int picsong_level_shift_fwd16(picsong_ctx *ctx, const uint16_t *d_in, void *d_out, void *stream);
+int picsong_dwt_forward_u16(picsong_ctx *ctx, const uint16_t *d_in, void *d_out, void *stream);
+int picsong_encode_frames16(picsong_ctx *ctx, int n, const uint16_t *d_frames, size_t frame_stride, int first_iter,
+                            uint16_t *d_streams, size_t stream_stride, void *stream);
+int picsong_decode_frames16(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride,
+                            uint16_t *d_frames_out, size_t frame_stride, void *stream);
 
 /* ---- batched RGB frames: n = 1..21 colour frames through ONE launch per stage (3 n <= 64, the batched grid's limit).
  *      Every stage launches once over 3 n planes: plane z is component z % 3 of frame z / 3, component c codes with
