@@ -337,6 +337,23 @@ inline SseLaunch select_sse(const SseArgs &s)
     const unsigned wgs = (unsigned)(tiles > kSseMaxWgs ? kSseMaxWgs : (tiles < 1 ? 1 : tiles));
     return { vec ? sse_kernel<true> : sse_kernel<false>, wgs };
 }
+// ---- the structural measure (ssim_kernel, quality_kernels.hpp) over sse_args' arguments (w, h >= 8: the callers
+// refuse less): 256 threads, a tile of four (strip, band) wave items a workgroup and step, grid-stride beyond kSseMaxWgs.
+// The dword form where both sides' pointers, pitches and strides are 4-byte aligned, else the per-byte one.
+inline bool ssim_geometry_ok(int w, int h) { return w >= 8 && h >= 8; }
+inline unsigned long long ssim_windows(int w, int h)
+{
+    return (unsigned long long)((w - 8) / 4 + 1) * (unsigned long long)((h - 8) / 4 + 1);
+}
+inline SseLaunch select_ssim(const SseArgs &s)
+{
+    const bool vec = ((((uintptr_t)s.a) | ((uintptr_t)s.b) | s.a_z | s.b_z | s.a_pitch | s.b_pitch) & 3u) == 0;
+    const size_t nx = (size_t)((s.W - 8) / 4 + 1), ny = (size_t)((s.H - 8) / 4 + 1);
+    const size_t items = ((nx + kSsimStripWindows - 1) / kSsimStripWindows) * ((ny + kSsimBandWindows - 1) / kSsimBandWindows);
+    const size_t tiles = (items + 3) / 4 * (size_t)s.n;
+    const unsigned wgs = (unsigned)(tiles > kSseMaxWgs ? kSseMaxWgs : (tiles < 1 ? 1 : tiles));
+    return { vec ? ssim_kernel<true> : ssim_kernel<false>, wgs };
+}
 // ---- the tail of an RGB quality probe (rgb_sse_kernel, quality_kernels.hpp): the inverse ICT of n frames' float
 // component planes (plane 3 f + k at c + (3 f + k) * c_z bytes, row pitch c_pitch floats) and the SSE of the visible
 // w x h samples against the input planes (frame f's in_z bytes after r / g / b, row pitch in_pitch) in one launch,

@@ -480,6 +480,17 @@ int frames_sse(const Go &go, const uint8_t *a, size_t a_pitch, unsigned long lon
     const SseArgs s = sse_args(a, a_pitch, a_z, b, b_pitch, b_z, w, h, n, out);
     return go(select_sse(s).kernel, dim3(select_sse(s).wgs), 256u, s);
 }
+// ---- structural distortion (ssim_kernel, quality_kernels.hpp): out[0 .. n) = the DSSIM sum (windows * 2^24 - the sum
+// of the windows' q: the kernel adds 2^24 - q a window, no conversion on the host) over the visible w x h samples,
+// w, h >= 8, of n pairs of padded arrays, zeroed on the launcher's stream first
+template <class Go>
+int frames_dssim(const Go &go, const uint8_t *a, size_t a_pitch, unsigned long long a_z, const uint8_t *b, size_t b_pitch,
+                 unsigned long long b_z, int w, int h, int n, unsigned long long *out)
+{
+    if (int rc = go(sse_zero_kernel, dim3(1), 64u, out, n)) return rc;
+    const SseArgs s = sse_args(a, a_pitch, a_z, b, b_pitch, b_z, w, h, n, out);
+    return go(select_ssim(s).kernel, dim3(select_ssim(s).wgs), 256u, s);
+}
 
 // ---- pixel layouts (layout_kernels.hpp): n frames of W x H pixels at a pitch into padded planar planes, and back.  The
 // arguments have passed layout_refusal.  *vec: the vector form ran
@@ -533,6 +544,8 @@ int decode_rgb_images_reduced(const Go &go, const DecodeCtx &c, const BpcArgs &a
 //   or, where select_rgb_sse refuses (the float planes not 16-byte aligned, rgb_sse_fused = false: the library's
 //   PICSONG_RGB_SSE_FUSED=0), the unfused tail: per frame the inverse ICT kernel writes R, G, B into pix (3 P bytes a
 //   frame), each compared with its input plane by frames_sse.
+// ssim (the SSIM calls, picsong_encode_frame_ssim and its mirrors): frames_dssim for frames_sse, out = DSSIM sums; an RGB
+// probe takes the unfused tail whatever rgb_sse_fused says.
 struct QualityProbe {
     const void *unit; unsigned long long unit_z;
     int32_t *coef_i; void *work; uint8_t *pix;
@@ -542,6 +555,7 @@ struct QualityProbe {
     const uint8_t *frames; size_t frame_stride;
     const uint8_t *r, *g, *b;
     bool rgb_sse_fused = true;
+    bool ssim = false;              // the SSIM calls: out = DSSIM sums (frames_dssim); RGB on the unfused tail
 };
 // mark(k): called after the quantise pass (1), after the synthesis' last launch (2) and after the SSE (3) -- the
 // library's stage timers; returns 0.  (RGB: the colour transform is in stage 2 on the unfused tail, in stage 3 on the
@@ -562,7 +576,7 @@ inline RgbSseLaunch quality_probe_rgb_sse(const QualityProbe &p, const std::vect
     const RgbSseArgs s = rgb_sse_args(plan.back().a.dst, (unsigned long long)(p.P + p.extra) * 4ull, (size_t)p.aw, p.r, p.g, p.b,
                                       (unsigned long long)p.frame_stride, (size_t)p.aw, p.w, p.h, p.nf / 3, p.off, out);
     if (args) *args = s;
-    return select_rgb_sse(s, p.rgb_sse_fused);
+    return select_rgb_sse(s, p.rgb_sse_fused && !p.ssim);
 }
 // does an RGB probe over these buffers take the fused tail?  (else it needs p.pix: 3 P bytes a frame)
 inline bool quality_probe_fuses(const QualityProbe &p)
@@ -602,7 +616,8 @@ int quality_probe(const Go &go, const QualityProbe &p, int j, unsigned long long
             const size_t at = n > 1 ? (size_t)f * p.frame_stride : 0;
             const uint8_t *in[3] = { p.r + at, p.g + at, p.b + at };
             for (int k = 0; k < 3; k++)
-                if (int rc = frames_sse(go, p.pix + (size_t)(3 * f + k) * p.P, (size_t)p.aw, 0, in[k], (size_t)p.aw, 0, p.w, p.h, 1, out + 3 * f + k)) return rc;
+                if (int rc = p.ssim ? frames_dssim(go, p.pix + (size_t)(3 * f + k) * p.P, (size_t)p.aw, 0, in[k], (size_t)p.aw, 0, p.w, p.h, 1, out + 3 * f + k)
+                                    : frames_sse(go, p.pix + (size_t)(3 * f + k) * p.P, (size_t)p.aw, 0, in[k], (size_t)p.aw, 0, p.w, p.h, 1, out + 3 * f + k)) return rc;
         }
         return mark(3);
     }
@@ -610,6 +625,11 @@ int quality_probe(const Go &go, const QualityProbe &p, int j, unsigned long long
         for (int f = 0; f < p.nf; f++)
             if (int rc = clamp_pixels(go, true, img + (size_t)f * z, p.pix + (size_t)f * p.P, p.P / 4, p.off)) return rc;
     if (int rc = mark(2)) return rc;
+    if (p.ssim) {
+        if (int rc = frames_dssim(go, p.pix, (size_t)p.aw, (unsigned long long)p.P, p.frames, (size_t)p.aw, (unsigned long long)p.frame_stride,
+                                  p.w, p.h, p.nf, out)) return rc;
+        return mark(3);
+    }
     if (int rc = frames_sse(go, p.pix, (size_t)p.aw, (unsigned long long)p.P, p.frames, (size_t)p.aw, (unsigned long long)p.frame_stride,
                             p.w, p.h, p.nf, out)) return rc;
     return mark(3);

@@ -1520,6 +1520,8 @@ static int rgb_forward_transform(picsong_ctx *c, const uint8_t *d_r, const uint8
 // RGB: nf = 3 n planes, plane 3 f + k component k of frame f.  The single-frame calls (n = 1) keep one candidate a
 // size round; the n-frame calls (RateJob::multi) take rgb_search_candidates (rate_search.hpp).
 // PICSONG_RGB_SSE_FUSED=0, read per call, keeps the RGB probe's unfused tail (rgb_inverse + frames_sse).
+// The SSIM calls (kSearchSsim) are quality searches whose probe ends in ssim_kernel (frames_dssim) and whose figures are
+// DSSIM sums; an RGB probe of theirs always takes the unfused tail.
 // ---------------------------------------------------------------------------------------------
 struct RateJob {
     int n;                                  // frames (RGB: three components each)
@@ -1531,7 +1533,7 @@ struct RateJob {
     bool multi = false;                     // the n-frame RGB calls (picsong_encode_rgb_frames_rate / _quality)
 };
 
-enum SearchKind { kSearchSize, kSearchQuality };
+enum SearchKind { kSearchSize, kSearchQuality, kSearchSsim };   // (kSearchSsim: a quality search whose measure is the DSSIM sum)
 
 static int search_candidates(const picsong_ctx *c, SearchKind kind, const RateJob &job)
 {
@@ -1685,9 +1687,10 @@ static int search_impl(picsong_ctx *c, const RateJob &job, SearchKind kind, uint
                        int *h_j, int *h_totals, uint64_t *h_sse, const char *who)
 {
     // (search_args_ok has made the null, context-kind, stride and alignment checks)
-    const bool size = kind == kSearchSize;
+    const bool size = kind == kSearchSize, ssim = kind == kSearchSsim;
     if (!c->p.lossy) return fail(PICSONG_ERR_ARG, "%s: a lossless context has no quantiser to search", who);
-    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 3 contexts have no %s control", who, size ? "rate" : "quality");
+    if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 3 contexts have no %s control", who, size ? "rate" : (ssim ? "SSIM" : "quality"));
+    if (ssim && !ssim_geometry_ok(c->p.width, c->p.height)) return fail(PICSONG_ERR_ARG, "%s: the SSIM's 8 x 8 windows need a frame of 8 x 8 or more", who);
     if (size && limit == 0) return fail(PICSONG_ERR_ARG, "%s: target_shorts must be positive", who);
     if (!rate_range_ok(j_min, j_max))
         return fail(PICSONG_ERR_ARG, "%s: range [%d, %d] is neither 0, 0 (the whole grid) nor inside 1..%d", who, j_min, j_max, kRateJMax);
@@ -1707,7 +1710,7 @@ static int search_impl(picsong_ctx *c, const RateJob &job, SearchKind kind, uint
     const char *const fe = getenv("PICSONG_RGB_SSE_FUSED");
     QualityProbe probe = { c->rate_coef, (unsigned long long)c->rate_z, c->batch.coef_i, c->batch.coef, nullptr,
                            c->aw, c->ah, c->p.wl, c->p.width, c->p.height, level_off(c), c->P, c->extra, nf,
-                           job.frames, job.frame_stride, job.r, job.g, job.b, !(fe && atoi(fe) == 0) };
+                           job.frames, job.frame_stride, job.r, job.g, job.b, !(fe && atoi(fe) == 0), ssim };
     if (!size) {
         if ((rc = ensure_quality(c, quality_probe_fuses(probe) ? 0 : nf))) return rc;
         probe.pix = c->q_pix;
@@ -1755,7 +1758,8 @@ static int search_impl(picsong_ctx *c, const RateJob &job, SearchKind kind, uint
     *h_j = 0;
     if (w.result < 0)
         return size ? fail(PICSONG_ERR_RATE, "%s: no quantiser of the search range meets %llu shorts", who, (unsigned long long)limit)
-                    : fail(PICSONG_ERR_QUALITY, "%s: no quantiser of the search range meets an SSE of %llu", who, (unsigned long long)limit);
+                    : fail(PICSONG_ERR_QUALITY, "%s: no quantiser of the search range meets %s of %llu", who, ssim ? "a DSSIM sum" : "an SSE",
+                           (unsigned long long)limit);
     const int j = grid[(size_t)w.result];
     // ---- the winner's staging: candidate `slot` of a size search's last round, or coded once more on its own
     int slot = -1;
@@ -1800,7 +1804,8 @@ static int search_args_ok(const picsong_ctx *c, const RateJob &job, SearchForm f
         return PICSONG_OK;
     }
     if (c->p.is_rgb)
-        return fail(PICSONG_ERR_ARG, "%s: grey contexts only (an RGB frame: picsong_encode_rgb_frame_%s)", who, kind == kSearchSize ? "rate" : "quality");
+        return fail(PICSONG_ERR_ARG, "%s: grey contexts only (an RGB frame: picsong_encode_rgb_%s)", who,
+                    kind == kSearchSize ? "frame_rate" : (kind == kSearchSsim ? "frames_ssim" : "frame_quality"));
     if (job.n > 1 && (job.frame_stride < c->P || job.stream_stride < max_shorts))
         return fail(PICSONG_ERR_ARG, "%s: strides smaller than a padded frame / a worst-case codestream", who);
     if (form == kFrames && (((uintptr_t)job.frames | job.frame_stride) & 15u)) return fail(PICSONG_ERR_ARG, "%s: frames must be 16-byte aligned", who);
@@ -1887,6 +1892,77 @@ int picsong_encode_rgb_frames_quality(picsong_ctx *c, int n, const uint8_t *d_r,
     job.multi = true;
     if (int rc = search_args_ok(c, job, kRgbFrames, kSearchQuality, h_j && h_totals && h_sse, who)) return rc;
     return search_impl(c, job, kSearchQuality, max_sse, j_min, j_max, (hipStream_t)stream, h_j, h_totals, h_sse, who);
+}
+
+// ---- the SSIM calls: the quality calls with the DSSIM sum (ssim_kernel, quality_kernels.hpp) for the SSE.  The probe
+// is quality_probe's with frames_dssim as its last step; an RGB probe takes the unfused tail (rgb_inverse into q_pix).
+int picsong_ssim_windows(int w, int h, uint64_t *windows)
+{
+    if (!windows) return fail(PICSONG_ERR_ARG, "ssim_windows: null argument");
+    if (!ssim_geometry_ok(w, h)) return fail(PICSONG_ERR_ARG, "ssim_windows: %d x %d is below the 8 x 8 of a window", w, h);
+    *windows = ssim_windows(w, h);
+    return PICSONG_OK;
+}
+
+int picsong_ssim_to_dssim(double ssim, uint64_t windows, uint64_t *max_dssim)
+{
+    if (!max_dssim) return fail(PICSONG_ERR_ARG, "ssim_to_dssim: null argument");
+    if (windows == 0) return fail(PICSONG_ERR_ARG, "ssim_to_dssim: no windows");
+    if (!(ssim >= -1.0 && ssim <= 1.0)) return fail(PICSONG_ERR_ARG, "ssim_to_dssim: the SSIM must lie in [-1, 1]");
+    const double v = std::floor(((1.0 - ssim) * (double)windows) * 16777216.0);
+    *max_dssim = v >= 18446744073709551615.0 ? UINT64_MAX : (uint64_t)v;
+    return PICSONG_OK;
+}
+
+int picsong_dssim_to_ssim(uint64_t dssim, uint64_t windows, double *ssim)
+{
+    if (!ssim) return fail(PICSONG_ERR_ARG, "dssim_to_ssim: null argument");
+    if (windows == 0) return fail(PICSONG_ERR_ARG, "dssim_to_ssim: no windows");
+    *ssim = 1.0 - (double)dssim / ((double)windows * 16777216.0);
+    return PICSONG_OK;
+}
+
+int picsong_frames_dssim(picsong_ctx *c, int n, const uint8_t *d_a, size_t a_stride, const uint8_t *d_b, size_t b_stride,
+                         uint64_t *d_dssim, void *stream)
+{
+    REFUSE_DEEP(c, "frames_dssim");
+    if (!c || !d_a || !d_b || !d_dssim) return fail(PICSONG_ERR_ARG, "frames_dssim: null argument");
+    if (n < 1 || n > kSseMaxFrames) return fail(PICSONG_ERR_ARG, "frames_dssim: %d frames outside 1..%d", n, kSseMaxFrames);
+    if (n > 1 && (a_stride < c->P || b_stride < c->P)) return fail(PICSONG_ERR_ARG, "frames_dssim: strides smaller than a padded frame");
+    if (!ssim_geometry_ok(c->p.width, c->p.height)) return fail(PICSONG_ERR_ARG, "frames_dssim: the SSIM's 8 x 8 windows need a frame of 8 x 8 or more");
+    HIP_TRY(hipSetDevice(c->device));
+    return frames_dssim(HipGo{ (hipStream_t)stream }, d_a, (size_t)c->aw, n > 1 ? a_stride : 0, d_b, (size_t)c->aw, n > 1 ? b_stride : 0,
+                        c->p.width, c->p.height, n, reinterpret_cast<unsigned long long *>(d_dssim));
+}
+
+int picsong_encode_frames_ssim(picsong_ctx *c, int n, const uint8_t *d_frames, size_t frame_stride, int first_iter,
+                               uint64_t max_dssim, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
+                               void *stream, int *h_j, int *h_totals, uint64_t *h_dssim)
+{
+    const char *who = "encode_frames_ssim";
+    const RateJob job = { n, d_frames, frame_stride, nullptr, nullptr, nullptr, first_iter, 0, d_streams, stream_stride, false };
+    if (int rc = search_args_ok(c, job, kFrames, kSearchSsim, h_j && h_totals && h_dssim, who)) return rc;
+    return search_impl(c, job, kSearchSsim, max_dssim, j_min, j_max, (hipStream_t)stream, h_j, h_totals, h_dssim, who);
+}
+
+int picsong_encode_frame_ssim(picsong_ctx *c, const uint8_t *d_frame, int iter, uint64_t max_dssim, int j_min, int j_max,
+                              uint16_t *d_stream, void *stream, int *h_j, int *h_total, uint64_t *h_dssim)
+{
+    const char *who = "encode_frame_ssim";
+    const RateJob job = { 1, d_frame, 0, nullptr, nullptr, nullptr, iter == 0 ? 0 : 1, 0, d_stream, 0, true };
+    if (int rc = search_args_ok(c, job, kOneFrame, kSearchSsim, h_j && h_total && h_dssim, who)) return rc;
+    return search_impl(c, job, kSearchSsim, max_dssim, j_min, j_max, (hipStream_t)stream, h_j, h_total, h_dssim, who);
+}
+
+int picsong_encode_rgb_frames_ssim(picsong_ctx *c, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, size_t frame_stride,
+                                   int first_iter, int header_mask, uint64_t max_dssim, int j_min, int j_max, uint16_t *d_streams,
+                                   size_t stream_stride, void *stream, int *h_j, int *h_totals, uint64_t *h_dssim)
+{
+    const char *who = "encode_rgb_frames_ssim";
+    RateJob job = { n, nullptr, n > 1 ? frame_stride : 0, d_r, d_g, d_b, first_iter, header_mask, d_streams, stream_stride, false };
+    job.multi = true;
+    if (int rc = search_args_ok(c, job, kRgbFrames, kSearchSsim, h_j && h_totals && h_dssim, who)) return rc;
+    return search_impl(c, job, kSearchSsim, max_dssim, j_min, j_max, (hipStream_t)stream, h_j, h_totals, h_dssim, who);
 }
 
 // ---------------------------------------------------------------------------------------------

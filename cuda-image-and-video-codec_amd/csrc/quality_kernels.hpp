@@ -29,6 +29,9 @@
 // of frame f.  The pixel arithmetic is rgb_inverse_kernel<float>'s, bit for bit; the squares are sse_kernel's identity
 // over the packed clamped pixels (3 v_lshl_or + 3 v_dot4 per four samples and channel against 4 byte extracts, 4
 // subtracts and 4 multiply-adds unpacked); the shape is sse_kernel's with groups of four pixels for its vectors.
+//
+// ssim_kernel (at the end of this file, with its definition): the structural measure of the SSIM calls
+// (picsong_frames_dssim, picsong_encode_frame_ssim and its mirrors) -- x264's integer 8 x 8 SSIM as a DSSIM sum.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -270,6 +273,127 @@ __global__ __launch_bounds__(256) void rgb_sse_kernel(RgbSseArgs s)
             }
             i += 256u; y += step_rows; g += step_groups;
             if (g >= gpr) { g -= gpr; y++; }
+        }
+    }
+}
+
+// ---- structural similarity of n pairs of u8 frames (picsong_frames_dssim, the -ssim search calls' probes)
+// The measure is x264 / ffmpeg's integer 8 x 8 SSIM over the VISIBLE W x H samples (W, H >= 8): windows of 8 x 8 samples
+// at the origins (4 x, 4 y), x < nx = (W - 8) / 4 + 1, y < ny = (H - 8) / 4 + 1; a window's exact integer sums
+//   s1 = sum a, s2 = sum b, ss = sum a^2 + sum b^2, s12 = sum a b      (64 samples)
+// give, with c1 = 416 and c2 = 235963,
+//   A = 2 s1 s2 + c1, B = 2 (64 s12 - s1 s2) + c2, C = s1^2 + s2^2 + c1, E = 64 ss - s1^2 - s2^2 + c2   (each below 2^30)
+//   v = ((double)A * (double)B) / ((double)C * (double)E)   -- three IEEE double operations, a true division, and no
+//   addition a product could contract into;  q = (int64)floor(v * 2^24) <= 2^24, negative for anti-correlated content.
+// out[f] += sum over frame f's windows of (2^24 - q): the DSSIM sum nx ny 2^24 - sum q, formed HERE window by window so
+// that every partial sum is a non-negative integer -- exact, and the same whatever order the atomics land in.
+//
+// Shape: a window is four 4 x 4 blocks.  A lane owns a block COLUMN: per sample row one dword of each image, the block's
+// four sums accumulated by five v_dot4_u32_u8 a row (sum a and sum b as dots with 0x01010101) -- each image byte is
+// loaded once but for the overlaps below, the traffic of sse_kernel.  After a block row the lane adds its LEFT
+// neighbour's block (wave_shr:1) for the pair sums of the window whose right half it owns; the previous block row's pair
+// sums stay in registers as the band streams down, so a window is pair(y) + pair(y + 1).  A wave takes a strip of 64
+// block columns = kSsimStripWindows = 63 window columns (lane 0's window would need the block left of the strip: strips
+// overlap by one block column) over a band of kSsimBandWindows window rows (kSsimBandWindows + 1 block rows: bands overlap
+// by one block row).  Window (x, y) is counted by the one strip with x / 63 and the one band with y / 16: exactly once.
+// Every block a window uses lies inside the visible part (4 (nx + 1) <= W): nothing is masked; the columns from
+// 4 (nx + 1) and the rows from 4 (ny + 1) on belong to no window and are not read.
+// The (strip, band) items of a frame are dealt four a tile to a workgroup's four waves, tiles grid-stride over all frames
+// as sse_kernel's: a workgroup's frame only grows, and it makes ONE 64-bit atomic add per frame it touched.
+//
+// VEC: both pointers, pitches and strides 4-byte aligned: dword loads.  Else the per-byte form: the same items, a
+// block row's four bytes loaded one by one, the same arithmetic.
+constexpr int kSsimStripWindows = 63;       // window columns a wave
+constexpr int kSsimBandWindows = 16;        // window rows a wave item
+constexpr int kSsimC1 = 416, kSsimC2 = 235963;
+
+// 2^24 - q of a window with the sums s1, s2, ss, s12
+__device__ __forceinline__ unsigned long long ssim_window_d(uint32_t s1, uint32_t s2, uint32_t ss, uint32_t s12)
+{
+    const int p12 = (int)(s1 * s2), sq = (int)(s1 * s1 + s2 * s2);         // <= 2 * 16320^2 < 2^30
+    const int vars = (int)(64u * ss) - sq, cov = (int)(64u * s12) - p12;
+    const double num = (double)(2 * p12 + kSsimC1) * (double)(2 * cov + kSsimC2);
+    const double den = (double)(sq + kSsimC1) * (double)(vars + kSsimC2);
+    const double v = num / den;
+    const long long q = (long long)floor(v * 16777216.0);
+    return (unsigned long long)(16777216ll - q);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void ssim_kernel(SseArgs s)
+{
+    __shared__ unsigned long long wave_sum[4];
+    const uint32_t nx = ((uint32_t)s.W - 8u) / 4u + 1u, ny = ((uint32_t)s.H - 8u) / 4u + 1u;
+    const uint32_t strips = (nx + (uint32_t)kSsimStripWindows - 1u) / (uint32_t)kSsimStripWindows;
+    const uint32_t bands = (ny + (uint32_t)kSsimBandWindows - 1u) / (uint32_t)kSsimBandWindows;
+    const uint32_t ipf = strips * bands;                                    // wave items a frame
+    const uint32_t tpf = (ipf + 3u) / 4u, tiles = tpf * (uint32_t)s.n;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+
+    unsigned long long sum = 0ull;
+    uint32_t cur = tiles ? blockIdx.x / tpf : 0u;                           // the frame `sum` belongs to (workgroup-uniform)
+
+    for (uint32_t t = blockIdx.x; ; t += gridDim.x) {
+        const bool more = t < tiles;
+        const uint32_t f = more ? t / tpf : cur + 1u;
+        if (f != cur) {
+            // ---- frame `cur` is done here: the waves reduce, the workgroup adds once
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
+            if (lane == 0u) wave_sum[wave] = sum;
+            __syncthreads();
+            if (threadIdx.x == 0u) {
+                const unsigned long long v = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+                if (v) (void)__hip_atomic_fetch_add(&s.out[cur], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __syncthreads();
+            sum = 0ull;
+            cur = f;
+        }
+        if (!more) break;
+        const uint32_t i = (t - f * tpf) * 4u + wave;                       // (wave-uniform)
+        if (i >= ipf) continue;
+        const uint32_t band = i / strips, strip = i - band * strips;
+        const uint32_t bx = strip * (uint32_t)kSsimStripWindows + lane;     // the lane's block column
+        const bool have = bx <= nx;                                         // block columns 0 .. nx carry windows
+        const bool win = have && lane != 0u;                                // window bx - 1: the left block is lane - 1's
+        const uint32_t by0 = band * (uint32_t)kSsimBandWindows;             // block rows by0 .. by1
+        const uint32_t by1 = by0 + (uint32_t)kSsimBandWindows < ny ? by0 + (uint32_t)kSsimBandWindows : ny;
+        const uint8_t *pa = s.a + (unsigned long long)f * s.a_z + (size_t)(4u * by0) * s.a_pitch + 4u * (size_t)bx;
+        const uint8_t *pb = s.b + (unsigned long long)f * s.b_z + (size_t)(4u * by0) * s.b_pitch + 4u * (size_t)bx;
+        uint32_t u1 = 0u, u2 = 0u, uss = 0u, u12 = 0u;                      // the pair sums of the block row above
+        for (uint32_t by = by0; by <= by1; by++) {
+            uint32_t b1 = 0u, b2 = 0u, bss = 0u, b12 = 0u;                  // the lane's block
+            if (have) {
+                uint32_t wa[4], wb[4];
+#pragma unroll
+                for (uint32_t r = 0; r < 4u; r++) {
+                    const uint8_t *const ra = pa + (size_t)r * s.a_pitch, *const rb = pb + (size_t)r * s.b_pitch;
+                    if (VEC) {
+                        wa[r] = *reinterpret_cast<const uint32_t *>(ra);
+                        wb[r] = *reinterpret_cast<const uint32_t *>(rb);
+                    } else {
+                        wa[r] = (uint32_t)ra[0] | (uint32_t)ra[1] << 8 | (uint32_t)ra[2] << 16 | (uint32_t)ra[3] << 24;
+                        wb[r] = (uint32_t)rb[0] | (uint32_t)rb[1] << 8 | (uint32_t)rb[2] << 16 | (uint32_t)rb[3] << 24;
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    b1 = dot4_u8(wa[r], 0x01010101u, b1);
+                    b2 = dot4_u8(wb[r], 0x01010101u, b2);
+                    bss = dot4_u8(wa[r], wa[r], bss);
+                    bss = dot4_u8(wb[r], wb[r], bss);
+                    b12 = dot4_u8(wa[r], wb[r], b12);
+                }
+            }
+            // the pair (bx - 1, bx) of this block row (wave_shr:1; lane 0 reads 0 and has no window)
+            const uint32_t h1 = b1 + __builtin_amdgcn_update_dpp(0u, b1, 0x138, 0xf, 0xf, true);
+            const uint32_t h2 = b2 + __builtin_amdgcn_update_dpp(0u, b2, 0x138, 0xf, 0xf, true);
+            const uint32_t hss = bss + __builtin_amdgcn_update_dpp(0u, bss, 0x138, 0xf, 0xf, true);
+            const uint32_t h12 = b12 + __builtin_amdgcn_update_dpp(0u, b12, 0x138, 0xf, 0xf, true);
+            if (win && by != by0) sum += ssim_window_d(u1 + h1, u2 + h2, uss + hss, u12 + h12);   // window (bx - 1, by - 1)
+            u1 = h1; u2 = h2; uss = hss; u12 = h12;
+            pa += 4u * (size_t)s.a_pitch; pb += 4u * (size_t)s.b_pitch;
         }
     }
 }

@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <iomanip>
 #include <iostream>
 #include <mutex>
 #include <sstream>
@@ -56,6 +57,9 @@ struct Options {
     bool has_rate = false, has_qs = false;
     double psnr = 0.0;                          // -psnr <dB>: choose qs so that the searched frames decode to at least that PSNR
     bool has_psnr = false;
+    double ssim = 0.0;                          // -ssim <v>: choose qs so that the searched frames decode to at least that SSIM
+    bool has_ssim = false;
+    bool has_quality() const { return has_psnr || has_ssim; }   // a search that measures the decode: -psnr or -ssim
     int search_frames = 0;                      // -searchFrames N: the frames of a video the -rate / -psnr search runs on (0: the default)
     std::string compare;                        // -compare <raw file>: decoding, the PSNR of the output against that file
     int layout = -1;                            // -layout: the pixel layout of the raw file (PICSONG_LAYOUT_*), -1: not given
@@ -137,11 +141,16 @@ void help()
         "                     least dB (an SSE of at most floor(65025 samples / 10^(dB/10)), samples = W H frames components).  A\n"
         "                     video as with -rate: the search runs on the first min(frames, 16) frames (an RGB video: its first\n"
         "                     frame).  Not with -qs, -rate, -type 0, -cp 3 or -train\n"
-        " -searchFrames N     coding, -video 1 with -rate or -psnr: the search runs on the first min(N, frames) frames -- grey\n"
+        " -ssim <v>           coding, -type 1: choose -qs so that the SSIM (x264's integer 8 x 8 measure, windows every 4 samples)\n"
+        "                     over the searched frames is at least v, 0 < v <= 1: a DSSIM sum of at most\n"
+        "                     floor((1 - v) windows 2^24), windows = ((W - 8) / 4 + 1) ((H - 8) / 4 + 1) frames components; W and\n"
+        "                     H 8 or more.  A video as with -psnr.  Not with -qs, -rate, -psnr, -type 0, -cp 3 or -train\n"
+        " -searchFrames N     coding, -video 1 with -rate, -psnr or -ssim: the search runs on the first min(N, frames) frames -- grey\n"
         "                     N = 1..16, an RGB video N = 1..21 (one search call over the N colour frames, whose streams are\n"
         "                     the search's own output).  Without it: grey min(frames, 16), an RGB video its first frame\n"
-        " -compare <file>     decoding: after the output is written, print its PSNR and SSE against that raw (or PGM) file of the\n"
-        "                     same geometry and planar layout.  Not with -reduce or -window\n"
+        " -compare <file>     decoding: after the output is written, print its PSNR and SSE (and, from 8 x 8 samples on, its SSIM\n"
+        "                     and DSSIM sum) against that raw (or PGM) file of the same geometry and planar layout.  Not with\n"
+        "                     -reduce or -window\n"
         " -layout grey|planar|rgb|bgr|rgba|bgra\n"
         "                     the pixel layout of the raw file: the input's when coding, the output's when decoding; rows of\n"
         "                     W * bpp bytes (1, 1, 3, 3, 4, 4 bytes a pixel; planar: the R, G, B planes one after the other;\n"
@@ -203,6 +212,15 @@ Options parse(const Args &a)
         o.has_psnr = true;
         if (v.empty() || *end != '\0' || !std::isfinite(o.psnr)) die("Incorrect parameters. -psnr takes a PSNR in dB.");
         echo("-psnr", v);
+    }
+    if (a.has("-ssim")) {
+        if (o.cd != 0) die("Incorrect parameters. -ssim applies to coding (-cd 0) only.");
+        const std::string v = a.get("-ssim");
+        char *end = nullptr;
+        o.ssim = std::strtod(v.c_str(), &end);
+        o.has_ssim = true;
+        if (v.empty() || *end != '\0' || !(o.ssim > 0.0 && o.ssim <= 1.0)) die("Incorrect parameters. -ssim takes an SSIM above 0 and at most 1.");
+        echo("-ssim", v);
     }
     if (a.has("-searchFrames")) {
         if (o.cd != 0) die("Incorrect parameters. -searchFrames applies to coding (-cd 0) only.");
@@ -335,6 +353,7 @@ picsong_params make_params(const Options &o)
 
 // ---- -psnr <dB>: what the search chose and what it achieved (the two console lines; --metrics carries them too)
 struct QualityReport { bool reported = false; int j = 0; float qs = 0; uint64_t max_sse = 0, sse = 0, samples = 0; long frames = 0; double psnr = 0; } g_quality;
+struct SsimReport { bool reported = false; int j = 0; float qs = 0; uint64_t max_dssim = 0, dssim = 0, windows = 0; long frames = 0; double ssim = 0; } g_ssim;
 long g_frames_searched = 0;             // the frames a -rate / -psnr search ran on (--metrics: "search_frames")
 
 void write_metrics(const Options &o, const char *mode, long frames, double seconds, double dwt, double bpc,
@@ -353,6 +372,11 @@ void write_metrics(const Options &o, const char *mode, long frames, double secon
         m << ", \"psnr_target\": " << o.psnr << ", \"psnr_j\": " << g_quality.j << ", \"psnr_qs\": " << g_quality.qs
           << ", \"psnr_max_sse\": " << g_quality.max_sse << ", \"psnr_frames_searched\": " << g_quality.frames
           << ", \"psnr_sse\": " << g_quality.sse << ", \"psnr_achieved\": " << g_quality.psnr;
+    if (g_ssim.reported)
+        m << ", \"ssim_target\": " << o.ssim << ", \"ssim_j\": " << g_ssim.j << ", \"ssim_qs\": " << g_ssim.qs
+          << ", \"ssim_max_dssim\": " << g_ssim.max_dssim << ", \"ssim_frames_searched\": " << g_ssim.frames
+          << ", \"ssim_dssim\": " << g_ssim.dssim << ", \"ssim_achieved\": " << std::fixed << std::setprecision(6) << g_ssim.ssim
+          << std::defaultfloat << std::setprecision(6);
     if (g_frames_searched > 0) m << ", \"search_frames\": " << g_frames_searched;
     if (o.win)
         m << ", \"window\": [" << o.wx << ", " << o.wy << ", " << o.ww << ", " << o.wh << "], \"codeblocks\": " << o.win_cb;
@@ -388,7 +412,34 @@ void quality_report(int j, float qs, uint64_t max_sse, uint64_t samples, long nf
     std::cout << "Quality control: achieved " << r.psnr << " dB (SSE " << r.sse << ") over the frames searched" << std::endl;
 }
 
-// ---- the search step of -rate / -psnr: the search `o` asks for over an input on the device, into d_out; the choice and
+// -ssim <v>: the limit over `planes` planes of the frame's geometry, and the two console lines
+uint64_t ssim_limit(const Options &o, uint64_t planes, uint64_t &windows)
+{
+    uint64_t lim = 0;
+    if (picsong_ssim_windows(o.x, o.y, &windows) != PICSONG_OK) die(std::string("-ssim: ") + picsong_last_error());
+    windows *= planes;
+    CK(picsong_ssim_to_dssim(o.ssim, windows, &lim));
+    return lim;
+}
+std::string ssim_text(double v)
+{
+    std::ostringstream t;
+    t << std::fixed << std::setprecision(6) << v;
+    return t.str();
+}
+void ssim_report(int j, float qs, uint64_t max_dssim, uint64_t windows, long nframes_searched, const uint64_t *dssim, int n)
+{
+    SsimReport &r = g_ssim;
+    g_frames_searched = nframes_searched;
+    r.reported = true; r.j = j; r.qs = qs; r.max_dssim = max_dssim; r.windows = windows; r.frames = nframes_searched; r.dssim = 0;
+    for (int i = 0; i < n; i++) r.dssim += dssim[i];
+    CK(picsong_dssim_to_ssim(r.dssim, windows, &r.ssim));
+    std::cout << "Quality control: qs = " << qs << " (j = " << j << ") chosen for a DSSIM sum of at most " << max_dssim << " over "
+              << nframes_searched << " frame(s)" << std::endl;
+    std::cout << "Quality control: achieved SSIM " << ssim_text(r.ssim) << " (DSSIM sum " << r.dssim << ")" << std::endl;
+}
+
+// ---- the search step of -rate / -psnr / -ssim: the search `o` asks for over an input on the device, into d_out; the choice and
 // its console lines.  The input: n padded grey frames `stride` bytes apart (n = 0: an image, through the one-frame
 // calls) or, with rgb_mask != 0, the R, G and B planes of a frame, which must lie at d, d + stride and d + 2 * stride
 // (run_encode_rgb carves them out of one allocation so), coded with that header mask.  Returns the failure
@@ -404,8 +455,14 @@ std::string search_step(const Options &o, picsong_ctx *ctx, hipStream_t s, const
     const uint64_t samples = (uint64_t)o.x * (uint64_t)o.y * (uint64_t)arrays;
     uint64_t lim = 0, sse[16] = { 0 };
     if (o.has_psnr && picsong_psnr_to_sse(o.psnr, samples, &lim) != PICSONG_OK) return std::string("-psnr: ") + picsong_last_error();
+    uint64_t windows = 0;
+    if (o.has_ssim) lim = ssim_limit(o, (uint64_t)arrays, windows);
     int rc;
-    if (in.rgb_mask)
+    if (o.has_ssim)         // (an RGB frame: n = 1 of the n-frame call)
+        rc = in.rgb_mask ? picsong_encode_rgb_frames_ssim(ctx, 1, in.d, g, b, 0, 0, in.rgb_mask, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse)
+             : in.n      ? picsong_encode_frames_ssim(ctx, in.n, in.d, in.stride, 0, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse)
+                         : picsong_encode_frame_ssim(ctx, in.d, 0, lim, 0, 0, d_out, s, &r.j, r.totals, sse);
+    else if (in.rgb_mask)
         rc = o.has_psnr ? picsong_encode_rgb_frame_quality(ctx, in.d, g, b, in.rgb_mask, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse)
                         : picsong_encode_rgb_frame_rate(ctx, in.d, g, b, in.rgb_mask, target, 0, 0, d_out, out_stride, s, &r.j, r.totals);
     else if (in.n)
@@ -415,9 +472,11 @@ std::string search_step(const Options &o, picsong_ctx *ctx, hipStream_t s, const
         rc = o.has_psnr ? picsong_encode_frame_quality(ctx, in.d, 0, lim, 0, 0, d_out, s, &r.j, r.totals, sse)
                         : picsong_encode_frame_rate(ctx, in.d, 0, target, 0, 0, d_out, s, &r.j, r.totals);
     if (rc == PICSONG_ERR_RATE) return std::string("-rate: no quantiser meets the target size (") + picsong_last_error() + ")";
-    if (rc == PICSONG_ERR_QUALITY) return std::string("-psnr: no quantiser meets the target quality (") + picsong_last_error() + ")";
+    if (rc == PICSONG_ERR_QUALITY)
+        return std::string(o.has_ssim ? "-ssim" : "-psnr") + ": no quantiser meets the target quality (" + picsong_last_error() + ")";
     if (rc != PICSONG_OK || picsong_rate_qs(r.j, &r.qs) != PICSONG_OK) return std::string("The quantiser search failed: ") + picsong_last_error();
-    if (o.has_psnr) quality_report(r.j, r.qs, lim, samples, frames, sse, arrays);
+    if (o.has_ssim) ssim_report(r.j, r.qs, lim, windows, frames, sse, arrays);
+    else if (o.has_psnr) quality_report(r.j, r.qs, lim, samples, frames, sse, arrays);
     else rate_report_choice(r.j, r.qs, target, frames);
     return std::string();
 }
@@ -530,14 +589,20 @@ float rgb_search_frames(const Options &o, picsong_ctx *ctx, hipStream_t s, std::
     std::vector<uint64_t> sse(3 * (size_t)n, 0);
     int j = 0;
     float qs = 0.0f;
-    const int rc = o.has_psnr ? picsong_encode_rgb_frames_quality(ctx, n, d_pad, d_pad + P, d_pad + 2 * P, 3 * P, 0, 7, lim, 0, 0, d_out, max_shorts,
+    uint64_t windows = 0;
+    if (o.has_ssim) lim = ssim_limit(o, 3ull * (uint64_t)n, windows);
+    const int rc = o.has_ssim ? picsong_encode_rgb_frames_ssim(ctx, n, d_pad, d_pad + P, d_pad + 2 * P, 3 * P, 0, 7, lim, 0, 0, d_out, max_shorts,
+                                                               s, &j, totals.data(), sse.data())
+                 : o.has_psnr ? picsong_encode_rgb_frames_quality(ctx, n, d_pad, d_pad + P, d_pad + 2 * P, 3 * P, 0, 7, lim, 0, 0, d_out, max_shorts,
                                                                   s, &j, totals.data(), sse.data())
                               : picsong_encode_rgb_frames_rate(ctx, n, d_pad, d_pad + P, d_pad + 2 * P, 3 * P, 0, 7, target, 0, 0, d_out, max_shorts,
                                                                s, &j, totals.data());
     if (rc == PICSONG_ERR_RATE) die(std::string("-rate: no quantiser meets the target size (") + picsong_last_error() + ")");
-    if (rc == PICSONG_ERR_QUALITY) die(std::string("-psnr: no quantiser meets the target quality (") + picsong_last_error() + ")");
+    if (rc == PICSONG_ERR_QUALITY)
+        die(std::string(o.has_ssim ? "-ssim" : "-psnr") + ": no quantiser meets the target quality (" + picsong_last_error() + ")");
     if (rc != PICSONG_OK || picsong_rate_qs(j, &qs) != PICSONG_OK) die(std::string("The quantiser search failed: ") + picsong_last_error());
-    if (o.has_psnr) quality_report(j, qs, lim, samples, n, sse.data(), 3 * n);
+    if (o.has_ssim) ssim_report(j, qs, lim, windows, n, sse.data(), 3 * n);
+    else if (o.has_psnr) quality_report(j, qs, lim, samples, n, sse.data(), 3 * n);
     else rate_report_choice(j, qs, target, n);
     size_t at = 0;
     for (int z = 0; z < 3 * n; z++) {
@@ -596,7 +661,7 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
     // a video (-cp 2): groups of frames through one call each (encode_rgb_groups) -- behind the first frame where that one
     // carries the -rate / -psnr search; an image and -cp 3: frame by frame, here
     const bool grouped = o.video && batched;
-    long nloop = grouped ? ((o.has_rate || o.has_psnr) ? 1 : 0) : nframes;
+    long nloop = grouped ? ((o.has_rate || o.has_quality()) ? 1 : 0) : nframes;
     long searched = 0;                                   // -searchFrames: the frames the n-frame search call coded itself
     if (grouped && o.search_frames > 0) {
         searched = std::min<long>(o.search_frames, nframes);
@@ -621,7 +686,7 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
             HIPCK(hipStreamSynchronize(s));          // h_in is reused for the next plane
         }
         int totals[3] = { 0, 0, 0 };
-        if ((o.has_rate || o.has_psnr) && f == 0) {
+        if ((o.has_rate || o.has_quality()) && f == 0) {
             // the search on the first frame (an image: the frame); the rest of a video is coded at the result
             SearchChoice r;
             const std::string err = search_step(o, ctx, s, { d_in[0], P, 1, o.video ? 7 : 1 }, d_out, max_shorts, r);
@@ -754,12 +819,12 @@ constexpr long kProfFrames = 256;     // frames per pipeline slot whose stages a
 // (picsong_decode_images).  What every other mode says when it meets such a depth:
 const char *const kDeepBuilt =
     "With -bps 9..16 this build codes one grey still image (-cd 0: a raw file of W*H little-endian 16-bit samples or a P5 PGM with "
-    "maxval > 255) and decodes it (-cd 1, -drop allowed): not -video, -isRGB, -rate, -psnr, -train, -reduce, -window, -gpus or a "
+    "maxval > 255) and decodes it (-cd 1, -drop allowed): not -video, -isRGB, -rate, -psnr, -ssim, -train, -reduce, -window, -gpus or a "
     "-layout other than grey; -signedOrUnsigned 1 is not built.";
 void deep_check_mode(const Options &o, bool rgb, int bps)
 {
     if (bps < 9 || bps > 16 || o.signed_or_unsigned != 0) die(std::string("Only unsigned samples of 8..16 bits are built. ") + kDeepBuilt);
-    if (o.video || rgb || o.has_rate || o.has_psnr || !o.train.empty() || o.reduce > 0 || o.win || o.gpus > 1 || !o.devices.empty() ||
+    if (o.video || rgb || o.has_rate || o.has_quality() || !o.train.empty() || o.reduce > 0 || o.win || o.gpus > 1 || !o.devices.empty() ||
         o.layout > PICSONG_LAYOUT_GREY8 || !o.compare.empty() || o.search_frames > 0)
         die(kDeepBuilt);
 }
@@ -852,9 +917,18 @@ int run_encode(Options o)
         if (o.cp == 3) die("Incorrect parameters. -psnr does not apply to -cp 3.");
         if (!o.train.empty()) die("Incorrect parameters. -psnr does not apply to -train.");
     }
+    if (o.has_ssim) {
+        if (o.has_qs) die("Incorrect parameters. -ssim chooses the quantiser: it cannot be combined with -qs.");
+        if (o.has_rate) die("Incorrect parameters. -ssim cannot be combined with -rate.");
+        if (o.has_psnr) die("Incorrect parameters. -ssim cannot be combined with -psnr.");
+        if (o.type != 1) die("Incorrect parameters. -ssim applies to lossy coding (-type 1) only.");
+        if (o.cp == 3) die("Incorrect parameters. -ssim does not apply to -cp 3.");
+        if (!o.train.empty()) die("Incorrect parameters. -ssim does not apply to -train.");
+        if (o.x < 8 || o.y < 8) die("Incorrect parameters. -ssim needs a frame of 8 x 8 samples or more.");
+    }
     if (o.search_frames > 0) {
         if (!o.video) die("Incorrect parameters. -searchFrames applies to a video (-video 1) only.");
-        if (!o.has_rate && !o.has_psnr) die("Incorrect parameters. -searchFrames needs -rate or -psnr: it sizes their search.");
+        if (!o.has_rate && !o.has_quality()) die("Incorrect parameters. -searchFrames needs -rate or -psnr (or -ssim): it sizes their search.");
         if (o.search_frames > (o.is_rgb ? 21 : 16))
             die(o.is_rgb ? "Incorrect parameters. -searchFrames takes 1..21 frames of an RGB video." : "Incorrect parameters. -searchFrames takes 1..16 grey frames.");
     }
@@ -923,7 +997,7 @@ int run_encode(Options o)
     }
     const int fd = open(o.input.c_str(), O_RDONLY);
     if (fd < 0) die("Cannot open input file " + o.input);
-    if ((o.has_rate || o.has_psnr) && o.video) {
+    if ((o.has_rate || o.has_quality()) && o.video) {
         // -rate on a video: the first slot's context (rank 0 of -gpus N) searches on the first min(frames, 16) frames and
         // their summed target, then every context takes the chosen qs: the stream has one header, hence one qs
         const int n = (int)std::min<long>(nframes, o.search_frames > 0 ? o.search_frames : 16);
@@ -1120,7 +1194,7 @@ int run_encode(Options o)
             (o.layout >= 0 ? hipMemcpyAsync(k.d_raw, k.h_in, frame_bytes * (size_t)n, hipMemcpyHostToDevice, k.stream)
                            : hipMemcpyAsync(k.d_in, k.h_in, P * (size_t)n, hipMemcpyHostToDevice, k.stream)) != hipSuccess) err = "HIP error in the frame upload";
         else if (o.layout >= 0 && picsong_ingest_frames(k.ctx, n, &im, frame_bytes, k.d_in, P, k.stream) != PICSONG_OK) err = picsong_last_error();
-        else if ((o.has_rate || o.has_psnr) && !o.video) {
+        else if ((o.has_rate || o.has_quality()) && !o.video) {
             // an image: one search call (synchronous); its length is the context's last total, as after picsong_encode_frame
             SearchChoice r;
             err = search_step(o, k.ctx, k.stream, { k.d_in, 0, 0, 0 }, k.d_out, 0, r);
@@ -1727,7 +1801,8 @@ int run_compare(const Options &o)
     HIPCK(hipMalloc(&d_sse, sizeof(uint64_t)));
     HIPCK(hipHostMalloc(&h_sse, sizeof(uint64_t)));
     std::vector<uint8_t> raw(plane_bytes);
-    uint64_t sse = 0;
+    uint64_t sse = 0, dssim = 0, windows = 0;
+    const bool ssim = picsong_ssim_windows(p.width, p.height, &windows) == PICSONG_OK;   // (8 x 8 samples or more)
     for (long i = 0; i < planes; i++) {
         if (!read_frame(fa, base_a, (size_t)i, p.width, p.height, raw.data())) die("Cannot read back " + o.output);
         CK(picsong_pad_frame_host(raw.data(), p.width, p.height, h, aw, ah));
@@ -1738,11 +1813,22 @@ int run_compare(const Options &o)
         HIPCK(hipMemcpyAsync(h_sse, d_sse, sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
         HIPCK(hipStreamSynchronize(nullptr));
         sse += *h_sse;
+        if (ssim) {
+            CK(picsong_frames_dssim(ctx, 1, d, 0, d + P, 0, d_sse, nullptr));
+            HIPCK(hipMemcpyAsync(h_sse, d_sse, sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
+            HIPCK(hipStreamSynchronize(nullptr));
+            dssim += *h_sse;
+        }
     }
     double psnr = 0.0;
     CK(picsong_sse_to_psnr(sse, (uint64_t)plane_bytes * (uint64_t)planes, &psnr));
     std::cout << "Compare: PSNR " << psnr << " dB, SSE " << sse << " over " << planes << " plane(s) of " << p.width << "x" << p.height
               << std::endl;
+    if (ssim) {
+        double v = 0.0;
+        CK(picsong_dssim_to_ssim(dssim, windows * (uint64_t)planes, &v));
+        std::cout << "Compare: SSIM " << ssim_text(v) << ", DSSIM sum " << dssim << " over " << planes << " plane(s)" << std::endl;
+    }
     picsong_ctx_destroy(ctx);
     (void)hipHostFree(h); (void)hipFree(d); (void)hipFree(d_sse); (void)hipHostFree(h_sse);
     return 0;

@@ -75,6 +75,8 @@ EXPORTS = [
     "picsong_ctx_set_decode_drop", "picsong_ctx_get_decode_drop", "picsong_drop_planes",
     "picsong_depth_range_guaranteed", "picsong_pad_frame16_host", "picsong_level_shift_fwd16", "picsong_dwt_forward_u16",
     "picsong_encode_frames16", "picsong_decode_frames16",
+    "picsong_ssim_windows", "picsong_ssim_to_dssim", "picsong_dssim_to_ssim", "picsong_frames_dssim",
+    "picsong_encode_frame_ssim", "picsong_encode_frames_ssim", "picsong_encode_rgb_frames_ssim",
 ]
 
 _lib = None
@@ -227,6 +229,17 @@ def load():
         L.picsong_dwt_forward_u16.argtypes = [vp, vp, vp, vp]
         L.picsong_encode_frames16.argtypes = [vp, i, vp, C.c_size_t, i, vp, C.c_size_t, vp]
         L.picsong_decode_frames16.argtypes = [vp, i, vp, C.c_size_t, vp, C.c_size_t, vp]
+    if hasattr(L, "picsong_frames_dssim"):
+        u64 = C.c_uint64
+        L.picsong_ssim_windows.argtypes = [i, i, C.POINTER(u64)]
+        L.picsong_ssim_to_dssim.argtypes = [C.c_double, u64, C.POINTER(u64)]
+        L.picsong_dssim_to_ssim.argtypes = [u64, u64, C.POINTER(C.c_double)]
+        L.picsong_frames_dssim.argtypes = [vp, i, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
+        L.picsong_encode_frame_ssim.argtypes = [vp, vp, i, u64, i, i, vp, vp, C.POINTER(i), C.POINTER(i), C.POINTER(u64)]
+        L.picsong_encode_frames_ssim.argtypes = [vp, i, vp, C.c_size_t, i, u64, i, i, vp, C.c_size_t, vp,
+                                                 C.POINTER(i), C.POINTER(i), C.POINTER(u64)]
+        L.picsong_encode_rgb_frames_ssim.argtypes = [vp, i, vp, vp, vp, C.c_size_t, i, i, u64, i, i, vp, C.c_size_t, vp,
+                                                     C.POINTER(i), C.POINTER(i), C.POINTER(u64)]
     _lib = L
     return L
 
@@ -271,6 +284,27 @@ def sse_to_psnr(sse, samples):
     """The PSNR (dB) of an SSE over `samples` 8-bit samples; inf for sse = 0 (picsong_sse_to_psnr)."""
     v = C.c_double()
     _check(load().picsong_sse_to_psnr(sse, samples, C.byref(v)))
+    return v.value
+
+
+def ssim_windows(w, h):
+    """The 8 x 8 windows (origins 4 x, 4 y) of a w x h plane (picsong_ssim_windows; raises below 8 x 8)."""
+    v = C.c_uint64()
+    _check(load().picsong_ssim_windows(w, h, C.byref(v)))
+    return v.value
+
+
+def ssim_to_dssim(ssim, windows):
+    """The largest DSSIM sum over `windows` windows whose SSIM is at least `ssim` (picsong_ssim_to_dssim)."""
+    v = C.c_uint64()
+    _check(load().picsong_ssim_to_dssim(ssim, windows, C.byref(v)))
+    return v.value
+
+
+def dssim_to_ssim(dssim, windows):
+    """The SSIM of a DSSIM sum over `windows` windows (picsong_dssim_to_ssim)."""
+    v = C.c_double()
+    _check(load().picsong_dssim_to_ssim(dssim, windows, C.byref(v)))
     return v.value
 
 
@@ -576,6 +610,54 @@ class Codec:
                                                                max_sse, j_min, j_max, self._p(out), out.stride(0),
                                                                self._stream(), C.byref(j), t, e))
         return j.value, [out[k, :t[k]] for k in range(3)], [int(v) for v in e]
+
+    # ---- SSIM control: the structural measure, and the 9/7 encode calls with qs chosen to meet a DSSIM-sum limit ----
+    def frames_dssim(self, a, b, out=None):
+        """a, b: uint8 padded frames [n, AH*AW] (or one frame [AH*AW]); returns an int64 device tensor [n] holding the
+        DSSIM sum over the visible samples of each pair (picsong_frames_dssim, asynchronous)."""
+        if a.dim() == 1:
+            a, b = a[None], b[None]
+        n = a.shape[0]
+        assert b.shape[0] == n and a.stride(-1) == 1 and b.stride(-1) == 1
+        if out is None:
+            out = self.torch.empty(n, dtype=self.torch.int64, device=self.dev)
+        _check(self.L.picsong_frames_dssim(self.h, n, self._p(a), a.stride(0), self._p(b), b.stride(0), self._p(out),
+                                           self._stream()))
+        return out
+
+    def encode_frame_ssim(self, frame_u8_padded, max_dssim, j_min=0, j_max=0, iter_=0, out=None):
+        """Returns (j, codestream, dssim): the stream of picsong_encode_frame at qs = rate_qs(j), j the quantiser search's
+        result for max_dssim; raises QualityError when nothing of the range meets it."""
+        if out is None:
+            out = self.torch.empty(self.max_stream_shorts(), dtype=self.torch.int16, device=self.dev)
+        j, t, e = C.c_int(), C.c_int(), C.c_uint64()
+        _check_quality(self.L.picsong_encode_frame_ssim(self.h, self._p(frame_u8_padded), iter_, max_dssim, j_min, j_max,
+                                                        self._p(out), self._stream(), C.byref(j), C.byref(t), C.byref(e)))
+        return j.value, out[:t.value], e.value
+
+    def encode_frames_ssim(self, frames_u8_padded, max_dssim, j_min=0, j_max=0, first_iter=0):
+        """frames_u8_padded: uint8 [n, AH*AW], n <= 16; max_dssim for the sum over the n frames.  Returns (j, streams, the
+        per-frame DSSIM sums)."""
+        n = frames_u8_padded.shape[0]
+        assert frames_u8_padded.stride(-1) == 1
+        out = self.torch.empty((n, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        j, t, e = C.c_int(), (C.c_int * n)(), (C.c_uint64 * n)()
+        _check_quality(self.L.picsong_encode_frames_ssim(self.h, n, self._p(frames_u8_padded), frames_u8_padded.stride(0),
+                                                         first_iter, max_dssim, j_min, j_max, self._p(out), out.stride(0),
+                                                         self._stream(), C.byref(j), t, e))
+        return j.value, [out[f, :t[f]] for f in range(n)], [int(v) for v in e]
+
+    def encode_rgb_frames_ssim(self, r, g, b, max_dssim, j_min=0, j_max=0, n=None, frame_stride=None, first_iter=0,
+                               header_mask=7):
+        """max_dssim for the sum over the 3 n planes (r / g / b as encode_rgb_frames takes them).  Returns (j, the 3 n
+        codestreams, the DSSIM sum per plane: frame f's R, G, B at 3 f ..)."""
+        n, frame_stride = self._rgb_frames_span(r, g, b, n, frame_stride)
+        out = self.torch.empty((3 * n, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        j, t, e = C.c_int(), (C.c_int * (3 * n))(), (C.c_uint64 * (3 * n))()
+        _check_quality(self.L.picsong_encode_rgb_frames_ssim(self.h, n, self._p(r), self._p(g), self._p(b), frame_stride,
+                                                             first_iter, header_mask, max_dssim, j_min, j_max, self._p(out),
+                                                             out.stride(0), self._stream(), C.byref(j), t, e))
+        return j.value, [out[k, :t[k]] for k in range(3 * n)], [int(v) for v in e]
 
     # ---- training: the statistics a probability table is made from (k = 0, -cp 2 contexts; no table needed) ----
     def train_begin(self, **geometry):

@@ -544,6 +544,48 @@ int picsong_encode_rgb_frames_quality(picsong_ctx *ctx, int n, const uint8_t *d_
 int picsong_train_rgb_frames(picsong_ctx *ctx, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b,
                              size_t frame_stride, void *stream);
 
+/* ---- encode to a target SSIM (x264 --ssim / ffmpeg's ssim filter measure it; the reference has no counterpart): the
+ *      quality calls above with a structural measure for the SSE.  The measure is x264's integer 8 x 8 SSIM of 8-bit
+ *      samples over the VISIBLE W x H part, W, H >= 8: windows of 8 x 8 samples at the origins (4 x, 4 y),
+ *      x < nx = (W - 8) / 4 + 1, y < ny = (H - 8) / 4 + 1 (columns from 4 (nx + 1) and rows from 4 (ny + 1) on belong to
+ *      no window); per window the exact sums s1 = sum a, s2 = sum b, ss = sum a^2 + sum b^2, s12 = sum a b and, with
+ *      c1 = 416, c2 = 235963,
+ *          A = 2 s1 s2 + c1, B = 2 (64 s12 - s1 s2) + c2, C = s1^2 + s2^2 + c1, E = 64 ss - s1^2 - s2^2 + c2,
+ *          v = ((double)A * (double)B) / ((double)C * (double)E),  q = (int64)floor(v * 2^24)   (q <= 2^24, may be negative).
+ *      The DSSIM sum of a pair of planes is windows * 2^24 - sum q: an exact, order-independent, non-negative integer,
+ *      0 for equal planes; SSIM = 1 - dssim / (windows * 2^24).  Host-only helpers: picsong_ssim_windows gives nx * ny
+ *      (PICSONG_ERR_ARG below 8 x 8); picsong_ssim_to_dssim gives floor(((1 - ssim) * windows) * 2^24) in double
+ *      arithmetic in that order, ssim in [-1, 1], windows > 0 (for a limit over several planes pass the windows of all
+ *      of them); picsong_dssim_to_ssim the way back.
+ *      picsong_frames_dssim measures: d_dssim[f] = the DSSIM sum of frame f of d_a against frame f of d_b; n, strides,
+ *      alignment (any: 4-byte aligned pointers and strides take dword loads), asynchrony and refusals as
+ *      picsong_frames_sse, and PICSONG_ERR_ARG on a context below 8 x 8.  d_dssim is a device uint64[n], overwritten.
+ *      The search calls are picsong_encode_frame_quality / picsong_encode_frames_quality /
+ *      picsong_encode_rgb_frames_quality with dssim(j) for sse(j): the same grid, sub-range and bisection
+ *          lo = -1, hi = len(G');  while hi - lo > 1: mid = (lo + hi) / 2;  dssim(G'[mid]) <= max_dssim ? hi = mid : lo = mid
+ *      result G'[hi]; dssim(j) = the DSSIM sum of the input against what picsong_decode_frame / picsong_decode_rgb_frame
+ *      return for the stream coded at q(j), summed over the call's frames (RGB: over the R, G and B planes of every
+ *      frame).  h_dssim receives 1, n or 3 n per-plane values; PICSONG_ERR_QUALITY with *h_j = 0 when nothing in the
+ *      range meets the limit; the streams are the plain encode calls' at q(*h_j) byte for byte; n = 1..16 grey, 1..21
+ *      RGB (a single RGB frame is n = 1); strides, alignment rules, synchrony and refusals as the quality calls', and
+ *      PICSONG_ERR_ARG on a context below 8 x 8.  Three candidates a round (PICSONG_RATE_K=1: one), one read-back a
+ *      round; a probe runs no coder: quantise, dividing synthesis, ssim_kernel (RGB: the inverse ICT writes the pixels
+ *      first). ---- */
+int picsong_ssim_windows(int w, int h, uint64_t *windows);
+int picsong_ssim_to_dssim(double ssim, uint64_t windows, uint64_t *max_dssim);
+int picsong_dssim_to_ssim(uint64_t dssim, uint64_t windows, double *ssim);
+int picsong_frames_dssim(picsong_ctx *ctx, int n, const uint8_t *d_a, size_t a_stride, const uint8_t *d_b, size_t b_stride,
+                         uint64_t *d_dssim, void *stream);
+int picsong_encode_frame_ssim(picsong_ctx *ctx, const uint8_t *d_frame, int iter, uint64_t max_dssim, int j_min, int j_max,
+                              uint16_t *d_stream, void *stream, int *h_j, int *h_total, uint64_t *h_dssim);
+int picsong_encode_frames_ssim(picsong_ctx *ctx, int n, const uint8_t *d_frames, size_t frame_stride, int first_iter,
+                               uint64_t max_dssim, int j_min, int j_max, uint16_t *d_streams, size_t stream_stride,
+                               void *stream, int *h_j, int *h_totals, uint64_t *h_dssim);
+int picsong_encode_rgb_frames_ssim(picsong_ctx *ctx, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b,
+                                   size_t frame_stride, int first_iter, int header_mask, uint64_t max_dssim, int j_min,
+                                   int j_max, uint16_t *d_streams, size_t stream_stride, void *stream, int *h_j,
+                                   int *h_totals, uint64_t *h_dssim);
+
 /* ---- frames as applications hold them (the reference reads files only, IO/IOManager.ipp:72-112; nvJPEG2000 and
  *      friends take a pitched image descriptor): W x H pixels (the context's unpadded -xSize / -ySize) at a byte pitch,
  *      one byte a pixel or interleaved RGB(A), converted ON THE DEVICE to and from the padded planar u8 planes every
