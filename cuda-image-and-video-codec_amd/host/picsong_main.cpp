@@ -5,14 +5,20 @@
 // paths, including the complexity-scalable mode -k > 0 and the three-coding-pass mode -cp 3 (deprecated in
 // the reference, whose tree ships no cp_sig / cp_sign tables for it: -LUTFolder must hold them).
 //
-// Pipeline (video encode): the reference's reader / worker / writer structure
+// Pipeline (grey video encode, run_encode): the reference's reader / worker / writer structure
 // (CodingEngine.cu:212-262,463-498,758-1069) with condition variables instead of its spin-wait flag
 // arrays (_doubleBufferInput/_doubleBufferOutput, :233-239).  A ring of slots, each with its own
-// picsong_ctx, HIP stream, pinned host buffers and device buffers; frame f lives in slot f mod S
-// (S = max(-numberOfStreams, 3) + 3).  Two reader threads fill the pinned input buffers straight from
-// the file (pread), the main thread launches H2D copy + encode on the slot's stream, a collector
-// thread waits for the streams in frame order, copies the codestream back and fixes its file offset,
-// two writer threads pwrite the payloads; the _SIZE entries are appended in frame order at the end.
+// picsong_ctx, HIP stream, pinned host buffers and device buffers; a slot carries one GROUP of up to B
+// consecutive frames (frames_per_launch), group g lives in slot g mod S (S = max(-numberOfStreams, 3) + 3,
+// rounded up to a multiple of the devices).  Two reader threads stage the groups in the pinned input
+// buffers (stage_frames), the main thread launches H2D copy + encode on the slot's stream (upload_frames),
+// a collector thread waits for the groups' stream lengths in group order and fixes every frame's file
+// offset, two writer threads copy the codestreams back and pwrite them; the _SIZE entries are appended in
+// frame order at the end.  The grey video decode (run_decode_video) is a second, deliberately separate
+// pipeline of the same shape without a collector: the _SIZE sidecar gives every offset up front.
+// Everything else -- RGB, -train, -bps 9..16, still-image decode, -compare -- is straight-line code on one
+// stream.  The file rules live in cli_io.hpp; device and pinned memory, streams and contexts are owned
+// (Owned) and freed where their scope ends -- die() exits without unwinding.
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -36,8 +42,11 @@
 #include <vector>
 
 #include "../../include/picsong_hip.h"
+#include "cli_io.hpp"
 
 namespace {
+
+using namespace cli_io;
 
 struct Options {
     std::string input, output, lut_folder;
@@ -81,6 +90,23 @@ struct Options {
         hipError_t e_ = (expr);                                                         \
         if (e_ != hipSuccess) die(std::string(#expr) + " failed: " + hipGetErrorString(e_)); \
     } while (0)
+
+// ---- owners of device memory, pinned memory, a stream and a context: move-only, released by the destructor
+template <typename H, auto Release> struct Owned {
+    H p = nullptr;
+    Owned() = default;
+    Owned(Owned &&o) noexcept : p(o.p) { o.p = nullptr; }
+    Owned &operator=(Owned &&o) noexcept { std::swap(p, o.p); return *this; }
+    ~Owned() { if (p) (void)Release(p); }
+    operator H() const { return p; }
+};
+template <typename T> using Dev = Owned<T *, hipFree>;
+template <typename T> using Pinned = Owned<T *, hipHostFree>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Ctx = Owned<picsong_ctx *, picsong_ctx_destroy>;       // (picsong_ctx_destroy makes the context's device current itself)
+template <typename T> Dev<T> dev_alloc(size_t bytes) { Dev<T> b; HIPCK(hipMalloc(&b.p, bytes)); return b; }
+template <typename T> Pinned<T> pinned_alloc(size_t bytes) { Pinned<T> b; HIPCK(hipHostMalloc(&b.p, bytes)); return b; }
+Stream stream_create() { Stream s; HIPCK(hipStreamCreate(&s.p)); return s; }
 
 // flag lookup: the value is the token after the flag (IO/CommandLineParser.cpp:10-25)
 struct Args {
@@ -193,37 +219,31 @@ Options parse(const Args &a)
         o.win = 1;
         echo("-window", v);
     }
-    if (a.has("-train")) {
-        if (o.cd != 0) die("Incorrect parameters. -train applies to coding (-cd 0) only.");
+    // a flag of coding only; -psnr / -ssim: a number read whole (strtod), echoed as given
+    auto coding_only = [&](const char *f) {
+        if (a.has(f) && o.cd != 0) die(std::string("Incorrect parameters. ") + f + " applies to coding (-cd 0) only.");
+        return a.has(f);
+    };
+    auto getd = [&](const char *f, double &dst, bool &given, bool (*ok)(double), const char *takes) {
+        const std::string v = a.get(f);
+        char *end = nullptr;
+        dst = std::strtod(v.c_str(), &end);
+        given = true;
+        if (v.empty() || *end != '\0' || !ok(dst)) die(std::string("Incorrect parameters. ") + f + " takes " + takes);
+        echo(f, v);
+    };
+    if (coding_only("-train")) {
         gets("-train", o.train);
         if (o.train.empty()) die("Incorrect parameters. -train takes the folder to write.");
     }
-    if (a.has("-rate")) {
-        if (o.cd != 0) die("Incorrect parameters. -rate applies to coding (-cd 0) only.");
+    if (coding_only("-rate")) {
         getf("-rate", o.rate);
         o.has_rate = true;
         if (!(o.rate > 0.0f)) die("Incorrect parameters. -rate takes a positive number of bits per pixel.");
     }
-    if (a.has("-psnr")) {
-        if (o.cd != 0) die("Incorrect parameters. -psnr applies to coding (-cd 0) only.");
-        const std::string v = a.get("-psnr");
-        char *end = nullptr;
-        o.psnr = std::strtod(v.c_str(), &end);
-        o.has_psnr = true;
-        if (v.empty() || *end != '\0' || !std::isfinite(o.psnr)) die("Incorrect parameters. -psnr takes a PSNR in dB.");
-        echo("-psnr", v);
-    }
-    if (a.has("-ssim")) {
-        if (o.cd != 0) die("Incorrect parameters. -ssim applies to coding (-cd 0) only.");
-        const std::string v = a.get("-ssim");
-        char *end = nullptr;
-        o.ssim = std::strtod(v.c_str(), &end);
-        o.has_ssim = true;
-        if (v.empty() || *end != '\0' || !(o.ssim > 0.0 && o.ssim <= 1.0)) die("Incorrect parameters. -ssim takes an SSIM above 0 and at most 1.");
-        echo("-ssim", v);
-    }
-    if (a.has("-searchFrames")) {
-        if (o.cd != 0) die("Incorrect parameters. -searchFrames applies to coding (-cd 0) only.");
+    if (coding_only("-psnr")) getd("-psnr", o.psnr, o.has_psnr, [](double v) { return std::isfinite(v); }, "a PSNR in dB.");
+    if (coding_only("-ssim")) getd("-ssim", o.ssim, o.has_ssim, [](double v) { return v > 0.0 && v <= 1.0; }, "an SSIM above 0 and at most 1.");
+    if (coding_only("-searchFrames")) {
         geti("-searchFrames", o.search_frames);
         if (o.search_frames < 1) die("Incorrect parameters. -searchFrames takes a number of frames, 1 or more.");
     }
@@ -254,37 +274,6 @@ Options parse(const Args &a)
     return o;
 }
 
-// ---- file helpers -----------------------------------------------------------------------------
-struct Pgm { bool is_pgm = false; int w = 0, h = 0, maxval = 0; size_t offset = 0; };
-
-Pgm sniff_pgm(const std::string &path)
-{
-    Pgm p;
-    std::ifstream f(path, std::ios::binary);
-    char magic[2] = { 0, 0 };
-    f.read(magic, 2);
-    if (!f || magic[0] != 'P' || magic[1] != '5') return p;
-    int vals[3], n = 0;
-    while (n < 3 && f) {
-        int c = f.peek();
-        if (c == '#') { std::string line; std::getline(f, line); continue; }
-        if (isspace(c)) { f.get(); continue; }
-        f >> vals[n++];
-    }
-    if (n < 3) return p;
-    f.get();                                   // single whitespace after maxval
-    p.is_pgm = true; p.w = vals[0]; p.h = vals[1]; p.maxval = vals[2]; p.offset = (size_t)f.tellg();
-    return p;
-}
-
-bool read_frame(std::ifstream &f, size_t base, size_t frame, int w, int h, uint8_t *dst)
-{
-    f.clear();
-    f.seekg((std::streamoff)(base + frame * (size_t)w * (size_t)h));
-    f.read(reinterpret_cast<char *>(dst), (std::streamsize)((size_t)w * h));
-    return (size_t)f.gcount() == (size_t)w * (size_t)h;
-}
-
 // ---- -layout: the raw file's frames as they are.  Bytes a pixel, bytes a frame of the file (rows of W * bpp bytes, planar:
 // three planes), and the picsong_image of such a frame at a device address
 int layout_bpp(int layout) { return layout < PICSONG_LAYOUT_RGB24 ? 1 : (layout < PICSONG_LAYOUT_RGBA32 ? 3 : 4); }
@@ -306,15 +295,72 @@ void layout_check_context(int layout, bool rgb)
                 : "Incorrect parameters. A one-component file is -layout grey (the colour layouts need -isRGB 1 -components 3).");
 }
 
+// ---- staging: frames [first, first + n) of `planes` planes each, from the raw file into the pinned h.  With -layout the
+// frames as the file holds them, back to back; otherwise every plane padded on the host (picsong_pad_frame_host through
+// `raw`, W * H bytes of scratch; a plane that needs no padding is read where it goes), P bytes a plane.  Returns the
+// failure (empty: none)
+const char *const kShortInput = "Input file is shorter than the requested frames.";
+std::string stage_frames(const Options &o, int fd, size_t file_base, long first, int n, int planes, uint8_t *h, uint8_t *raw)
+{
+    if (o.layout >= 0) {
+        const size_t fb = layout_frame_bytes(o.layout, o.x, o.y);
+        return pread_exact(fd, h, fb * (size_t)n, file_base + (size_t)first * fb) ? "" : kShortInput;
+    }
+    const int aw = picsong_pad_dim(o.x), ah = picsong_pad_dim(o.y);
+    const size_t P = (size_t)aw * ah, plane = (size_t)o.x * o.y;
+    const bool padded_already = (o.x == aw && o.y == ah);
+    for (int j = 0; j < n * planes; j++) {
+        uint8_t *dst = h + (size_t)j * P;
+        if (!pread_exact(fd, padded_already ? dst : raw, plane, file_base + ((size_t)first * planes + j) * plane)) return kShortInput;
+        if (!padded_already && picsong_pad_frame_host(raw, o.x, o.y, dst, aw, ah) != PICSONG_OK) return picsong_last_error();
+    }
+    return "";
+}
+// ... and to the device: n staged frames into padded planes at d_pad, P bytes a plane; -layout: as they are to d_raw,
+// padded and split there by picsong_ingest_frames
+std::string upload_frames(const Options &o, picsong_ctx *ctx, hipStream_t s, const uint8_t *h, int n, int planes, uint8_t *d_raw, uint8_t *d_pad)
+{
+    const size_t P = (size_t)picsong_pad_dim(o.x) * picsong_pad_dim(o.y) * (size_t)planes;
+    const size_t fb = o.layout >= 0 ? layout_frame_bytes(o.layout, o.x, o.y) : P;
+    if (hipMemcpyAsync(o.layout >= 0 ? d_raw : d_pad, h, fb * (size_t)n, hipMemcpyHostToDevice, s) != hipSuccess) return "HIP error in the frame upload";
+    if (o.layout < 0) return "";
+    const picsong_image im = layout_image(o.layout, d_raw, o.x, o.y);
+    return picsong_ingest_frames(ctx, n, &im, fb, d_pad, P, s) == PICSONG_OK ? "" : picsong_last_error();
+}
+
+// ---- the streams a straight-line encode path writes: <o>, <o>_SIZE and the running total
+struct StreamSink {
+    std::ofstream out;
+    SizeList sizes;
+    long total_shorts = 0;
+    explicit StreamSink(const std::string &o) : out(o, std::ios::binary | std::ios::app), sizes(o + "_SIZE") {}
+};
+// the n streams a call left `stride` shorts apart at d_out: back to back into the pinned h_out, one wait for the stream,
+// then appended to the output, their lengths to _SIZE
+void collect_streams(hipStream_t s, const uint16_t *d_out, size_t stride, const int *totals, int n, uint16_t *h_out, StreamSink &to)
+{
+    size_t at = 0;
+    for (int j = 0; j < n; j++) {
+        HIPCK(hipMemcpyAsync(h_out + at, d_out + (size_t)j * stride, (size_t)totals[j] * 2, hipMemcpyDeviceToHost, s));
+        at += (size_t)totals[j];
+        to.total_shorts += totals[j];
+    }
+    HIPCK(hipStreamSynchronize(s));
+    to.out.write(reinterpret_cast<const char *>(h_out), (std::streamsize)(at * 2));
+    to.sizes.append(totals, (size_t)n);
+}
+
 struct Worker {
-    picsong_ctx *ctx = nullptr;
-    hipStream_t stream = nullptr;
     int device = 0;                                // the GPU this slot's context, stream and buffers live on
-    uint8_t *h_in = nullptr, *d_in = nullptr;      // padded frame, pinned / device
-    uint16_t *h_out = nullptr, *d_out = nullptr;   // codestream, pinned / device
-    uint8_t *h_raw = nullptr;                      // unpadded frame (host)
-    uint8_t *d_raw = nullptr;                      // -layout: the unpadded frames as read, on the device
-    long frame = -1;
+    Ctx ctx;
+    Stream stream;
+    Pinned<uint8_t> h_in;                          // padded frames, pinned / device
+    Dev<uint8_t> d_in;
+    Pinned<uint16_t> h_out;                        // codestreams, pinned / device
+    Dev<uint16_t> d_out;
+    std::vector<uint8_t> h_raw;                    // unpadded frame (host)
+    Dev<uint8_t> d_raw;                            // -layout: the unpadded frames as read, on the device
+    ~Worker() { (void)hipSetDevice(device); }      // ... and are released there
 };
 
 // component c uses the {ref,sig,sign}{R,G,B}.txt_0 files (Engine::initLUT Engines/Engine.cu:124-136);
@@ -440,37 +486,46 @@ void ssim_report(int j, float qs, uint64_t max_dssim, uint64_t windows, long nfr
 }
 
 // ---- the search step of -rate / -psnr / -ssim: the search `o` asks for over an input on the device, into d_out; the choice and
-// its console lines.  The input: n padded grey frames `stride` bytes apart (n = 0: an image, through the one-frame
-// calls) or, with rgb_mask != 0, the R, G and B planes of a frame, which must lie at d, d + stride and d + 2 * stride
-// (run_encode_rgb carves them out of one allocation so), coded with that header mask.  Returns the failure
-// (empty: none); re-tuning contexts to the choice is the caller's.
-struct SearchInput { const uint8_t *d; size_t stride; int n, rgb_mask; };
-struct SearchChoice { int j = 0; float qs = 0.0f; int totals[16] = { 0 }; };
+// its console lines.  The input, by the family of library call it goes through: one padded grey frame (an image); n
+// grey frames `stride` bytes apart; the R, G and B planes of one frame at d, d + stride and d + 2 * stride, coded with the
+// header mask rgb_mask; or n such frames 3 * stride apart (-searchFrames on an RGB video).  The one-frame and n-frame
+// calls set the search up differently in the library: n = 1 does not make them interchangeable here.  Returns the
+// failure (empty: none); re-tuning contexts to the choice is the caller's.
+enum SearchFamily { GREY_FRAME = 0, GREY_FRAMES = 1, RGB_FRAME = 2, RGB_FRAMES = 3 };
+struct SearchInput { SearchFamily family; const uint8_t *d; size_t stride; int n, rgb_mask; };
+struct SearchChoice { int j = 0; float qs = 0.0f; int totals[3 * 21] = { 0 }; };
 std::string search_step(const Options &o, picsong_ctx *ctx, hipStream_t s, const SearchInput &in, uint16_t *d_out, size_t out_stride,
                         SearchChoice &r)
 {
-    const int frames = in.n ? in.n : 1, arrays = in.rgb_mask ? 3 : frames;
+    const bool rgb = in.family >= RGB_FRAME;
+    const int frames = in.n, arrays = rgb ? 3 * frames : frames;
     const uint8_t *g = in.d + in.stride, *b = g + in.stride;
     const size_t target = rate_target_shorts(o) * (size_t)frames;
     const uint64_t samples = (uint64_t)o.x * (uint64_t)o.y * (uint64_t)arrays;
-    uint64_t lim = 0, sse[16] = { 0 };
+    uint64_t lim = 0, sse[3 * 21] = { 0 };
     if (o.has_psnr && picsong_psnr_to_sse(o.psnr, samples, &lim) != PICSONG_OK) return std::string("-psnr: ") + picsong_last_error();
     uint64_t windows = 0;
     if (o.has_ssim) lim = ssim_limit(o, (uint64_t)arrays, windows);
-    int rc;
-    if (o.has_ssim)         // (an RGB frame: n = 1 of the n-frame call)
-        rc = in.rgb_mask ? picsong_encode_rgb_frames_ssim(ctx, 1, in.d, g, b, 0, 0, in.rgb_mask, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse)
-             : in.n      ? picsong_encode_frames_ssim(ctx, in.n, in.d, in.stride, 0, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse)
-                         : picsong_encode_frame_ssim(ctx, in.d, 0, lim, 0, 0, d_out, s, &r.j, r.totals, sse);
-    else if (in.rgb_mask)
-        rc = o.has_psnr ? picsong_encode_rgb_frame_quality(ctx, in.d, g, b, in.rgb_mask, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse)
-                        : picsong_encode_rgb_frame_rate(ctx, in.d, g, b, in.rgb_mask, target, 0, 0, d_out, out_stride, s, &r.j, r.totals);
-    else if (in.n)
-        rc = o.has_psnr ? picsong_encode_frames_quality(ctx, in.n, in.d, in.stride, 0, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse)
-                        : picsong_encode_frames_rate(ctx, in.n, in.d, in.stride, 0, target, 0, 0, d_out, out_stride, s, &r.j, r.totals);
-    else
-        rc = o.has_psnr ? picsong_encode_frame_quality(ctx, in.d, 0, lim, 0, 0, d_out, s, &r.j, r.totals, sse)
-                        : picsong_encode_frame_rate(ctx, in.d, 0, target, 0, 0, d_out, s, &r.j, r.totals);
+    enum { SIZE = 0, PSNR = 1, SSIM = 2 };
+    int rc = PICSONG_ERR_ARG;
+    switch (in.family * 3 + (o.has_ssim ? SSIM : o.has_psnr ? PSNR : SIZE)) {
+    case GREY_FRAME * 3 + SIZE: rc = picsong_encode_frame_rate(ctx, in.d, 0, target, 0, 0, d_out, s, &r.j, r.totals); break;
+    case GREY_FRAME * 3 + PSNR: rc = picsong_encode_frame_quality(ctx, in.d, 0, lim, 0, 0, d_out, s, &r.j, r.totals, sse); break;
+    case GREY_FRAME * 3 + SSIM: rc = picsong_encode_frame_ssim(ctx, in.d, 0, lim, 0, 0, d_out, s, &r.j, r.totals, sse); break;
+    case GREY_FRAMES * 3 + SIZE: rc = picsong_encode_frames_rate(ctx, in.n, in.d, in.stride, 0, target, 0, 0, d_out, out_stride, s, &r.j, r.totals); break;
+    case GREY_FRAMES * 3 + PSNR: rc = picsong_encode_frames_quality(ctx, in.n, in.d, in.stride, 0, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse); break;
+    case GREY_FRAMES * 3 + SSIM: rc = picsong_encode_frames_ssim(ctx, in.n, in.d, in.stride, 0, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse); break;
+    case RGB_FRAME * 3 + SIZE: rc = picsong_encode_rgb_frame_rate(ctx, in.d, g, b, in.rgb_mask, target, 0, 0, d_out, out_stride, s, &r.j, r.totals); break;
+    case RGB_FRAME * 3 + PSNR: rc = picsong_encode_rgb_frame_quality(ctx, in.d, g, b, in.rgb_mask, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse); break;
+    case RGB_FRAME * 3 + SSIM:       // (there is no one-frame call: n = 1 of the n-frame one, with no frame stride)
+        rc = picsong_encode_rgb_frames_ssim(ctx, 1, in.d, g, b, 0, 0, in.rgb_mask, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse); break;
+    case RGB_FRAMES * 3 + SIZE:
+        rc = picsong_encode_rgb_frames_rate(ctx, in.n, in.d, g, b, 3 * in.stride, 0, in.rgb_mask, target, 0, 0, d_out, out_stride, s, &r.j, r.totals); break;
+    case RGB_FRAMES * 3 + PSNR:
+        rc = picsong_encode_rgb_frames_quality(ctx, in.n, in.d, g, b, 3 * in.stride, 0, in.rgb_mask, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse); break;
+    case RGB_FRAMES * 3 + SSIM:
+        rc = picsong_encode_rgb_frames_ssim(ctx, in.n, in.d, g, b, 3 * in.stride, 0, in.rgb_mask, lim, 0, 0, d_out, out_stride, s, &r.j, r.totals, sse); break;
+    }
     if (rc == PICSONG_ERR_RATE) return std::string("-rate: no quantiser meets the target size (") + picsong_last_error() + ")";
     if (rc == PICSONG_ERR_QUALITY)
         return std::string(o.has_ssim ? "-ssim" : "-psnr") + ": no quantiser meets the target quality (" + picsong_last_error() + ")";
@@ -484,46 +539,28 @@ std::string search_step(const Options &o, picsong_ctx *ctx, hipStream_t s, const
 // ---- frames a call of an RGB video (-framesPerLaunch B, else the grey path's rule on a frame's three planes of P bytes -- a
 // reduced or windowed decode: the planes it writes), at most the 21 a call of picsong_encode_rgb_frames /
 // picsong_decode_rgb_frames and the proxy calls takes and the frames there are
-int rgb_group_frames(const Options &o, size_t P, long nframes)
-{
-    long B = o.frames_per_launch > 0 ? o.frames_per_launch : (3 * P <= (size_t)3840 * 2176 ? 4 : 1);
-    if (B > 21) B = 21;
-    if (B > nframes) B = nframes;
-    return (int)(B < 1 ? 1 : B);
-}
+int rgb_group_frames(const Options &o, size_t P, long nframes) { return frames_per_launch(o.frames_per_launch, 3 * P, 21, nframes); }
 
 // The frames [f0, nframes) of an RGB video (-cp 2) in groups of B through ONE call each: picsong_encode_rgb_frames on
 // host-padded planes, or, -layout, picsong_encode_rgb_images on the frames as the file holds them -- one pinned staging
 // area and one upload a group, one read-back of the group's 3 n streams.  Streams and _SIZE entries as frame by frame.
-void encode_rgb_groups(const Options &o, picsong_ctx *ctx, hipStream_t s, std::ifstream &in, size_t file_base, long f0, long nframes,
-                       std::ofstream &out, std::ofstream &sizes, long &total_shorts)
+void encode_rgb_groups(const Options &o, picsong_ctx *ctx, hipStream_t s, int fd, size_t file_base, long f0, long nframes, StreamSink &to)
 {
     const int aw = picsong_pad_dim(o.x), ah = picsong_pad_dim(o.y);
     const size_t P = (size_t)aw * ah, max_shorts = picsong_max_stream_shorts(aw, ah);
     const int B = rgb_group_frames(o, P, nframes - f0);
     const size_t raw_bytes = o.layout >= 0 ? layout_frame_bytes(o.layout, o.x, o.y) : 0;
     const size_t frame_bytes = o.layout >= 0 ? raw_bytes : 3 * P;        // a frame of the staging area
-    uint8_t *h_in = nullptr, *d_in = nullptr;
-    uint16_t *h_out = nullptr, *d_out = nullptr;
-    HIPCK(hipHostMalloc(&h_in, frame_bytes * (size_t)B));
-    HIPCK(hipMalloc(&d_in, frame_bytes * (size_t)B));
-    HIPCK(hipHostMalloc(&h_out, max_shorts * 2 * 3 * (size_t)B));
-    HIPCK(hipMalloc(&d_out, max_shorts * 2 * 3 * (size_t)B));
+    const auto h_in = pinned_alloc<uint8_t>(frame_bytes * (size_t)B);
+    const auto d_in = dev_alloc<uint8_t>(frame_bytes * (size_t)B);
+    const auto h_out = pinned_alloc<uint16_t>(max_shorts * 2 * 3 * (size_t)B);
+    const auto d_out = dev_alloc<uint16_t>(max_shorts * 2 * 3 * (size_t)B);
     std::vector<uint8_t> raw((size_t)o.x * o.y);
     std::vector<int> totals(3 * (size_t)B);
     for (long f = f0; f < nframes; f += B) {
         const int n = (int)std::min<long>(B, nframes - f);
-        if (o.layout >= 0) {
-            in.clear();
-            in.seekg((std::streamoff)(file_base + (size_t)f * raw_bytes));
-            in.read(reinterpret_cast<char *>(h_in), (std::streamsize)(raw_bytes * (size_t)n));
-            if ((size_t)in.gcount() != raw_bytes * (size_t)n) die("Input file is shorter than the requested frames.");
-        } else {
-            for (int j = 0; j < 3 * n; j++) {
-                if (!read_frame(in, file_base, (size_t)(f * 3 + j), o.x, o.y, raw.data())) die("Input file is shorter than the requested frames.");
-                CK(picsong_pad_frame_host(raw.data(), o.x, o.y, h_in + (size_t)j * P, aw, ah));
-            }
-        }
+        const std::string err = stage_frames(o, fd, file_base, f, n, 3, h_in, raw.data());
+        if (!err.empty()) die(err);
         HIPCK(hipMemcpyAsync(d_in, h_in, frame_bytes * (size_t)n, hipMemcpyHostToDevice, s));
         if (o.layout >= 0) {
             const picsong_image im = layout_image(o.layout, d_in, o.x, o.y);
@@ -532,92 +569,33 @@ void encode_rgb_groups(const Options &o, picsong_ctx *ctx, hipStream_t s, std::i
             CK(picsong_encode_rgb_frames(ctx, n, d_in, d_in + P, d_in + 2 * P, 3 * P, (int)f, 7, d_out, max_shorts, s));
         }
         CK(picsong_last_totals(ctx, s, 3 * n, totals.data()));
-        size_t at = 0;                                   // the group's streams back to back in the pinned buffer
-        for (int j = 0; j < 3 * n; j++) {
-            HIPCK(hipMemcpyAsync(h_out + at, d_out + (size_t)j * max_shorts, (size_t)totals[(size_t)j] * 2, hipMemcpyDeviceToHost, s));
-            at += (size_t)totals[(size_t)j];
-        }
-        HIPCK(hipStreamSynchronize(s));                  // (h_in is free for the next group too)
-        out.write(reinterpret_cast<const char *>(h_out), (std::streamsize)(at * 2));
-        for (int j = 0; j < 3 * n; j++) {
-            if (f == 0 && j == 0) sizes << totals[(size_t)j]; else sizes << "," << totals[(size_t)j];
-            total_shorts += totals[(size_t)j];
-        }
+        collect_streams(s, d_out, max_shorts, totals.data(), 3 * n, h_out, to);      // (its wait frees h_in for the next group too)
     }
-    (void)hipHostFree(h_in); (void)hipFree(d_in); (void)hipHostFree(h_out); (void)hipFree(d_out);
 }
 
-// -searchFrames N on an RGB video (-cp 2): the -rate / -psnr search over the first n frames through ONE call
-// (picsong_encode_rgb_frames_rate / _quality) on host-padded planes or, -layout, on the planes one picsong_ingest_frames
-// makes of the frames as the file holds them.  The n frames' streams are the call's own output, written here with their
-// _SIZE entries; returns the chosen qs -- the caller re-tunes the context and continues behind frame n - 1.
-float rgb_search_frames(const Options &o, picsong_ctx *ctx, hipStream_t s, std::ifstream &in, size_t file_base, int n, std::ofstream &out,
-                        std::ofstream &sizes, long &total_shorts)
+// -searchFrames N on an RGB video (-cp 2): the -rate / -psnr / -ssim search over the first n frames through ONE call
+// (search_step, RGB_FRAMES) on host-padded planes or, -layout, on the planes one picsong_ingest_frames makes of the frames
+// as the file holds them.  The n frames' streams are the call's own output, written here with their _SIZE entries;
+// returns the chosen qs -- the caller re-tunes the context and continues behind frame n - 1.
+float rgb_search_frames(const Options &o, picsong_ctx *ctx, hipStream_t s, int fd, size_t file_base, int n, StreamSink &to)
 {
     const int aw = picsong_pad_dim(o.x), ah = picsong_pad_dim(o.y);
     const size_t P = (size_t)aw * ah, max_shorts = picsong_max_stream_shorts(aw, ah);
     const size_t raw_bytes = o.layout >= 0 ? layout_frame_bytes(o.layout, o.x, o.y) : 0;
-    const size_t frame_bytes = o.layout >= 0 ? raw_bytes : 3 * P;
-    uint8_t *h_in = nullptr, *d_raw = nullptr, *d_pad = nullptr;
-    uint16_t *h_out = nullptr, *d_out = nullptr;
-    HIPCK(hipHostMalloc(&h_in, frame_bytes * (size_t)n));
-    HIPCK(hipMalloc(&d_pad, 3 * P * (size_t)n));
-    HIPCK(hipHostMalloc(&h_out, max_shorts * 2 * 3 * (size_t)n));
-    HIPCK(hipMalloc(&d_out, max_shorts * 2 * 3 * (size_t)n));
-    if (o.layout >= 0) {
-        in.clear();
-        in.seekg((std::streamoff)file_base);
-        in.read(reinterpret_cast<char *>(h_in), (std::streamsize)(raw_bytes * (size_t)n));
-        if ((size_t)in.gcount() != raw_bytes * (size_t)n) die("Input file is shorter than the requested frames.");
-        HIPCK(hipMalloc(&d_raw, raw_bytes * (size_t)n));
-        HIPCK(hipMemcpyAsync(d_raw, h_in, raw_bytes * (size_t)n, hipMemcpyHostToDevice, s));
-        const picsong_image im = layout_image(o.layout, d_raw, o.x, o.y);
-        CK(picsong_ingest_frames(ctx, n, &im, raw_bytes, d_pad, 3 * P, s));
-    } else {
-        std::vector<uint8_t> raw((size_t)o.x * o.y);
-        for (int j = 0; j < 3 * n; j++) {
-            if (!read_frame(in, file_base, (size_t)j, o.x, o.y, raw.data())) die("Input file is shorter than the requested frames.");
-            CK(picsong_pad_frame_host(raw.data(), o.x, o.y, h_in + (size_t)j * P, aw, ah));
-        }
-        HIPCK(hipMemcpyAsync(d_pad, h_in, 3 * P * (size_t)n, hipMemcpyHostToDevice, s));
-    }
-    const size_t target = rate_target_shorts(o) * (size_t)n;
-    const uint64_t samples = (uint64_t)o.x * (uint64_t)o.y * 3ull * (uint64_t)n;
-    uint64_t lim = 0;
-    if (o.has_psnr && picsong_psnr_to_sse(o.psnr, samples, &lim) != PICSONG_OK) die(std::string("-psnr: ") + picsong_last_error());
-    std::vector<int> totals(3 * (size_t)n, 0);
-    std::vector<uint64_t> sse(3 * (size_t)n, 0);
-    int j = 0;
-    float qs = 0.0f;
-    uint64_t windows = 0;
-    if (o.has_ssim) lim = ssim_limit(o, 3ull * (uint64_t)n, windows);
-    const int rc = o.has_ssim ? picsong_encode_rgb_frames_ssim(ctx, n, d_pad, d_pad + P, d_pad + 2 * P, 3 * P, 0, 7, lim, 0, 0, d_out, max_shorts,
-                                                               s, &j, totals.data(), sse.data())
-                 : o.has_psnr ? picsong_encode_rgb_frames_quality(ctx, n, d_pad, d_pad + P, d_pad + 2 * P, 3 * P, 0, 7, lim, 0, 0, d_out, max_shorts,
-                                                                  s, &j, totals.data(), sse.data())
-                              : picsong_encode_rgb_frames_rate(ctx, n, d_pad, d_pad + P, d_pad + 2 * P, 3 * P, 0, 7, target, 0, 0, d_out, max_shorts,
-                                                               s, &j, totals.data());
-    if (rc == PICSONG_ERR_RATE) die(std::string("-rate: no quantiser meets the target size (") + picsong_last_error() + ")");
-    if (rc == PICSONG_ERR_QUALITY)
-        die(std::string(o.has_ssim ? "-ssim" : "-psnr") + ": no quantiser meets the target quality (" + picsong_last_error() + ")");
-    if (rc != PICSONG_OK || picsong_rate_qs(j, &qs) != PICSONG_OK) die(std::string("The quantiser search failed: ") + picsong_last_error());
-    if (o.has_ssim) ssim_report(j, qs, lim, windows, n, sse.data(), 3 * n);
-    else if (o.has_psnr) quality_report(j, qs, lim, samples, n, sse.data(), 3 * n);
-    else rate_report_choice(j, qs, target, n);
-    size_t at = 0;
-    for (int z = 0; z < 3 * n; z++) {
-        HIPCK(hipMemcpyAsync(h_out + at, d_out + (size_t)z * max_shorts, (size_t)totals[(size_t)z] * 2, hipMemcpyDeviceToHost, s));
-        at += (size_t)totals[(size_t)z];
-    }
-    HIPCK(hipStreamSynchronize(s));
-    out.write(reinterpret_cast<const char *>(h_out), (std::streamsize)(at * 2));
-    for (int z = 0; z < 3 * n; z++) {
-        if (z == 0) sizes << totals[(size_t)z]; else sizes << "," << totals[(size_t)z];
-        total_shorts += totals[(size_t)z];
-    }
-    (void)hipHostFree(h_in); (void)hipFree(d_pad); (void)hipHostFree(h_out); (void)hipFree(d_out);
-    if (d_raw) (void)hipFree(d_raw);
-    return qs;
+    const auto h_in = pinned_alloc<uint8_t>((o.layout >= 0 ? raw_bytes : 3 * P) * (size_t)n);
+    const auto d_pad = dev_alloc<uint8_t>(3 * P * (size_t)n);
+    const auto h_out = pinned_alloc<uint16_t>(max_shorts * 2 * 3 * (size_t)n);
+    const auto d_out = dev_alloc<uint16_t>(max_shorts * 2 * 3 * (size_t)n);
+    Dev<uint8_t> d_raw;
+    if (o.layout >= 0) d_raw = dev_alloc<uint8_t>(raw_bytes * (size_t)n);
+    std::vector<uint8_t> raw((size_t)o.x * o.y);
+    std::string err = stage_frames(o, fd, file_base, 0, n, 3, h_in, raw.data());
+    if (err.empty()) err = upload_frames(o, ctx, s, h_in, n, 3, d_raw, d_pad);
+    SearchChoice r;
+    if (err.empty()) err = search_step(o, ctx, s, { RGB_FRAMES, d_pad, P, n, 7 }, d_out, max_shorts, r);
+    if (!err.empty()) die(err);
+    collect_streams(s, d_out, max_shorts, r.totals, 3 * n, h_out, to);
+    return r.qs;
 }
 
 // ---- RGB coding (CodingEngine::runImage / runVideo, RGB branches: CodingEngine.cu:598-633,676-712,
@@ -631,32 +609,28 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
     const int aw = picsong_pad_dim(o.x), ah = picsong_pad_dim(o.y);
     const size_t P = (size_t)aw * ah, max_shorts = picsong_max_stream_shorts(aw, ah);
     picsong_params params = make_params(o);
-    picsong_ctx *ctx = nullptr;
-    CK(picsong_ctx_create(&params, o.device, &ctx));
+    Ctx ctx;
+    CK(picsong_ctx_create(&params, o.device, &ctx.p));
     load_lut(ctx, o, o.wl, 3, o.k, o.cp);
-    hipStream_t s;
-    HIPCK(hipStreamCreate(&s));
-    uint8_t *h_in, *d_in[3], *d_raw = nullptr;
-    void *d_c[3];
-    uint16_t *h_out, *d_out;
-    // -layout: the frame of the file as it is, pinned and on the device; the three padded planes are made there
+    const Stream s = stream_create();
+    // a frame's three padded planes, back to back pinned and on the device; -layout: the frame of the file as it is,
+    // pinned and on the device, where the planes are then made
     const size_t raw_bytes = o.layout >= 0 ? layout_frame_bytes(o.layout, o.x, o.y) : 0;
-    HIPCK(hipHostMalloc(&h_in, raw_bytes > P ? raw_bytes : P));
-    HIPCK(hipMalloc(&d_in[0], 3 * P));
-    d_in[1] = d_in[0] + P; d_in[2] = d_in[0] + 2 * P;
-    if (o.layout >= 0) HIPCK(hipMalloc(&d_raw, raw_bytes));
-    for (int c = 0; c < 3; c++) HIPCK(hipMalloc(&d_c[c], P * 4));
+    const auto h_in = pinned_alloc<uint8_t>(std::max(raw_bytes, 3 * P));
+    const auto d_in = dev_alloc<uint8_t>(3 * P);
+    Dev<uint8_t> d_raw;
+    if (o.layout >= 0) d_raw = dev_alloc<uint8_t>(raw_bytes);
+    Dev<char> d_c[3];
+    for (int c = 0; c < 3; c++) d_c[c] = dev_alloc<char>(P * 4);
     // the three components of a frame through ONE launch per stage (picsong_encode_rgb_frame) wherever the library
-    // offers it: -cp 2, k = 0; otherwise plane by plane
+    // offers it: -cp 2; otherwise plane by plane
     const bool batched = o.cp != 3;
-    HIPCK(hipHostMalloc(&h_out, max_shorts * 2));
-    HIPCK(hipMalloc(&d_out, max_shorts * 2 * (batched ? 3 : 1)));
+    const auto h_out = pinned_alloc<uint16_t>(max_shorts * 2 * (batched ? 3 : 1));
+    const auto d_out = dev_alloc<uint16_t>(max_shorts * 2 * (batched ? 3 : 1));
     std::vector<uint8_t> raw((size_t)o.x * o.y);
-    std::ifstream in(o.input, std::ios::binary);
-    if (!in) die("Cannot open input file " + o.input);
-    std::ofstream out(o.output, std::ios::binary | std::ios::app);
-    std::ofstream sizes(o.output + "_SIZE", std::ios::binary | std::ios::app);
-    long total_shorts = 0;
+    const int fd = open(o.input.c_str(), O_RDONLY);
+    if (fd < 0) die("Cannot open input file " + o.input);
+    StreamSink to(o.output);
     auto t0 = std::chrono::steady_clock::now();
     // a video (-cp 2): groups of frames through one call each (encode_rgb_groups) -- behind the first frame where that one
     // carries the -rate / -psnr search; an image and -cp 3: frame by frame, here
@@ -665,66 +639,47 @@ int run_encode_rgb(const Options &o, size_t file_base, long nframes)
     long searched = 0;                                   // -searchFrames: the frames the n-frame search call coded itself
     if (grouped && o.search_frames > 0) {
         searched = std::min<long>(o.search_frames, nframes);
-        CK(picsong_ctx_set_qs(ctx, rgb_search_frames(o, ctx, s, in, file_base, (int)searched, out, sizes, total_shorts)));
+        CK(picsong_ctx_set_qs(ctx, rgb_search_frames(o, ctx, s, fd, file_base, (int)searched, to)));
         nloop = 0;
     }
     for (long f = 0; f < nloop; f++) {
+        const std::string short_input = stage_frames(o, fd, file_base, f, 1, 3, h_in, raw.data());
+        if (!short_input.empty()) die(short_input);
         if (o.layout >= 0) {
-            in.clear();
-            in.seekg((std::streamoff)(file_base + (size_t)f * raw_bytes));
-            in.read(reinterpret_cast<char *>(h_in), (std::streamsize)raw_bytes);
-            if ((size_t)in.gcount() != raw_bytes) die("Input file is shorter than the requested frames.");
             HIPCK(hipMemcpyAsync(d_raw, h_in, raw_bytes, hipMemcpyHostToDevice, s));
             const picsong_image im = layout_image(o.layout, d_raw, o.x, o.y);
-            CK(picsong_ingest_frames(ctx, 1, &im, 0, d_in[0], 0, s));
-            HIPCK(hipStreamSynchronize(s));              // h_in is reused for the next frame
+            CK(picsong_ingest_frames(ctx, 1, &im, 0, d_in, 0, s));
+        } else {
+            HIPCK(hipMemcpyAsync(d_in, h_in, 3 * P, hipMemcpyHostToDevice, s));
         }
-        for (int c = 0; c < 3 && o.layout < 0; c++) {
-            if (!read_frame(in, file_base, (size_t)(f * 3 + c), o.x, o.y, raw.data())) die("Input file is shorter than the requested frames.");
-            CK(picsong_pad_frame_host(raw.data(), o.x, o.y, h_in, aw, ah));
-            HIPCK(hipMemcpyAsync(d_in[c], h_in, P, hipMemcpyHostToDevice, s));
-            HIPCK(hipStreamSynchronize(s));          // h_in is reused for the next plane
-        }
+        HIPCK(hipStreamSynchronize(s));                  // h_in is reused for the next frame
         int totals[3] = { 0, 0, 0 };
         if ((o.has_rate || o.has_quality()) && f == 0) {
             // the search on the first frame (an image: the frame); the rest of a video is coded at the result
             SearchChoice r;
-            const std::string err = search_step(o, ctx, s, { d_in[0], P, 1, o.video ? 7 : 1 }, d_out, max_shorts, r);
+            const std::string err = search_step(o, ctx, s, { RGB_FRAME, d_in, P, 1, o.video ? 7 : 1 }, d_out, max_shorts, r);
             if (!err.empty()) die(err);
             CK(picsong_ctx_set_qs(ctx, r.qs));
             std::copy(r.totals, r.totals + 3, totals);
         } else if (batched) {
-            CK(picsong_encode_rgb_frame(ctx, d_in[0], d_in[1], d_in[2], o.video ? (f == 0 ? 7 : 0) : 1, d_out, max_shorts, s));
+            CK(picsong_encode_rgb_frame(ctx, d_in, d_in + P, d_in + 2 * P, o.video ? (f == 0 ? 7 : 0) : 1, d_out, max_shorts, s));
             CK(picsong_last_totals(ctx, s, 3, totals));
         } else {
-            CK(picsong_rgb_forward(ctx, d_in[0], d_in[1], d_in[2], d_c[0], d_c[1], d_c[2], s));
+            CK(picsong_rgb_forward(ctx, d_in, d_in + P, d_in + 2 * P, d_c[0], d_c[1], d_c[2], s));
         }
-        for (int c = 0; c < 3; c++) {
-            int total = totals[c];
-            if (!batched) {
-                const int with_header = o.video ? (f == 0) : (c == 0);
-                CK(picsong_encode_plane(ctx, d_c[c], c, with_header, d_out, s));
-                CK(picsong_last_total(ctx, s, &total));
-            }
-            HIPCK(hipMemcpyAsync(h_out, d_out + (batched ? (size_t)c * max_shorts : 0), (size_t)total * 2, hipMemcpyDeviceToHost, s));
-            HIPCK(hipStreamSynchronize(s));
-            out.write(reinterpret_cast<const char *>(h_out), (std::streamsize)total * 2);
-            if (f == 0 && c == 0) sizes << total; else sizes << "," << total;
-            total_shorts += total;
+        if (batched) collect_streams(s, d_out, max_shorts, totals, 3, h_out, to);
+        for (int c = 0; c < 3 && !batched; c++) {
+            CK(picsong_encode_plane(ctx, d_c[c], c, o.video ? (f == 0) : (c == 0), d_out, s));
+            CK(picsong_last_total(ctx, s, &totals[c]));
+            collect_streams(s, d_out, 0, &totals[c], 1, h_out, to);
         }
     }
-    if (grouped && std::max(nloop, searched) < nframes)
-        encode_rgb_groups(o, ctx, s, in, file_base, std::max(nloop, searched), nframes, out, sizes, total_shorts);
+    if (grouped && std::max(nloop, searched) < nframes) encode_rgb_groups(o, ctx, s, fd, file_base, std::max(nloop, searched), nframes, to);
+    close(fd);
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::cout << "The time spent with the app without considering allocation periods is: " << sec << std::endl;
-    if (o.has_rate) rate_report_achieved(o, total_shorts, nframes);
-    write_metrics(o, "encode_rgb", nframes, sec, 0, 0, 0, total_shorts);
-    picsong_ctx_destroy(ctx);
-    (void)hipStreamDestroy(s);
-    (void)hipHostFree(h_in); (void)hipHostFree(h_out); (void)hipFree(d_out);
-    (void)hipFree(d_in[0]);
-    if (d_raw) (void)hipFree(d_raw);
-    for (int c = 0; c < 3; c++) (void)hipFree(d_c[c]);
+    if (o.has_rate) rate_report_achieved(o, to.total_shorts, nframes);
+    write_metrics(o, "encode_rgb", nframes, sec, 0, 0, 0, to.total_shorts);
     return 0;
 }
 
@@ -738,8 +693,8 @@ int run_train(const Options &o, size_t file_base, long nframes)
     const int aw = picsong_pad_dim(o.x), ah = picsong_pad_dim(o.y), comps = o.is_rgb ? 3 : 1;
     const size_t P = (size_t)aw * ah;
     picsong_params params = make_params(o);
-    picsong_ctx *ctx = nullptr;
-    CK(picsong_ctx_create(&params, o.device, &ctx));
+    Ctx ctx;
+    CK(picsong_ctx_create(&params, o.device, &ctx.p));
     // the geometry counted for: the prior folder's, or the shipped folders' 15 / 3 / 1 / 4 / 9 / 7
     picsong_lut_info geo;
     memset(&geo, 0, sizeof geo);
@@ -757,25 +712,19 @@ int run_train(const Options &o, size_t file_base, long nframes)
     CK(picsong_train_begin(ctx, &geo));
     picsong_lut_info info;
     CK(picsong_train_info(ctx, &info));
-    int B = o.frames_per_launch > 0 ? o.frames_per_launch : (P <= (size_t)3840 * 2176 ? 4 : 1);
-    if (o.is_rgb) B = 3;                                    // (the three planes of a frame)
-    if (B > 16) B = 16;
-    hipStream_t s;
-    HIPCK(hipStreamCreate(&s));
-    uint8_t *h_in, *d_in;
-    HIPCK(hipHostMalloc(&h_in, P * B));
-    HIPCK(hipMalloc(&d_in, P * B));
-    std::vector<uint8_t> raw((size_t)o.x * o.y);
-    std::ifstream in(o.input, std::ios::binary);
-    if (!in) die("Cannot open input file " + o.input);
-    auto t0 = std::chrono::steady_clock::now();
     const long planes = nframes * comps;
+    const int B = o.is_rgb ? 3 : frames_per_launch(o.frames_per_launch, P, 16, planes);      // (RGB: the three planes of a frame)
+    const Stream s = stream_create();
+    const auto h_in = pinned_alloc<uint8_t>(P * B);
+    const auto d_in = dev_alloc<uint8_t>(P * B);
+    std::vector<uint8_t> raw((size_t)o.x * o.y);
+    const int fd = open(o.input.c_str(), O_RDONLY);
+    if (fd < 0) die("Cannot open input file " + o.input);
+    auto t0 = std::chrono::steady_clock::now();
     for (long f = 0; f < planes; f += B) {
         const int n = (int)std::min<long>(B, planes - f);
-        for (int j = 0; j < n; j++) {
-            if (!read_frame(in, file_base, (size_t)(f + j), o.x, o.y, raw.data())) die("Input file is shorter than the requested frames.");
-            CK(picsong_pad_frame_host(raw.data(), o.x, o.y, h_in + (size_t)j * P, aw, ah));
-        }
+        const std::string err = stage_frames(o, fd, file_base, f, n, 1, h_in, raw.data());      // (-layout is refused with -train)
+        if (!err.empty()) die(err);
         HIPCK(hipMemcpyAsync(d_in, h_in, P * n, hipMemcpyHostToDevice, s));
         if (o.is_rgb) CK(picsong_train_rgb_frame(ctx, d_in, d_in + P, d_in + 2 * P, s));
         else CK(picsong_train_frames(ctx, n, d_in, P, s));
@@ -807,9 +756,7 @@ int run_train(const Options &o, size_t file_base, long nframes)
     std::cout << "The time spent with the app without considering allocation periods is: " << sec << std::endl;
     write_metrics(o, "train", nframes, sec, 0, 0, 0, 0);
     CK(picsong_train_end(ctx));
-    picsong_ctx_destroy(ctx);
-    (void)hipStreamDestroy(s);
-    (void)hipHostFree(h_in); (void)hipFree(d_in);
+    close(fd);
     return 0;
 }
 
@@ -838,26 +785,22 @@ int run_encode_deep(const Options &o, const Pgm &pgm)
     {
         std::ifstream in(o.input, std::ios::binary);
         if (!in) die("Cannot open input file " + o.input);
-        in.seekg((std::streamoff)(pgm.is_pgm ? pgm.offset : 0));
-        in.read(reinterpret_cast<char *>(img.data()), (std::streamsize)(n * 2));
-        if ((size_t)in.gcount() != n * 2) die("Input file is shorter than the requested frames.");
+        if (!read_exact(in, img.data(), n * 2, pgm.is_pgm ? pgm.offset : 0)) die(kShortInput);
         // (Netpbm: a PGM's two-byte samples are big-endian; a raw file's are little-endian, the host's order)
         if (pgm.is_pgm) for (uint16_t &v : img) v = (uint16_t)((v >> 8) | (v << 8));
     }
     HIPCK(hipSetDevice(o.device));
     picsong_params p = make_params(o);
     p.frames = 0;
-    picsong_ctx *ctx = nullptr;
-    CK(picsong_ctx_create(&p, o.device, &ctx));
+    Ctx ctx;
+    CK(picsong_ctx_create(&p, o.device, &ctx.p));
     load_lut(ctx, o, o.wl, 1, o.k, o.cp);
     int aw, ah, ncb;
     CK(picsong_ctx_padded_dims(ctx, &aw, &ah, &ncb));
     const size_t max_shorts = picsong_max_stream_shorts(aw, ah);
-    hipStream_t s;
-    HIPCK(hipStreamCreate(&s));
-    uint16_t *d_raw = nullptr, *d_out = nullptr;
-    HIPCK(hipMalloc(&d_raw, n * 2));
-    HIPCK(hipMalloc(&d_out, max_shorts * 2));
+    const Stream s = stream_create();
+    const auto d_raw = dev_alloc<uint16_t>(n * 2);
+    const auto d_out = dev_alloc<uint16_t>(max_shorts * 2);
     std::vector<uint16_t> out(max_shorts);
     auto t0 = std::chrono::steady_clock::now();
     HIPCK(hipMemcpyAsync(d_raw, img.data(), n * 2, hipMemcpyHostToDevice, s));
@@ -879,10 +822,19 @@ int run_encode_deep(const Options &o, const Pgm &pgm)
     }
     std::cout << "The time spent with the app without considering allocation periods is: " << sec << std::endl;
     write_metrics(o, "encode", 1, sec, 0, 0, 0, total);
-    picsong_ctx_destroy(ctx);
-    (void)hipStreamDestroy(s);
-    (void)hipFree(d_raw); (void)hipFree(d_out);
     return 0;
+}
+
+// ---- what -rate, -psnr and -ssim refuse alike, in this order; with_rate / with_psnr: that flag is given too and wins
+void check_search_flag(const Options &o, const std::string &flag, bool with_rate, bool with_psnr)
+{
+    const std::string pre = "Incorrect parameters. " + flag;
+    if (o.has_qs) die(pre + " chooses the quantiser: it cannot be combined with -qs.");
+    if (with_rate) die(pre + " cannot be combined with -rate.");
+    if (with_psnr) die(pre + " cannot be combined with -psnr.");
+    if (o.type != 1) die(pre + " applies to lossy coding (-type 1) only.");
+    if (o.cp == 3) die(pre + " does not apply to -cp 3.");
+    if (!o.train.empty()) die(pre + " does not apply to -train.");
 }
 
 // ---- coding engine: CodingEngine::runImage / runVideo call sequence ---------------------------
@@ -904,26 +856,10 @@ int run_encode(Options o)
     if (o.signed_or_unsigned != 0 || o.bps != 8) return run_encode_deep(o, pgm);
     const long nframes = o.video ? o.frames : 1;
     if (nframes <= 0) die("Incorrect parameters. Please choose valid values. (-frames)");
-    if (o.has_rate) {
-        if (o.has_qs) die("Incorrect parameters. -rate chooses the quantiser: it cannot be combined with -qs.");
-        if (o.type != 1) die("Incorrect parameters. -rate applies to lossy coding (-type 1) only.");
-        if (o.cp == 3) die("Incorrect parameters. -rate does not apply to -cp 3.");
-        if (!o.train.empty()) die("Incorrect parameters. -rate does not apply to -train.");
-    }
-    if (o.has_psnr) {
-        if (o.has_qs) die("Incorrect parameters. -psnr chooses the quantiser: it cannot be combined with -qs.");
-        if (o.has_rate) die("Incorrect parameters. -psnr cannot be combined with -rate.");
-        if (o.type != 1) die("Incorrect parameters. -psnr applies to lossy coding (-type 1) only.");
-        if (o.cp == 3) die("Incorrect parameters. -psnr does not apply to -cp 3.");
-        if (!o.train.empty()) die("Incorrect parameters. -psnr does not apply to -train.");
-    }
+    if (o.has_rate) check_search_flag(o, "-rate", false, false);
+    if (o.has_psnr) check_search_flag(o, "-psnr", o.has_rate, false);
     if (o.has_ssim) {
-        if (o.has_qs) die("Incorrect parameters. -ssim chooses the quantiser: it cannot be combined with -qs.");
-        if (o.has_rate) die("Incorrect parameters. -ssim cannot be combined with -rate.");
-        if (o.has_psnr) die("Incorrect parameters. -ssim cannot be combined with -psnr.");
-        if (o.type != 1) die("Incorrect parameters. -ssim applies to lossy coding (-type 1) only.");
-        if (o.cp == 3) die("Incorrect parameters. -ssim does not apply to -cp 3.");
-        if (!o.train.empty()) die("Incorrect parameters. -ssim does not apply to -train.");
+        check_search_flag(o, "-ssim", o.has_rate, o.has_psnr);
         if (o.x < 8 || o.y < 8) die("Incorrect parameters. -ssim needs a frame of 8 x 8 samples or more.");
     }
     if (o.search_frames > 0) {
@@ -961,11 +897,7 @@ int run_encode(Options o)
     const int ndevs = (int)devs.size();
     const int aw = picsong_pad_dim(o.x), ah = picsong_pad_dim(o.y);
     const size_t P = (size_t)aw * ah, max_shorts = picsong_max_stream_shorts(aw, ah);
-    // frames per launch: a 4K frame is 1020 coder waves, one per SIMD; four of them fill the GPU like an 8K frame
-    int B = o.frames_per_launch > 0 ? o.frames_per_launch : (P <= (size_t)3840 * 2176 ? 4 : 1);
-    if (!o.video || o.cp == 3) B = 1;
-    if (B > 16) B = 16;
-    if ((long)B > nframes) B = (int)nframes;
+    const int B = (!o.video || o.cp == 3) ? 1 : frames_per_launch(o.frames_per_launch, P, 16, nframes);
     const long ngroups = (nframes + B - 1) / B;
     // slots of the pipeline: at least 6 for a video (2 readers | launch | run | collect | 2 writers overlap),
     // a multiple of the device count so that slot i always belongs to device i mod ndevs
@@ -974,23 +906,22 @@ int run_encode(Options o)
     if (nstreams < ndevs) nstreams = ndevs;
 
     const size_t frame_bytes = (size_t)o.x * o.y, file_base = pgm.is_pgm ? pgm.offset : 0;
-    const bool padded_already = (o.x == aw && o.y == ah);
     picsong_params params = make_params(o);
     std::vector<Worker> w((size_t)nstreams);
     for (int i = 0; i < nstreams; i++) {
         Worker &k = w[(size_t)i];
         k.device = devs[(size_t)(i % ndevs)];
         HIPCK(hipSetDevice(k.device));
-        CK(picsong_ctx_create(&params, k.device, &k.ctx));
+        CK(picsong_ctx_create(&params, k.device, &k.ctx.p));
         if (nstreams > 1) CK(picsong_ctx_set_pipelined(k.ctx, 1));     // the video engine keeps frames in flight
         load_lut(k.ctx, o, o.wl, 1, o.k, o.cp);
-        HIPCK(hipStreamCreate(&k.stream));
-        HIPCK(hipHostMalloc(&k.h_in, P * B));
-        HIPCK(hipMalloc(&k.d_in, P * B));
-        HIPCK(hipHostMalloc(&k.h_out, max_shorts * 2 * B));
-        HIPCK(hipMalloc(&k.d_out, max_shorts * 2 * B));
-        k.h_raw = (uint8_t *)malloc(frame_bytes);
-        if (o.layout >= 0) HIPCK(hipMalloc(&k.d_raw, frame_bytes * (size_t)B));
+        k.stream = stream_create();
+        k.h_in = pinned_alloc<uint8_t>(P * B);
+        k.d_in = dev_alloc<uint8_t>(P * B);
+        k.h_out = pinned_alloc<uint16_t>(max_shorts * 2 * B);
+        k.d_out = dev_alloc<uint16_t>(max_shorts * 2 * B);
+        k.h_raw.resize(frame_bytes);
+        if (o.layout >= 0) k.d_raw = dev_alloc<uint8_t>(frame_bytes * (size_t)B);
         // stage timers (HIP events): at most kProfFrames launches per slot are timed, so the event count does
         // not grow with the video; "BPC acum time" scales their mean to all frames
         CK(picsong_profile_begin(k.ctx, (int)std::min<long>((ngroups + nstreams - 1) / nstreams, kProfFrames)));
@@ -1003,39 +934,17 @@ int run_encode(Options o)
         const int n = (int)std::min<long>(nframes, o.search_frames > 0 ? o.search_frames : 16);
         Worker &k = w[0];
         HIPCK(hipSetDevice(k.device));
-        uint8_t *h_f = nullptr, *d_f = nullptr;
-        uint16_t *d_s = nullptr;
-        HIPCK(hipHostMalloc(&h_f, P * (size_t)n));
-        HIPCK(hipMalloc(&d_f, P * (size_t)n));
-        HIPCK(hipMalloc(&d_s, max_shorts * 2 * (size_t)n));
-        std::vector<uint8_t> raw(frame_bytes);
-        for (int f = 0; f < n; f++) {
-            size_t got = 0;
-            while (got < frame_bytes) {
-                ssize_t m = pread(fd, raw.data() + got, frame_bytes - got, (off_t)(file_base + (size_t)f * frame_bytes + got));
-                if (m <= 0) break;
-                got += (size_t)m;
-            }
-            if (got != frame_bytes) die("Input file is shorter than the requested frames.");
-            if (o.layout >= 0) memcpy(h_f + (size_t)f * frame_bytes, raw.data(), frame_bytes);
-            else CK(picsong_pad_frame_host(raw.data(), o.x, o.y, h_f + (size_t)f * P, aw, ah));
-        }
-        if (o.layout >= 0) {            // the frames as read, padded on the device
-            uint8_t *d_r = nullptr;
-            HIPCK(hipMalloc(&d_r, frame_bytes * (size_t)n));
-            HIPCK(hipMemcpyAsync(d_r, h_f, frame_bytes * (size_t)n, hipMemcpyHostToDevice, k.stream));
-            const picsong_image im = layout_image(o.layout, d_r, o.x, o.y);
-            CK(picsong_ingest_frames(k.ctx, n, &im, frame_bytes, d_f, P, k.stream));
-            HIPCK(hipStreamSynchronize(k.stream));
-            (void)hipFree(d_r);
-        } else {
-            HIPCK(hipMemcpyAsync(d_f, h_f, P * (size_t)n, hipMemcpyHostToDevice, k.stream));
-        }
+        const auto h_f = pinned_alloc<uint8_t>(P * (size_t)n);
+        const auto d_f = dev_alloc<uint8_t>(P * (size_t)n);
+        const auto d_s = dev_alloc<uint16_t>(max_shorts * 2 * (size_t)n);
+        Dev<uint8_t> d_r;               // -layout: the frames as read, padded on the device
+        if (o.layout >= 0) d_r = dev_alloc<uint8_t>(frame_bytes * (size_t)n);
+        std::string err = stage_frames(o, fd, file_base, 0, n, 1, h_f, k.h_raw.data());
+        if (err.empty()) err = upload_frames(o, k.ctx, k.stream, h_f, n, 1, d_r, d_f);
         SearchChoice r;                 // the target, or the limit, over all n frames
-        const std::string err = search_step(o, k.ctx, k.stream, { d_f, P, n, 0 }, d_s, max_shorts, r);
+        if (err.empty()) err = search_step(o, k.ctx, k.stream, { GREY_FRAMES, d_f, P, n, 0 }, d_s, max_shorts, r);
         if (!err.empty()) die(err);
         for (auto &x : w) CK(picsong_ctx_set_qs(x.ctx, r.qs));
-        (void)hipHostFree(h_f); (void)hipFree(d_f); (void)hipFree(d_s);
     }
     // image: one truncating write (IOManager.ipp:615-620); video: append + _SIZE (:176-190)
     const int ofd = open(o.output.c_str(), O_WRONLY | O_CREAT | (o.video ? 0 : O_TRUNC), 0644);
@@ -1074,21 +983,7 @@ int run_encode(Options o)
             Worker &k = w[si];
             const int n = group_frames(g);
             const auto tr0 = now();
-            std::string err;
-            for (int j = 0; j < n && err.empty(); j++) {
-                const long f = g * B + j;
-                // (-layout: the frames as they are, back to back in the pinned buffer; the GPU pads them)
-                uint8_t *dst = o.layout >= 0 ? k.h_in + (size_t)j * frame_bytes : padded_already ? k.h_in + (size_t)j * P : k.h_raw;
-                size_t got = 0;
-                while (got < frame_bytes) {
-                    ssize_t m = pread(fd, dst + got, frame_bytes - got, (off_t)(file_base + (size_t)f * frame_bytes + got));
-                    if (m <= 0) break;
-                    got += (size_t)m;
-                }
-                if (got != frame_bytes) err = "Input file is shorter than the requested frames.";
-                else if (o.layout < 0 && !padded_already && picsong_pad_frame_host(k.h_raw, o.x, o.y, k.h_in + (size_t)j * P, aw, ah) != PICSONG_OK)
-                    err = picsong_last_error();
-            }
+            const std::string err = stage_frames(o, fd, file_base, g * B, n, 1, k.h_in, k.h_raw.data());
             t_read[(size_t)r] += secs(tr0, now());
             std::lock_guard<std::mutex> lk(mu);
             if (!err.empty() && failure.empty()) failure = err;
@@ -1150,15 +1045,9 @@ int run_encode(Options o)
                                    (size_t)ss.total[j] * 2, hipMemcpyDeviceToHost, w[si].stream) != hipSuccess)
                     err = "HIP error while copying a codestream back";
             if (err.empty() && hipStreamSynchronize(w[si].stream) != hipSuccess) err = "HIP error while copying a codestream back";
-            for (int j = 0; j < ss.n && err.empty(); j++) {
-                const char *src = reinterpret_cast<const char *>(w[si].h_out + (size_t)j * max_shorts);
-                size_t left = (size_t)ss.total[j] * 2, done = 0;
-                while (left) {
-                    ssize_t m = pwrite(ofd, src + done, left, ss.offset[j] + (off_t)done);
-                    if (m <= 0) { err = "Cannot write the output file " + o.output; break; }
-                    done += (size_t)m; left -= (size_t)m;
-                }
-            }
+            for (int j = 0; j < ss.n && err.empty(); j++)
+                if (!pwrite_exact(ofd, w[si].h_out + (size_t)j * max_shorts, (size_t)ss.total[j] * 2, (size_t)ss.offset[j]))
+                    err = "Cannot write the output file " + o.output;
             t_write_v[(size_t)r] += secs(tw1, now());
             std::lock_guard<std::mutex> lk(mu);
             if (!err.empty() && failure.empty()) failure = err;
@@ -1189,15 +1078,12 @@ int run_encode(Options o)
         Worker &k = w[si];
         const int n = st[si].n;
         std::string err;
-        const picsong_image im = layout_image(o.layout, k.d_raw, o.x, o.y);
-        if (hipSetDevice(k.device) != hipSuccess ||
-            (o.layout >= 0 ? hipMemcpyAsync(k.d_raw, k.h_in, frame_bytes * (size_t)n, hipMemcpyHostToDevice, k.stream)
-                           : hipMemcpyAsync(k.d_in, k.h_in, P * (size_t)n, hipMemcpyHostToDevice, k.stream)) != hipSuccess) err = "HIP error in the frame upload";
-        else if (o.layout >= 0 && picsong_ingest_frames(k.ctx, n, &im, frame_bytes, k.d_in, P, k.stream) != PICSONG_OK) err = picsong_last_error();
+        if (hipSetDevice(k.device) != hipSuccess) err = "HIP error in the frame upload";
+        else if (!(err = upload_frames(o, k.ctx, k.stream, k.h_in, n, 1, k.d_raw, k.d_in)).empty()) { }
         else if ((o.has_rate || o.has_quality()) && !o.video) {
             // an image: one search call (synchronous); its length is the context's last total, as after picsong_encode_frame
             SearchChoice r;
-            err = search_step(o, k.ctx, k.stream, { k.d_in, 0, 0, 0 }, k.d_out, 0, r);
+            err = search_step(o, k.ctx, k.stream, { GREY_FRAME, k.d_in, 0, 1, 0 }, k.d_out, 0, r);
         }
         else if (B == 1) { if (picsong_encode_frame(k.ctx, k.d_in, g == 0 ? 0 : 1, k.d_out, k.stream) != PICSONG_OK) err = picsong_last_error(); }
         else if (picsong_encode_frames(k.ctx, n, k.d_in, P, (int)(g * B), k.d_out, max_shorts, k.stream) != PICSONG_OK) err = picsong_last_error();
@@ -1211,11 +1097,7 @@ int run_encode(Options o)
     close(fd);
     close(ofd);
     if (!failure.empty()) die(failure);
-    if (o.video) {
-        // IOManager.ipp:176-190: lengths in shorts, comma separated, appended in frame order
-        std::ofstream sizes(o.output + "_SIZE", std::ios::binary | std::ios::app);
-        for (long f = 0; f < nframes; f++) { if (f) sizes << ","; sizes << frame_totals[(size_t)f]; }
-    }
+    if (o.video) SizeList(o.output + "_SIZE").append(frame_totals.data(), (size_t)nframes);      // in frame order
     for (double v : t_write_v) t_write += v;
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (!o.metrics.empty()) {
@@ -1239,27 +1121,21 @@ int run_encode(Options o)
     if (o.has_rate) rate_report_achieved(o, total_shorts, nframes);
     write_metrics(o, "encode", nframes, sec, counted ? dwt / counted / B : 0, counted ? bpc / counted / B : 0,
                   counted ? pack / counted / B : 0, total_shorts);
-    for (auto &k : w) {
-        (void)hipSetDevice(k.device);
-        picsong_ctx_destroy(k.ctx);
-        (void)hipStreamDestroy(k.stream);
-        (void)hipHostFree(k.h_in); (void)hipFree(k.d_in); (void)hipHostFree(k.h_out); (void)hipFree(k.d_out);
-        if (k.d_raw) (void)hipFree(k.d_raw);
-        free(k.h_raw);
-    }
     return 0;
 }
 
 // A decode context from a stream's header.  picsong_ctx_create keeps the coding launcher's -qs range (0, 1]; a stream coded
 // by -rate may carry any gain the header stores (up to 1.6383): such a context is created at 1 and re-tuned.
 // drop (-drop d): the context's decode setting (picsong_ctx_set_decode_drop).
-void create_decode_ctx(picsong_params p, int device, picsong_ctx **ctx, int drop = 0)
+Ctx create_decode_ctx(picsong_params p, int device, int drop = 0)
 {
+    Ctx ctx;
     const float qs = p.qs;
     if (p.lossy && qs > 1.0f) p.qs = 1.0f;
-    CK(picsong_ctx_create(&p, device, ctx));
-    if (p.lossy && qs > 1.0f) CK(picsong_ctx_set_qs(*ctx, qs));
-    if (drop > 0) CK(picsong_ctx_set_decode_drop(*ctx, drop));
+    CK(picsong_ctx_create(&p, device, &ctx.p));
+    if (p.lossy && qs > 1.0f) CK(picsong_ctx_set_qs(ctx, qs));
+    if (drop > 0) CK(picsong_ctx_set_decode_drop(ctx, drop));
+    return ctx;
 }
 
 // ---- decoding engine: DecodingEngine::runImage / runVideo call sequence -----------------------
@@ -1284,6 +1160,7 @@ struct OutDims { int r, w, h, pw, ph, win = 0, x = 0, y = 0; };
 // picsong_decode_rgb_frames_reduced; -window: picsong_decode_rgb_frames_window) into planes of od.pw x od.ph bytes, cropped
 // on the host, or, -layout (full size only), picsong_decode_rgb_images into the frames as the file takes them -- one pinned
 // staging area, one upload and one read-back a group.  The output as frame by frame.
+const char *const kShortStream = "Input file is shorter than its _SIZE sidecar says.";
 void decode_rgb_groups(const Options &o, const picsong_params &p, picsong_ctx *ctx, hipStream_t s, std::ifstream &in,
                        const std::vector<long> &shorts, long nframes, int aw, int ah, const OutDims &od)
 {
@@ -1293,12 +1170,10 @@ void decode_rgb_groups(const Options &o, const picsong_params &p, picsong_ctx *c
     const int B = rgb_group_frames(og, P, nframes);
     const size_t raw_bytes = o.layout >= 0 ? layout_frame_bytes(o.layout, p.width, p.height) : 0;
     const size_t frame_bytes = o.layout >= 0 ? raw_bytes : 3 * P;        // a frame of the pixel side
-    uint16_t *h_in = nullptr, *d_in = nullptr;
-    uint8_t *h_pix = nullptr, *d_pix = nullptr;
-    HIPCK(hipHostMalloc(&h_in, max_shorts * 2 * 3 * (size_t)B));
-    HIPCK(hipMalloc(&d_in, max_shorts * 2 * 3 * (size_t)B));
-    HIPCK(hipHostMalloc(&h_pix, frame_bytes * (size_t)B));
-    HIPCK(hipMalloc(&d_pix, frame_bytes * (size_t)B));
+    const auto h_in = pinned_alloc<uint16_t>(max_shorts * 2 * 3 * (size_t)B);
+    const auto d_in = dev_alloc<uint16_t>(max_shorts * 2 * 3 * (size_t)B);
+    const auto h_pix = pinned_alloc<uint8_t>(frame_bytes * (size_t)B);
+    const auto d_pix = dev_alloc<uint8_t>(frame_bytes * (size_t)B);
     std::vector<uint8_t> crop((size_t)od.w * od.h);
     std::ofstream out(o.output, std::ios::binary | std::ios::app);
     size_t pos = 0;
@@ -1311,10 +1186,7 @@ void decode_rgb_groups(const Options &o, const picsong_params &p, picsong_ctx *c
             if (len > max_shorts) die("Component codestream longer than the maximum for this geometry.");
             group += len;
         }
-        in.clear();
-        in.seekg((std::streamoff)(pos * 2));
-        in.read(reinterpret_cast<char *>(h_in), (std::streamsize)(group * 2));
-        if ((size_t)in.gcount() != group * 2) die("Input file is shorter than its _SIZE sidecar says.");
+        if (!read_exact(in, h_in, group * 2, pos * 2)) die(kShortStream);
         pos += group;
         size_t at = 0;
         for (int j = 0; j < 3 * n; j++) {
@@ -1336,15 +1208,14 @@ void decode_rgb_groups(const Options &o, const picsong_params &p, picsong_ctx *c
         HIPCK(hipMemcpyAsync(h_pix, d_pix, frame_bytes * (size_t)n, hipMemcpyDeviceToHost, s));
         HIPCK(hipStreamSynchronize(s));
         if (o.layout >= 0) {
-            out.write(reinterpret_cast<const char *>(h_pix), (std::streamsize)(raw_bytes * (size_t)n));
+            out.write(reinterpret_cast<const char *>(h_pix.p), (std::streamsize)(raw_bytes * (size_t)n));
             continue;
         }
         for (int j = 0; j < 3 * n; j++) {
-            for (int y = 0; y < od.h; y++) memcpy(&crop[(size_t)y * od.w], h_pix + (size_t)j * P + (size_t)y * od.pw, (size_t)od.w);
+            crop_rows(crop.data(), h_pix + (size_t)j * P, od.w, od.h, (size_t)od.pw);
             out.write(reinterpret_cast<const char *>(crop.data()), (std::streamsize)crop.size());
         }
     }
-    (void)hipHostFree(h_in); (void)hipFree(d_in); (void)hipHostFree(h_pix); (void)hipFree(d_pix);
 }
 
 int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, std::ifstream &in,
@@ -1352,22 +1223,19 @@ int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, 
 {
     const size_t P = (size_t)aw * ah, max_shorts = picsong_max_stream_shorts(aw, ah);
     const size_t extra = picsong_dwt_extra(aw, ah, p.wl);
-    hipStream_t s;
-    HIPCK(hipStreamCreate(&s));
-    uint16_t *h_in, *d_in;
-    uint8_t *h_pix, *d_pix[3];
-    char *d_plane[3];
+    const Stream s = stream_create();
     const bool batched = p.cp != 3;      // (picsong_decode_rgb_frame: one launch per stage for the three components)
-    HIPCK(hipHostMalloc(&h_in, max_shorts * 2));
-    HIPCK(hipMalloc(&d_in, max_shorts * 2 * (batched ? 3 : 1)));
+    const auto h_in = pinned_alloc<uint16_t>(max_shorts * 2);
+    const auto d_in = dev_alloc<uint16_t>(max_shorts * 2 * (batched ? 3 : 1));
     // -layout: the three padded planes are cropped and interleaved on the device, the frame comes back as the file takes it
     const size_t raw_bytes = o.layout >= 0 ? layout_frame_bytes(o.layout, p.width, p.height) : 0;
-    uint8_t *d_emit = nullptr;
-    HIPCK(hipHostMalloc(&h_pix, raw_bytes > P ? raw_bytes : P));
-    HIPCK(hipMalloc(&d_pix[0], 3 * P));
-    d_pix[1] = d_pix[0] + P; d_pix[2] = d_pix[0] + 2 * P;
-    if (o.layout >= 0) HIPCK(hipMalloc(&d_emit, raw_bytes));
-    for (int c = 0; c < 3; c++) HIPCK(hipMalloc(&d_plane[c], (P + extra) * 4));
+    const auto h_pix = pinned_alloc<uint8_t>(raw_bytes > P ? raw_bytes : P);
+    const auto d_pix0 = dev_alloc<uint8_t>(3 * P);
+    uint8_t *const d_pix[3] = { d_pix0, d_pix0 + P, d_pix0 + 2 * P };
+    Dev<uint8_t> d_emit;
+    if (o.layout >= 0) d_emit = dev_alloc<uint8_t>(raw_bytes);
+    Dev<char> d_plane[3];
+    for (int c = 0; c < 3; c++) d_plane[c] = dev_alloc<char>((P + extra) * 4);
     std::vector<uint8_t> crop((size_t)od.w * od.h);
     { std::ofstream trunc(o.output, std::ios::binary | std::ios::trunc); }
     auto t0 = std::chrono::steady_clock::now();
@@ -1380,10 +1248,7 @@ int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, 
         for (int c = 0; c < 3; c++) {
             const size_t n = (size_t)shorts[(size_t)(f * 3 + c)];
             if (n > max_shorts) die("Component codestream longer than the maximum for this geometry.");
-            in.clear();
-            in.seekg((std::streamoff)(pos * 2));
-            in.read(reinterpret_cast<char *>(h_in), (std::streamsize)(n * 2));
-            if ((size_t)in.gcount() != n * 2) die("Input file is shorter than its _SIZE sidecar says.");
+            if (!read_exact(in, h_in, n * 2, pos * 2)) die(kShortStream);
             pos += n;
             HIPCK(hipMemcpyAsync(d_in + (batched ? (size_t)c * max_shorts : 0), h_in, n * 2, hipMemcpyHostToDevice, s));
             if (!batched) CK(picsong_decode_plane(ctx, d_in, c, d_plane[c], s));
@@ -1405,23 +1270,17 @@ int run_decode_rgb(const Options &o, const picsong_params &p, picsong_ctx *ctx, 
             CK(picsong_emit_frames(ctx, 1, d_pix[0], 0, &im, 0, s));
             HIPCK(hipMemcpyAsync(h_pix, d_emit, raw_bytes, hipMemcpyDeviceToHost, s));
             HIPCK(hipStreamSynchronize(s));
-            out.write(reinterpret_cast<const char *>(h_pix), (std::streamsize)raw_bytes);
+            out.write(reinterpret_cast<const char *>(h_pix.p), (std::streamsize)raw_bytes);
         }
         for (int c = 0; c < 3 && o.layout < 0; c++) {
             HIPCK(hipMemcpyAsync(h_pix, d_pix[c], (size_t)od.pw * od.ph, hipMemcpyDeviceToHost, s));
             HIPCK(hipStreamSynchronize(s));
-            for (int y = 0; y < od.h; y++) memcpy(&crop[(size_t)y * od.w], h_pix + (size_t)y * od.pw, (size_t)od.w);
+            crop_rows(crop.data(), h_pix, od.w, od.h, (size_t)od.pw);
             out.write(reinterpret_cast<const char *>(crop.data()), (std::streamsize)crop.size());
         }
     }
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::cout << "The time spent with the app without considering allocation periods and I/O is: " << sec << std::endl;
-    picsong_ctx_destroy(ctx);
-    (void)hipStreamDestroy(s);
-    (void)hipHostFree(h_in); (void)hipFree(d_in); (void)hipHostFree(h_pix);
-    (void)hipFree(d_pix[0]);
-    if (d_emit) (void)hipFree(d_emit);
-    for (int c = 0; c < 3; c++) (void)hipFree(d_plane[c]);
     return 0;
 }
 
@@ -1441,15 +1300,12 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
     const int nslots = (o.streams < 3 ? 3 : o.streams) + 3;
     // groups of B consecutive frames per launch (picsong_decode_frames), as the encoder's video engine codes them:
     // a 4K frame alone is one decoder wave per SIMD
-    int B = o.frames_per_launch > 0 ? o.frames_per_launch : ((size_t)aw * ah <= (size_t)3840 * 2176 ? 4 : 1);
-    if (p.cp == 3) B = 1;
-    if (B > 16) B = 16;
-    if ((long)B > nframes) B = (int)nframes;
+    const int B = p.cp == 3 ? 1 : frames_per_launch(o.frames_per_launch, (size_t)aw * ah, 16, nframes);
     const long ngroups = (nframes + B - 1) / B;
     struct Slot {
-        picsong_ctx *ctx = nullptr; hipStream_t stream = nullptr;
-        uint16_t *h_in = nullptr, *d_in = nullptr; uint8_t *h_pix = nullptr, *d_pix = nullptr;
-        uint8_t *d_emit = nullptr;                       // -layout: the frames cropped on the device, frame_bytes apart
+        Ctx ctx; Stream stream;
+        Pinned<uint16_t> h_in; Dev<uint16_t> d_in; Pinned<uint8_t> h_pix; Dev<uint8_t> d_pix;
+        Dev<uint8_t> d_emit;                             // -layout: the frames cropped on the device, frame_bytes apart
         std::vector<uint8_t> crop;
         int state = 0; long expect = 0;
     };
@@ -1457,14 +1313,14 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
     std::vector<Slot> sl((size_t)nslots);
     for (int i = 0; i < nslots; i++) {
         Slot &k = sl[(size_t)i];
-        create_decode_ctx(p, o.device, &k.ctx, o.drop);
+        k.ctx = create_decode_ctx(p, o.device, o.drop);
         load_lut(k.ctx, o, p.wl, 1, p.k, p.cp);
-        HIPCK(hipStreamCreate(&k.stream));
-        HIPCK(hipHostMalloc(&k.h_in, max_shorts * 2 * B));
-        HIPCK(hipMalloc(&k.d_in, max_shorts * 2 * B));
-        HIPCK(hipHostMalloc(&k.h_pix, P * B));
-        HIPCK(hipMalloc(&k.d_pix, P * B));
-        if (o.layout >= 0) HIPCK(hipMalloc(&k.d_emit, frame_bytes * (size_t)B));
+        k.stream = stream_create();
+        k.h_in = pinned_alloc<uint16_t>(max_shorts * 2 * B);
+        k.d_in = dev_alloc<uint16_t>(max_shorts * 2 * B);
+        k.h_pix = pinned_alloc<uint8_t>(P * B);
+        k.d_pix = dev_alloc<uint8_t>(P * B);
+        if (o.layout >= 0) k.d_emit = dev_alloc<uint8_t>(frame_bytes * (size_t)B);
         else if (od.pw != od.w) k.crop.resize(frame_bytes);
         k.expect = i;
     }
@@ -1492,19 +1348,11 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
                 if (!failure.empty()) return;
             }
             bool short_file = false;
-            for (long f = g * B; f < nframes && f < (g + 1) * B; f++) {
-                const size_t bytes = (size_t)frame_shorts[(size_t)f] * 2;
-                char *dst = reinterpret_cast<char *>(k.h_in + (size_t)(f - g * B) * max_shorts);
-                size_t got = 0;
-                while (got < bytes) {
-                    ssize_t n = pread(ifd, dst + got, bytes - got, (off_t)(in_off[(size_t)f] * 2 + got));
-                    if (n <= 0) break;
-                    got += (size_t)n;
-                }
-                short_file = short_file || got != bytes;
-            }
+            for (long f = g * B; f < nframes && f < (g + 1) * B; f++)
+                if (!pread_exact(ifd, k.h_in + (size_t)(f - g * B) * max_shorts, (size_t)frame_shorts[(size_t)f] * 2, in_off[(size_t)f] * 2))
+                    short_file = true;
             std::lock_guard<std::mutex> lk(mu);
-            if (short_file && failure.empty()) failure = "Input file is shorter than its _SIZE sidecar says.";
+            if (short_file && failure.empty()) failure = kShortStream;
             k.state = FILLED;
             cv.notify_all();
         }
@@ -1523,15 +1371,10 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
             for (long f = g * B; err.empty() && f < nframes && f < (g + 1) * B; f++) {
                 const uint8_t *pix = k.h_pix + (size_t)(f - g * B) * (o.layout >= 0 ? frame_bytes : P), *src = pix;
                 if (o.layout < 0 && od.pw != od.w) {
-                    for (int y = 0; y < od.h; y++) memcpy(&k.crop[(size_t)y * od.w], pix + (size_t)y * od.pw, (size_t)od.w);
+                    crop_rows(k.crop.data(), pix, od.w, od.h, (size_t)od.pw);
                     src = k.crop.data();
                 }
-                size_t left = frame_bytes, done = 0;
-                while (left) {
-                    ssize_t n = pwrite(ofd, src + done, left, out_base + (off_t)((size_t)f * frame_bytes + done));
-                    if (n <= 0) { err = "Cannot write the output file " + o.output; break; }
-                    done += (size_t)n; left -= (size_t)n;
-                }
+                if (!pwrite_exact(ofd, src, frame_bytes, (size_t)out_base + (size_t)f * frame_bytes)) err = "Cannot write the output file " + o.output;
             }
             std::lock_guard<std::mutex> lk(mu);
             if (!err.empty() && failure.empty()) failure = err;
@@ -1589,12 +1432,6 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
     Options mo = o;
     mo.x = od.w; mo.y = od.h;
     write_metrics(mo, "decode", nframes, sec, 0, 0, 0, (long)in_off[(size_t)nframes]);
-    for (auto &k : sl) {
-        picsong_ctx_destroy(k.ctx);
-        (void)hipStreamDestroy(k.stream);
-        (void)hipHostFree(k.h_in); (void)hipFree(k.d_in); (void)hipHostFree(k.h_pix); (void)hipFree(k.d_pix);
-        if (k.d_emit) (void)hipFree(k.d_emit);
-    }
     return 0;
 }
 
@@ -1608,8 +1445,7 @@ int run_decode_deep(const Options &o, const picsong_params &p, std::ifstream &in
     in.seekg(0, std::ios::end);
     const size_t shorts = (size_t)in.tellg() / 2;
     HIPCK(hipSetDevice(o.device));
-    picsong_ctx *ctx = nullptr;
-    create_decode_ctx(p, o.device, &ctx, o.drop);
+    const Ctx ctx = create_decode_ctx(p, o.device, o.drop);
     load_lut(ctx, o, p.wl, 1, p.k, p.cp);
     int aw, ah, ncb;
     CK(picsong_ctx_padded_dims(ctx, &aw, &ah, &ncb));
@@ -1618,11 +1454,9 @@ int run_decode_deep(const Options &o, const picsong_params &p, std::ifstream &in
     std::vector<uint16_t> stream(max_shorts, 0xFFFFu), img(n);
     in.seekg(0);
     in.read(reinterpret_cast<char *>(stream.data()), (std::streamsize)(shorts * 2));
-    hipStream_t s;
-    HIPCK(hipStreamCreate(&s));
-    uint16_t *d_in = nullptr, *d_pix = nullptr;
-    HIPCK(hipMalloc(&d_in, max_shorts * 2));
-    HIPCK(hipMalloc(&d_pix, n * 2));
+    const Stream s = stream_create();
+    const auto d_in = dev_alloc<uint16_t>(max_shorts * 2);
+    const auto d_pix = dev_alloc<uint16_t>(n * 2);
     auto t0 = std::chrono::steady_clock::now();
     HIPCK(hipMemcpyAsync(d_in, stream.data(), max_shorts * 2, hipMemcpyHostToDevice, s));
     picsong_image im;
@@ -1642,9 +1476,6 @@ int run_decode_deep(const Options &o, const picsong_params &p, std::ifstream &in
     Options mo = o;
     mo.x = p.width; mo.y = p.height;
     write_metrics(mo, "decode", 1, sec, 0, 0, 0, (long)shorts);
-    picsong_ctx_destroy(ctx);
-    (void)hipStreamDestroy(s);
-    (void)hipFree(d_in); (void)hipFree(d_pix);
     return 0;
 }
 
@@ -1682,8 +1513,7 @@ int run_decode(const Options &o)
         frame_shorts.push_back((long)((size_t)in.tellg() / 2));
     }
     HIPCK(hipSetDevice(o.device));
-    picsong_ctx *ctx = nullptr;
-    create_decode_ctx(p, o.device, &ctx, o.drop);
+    Ctx ctx = create_decode_ctx(p, o.device, o.drop);
     Options lo = o;
     load_lut(ctx, lo, p.wl, p.components, p.k, p.cp);
     int aw, ah, ncb;
@@ -1702,21 +1532,18 @@ int run_decode(const Options &o)
     }
     if (p.is_rgb) return run_decode_rgb(o, p, ctx, in, frame_shorts, nframes, aw, ah, od);
     if (o.video) {
-        picsong_ctx_destroy(ctx);
+        ctx = Ctx();                         // (the slots of the video pipeline create their own)
         in.close();
         return run_decode_video(lo, p, frame_shorts, nframes, od);
     }
     const size_t P = (size_t)od.pw * od.ph, max_shorts = picsong_max_stream_shorts(aw, ah);
-    hipStream_t s;
-    HIPCK(hipStreamCreate(&s));
-    uint16_t *h_in, *d_in;
-    uint8_t *h_pix, *d_pix;
-    HIPCK(hipHostMalloc(&h_in, max_shorts * 2));
-    HIPCK(hipMalloc(&d_in, max_shorts * 2));
-    HIPCK(hipHostMalloc(&h_pix, P));
-    HIPCK(hipMalloc(&d_pix, P));
-    uint8_t *d_emit = nullptr;                           // -layout grey: the frame cropped on the device
-    if (o.layout >= 0) HIPCK(hipMalloc(&d_emit, (size_t)od.w * od.h));
+    const Stream s = stream_create();
+    const auto h_in = pinned_alloc<uint16_t>(max_shorts * 2);
+    const auto d_in = dev_alloc<uint16_t>(max_shorts * 2);
+    const auto h_pix = pinned_alloc<uint8_t>(P);
+    const auto d_pix = dev_alloc<uint8_t>(P);
+    Dev<uint8_t> d_emit;                                 // -layout grey: the frame cropped on the device
+    if (o.layout >= 0) d_emit = dev_alloc<uint8_t>((size_t)od.w * od.h);
     std::vector<uint8_t> crop((size_t)od.w * od.h);
     if (o.video) { std::ofstream trunc(o.output, std::ios::binary | std::ios::app); }
     auto t0 = std::chrono::steady_clock::now();
@@ -1724,10 +1551,7 @@ int run_decode(const Options &o)
     for (long f = 0; f < nframes; f++) {
         const size_t n = (size_t)frame_shorts[(size_t)f];
         if (n > max_shorts) die("Frame codestream longer than the maximum for this geometry.");
-        in.clear();
-        in.seekg((std::streamoff)(pos * 2));
-        in.read(reinterpret_cast<char *>(h_in), (std::streamsize)(n * 2));
-        if ((size_t)in.gcount() != n * 2) die("Input file is shorter than its _SIZE sidecar says.");
+        if (!read_exact(in, h_in, n * 2, pos * 2)) die(kShortStream);
         pos += n;
         HIPCK(hipMemcpyAsync(d_in, h_in, n * 2, hipMemcpyHostToDevice, s));
         if (od.win) CK(picsong_decode_frame_window(ctx, d_in, od.r, od.x, od.y, od.w, od.h, d_pix, (size_t)od.pw, s));
@@ -1739,9 +1563,9 @@ int run_decode(const Options &o)
             HIPCK(hipMemcpyAsync(crop.data(), d_emit, crop.size(), hipMemcpyDeviceToHost, s));
             HIPCK(hipStreamSynchronize(s));
         } else {
-        HIPCK(hipMemcpyAsync(h_pix, d_pix, P, hipMemcpyDeviceToHost, s));
-        HIPCK(hipStreamSynchronize(s));
-        for (int y = 0; y < od.h; y++) memcpy(&crop[(size_t)y * od.w], h_pix + (size_t)y * od.pw, (size_t)od.w);
+            HIPCK(hipMemcpyAsync(h_pix, d_pix, P, hipMemcpyDeviceToHost, s));
+            HIPCK(hipStreamSynchronize(s));
+            crop_rows(crop.data(), h_pix, od.w, od.h, (size_t)od.pw);
         }
         if (o.video) {
             // IOManager::writeDecodedFrame IO/IOManager.ipp:214-231: raw W*H bytes appended
@@ -1756,10 +1580,6 @@ int run_decode(const Options &o)
     Options mo = lo;
     mo.x = od.w; mo.y = od.h;
     write_metrics(mo, "decode", nframes, sec, 0, 0, 0, (long)pos);
-    picsong_ctx_destroy(ctx);
-    (void)hipStreamDestroy(s);
-    (void)hipHostFree(h_in); (void)hipFree(d_in); (void)hipHostFree(h_pix); (void)hipFree(d_pix);
-    if (d_emit) (void)hipFree(d_emit);
     return 0;
 }
 
@@ -1789,24 +1609,21 @@ int run_compare(const Options &o)
     open_planes(o.output, fa, base_a);
     open_planes(o.compare, fb, base_b);
     HIPCK(hipSetDevice(o.device));
-    picsong_ctx *ctx = nullptr;
-    create_decode_ctx(p, o.device, &ctx);
+    const Ctx ctx = create_decode_ctx(p, o.device);
     int aw, ah, ncb;
     CK(picsong_ctx_padded_dims(ctx, &aw, &ah, &ncb));
     const size_t P = (size_t)aw * ah;
-    uint8_t *h = nullptr, *d = nullptr;
-    uint64_t *d_sse = nullptr, *h_sse = nullptr;
-    HIPCK(hipHostMalloc(&h, 2 * P));
-    HIPCK(hipMalloc(&d, 2 * P));
-    HIPCK(hipMalloc(&d_sse, sizeof(uint64_t)));
-    HIPCK(hipHostMalloc(&h_sse, sizeof(uint64_t)));
+    const auto h = pinned_alloc<uint8_t>(2 * P);
+    const auto d = dev_alloc<uint8_t>(2 * P);
+    const auto d_sse = dev_alloc<uint64_t>(sizeof(uint64_t));
+    const auto h_sse = pinned_alloc<uint64_t>(sizeof(uint64_t));
     std::vector<uint8_t> raw(plane_bytes);
     uint64_t sse = 0, dssim = 0, windows = 0;
     const bool ssim = picsong_ssim_windows(p.width, p.height, &windows) == PICSONG_OK;   // (8 x 8 samples or more)
     for (long i = 0; i < planes; i++) {
-        if (!read_frame(fa, base_a, (size_t)i, p.width, p.height, raw.data())) die("Cannot read back " + o.output);
+        if (!read_exact(fa, raw.data(), plane_bytes, base_a + (size_t)i * plane_bytes)) die("Cannot read back " + o.output);
         CK(picsong_pad_frame_host(raw.data(), p.width, p.height, h, aw, ah));
-        if (!read_frame(fb, base_b, (size_t)i, p.width, p.height, raw.data())) die("Cannot read " + o.compare);
+        if (!read_exact(fb, raw.data(), plane_bytes, base_b + (size_t)i * plane_bytes)) die("Cannot read " + o.compare);
         CK(picsong_pad_frame_host(raw.data(), p.width, p.height, h + P, aw, ah));
         HIPCK(hipMemcpyAsync(d, h, 2 * P, hipMemcpyHostToDevice, nullptr));
         CK(picsong_frames_sse(ctx, 1, d, 0, d + P, 0, d_sse, nullptr));
@@ -1829,8 +1646,6 @@ int run_compare(const Options &o)
         CK(picsong_dssim_to_ssim(dssim, windows * (uint64_t)planes, &v));
         std::cout << "Compare: SSIM " << ssim_text(v) << ", DSSIM sum " << dssim << " over " << planes << " plane(s)" << std::endl;
     }
-    picsong_ctx_destroy(ctx);
-    (void)hipHostFree(h); (void)hipFree(d); (void)hipFree(d_sse); (void)hipHostFree(h_sse);
     return 0;
 }
 
