@@ -93,9 +93,10 @@ struct DwtFwdArgs {
     // fused head, RGB frames (dwt_fwd2_kernel<..., RGB>): `src` is the R plane, these the G and B planes (padded u8,
     // same stride); plane blockIdx.z of the launch is COMPONENT z % 3, which the RCT delivers from the three planes of
     // frame z / 3, src_z bytes after frame 0's (level 0's src_z: every component of a frame reads all three)
+    // (deep RGB contexts, dwt_fwd_kernel's RGB16 instantiations: the same three pointers, padded uint16 planes)
     const void *src_g, *src_b;
-    // deep contexts (9- to 16-bit samples; the U16IN instantiations of dwt_fwd_kernel alone read it): level 0's `src` holds
-    // native uint16 samples, `off` = 2^(bit depth - 1) is the level shift its load stage subtracts.  0 everywhere else.
+    // deep contexts (9- to 16-bit samples; the U16IN and RGB16 instantiations of dwt_fwd_kernel alone read it): level 0's
+    // `src` holds native uint16 samples, `off` = 2^(bit depth - 1) is the level shift its load stage subtracts.  0 everywhere else.
     int off;
 };
 
@@ -453,8 +454,11 @@ __device__ __forceinline__ void hinv(float v[4], bool le, bool re)
 // A row segment as it comes from memory (conversion deferred so that many loads can be in flight):
 // u8 input: one dword = 4 samples; T input: four dwords; uint16 input (deep contexts): two dwords.
 // IN: the kind of the level's input -- kInT, kInU8 (= false / true of the kernels' U8IN) or kInU16
-constexpr int kInT = 0, kInU8 = 1, kInU16 = 2;
+// kInRgb16 (deep RGB contexts): the lane's four samples of the R, G and B planes, two dwords each; the unpack applies row
+// `comp` of the colour transform, so the component planes a separate launch would write never exist
+constexpr int kInT = 0, kInU8 = 1, kInU16 = 2, kInRgb16 = 3;
 template <int IN> struct RawRow;
+template <> struct RawRow<kInRgb16> { uint32_t w[6]; };
 template <> struct RawRow<kInU8> { uint32_t w; };
 template <> struct RawRow<kInT> { uint32_t w[4]; };
 template <> struct RawRow<kInU16> { uint32_t w[2]; };
@@ -464,7 +468,21 @@ __device__ __forceinline__ RawRow<IN> load_raw(const DwtFwdArgs &a, int y, int c
 {
     RawRow<IN> r;
     const int ry = reflect(y, a.H);
-    if constexpr (IN == kInU16) {
+    if constexpr (IN == kInRgb16) {
+        const size_t ro = (size_t)ry * (size_t)a.src_stride;
+        const uint16_t *const p[3] = { (const uint16_t *)a.src + ro, (const uint16_t *)a.src_g + ro, (const uint16_t *)a.src_b + ro };
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            if constexpr (VEC) {
+                // three 8-byte loads (rows 8-byte aligned: 16-byte aligned planes and frame stride, AW a multiple of 4)
+                const uint2 q = *reinterpret_cast<const uint2 *>(p[k] + (uint32_t)c0);
+                r.w[2 * k] = q.x; r.w[2 * k + 1] = q.y;
+            } else {
+                r.w[2 * k] = (uint32_t)p[k][reflect(c0, a.W)] | ((uint32_t)p[k][reflect(c0 + 1, a.W)] << 16);
+                r.w[2 * k + 1] = (uint32_t)p[k][reflect(c0 + 2, a.W)] | ((uint32_t)p[k][reflect(c0 + 3, a.W)] << 16);
+            }
+        }
+    } else if constexpr (IN == kInU16) {
         const uint16_t *p = (const uint16_t *)a.src + (size_t)ry * (size_t)a.src_stride;
         if constexpr (VEC) {
             // the lane's four samples: one 8-byte load (rows 8-byte aligned: 16-byte aligned frames, AW a multiple of 4)
@@ -524,11 +542,40 @@ __device__ __forceinline__ float byte_to_float(uint32_t w)
     return (float)(int)((w >> (8 * N)) & 0xFFu);
 #endif
 }
-// off: the level shift of the uint16 stage (DwtFwdArgs::off); the u8 stage keeps its literal 128
+// What the unpack of an input kind needs beyond the row: nothing -- or, kInRgb16, row `comp` of the colour transform as a
+// wave-uniform linear form, so that the component is no branch in the unrolled band (as unpack_rct / unpack_ict of the
+// 8-bit fused head): RCT (cr R + cg G + cb B) >> sh; ICT m2 b + (m1 g + (m0 r)), each step one fmaf, the operation order of
+// rgb_forward_kernel<float>, its coefficients in vector registers (a multiply with a scalar operand issues at half rate).
+template <int IN> struct InCoef {};
+template <> struct InCoef<kInRgb16> { int cr, cg, cb, sh; float m0, m1, m2; };
 template <typename T, int IN>
-__device__ __forceinline__ void unpack_row(const RawRow<IN> &r, T v[4], int off = 0)
+__device__ __forceinline__ InCoef<IN> in_coef(int comp)
 {
-    if constexpr (IN == kInU16) {
+    InCoef<IN> k = InCoef<IN>();
+    if constexpr (IN == kInRgb16 && std::is_same<T, float>::value) {
+        k.m0 = in_vgpr(comp == 0 ? 0.299f : (comp == 1 ? -0.168736f : 0.5f));
+        k.m1 = in_vgpr(comp == 0 ? 0.587f : (comp == 1 ? -0.331264f : -0.418688f));
+        k.m2 = in_vgpr(comp == 0 ? 0.114f : (comp == 1 ? 0.5f : -0.081312f));
+    } else if constexpr (IN == kInRgb16) {
+        k.cr = comp == 1 ? 0 : 1; k.cg = comp == 0 ? 2 : -1; k.cb = comp == 2 ? 0 : 1; k.sh = comp == 0 ? 2 : 0;
+    }
+    return k;
+}
+// off: the level shift of the uint16 stages (DwtFwdArgs::off); the u8 stage keeps its literal 128
+template <typename T, int IN>
+__device__ __forceinline__ void unpack_row(const RawRow<IN> &r, T v[4], int off = 0, const InCoef<IN> &kc = InCoef<IN>())
+{
+    if constexpr (IN == kInRgb16) {
+        // the samples are UNSIGNED 16-bit words; x - off is exact in both types (x < 2^16, off <= 2^15)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int sh = 16 * (i & 1);
+            const int R = (int)((r.w[i >> 1] >> sh) & 0xFFFFu) - off, G = (int)((r.w[2 + (i >> 1)] >> sh) & 0xFFFFu) - off,
+                      B = (int)((r.w[4 + (i >> 1)] >> sh) & 0xFFFFu) - off;
+            if constexpr (std::is_same<T, float>::value) v[i] = fmaf(kc.m2, (float)B, fmaf(kc.m1, (float)G, kc.m0 * (float)R));
+            else v[i] = (R * kc.cr + G * kc.cg + B * kc.cb) >> kc.sh;
+        }
+    } else if constexpr (IN == kInU16) {
         // offsetImage with the depth as a parameter: the samples are UNSIGNED 16-bit words (65535 is never -1), and
         // (T)v - (T)off is exact in both types (v < 2^16, off <= 2^15)
         v[0] = (T)(int)(r.w[0] & 0xFFFFu) - (T)off; v[1] = (T)(int)(r.w[0] >> 16) - (T)off;
@@ -611,11 +658,13 @@ __device__ __forceinline__ void emit_pair(const DwtFwdArgs &a, int m, int pc, bo
 #endif
 // U16IN (deep contexts, level 0): the input is native uint16 samples, the level shift DwtFwdArgs::off subtracted in the load
 // stage as the U8IN stage subtracts its 128
-template <typename T, bool LOSSY, bool U8IN, int BAND, bool VEC, bool U16IN = false>
+// RGB16 (deep RGB contexts, level 0, grid.z = 3 n planes): plane z is component z % 3 of frame z / 3 -- it reads that frame's
+// three uint16 planes (src, src_g, src_b; frame f's src_z bytes behind) and writes plane z's coefficients (dst_z)
+template <typename T, bool LOSSY, bool U8IN, int BAND, bool VEC, bool U16IN = false, bool RGB16 = false>
 __global__ __launch_bounds__(256) PS_DWT_OCC void dwt_fwd_kernel(DwtFwdArgs a)
 {
-    static_assert(!(U8IN && U16IN), "one kind of sample input");
-    constexpr int IN = U16IN ? kInU16 : (U8IN ? kInU8 : kInT);
+    static_assert(!(U8IN && U16IN) && !(RGB16 && (U8IN || U16IN)), "one kind of sample input");
+    constexpr int IN = RGB16 ? kInRgb16 : (U16IN ? kInU16 : (U8IN ? kInU8 : kInT));
     constexpr int kFwdBandRows = BAND;
 #ifdef PICSONG_DWT_CHUNKED
     constexpr int kFwdChunk = BAND / 2 < 4 ? BAND / 2 : 4;
@@ -626,7 +675,17 @@ __global__ __launch_bounds__(256) PS_DWT_OCC void dwt_fwd_kernel(DwtFwdArgs a)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int strip = blockIdx.x * 4 + wave;
     if (strip * kStripUseful >= a.W) return;               // whole wave idle (no cross-lane use)
-    dwt_fwd_select_frame(a);
+    int comp = 0;
+    if constexpr (RGB16) {
+        const unsigned long long z = blockIdx.z, fr = z / 3ull;
+        comp = (int)(z - 3ull * fr);
+        a.src = (const char *)a.src + fr * a.src_z;
+        a.src_g = (const char *)a.src_g + fr * a.src_z;
+        a.src_b = (const char *)a.src_b + fr * a.src_z;
+        a.ll = (char *)a.ll + z * a.dst_z;
+        a.mallat = (char *)a.mallat + z * a.dst_z;
+    } else dwt_fwd_select_frame(a);
+    const InCoef<IN> kc = in_coef<T, IN>(comp);
     const int c0 = strip * kStripUseful - 4 * kEdgeLanes + 4 * lane;    // first of the lane's 4 columns
     const int m0 = a.pair_base + blockIdx.y * (kFwdBandRows / 2);
     int m1 = m0 + kFwdBandRows / 2;
@@ -662,9 +721,9 @@ __global__ __launch_bounds__(256) PS_DWT_OCC void dwt_fwd_kernel(DwtFwdArgs a)
 #pragma unroll
         for (int r = 0; r < 2 * kFwdChunk; r++) raw[0][r] = load_raw<T, IN, VEC>(a, 2 * m0 + 1 + r, cl);
         __builtin_amdgcn_s_setprio(0);
-        unpack_row<T, IN>(r0, xe, a.off);
-        unpack_row<T, IN>(r1, xo, a.off);
-        unpack_row<T, IN>(r2, xn, a.off);
+        unpack_row<T, IN>(r0, xe, a.off, kc);
+        unpack_row<T, IN>(r1, xo, a.off, kc);
+        unpack_row<T, IN>(r2, xn, a.off, kc);
 #pragma unroll
         for (int k = 0; k < 4; k++) { dp[k] = xo[k] - ((xe[k] + xn[k]) >> 1); xe[k] = xn[k]; }
 #pragma unroll
@@ -678,8 +737,8 @@ __global__ __launch_bounds__(256) PS_DWT_OCC void dwt_fwd_kernel(DwtFwdArgs a)
 #pragma unroll
             for (int q = 0; q < kFwdChunk; q++) {
                 const int m = mc + q;
-                unpack_row<T, IN>(raw[c & 1][2 * q], xo, a.off);
-                unpack_row<T, IN>(raw[c & 1][2 * q + 1], xn, a.off);
+                unpack_row<T, IN>(raw[c & 1][2 * q], xo, a.off, kc);
+                unpack_row<T, IN>(raw[c & 1][2 * q + 1], xn, a.off, kc);
                 T Lr[4], Hr[4];
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
@@ -703,7 +762,7 @@ __global__ __launch_bounds__(256) PS_DWT_OCC void dwt_fwd_kernel(DwtFwdArgs a)
 #pragma unroll
         for (int r = 0; r < 2 * kFwdChunk; r++) raw[0][r] = load_raw<T, IN, VEC>(a, 2 * (m0 - 2) + 1 + r, cl);
         __builtin_amdgcn_s_setprio(0);
-        unpack_row<T, IN>(r0, xe, a.off);
+        unpack_row<T, IN>(r0, xe, a.off, kc);
 #pragma unroll
         for (int c = 0; c < NCH; c++) {
             const int jc = m0 - 2 + c * kFwdChunk;
@@ -715,8 +774,8 @@ __global__ __launch_bounds__(256) PS_DWT_OCC void dwt_fwd_kernel(DwtFwdArgs a)
 #pragma unroll
             for (int q = 0; q < kFwdChunk; q++) {
                 const int j = jc + q;
-                unpack_row<T, IN>(raw[c & 1][2 * q], xo, a.off);
-                unpack_row<T, IN>(raw[c & 1][2 * q + 1], xn, a.off);
+                unpack_row<T, IN>(raw[c & 1][2 * q], xo, a.off, kc);
+                unpack_row<T, IN>(raw[c & 1][2 * q + 1], xn, a.off, kc);
                 T Lr[4], Hr[4];
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
@@ -2360,6 +2419,125 @@ __global__ __launch_bounds__(256) void rgb_inverse_kernel(const T *c0, const T *
         reinterpret_cast<uint32_t *>(r)[i] = oR;
         reinterpret_cast<uint32_t *>(g)[i] = oG;
         reinterpret_cast<uint32_t *>(b)[i] = oB;
+    }
+}
+
+// ---- deep RGB contexts (9- to 16-bit colour samples as native uint16): the colour transforms above with the level shift
+// `off` = 2^(bit depth - 1) and the clamp at mx = 2^(bit depth) - 1 in place of 255, over the n frames of a call in ONE
+// launch -- grid.y = frame: frame f's sample planes smp_z BYTES after frame 0's, its three T planes (c0, c1, c2 of frame
+// 0 given) cmp_z bytes after frame 0's.  Four samples a lane; `wide`: every sample plane of every frame is 8-byte aligned
+// (one 8-byte access), else four 2-byte ones -- the same values; the T side is dwordx4 (the library's work buffers).
+// The samples are read UNSIGNED (65535 is never -1); (T)v - (T)off is exact in both types.
+struct Rgb16Args {
+    const void *c0, *c1, *c2;       // T planes (the forward kernel writes them, the inverse one reads them)
+    const void *r, *g, *b;          // uint16 planes (the forward kernel reads them, the inverse one writes them)
+    unsigned long long cmp_z, smp_z;
+    size_t n4;                      // groups of four samples a plane
+    int off, mx, wide;
+};
+__device__ __forceinline__ void load4_u16(const void *plane, size_t i, int wide, int v[4], int off)
+{
+    uint32_t w0, w1;
+    if (wide) {
+        const uint2 q = reinterpret_cast<const uint2 *>(plane)[i];
+        w0 = q.x; w1 = q.y;
+    } else {
+        const uint16_t *p = reinterpret_cast<const uint16_t *>(plane) + 4 * i;
+        w0 = (uint32_t)p[0] | ((uint32_t)p[1] << 16);
+        w1 = (uint32_t)p[2] | ((uint32_t)p[3] << 16);
+    }
+    v[0] = (int)(w0 & 0xFFFFu) - off; v[1] = (int)(w0 >> 16) - off;
+    v[2] = (int)(w1 & 0xFFFFu) - off; v[3] = (int)(w1 >> 16) - off;
+}
+__device__ __forceinline__ void store4_u16(void *plane, size_t i, int wide, const uint32_t s[4])
+{
+    if (wide) {
+        uint2 o;
+        o.x = s[0] | (s[1] << 16); o.y = s[2] | (s[3] << 16);
+        reinterpret_cast<uint2 *>(plane)[i] = o;
+    } else {
+        uint16_t *p = reinterpret_cast<uint16_t *>(plane) + 4 * i;
+        p[0] = (uint16_t)s[0]; p[1] = (uint16_t)s[1]; p[2] = (uint16_t)s[2]; p[3] = (uint16_t)s[3];
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void rgb_forward16_kernel(Rgb16Args a)
+{
+    const float M[3][3] = { { 0.299f, 0.587f, 0.114f }, { -0.168736f, -0.331264f, 0.5f }, { 0.5f, -0.418688f, -0.081312f } };
+    const unsigned long long f = blockIdx.y;
+    const char *r = (const char *)a.r + f * a.smp_z, *g = (const char *)a.g + f * a.smp_z, *b = (const char *)a.b + f * a.smp_z;
+    char *c0 = (char *)a.c0 + f * a.cmp_z, *c1 = (char *)a.c1 + f * a.cmp_z, *c2 = (char *)a.c2 + f * a.cmp_z;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n4; i += (size_t)gridDim.x * blockDim.x) {
+        int R[4], G[4], B[4];
+        load4_u16(r, i, a.wide, R, a.off);
+        load4_u16(g, i, a.wide, G, a.off);
+        load4_u16(b, i, a.wide, B, a.off);
+        uint4 o0, o1, o2;
+        uint32_t *q0 = &o0.x, *q1 = &o1.x, *q2 = &o2.x;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if constexpr (std::is_integral<T>::value) {                      // integer: RCT
+                q0[k] = (uint32_t)((R[k] + 2 * G[k] + B[k]) >> 2);
+                q1[k] = (uint32_t)(B[k] - G[k]);
+                q2[k] = (uint32_t)(R[k] - G[k]);
+            } else {                                                      // float: ICT ((float) of |x| <= 2^16 is exact)
+                const float fr = (float)R[k], fg = (float)G[k], fb = (float)B[k];
+                q0[k] = __float_as_uint(fmaf(M[0][2], fb, fmaf(M[0][1], fg, M[0][0] * fr)));
+                q1[k] = __float_as_uint(fmaf(M[1][2], fb, fmaf(M[1][1], fg, M[1][0] * fr)));
+                q2[k] = __float_as_uint(fmaf(M[2][2], fb, fmaf(M[2][1], fg, M[2][0] * fr)));
+            }
+        }
+        reinterpret_cast<uint4 *>(c0)[i] = o0;
+        reinterpret_cast<uint4 *>(c1)[i] = o1;
+        reinterpret_cast<uint4 *>(c2)[i] = o2;
+    }
+}
+
+// clamp(x + off, 0, mx) of an inverse-transformed sample.  The float form clamps rintf's result to [-off, mx - off]
+// BEFORE the conversion: for every finite value that is clamp((int)rintf(..) + off, 0, mx), and no conversion or sum
+// leaves the int range whatever a damaged stream decodes to.
+__device__ __forceinline__ uint32_t clamp_u16(int v, int off, int mx)
+{
+    const int t = v + off;
+    return (uint32_t)(t > mx ? mx : (t < 0 ? 0 : t));
+}
+__device__ __forceinline__ uint32_t clamp_u16(float rounded, int off, int mx)
+{
+    const float r = fminf(fmaxf(rounded, -(float)off), (float)(mx - off));
+    return (uint32_t)((int)r + off);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void rgb_inverse16_kernel(Rgb16Args a)
+{
+    const float M[3][3] = { { 1.0f, 0.0f, 1.402f }, { 1.0f, -0.344136f, -0.714136f }, { 1.0f, 1.772f, 0.0f } };
+    const unsigned long long f = blockIdx.y;
+    const char *c0 = (const char *)a.c0 + f * a.cmp_z, *c1 = (const char *)a.c1 + f * a.cmp_z, *c2 = (const char *)a.c2 + f * a.cmp_z;
+    char *r = (char *)a.r + f * a.smp_z, *g = (char *)a.g + f * a.smp_z, *b = (char *)a.b + f * a.smp_z;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n4; i += (size_t)gridDim.x * blockDim.x) {
+        const uint4 w0 = reinterpret_cast<const uint4 *>(c0)[i], w1 = reinterpret_cast<const uint4 *>(c1)[i],
+                    w2 = reinterpret_cast<const uint4 *>(c2)[i];
+        const uint32_t *q0 = &w0.x, *q1 = &w1.x, *q2 = &w2.x;
+        uint32_t oR[4], oG[4], oB[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if constexpr (std::is_integral<T>::value) {
+                const int y = (int)q0[k], cb = (int)q1[k], cr = (int)q2[k];
+                const int G = y - ((cb + cr) >> 2);
+                oR[k] = clamp_u16(cr + G, a.off, a.mx);
+                oG[k] = clamp_u16(G, a.off, a.mx);
+                oB[k] = clamp_u16(cb + G, a.off, a.mx);
+            } else {
+                const float y = __uint_as_float(q0[k]), cb = __uint_as_float(q1[k]), cr = __uint_as_float(q2[k]);
+                oR[k] = clamp_u16(rintf(fmaf(M[0][2], cr, fmaf(M[0][1], cb, M[0][0] * y)) + 0.01f), a.off, a.mx);
+                oG[k] = clamp_u16(rintf(fmaf(M[1][2], cr, fmaf(M[1][1], cb, M[1][0] * y)) + 0.01f), a.off, a.mx);
+                oB[k] = clamp_u16(rintf(fmaf(M[2][2], cr, fmaf(M[2][1], cb, M[2][0] * y)) + 0.01f), a.off, a.mx);
+            }
+        }
+        store4_u16(r, i, a.wide, oR);
+        store4_u16(g, i, a.wide, oG);
+        store4_u16(b, i, a.wide, oB);
     }
 }
 

@@ -56,8 +56,26 @@ inline FwdKernel select_fwd16(bool lossy, const FwdLaunch &f)
     default: return f.vec ? fwd16_kernel_of<4, true>(lossy) : fwd16_kernel_of<4, false>(lossy);
     }
 }
+// a deep RGB context's level 0 (FwdLaunch::rgb16): the three planes' uint16 load stage with the colour transform; the
+// per-column form in bands of at most kRgb16ColumnMaxBand rows (plan_dwt_forward_rgb16 gives it no taller one)
+template <int BAND, bool VEC>
+inline FwdKernel fwd_rgb16_kernel_of(bool lossy)
+{
+    return lossy ? dwt_fwd_kernel<float, true, false, BAND, VEC, false, true> : dwt_fwd_kernel<int, false, false, BAND, VEC, false, true>;
+}
+inline FwdKernel select_fwd_rgb16(bool lossy, const FwdLaunch &f)
+{
+    static_assert(kRgb16ColumnMaxBand == 8, "the per-column instantiations below");
+    switch (f.band) {
+    case 32: return f.vec ? fwd_rgb16_kernel_of<32, true>(lossy) : fwd_rgb16_kernel_of<8, false>(lossy);
+    case 16: return f.vec ? fwd_rgb16_kernel_of<16, true>(lossy) : fwd_rgb16_kernel_of<8, false>(lossy);
+    case 8: return f.vec ? fwd_rgb16_kernel_of<8, true>(lossy) : fwd_rgb16_kernel_of<8, false>(lossy);
+    default: return f.vec ? fwd_rgb16_kernel_of<4, true>(lossy) : fwd_rgb16_kernel_of<4, false>(lossy);
+    }
+}
 inline FwdKernel select_fwd(bool lossy, const FwdLaunch &f)
 {
+    if (f.rgb16) return select_fwd_rgb16(lossy, f);
     if (f.u16) return select_fwd16(lossy, f);
     switch (f.band) {
     case 32: return f.vec ? fwd_kernel_of<32, true>(lossy, f.u8) : fwd_kernel_of<32, false>(lossy, f.u8);
@@ -385,17 +403,25 @@ inline RgbSseLaunch select_rgb_sse(const RgbSseArgs &s, bool fused = true)
 }
 
 // ---- pixel layouts (ingest_kernel / emit_kernel, layout_kernels.hpp).  bytes a pixel, planes of the padded side
-inline int layout_bpp(int layout) { return layout == kLayoutGrey16 ? 2 : (layout < kLayoutRgb24 ? 1 : (layout < kLayoutRgba32 ? 3 : 4)); }
+inline bool layout_is_rgb16(int layout) { return layout == kLayoutPlanar3_16 || layout == kLayoutRgb48 || layout == kLayoutRgba64; }
+inline int layout_bpp(int layout)
+{
+    if (layout_is_rgb16(layout)) return layout == kLayoutPlanar3_16 ? 2 : (layout == kLayoutRgb48 ? 6 : 8);
+    return layout == kLayoutGrey16 ? 2 : (layout < kLayoutRgb24 ? 1 : (layout < kLayoutRgba32 ? 3 : 4));
+}
 inline int layout_planes(int layout) { return layout == kLayoutGrey8 || layout == kLayoutGrey16 ? 1 : 3; }
 // What picsong_ingest_frames / picsong_emit_frames (and the whole-frame calls over them) refuse, as a message; nullptr:
 // the arguments are fine.  `data`, pitch, plane_stride: the picsong_image's; n frames frame_stride bytes apart; the
 // padded side at `padded`, frames padded_stride apart.
-// deep (a context of 9- to 16-bit samples): GREY16 and nothing else; false: the six 8-bit layouts, as ever
+// deep (a context of 9- to 16-bit samples): GREY16 and nothing else -- or, deep_rgb, PLANAR3_16, RGB48 and RGBA64 and nothing
+// else; both false: the six 8-bit layouts, as ever
 inline const char *layout_refusal(int layout, const void *data, size_t pitch, size_t plane_stride, size_t frame_stride,
-                                  const void *padded, size_t padded_stride, int n, int W, int H, int AW, int AH, bool deep = false)
+                                  const void *padded, size_t padded_stride, int n, int W, int H, int AW, int AH, bool deep = false,
+                                  bool deep_rgb = false)
 {
     if (!data || !padded) return "null pointer";
-    if (deep && layout != kLayoutGrey16) return "the layout of a deep context (bit_depth 9..16) is GREY16";
+    if (deep_rgb && !layout_is_rgb16(layout)) return "the layouts of a deep RGB context (bit_depth 9..16) are PLANAR3_16, RGB48 and RGBA64";
+    if (deep && !deep_rgb && layout != kLayoutGrey16) return "the layout of a deep context (bit_depth 9..16) is GREY16";
     if (!deep && (layout < 0 || layout >= kLayoutCount)) return "unknown layout";
     if (n < 1 || n > kLayoutMaxFrames) return "n outside 1..64";
     if (W < 1 || H < 1 || AW < W || AH < H) return "bad geometry";
@@ -403,11 +429,19 @@ inline const char *layout_refusal(int layout, const void *data, size_t pitch, si
     const size_t row = (size_t)W * (size_t)layout_bpp(layout);
     if (pitch < row) return "pitch smaller than a row of pixels";
     size_t span = (size_t)(H - 1) * pitch + row;                        // the bytes one plane (one interleaved frame) spans
-    if (layout == kLayoutPlanar3) {
+    if (layout == kLayoutPlanar3 || layout == kLayoutPlanar3_16) {
         if (plane_stride < span) return "plane_stride smaller than a plane";
         span += 2 * plane_stride;
     }
     if (n > 1 && frame_stride < span) return "frame_stride smaller than a frame";
+    if (layout_is_rgb16(layout)) {
+        // (the padded side: three uint16 planes a frame, its stride in bytes)
+        if ((((uintptr_t)data) | pitch | (uintptr_t)padded) & 1u) return "16-bit samples need 2-byte aligned pointers and pitch";
+        if (layout == kLayoutPlanar3_16 && (plane_stride & 1u)) return "16-bit samples need an even plane_stride";
+        if (n > 1 && ((frame_stride | padded_stride) & 1u)) return "16-bit samples need even strides";
+        if (n > 1 && padded_stride < 6 * (size_t)AW * (size_t)AH) return "padded_stride smaller than a frame's padded planes";
+        return nullptr;
+    }
     if (layout == kLayoutGrey16) {
         // (the padded side: uint16 planes, its stride in bytes)
         if ((((uintptr_t)data) | pitch | (uintptr_t)padded) & 1u) return "16-bit samples need 2-byte aligned pointers and pitch";
@@ -460,12 +494,13 @@ inline const char *rgb_images_refusal(int layout, const void *data, size_t pitch
 // the vector form where the image side is 4-byte and the padded side 16-byte aligned, else the per-byte one.
 struct LayoutLaunch { LayoutKernel kernel; dim3 grid; bool vec; };
 inline LayoutArgs layout_args(int layout, const void *data, size_t pitch, size_t plane_stride, size_t frame_stride, const void *padded,
-                              size_t padded_stride, int n, int W, int H, int AW, int AH)
+                              size_t padded_stride, int n, int W, int H, int AW, int AH, int px_max = 0)
 {
     LayoutArgs a;
     memset(&a, 0, sizeof a);
     a.img = (uint8_t *)data; a.pitch = pitch;
-    a.plane_stride = layout == kLayoutPlanar3 ? plane_stride : 0; a.frame_stride = n > 1 ? frame_stride : 0;
+    a.plane_stride = layout == kLayoutPlanar3 || layout == kLayoutPlanar3_16 ? plane_stride : 0; a.frame_stride = n > 1 ? frame_stride : 0;
+    a.px_max = layout_is_rgb16(layout) ? px_max : 0;
     a.pad = (uint8_t *)padded; a.pad_stride = n > 1 ? padded_stride : 0; a.P = (unsigned long long)AW * (unsigned long long)AH;
     a.W = W; a.H = H; a.AW = AW; a.AH = AH;
     a.a16 = ((((uintptr_t)a.img) | a.pitch | a.plane_stride | a.frame_stride) & 15u) == 0 ? 1 : 0;
@@ -480,6 +515,30 @@ inline LayoutLaunch select_layout16(bool ingest, const LayoutArgs &a)
     const dim3 grid((unsigned)((groups + 255) / 256), 1u, 1u);
     if (ingest) return { vec ? ingest16_kernel<true> : ingest16_kernel<false>, grid, vec };
     return { vec ? emit16_kernel<true> : emit16_kernel<false>, grid, vec };
+}
+// the 16-bit colour layouts (ingest_rgb16_kernel / emit_rgb16_kernel): the same groups and grid.x, a thread 8 pixels; grid.y
+// = the planes of PLANAR3_16; the vector form where the padded side is 16-byte and the image side 4-byte aligned
+inline LayoutLaunch select_layout_rgb16(bool ingest, int layout, const LayoutArgs &a)
+{
+    const bool vec = ((((uintptr_t)a.img) | a.pitch | a.plane_stride | a.frame_stride) & 3u) == 0 && ((((uintptr_t)a.pad) | a.pad_stride) & 15u) == 0;
+    const size_t groups = ingest ? (size_t)(a.AW / 8) * (size_t)a.AH : (size_t)((a.W + 7) / 8) * (size_t)a.H;
+    const dim3 grid((unsigned)((groups + 255) / 256), layout == kLayoutPlanar3_16 ? 3u : 1u, 1u);
+    LayoutKernel k = nullptr;
+    switch (layout) {
+    case kLayoutPlanar3_16:
+        k = ingest ? (vec ? ingest_rgb16_kernel<kLayoutPlanar3_16, true> : ingest_rgb16_kernel<kLayoutPlanar3_16, false>)
+                   : (vec ? emit_rgb16_kernel<kLayoutPlanar3_16, true> : emit_rgb16_kernel<kLayoutPlanar3_16, false>);
+        break;
+    case kLayoutRgb48:
+        k = ingest ? (vec ? ingest_rgb16_kernel<kLayoutRgb48, true> : ingest_rgb16_kernel<kLayoutRgb48, false>)
+                   : (vec ? emit_rgb16_kernel<kLayoutRgb48, true> : emit_rgb16_kernel<kLayoutRgb48, false>);
+        break;
+    default:
+        k = ingest ? (vec ? ingest_rgb16_kernel<kLayoutRgba64, true> : ingest_rgb16_kernel<kLayoutRgba64, false>)
+                   : (vec ? emit_rgb16_kernel<kLayoutRgba64, true> : emit_rgb16_kernel<kLayoutRgba64, false>);
+        break;
+    }
+    return { k, grid, vec };
 }
 template <template <int, bool> class K>
 inline LayoutLaunch select_layout(int layout, const LayoutArgs &a)
@@ -503,8 +562,16 @@ inline LayoutLaunch select_layout(int layout, const LayoutArgs &a)
 template <int L, bool VEC> struct IngestOf { static LayoutKernel fn() { return ingest_kernel<L, VEC>; } };
 template <int L, bool VEC> struct EmitOf { static LayoutKernel fn() { return emit_kernel<L, VEC>; } };
 static_assert(LayoutTraits<kLayoutGrey8>::max_rows == 64 && LayoutTraits<kLayoutRgb24>::max_rows == 21, "select_layout's rows are the kernels'");
-inline LayoutLaunch select_ingest(int layout, const LayoutArgs &a) { return layout == kLayoutGrey16 ? select_layout16(true, a) : select_layout<IngestOf>(layout, a); }
-inline LayoutLaunch select_emit(int layout, const LayoutArgs &a) { return layout == kLayoutGrey16 ? select_layout16(false, a) : select_layout<EmitOf>(layout, a); }
+inline LayoutLaunch select_ingest(int layout, const LayoutArgs &a)
+{
+    if (layout_is_rgb16(layout)) return select_layout_rgb16(true, layout, a);
+    return layout == kLayoutGrey16 ? select_layout16(true, a) : select_layout<IngestOf>(layout, a);
+}
+inline LayoutLaunch select_emit(int layout, const LayoutArgs &a)
+{
+    if (layout_is_rgb16(layout)) return select_layout_rgb16(false, layout, a);
+    return layout == kLayoutGrey16 ? select_layout16(false, a) : select_layout<EmitOf>(layout, a);
+}
 
 // ---- the n-frame RGB proxy calls (picsong_decode_rgb_frames_reduced / _window, picsong_decode_rgb_images_reduced /
 // _window): what they refuse, as a message; nullptr: the arguments are fine.  The context's side as rgb_frames_refusal

@@ -28,7 +28,9 @@ static const float kQSteps[10][4] = {
 };
 
 // u16 (deep contexts, level 0 only): the input is uint16 samples (select_fwd: the U16IN instantiations); false: as ever
-struct FwdLaunch { DwtFwdArgs a; unsigned gx, gy; bool u8; int band; bool vec; bool u16; };
+// rgb16 (deep RGB contexts, level 0 only): the input is three uint16 planes a frame, the colour transform in the load stage,
+// grid.z = 3 n planes (select_fwd: the RGB16 instantiations); false: as ever
+struct FwdLaunch { DwtFwdArgs a; unsigned gx, gy; bool u8; int band; bool vec; bool u16; bool rgb16; };
 struct InvLaunch { DwtInvArgs a; unsigned gx, gy; int band; bool vec; bool fast; };
 
 // The vector-only kernel instantiations need whole 4-column groups and 16-byte aligned rows
@@ -154,6 +156,7 @@ inline std::vector<FwdLaunch> plan_dwt_forward(const void *d_in, bool u8in, void
         f.gy = (unsigned)(((H >> 1) + f.band / 2 - 1) / (f.band / 2));
         f.u8 = u8in && l == 0;
         f.u16 = false;
+        f.rgb16 = false;
         // rows of every buffer this level touches start 16-byte aligned when W % 4 == 0: strides are
         // aw, W or W/2 (even), scratch offsets are sums of W*H (multiples of 16 elements)
         f.vec = dwt_vec_ok(W, aw, d_in, d_out) && (W >> 1) % 2 == 0;
@@ -190,6 +193,28 @@ inline std::vector<FwdLaunch> plan_dwt_forward_u16(const uint16_t *d_in, size_t 
     v[0].u16 = true;
     v[0].a.off = off;
     if (frames > 1 && (frame_stride & 15u)) v[0].vec = false;
+    return v;
+}
+
+// ... of n deep RGB frames: three uint16 planes a frame at d_r / d_g / d_b, frame f's frame_stride bytes behind.  Level 0
+// reads them and applies the colour transform itself (FwdLaunch::rgb16, grid.z = 3 n): its vector form where the plan's
+// level 0 has it, all three planes start 16-byte aligned and frame_stride is a multiple of 16; its per-column form
+// otherwise.  A lane holds six dwords a raw row, three times the grey stage's: the vector form keeps every band height's
+// rows in registers; the per-column form, whose mirrored addresses cost registers too, does so up to 8 rows (at 16 and 32
+// its instantiations spill into accumulation registers at one wave a SIMD: DESIGN.md 4.19), so it takes at most 8.
+constexpr int kRgb16ColumnMaxBand = 8;
+inline std::vector<FwdLaunch> plan_dwt_forward_rgb16(const uint16_t *d_r, const uint16_t *d_g, const uint16_t *d_b, size_t frame_stride,
+                                                     unsigned frames, void *d_out, int aw, int ah, int wl, float qs, int off)
+{
+    std::vector<FwdLaunch> v = plan_dwt_forward_u16(d_r, frame_stride, frames, d_out, aw, ah, wl, qs, off);
+    FwdLaunch &f = v[0];
+    f.u16 = false; f.rgb16 = true;
+    f.a.src_g = d_g; f.a.src_b = d_b;
+    if ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 15u) f.vec = false;
+    if (!f.vec && f.band > kRgb16ColumnMaxBand) {
+        f.band = kRgb16ColumnMaxBand;
+        f.gy = (unsigned)(((ah >> 1) + f.band / 2 - 1) / (f.band / 2));
+    }
     return v;
 }
 

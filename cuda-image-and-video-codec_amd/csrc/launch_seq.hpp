@@ -89,6 +89,39 @@ int rgb_inverse(const Go &go, bool lossy, const void *c0, const void *c1, const 
     return lossy ? go(rgb_inverse_kernel<float>, grid, 256u, (const float *)c0, (const float *)c1, (const float *)c2, r, g, b, n4, off)
                  : go(rgb_inverse_kernel<int32_t>, grid, 256u, (const int32_t *)c0, (const int32_t *)c1, (const int32_t *)c2, r, g, b, n4, off);
 }
+// ---- deep RGB contexts: the colour transforms on uint16 samples, ONE launch over the n frames of a call (grid.y = frame):
+// frame f's sample planes smp_z bytes after r / g / b, its T planes cmp_z bytes after c0 / c1 / c2.  The 8-byte accesses
+// where every sample plane of every frame is 8-byte aligned, 2-byte ones otherwise: the same values.
+inline Rgb16Args rgb16_args(const void *c0, const void *c1, const void *c2, const void *r, const void *g, const void *b, size_t n4,
+                            int off, int px_max, unsigned n, unsigned long long cmp_z, unsigned long long smp_z)
+{
+    Rgb16Args a;
+    memset(&a, 0, sizeof a);
+    a.c0 = c0; a.c1 = c1; a.c2 = c2; a.r = r; a.g = g; a.b = b;
+    a.cmp_z = n > 1 ? cmp_z : 0; a.smp_z = n > 1 ? smp_z : 0;
+    a.n4 = n4; a.off = off; a.mx = px_max;
+    a.wide = (((((uintptr_t)r) | ((uintptr_t)g) | ((uintptr_t)b)) & 7u) == 0 && (a.smp_z & 7u) == 0) ? 1 : 0;
+    return a;
+}
+inline dim3 rgb16_grid(size_t n4, unsigned n)
+{
+    // (a frame's workgroups as ever, grid-stride beyond the cap the n frames share)
+    return dim3(elementwise_blocks(n4, 8192u / n > 0 ? 8192u / n : 1u), n);
+}
+template <class Go>
+int rgb_forward16(const Go &go, bool lossy, const uint16_t *r, const uint16_t *g, const uint16_t *b, void *c0, void *c1, void *c2,
+                  size_t n4, int off, unsigned n = 1, unsigned long long smp_z = 0, unsigned long long cmp_z = 0)
+{
+    const Rgb16Args a = rgb16_args(c0, c1, c2, r, g, b, n4, off, 0, n, cmp_z, smp_z);
+    return lossy ? go(rgb_forward16_kernel<float>, rgb16_grid(n4, n), 256u, a) : go(rgb_forward16_kernel<int32_t>, rgb16_grid(n4, n), 256u, a);
+}
+template <class Go>
+int rgb_inverse16(const Go &go, bool lossy, const void *c0, const void *c1, const void *c2, uint16_t *r, uint16_t *g, uint16_t *b,
+                  size_t n4, int off, int px_max, unsigned n = 1, unsigned long long cmp_z = 0, unsigned long long smp_z = 0)
+{
+    const Rgb16Args a = rgb16_args(c0, c1, c2, r, g, b, n4, off, px_max, n, cmp_z, smp_z);
+    return lossy ? go(rgb_inverse16_kernel<float>, rgb16_grid(n4, n), 256u, a) : go(rgb_inverse16_kernel<int32_t>, rgb16_grid(n4, n), 256u, a);
+}
 
 // ---- forward transform.  Levels [from, end) of a plan, one launch each; `frames` = grid.z of a batched call.
 template <class Go>
@@ -142,6 +175,32 @@ int deep_forward(const Go &go, bool lossy, bool nofuse, const uint16_t *frames, 
     std::vector<FwdLaunch> plan = plan_dwt_forward(shifted, false, coef, aw, ah, wl, qs, false);
     plan_frame_strides(plan, (unsigned long long)P * 4ull, coef_z);
     return launch_fwd_levels(go, lossy, plan, 0, n);
+}
+
+// The forward transform of n deep RGB frames (picsong_encode_rgb_frames16): uint16 planes at r / g / b, frame f's
+// frame_stride bytes behind; plane z = component z % 3 of frame z / 3, its coefficients in its buffer of coef_z bytes at
+// coef; one launch a level (grid.z = 3 n).  Level 0 reads the three sample planes of a frame and applies the colour
+// transform itself (plan_dwt_forward_rgb16), so no component plane is ever written; or -- nofuse (PICSONG_DEEP_NOFUSE=1:
+// the caller reads it) -- the colour transform of the n frames as ONE launch (rgb_forward16) into `planes` (3 n planes of
+// P samples of T, 16-byte aligned), then the T-input plan.  Always the 32-bit coefficient form.  *in_kernel says which ran.
+template <class Go>
+int deep_rgb_forward(const Go &go, bool lossy, bool nofuse, const uint16_t *r, const uint16_t *g, const uint16_t *b, size_t frame_stride,
+                     unsigned n, void *coef, void *planes, int aw, int ah, int wl, float qs, int off, unsigned long long coef_z,
+                     bool *in_kernel = nullptr)
+{
+    const size_t P = (size_t)aw * (size_t)ah;
+    if (n <= 1) frame_stride = 0;
+    if (in_kernel) *in_kernel = !nofuse;
+    if (!nofuse) {
+        std::vector<FwdLaunch> plan = plan_dwt_forward_rgb16(r, g, b, frame_stride, n, coef, aw, ah, wl, qs, off);
+        plan_frame_strides(plan, frame_stride, coef_z);      // level 0: every component of a frame reads its three planes
+        return launch_fwd_levels(go, lossy, plan, 0, 3u * n);
+    }
+    char *q = (char *)planes;
+    if (int rc = rgb_forward16(go, lossy, r, g, b, q, q + P * 4, q + 2 * P * 4, P / 4, off, n, frame_stride, 3ull * P * 4ull)) return rc;
+    std::vector<FwdLaunch> plan = plan_dwt_forward(planes, false, coef, aw, ah, wl, qs, false);
+    plan_frame_strides(plan, (unsigned long long)P * 4ull, coef_z);
+    return launch_fwd_levels(go, lossy, plan, 0, 3u * n);
 }
 
 // An RGB frame's colour transform (level shift fused) and the forward transform of its three components, component k's
@@ -402,6 +461,14 @@ int decode_rgb_frames(const Go &go, const DecodeCtx &c, BpcArgs a, const Workspa
         rep.vec = l.vec;
         return go(l.kernel, l.grid, 256u, ra);
     }
+    if (c.px_max > 0) {
+        // a deep RGB context (picsong_decode_rgb_frames16): d0 .. d2 hold uint16 samples.  The synthesis writes the 3 n T
+        // planes (plan_inverse_frames' deep plan, no pixel destination), then ONE inverse-transform launch over the n frames
+        if (int rc = run_inverse(go, c.lossy, lean97, plan, 3u * n, &rep.fused10)) return rc;
+        const char *img = (const char *)plan.back().a.dst;
+        return rgb_inverse16(go, c.lossy, img, img + z, img + 2 * z, (uint16_t *)d0, (uint16_t *)d1, (uint16_t *)d2, n4, c.off, c.px_max, n,
+                             3ull * z, frame_stride);
+    }
     const bool px_aligned = ((((uintptr_t)d0) | ((uintptr_t)d1) | ((uintptr_t)d2) | frame_stride) & 3u) == 0;
     rep.rgb_tail = fuse_tail && px_aligned && inv_rgb_tail_ok(plan, c.lossy);
     if (rep.rgb_tail) return run_inverse_rgb(go, c.lossy, lean97, plan, c.off, d0, d1, d2, n, frame_stride);
@@ -496,9 +563,9 @@ int frames_dssim(const Go &go, const uint8_t *a, size_t a_pitch, unsigned long l
 // arguments have passed layout_refusal.  *vec: the vector form ran
 template <class Go>
 int ingest_frames(const Go &go, int layout, const void *data, size_t pitch, size_t plane_stride, size_t frame_stride, uint8_t *padded,
-                  size_t padded_stride, int n, int W, int H, int AW, int AH, bool *vec = nullptr)
+                  size_t padded_stride, int n, int W, int H, int AW, int AH, bool *vec = nullptr, int px_max = 0)
 {
-    const LayoutArgs a = layout_args(layout, data, pitch, plane_stride, frame_stride, padded, padded_stride, n, W, H, AW, AH);
+    const LayoutArgs a = layout_args(layout, data, pitch, plane_stride, frame_stride, padded, padded_stride, n, W, H, AW, AH, px_max);
     LayoutLaunch l = select_ingest(layout, a);
     l.grid.z = (unsigned)n;
     if (vec) *vec = l.vec;
@@ -506,9 +573,9 @@ int ingest_frames(const Go &go, int layout, const void *data, size_t pitch, size
 }
 template <class Go>
 int emit_frames(const Go &go, int layout, const uint8_t *padded, size_t padded_stride, void *data, size_t pitch, size_t plane_stride,
-                size_t frame_stride, int n, int W, int H, int AW, int AH, bool *vec = nullptr)
+                size_t frame_stride, int n, int W, int H, int AW, int AH, bool *vec = nullptr, int px_max = 0)
 {
-    const LayoutArgs a = layout_args(layout, data, pitch, plane_stride, frame_stride, padded, padded_stride, n, W, H, AW, AH);
+    const LayoutArgs a = layout_args(layout, data, pitch, plane_stride, frame_stride, padded, padded_stride, n, W, H, AW, AH, px_max);
     LayoutLaunch l = select_emit(layout, a);
     l.grid.z = (unsigned)n;
     if (vec) *vec = l.vec;

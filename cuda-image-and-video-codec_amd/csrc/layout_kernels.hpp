@@ -28,6 +28,10 @@ namespace picsong {
 constexpr int kLayoutGrey8 = 0, kLayoutPlanar3 = 1, kLayoutRgb24 = 2, kLayoutBgr24 = 3, kLayoutRgba32 = 4, kLayoutBgra32 = 5;
 constexpr int kLayoutCount = 6;             // the layouts of 8-bit contexts
 constexpr int kLayoutGrey16 = 6;            // deep contexts' one layout: 2 bytes a pixel (native uint16), the padded side uint16 planes
+// deep RGB contexts' layouts (native uint16 samples; the padded side three uint16 planes a frame): three planes
+// plane_stride bytes apart; interleaved R, G, B (6 bytes a pixel); interleaved R, G, B, A (8 bytes; A ignored on input,
+// written as LayoutArgs::px_max on output)
+constexpr int kLayoutPlanar3_16 = 7, kLayoutRgb48 = 8, kLayoutRgba64 = 9;
 constexpr int kLayoutMaxFrames = 64;
 constexpr int kLayoutTail = 80;             // bytes a row and plane kept for the pad phase: 63 mirrored + 15 of a partial group
 constexpr int kLayoutLds = 64 * kLayoutTail;
@@ -49,6 +53,7 @@ struct LayoutArgs {
     unsigned long long pad_stride, P;
     int W, H, AW, AH;
     int a16;                                // the image side is 16-byte aligned as well (VEC only)
+    int px_max;                             // the 16-bit colour layouts' emit: the alpha sample, 2^(bit depth) - 1; 0 everywhere else
 };
 
 // rows of a workgroup: as many as its 256 threads hold groups of, the LDS tails permitting
@@ -349,6 +354,120 @@ __global__ __launch_bounds__(256) void emit16_kernel(LayoutArgs s)
 #pragma unroll
         for (uint32_t i = 0; i < 8u; i++)
             if (i < nvis) reinterpret_cast<uint16_t *>(dst)[i] = (uint16_t)(w[i / 2u] >> (16u * (i % 2u)));
+    }
+}
+
+// ---- the 16-bit colour layouts (deep RGB contexts): kLayoutPlanar3_16, kLayoutRgb48, kLayoutRgba64 to and from three padded
+// uint16 planes a frame (plane c of frame f at pad + f * pad_stride + c * 2 P BYTES, row stride AW samples).  The scheme is
+// ingest16_kernel's / emit16_kernel's: ingest_rgb16_kernel runs over the PADDED rows, a thread a group of 8 pixels of one,
+// reads the source row that row mirrors -- only bytes [y * pitch, y * pitch + W * bpp) of rows 0 .. H - 1 -- and
+// de-interleaves in the same pass; emit_rgb16_kernel crops and interleaves, a thread 8 pixels of a visible row, alpha = px_max,
+// and writes no byte outside [y * pitch, y * pitch + W * bpp).  The planar layout runs a plane a grid.y.
+// VEC: a dwordx4 a plane on the padded side (16-byte aligned); dwords on the image side where it is 4-byte aligned and the
+// group lies wholly inside the row.  Else every sample on its own; the same bytes.
+template <int L> struct Layout16Traits {
+    static constexpr int spp = L == kLayoutRgb48 ? 3 : (L == kLayoutRgba64 ? 4 : 1);     // samples a pixel on the image side
+    static constexpr int np = L == kLayoutPlanar3_16 ? 1 : 3;                            // planes a thread
+};
+__device__ __forceinline__ uint32_t half_of(const uint32_t *w, int h) { return (w[h >> 1] >> (16 * (h & 1))) & 0xFFFFu; }
+
+template <int L, bool VEC>
+__global__ __launch_bounds__(256) void ingest_rgb16_kernel(LayoutArgs s)
+{
+    using T = Layout16Traits<L>;
+    const uint32_t W = (uint32_t)s.W, H = (uint32_t)s.H, AW = (uint32_t)s.AW, AH = (uint32_t)s.AH;
+    const uint32_t gpr = AW / 8u;
+    const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (t >= (size_t)gpr * AH) return;
+    const uint32_t y = (uint32_t)(t / gpr), x0 = (uint32_t)(t % gpr) * 8u;
+    const uint32_t sy = y < H ? y : 2u * H - 1u - y;
+    const uint8_t *const src = s.img + (size_t)blockIdx.z * s.frame_stride + (size_t)blockIdx.y * s.plane_stride + (size_t)sy * s.pitch;
+    uint8_t *const dst = s.pad + (size_t)blockIdx.z * s.pad_stride + (size_t)blockIdx.y * s.P * 2u + ((size_t)y * AW + x0) * 2u;
+    uint32_t p[T::np][4];
+#pragma unroll
+    for (int c = 0; c < T::np; c++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) p[c][k] = 0u;
+    if (VEC && x0 + 8u <= W) {
+        uint32_t w[4 * T::spp];
+#pragma unroll
+        for (int k = 0; k < 4 * T::spp; k++) w[k] = reinterpret_cast<const uint32_t *>(src + (size_t)x0 * 2u * T::spp)[k];
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+#pragma unroll
+            for (int c = 0; c < T::np; c++) p[c][i >> 1] |= half_of(w, T::spp * i + c) << (16 * (i & 1));
+    } else {
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++) {
+            const uint32_t x = x0 + i, sx = x < W ? x : 2u * W - 1u - x;
+#pragma unroll
+            for (int c = 0; c < T::np; c++)
+                p[c][i >> 1] |= (uint32_t)reinterpret_cast<const uint16_t *>(src)[(size_t)sx * T::spp + c] << (16u * (i & 1u));
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < T::np; c++) {
+        uint8_t *const d = dst + (size_t)c * s.P * 2u;
+        if constexpr (VEC) {
+            uint4 v;
+            v.x = p[c][0]; v.y = p[c][1]; v.z = p[c][2]; v.w = p[c][3];
+            *reinterpret_cast<uint4 *>(d) = v;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; i++) reinterpret_cast<uint16_t *>(d)[i] = (uint16_t)half_of(p[c], i);
+        }
+    }
+}
+
+template <int L, bool VEC>
+__global__ __launch_bounds__(256) void emit_rgb16_kernel(LayoutArgs s)
+{
+    using T = Layout16Traits<L>;
+    const uint32_t W = (uint32_t)s.W, H = (uint32_t)s.H, AW = (uint32_t)s.AW;
+    const uint32_t gpr = (W + 7u) / 8u;
+    const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (t >= (size_t)gpr * H) return;
+    const uint32_t y = (uint32_t)(t / gpr), x0 = (uint32_t)(t % gpr) * 8u;
+    const uint32_t nvis = W - x0 < 8u ? W - x0 : 8u;
+    // (a whole group of the padded row is always there: AW is a multiple of 64)
+    const uint8_t *const src = s.pad + (size_t)blockIdx.z * s.pad_stride + (size_t)blockIdx.y * s.P * 2u + ((size_t)y * AW + x0) * 2u;
+    uint8_t *const dst = s.img + (size_t)blockIdx.z * s.frame_stride + (size_t)blockIdx.y * s.plane_stride + (size_t)y * s.pitch +
+                         (size_t)x0 * 2u * T::spp;
+    uint32_t p[T::np][4];
+#pragma unroll
+    for (int c = 0; c < T::np; c++) {
+        const uint8_t *const q = src + (size_t)c * s.P * 2u;
+        if constexpr (VEC) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(q);
+            p[c][0] = v.x; p[c][1] = v.y; p[c][2] = v.z; p[c][3] = v.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                p[c][k] = (uint32_t)reinterpret_cast<const uint16_t *>(q)[2 * k] | ((uint32_t)reinterpret_cast<const uint16_t *>(q)[2 * k + 1] << 16);
+        }
+    }
+    const uint32_t alpha = (uint32_t)s.px_max & 0xFFFFu;
+    if (VEC && nvis == 8u) {
+        uint32_t w[4 * T::spp];
+#pragma unroll
+        for (int k = 0; k < 4 * T::spp; k++) w[k] = 0u;
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+#pragma unroll
+            for (int c = 0; c < T::spp; c++) {
+                const int h = T::spp * i + c;
+                w[h >> 1] |= (c < T::np ? half_of(p[c < T::np ? c : 0], i) : alpha) << (16 * (h & 1));
+            }
+#pragma unroll
+        for (int k = 0; k < 4 * T::spp; k++) reinterpret_cast<uint32_t *>(dst)[k] = w[k];
+    } else {
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++)
+            if (i < nvis) {
+#pragma unroll
+                for (int c = 0; c < T::spp; c++)
+                    reinterpret_cast<uint16_t *>(dst)[i * T::spp + c] = (uint16_t)(c < T::np ? half_of(p[c < T::np ? c : 0], (int)i) : alpha);
+            }
     }
 }
 

@@ -118,9 +118,14 @@ static int level_off(const picsong_ctx *c) { return 1 << (c->p.bit_depth - 1); }
 // a deep context: 9- to 16-bit samples, uint16 frames through the *16 calls; its largest sample
 static bool is_deep(const picsong_ctx *c) { return c->p.bit_depth > 8; }
 static int px_max(const picsong_ctx *c) { return (1 << c->p.bit_depth) - 1; }
+// a deep RGB context: three uint16 planes a frame through the *16 RGB calls
+static bool is_deep_rgb(const picsong_ctx *c) { return is_deep(c) && c->p.is_rgb != 0; }
 // the calls that take or return uint8_t frames, on a deep context (nothing launched)
 #define REFUSE_DEEP(c, who)                                                                                              \
     do {                                                                                                                 \
+        if ((c) && is_deep_rgb(c))                                                                                       \
+            return fail(PICSONG_ERR_ARG, "%s: 8-bit frames on a %d-bit RGB context (its frame calls: "                    \
+                                         "picsong_encode_rgb_frames16, picsong_decode_rgb_frames16)", who, (c)->p.bit_depth); \
         if ((c) && is_deep(c))                                                                                           \
             return fail(PICSONG_ERR_ARG, "%s: 8-bit frames on a %d-bit context (its frame calls: picsong_encode_frames16, " \
                                          "picsong_decode_frames16, GREY16 images)", who, (c)->p.bit_depth);             \
@@ -341,8 +346,6 @@ int picsong_ctx_create(const picsong_params *p, int device, picsong_ctx **out)
     if (!(p->k >= 0.0f && p->k <= 65.535f)) return fail(PICSONG_ERR_ARG, "k %g outside [0, 65.535]", p->k);
     if (p->lossy && !(p->qs > 0.0f && p->qs <= 1.0f)) return fail(PICSONG_ERR_ARG, "qs %g outside (0,1]", p->qs);
     if (p->bit_depth < 8 || p->bit_depth > 16) return fail(PICSONG_ERR_ARG, "bit depth %d outside 8..16", p->bit_depth);
-    if (p->bit_depth > 8 && (p->components != 1 || p->is_rgb))
-        return fail(PICSONG_ERR_ARG, "%d-bit samples: grey contexts only (components 1, is_rgb 0)", p->bit_depth);
     if (!((p->components == 1 && !p->is_rgb) || (p->components == 3 && p->is_rgb)))
         return fail(PICSONG_ERR_ARG, "components must be 1 (grey) or 3 with is_rgb (got %d, is_rgb %d)", p->components,
                     p->is_rgb);
@@ -1340,6 +1343,18 @@ int picsong_depth_range_guaranteed(int bit_depth, int lossy, int wl, float qs, i
     return PICSONG_OK;
 }
 
+// ... of a deep RGB context: the RCT's chroma differences span +-(2^bd - 1), one bit more than a grey sample; the ICT's rows
+// have absolute sum 1, so its components stay within +-2^(bd-1)
+int picsong_depth_range_guaranteed_rgb(int bit_depth, int lossy, int wl, float qs, int *yes)
+{
+    if (!yes) return fail(PICSONG_ERR_ARG, "depth_range_guaranteed_rgb: null argument");
+    if (bit_depth < 9 || bit_depth > 16) return fail(PICSONG_ERR_ARG, "depth_range_guaranteed_rgb: bit depth %d outside 9..16", bit_depth);
+    if (wl < 1 || wl > 7) return fail(PICSONG_ERR_ARG, "depth_range_guaranteed_rgb: wl %d outside 1..7", wl);
+    if (lossy && !(qs > 0.0f && qs <= 1.0f)) return fail(PICSONG_ERR_ARG, "depth_range_guaranteed_rgb: qs %g outside (0,1]", qs);
+    *yes = coef16_bound(lossy != 0, wl, qs, lossy ? 1 << (bit_depth - 1) : 1 << bit_depth) ? 1 : 0;
+    return PICSONG_OK;
+}
+
 int picsong_level_shift_fwd16(picsong_ctx *c, const uint16_t *d_in, void *d_out, void *stream)
 {
     REFUSE_SHALLOW(c, "level_shift_fwd16");
@@ -1364,6 +1379,9 @@ static int frames16_args_ok(const picsong_ctx *c, int n, const void *d_frames, s
                             size_t stream_stride, const char *who)
 {
     REFUSE_SHALLOW(c, who);
+    if (c && is_deep_rgb(c))
+        return fail(PICSONG_ERR_ARG, "%s: grey frames on an RGB context (its frame calls: picsong_encode_rgb_frames16, "
+                                     "picsong_decode_rgb_frames16)", who);
     if (!c || !d_frames || !d_streams) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     if (n < 1 || n > 64) return fail(PICSONG_ERR_ARG, "%s: %d frames outside 1..64", who, n);
     if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 2 contexts only", who);
@@ -2109,6 +2127,7 @@ int picsong_train_frames(picsong_ctx *c, int n, const uint8_t *d_frames, size_t 
 
 int picsong_train_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, void *stream)
 {
+    REFUSE_DEEP(c, "train_rgb_frame");
     if (int rc = train_ready(c, "train_rgb_frame")) return rc;
     if (!d_r || !d_g || !d_b) return fail(PICSONG_ERR_ARG, "train_rgb_frame: null argument");
     if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "train_rgb_frame: the context is not an RGB one");
@@ -2132,6 +2151,7 @@ int picsong_train_rgb_frame(picsong_ctx *c, const uint8_t *d_r, const uint8_t *d
 int picsong_train_rgb_frames(picsong_ctx *c, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, size_t frame_stride,
                              void *stream)
 {
+    REFUSE_DEEP(c, "train_rgb_frames");
     if (int rc = train_ready(c, "train_rgb_frames")) return rc;
     if (!d_r || !d_g || !d_b) return fail(PICSONG_ERR_ARG, "train_rgb_frames: null argument");
     if (!c->p.is_rgb) return fail(PICSONG_ERR_ARG, "train_rgb_frames: the context is not an RGB one");
@@ -2240,7 +2260,7 @@ static int layout_args_ok(const picsong_ctx *c, int n, const picsong_image *img,
 {
     if (!c || !img) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     if (const char *why = layout_refusal(img->layout, img->data, img->pitch, img->plane_stride, frame_stride, d_padded, padded_stride, n,
-                                         c->p.width, c->p.height, c->aw, c->ah, is_deep(c)))
+                                         c->p.width, c->p.height, c->aw, c->ah, is_deep(c), is_deep_rgb(c)))
         return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
     return PICSONG_OK;
 }
@@ -2251,7 +2271,7 @@ int picsong_ingest_frames(picsong_ctx *c, int n, const picsong_image *src, size_
     if (int rc = layout_args_ok(c, n, src, frame_stride, d_padded, padded_stride, "ingest_frames")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     return ingest_frames(HipGo{ (hipStream_t)stream }, src->layout, src->data, src->pitch, src->plane_stride, frame_stride, d_padded,
-                         padded_stride, n, c->p.width, c->p.height, c->aw, c->ah);
+                         padded_stride, n, c->p.width, c->p.height, c->aw, c->ah, nullptr, is_deep(c) ? px_max(c) : 0);
 }
 
 int picsong_emit_frames(picsong_ctx *c, int n, const uint8_t *d_padded, size_t padded_stride, const picsong_image *dst,
@@ -2260,7 +2280,7 @@ int picsong_emit_frames(picsong_ctx *c, int n, const uint8_t *d_padded, size_t p
     if (int rc = layout_args_ok(c, n, dst, frame_stride, d_padded, padded_stride, "emit_frames")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     return emit_frames(HipGo{ (hipStream_t)stream }, dst->layout, d_padded, padded_stride, dst->data, dst->pitch, dst->plane_stride,
-                       frame_stride, n, c->p.width, c->p.height, c->aw, c->ah);
+                       frame_stride, n, c->p.width, c->p.height, c->aw, c->ah, nullptr, is_deep(c) ? px_max(c) : 0);
 }
 
 // the context's padded planes for the image calls: `planes` of P bytes (hipMalloc: 256-byte aligned)
@@ -2281,7 +2301,10 @@ static int image_args_ok(const picsong_ctx *c, int n, const picsong_image *img, 
 {
     if (!c || !img || !d_streams) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     // (the padded side is the context's buffer, allocated later: any non-null address stands for it, its stride a frame's planes)
-    if (int rc = layout_args_ok(c, n, img, frame_stride, c, (size_t)3 * c->P, who)) return rc;
+    if (int rc = layout_args_ok(c, n, img, frame_stride, c, (size_t)(is_deep_rgb(c) ? 6 : 3) * c->P, who)) return rc;
+    if (is_deep_rgb(c))                                     // (16-bit colour layouts: the n-frame RGB image calls alone)
+        return fail(PICSONG_ERR_ARG, "%s: a %d-bit RGB context's image calls are picsong_encode_rgb_images / picsong_decode_rgb_images",
+                    who, c->p.bit_depth);
     if (img->layout == kLayoutGrey16) {                     // (a deep context: layout_args_ok; grey by its creation)
         if (rgb) return fail(PICSONG_ERR_ARG, "%s: the context is not an RGB one", who);
         if (c->p.cp == 3) return fail(PICSONG_ERR_ARG, "%s: -cp 2 contexts only, as the frame call behind it", who);
@@ -2336,6 +2359,7 @@ int picsong_encode_rgb_image(picsong_ctx *c, const picsong_image *src, int heade
                              void *stream)
 {
     const char *who = "encode_rgb_image";
+    REFUSE_DEEP(c, who);
     if (int rc = image_args_ok(c, 1, src, 0, d_streams, true, who)) return rc;
     if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah))
         return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
@@ -2351,6 +2375,7 @@ int picsong_encode_rgb_image(picsong_ctx *c, const picsong_image *src, int heade
 int picsong_decode_rgb_image(picsong_ctx *c, const uint16_t *d_streams, size_t stream_stride, const picsong_image *dst, void *stream)
 {
     const char *who = "decode_rgb_image";
+    REFUSE_DEEP(c, who);
     if (int rc = image_args_ok(c, 1, dst, 0, d_streams, true, who)) return rc;
     if (stream_stride < picsong_max_stream_shorts(c->aw, c->ah))
         return fail(PICSONG_ERR_ARG, "%s: stream stride smaller than a worst-case codestream", who);
@@ -2381,9 +2406,30 @@ static int rgb_frames_args(picsong_ctx *c, int n, const void *r, const void *g, 
     return PICSONG_OK;
 }
 
+// The tail of the n-frame colour encode calls, 8-bit and deep alike, behind the transform of the 3 n planes into batch.coef
+// (c16: as int16 Mallat arrays): the coder, one grid over the planes' codeblock pairs, plane z with table z % 3; then the
+// pack, the populated header on the components of header_mask, on the video's frame 0 where the call holds it
+static int rgb_code_and_pack(picsong_ctx *c, BpcArgs &a, int n, bool c16, int first_iter, int header_mask, uint16_t *d_streams,
+                             size_t stream_stride, hipStream_t s)
+{
+    const unsigned np = 3u * (unsigned)n;
+    a.c16 = c16 ? 1 : 0;
+    a.coeffs_in = c->batch.coef; a.is_float = c->p.lossy ? 1 : 0;
+    a.staging16 = reinterpret_cast<uint16_t *>(c->batch.staging);
+    a.sizes = c->batch.sizes; a.plane_scratch = c->batch.plane_scratch; a.coef_z = (c->P + c->extra) * 4;
+    if (int rc = launch_encoder(c, a, np * (unsigned)a.waves_per_frame, 0, 3, s)) return rc;
+    uint16_t hdr[PICSONG_HDR_SHORTS];
+    picsong_header_pack(&c->p, hdr);
+    if (int rc = pack_rgb_frames(HipGo{ s }, a.staging16, c->batch, c->ncb, (unsigned)n, hdr, first_iter, header_mask, d_streams, c->P,
+                                 stream_stride)) return rc;
+    c->last_batch = (int)np;
+    return PICSONG_OK;
+}
+
 static int encode_rgb_frames_impl(picsong_ctx *c, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, size_t frame_stride,
                                   int first_iter, int header_mask, uint16_t *d_streams, size_t stream_stride, void *stream, const char *who)
 {
+    REFUSE_DEEP(c, who);
     BpcArgs a;
     int rc = rgb_frames_args(c, n, d_r, d_g, d_b, d_streams, frame_stride, stream_stride, who, a);
     if (rc) return rc;
@@ -2394,19 +2440,7 @@ static int encode_rgb_frames_impl(picsong_ctx *c, int n, const uint8_t *d_r, con
     hipStream_t s = (hipStream_t)stream;
     bool c16 = false;
     if ((rc = rgb_forward_transform(c, d_r, d_g, d_b, s, &c16, n, frame_stride))) return rc;
-    a.c16 = c16 ? 1 : 0;
-    // ---- coder: one grid over the 3 n planes' codeblock pairs, plane z with table z % 3
-    a.coeffs_in = c->batch.coef; a.is_float = c->p.lossy ? 1 : 0;
-    a.staging16 = reinterpret_cast<uint16_t *>(c->batch.staging);
-    a.sizes = c->batch.sizes; a.plane_scratch = c->batch.plane_scratch; a.coef_z = (c->P + c->extra) * 4;
-    if ((rc = launch_encoder(c, a, np * (unsigned)a.waves_per_frame, 0, 3, s))) return rc;
-    // ---- pack: the populated header on the components of header_mask, on the video's frame 0 where the call holds it
-    uint16_t hdr[PICSONG_HDR_SHORTS];
-    picsong_header_pack(&c->p, hdr);
-    if ((rc = pack_rgb_frames(HipGo{ s }, a.staging16, c->batch, c->ncb, (unsigned)n, hdr, first_iter, header_mask, d_streams, c->P,
-                              stream_stride))) return rc;
-    c->last_batch = (int)np;
-    return PICSONG_OK;
+    return rgb_code_and_pack(c, a, n, c16, first_iter, header_mask, d_streams, stream_stride, s);
 }
 
 int picsong_encode_rgb_frames(picsong_ctx *c, int n, const uint8_t *d_r, const uint8_t *d_g, const uint8_t *d_b, size_t frame_stride,
@@ -2455,6 +2489,7 @@ static int decode_rgb(picsong_ctx *c, int n, const uint16_t *d_streams, size_t s
 static int decode_rgb_frames_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, uint8_t *d_r,
                                   uint8_t *d_g, uint8_t *d_b, size_t frame_stride, void *stream, const char *who)
 {
+    REFUSE_DEEP(c, who);
     if (!c) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     if (const char *why = rgb_frames_reduced_refusal(c->p.is_rgb != 0, c->p.cp, true, n, d_r, d_g, d_b, d_streams, frame_stride, stream_stride,
                                                      picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce))
@@ -2486,6 +2521,90 @@ int picsong_decode_rgb_frame_reduced(picsong_ctx *c, const uint16_t *d_streams, 
     return decode_rgb_frames_impl(c, 1, d_streams, stream_stride, reduce, d_r, d_g, d_b, 0, stream, "decode_rgb_frame_reduced");
 }
 
+// ---------------------------------------------------------------------------------------------
+// deep RGB contexts (bit_depth 9..16, components 3, is_rgb 1): n colour frames of three uint16 planes.  Encoding, level 0
+// applies the colour transform in its load stage (deep_rgb_forward, launch_seq.hpp; PICSONG_DEEP_NOFUSE=1, read per call: one
+// rgb_forward16 launch over the n frames); decoding ends in one rgb_inverse16 launch over the n frames.  Between the ends the
+// 3 n planes are deep grey planes: 32-bit coefficients, one launch a stage, plane z with table z % 3.
+// ---------------------------------------------------------------------------------------------
+#define REFUSE_NOT_DEEP_RGB(c, who)                                                                                      \
+    do {                                                                                                                 \
+        if ((c) && !is_deep_rgb(c))                                                                                      \
+            return fail(PICSONG_ERR_ARG, "%s: uint16 RGB planes want a deep RGB context (bit_depth 9..16, components 3, is_rgb 1)", who); \
+    } while (0)
+
+int picsong_rgb_forward16(picsong_ctx *c, const uint16_t *d_r, const uint16_t *d_g, const uint16_t *d_b, void *d_c0, void *d_c1,
+                          void *d_c2, void *stream)
+{
+    REFUSE_NOT_DEEP_RGB(c, "rgb_forward16");
+    if (!c || !d_r || !d_g || !d_b || !d_c0 || !d_c1 || !d_c2) return fail(PICSONG_ERR_ARG, "rgb_forward16: null argument");
+    if ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 1u)
+        return fail(PICSONG_ERR_ARG, "rgb_forward16: uint16 samples need 2-byte aligned pointers");
+    if ((((uintptr_t)d_c0) | ((uintptr_t)d_c1) | ((uintptr_t)d_c2)) & 15u)
+        return fail(PICSONG_ERR_ARG, "rgb_forward16: the component planes need 16-byte aligned pointers");
+    return rgb_forward16(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, d_r, d_g, d_b, d_c0, d_c1, d_c2, c->P / 4, level_off(c));
+}
+
+int picsong_rgb_inverse16(picsong_ctx *c, const void *d_c0, const void *d_c1, const void *d_c2, uint16_t *d_r, uint16_t *d_g,
+                          uint16_t *d_b, void *stream)
+{
+    REFUSE_NOT_DEEP_RGB(c, "rgb_inverse16");
+    if (!c || !d_r || !d_g || !d_b || !d_c0 || !d_c1 || !d_c2) return fail(PICSONG_ERR_ARG, "rgb_inverse16: null argument");
+    if ((((uintptr_t)d_r) | ((uintptr_t)d_g) | ((uintptr_t)d_b)) & 1u)
+        return fail(PICSONG_ERR_ARG, "rgb_inverse16: uint16 samples need 2-byte aligned pointers");
+    if ((((uintptr_t)d_c0) | ((uintptr_t)d_c1) | ((uintptr_t)d_c2)) & 15u)
+        return fail(PICSONG_ERR_ARG, "rgb_inverse16: the component planes need 16-byte aligned pointers");
+    return rgb_inverse16(HipGo{ (hipStream_t)stream }, c->p.lossy != 0, d_c0, d_c1, d_c2, d_r, d_g, d_b, c->P / 4, level_off(c), px_max(c));
+}
+
+// what the two frame calls refuse alike (nothing launched): rgb_frames_refusal's rules on planes of 2 P bytes, and the
+// alignment of 2-byte samples
+static int rgb_frames16_args(picsong_ctx *c, int n, const void *r, const void *g, const void *b, const void *streams, size_t frame_stride,
+                             size_t stream_stride, const char *who, BpcArgs &a)
+{
+    REFUSE_NOT_DEEP_RGB(c, who);
+    if (!c) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (const char *why = rgb_frames_refusal(true, c->p.cp, true, n, r, g, b, streams, frame_stride, stream_stride, 2 * c->P,
+                                             picsong_max_stream_shorts(c->aw, c->ah)))
+        return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+    if ((((uintptr_t)r) | ((uintptr_t)g) | ((uintptr_t)b) | ((uintptr_t)streams)) & 1u)
+        return fail(PICSONG_ERR_ARG, "%s: pointers need 2-byte alignment", who);
+    if (n > 1 && (frame_stride & 1u)) return fail(PICSONG_ERR_ARG, "%s: frame_stride %zu must be even", who, frame_stride);
+    if (int rc = bpc_args_rgb(c, a)) return rc;             // (the tables' geometry)
+    a.frames = 3 * n;
+    return PICSONG_OK;
+}
+
+int picsong_encode_rgb_frames16(picsong_ctx *c, int n, const uint16_t *d_r, const uint16_t *d_g, const uint16_t *d_b, size_t frame_stride,
+                                int first_iter, int header_mask, uint16_t *d_streams, size_t stream_stride, void *stream)
+{
+    BpcArgs a;
+    int rc = rgb_frames16_args(c, n, d_r, d_g, d_b, d_streams, frame_stride, stream_stride, "encode_rgb_frames16", a);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const unsigned np = 3u * (unsigned)n;
+    if ((rc = ensure_batch(c, (int)np))) return rc;
+    if ((rc = ensure_coef_i(c, (int)np))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t coef_z = (c->P + c->extra) * 4;
+    // ---- the levels over the 3 n planes, the colour transform in level 0's load stage (PICSONG_DEEP_NOFUSE=1: one launch of
+    // its own, the component planes in batch.coef_i)
+    if ((rc = deep_rgb_forward(HipGo{ s }, c->p.lossy != 0, deep_nofuse(), d_r, d_g, d_b, n > 1 ? frame_stride : 0, (unsigned)n, c->batch.coef,
+                               c->batch.coef_i, c->aw, c->ah, c->p.wl, c->p.qs, level_off(c), coef_z))) return rc;
+    // ---- coder and pack as picsong_encode_rgb_frames, 32-bit coefficients (the header's two depth fields carry bit_depth)
+    return rgb_code_and_pack(c, a, n, false, first_iter, header_mask, d_streams, stream_stride, s);
+}
+
+int picsong_decode_rgb_frames16(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, uint16_t *d_r, uint16_t *d_g,
+                                uint16_t *d_b, size_t frame_stride, void *stream)
+{
+    BpcArgs a;
+    if (int rc = rgb_frames16_args(c, n, d_r, d_g, d_b, d_streams, frame_stride, stream_stride, "decode_rgb_frames16", a)) return rc;
+    // (decode_ctx hands the sequence px_max: uint16 samples at d_r / d_g / d_b, frame_stride bytes apart)
+    return decode_rgb(c, n, d_streams, stream_stride, 0, nullptr, kLayoutPlanar3, reinterpret_cast<uint8_t *>(d_r),
+                      reinterpret_cast<uint8_t *>(d_g), reinterpret_cast<uint8_t *>(d_b), 0, frame_stride, stream);
+}
+
 // the window calls, their arguments checked: the window's plan against the decoder's scratch, then the sequence
 static int decode_rgb_window_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y, int w,
                                   int h, int layout, uint8_t *d0, uint8_t *d1, uint8_t *d2, size_t pitch, size_t frame_stride, void *stream,
@@ -2500,6 +2619,7 @@ static int decode_rgb_frames_window_impl(picsong_ctx *c, int n, const uint16_t *
                                          int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, size_t out_pitch, size_t frame_stride,
                                          void *stream, const char *who)
 {
+    REFUSE_DEEP(c, who);
     if (!c) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     if (const char *why = rgb_frames_window_refusal(c->p.is_rgb != 0, c->p.cp, true, n, d_r, d_g, d_b, d_streams, out_pitch, frame_stride,
                                                     stream_stride, picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce,
@@ -2527,6 +2647,7 @@ int picsong_decode_rgb_frame_window(picsong_ctx *c, const uint16_t *d_streams, s
 static int decode_rgb_images_window_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
                                          int w, int h, const picsong_image *dst, size_t frame_stride, void *stream, const char *who)
 {
+    REFUSE_DEEP(c, who);
     if (const char *why = rgb_images_window_refusal(c->p.is_rgb != 0, c->p.cp, true, n, d_streams, stream_stride,
                                                     picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce, x, y, w, h,
                                                     dst->layout, dst->data, dst->pitch, dst->plane_stride, frame_stride))
@@ -2551,6 +2672,7 @@ int picsong_decode_rgb_images_reduced(picsong_ctx *c, int n, const uint16_t *d_s
                                       const picsong_image *dst, size_t frame_stride, void *stream)
 {
     const char *who = "decode_rgb_images_reduced";
+    REFUSE_DEEP(c, who);
     if (!c || !dst) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
     if (!reduce_ok(c->p.wl, reduce)) return fail(PICSONG_ERR_ARG, "%s: reduce %d outside 0..%d (wl - 1)", who, reduce, c->p.wl - 1);
     int d[5];
@@ -2574,6 +2696,16 @@ static int rgb_images_args(picsong_ctx *c, int n, const picsong_image *img, size
                            const char *who, BpcArgs &a)
 {
     if (!c || !img || !d_streams) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (is_deep_rgb(c)) {
+        // the 16-bit colour layouts; the padded side is the context's buffer: three uint16 planes a frame, 6 P bytes
+        if (n < 1 || n > kRgbMaxFrames) return fail(PICSONG_ERR_ARG, "%s: n outside 1..21", who);
+        if (const char *why = layout_refusal(img->layout, img->data, img->pitch, img->plane_stride, frame_stride, img->data, 6 * c->P, n,
+                                             c->p.width, c->p.height, c->aw, c->ah, true, true))
+            return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+        const uint8_t *stand_in = (const uint8_t *)(uintptr_t)4096;
+        return rgb_frames16_args(c, n, stand_in, stand_in + 2 * c->P, stand_in + 4 * c->P, d_streams, 6 * c->P, stream_stride, who, a);
+    }
+    REFUSE_DEEP(c, who);
     if (const char *why = rgb_images_refusal(img->layout, img->data, img->pitch, img->plane_stride, frame_stride, n, c->p.width, c->p.height,
                                              c->aw, c->ah))
         return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
@@ -2588,6 +2720,13 @@ int picsong_encode_rgb_images(picsong_ctx *c, int n, const picsong_image *src, s
     BpcArgs a;
     if (int rc = rgb_images_args(c, n, src, frame_stride, d_streams, stream_stride, "encode_rgb_images", a)) return rc;
     HIP_TRY(hipSetDevice(c->device));
+    if (is_deep_rgb(c)) {
+        if (int rc = ensure_layout(c, (size_t)6 * (size_t)n)) return rc;
+        if (int rc = ingest_frames(HipGo{ (hipStream_t)stream }, src->layout, src->data, src->pitch, src->plane_stride, frame_stride, c->lay_buf,
+                                   6 * c->P, n, c->p.width, c->p.height, c->aw, c->ah, nullptr, px_max(c))) return rc;
+        const uint16_t *const lay = reinterpret_cast<const uint16_t *>(c->lay_buf);
+        return picsong_encode_rgb_frames16(c, n, lay, lay + c->P, lay + 2 * c->P, 6 * c->P, first_iter, header_mask, d_streams, stream_stride, stream);
+    }
     if (int rc = ensure_layout(c, (size_t)3 * (size_t)n)) return rc;
     if (int rc = ingest_frames(HipGo{ (hipStream_t)stream }, src->layout, src->data, src->pitch, src->plane_stride, frame_stride, c->lay_buf,
                                3 * c->P, n, c->p.width, c->p.height, c->aw, c->ah)) return rc;
@@ -2601,6 +2740,13 @@ int picsong_decode_rgb_images(picsong_ctx *c, int n, const uint16_t *d_streams, 
     BpcArgs a;
     if (int rc = rgb_images_args(c, n, dst, frame_stride, d_streams, stream_stride, "decode_rgb_images", a)) return rc;
     HIP_TRY(hipSetDevice(c->device));
+    if (is_deep_rgb(c)) {
+        if (int rc = ensure_layout(c, (size_t)6 * (size_t)n)) return rc;
+        uint16_t *const lay = reinterpret_cast<uint16_t *>(c->lay_buf);
+        if (int rc = picsong_decode_rgb_frames16(c, n, d_streams, stream_stride, lay, lay + c->P, lay + 2 * c->P, 6 * c->P, stream)) return rc;
+        return emit_frames(HipGo{ (hipStream_t)stream }, dst->layout, c->lay_buf, 6 * c->P, dst->data, dst->pitch, dst->plane_stride, frame_stride,
+                           n, c->p.width, c->p.height, c->aw, c->ah, nullptr, px_max(c));
+    }
     if (int rc = ensure_layout(c, (size_t)3 * (size_t)n)) return rc;
     if (int rc = picsong_decode_rgb_frames(c, n, d_streams, stream_stride, c->lay_buf, c->lay_buf + c->P, c->lay_buf + 2 * c->P, 3 * c->P,
                                            stream)) return rc;

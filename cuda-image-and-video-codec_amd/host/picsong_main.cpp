@@ -138,8 +138,11 @@ void help()
         " -k 0..65.535        complexity-scalable factor (needs the bit-plane LUT files _0.._14)\n"
         " -bps 8..16          bits a sample (default 8).  9..16: ONE grey still image -- coding reads a raw file of W*H\n"
         "                     little-endian 16-bit samples or a P5 PGM with maxval > 255 (big-endian samples), decoding\n"
-        "                     writes a P5 with maxval 2^bps - 1; -drop works; no video, RGB, -rate, -psnr, -train, -reduce,\n"
-        "                     -window, -gpus, or -layout other than grey\n"
+        "                     writes a P5 with maxval 2^bps - 1.  With -isRGB 1 -components 3: one RGB still image or a video\n"
+        "                     (-video 1 -frames F, -framesPerLaunch 1..21) of raw little-endian 16-bit samples, -layout planar\n"
+        "                     (default: R, G, B planes of W*H), rgb (6 bytes a pixel) or rgba (8 bytes a pixel), in and out.\n"
+        "                     -drop works; no grey video, -rate, -psnr, -ssim, -train, -reduce, -window, -gpus, -cp 3, -compare,\n"
+        "                     and no -layout bgr / bgra\n"
         " -device D           GPU index (default 0);  --metrics <file>  JSON stage timings\n"
         " -gpus N             video coding: groups of frames sharded round-robin over devices D .. D+N-1 of this node\n"
         "                     (--devices a,b,c names them explicitly); every device copies its codestreams to the\n"
@@ -763,22 +766,100 @@ int run_train(const Options &o, size_t file_base, long nframes)
 constexpr long kProfFrames = 256;     // frames per pipeline slot whose stages are timed with HIP events
 
 // ---- -bps 9..16: ONE grey still image of 16-bit samples, coded (picsong_encode_images, GREY16) and decoded
-// (picsong_decode_images).  What every other mode says when it meets such a depth:
+// (picsong_decode_images); or, -isRGB 1 -components 3, one RGB still image or a video of 16-bit samples, coded
+// (picsong_encode_rgb_images) and decoded (picsong_decode_rgb_images) straight-line, a group of frames a call.  What every
+// other mode says when it meets such a depth:
 const char *const kDeepBuilt =
     "With -bps 9..16 this build codes one grey still image (-cd 0: a raw file of W*H little-endian 16-bit samples or a P5 PGM with "
-    "maxval > 255) and decodes it (-cd 1, -drop allowed): not -video, -isRGB, -rate, -psnr, -ssim, -train, -reduce, -window, -gpus or a "
-    "-layout other than grey; -signedOrUnsigned 1 is not built.";
+    "maxval > 255) and decodes it (-cd 1, -drop allowed); with -isRGB 1 -components 3 it codes one RGB still image or a video (-video 1 "
+    "-frames F, -framesPerLaunch 1..21) from a raw file of little-endian 16-bit samples -- -layout planar (the default: R, G, B planes "
+    "of W*H samples a frame), rgb (6 bytes a pixel) or rgba (8 bytes a pixel) -- and decodes it to such a file (-drop allowed): not a "
+    "grey -video, -rate, -psnr, -ssim, -train, -reduce, -window, -gpus, -cp 3, -compare, a PGM for RGB, -layout grey with RGB, bgr or bgra, "
+    "or a colour -layout without -isRGB; -signedOrUnsigned 1 is not built.";
 void deep_check_mode(const Options &o, bool rgb, int bps)
 {
     if (bps < 9 || bps > 16 || o.signed_or_unsigned != 0) die(std::string("Only unsigned samples of 8..16 bits are built. ") + kDeepBuilt);
-    if (o.video || rgb || o.has_rate || o.has_quality() || !o.train.empty() || o.reduce > 0 || o.win || o.gpus > 1 || !o.devices.empty() ||
-        o.layout > PICSONG_LAYOUT_GREY8 || !o.compare.empty() || o.search_frames > 0)
+    if (o.has_rate || o.has_quality() || !o.train.empty() || o.reduce > 0 || o.win || o.gpus > 1 || !o.devices.empty() || !o.compare.empty() ||
+        o.search_frames > 0)
         die(kDeepBuilt);
+    if (!rgb && (o.video || o.layout > PICSONG_LAYOUT_GREY8)) die(kDeepBuilt);
+    if (rgb && (o.layout == PICSONG_LAYOUT_GREY8 || o.layout == PICSONG_LAYOUT_BGR24 || o.layout == PICSONG_LAYOUT_BGRA32)) die(kDeepBuilt);
+}
+// the 16-bit layout of a deep RGB file (-layout planar | rgb | rgba, default planar), its bytes a frame and its picsong_image
+int deep_rgb_layout(int layout) { return layout == PICSONG_LAYOUT_RGB24 ? PICSONG_LAYOUT_RGB48 : (layout == PICSONG_LAYOUT_RGBA32 ? PICSONG_LAYOUT_RGBA64 : PICSONG_LAYOUT_PLANAR3_16); }
+size_t deep_rgb_frame_bytes(int layout16, int w, int h) { return (size_t)w * (size_t)h * (layout16 == PICSONG_LAYOUT_RGBA64 ? 8u : 6u); }
+picsong_image deep_rgb_image(int layout16, void *d, int w, int h)
+{
+    picsong_image im;
+    im.data = d; im.layout = layout16; im.plane_stride = (size_t)w * (size_t)h * 2;
+    im.pitch = (size_t)w * (layout16 == PICSONG_LAYOUT_PLANAR3_16 ? 2u : (layout16 == PICSONG_LAYOUT_RGB48 ? 6u : 8u));
+    return im;
+}
+// -bps 9..16 -isRGB 1 -components 3: the frames as the raw file holds them, a group of B a call of picsong_encode_rgb_images;
+// streams and _SIZE entries as the 8-bit RGB paths write them (an image: the header on component 0; a video: on frame 0's three)
+int run_encode_deep_rgb(const Options &o, const Pgm &pgm)
+{
+    if (pgm.is_pgm) die(std::string("A PGM holds one component. ") + kDeepBuilt);
+    const long nframes = o.video ? o.frames : 1;
+    if (nframes <= 0) die("Incorrect parameters. Please choose valid values. (-frames)");
+    if (o.frames_per_launch > 21) die(std::string("Incorrect parameters. -framesPerLaunch takes 1..21 RGB frames. ") + kDeepBuilt);
+    const int layout16 = deep_rgb_layout(o.layout);
+    const size_t fb = deep_rgb_frame_bytes(layout16, o.x, o.y);
+    {   // (before anything is created: a file of another kind, a grey one for instance, is too short)
+        std::ifstream in(o.input, std::ios::binary | std::ios::ate);
+        if (!in) die("Cannot open input file " + o.input);
+        if ((size_t)in.tellg() < fb * (size_t)nframes) die(std::string(kShortInput) + " " + kDeepBuilt);
+    }
+    HIPCK(hipSetDevice(o.device));
+    picsong_params p = make_params(o);
+    p.frames = o.video ? (int)nframes : 0;
+    Ctx ctx;
+    CK(picsong_ctx_create(&p, o.device, &ctx.p));
+    load_lut(ctx, o, o.wl, 3, o.k, o.cp);
+    int aw, ah, ncb;
+    CK(picsong_ctx_padded_dims(ctx, &aw, &ah, &ncb));
+    const size_t max_shorts = picsong_max_stream_shorts(aw, ah);
+    const int B = frames_per_launch(o.frames_per_launch, 6 * (size_t)aw * ah, 21, nframes);
+    const Stream s = stream_create();
+    const auto h_in = pinned_alloc<uint8_t>(fb * (size_t)B);
+    const auto d_in = dev_alloc<uint8_t>(fb * (size_t)B);
+    const auto h_out = pinned_alloc<uint16_t>(max_shorts * 2 * 3 * (size_t)B);
+    const auto d_out = dev_alloc<uint16_t>(max_shorts * 2 * 3 * (size_t)B);
+    std::vector<int> totals(3 * (size_t)B);
+    const int fd = open(o.input.c_str(), O_RDONLY);
+    if (fd < 0) die("Cannot open input file " + o.input);
+    { std::ofstream t0(o.output, std::ios::binary | std::ios::trunc), t1(o.output + "_SIZE", std::ios::trunc); }
+    StreamSink to(o.output);
+    auto t0 = std::chrono::steady_clock::now();
+    for (long f = 0; f < nframes; f += B) {
+        const int n = (int)std::min<long>(B, nframes - f);
+        if (!pread_exact(fd, h_in, fb * (size_t)n, (size_t)f * fb)) die(kShortInput);
+        HIPCK(hipMemcpyAsync(d_in, h_in, fb * (size_t)n, hipMemcpyHostToDevice, s));
+        const picsong_image im = deep_rgb_image(layout16, d_in, o.x, o.y);
+        CK(picsong_encode_rgb_images(ctx, n, &im, fb, (int)f, o.video ? 7 : 1, d_out, max_shorts, s));
+        CK(picsong_last_totals(ctx, s, 3 * n, totals.data()));
+        int flag = 0;
+        CK(picsong_range_flag(ctx, s, &flag));
+        if (flag) {
+            to.out.close();
+            std::remove(o.output.c_str());
+            std::remove((o.output + "_SIZE").c_str());
+            die("A coefficient of this input reaches 2^15, beyond what the coder codes (picsong_depth_range_guaranteed_rgb says which "
+                "depths never do): nothing written.");
+        }
+        collect_streams(s, d_out, max_shorts, totals.data(), 3 * n, h_out, to);
+    }
+    close(fd);
+    double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::cout << "The time spent with the app without considering allocation periods is: " << sec << std::endl;
+    write_metrics(o, "encode_rgb", nframes, sec, 0, 0, 0, to.total_shorts);
+    return 0;
 }
 int run_encode_deep(const Options &o, const Pgm &pgm)
 {
     deep_check_mode(o, o.is_rgb != 0, o.bps);
     if (o.cp == 3) die(std::string("-cp 3 is not built for -bps 9..16. ") + kDeepBuilt);
+    if (o.is_rgb) return run_encode_deep_rgb(o, pgm);
     if (pgm.is_pgm && pgm.maxval <= 255) die("Incorrect parameters. -bps " + std::to_string(o.bps) + " takes a P5 PGM with maxval > 255 (two bytes a sample).");
     const size_t n = (size_t)o.x * (size_t)o.y;
     std::vector<uint16_t> img(n);
@@ -1437,10 +1518,73 @@ int run_decode_video(const Options &o, const picsong_params &p, const std::vecto
 
 // -bps 9..16 (the stream's header says so): one grey still image through picsong_decode_images with GREY16, written as
 // the 8-bit path writes -- a P5 with maxval 2^bd - 1, its two-byte samples big-endian as Netpbm defines
+// ... or, an RGB stream: the frames in groups of B through picsong_decode_rgb_images, appended to the raw output in -layout
+int run_decode_deep_rgb(const Options &o, const picsong_params &p, std::ifstream &in)
+{
+    const long nframes = o.video ? p.frames : 1;
+    if (nframes <= 0) die("The header of this stream gives no frames.");
+    if (o.frames_per_launch > 21) die(std::string("Incorrect parameters. -framesPerLaunch takes 1..21 RGB frames. ") + kDeepBuilt);
+    std::vector<long> shorts;
+    {
+        std::ifstream sz(o.input + "_SIZE");
+        if (!sz) die("Cannot open " + o.input + "_SIZE");
+        std::string tok;
+        while (std::getline(sz, tok, ',')) if (!tok.empty()) shorts.push_back(std::stol(tok));
+        if ((long)shorts.size() < nframes * 3) die("_SIZE sidecar lists fewer streams than the header.");
+    }
+    HIPCK(hipSetDevice(o.device));
+    const Ctx ctx = create_decode_ctx(p, o.device, o.drop);
+    load_lut(ctx, o, p.wl, 3, p.k, p.cp);
+    int aw, ah, ncb;
+    CK(picsong_ctx_padded_dims(ctx, &aw, &ah, &ncb));
+    const size_t max_shorts = picsong_max_stream_shorts(aw, ah);
+    const int layout16 = deep_rgb_layout(o.layout);
+    const size_t fb = deep_rgb_frame_bytes(layout16, p.width, p.height);
+    const int B = frames_per_launch(o.frames_per_launch, 6 * (size_t)aw * ah, 21, nframes);
+    const Stream s = stream_create();
+    const auto h_in = pinned_alloc<uint16_t>(max_shorts * 2 * 3 * (size_t)B);
+    const auto d_in = dev_alloc<uint16_t>(max_shorts * 2 * 3 * (size_t)B);
+    const auto h_pix = pinned_alloc<uint8_t>(fb * (size_t)B);
+    const auto d_pix = dev_alloc<uint8_t>(fb * (size_t)B);
+    std::ofstream out(o.output, std::ios::binary | std::ios::trunc);
+    if (!out) die("Cannot open output file " + o.output);
+    auto t0 = std::chrono::steady_clock::now();
+    size_t pos = 0, all = 0;
+    for (long f = 0; f < nframes; f += B) {
+        const int n = (int)std::min<long>(B, nframes - f);
+        size_t group = 0;
+        for (int j = 0; j < 3 * n; j++) {
+            const size_t len = (size_t)shorts[(size_t)(f * 3 + j)];
+            if (len > max_shorts) die("Component codestream longer than the maximum for this geometry.");
+            group += len;
+        }
+        if (!read_exact(in, h_in, group * 2, pos * 2)) die(kShortStream);
+        pos += group;
+        size_t at = 0;
+        for (int j = 0; j < 3 * n; j++) {
+            const size_t len = (size_t)shorts[(size_t)(f * 3 + j)];
+            HIPCK(hipMemcpyAsync(d_in + (size_t)j * max_shorts, h_in + at, len * 2, hipMemcpyHostToDevice, s));
+            at += len;
+        }
+        const picsong_image im = deep_rgb_image(layout16, d_pix, p.width, p.height);
+        CK(picsong_decode_rgb_images(ctx, n, d_in, max_shorts, &im, fb, s));
+        HIPCK(hipMemcpyAsync(h_pix, d_pix, fb * (size_t)n, hipMemcpyDeviceToHost, s));
+        HIPCK(hipStreamSynchronize(s));
+        out.write(reinterpret_cast<const char *>(h_pix.p), (std::streamsize)(fb * (size_t)n));
+        all += group;
+    }
+    double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::cout << "The time spent with the app without considering allocation periods and I/O is: " << sec << std::endl;
+    Options mo = o;
+    mo.x = p.width; mo.y = p.height;
+    write_metrics(mo, "decode_rgb", nframes, sec, 0, 0, 0, (long)all);
+    return 0;
+}
 int run_decode_deep(const Options &o, const picsong_params &p, std::ifstream &in)
 {
     deep_check_mode(o, p.is_rgb != 0, p.bit_depth);
     if (p.cp == 3) die(std::string("-cp 3 is not built for -bps 9..16. ") + kDeepBuilt);
+    if (p.is_rgb) return run_decode_deep_rgb(o, p, in);
     in.clear();
     in.seekg(0, std::ios::end);
     const size_t shorts = (size_t)in.tellg() / 2;

@@ -30,7 +30,9 @@ class Image(C.Structure):
 
 
 LAYOUT_GREY8, LAYOUT_PLANAR3, LAYOUT_RGB24, LAYOUT_BGR24, LAYOUT_RGBA32, LAYOUT_BGRA32, LAYOUT_GREY16 = range(7)
-LAYOUT_BPP = (1, 1, 3, 3, 4, 4, 2)
+LAYOUT_PLANAR3_16, LAYOUT_RGB48, LAYOUT_RGBA64 = 7, 8, 9          # deep RGB contexts: native uint16 samples
+LAYOUT_BPP = (1, 1, 3, 3, 4, 4, 2, 2, 6, 8)
+LAYOUTS_16 = (LAYOUT_GREY16, LAYOUT_PLANAR3_16, LAYOUT_RGB48, LAYOUT_RGBA64)
 
 
 class LutInfo(C.Structure):
@@ -75,6 +77,8 @@ EXPORTS = [
     "picsong_ctx_set_decode_drop", "picsong_ctx_get_decode_drop", "picsong_drop_planes",
     "picsong_depth_range_guaranteed", "picsong_pad_frame16_host", "picsong_level_shift_fwd16", "picsong_dwt_forward_u16",
     "picsong_encode_frames16", "picsong_decode_frames16",
+    "picsong_depth_range_guaranteed_rgb", "picsong_rgb_forward16", "picsong_rgb_inverse16",
+    "picsong_encode_rgb_frames16", "picsong_decode_rgb_frames16",
     "picsong_ssim_windows", "picsong_ssim_to_dssim", "picsong_dssim_to_ssim", "picsong_frames_dssim",
     "picsong_encode_frame_ssim", "picsong_encode_frames_ssim", "picsong_encode_rgb_frames_ssim",
 ]
@@ -229,6 +233,12 @@ def load():
         L.picsong_dwt_forward_u16.argtypes = [vp, vp, vp, vp]
         L.picsong_encode_frames16.argtypes = [vp, i, vp, C.c_size_t, i, vp, C.c_size_t, vp]
         L.picsong_decode_frames16.argtypes = [vp, i, vp, C.c_size_t, vp, C.c_size_t, vp]
+    if hasattr(L, "picsong_encode_rgb_frames16"):
+        L.picsong_depth_range_guaranteed_rgb.argtypes = [i, i, i, C.c_float, C.POINTER(i)]
+        L.picsong_rgb_forward16.argtypes = [vp] * 8
+        L.picsong_rgb_inverse16.argtypes = [vp] * 8
+        L.picsong_encode_rgb_frames16.argtypes = [vp, i, vp, vp, vp, C.c_size_t, i, i, vp, C.c_size_t, vp]
+        L.picsong_decode_rgb_frames16.argtypes = [vp, i, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp]
     if hasattr(L, "picsong_frames_dssim"):
         u64 = C.c_uint64
         L.picsong_ssim_windows.argtypes = [i, i, C.POINTER(u64)]
@@ -391,6 +401,14 @@ def depth_range_guaranteed(bit_depth, lossy, wl, qs=1.0):
     return bool(yes.value)
 
 
+def depth_range_guaranteed_rgb(bit_depth, lossy, wl, qs=1.0):
+    """The same question for a deep RGB context (picsong_depth_range_guaranteed_rgb): the RCT's chroma components span one
+    bit more than a grey sample, the ICT's components as much as one."""
+    yes = C.c_int()
+    _check(load().picsong_depth_range_guaranteed_rgb(bit_depth, int(lossy), wl, qs, C.byref(yes)))
+    return bool(yes.value)
+
+
 def pad_frame16(img_u16, aw, ah):
     """picsong_pad_frame16_host: the (H, W) uint16 frame mirror-padded to (ah, aw)."""
     img_u16 = np.ascontiguousarray(img_u16, np.uint16)
@@ -418,15 +436,22 @@ class Codec:
     objects + the LUT upload of Engine::initLUT).  All tensor arguments are torch CUDA tensors."""
 
     def __init__(self, width, height, wl=5, lossy=False, qs=1.0, lut_folder=None, lut_fill=0,
-                 device=0, frames=0, rgb=False, k=0.0, pipelined=False, cp=2, bit_depth=8):
+                 device=0, frames=0, rgb=False, k=0.0, pipelined=False, cp=2, bit_depth=8, is_rgb=False):
+        """rgb: an 8-bit RGB context, whose methods take and return uint8 planes (encode_rgb_frame and its kin) -- with
+        bit_depth 9..16 it is refused here, as it always was.  is_rgb (with bit_depth 9..16): a deep RGB context, three uint16
+        planes a frame through the *16 RGB methods; with bit_depth 8 it is rgb."""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the picsong HIP path has no CPU fallback")
         self.torch = torch
         self.L = load()
+        if rgb and bit_depth != 8:
+            raise PicsongError(f"Codec(rgb=True) is the 8-bit RGB context (uint8 planes); {bit_depth}-bit colour: Codec(bit_depth={bit_depth}, "
+                               "is_rgb=True), uint16 planes through encode_rgb_frames16 / decode_rgb_frames16")
+        rgb = bool(rgb or is_rgb)
         self.params = make_params(width, height, wl, lossy, qs, frames, rgb, k, cp, bit_depth)
         self.bit_depth = bit_depth
-        self.rgb = bool(rgb)
+        self.rgb = rgb
         self.device = device
         h = C.c_void_p()
         _check(self.L.picsong_ctx_create(C.byref(self.params), device, C.byref(h)))
@@ -485,7 +510,7 @@ class Codec:
     def image(self, t, layout, pitch=None, plane_stride=0, offset=0):
         """The picsong_image of the uint8 CUDA tensor `t` (any shape; its storage from byte `offset` on is the frame):
         rows `pitch` bytes apart (default: packed, W * bpp), PLANAR3 planes plane_stride bytes apart."""
-        assert (t.dtype == self.torch.uint8 or layout == LAYOUT_GREY16) and t.is_cuda
+        assert (t.dtype == self.torch.uint8 or layout in LAYOUTS_16) and t.is_cuda
         pitch = self.params.width * LAYOUT_BPP[layout] if pitch is None else pitch
         return Image(data=t.data_ptr() + offset, pitch=pitch, plane_stride=plane_stride, layout=layout)
 
@@ -493,8 +518,8 @@ class Codec:
         """n frames of `img` (an Image; frame f frame_stride bytes behind frame 0) to padded planar planes on the device:
         uint8 [n, planes, AH, AW] (planes: 1 for GREY8, else R, G, B), mirror-padded as picsong_pad_frame_host pads."""
         planes = 1 if img.layout in (LAYOUT_GREY8, LAYOUT_GREY16) else 3
-        if out is None:                                  # (GREY16: int16 tensors holding the uint16 samples)
-            out = self.torch.empty((n, planes, self.ah, self.aw), dtype=self.torch.int16 if img.layout == LAYOUT_GREY16 else self.torch.uint8,
+        if out is None:                                  # (the 16-bit layouts: int16 tensors holding the uint16 samples)
+            out = self.torch.empty((n, planes, self.ah, self.aw), dtype=self.torch.int16 if img.layout in LAYOUTS_16 else self.torch.uint8,
                                    device=self.dev)
         _check(self.L.picsong_ingest_frames(self.h, n, C.byref(img), frame_stride, self._p(out), out.stride(0) * out.element_size(),
                                             self._stream()))
@@ -922,6 +947,45 @@ class Codec:
         _check(self.L.picsong_decode_frames16(self.h, n, self._p(streams), streams.stride(0), self._p(out), frame_stride,
                                               self._stream()))
         return out
+
+    # ---- deep RGB contexts (Codec(bit_depth=9..16, is_rgb=True)): three uint16 planes a frame, int16 tensors as above ----
+    def rgb_forward16(self, r, g, b):
+        outs = [self.torch.empty(self.P, dtype=self.dtype, device=self.dev) for _ in range(3)]
+        _check(self.L.picsong_rgb_forward16(self.h, self._p(r), self._p(g), self._p(b), self._p(outs[0]), self._p(outs[1]),
+                                            self._p(outs[2]), self._stream()))
+        return outs
+
+    def rgb_inverse16(self, c0, c1, c2):
+        outs = [self.torch.empty((self.ah, self.aw), dtype=self.torch.int16, device=self.dev) for _ in range(3)]
+        _check(self.L.picsong_rgb_inverse16(self.h, self._p(c0), self._p(c1), self._p(c2), self._p(outs[0]), self._p(outs[1]),
+                                            self._p(outs[2]), self._stream()))
+        return outs
+
+    def encode_rgb_frames16(self, r, g, b, n=None, frame_stride=None, first_iter=0, header_mask=7):
+        """n deep RGB frames; r / g / b: int16 [n, AH, AW] tensors (frame f stride(0) elements behind frame 0, the same for
+        all three), or frame 0's planes with n and frame_stride (BYTES) given.  Returns the 3 n codestreams, frame f's
+        component c at index 3 f + c."""
+        if n is None:
+            n = r.shape[0]
+        if frame_stride is None:
+            frame_stride = 2 * r.stride(0) if n > 1 else 0
+            assert n == 1 or (g.stride(0) == r.stride(0) and b.stride(0) == r.stride(0))
+        out = self.torch.empty((3 * n, self.max_stream_shorts()), dtype=self.torch.int16, device=self.dev)
+        _check(self.L.picsong_encode_rgb_frames16(self.h, n, self._p(r), self._p(g), self._p(b), frame_stride, first_iter, header_mask,
+                                                  self._p(out), out.stride(0), self._stream()))
+        return [out[k, :t] for k, t in enumerate(self.last_totals(3 * n))]
+
+    def decode_rgb_frames16(self, streams, outs=None, frame_stride=None):
+        """streams: int16 [3 n, >= max_stream_shorts()]; returns the R, G, B planes as three int16 [n, AH, AW] tensors holding
+        the uint16 samples (or writes frame f's planes frame_stride BYTES behind outs[0..2], frame 0's)."""
+        assert streams.stride(-1) == 1 and streams.shape[0] % 3 == 0
+        n = streams.shape[0] // 3
+        if outs is None:
+            outs = [self.torch.empty((n, self.ah, self.aw), dtype=self.torch.int16, device=self.dev) for _ in range(3)]
+            frame_stride = 2 * outs[0].stride(0)
+        _check(self.L.picsong_decode_rgb_frames16(self.h, n, self._p(streams), streams.stride(0), self._p(outs[0]), self._p(outs[1]),
+                                                  self._p(outs[2]), frame_stride or 0, self._stream()))
+        return outs
 
     # ---- whole frame (asynchronous; last_total() synchronises) ----
     def encode_frame_async(self, frame_u8_padded, out_stream, iter_=0):

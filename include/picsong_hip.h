@@ -625,6 +625,9 @@ int picsong_encode_rgb_frames_ssim(picsong_ctx *ctx, int n, const uint8_t *d_r, 
 #define PICSONG_LAYOUT_RGBA32  4   /* A ignored on input, 255 on output */
 #define PICSONG_LAYOUT_BGRA32  5
 #define PICSONG_LAYOUT_GREY16  6   /* 2 bytes a pixel, little-endian; deep contexts */
+#define PICSONG_LAYOUT_PLANAR3_16 7 /* deep RGB contexts: three uint16 planes plane_stride bytes apart */
+#define PICSONG_LAYOUT_RGB48   8   /* ... interleaved R, G, B, 6 bytes a pixel */
+#define PICSONG_LAYOUT_RGBA64  9   /* ... interleaved R, G, B, A, 8 bytes; A ignored on input, 2^bd - 1 on output */
 typedef struct picsong_image { void *data; size_t pitch; size_t plane_stride; int layout; } picsong_image;
 int picsong_ingest_frames(picsong_ctx *ctx, int n, const picsong_image *src, size_t frame_stride, uint8_t *d_padded,
                           size_t padded_stride, void *stream);
@@ -640,7 +643,7 @@ int picsong_decode_rgb_image(picsong_ctx *ctx, const uint16_t *d_streams, size_t
                              void *stream);
 
 /* ---- deep contexts: 9- to 16-bit grey samples (cinema, broadcast, medical, remote sensing).  A context created with
- *      bit_depth 9..16 (components 1, is_rgb 0; an RGB one is refused) takes its frames as native (little-endian)
+ *      bit_depth 9..16 (components 1, is_rgb 0; an RGB one: "deep RGB contexts" below) takes its frames as native (little-endian)
  *      uint16_t samples v in [0, 2^bd - 1]; off = 2^(bd-1).  Only the transform's two ends differ from an 8-bit context:
  *        forward   5/3: x = (int32)v - off;  9/7: x = (float)v - (float)off (offsetImage with the depth as a parameter).
  *                  v is read UNSIGNED (65535 is never -1); a v above 2^bd - 1 is the caller's error: coded as it is,
@@ -722,6 +725,70 @@ int picsong_encode_rgb_images(picsong_ctx *ctx, int n, const picsong_image *src,
                               int header_mask, uint16_t *d_streams, size_t stream_stride, void *stream);
 int picsong_decode_rgb_images(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride,
                               const picsong_image *dst, size_t frame_stride, void *stream);
+
+/* ---- deep RGB contexts: 9- to 16-bit colour samples (HDR and broadcast video, cinema masters, camera and scanner RGB).
+ *      A context created with bit_depth 9..16, components 3 and is_rgb 1 takes a frame as three padded planes of native
+ *      (little-endian) uint16_t samples v in [0, 2^bd - 1], padded by the rule of picsong_pad_frame16_host;
+ *      off = 2^(bd-1), mx = 2^bd - 1.  The colour transforms are the 8-bit ones on level-shifted 16-bit samples:
+ *        forward 5/3 (RCT)  R' = (int32)R - off (likewise G', B'); c0 = (R' + 2 G' + B') >> 2, c1 = B' - G', c2 = R' - G'.
+ *        forward 9/7 (ICT)  R' = (float)R - (float)off; c_k = fmaf(m_k2, B', fmaf(m_k1, G', m_k0 * R')), the matrix and
+ *                           order of the 8-bit transform.
+ *        inverse 5/3        G' = c0 - ((c1 + c2) >> 2), R' = c2 + G', B' = c1 + G'; sample = clamp(x + off, 0, mx).
+ *        inverse 9/7        x = (int)rintf(fmaf(M_k2, c2, fmaf(M_k1, c1, M_k0 * c0)) + 0.01f); sample = clamp(x + off, 0, mx):
+ *                           the 8-bit arithmetic with 255 replaced by mx (a NaN component is left unspecified).
+ *      Samples are read UNSIGNED; one above mx is the caller's error: coded as it is, decoded clamped.  Component c is
+ *      then a deep grey plane coded with table c (32-bit coefficients, one launch a stage over the 3 n planes, plane z
+ *      with table z % 3).  Header: both depth fields carry bd, components 3, is_rgb 1, n_samples = W * H * 3.
+ *      picsong_ctx_set_decode_drop stays allowed: the three components use the same drop.
+ *      Range: the RCT's chroma components span +-(2^bd - 1), one bit more than a grey sample; the ICT's rows have absolute
+ *      sum 1, so |c_k| <= off.  picsong_depth_range_guaranteed_rgb (host only): the bound of
+ *      picsong_depth_range_guaranteed with max|sample| = 2^bd for 5/3 and 2^(bd-1) for 9/7; refuses what that call
+ *      refuses and bit_depth 8.  Where it says no the calls do not refuse: a coefficient that reaches 2^15 raises
+ *      picsong_range_flag, as on a deep grey context.
+ *      picsong_rgb_forward16 / picsong_rgb_inverse16: the stage seams, uint16[P] x 3 <-> T[P] x 3 (T = int32 / float);
+ *        the sample pointers need 2-byte alignment (8-byte aligned ones take one 8-byte access a lane's four samples,
+ *        others 2-byte accesses: the same values); the T planes 16-byte alignment (refused otherwise).
+ *      picsong_encode_rgb_frames16 / picsong_decode_rgb_frames16: n = 1..21 frames.  d_r / d_g / d_b are frame 0's
+ *        planes, frame f's lie f * frame_stride BYTES after each; frame_stride is even, >= 2 P, must not let a frame's
+ *        planes overlap the next frame's, and is ignored for n = 1.  Streams at (3 f + c) * stream_stride shorts;
+ *        first_iter, header_mask, lengths and asynchrony exactly as picsong_encode_rgb_frames /
+ *        picsong_decode_rgb_frames; -cp 2 only, any -k; the three tables must share one geometry.  One launch a
+ *        transform level over the 3 n planes (grid.z = plane).  Encoding, level 0 reads a frame's three sample planes
+ *        and applies the colour transform in its load stage, so the component planes are never written: its vector
+ *        form (three 8-byte loads a lane) where all three planes are 16-byte aligned and frame_stride is a multiple
+ *        of 16, its per-column form otherwise; PICSONG_DEEP_NOFUSE=1 (read per call) runs the colour transform of the
+ *        n frames as ONE launch of its own (grid.y = frame) and the T-input level 0 instead: the same bytes.
+ *        Decoding, the synthesis writes the 3 n T planes and ONE inverse-transform launch follows.  Every stream is
+ *        byte-identical to picsong_rgb_forward16 + 3 x picsong_encode_plane of that frame, every decoded plane to
+ *        3 x picsong_decode_plane + picsong_rgb_inverse16.  Decoding writes exactly 2 P bytes a plane.  Pointers
+ *        need 2-byte alignment.
+ *      picsong_image layouts PLANAR3_16, RGB48 and RGBA64 (native uint16 samples): data, pitch and the strides are
+ *        2-byte aligned (refused otherwise), pitch >= W * bpp (2, 6, 8); no byte outside [y * pitch, y * pitch + W * bpp)
+ *        of rows 0 .. H - 1 is read or written; RGBA64's A is ignored on input and written as mx on output.
+ *        picsong_ingest_frames / picsong_emit_frames accept them on a deep RGB context: the padded side is three
+ *        uint16 planes a frame (R, G, B, 2 P bytes each), passed through the uint8_t * parameter, padded_stride in
+ *        bytes (>= 6 P).  picsong_encode_rgb_images / picsong_decode_rgb_images accept them there: ONE ingest (emit)
+ *        of the n frames into (from) the context's aligned buffer, then the frame calls above, byte-identical to them
+ *        on host-padded planes.  A 4-byte aligned image side and a 16-byte aligned padded side take the vector form
+ *        (dwords of the image, a dwordx4 a plane), anything else 2-byte accesses: the same bytes.  They are refused on
+ *        every other context; the 8-bit layouts and GREY16 are refused on a deep RGB context.
+ *      Refused on a deep RGB context (PICSONG_ERR_ARG, nothing launched, outputs untouched): every call that takes or
+ *      returns uint8_t frames, the 8-bit RGB calls included; picsong_encode_frames16 / picsong_decode_frames16; the
+ *      searches, training on frames, proxies and stripes; picsong_encode_images / picsong_decode_images and the
+ *      single-frame picsong_encode_rgb_image / picsong_decode_rgb_image.  The plane calls (picsong_encode_plane,
+ *      picsong_decode_plane and the stage calls on T arrays) work as on a deep grey context.  Refused on every other
+ *      context: the four device calls below.
+ *      Not built: a fused tail for the decode, bgr / bgra 16-bit layouts. ---- */
+int picsong_depth_range_guaranteed_rgb(int bit_depth, int lossy, int wl, float qs, int *yes);          /* host only */
+int picsong_rgb_forward16(picsong_ctx *ctx, const uint16_t *d_r, const uint16_t *d_g, const uint16_t *d_b, void *d_c0,
+                          void *d_c1, void *d_c2, void *stream);
+int picsong_rgb_inverse16(picsong_ctx *ctx, const void *d_c0, const void *d_c1, const void *d_c2, uint16_t *d_r,
+                          uint16_t *d_g, uint16_t *d_b, void *stream);
+int picsong_encode_rgb_frames16(picsong_ctx *ctx, int n, const uint16_t *d_r, const uint16_t *d_g, const uint16_t *d_b,
+                                size_t frame_stride, int first_iter, int header_mask,
+                                uint16_t *d_streams, size_t stream_stride, void *stream);
+int picsong_decode_rgb_frames16(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride,
+                                uint16_t *d_r, uint16_t *d_g, uint16_t *d_b, size_t frame_stride, void *stream);
 
 /* ---- colour proxies: n = 1..21 RGB frames at 1/2^reduce, or a window of them, through ONE launch per stage over the
  *      3 n planes -- thumbnails, previews and editing proxies of a colour video, whose launches are too small to run

@@ -49,6 +49,11 @@ def make_inputs(d):
     deep = (orc.gen_frame(W, H, 5).astype(np.uint16) * 16 + orc.gen_frame(W, H, 6) % 16).astype(">u2")
     with open(os.path.join(d, "deep12.pgm"), "wb") as f:
         f.write(f"P5\n# 12 bits\n{W} {H}\n4095\n".encode() + deep.tobytes())
+    # three 12-bit RGB frames: planar (R, G, B planes a frame) and interleaved, 6 bytes a pixel
+    deep_rgb = [[(orc.gen_frame(W, H, 20 * f + c).astype(np.uint16) * 16 + orc.gen_frame(W, H, 20 * f + c + 7) % 16).astype("<u2")
+                 for c in range(3)] for f in range(3)]
+    np.concatenate([p.ravel() for fr in deep_rgb for p in fr]).tofile(os.path.join(d, "deep12_planar.raw"))
+    np.concatenate([np.stack(fr, axis=-1).ravel() for fr in deep_rgb]).tofile(os.path.join(d, "deep12_rgb48.raw"))
     raw = open(os.path.join(d, "grey_a.raw"), "rb").read()
     open(os.path.join(d, "grey_a_5.raw"), "wb").write(raw[:5 * W * H])                   # (-compare: the frames coded)
     open(os.path.join(d, "grey_a_truncated.raw"), "wb").write(raw[:2 * W * H + 1000])    # short within the first group
@@ -117,6 +122,10 @@ def commands():
         video=5)
     # ---- one -bps 12 PGM; -train (a grey video, an RGB image)
     enc("deep12", "deep12.pgm", LOSSLESS, "-wl", 3, "-type", 0, "-bps", 12)
+    # ---- -bps 12 RGB: an image from planar planes, a video from interleaved pixels, two frames a launch
+    enc("deep12_rgb_img", "deep12_planar.raw", LOSSLESS, *A, *RGB, "-wl", 3, "-type", 0, "-bps", 12)
+    enc("deep12_rgb_vid", "deep12_rgb48.raw", LOSSY, *A, *RGB, "-wl", 3, "-type", 1, "-qs", 0.25, "-bps", 12, "-layout", "rgb",
+        "-framesPerLaunch", 2, video=3)
     out.append(("train_grey", ["-cd", 0, "-i", "../in/grey_a.raw", *A, "-wl", 3, "-video", 1, "-frames", 9, "-framesPerLaunch", 4,
                                "-train", "train_grey"], None))
     out.append(("train_rgb", ["-cd", 0, "-i", "../in/planar_b.raw", *B, *RGB, "-wl", 2, "-train", "train_rgb", "-LUTFolder", LOSSLESS], None))
@@ -125,7 +134,7 @@ def commands():
     for name, video, lut in encoded:
         v = ("-video", 1) if video else ()
         for tag, extra in (("full", ()), ("reduce", ("-reduce", 1)), ("window", ("-window", "8,8,64,40")), ("drop", ("-drop", 2))):
-            if name == "deep12" and tag in ("reduce", "window"):
+            if name.startswith("deep12") and tag in ("reduce", "window"):
                 continue                                          # (refused before the stream is opened: nothing to compare)
             m = ("--metrics", f"{name}.{tag}.json") if name in ("vid_grey_b_5", "img_rgb_a_53", "vid_rgb_a_5") else ()
             out.append((f"{name}.{tag}", ["-cd", 1, "-i", f"{name}.enc", "-o", f"{name}.{tag}.dec", "-LUTFolder", lut, *v, *extra, *m], None))
