@@ -2508,10 +2508,29 @@ __device__ __forceinline__ uint32_t clamp_u16(float rounded, int off, int mx)
     return (uint32_t)((int)r + off);
 }
 
+// The inverse RCT / ICT of one pixel's three component samples (the bits of T as they lie in memory), level shift and clamp
+// to [0, mx]: rgb_inverse16_kernel's arithmetic, and the deep window epilogue's (window_rgb16_image_kernel)
+template <typename T>
+__device__ __forceinline__ void rgb_inverse16_px(uint32_t q0, uint32_t q1, uint32_t q2, int off, int mx, uint32_t &R, uint32_t &G, uint32_t &B)
+{
+    if constexpr (std::is_integral<T>::value) {
+        const int y = (int)q0, cb = (int)q1, cr = (int)q2;
+        const int g = y - ((cb + cr) >> 2);
+        R = clamp_u16(cr + g, off, mx);
+        G = clamp_u16(g, off, mx);
+        B = clamp_u16(cb + g, off, mx);
+    } else {
+        const float M[3][3] = { { 1.0f, 0.0f, 1.402f }, { 1.0f, -0.344136f, -0.714136f }, { 1.0f, 1.772f, 0.0f } };
+        const float y = __uint_as_float(q0), cb = __uint_as_float(q1), cr = __uint_as_float(q2);
+        R = clamp_u16(rintf(fmaf(M[0][2], cr, fmaf(M[0][1], cb, M[0][0] * y)) + 0.01f), off, mx);
+        G = clamp_u16(rintf(fmaf(M[1][2], cr, fmaf(M[1][1], cb, M[1][0] * y)) + 0.01f), off, mx);
+        B = clamp_u16(rintf(fmaf(M[2][2], cr, fmaf(M[2][1], cb, M[2][0] * y)) + 0.01f), off, mx);
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void rgb_inverse16_kernel(Rgb16Args a)
 {
-    const float M[3][3] = { { 1.0f, 0.0f, 1.402f }, { 1.0f, -0.344136f, -0.714136f }, { 1.0f, 1.772f, 0.0f } };
     const unsigned long long f = blockIdx.y;
     const char *c0 = (const char *)a.c0 + f * a.cmp_z, *c1 = (const char *)a.c1 + f * a.cmp_z, *c2 = (const char *)a.c2 + f * a.cmp_z;
     char *r = (char *)a.r + f * a.smp_z, *g = (char *)a.g + f * a.smp_z, *b = (char *)a.b + f * a.smp_z;
@@ -2521,20 +2540,7 @@ __global__ __launch_bounds__(256) void rgb_inverse16_kernel(Rgb16Args a)
         const uint32_t *q0 = &w0.x, *q1 = &w1.x, *q2 = &w2.x;
         uint32_t oR[4], oG[4], oB[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if constexpr (std::is_integral<T>::value) {
-                const int y = (int)q0[k], cb = (int)q1[k], cr = (int)q2[k];
-                const int G = y - ((cb + cr) >> 2);
-                oR[k] = clamp_u16(cr + G, a.off, a.mx);
-                oG[k] = clamp_u16(G, a.off, a.mx);
-                oB[k] = clamp_u16(cb + G, a.off, a.mx);
-            } else {
-                const float y = __uint_as_float(q0[k]), cb = __uint_as_float(q1[k]), cr = __uint_as_float(q2[k]);
-                oR[k] = clamp_u16(rintf(fmaf(M[0][2], cr, fmaf(M[0][1], cb, M[0][0] * y)) + 0.01f), a.off, a.mx);
-                oG[k] = clamp_u16(rintf(fmaf(M[1][2], cr, fmaf(M[1][1], cb, M[1][0] * y)) + 0.01f), a.off, a.mx);
-                oB[k] = clamp_u16(rintf(fmaf(M[2][2], cr, fmaf(M[2][1], cb, M[2][0] * y)) + 0.01f), a.off, a.mx);
-            }
-        }
+        for (int k = 0; k < 4; k++) rgb_inverse16_px<T>(q0[k], q1[k], q2[k], a.off, a.mx, oR[k], oG[k], oB[k]);
         store4_u16(r, i, a.wide, oR);
         store4_u16(g, i, a.wide, oG);
         store4_u16(b, i, a.wide, oB);

@@ -185,8 +185,14 @@ inline InvRgbLaunch select_inv_rgb(bool lossy, const InvLaunch &f)
 // ---- the window synthesis (256 threads, the WinLaunch's grid)
 inline WinKernel select_window(bool lossy, bool u8)
 {
-    if (lossy) return u8 ? dwt_window_kernel<float, true> : dwt_window_kernel<float, false>;
-    return u8 ? dwt_window_kernel<int, true> : dwt_window_kernel<int, false>;
+    if (lossy) return u8 ? dwt_window_kernel<float, kWinOutU8> : dwt_window_kernel<float, kWinOutT>;
+    return u8 ? dwt_window_kernel<int, kWinOutU8> : dwt_window_kernel<int, kWinOutT>;
+}
+// ... by a launch's output form (WinLaunch::out): kWinOutU16 is level r of a deep grey call
+inline WinKernel select_window_out(bool lossy, int out)
+{
+    if (out != kWinOutU16) return select_window(lossy, out == kWinOutU8);
+    return lossy ? dwt_window_kernel<float, kWinOutU16> : dwt_window_kernel<int, kWinOutU16>;
 }
 
 // ---- the coders: kernel, threads a workgroup, workgroups for `waves` waves (a wave codes a codeblock pair), and the
@@ -608,10 +614,11 @@ inline const char *rgb_frames_window_refusal(bool ctx_rgb, int cp, bool same_geo
     return rgb_frames_refusal(ctx_rgb, cp, same_geometry, n, r, g, b, streams, frame_stride, stream_stride, span, max_stream);
 }
 // picsong_decode_rgb_images_window (and _reduced, its window (0, 0, rw, rh)): the w x h window in a colour layout of
-// picsong_image -- layout_refusal's rules on a w x h image, no grey layout
+// picsong_image -- layout_refusal's rules on a w x h image, no grey layout.  deep_rgb (a deep RGB context): PLANAR3_16,
+// RGB48 and RGBA64 and nothing else; they are unknown layouts to every other context
 inline const char *rgb_images_window_refusal(bool ctx_rgb, int cp, bool same_geometry, int n, const void *streams, size_t stream_stride,
                                              size_t max_stream, int aw, int ah, int wl, int reduce, int x, int y, int w, int h, int layout,
-                                             const void *data, size_t pitch, size_t plane_stride, size_t frame_stride)
+                                             const void *data, size_t pitch, size_t plane_stride, size_t frame_stride, bool deep_rgb = false)
 {
     if (!data || !streams) return "null pointer";
     if (!ctx_rgb) return "the context is not an RGB one";
@@ -621,7 +628,8 @@ inline const char *rgb_images_window_refusal(bool ctx_rgb, int cp, bool same_geo
     if (stream_stride < max_stream) return "stream stride smaller than a worst-case codestream";
     if (!same_geometry) return "the components' tables differ in geometry: code the planes one by one";
     if (layout == kLayoutGrey8) return "a grey layout on an RGB call";
-    return layout_refusal(layout, data, pitch, plane_stride, frame_stride, data, 3 * (size_t)w * (size_t)h, n, w, h, w, h);
+    return layout_refusal(layout, data, pitch, plane_stride, frame_stride, data, (deep_rgb ? 6 : 3) * (size_t)w * (size_t)h, n, w, h, w, h,
+                          deep_rgb, deep_rgb);
 }
 
 // picsong_decode_rgb_images_reduced's route: the reduced sequence into aligned planar planes, then emit_frames with the
@@ -666,6 +674,129 @@ inline WinRgbLaunch select_window_rgb(bool lossy, int layout, const WinRgbArgs &
     case kLayoutBgr24:   k = window_rgb_kernel_of<kLayoutBgr24>(lossy, vec); break;
     case kLayoutRgba32:  k = window_rgb_kernel_of<kLayoutRgba32>(lossy, vec); break;
     case kLayoutBgra32:  k = window_rgb_kernel_of<kLayoutBgra32>(lossy, vec); break;
+    }
+    return { k, grid, vec };
+}
+
+// ---- the deep proxy calls (picsong_decode_frames16_reduced / _window, picsong_decode_rgb_frames16_reduced / _window):
+// uint16 samples, every pitch and stride in BYTES.  What they refuse, as a message that names the call to use instead
+// where the context is of another kind; nullptr: the arguments are fine.
+// The context's side: bit_depth 9..16, grey for the grey pair and RGB for the RGB pair, -cp 2
+inline const char *deep_proxy_ctx_refusal(int bit_depth, bool ctx_rgb, bool want_rgb, int cp, bool window)
+{
+    if (!deep_depth_ok(bit_depth)) {
+        if (want_rgb) return window ? "uint16 samples want a deep RGB context (bit_depth 9..16): an 8-bit context's call is picsong_decode_rgb_frames_window"
+                                    : "uint16 samples want a deep RGB context (bit_depth 9..16): an 8-bit context's call is picsong_decode_rgb_frames_reduced";
+        return window ? "uint16 samples want a deep context (bit_depth 9..16): an 8-bit context's call is picsong_decode_frames_window"
+                      : "uint16 samples want a deep context (bit_depth 9..16): an 8-bit context's call is picsong_decode_frames_reduced";
+    }
+    if (ctx_rgb && !want_rgb)
+        return window ? "grey frames on an RGB context: its call is picsong_decode_rgb_frames16_window"
+                      : "grey frames on an RGB context: its call is picsong_decode_rgb_frames16_reduced";
+    if (!ctx_rgb && want_rgb)
+        return window ? "the context is not an RGB one: its call is picsong_decode_frames16_window"
+                      : "the context is not an RGB one: its call is picsong_decode_frames16_reduced";
+    if (cp == 3) return "-cp 3 contexts decode whole planes only (picsong_decode_plane)";
+    return nullptr;
+}
+// n grey frames of `span` bytes each (the reduced plane, or the window's (h - 1) * pitch + 2 w), frame_stride bytes apart
+inline const char *frames16_span_refusal(int n, const void *out, const void *streams, size_t frame_stride, size_t stream_stride,
+                                         size_t max_stream, size_t span)
+{
+    if (n < 1 || n > 64) return "n outside 1..64";
+    if ((((uintptr_t)out) | ((uintptr_t)streams)) & 1u) return "pointers need 2-byte alignment";
+    if (n > 1 && (frame_stride & 1u)) return "frame_stride must be even";
+    if (n > 1 && frame_stride < span) return "frame_stride smaller than a frame's samples";
+    if (n > 1 && stream_stride < max_stream) return "stream stride smaller than a worst-case codestream";
+    return nullptr;
+}
+inline const char *frames16_reduced_refusal(int bit_depth, bool ctx_rgb, int cp, int n, const void *out, const void *streams, size_t frame_stride,
+                                            size_t stream_stride, size_t max_stream, int aw, int ah, int wl, int reduce)
+{
+    if (const char *why = deep_proxy_ctx_refusal(bit_depth, ctx_rgb, false, cp, false)) return why;
+    if (!out || !streams) return "null pointer";
+    if (!reduce_ok(wl, reduce)) return "reduce outside 0..wl - 1";
+    return frames16_span_refusal(n, out, streams, frame_stride, stream_stride, max_stream, 2 * (size_t)(aw >> reduce) * (size_t)(ah >> reduce));
+}
+inline const char *frames16_window_refusal(int bit_depth, bool ctx_rgb, int cp, int n, const void *out, const void *streams, size_t pitch,
+                                           size_t frame_stride, size_t stream_stride, size_t max_stream, int aw, int ah, int wl, int reduce,
+                                           int x, int y, int w, int h)
+{
+    if (const char *why = deep_proxy_ctx_refusal(bit_depth, ctx_rgb, false, cp, true)) return why;
+    if (!out || !streams) return "null pointer";
+    if (const char *why = proxy_window_refusal(aw, ah, wl, reduce, x, y, w, h)) return why;
+    if (pitch & 1u) return "out_pitch must be even";
+    if (pitch < 2 * (size_t)w) return "out_pitch smaller than the window's row of 2 w bytes";
+    return frames16_span_refusal(n, out, streams, frame_stride, stream_stride, max_stream, (size_t)(h - 1) * pitch + 2 * (size_t)w);
+}
+// the RGB pair: rgb_frames_refusal's rules on planes of `span` bytes, and the alignment of 2-byte samples
+inline const char *rgb_frames16_span_refusal(int cp, bool same_geometry, int n, const void *r, const void *g, const void *b, const void *streams,
+                                             size_t frame_stride, size_t stream_stride, size_t max_stream, size_t span)
+{
+    if (const char *why = rgb_frames_refusal(true, cp, same_geometry, n, r, g, b, streams, frame_stride, stream_stride, span, max_stream)) return why;
+    if ((((uintptr_t)r) | ((uintptr_t)g) | ((uintptr_t)b) | ((uintptr_t)streams)) & 1u) return "pointers need 2-byte alignment";
+    if (n > 1 && (frame_stride & 1u)) return "frame_stride must be even";
+    return nullptr;
+}
+inline const char *rgb_frames16_reduced_refusal(int bit_depth, bool ctx_rgb, int cp, bool same_geometry, int n, const void *r, const void *g,
+                                                const void *b, const void *streams, size_t frame_stride, size_t stream_stride,
+                                                size_t max_stream, int aw, int ah, int wl, int reduce)
+{
+    if (const char *why = deep_proxy_ctx_refusal(bit_depth, ctx_rgb, true, cp, false)) return why;
+    if (!r || !g || !b || !streams) return "null pointer";
+    if (!reduce_ok(wl, reduce)) return "reduce outside 0..wl - 1";
+    return rgb_frames16_span_refusal(cp, same_geometry, n, r, g, b, streams, frame_stride, stream_stride, max_stream,
+                                     2 * (size_t)(aw >> reduce) * (size_t)(ah >> reduce));
+}
+inline const char *rgb_frames16_window_refusal(int bit_depth, bool ctx_rgb, int cp, bool same_geometry, int n, const void *r, const void *g,
+                                               const void *b, const void *streams, size_t pitch, size_t frame_stride, size_t stream_stride,
+                                               size_t max_stream, int aw, int ah, int wl, int reduce, int x, int y, int w, int h)
+{
+    if (const char *why = deep_proxy_ctx_refusal(bit_depth, ctx_rgb, true, cp, true)) return why;
+    if (!r || !g || !b || !streams) return "null pointer";
+    if (const char *why = proxy_window_refusal(aw, ah, wl, reduce, x, y, w, h)) return why;
+    if (pitch & 1u) return "out_pitch must be even";
+    if (pitch < 2 * (size_t)w) return "out_pitch smaller than the window's row of 2 w bytes";
+    return rgb_frames16_span_refusal(cp, same_geometry, n, r, g, b, streams, frame_stride, stream_stride, max_stream,
+                                     (size_t)(h - 1) * pitch + 2 * (size_t)w);
+}
+
+// Their colour epilogue (window_rgb16_image_kernel, window_kernels.hpp): select_window_rgb's grid -- 256 threads, a thread
+// four adjacent pixels of a row, grid.x over the rows' groups, grid.z = frame.  d0 .. d2: frame 0's R, G, B planes
+// (kLayoutPlanar3_16) or d0 its pixels (kLayoutRgb48, kLayoutRgba64).  The vector form where every store address is 4-byte
+// aligned: pointers, pitch and, n > 1, the frame stride; a8: 8-byte aligned as well (dwordx2 stores).
+using WinRgb16Kernel = void (*)(WinRgb16Args);
+struct WinRgb16Launch { WinRgb16Kernel kernel; dim3 grid; bool vec; };
+inline WinRgb16Args window_rgb16_args(int layout, const void *work, unsigned long long z_stride, int w, int h, uint8_t *d0, uint8_t *d1,
+                                      uint8_t *d2, size_t pitch, size_t frame_stride, unsigned n, int off, int px_max)
+{
+    WinRgb16Args a;
+    memset(&a, 0, sizeof a);
+    a.work = work; a.z_stride = z_stride; a.w = w; a.h = h;
+    a.src16 = (w & 3) == 0 && ((((uintptr_t)work) | z_stride) & 15u) == 0 ? 1 : 0;
+    a.dst[0] = d0;
+    a.dst[1] = layout == kLayoutPlanar3_16 ? d1 : d0;
+    a.dst[2] = layout == kLayoutPlanar3_16 ? d2 : d0;
+    a.pitch = pitch; a.frame_stride = n > 1 ? frame_stride : 0; a.off = off; a.mx = px_max;
+    a.a8 = ((((uintptr_t)a.dst[0]) | ((uintptr_t)a.dst[1]) | ((uintptr_t)a.dst[2]) | a.pitch | a.frame_stride) & 7u) == 0 ? 1 : 0;
+    return a;
+}
+template <int L>
+inline WinRgb16Kernel window_rgb16_kernel_of(bool lossy, bool vec)
+{
+    if (lossy) return vec ? window_rgb16_image_kernel<float, L, true> : window_rgb16_image_kernel<float, L, false>;
+    return vec ? window_rgb16_image_kernel<int, L, true> : window_rgb16_image_kernel<int, L, false>;
+}
+inline WinRgb16Launch select_window_rgb16(bool lossy, int layout, const WinRgb16Args &a, unsigned n)
+{
+    const bool vec = ((((uintptr_t)a.dst[0]) | ((uintptr_t)a.dst[1]) | ((uintptr_t)a.dst[2]) | a.pitch | a.frame_stride) & 3u) == 0;
+    const size_t groups = (size_t)((a.w + 3) / 4) * (size_t)a.h;
+    const dim3 grid((unsigned)((groups + 255) / 256), 1u, n);
+    WinRgb16Kernel k = nullptr;
+    switch (layout) {
+    case kLayoutPlanar3_16: k = window_rgb16_kernel_of<kLayoutPlanar3_16>(lossy, vec); break;
+    case kLayoutRgb48:      k = window_rgb16_kernel_of<kLayoutRgb48>(lossy, vec); break;
+    case kLayoutRgba64:     k = window_rgb16_kernel_of<kLayoutRgba64>(lossy, vec); break;
     }
     return { k, grid, vec };
 }

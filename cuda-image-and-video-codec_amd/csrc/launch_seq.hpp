@@ -293,15 +293,16 @@ int run_inverse_rgb(const Go &go, bool lossy, bool lean97, const std::vector<Inv
 // ---- the windowed synthesis (window_kernels.hpp) of `frames` frames, grid.z = frame: frame z's coefficients at coef_i +
 // z * coef_z bytes, its scratch (T[P + extra]) at work + z * work_z bytes.  u8 != nullptr: level r writes frame z's
 // window at u8 + z * u8_z, row stride pitch; else level r's samples stay at frame z's `work` (compact, row stride w).
+// px_max > 0 (a deep context): the window holds uint16 samples clamped to px_max; pitch and u8_z stay in bytes.
 template <class Go>
 int run_window(const Go &go, bool lossy, const WindowPlan &w, const int32_t *coef_i, void *work, size_t P, int aw, int ah, float qs,
                int off, unsigned frames, unsigned long long coef_z, unsigned long long work_z, uint8_t *u8, size_t pitch,
-               unsigned long long u8_z)
+               unsigned long long u8_z, int px_max = 0)
 {
-    for (WinLaunch &f : plan_window_synthesis(w, coef_i, work, P, aw, ah, qs, u8, pitch, off)) {
+    for (WinLaunch &f : plan_window_synthesis(w, coef_i, work, P, aw, ah, qs, u8, pitch, off, px_max)) {
         f.a.mallat_z = coef_z; f.a.ll_z = work_z; f.a.dst_z = work_z; f.a.u8_z = u8_z;
         f.grid.z = frames;
-        if (int rc = go(select_window(lossy, f.u8), f.grid, 256u, f.a)) return rc;
+        if (int rc = go(select_window_out(lossy, f.out), f.grid, 256u, f.a)) return rc;
     }
     return 0;
 }
@@ -418,7 +419,8 @@ int decode_frames(const Go &go, const DecodeCtx &c, BpcArgs a, const Workspace &
     if (n <= 1) frame_stride = 0;
     if (int rc = decode_head(go, c, a, w, n, streams, stream_stride, reduce, win, want_c16, out, frame_stride, plan, rep)) return rc;
     const size_t z = (c.P + c.extra) * 4, n4 = (size_t)(c.aw >> reduce) * (size_t)(c.ah >> reduce) / 4;
-    if (win) return run_window(go, c.lossy, *win, w.coef_i, w.coef, c.P, c.aw, c.ah, c.qs, c.off, n, (unsigned long long)c.P * 4ull, z, out, pitch, frame_stride);
+    // (a deep context, px_max > 0: level r stores uint16 samples, pitch and frame_stride in bytes)
+    if (win) return run_window(go, c.lossy, *win, w.coef_i, w.coef, c.P, c.aw, c.ah, c.qs, c.off, n, (unsigned long long)c.P * 4ull, z, out, pitch, frame_stride, c.px_max);
     if (int rc = run_inverse(go, c.lossy, lean97, plan, n, &rep.fused10)) return rc;
     // (level `reduce`'s samples of frame f: c.extra elements into its work buffer when reduce = 0)
     for (unsigned f = 0; f < n && !rep.pixels; f++) {
@@ -436,6 +438,8 @@ int decode_frames(const Go &go, const DecodeCtx &c, BpcArgs a, const Workspace &
 // win: run_window with frames = 3 n, level r's samples left compact in the planes' work buffers, and the epilogue
 // (window_rgb_image_kernel, grid.z = frame) that stores them in `layout`: d0 .. d2 frame 0's R, G, B planes
 // (kLayoutPlanar3), or d0 its interleaved pixels; rows `pitch` bytes apart.  One frame into planar planes: window_rgb_kernel.
+// A deep RGB context (px_max > 0): uint16 samples, `layout` one of the three 16-bit ones, pitch and frame_stride in bytes --
+// the reduced planes through rgb_inverse16 over (aw >> reduce) x (ah >> reduce) samples, a window through window_rgb16_image_kernel.
 template <class Go>
 int decode_rgb_frames(const Go &go, const DecodeCtx &c, BpcArgs a, const Workspace &w, unsigned n, const uint16_t *streams,
                       size_t stream_stride, int reduce, const WindowPlan *win, bool want_c16, bool lean97, bool fuse_tail, int layout,
@@ -450,6 +454,14 @@ int decode_rgb_frames(const Go &go, const DecodeCtx &c, BpcArgs a, const Workspa
         if (int rc = run_window(go, c.lossy, *win, w.coef_i, w.coef, c.P, c.aw, c.ah, c.qs, c.off, 3u * n, (unsigned long long)c.P * 4ull, z,
                                 nullptr, 0, 0)) return rc;
         const IRect &o = win->R[win->r];
+        if (c.px_max > 0) {
+            // a deep RGB context: uint16 samples in kLayoutPlanar3_16, kLayoutRgb48 or kLayoutRgba64, one launch whatever n
+            const WinRgb16Args ra = window_rgb16_args(layout, w.coef, z, o.x1 - o.x0, o.y1 - o.y0, d0, d1, d2, pitch, frame_stride, n, c.off, c.px_max);
+            const WinRgb16Launch l = select_window_rgb16(c.lossy, layout, ra, n);
+            if (!l.kernel) return kLaunchRefused;
+            rep.vec = l.vec;
+            return go(l.kernel, l.grid, 256u, ra);
+        }
         // (one frame into planar planes keeps the per-pixel epilogue: measured against the n-frame one, profiles/NOTES.md)
         if (n == 1 && layout == kLayoutPlanar3) {
             const dim3 grid((unsigned)((o.x1 - o.x0 + 255) / 256), (unsigned)(o.y1 - o.y0));

@@ -1435,6 +1435,35 @@ int picsong_decode_frames16(picsong_ctx *c, int n, const uint16_t *d_streams, si
     return decode_grey(c, n, d_streams, stream_stride, reinterpret_cast<uint8_t *>(d_frames_out), frame_stride, stream, 0);
 }
 
+// The proxies of deep grey frames: picsong_decode_frames_reduced / _window on uint16 samples, strides and pitch in bytes.
+// The same sequence (decode_frames with DecodeCtx::px_max): the reduced corner's or the cone's codeblocks, the synthesis to
+// level `reduce`, whose launch stores the clamped samples (reduced: where the output is 16-byte aligned and
+// PICSONG_DEEP_NOFUSE is unset, else a clamp_pixels16 pass a frame; window: always).
+int picsong_decode_frames16_reduced(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                    uint16_t *d_frames_out, size_t frame_stride, void *stream)
+{
+    const char *who = "decode_frames16_reduced";
+    if (!c) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (const char *why = frames16_reduced_refusal(c->p.bit_depth, c->p.is_rgb != 0, c->p.cp, n, d_frames_out, d_streams, frame_stride, stream_stride,
+                                                   picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce))
+        return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+    return decode_grey(c, n, d_streams, stream_stride, reinterpret_cast<uint8_t *>(d_frames_out), frame_stride, stream, reduce);
+}
+
+int picsong_decode_frames16_window(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y, int w,
+                                   int h, uint16_t *d_out, size_t out_pitch, size_t frame_stride, void *stream)
+{
+    const char *who = "decode_frames16_window";
+    if (!c) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (const char *why = frames16_window_refusal(c->p.bit_depth, c->p.is_rgb != 0, c->p.cp, n, d_out, d_streams, out_pitch, frame_stride,
+                                                  stream_stride, picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce, x, y,
+                                                  w, h))
+        return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+    WindowPlan plan;
+    if (int rc = window_args_ok(c, reduce, x, y, w, h, who, &plan)) return rc;
+    return decode_grey(c, n, d_streams, stream_stride, reinterpret_cast<uint8_t *>(d_out), frame_stride, stream, reduce, &plan, out_pitch);
+}
+
 // ---------------------------------------------------------------------------------------------
 // RGB path
 // ---------------------------------------------------------------------------------------------
@@ -2615,6 +2644,36 @@ static int decode_rgb_window_impl(picsong_ctx *c, int n, const uint16_t *d_strea
     return decode_rgb(c, n, d_streams, stream_stride, reduce, &plan, layout, d0, d1, d2, pitch, frame_stride, stream);
 }
 
+// The proxies of deep RGB frames: picsong_decode_rgb_frames_reduced / _window on uint16 planes, strides and pitch in bytes.
+// The same sequence (decode_rgb_frames with DecodeCtx::px_max).  Reduced: the synthesis of the 3 n planes to level
+// `reduce`, then ONE rgb_inverse16 launch over the n frames' reduced planes.  Window: level r leaves T samples compact, then
+// ONE window_rgb16_image_kernel launch, grid.z = frame.
+int picsong_decode_rgb_frames16_reduced(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, uint16_t *d_r,
+                                        uint16_t *d_g, uint16_t *d_b, size_t frame_stride, void *stream)
+{
+    const char *who = "decode_rgb_frames16_reduced";
+    if (!c) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (const char *why = rgb_frames16_reduced_refusal(c->p.bit_depth, c->p.is_rgb != 0, c->p.cp, true, n, d_r, d_g, d_b, d_streams, frame_stride,
+                                                       stream_stride, picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce))
+        return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+    return decode_rgb(c, n, d_streams, stream_stride, reduce, nullptr, kLayoutPlanar3_16, reinterpret_cast<uint8_t *>(d_r),
+                      reinterpret_cast<uint8_t *>(d_g), reinterpret_cast<uint8_t *>(d_b), 0, frame_stride, stream);
+}
+
+int picsong_decode_rgb_frames16_window(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
+                                       int w, int h, uint16_t *d_r, uint16_t *d_g, uint16_t *d_b, size_t out_pitch, size_t frame_stride,
+                                       void *stream)
+{
+    const char *who = "decode_rgb_frames16_window";
+    if (!c) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (const char *why = rgb_frames16_window_refusal(c->p.bit_depth, c->p.is_rgb != 0, c->p.cp, true, n, d_r, d_g, d_b, d_streams, out_pitch,
+                                                      frame_stride, stream_stride, picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah,
+                                                      c->p.wl, reduce, x, y, w, h))
+        return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
+    return decode_rgb_window_impl(c, n, d_streams, stream_stride, reduce, x, y, w, h, kLayoutPlanar3_16, reinterpret_cast<uint8_t *>(d_r),
+                                  reinterpret_cast<uint8_t *>(d_g), reinterpret_cast<uint8_t *>(d_b), out_pitch, frame_stride, stream, who);
+}
+
 static int decode_rgb_frames_window_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
                                          int w, int h, uint8_t *d_r, uint8_t *d_g, uint8_t *d_b, size_t out_pitch, size_t frame_stride,
                                          void *stream, const char *who)
@@ -2647,10 +2706,12 @@ int picsong_decode_rgb_frame_window(picsong_ctx *c, const uint16_t *d_streams, s
 static int decode_rgb_images_window_impl(picsong_ctx *c, int n, const uint16_t *d_streams, size_t stream_stride, int reduce, int x, int y,
                                          int w, int h, const picsong_image *dst, size_t frame_stride, void *stream, const char *who)
 {
-    REFUSE_DEEP(c, who);
+    // (a deep RGB context takes PLANAR3_16, RGB48 and RGBA64 -- uint16 samples through window_rgb16_image_kernel -- and
+    // refuses the 8-bit layouts; a deep grey one has no colour call)
+    if (!is_deep_rgb(c)) REFUSE_DEEP(c, who);
     if (const char *why = rgb_images_window_refusal(c->p.is_rgb != 0, c->p.cp, true, n, d_streams, stream_stride,
                                                     picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce, x, y, w, h,
-                                                    dst->layout, dst->data, dst->pitch, dst->plane_stride, frame_stride))
+                                                    dst->layout, dst->data, dst->pitch, dst->plane_stride, frame_stride, is_deep_rgb(c)))
         return fail(PICSONG_ERR_ARG, "%s: %s", who, why);
     uint8_t *const d = (uint8_t *)dst->data;
     return decode_rgb_window_impl(c, n, d_streams, stream_stride, reduce, x, y, w, h, dst->layout, d, d + dst->plane_stride,
@@ -2672,12 +2733,14 @@ int picsong_decode_rgb_images_reduced(picsong_ctx *c, int n, const uint16_t *d_s
                                       const picsong_image *dst, size_t frame_stride, void *stream)
 {
     const char *who = "decode_rgb_images_reduced";
-    REFUSE_DEEP(c, who);
     if (!c || !dst) return fail(PICSONG_ERR_ARG, "%s: null argument", who);
+    if (!is_deep_rgb(c)) REFUSE_DEEP(c, who);
     if (!reduce_ok(c->p.wl, reduce)) return fail(PICSONG_ERR_ARG, "%s: reduce %d outside 0..%d (wl - 1)", who, reduce, c->p.wl - 1);
     int d[5];
     reduced_dims(c->p.width, c->p.height, c->aw, c->ah, reduce, d);
-    if (!reduced_emit_ok(c->aw, reduce))
+    // (a deep RGB context: the window route alone -- it decodes no more codeblocks than the reduced sequence and its
+    // epilogue writes the layout itself, where the other route would add a uint16 emit pass over planes just written)
+    if (is_deep_rgb(c) || !reduced_emit_ok(c->aw, reduce))
         return decode_rgb_images_window_impl(c, n, d_streams, stream_stride, reduce, 0, 0, d[0], d[1], dst, frame_stride, stream, who);
     if (const char *why = rgb_images_window_refusal(c->p.is_rgb != 0, c->p.cp, true, n, d_streams, stream_stride,
                                                     picsong_max_stream_shorts(c->aw, c->ah), c->aw, c->ah, c->p.wl, reduce, 0, 0, d[0], d[1],

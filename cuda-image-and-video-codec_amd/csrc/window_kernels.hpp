@@ -12,8 +12,8 @@
 // vertical, a barrier between steps.  9/7 divides as the oracle does -- ((m * s) / q) / qs on the read, x / N1 and
 // x / N2 with true divisions (div_n1<true>, div_n2<true>), explicit fmaf in po_97_inv_1d's operation order.
 // Intermediate levels store R_l as T (row stride its width); level r stores pixels into the caller's window through
-// to_pixel (grey), or T that window_rgb_kernel turns into the three pixel planes (RGB; n frames in any colour layout:
-// window_rgb_image_kernel).
+// to_pixel (grey; a deep context: uint16 samples through to_sample16), or T that window_rgb_kernel turns into the three
+// pixel planes (RGB; n frames in any colour layout: window_rgb_image_kernel; a deep RGB context: window_rgb16_image_kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,6 +28,8 @@
 namespace picsong {
 
 constexpr int kWinTile = 64;            // output samples per tile side; 256 threads a workgroup
+// what a level stores: T over its rectangle, or -- level r of a grey call -- the window's u8 pixels or uint16 samples
+constexpr int kWinOutT = 0, kWinOutU8 = 1, kWinOutU16 = 2;
 
 struct WinSynArgs {
     const int32_t *mallat;              // the decoder's int32 Mallat array, row stride AW
@@ -37,14 +39,16 @@ struct WinSynArgs {
     int first;                          // l = wl - 1: LL_wl is read (and de-quantised) from the Mallat array instead
     int W, H;                           // LL_l's size
     int x0, y0, x1, y1;                 // R_l
-    void *dst;                          // T over R_l, row stride x1 - x0 (no U8OUT)
-    uint8_t *dst_u8;                    // U8OUT: the window's pixels, row (y - y0) at dst_u8 + (y - y0) * pitch
+    void *dst;                          // kWinOutT: T over R_l, row stride x1 - x0
+    uint8_t *dst_u8;                    // kWinOutU8: the window's pixels, row (y - y0) at dst_u8 + (y - y0) * pitch;
+                                        // kWinOutU16: its uint16 samples, the same row address (pitch in bytes, even)
     unsigned long long pitch;
     int off;                            // level shift
     float qs, q[4];                     // 9/7: the quantisation steps of level l (LL, HL, LH, HH) and the context's qs
     // grid.z = frames of a batched call (or the components of an RGB frame): frame z reads mallat + z * mallat_z and
     // ll + z * ll_z, writes dst + z * dst_z and dst_u8 + z * u8_z (bytes)
     unsigned long long mallat_z, ll_z, dst_z, u8_z;
+    int px_max;                         // kWinOutU16: the samples are clamped to [0, px_max]  (last: the fields above keep their offsets)
 };
 
 // reflect() folded twice (see above); i in [-4, n + 3], n >= 4
@@ -98,8 +102,9 @@ __device__ __forceinline__ void win_step(T *tile, int nx, int ny, int gx0, int g
     __syncthreads();
 }
 
-// T = int (5/3) or float (9/7); U8OUT: level r of a grey call, pixels into the window
-template <typename T, bool U8OUT>
+// T = int (5/3) or float (9/7); OUT: kWinOutT, or level r of a grey call -- kWinOutU8: pixels into the window, kWinOutU16
+// (a deep context): uint16 samples into it, rows a.pitch BYTES apart
+template <typename T, int OUT>
 __global__ __launch_bounds__(256) void dwt_window_kernel(WinSynArgs a)
 {
     constexpr bool LOSSY = std::is_same<T, float>::value;
@@ -111,7 +116,7 @@ __global__ __launch_bounds__(256) void dwt_window_kernel(WinSynArgs a)
         a.mallat = (const int32_t *)((const char *)a.mallat + z * a.mallat_z);
         a.ll = (const char *)a.ll + z * a.ll_z;
         a.dst = (char *)a.dst + z * a.dst_z;
-        if (U8OUT) a.dst_u8 += z * a.u8_z;
+        if (OUT != kWinOutT) a.dst_u8 += z * a.u8_z;
     }
     const int tx0 = a.x0 + (int)blockIdx.x * kWinTile, ty0 = a.y0 + (int)blockIdx.y * kWinTile;
     const int tw = imin(kWinTile, a.x1 - tx0), th = imin(kWinTile, a.y1 - ty0);
@@ -176,7 +181,9 @@ __global__ __launch_bounds__(256) void dwt_window_kernel(WinSynArgs a)
     for (int j = (int)threadIdx.x >> 6; j < th; j += 4)
         for (int i = (int)threadIdx.x & 63; i < tw; i += 64) {
             const T v = tile[(j + HL) * TS + i + HL];
-            if constexpr (U8OUT) a.dst_u8[(size_t)(oy + j) * a.pitch + (size_t)(ox + i)] = (uint8_t)to_pixel(v, a.off);
+            if constexpr (OUT == kWinOutU8) a.dst_u8[(size_t)(oy + j) * a.pitch + (size_t)(ox + i)] = (uint8_t)to_pixel(v, a.off);
+            else if constexpr (OUT == kWinOutU16)
+                reinterpret_cast<uint16_t *>(a.dst_u8 + (size_t)(oy + j) * a.pitch)[(size_t)(ox + i)] = (uint16_t)to_sample16(v, a.off, a.px_max);
             else reinterpret_cast<T *>(a.dst)[(size_t)(oy + j) * (size_t)ow + (size_t)(ox + i)] = v;
         }
 }
@@ -313,6 +320,117 @@ __global__ __launch_bounds__(256) void window_rgb_image_kernel(WinRgbArgs a)
     }
 }
 
+// The epilogue of the deep RGB window calls (picsong_decode_rgb_frames16_window, picsong_decode_rgb_images_window and
+// _reduced on a deep RGB context): the same walk -- a thread four adjacent pixels of a row, threads along the rows of the
+// window, row after row, grid.z = frame, 3 x 16 bytes read, no LDS -- with rgb_inverse16_kernel's arithmetic
+// (rgb_inverse16_px: level shift `off`, clamp to [0, mx]) and uint16 samples stored in kLayoutPlanar3_16 (8 bytes a
+// plane), kLayoutRgb48 (24 bytes) or kLayoutRgba64 (32 bytes, alpha = mx).  Pitch and frame stride in bytes.
+//   VEC: every store address is 4-byte aligned (pointers, pitch, frame stride): dword stores, or -- a8: all of them 8-byte
+//   aligned as well -- dwordx2 ones; a thread's bytes are contiguous and so are a wave's, 512 / 1536 / 2048 bytes a row
+//   segment.  The row's last, partial group and every destination that is not so aligned are stored sample by sample; the
+//   bytes are the same.  No byte outside [i * pitch, i * pitch + w * bpp) of rows 0 .. h - 1 is written.
+struct WinRgb16Args {
+    const void *work;                   // frame z's component c: T[w * h], row stride w, at work + (3 z + c) * z_stride
+    unsigned long long z_stride;
+    int w, h;
+    int src16;                          // the component rows take dwordx4 loads
+    uint8_t *dst[3];                    // frame 0 -- planar: the R, G, B planes; interleaved: dst[0], the pixels
+    unsigned long long pitch, frame_stride;
+    int off, mx;                        // level shift, 2^(bit depth) - 1
+    int a8;                             // VEC: the destination is 8-byte aligned as well
+};
+
+template <int L> struct WinRgb16Traits {
+    static_assert(L == kLayoutPlanar3_16 || L == kLayoutRgb48 || L == kLayoutRgba64, "a 16-bit colour layout");
+    static constexpr bool inter = L != kLayoutPlanar3_16;
+    static constexpr int spp = L == kLayoutRgba64 ? 4 : 3;               // samples a pixel (interleaved)
+};
+
+// ND dwords to q (4-byte aligned; a8: 8-byte aligned, ND even)
+template <int ND>
+__device__ __forceinline__ void win_store_dwords(uint8_t *q, bool a8, const uint32_t (&d)[ND])
+{
+    static_assert(ND % 2 == 0, "whole dwordx2");
+    if (a8) {
+#pragma unroll
+        for (int k = 0; k < ND / 2; k++) {
+            uint2 v;
+            v.x = d[2 * k]; v.y = d[2 * k + 1];
+            reinterpret_cast<uint2 *>(q)[k] = v;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < ND; k++) reinterpret_cast<uint32_t *>(q)[k] = d[k];
+    }
+}
+
+template <typename T, int L, bool VEC>
+__global__ __launch_bounds__(256) void window_rgb16_image_kernel(WinRgb16Args a)
+{
+    using LT = WinRgb16Traits<L>;
+    const uint32_t w = (uint32_t)a.w, gpr = (w + 3u) / 4u;                  // groups of four pixels a row
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= gpr * (uint32_t)a.h) return;
+    const uint32_t y = t / gpr, x0 = (t - y * gpr) * 4u, nvis = w - x0 < 4u ? w - x0 : 4u;
+    const unsigned long long z = blockIdx.z;
+    const char *const src = (const char *)a.work + 3ull * z * a.z_stride;
+    const size_t i = (size_t)y * (size_t)w + (size_t)x0;
+    T c[3][4];
+#pragma unroll
+    for (int k = 0; k < 3; k++) win_load4<T>((const T *)(src + (unsigned long long)k * a.z_stride) + i, a.src16 != 0, nvis, c[k]);
+    uint32_t s[3][4];                                                       // four pixels of R, G, B, a sample each
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        uint32_t q[3];
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+            if constexpr (std::is_integral<T>::value) q[m] = (uint32_t)c[m][k];
+            else q[m] = __float_as_uint(c[m][k]);
+        }
+        rgb_inverse16_px<T>(q[0], q[1], q[2], a.off, a.mx, s[0][k], s[1][k], s[2][k]);
+    }
+    const size_t row = (size_t)z * a.frame_stride + (size_t)y * a.pitch;
+    if constexpr (!LT::inter) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            uint8_t *const q = a.dst[k] + row + (size_t)x0 * 2u;
+            if (VEC && nvis == 4u) {
+                const uint32_t d[2] = { s[k][0] | (s[k][1] << 16), s[k][2] | (s[k][3] << 16) };
+                win_store_dwords<2>(q, a.a8 != 0, d);
+            } else {
+#pragma unroll
+                for (uint32_t j = 0; j < 4u; j++)
+                    if (j < nvis) reinterpret_cast<uint16_t *>(q)[j] = (uint16_t)s[k][j];
+            }
+        }
+    } else {
+        uint8_t *const q = a.dst[0] + row + (size_t)x0 * (2u * LT::spp);
+        if (VEC && nvis == 4u) {
+            if constexpr (LT::spp == 3) {
+                // r0 g0 | b0 r1 | g1 b1 | r2 g2 | b2 r3 | g3 b3
+                const uint32_t d[6] = { s[0][0] | (s[1][0] << 16), s[2][0] | (s[0][1] << 16), s[1][1] | (s[2][1] << 16),
+                                        s[0][2] | (s[1][2] << 16), s[2][2] | (s[0][3] << 16), s[1][3] | (s[2][3] << 16) };
+                win_store_dwords<6>(q, a.a8 != 0, d);
+            } else {
+                const uint32_t al = (uint32_t)a.mx << 16;
+                const uint32_t d[8] = { s[0][0] | (s[1][0] << 16), s[2][0] | al, s[0][1] | (s[1][1] << 16), s[2][1] | al,
+                                        s[0][2] | (s[1][2] << 16), s[2][2] | al, s[0][3] | (s[1][3] << 16), s[2][3] | al };
+                win_store_dwords<8>(q, a.a8 != 0, d);
+            }
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; j++) {
+                if (j < nvis) {
+                    uint16_t *const px = reinterpret_cast<uint16_t *>(q) + j * LT::spp;
+#pragma unroll
+                    for (int k = 0; k < 3; k++) px[k] = (uint16_t)s[k][j];
+                    if (LT::spp == 4) px[3] = (uint16_t)a.mx;
+                }
+            }
+        }
+    }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------
 // The decoder's rectangle table of a window plan (BpcArgs::win_n ...); returns the waves of one frame
 inline int window_bpc_table(BpcArgs &a, const WindowPlan &p)
@@ -336,10 +454,11 @@ inline int window_bpc_table(BpcArgs &a, const WindowPlan &p)
 // The synthesis launches of a window plan, level wl - 1 first.  Level l > r writes its compact rectangle into `work`
 // (one frame's T[P + extra] scratch): levels r + 1, r + 3, ... at element P (each at most P / 4 samples: the `extra`
 // region, wl >= 2 whenever such a level exists), levels r + 2, r + 4, ... at element 0; level r (rgb) at element 0.
-// Level r of a grey call writes the pixels: u8 != nullptr.
-struct WinLaunch { WinSynArgs a; dim3 grid; bool u8; };
+// Level r of a grey call writes the pixels: u8 != nullptr -- a deep context's (px_max > 0) as uint16 samples clamped to
+// px_max, `pitch` in bytes: WinLaunch::out says which form (kWinOutT ...), ::u8 that it is kWinOutU8.
+struct WinLaunch { WinSynArgs a; dim3 grid; bool u8; int out; };
 inline std::vector<WinLaunch> plan_window_synthesis(const WindowPlan &p, const int32_t *mallat, void *work, size_t P, int aw,
-                                                    int ah, float qs, uint8_t *u8, size_t pitch, int off)
+                                                    int ah, float qs, uint8_t *u8, size_t pitch, int off, int px_max = 0)
 {
     std::vector<WinLaunch> v;
     for (int l = p.wl - 1; l >= p.r; l--) {
@@ -359,11 +478,13 @@ inline std::vector<WinLaunch> plan_window_synthesis(const WindowPlan &p, const i
         a.dst_u8 = l == p.r ? u8 : nullptr;
         a.pitch = pitch;
         a.off = off;
+        a.px_max = px_max;
         a.qs = qs;
         for (int k = 0; k < 4; k++) a.q[k] = kQSteps[l][k];
         a.mallat_z = a.ll_z = a.dst_z = a.u8_z = 0;
         f.grid = dim3((unsigned)((out.x1 - out.x0 + kWinTile - 1) / kWinTile), (unsigned)((out.y1 - out.y0 + kWinTile - 1) / kWinTile), 1);
-        f.u8 = a.dst_u8 != nullptr;
+        f.out = a.dst_u8 == nullptr ? kWinOutT : (px_max > 0 ? kWinOutU16 : kWinOutU8);
+        f.u8 = f.out == kWinOutU8;
         v.push_back(f);
     }
     return v;

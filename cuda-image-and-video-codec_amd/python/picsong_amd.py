@@ -79,6 +79,8 @@ EXPORTS = [
     "picsong_encode_frames16", "picsong_decode_frames16",
     "picsong_depth_range_guaranteed_rgb", "picsong_rgb_forward16", "picsong_rgb_inverse16",
     "picsong_encode_rgb_frames16", "picsong_decode_rgb_frames16",
+    "picsong_decode_frames16_reduced", "picsong_decode_frames16_window", "picsong_decode_rgb_frames16_reduced",
+    "picsong_decode_rgb_frames16_window",
     "picsong_ssim_windows", "picsong_ssim_to_dssim", "picsong_dssim_to_ssim", "picsong_frames_dssim",
     "picsong_encode_frame_ssim", "picsong_encode_frames_ssim", "picsong_encode_rgb_frames_ssim",
 ]
@@ -239,6 +241,11 @@ def load():
         L.picsong_rgb_inverse16.argtypes = [vp] * 8
         L.picsong_encode_rgb_frames16.argtypes = [vp, i, vp, vp, vp, C.c_size_t, i, i, vp, C.c_size_t, vp]
         L.picsong_decode_rgb_frames16.argtypes = [vp, i, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp]
+    if hasattr(L, "picsong_decode_frames16_reduced"):
+        L.picsong_decode_frames16_reduced.argtypes = [vp, i, vp, C.c_size_t, i, vp, C.c_size_t, vp]
+        L.picsong_decode_frames16_window.argtypes = [vp, i, vp, C.c_size_t, i, i, i, i, i, vp, C.c_size_t, C.c_size_t, vp]
+        L.picsong_decode_rgb_frames16_reduced.argtypes = [vp, i, vp, C.c_size_t, i, vp, vp, vp, C.c_size_t, vp]
+        L.picsong_decode_rgb_frames16_window.argtypes = [vp, i, vp, C.c_size_t, i, i, i, i, i, vp, vp, vp, C.c_size_t, C.c_size_t, vp]
     if hasattr(L, "picsong_frames_dssim"):
         u64 = C.c_uint64
         L.picsong_ssim_windows.argtypes = [i, i, C.POINTER(u64)]
@@ -987,6 +994,60 @@ class Codec:
                                                   self._p(outs[2]), frame_stride or 0, self._stream()))
         return outs
 
+    # ---- deep proxies: deep frames at 1/2^r, or a window of them; uint16 samples in int16 tensors, strides in bytes ----
+    def decode_frames16_reduced(self, streams, r, out=None, frame_stride=None):
+        """streams: int16 [n, >= max_stream_shorts()]; returns int16 [n, AH >> r, AW >> r] holding the uint16 samples (or
+        writes frame f frame_stride BYTES behind `out`)."""
+        n = streams.shape[0]
+        assert streams.stride(-1) == 1
+        if out is None:
+            out = self.torch.empty((n, self.ah >> r, self.aw >> r), dtype=self.torch.int16, device=self.dev)
+        if frame_stride is None:
+            frame_stride = 2 * out.stride(0)
+        _check(self.L.picsong_decode_frames16_reduced(self.h, n, self._p(streams), streams.stride(0), r, self._p(out), frame_stride,
+                                                      self._stream()))
+        return out
+
+    def decode_frames16_window(self, streams, x, y, w, h, r=0, out=None):
+        """streams: int16 [n, >= max_stream_shorts()]; returns int16 [n, h, w] (or fills `out`, a 3-D int16 view: frame
+        stride out.stride(0), pitch out.stride(1), in elements)."""
+        n = streams.shape[0]
+        assert streams.stride(-1) == 1
+        if out is None:
+            out = self.torch.empty((n, h, w), dtype=self.torch.int16, device=self.dev)
+        assert out.dtype == self.torch.int16 and tuple(out.shape) == (n, h, w) and out.stride(2) == 1
+        _check(self.L.picsong_decode_frames16_window(self.h, n, self._p(streams), streams.stride(0), r, x, y, w, h, self._p(out),
+                                                     2 * out.stride(1), 2 * out.stride(0), self._stream()))
+        return out
+
+    def decode_rgb_frames16_reduced(self, streams, r, outs=None, frame_stride=None):
+        """streams: int16 [3 n, >= max_stream_shorts()]; returns the reduced R, G, B planes as three int16
+        [n, AH >> r, AW >> r] tensors (or writes frame f's planes frame_stride BYTES behind outs[0..2], frame 0's)."""
+        assert streams.stride(-1) == 1 and streams.shape[0] % 3 == 0
+        n = streams.shape[0] // 3
+        if outs is None:
+            outs = [self.torch.empty((n, self.ah >> r, self.aw >> r), dtype=self.torch.int16, device=self.dev) for _ in range(3)]
+        if frame_stride is None:
+            frame_stride = 2 * outs[0].stride(0) if n > 1 else 0
+        _check(self.L.picsong_decode_rgb_frames16_reduced(self.h, n, self._p(streams), streams.stride(0), r, self._p(outs[0]),
+                                                          self._p(outs[1]), self._p(outs[2]), frame_stride or 0, self._stream()))
+        return outs
+
+    def decode_rgb_frames16_window(self, streams, x, y, w, h, r=0, outs=None):
+        """streams: int16 [3 n, >= max_stream_shorts()]; returns the R, G, B windows as three int16 [n, h, w] tensors (or
+        fills `outs`, three 3-D int16 views with the same frame stride, stride(0), and pitch, stride(1))."""
+        assert streams.stride(-1) == 1 and streams.shape[0] % 3 == 0
+        n = streams.shape[0] // 3
+        if outs is None:
+            outs = [self.torch.empty((n, h, w), dtype=self.torch.int16, device=self.dev) for _ in range(3)]
+        for o in outs:
+            assert o.dtype == self.torch.int16 and tuple(o.shape) == (n, h, w) and o.stride(2) == 1
+            assert o.stride(0) == outs[0].stride(0) and o.stride(1) == outs[0].stride(1)
+        _check(self.L.picsong_decode_rgb_frames16_window(self.h, n, self._p(streams), streams.stride(0), r, x, y, w, h, self._p(outs[0]),
+                                                         self._p(outs[1]), self._p(outs[2]), 2 * outs[0].stride(1), 2 * outs[0].stride(0),
+                                                         self._stream()))
+        return outs
+
     # ---- whole frame (asynchronous; last_total() synchronises) ----
     def encode_frame_async(self, frame_u8_padded, out_stream, iter_=0):
         _check(self.L.picsong_encode_frame(self.h, self._p(frame_u8_padded), iter_, self._p(out_stream),
@@ -1172,13 +1233,15 @@ class Codec:
 
     def decode_rgb_images_reduced(self, streams, r, img, frame_stride=0):
         """streams: int16 [3 n, >= max_stream_shorts()]; the visible rw x rh pixels (reduced_dims) of the n frames at 1/2^r
-        land in `img` (any colour layout; frame f frame_stride bytes behind frame 0), alpha (if any) 255."""
+        land in `img` (any colour layout; frame f frame_stride bytes behind frame 0), alpha (if any) 255.  A deep RGB context
+        takes LAYOUT_PLANAR3_16, LAYOUT_RGB48 and LAYOUT_RGBA64 (alpha 2^bd - 1)."""
         assert streams.stride(-1) == 1 and streams.shape[0] % 3 == 0
         _check(self.L.picsong_decode_rgb_images_reduced(self.h, streams.shape[0] // 3, self._p(streams), streams.stride(0), r,
                                                         C.byref(img), frame_stride, self._stream()))
 
     def decode_rgb_images_window(self, streams, x, y, w, h, img, r=0, frame_stride=0):
-        """... and the w x h window at (x, y) of the padded image at 1/2^r, in the layout of `img`."""
+        """... and the w x h window at (x, y) of the padded image at 1/2^r, in the layout of `img` (a deep RGB context:
+        LAYOUT_PLANAR3_16, LAYOUT_RGB48 or LAYOUT_RGBA64, alpha 2^bd - 1)."""
         assert streams.stride(-1) == 1 and streams.shape[0] % 3 == 0
         _check(self.L.picsong_decode_rgb_images_window(self.h, streams.shape[0] // 3, self._p(streams), streams.stride(0), r, x, y, w,
                                                        h, C.byref(img), frame_stride, self._stream()))

@@ -774,8 +774,9 @@ int picsong_decode_rgb_images(picsong_ctx *ctx, int n, const uint16_t *d_streams
  *        every other context; the 8-bit layouts and GREY16 are refused on a deep RGB context.
  *      Refused on a deep RGB context (PICSONG_ERR_ARG, nothing launched, outputs untouched): every call that takes or
  *      returns uint8_t frames, the 8-bit RGB calls included; picsong_encode_frames16 / picsong_decode_frames16; the
- *      searches, training on frames, proxies and stripes; picsong_encode_images / picsong_decode_images and the
- *      single-frame picsong_encode_rgb_image / picsong_decode_rgb_image.  The plane calls (picsong_encode_plane,
+ *      searches, training on frames, the uint8_t proxies ("deep proxies" below are the uint16 ones) and stripes;
+ *      picsong_encode_images / picsong_decode_images and the single-frame picsong_encode_rgb_image /
+ *      picsong_decode_rgb_image.  The plane calls (picsong_encode_plane,
  *      picsong_decode_plane and the stage calls on T arrays) work as on a deep grey context.  Refused on every other
  *      context: the four device calls below.
  *      Not built: a fused tail for the decode, bgr / bgra 16-bit layouts. ---- */
@@ -828,6 +829,52 @@ int picsong_decode_rgb_images_reduced(picsong_ctx *ctx, int n, const uint16_t *d
                                       const picsong_image *dst, size_t frame_stride, void *stream);
 int picsong_decode_rgb_images_window(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
                                      int x, int y, int w, int h, const picsong_image *dst, size_t frame_stride, void *stream);
+
+/* ---- deep proxies: the reduced and the window decode of 9- to 16-bit frames, grey and RGB -- thumbnails and regions of
+ *      cinema, broadcast, medical and remote-sensing masters without decoding the whole frame at 32-bit coefficients.
+ *      The four calls mirror picsong_decode_frames_reduced / _window and picsong_decode_rgb_frames_reduced / _window on
+ *      native (little-endian) uint16_t samples; asynchronous on `stream`.  What changes:
+ *        the level shift and clamp are the deep context's (off = 2^(bd-1), mx = 2^bd - 1): 5/3 clamp(v + off, 0, mx);
+ *        9/7 clamp(rintf((v + off) + 0.01f), 0, mx), NaN -> 0; RGB the inverse RCT / ICT of "deep RGB contexts" above,
+ *        applied to the three components' LL_reduce.
+ *        frame_stride and out_pitch are in BYTES and must be even; pointers need 2-byte alignment.
+ *        Grey takes n = 1..64 (a deep grey context), RGB n = 1..21 (a deep RGB one); frame_stride is ignored for n = 1.
+ *      The reduced calls write exactly paw * pah samples a plane (picsong_reduced_dims), row stride paw samples, and
+ *      nothing else; reduce = 0 is byte-identical to picsong_decode_frames16 / picsong_decode_rgb_frames16.  The window
+ *      calls write the w samples of row i at (char *)d_out + f * frame_stride + i * out_pitch and nothing else; a window is
+ *      byte for byte that rectangle of the reduced call's output.  Only the codeblocks of the corner or of the window's
+ *      cone are decoded (picsong_window_codeblocks); picsong_range_flag covers those.  picsong_ctx_set_decode_drop
+ *      composes as on 8-bit contexts.  -cp 2 only, any -k, 5/3 and 9/7, the 32-bit coefficient form.
+ *      Forms, always the same bytes.  Grey reduced: the level-`reduce` launch stores the samples itself where the output
+ *      and frame_stride are 16-byte aligned and PICSONG_DEEP_NOFUSE is unset, else a clamp pass a frame.  RGB reduced:
+ *      the synthesis of the 3 n planes, then ONE inverse-transform launch over the n frames.  Grey window: level r of the
+ *      cone stores the samples.  RGB window: one epilogue launch (grid.z = frame) that reads the three components' T
+ *      samples, four pixels a thread, and stores dwords (dwordx2 where 8-byte aligned) where pointers, pitch and
+ *      frame_stride are 4-byte aligned, single samples otherwise and in a row's last partial group.
+ *      picsong_decode_rgb_images_window / picsong_decode_rgb_images_reduced accept PLANAR3_16, RGB48 and RGBA64 on a deep
+ *      RGB context: data, pitch, plane_stride and frame_stride 2-byte aligned, pitch >= w * bpp (2, 6, 8), alpha written
+ *      as mx, no byte outside [i * pitch, i * pitch + w * bpp) of rows 0..h-1 written; the epilogue writes the layout
+ *      itself.  _reduced yields the visible rw x rh samples through the window (0, 0, rw, rh) -- the only route on a deep
+ *      context.  The 8-bit layouts stay refused on a deep RGB context, the 16-bit ones on every other context.
+ *      picsong_reduced_dims and picsong_window_codeblocks answer on deep contexts (geometry only).
+ *      Refused (PICSONG_ERR_ARG, nothing launched, outputs untouched; the message names the call to use instead where the
+ *      context is of another kind): the four calls on an 8-bit context; the grey pair on a deep RGB context and the RGB
+ *      pair on a deep grey one; -cp 3; null pointers; n out of range; reduce outside 0..wl-1; a window not inside
+ *      paw x pah or with w or h < 1; odd pointers, pitches or strides; out_pitch < 2 w; with n > 1 a frame_stride below
+ *      a plane's span (2 paw pah; (h - 1) * out_pitch + 2 w) or, RGB, one that makes a frame's planes overlap the next
+ *      frame's; a stream stride below picsong_max_stream_shorts (grey: with n > 1); component tables of different
+ *      geometry.  The uint8_t proxy calls stay refused on deep contexts.
+ *      Not built: 8-bit output from deep streams, bgr / bgra 16-bit layouts, the int16 coefficient form,
+ *      a fused deep RGB tail, the CLI flags. ---- */
+int picsong_decode_frames16_reduced(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                    uint16_t *d_frames_out, size_t frame_stride, void *stream);
+int picsong_decode_frames16_window(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                   int x, int y, int w, int h, uint16_t *d_out, size_t out_pitch, size_t frame_stride, void *stream);
+int picsong_decode_rgb_frames16_reduced(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                        uint16_t *d_r, uint16_t *d_g, uint16_t *d_b, size_t frame_stride, void *stream);
+int picsong_decode_rgb_frames16_window(picsong_ctx *ctx, int n, const uint16_t *d_streams, size_t stream_stride, int reduce,
+                                       int x, int y, int w, int h, uint16_t *d_r, uint16_t *d_g, uint16_t *d_b,
+                                       size_t out_pitch, size_t frame_stride, void *stream);
 
 /* ---- intra-frame sharding (BASELINE config 5): codeblocks are independent
  *      (correctCBBorders zeroes outside neighbours, BPC/BPCEngine.cu:465-484), so a rank can code
